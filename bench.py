@@ -17,7 +17,12 @@ Workloads (config.name):
            one GPU (--mode fused: table-free): the largest case an index of 32 bits can address.
 
   python bench.py [--gpus N --steps K --warmup W] [--workload real|config5|big2048] [--grid 1024] [--mode lut|fused]
+                  [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+--dump-outputs DIR writes what the headline mode's last timed step handed its caller -- the ordered survivor list
+(idx, rgb, seen), all ranks' lists gathered when N > 1 -- as float .npy files, so that two builds run with the same
+arguments (hence the same seeded inputs) can be compared output for output.
 
 Prints ONE JSON line on rank 0.  No framework is imported: for N > 1 the RCCL unique id travels through a
 node-local file and barriers / the max-over-ranks timing go through RCCL.  A rank that cannot join the RCCL
@@ -42,6 +47,8 @@ FP64_PEAK_TFLOPS = 78.6        # MI355X_MICROARCH.md: FP64 vector (an FMA counts
 FLOPS_PER_PROJECTION = 52      # 52 f64 flop + 1 f64 divide per voxel-view
 LUT_BYTES_PER_VV = 4           # one packed int32 per voxel-view
 N_SLOTS = 8                    # resident frame sets (distinct byte masks); every timed step prepares its set again
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: all .npy files together stay below this (64 MB, also < 64 MiB)
+DUMP_SEED = 0                  # --dump-outputs: the row sample of a list that does not fit
 
 
 def parse():
@@ -77,6 +84,8 @@ def parse():
                          "step prepares its frame set on the device)")
     ap.add_argument("--only-headline", action="store_true", help="skip the other modes and the side measurements")
     ap.add_argument("--e2e-steps", type=int, default=5, help="steps of the PCIe-inclusive leg (0: skip it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the survivor list of the headline mode's last timed step as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -240,6 +249,35 @@ def run_mode(eng, grp, mode, steps, warmup, multi, host_transport=None, depth=3,
     return dt, last[0], last[1], tm
 
 
+def last_step_records(eng, multi, host_transport, exchange):
+    """The u64 survivor records of the step run_mode collected last, as its caller receives them: this rank's list at
+    N = 1, the gathered list of all ranks at N > 1 (the same branches as run_mode's finish())."""
+    if multi and host_transport is not None and exchange != "compact":
+        return np.array(host_transport.fetch(), dtype=np.uint64)
+    if multi:
+        return eng.fetch_gathered()
+    return eng.fetch_records()
+
+
+def dump_outputs(out_dir, rec):
+    """--dump-outputs: the records as survivor_idx (float64: every u32 index is exact), survivor_rgb [S,3] and
+    survivor_seen (float32), their positions in the list (survivor_rows, float64) and the list length (survivors).
+    A list whose rows do not fit DUMP_BYTES is written as a fixed sample of its rows (seed DUMP_SEED, ascending)."""
+    from voxcarve.engine import unpack_records
+    S = int(rec.size)
+    cap = (DUMP_BYTES - 5 * 4096) // (8 + 3 * 4 + 4 + 8)       # 32 B per row over the four per-row files, 4 KB per header
+    rows = np.arange(S) if S <= cap else np.sort(np.random.default_rng(DUMP_SEED).choice(S, cap, replace=False))
+    idx, rgb, seen = unpack_records(rec[rows])
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"survivors": np.array([S], np.float64), "survivor_rows": rows.astype(np.float64),
+              "survivor_idx": idx.astype(np.float64), "survivor_rgb": rgb.astype(np.float32),
+              "survivor_seen": seen.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(arrays), "survivors": S, "rows_written": int(rows.size),
+            "sampled": bool(rows.size < S)}
+
+
 def cpu_baseline(grid, cams, masks, frames, seconds, cc, device_digest=None):
     """The C/OpenMP oracle ("port") on this host's cores: the WHOLE grid of the same workload when that
     fits the time budget (a few seconds on a many-core host), else a centred z-slab sized to it.  When it is the
@@ -374,9 +412,13 @@ def main():
     order = [args.mode]
     if not args.only_headline and have_lut:
         order += [m for m in ("lut", "lut_stream", "fused", "fused_table_free") if m != args.mode]
+    dumped = None
     for mode in order:
         dt, n_local, n_total, tm = run_mode(eng, grp, mode, args.steps, args.warmup, fresh=not args.resident_prep, **common)
         results[mode] = {"seconds": dt, "survivors": int(n_total), "survivors_this_rank": int(n_local), "tm": tm}
+        if mode == args.mode and args.dump_outputs and grp.rank == 0:
+            # after the timed region, before another mode reuses the result buffers
+            dumped = dump_outputs(args.dump_outputs, last_step_records(eng, multi, host_transport, args.exchange))
     head = results[args.mode]
 
     # side measurements of the headline mode (short runs, never `value`)
@@ -631,6 +673,8 @@ def main():
         "other_modes": others,
         "phases_ms": phases,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if args.e2e_steps > 0 and grp.world == 1 and not args.force_comm:
         # PCIe-inclusive rate (never `value`): "writes a packed surviving-voxel list (+ sampled colour) back to host".
         # Per step: byte masks + colour frame up (page-locked staging, upload stream, beside the previous carve),
