@@ -195,9 +195,11 @@ int vc_fetch_viewmask(vc_ctx *ctx, uint16_t *viewmask);
  * slab-local voxel j (consumer shape of assignment.py:143-146). */
 int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits);
 
-/* ---- the step before the path, its data-parallel part ------------------------------------------------------
- * Front half of extract_foreground_mask, background_subtraction.py:153-168.  Host buffers in and out (findContours / fill
- * :171-193 sits between the pre- and the post-filter and stays with cv2 on the CPU).
+/* ---- the step before the path ---------------------------------------------------------------------------------
+ * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
+ * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own
+ * preparation (vc_set_mask_postfilter); vc_foreground_to_slot chains all of it into a carve slot.  Host buffers in and out
+ * except for vc_foreground_to_slot.
  * vc_bgr_to_hsv: replaces cv2.cvtColor(image, cv2.COLOR_BGR2HSV) (:155) on uint8 [H,W,3] -- OpenCV's 8-bit fixed-point
  * conversion (H in 0..179).  vc_mask_morphology: replaces cv2.morphologyEx(mask, MORPH_OPEN / MORPH_CLOSE,
  * getStructuringElement(MORPH_RECT, (ksize, ksize))) on uint8 [H,W], opening first when both flags are set: ksize 3 = the
@@ -224,6 +226,24 @@ int vc_mog_destroy(vc_ctx *ctx, uint32_t model);
  * (:161-168).  bgr uint8 [H,W,3] in, the model's mask uint8 [H,W] out. */
 int vc_foreground_front(vc_ctx *ctx, uint32_t model, const uint8_t *bgr, uint32_t H, uint32_t W, int to_hsv, double learning_rate,
                         int open, int close, uint8_t *mask);
+/* The contour stage, background_subtraction.py:171-193: cv2.findContours(mask, RETR_TREE, CHAIN_APPROX_SIMPLE), every contour
+ * with contourArea >= figure_threshold drawn and filled with 255, each of its children with contourArea(child, True) >=
+ * inner_threshold filled with 0 and its outline drawn again.  mask uint8 [H,W] (foreground where != 0) in, uint8 [H,W] {0, 255}
+ * out.  Computed from connected components, the component tree and per-cell areas instead of border following (csrc/vc_contour.h);
+ * held to a literal restatement of Suzuki-Abe border following, fillPoly and drawContours (tests/contour_literal.py), parity with
+ * cv2 itself unpinned. */
+int vc_fill_figures(vc_ctx *ctx, const uint8_t *mask, uint32_t H, uint32_t W, double figure_threshold, double inner_threshold,
+                    uint8_t *out);
+/* extract_foreground_mask of every camera into a carve slot without a host round trip, background_subtraction.py:129-208 as
+ * assignment.py:98-109 calls it: camera c's BGR image bgr[c] ([C][H][W][3], the vc_set_cameras size) goes through BGR -> HSV, the
+ * apply of background model models[c] with learning_rate (:155-158), the 3x3 opening / closing where open_pre[c] / close_pre[c]
+ * (:161-168; NULL = none) and the contour stage with figure_thr[c], inner_thr[c] (:171-193); the masks land in the slot's byte
+ * masks and the images in its frames (any camera can colour the records).  The 2x2 post-filter and the final threshold
+ * (:195-206) are the slot's preparation in front of the next carve (vc_set_mask_postfilter), as after vc_upload_masks.
+ * n_models >= C.  ASYNCHRONOUS like vc_upload_masks: one staged copy of the C images, then kernels on the upload stream. */
+int vc_foreground_to_slot(vc_ctx *ctx, uint32_t slot, const uint32_t *models, uint32_t n_models, const uint8_t *bgr, uint32_t H,
+                          uint32_t W, double learning_rate, const double *figure_thr, const double *inner_thr, const uint8_t *open_pre,
+                          const uint8_t *close_pre);
 
 /* ---- the step after the path: marching cubes over the dense ON/OFF volume -------------------------------
  * Replaces skimage.measure.marching_cubes(voxels_status, 0) of plot_marching_cubes, voxel_reconstruction.py:127-163, whose

@@ -75,6 +75,9 @@ SIGNATURES = {
     "vc_mog_destroy": (ctypes.c_int, [c_ctx, ctypes.c_uint32]),
     "vc_foreground_front": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_double,
                                            ctypes.c_int, ctypes.c_int, c_u8p]),
+    "vc_fill_figures": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, c_u8p]),
+    "vc_foreground_to_slot": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_double, c_f64p, c_f64p, c_u8p, c_u8p]),
     "vc_upload_frame": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, c_u8p]),
     "vc_build_lut": (ctypes.c_int, [c_ctx]),
     "vc_fetch_lut": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_i32p]),

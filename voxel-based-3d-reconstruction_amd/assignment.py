@@ -88,6 +88,62 @@ class ReferenceVideoSource:
         return frames, masks
 
 
+class DeviceVideoSource:
+    """Reference acquisition (assignment.py:68-82, 93-109) on the GPU: one BackgroundSubtractorMOG per camera trained with
+    the reference's parameters (history = number of background frames, 50 mixtures (the model keeps at most 8),
+    backgroundRatio 0.90, noiseSigma 0), then every frame set through extract_foreground_mask straight into the carve slot
+    (CarveEngine.foreground_to_slot with cam_bg_model_params; the 2x2 post-filter is the slot's, set by set_voxel_positions).
+    Nothing returns to the host before the survivors do, and cv2 is needed only to decode videos (from_videos).
+
+    frames_per_camera[c]: camera c's BGR video frames (uint8 [H, W, 3] each); background_frames_per_camera[c]: its
+    background video's frames."""
+
+    post_on_device = True
+
+    def __init__(self, frames_per_camera, background_frames_per_camera, num_cameras=4):
+        self.num_cameras = num_cameras
+        self._frames = [list(frames_per_camera[c]) for c in range(num_cameras)]
+        self._bg = [list(background_frames_per_camera[c]) for c in range(num_cameras)]
+        self._pos = 0
+        self._models = None
+        self._engine = None
+        H, W = np.asarray(self._frames[0][0]).shape[:2] if self._frames[0] else np.asarray(self._bg[0][0]).shape[:2]
+        self.image_size = (int(H), int(W))
+
+    @classmethod
+    def from_videos(cls, data_path="data", num_cameras=4):
+        """Decodes data_path/cam<c>/video.avi and background.avi with cv2 (which must be importable)."""
+        from .background_subtraction import _video_frames
+        fr, bg = [], []
+        for camera in range(num_cameras):
+            directory = os.path.join(data_path, "cam" + str(camera + 1))
+            f = _video_frames(os.path.join(directory, "video.avi"))
+            b = _video_frames(os.path.join(directory, "background.avi"))
+            if f is None or b is None:
+                raise VoxcarveError("DeviceVideoSource: cannot open the videos of %s" % directory)
+            fr.append(list(f))
+            bg.append(list(b))
+        return cls(fr, bg, num_cameras)
+
+    def _train(self, engine):
+        from .background_subtraction import train_MOG_background_model
+        self._models = [train_MOG_background_model(use_hsv=True, history=len(self._bg[c]), n_mixtures=50, bg_ratio=0.90,
+                                                   noise_sigma=0, engine=engine, frames=self._bg[c])
+                        for c in range(self.num_cameras)]
+        self._engine = engine
+
+    def fill_slot(self, engine, slot=0):
+        """The next frame set's masks and images into `slot` of `engine`; False at the end of the video."""
+        if self._pos >= min(len(f) for f in self._frames):
+            return False
+        if self._engine is not engine:
+            self._train(engine)
+        frames = [self._frames[c][self._pos] for c in range(self.num_cameras)]
+        self._pos += 1
+        engine.foreground_to_slot(self._models, frames, cam_bg_model_params[:self.num_cameras], slot=slot, learning_rate=0)
+        return True
+
+
 # module state, as the reference keeps it (assignment.py:22-40)
 initialized = False
 frame_count = 0
@@ -130,13 +186,16 @@ def set_voxel_positions(width, height, depth):
         _engine._sized = None
         initialized = True
 
-    item = _source.next()                                                       # assignment.py:94-96
-    if item is None:
-        return [], []
-    frames, masks = item
-    frame_count += 1
-
-    H, W = np.asarray(masks[0]).shape[:2]
+    device_source = hasattr(_source, "fill_slot")
+    if device_source:
+        H, W = _source.image_size
+    else:
+        item = _source.next()                                                   # assignment.py:94-96
+        if item is None:
+            return [], []
+        frames, masks = item
+        frame_count += 1
+        H, W = np.asarray(masks[0]).shape[:2]
     if _engine._sized != (H, W):
         _engine.set_cameras(_engine._cameras, H, W)
         if getattr(_source, "post_on_device", False):
@@ -147,8 +206,13 @@ def set_voxel_positions(width, height, depth):
             _engine.build_lut()
         _engine._sized = (H, W)
     cc = _settings["color_camera"]
-    _engine.upload_masks(masks, slot=0)
-    _engine.upload_frame(cc, frames[cc], slot=0)
+    if device_source:
+        if not _source.fill_slot(_engine, 0):                                   # masks and images made on the device
+            return [], []
+        frame_count += 1
+    else:
+        _engine.upload_masks(masks, slot=0)
+        _engine.upload_frame(cc, frames[cc], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"])
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())

@@ -9,13 +9,18 @@ SURVEY 8(f)-2, the step BEFORE the carve path.  Same names, parameters and defau
                                                object works as before, on the CPU)
   3x3 open / close before the contours   GPU   CarveEngine.mask_morphology(.., 3, ..)
   contours: fill the figures, re-open
-  their large holes (:171-193)           CPU   cv2.findContours / fillPoly / drawContours: sequential border following
+  their large holes (:171-193)           GPU   CarveEngine.fill_figures (contour_stage="device"): components, their containment
+                                               tree and per-cell areas in place of border following (csrc/vc_contour.h)
+                                         CPU   fill_figures, the default: cv2.findContours / fillPoly / drawContours
   2x2 open / close after them (:195-203) GPU   CarveEngine.mask_morphology(.., 2, ..)
   final threshold (:206)                 host  one comparison
 
-The CPU stage needs cv2 (as the reference does), and so does decoding the training video; without it those calls fail by name --
-there is no substitute for them in this package.  Parity of the GPU stages with cv2 is unpinned (see oracle/foreground_np.py,
-oracle/mog_np.py)."""
+With a device model and contour_stage="device" no stage needs cv2 (each GPU call here copies its image down and back);
+CarveEngine.foreground_to_slot runs the whole function for every camera into a carve slot, with nothing coming back
+(assignment.DeviceVideoSource).
+The cv2 stage needs cv2 (as the reference does), and so does decoding the training video; without it those calls fail by name.
+Parity of the GPU stages with cv2 is unpinned: the contour stage is held to a literal restatement of the published border
+following, fillPoly and drawContours (tests/contour_literal.py), the others to oracle/foreground_np.py and oracle/mog_np.py."""
 import numpy as np
 
 from ._lib import VoxcarveError
@@ -125,13 +130,21 @@ def fill_figures(mask, figure_threshold, figure_inner_threshold):
     return out
 
 
+def fill_figures_device(mask, figure_threshold, figure_inner_threshold, engine=None):
+    """fill_figures on the GPU (CarveEngine.fill_figures): the same stage without cv2."""
+    eng = engine if engine is not None else _default_engine()
+    return eng.fill_figures(mask, figure_threshold, figure_inner_threshold)
+
+
 def extract_foreground_mask(image, bg_model, learning_rate=0, figure_threshold=5000, figure_inner_threshold=115,
                             apply_opening_pre=False, apply_closing_pre=False, apply_opening_post=False,
                             apply_closing_post=False, engine=None, contour_stage=None):
     """Foreground mask (uint8 {0, 255} [H, W]) of a BGR image; reference background_subtraction.py:129-208, same parameters.
-    ``engine``: the CarveEngine whose device does the work (default: one on device 0); ``contour_stage``: what stands in for
-    ``fill_figures`` (tests; default: the cv2 one)."""
+    ``engine``: the CarveEngine whose device does the work (default: one on device 0); ``contour_stage``: None = ``fill_figures``
+    (cv2), "device" = ``fill_figures_device``, or a callable standing in for it (tests)."""
     eng = engine if engine is not None else _default_engine()
+    if contour_stage == "device":
+        contour_stage = lambda m, ft, fit: fill_figures_device(m, ft, fit, eng)
     if isinstance(bg_model, BackgroundSubtractorMOG) and bg_model._eng is eng:
         # the model lives on this device: colour conversion, apply and pre-filter without leaving it
         model_mask = eng.foreground_front(bg_model._model, image, learning_rate, apply_opening_pre, apply_closing_pre)

@@ -3,7 +3,7 @@
 //   k_bgr2hsv        cv2.cvtColor(image, cv2.COLOR_BGR2HSV) on uint8 (:155) -- OpenCV's 8-bit fixed-point path (RGB2HSV_b, hrange 180)
 //   k_morph3x3       one pass of cv2.erode / cv2.dilate with the 3x3 MORPH_RECT element of the pre open / close (:161-168)
 //   k_mog_apply      bg_model.apply of the MOG model assignment.py trains (:158; training background_subtraction.py:75-92)
-// findContours / fill (:171-193, sequential border following) stays with cv2 on the CPU.
+// findContours / fill (:171-193) is vc_contour.h.
 // PARITY UNPINNED (no cv2 here, no intermediate image in the reference): checked against oracle/foreground_np.py.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -33,6 +33,7 @@
 #include "vc_kernels.h"
 #include "vc_mc.h"
 #include "vc_fg.h"
+#include "vc_contour.h"
 
 #pragma clang fp contract(off)
 
@@ -97,6 +98,9 @@ struct Slot {
     size_t h_bytes_cap = 0;
     DevBuf<uint8_t> fbytes[VC_MAX_CAMERAS];   // [H*W*3] BGR image of a camera as uploaded
     uint8_t *h_fbytes[VC_MAX_CAMERAS] = {nullptr};
+    DevBuf<uint8_t> bgr_all;    // [C][H*W*3] the images of vc_foreground_to_slot as copied (one staged copy for all cameras)
+    uint8_t *h_bgr_all = nullptr;
+    size_t h_bgr_all_cap = 0;
     DevBuf<uint32_t> bits;      // [C][mwords]
     DevBuf<uint32_t> frames;    // [C][H*W] one dword per pixel: R | G << 8 | B << 16 | seen << 24 (a record's upper half)
     std::vector<uint8_t> have_frame, frame_dirty;
@@ -329,6 +333,7 @@ struct vc_ctx {
     int lut_color_cam = -1;
 
     DevBuf<uint8_t> d_fg;            // vc_bgr_to_hsv / vc_mask_morphology: input | output | scratch images
+    DevBuf<uint32_t> d_cc;           // vc_fill_figures / vc_foreground_to_slot: lab | own | tot | par planes per camera (vc_contour.h)
     DevBuf<int32_t> d_hsvdiv;        // OpenCV's two division tables of the 8-bit HSV conversion (sdiv | hdiv)
     struct MogModel {                // vc_mog_*: one background model (the reference keeps one per camera, assignment.py:79)
         bool used = false;
@@ -687,6 +692,8 @@ void release_slot(Slot &s)
         if (s.h_fbytes[c]) { (void)hipHostFree(s.h_fbytes[c]); s.h_fbytes[c] = nullptr; }
     }
     if (s.h_bytes) { (void)hipHostFree(s.h_bytes); s.h_bytes = nullptr; s.h_bytes_cap = 0; }
+    release(s.bgr_all);
+    if (s.h_bgr_all) { (void)hipHostFree(s.h_bgr_all); s.h_bgr_all = nullptr; s.h_bgr_all_cap = 0; }
     s.have_masks = s.bits_valid = s.grids_valid = false;
     s.have_frame.clear(); s.frame_dirty.clear();
 }
@@ -1153,6 +1160,7 @@ int vc_destroy(vc_ctx *ctx)
     }
     release(ctx->d_stats); release(ctx->d_fg); release(ctx->d_hsvdiv);
     for (auto &m : ctx->mog) release(m.state);
+    release(ctx->d_cc);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xcnt); release(ctx->d_xoff); release(ctx->d_xbsum);
     release(ctx->d_xboff); release(ctx->d_lut_color);
@@ -2269,6 +2277,117 @@ int vc_foreground_front(vc_ctx *ctx, uint32_t model, const uint8_t *bgr, uint32_
     VC_HIP(ctx, hipGetLastError());
     VC_HIP(ctx, hipMemcpyAsync(mask, a, npix, hipMemcpyDeviceToHost, st));
     VC_HIP(ctx, hipStreamSynchronize(st));
+    return VC_OK;
+}
+
+// The contour stage (background_subtraction.py:171-193) of `cams` masks of H x W at d_mask ([cams][H W]) into d_out, on the
+// upload stream; thresholds per camera.  Eight launches, the cameras in grid z, no host synchronisation (vc_contour.h).
+static int fill_enqueue(vc_ctx *ctx, const uint8_t *d_mask, uint8_t *d_out, uint32_t H, uint32_t W, uint32_t cams, const double *T,
+                        const double *t)
+{
+    if (cams == 0 || cams > kFillMaxCameras) return fail(ctx, VC_ERR_ARG, "contour stage of %u masks: 1..%u at once", cams, kFillMaxCameras);
+    const uint64_t Np = (uint64_t)(H + 2) * (W + 2);
+    if (Np >= 0x7fffffffull) return fail(ctx, VC_ERR_ARG, "image size %u x %u too large for the contour stage", H, W);
+    VC_TRY(ensure(ctx, ctx->d_cc, (size_t)Np * 4 * cams));
+    FillParams p;
+    memset(&p, 0, sizeof p);
+    p.mask = d_mask; p.out = d_out;
+    p.lab = ctx->d_cc.ptr;
+    p.own = p.lab + (size_t)Np * cams;
+    p.tot = p.own + (size_t)Np * cams;
+    p.par = p.tot + (size_t)Np * cams;
+    p.H = H; p.W = W; p.Wp = W + 2; p.Np = (uint32_t)Np;
+    p.max_depth = (H < W ? H : W) + 4;
+    for (uint32_t c = 0; c < cams; ++c) { p.T[c] = T[c]; p.t[c] = t[c]; }
+    hipStream_t st = ctx->stream_up;
+    const dim3 blk(kFillBlock);
+    const dim3 gp((uint32_t)((Np + kFillBlock - 1) / kFillBlock), 1, cams);
+    const dim3 gc((uint32_t)(((uint64_t)(H + 1) * (W + 1) + kFillBlock - 1) / kFillBlock), 1, cams);
+    const dim3 gi((uint32_t)(((uint64_t)H * W + kFillBlock - 1) / kFillBlock), 1, cams);
+    const dim3 gt((W + 2 + kTile - 1) / kTile, (H + 2 + kTile - 1) / kTile, cams);
+    hipLaunchKernelGGL(k_fill_init, gp, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_local, gt, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_merge, gt, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_compress, gp, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_area, gc, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_subtree, gp, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_resolve, gp, blk, 0, st, p);
+    hipLaunchKernelGGL(k_fill_output, gi, blk, 0, st, p);
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
+int vc_fill_figures(vc_ctx *ctx, const uint8_t *mask, uint32_t H, uint32_t W, double figure_threshold, double inner_threshold, uint8_t *out)
+{
+    if (!ctx || !mask || !out) return VC_ERR_ARG;
+    if (H == 0 || W == 0 || (uint64_t)H * W > 0x0fffffffull) return fail(ctx, VC_ERR_ARG, "image size %u x %u", H, W);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)H * W;
+    hipStream_t st = ctx->stream_up;
+    VC_TRY(ensure(ctx, ctx->d_fg, npix * 2 + 64));
+    uint8_t *d_in = ctx->d_fg.ptr, *d_out = d_in + npix;
+    VC_HIP(ctx, hipMemcpyAsync(d_in, mask, npix, hipMemcpyHostToDevice, st));
+    VC_TRY(fill_enqueue(ctx, d_in, d_out, H, W, 1, &figure_threshold, &inner_threshold));
+    VC_HIP(ctx, hipMemcpyAsync(out, d_out, npix, hipMemcpyDeviceToHost, st));
+    VC_HIP(ctx, hipStreamSynchronize(st));
+    return VC_OK;
+}
+
+int vc_foreground_to_slot(vc_ctx *ctx, uint32_t slot, const uint32_t *models, uint32_t n_models, const uint8_t *bgr, uint32_t H, uint32_t W,
+                          double learning_rate, const double *figure_thr, const double *inner_thr, const uint8_t *open_pre,
+                          const uint8_t *close_pre)
+{
+    if (!ctx || !models || !bgr || !figure_thr || !inner_thr) return VC_ERR_ARG;
+    if (!ctx->have_cams) return fail(ctx, VC_ERR_ARG, "vc_set_cameras must precede vc_foreground_to_slot");
+    const uint32_t C = ctx->C;
+    if (n_models < C) return fail(ctx, VC_ERR_ARG, "vc_foreground_to_slot: %u background models for %u cameras", n_models, C);
+    for (uint32_t c = 0; c < C; ++c)
+        if (models[c] >= VC_MAX_MOG_MODELS || !ctx->mog[models[c]].used)
+            return fail(ctx, VC_ERR_ARG, "vc_foreground_to_slot: camera %u: no background model %u", c, models[c]);
+    if (H != ctx->H || W != ctx->W)
+        return fail(ctx, VC_ERR_ARG, "vc_foreground_to_slot: images of %u x %u, the cameras were set for %u x %u", H, W, ctx->H, ctx->W);
+    if (slot >= 64) return fail(ctx, VC_ERR_ARG, "slot %u out of range (max 64 resident frame sets)", slot);
+    Slot *s = nullptr;
+    VC_TRY(slot_at(ctx, slot, &s));
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t HW = (size_t)H * W;
+    hipStream_t st = ctx->stream_up;
+    VC_TRY(hsv_tables(ctx));
+    VC_TRY(ensure(ctx, s->bytes, HW * C + 64));
+    VC_TRY(ensure(ctx, s->frames, HW * C));
+    for (uint32_t c = 0; c < C; ++c) VC_TRY(ensure(ctx, s->fbytes[c], HW * 3 + 64));
+    VC_TRY(ensure(ctx, s->bgr_all, HW * 3 * C));
+    // scratch: HSV image | model mask | morphology buffer | the C pre-filtered masks
+    VC_TRY(ensure(ctx, ctx->d_fg, HW * (5 + C) + 64));
+    uint8_t *d_hsv = ctx->d_fg.ptr, *ma = d_hsv + HW * 3, *mb = ma + HW, *pre = mb + HW;
+    VC_TRY(stage_upload(ctx, *s, &s->h_bgr_all, &s->h_bgr_all_cap, s->bgr_all.ptr, bgr, HW * 3 * C, false));
+    const dim3 g((uint32_t)((HW + 255) / 256)), blk(256);
+    for (uint32_t c = 0; c < C; ++c) {
+        const uint8_t *img = s->bgr_all.ptr + HW * 3 * c;
+        VC_HIP(ctx, hipMemcpyAsync(s->fbytes[c].ptr, img, HW * 3, hipMemcpyDeviceToDevice, st));   // the records' colours
+        hipLaunchKernelGGL(k_bgr2hsv, g, blk, 0, st, img, d_hsv, (uint32_t)HW, (const int32_t *)ctx->d_hsvdiv.ptr,
+                           (const int32_t *)(ctx->d_hsvdiv.ptr + 256));
+        uint8_t *a = ma, *b = mb;
+        VC_TRY(mog_enqueue(ctx, models[c], d_hsv, H, W, learning_rate, a));
+        const bool op = open_pre && open_pre[c], cl = close_pre && close_pre[c];
+        const int passes = (op ? 2 : 0) + (cl ? 2 : 0);
+        int k = 0;
+        auto pass = [&](bool dilate) {                           // a -> b (the last pass -> the camera's pre-filtered mask)
+            uint8_t *dst = ++k == passes ? pre + HW * c : b;
+            if (dilate) hipLaunchKernelGGL(k_morph3x3<true>, g, blk, 0, st, (const uint8_t *)a, dst, H, W);
+            else hipLaunchKernelGGL(k_morph3x3<false>, g, blk, 0, st, (const uint8_t *)a, dst, H, W);
+            b = a; a = dst;
+        };
+        if (op) { pass(false); pass(true); }
+        if (cl) { pass(true); pass(false); }
+        if (passes == 0) VC_HIP(ctx, hipMemcpyAsync(pre + HW * c, a, HW, hipMemcpyDeviceToDevice, st));
+        VC_HIP(ctx, hipGetLastError());
+    }
+    VC_TRY(fill_enqueue(ctx, pre, s->bytes.ptr, H, W, C, figure_thr, inner_thr));
+    s->have_masks = true;
+    s->bits_valid = false;                                       // the next carve derives bits, images, grids from the new bytes
+    s->grids_valid = false;
+    for (uint32_t c = 0; c < C; ++c) { s->have_frame[c] = 1; s->frame_dirty[c] = 1; }
     return VC_OK;
 }
 

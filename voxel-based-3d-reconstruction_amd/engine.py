@@ -186,6 +186,40 @@ class CarveEngine:
                     "vc_foreground_front")
         return out
 
+    def fill_figures(self, mask, figure_threshold, figure_inner_threshold):
+        """The contour stage of extract_foreground_mask (background_subtraction.py:171-193) on the device: contours of area
+        >= figure_threshold filled, their children of oriented area >= figure_inner_threshold cleared with the outline kept.
+        uint8 [H, W] (foreground where != 0) in, uint8 [H, W] {0, 255} out."""
+        a = np.ascontiguousarray(mask, dtype=np.uint8)
+        if a.ndim != 2:
+            raise ValueError("mask shape %s, expected [H, W]" % (a.shape,))
+        out = np.empty(a.shape, dtype=np.uint8)
+        self._check(self._L.vc_fill_figures(self._ctx, _ptr(a, ctypes.c_uint8), a.shape[0], a.shape[1], float(figure_threshold),
+                                            float(figure_inner_threshold), _ptr(out, ctypes.c_uint8)), "vc_fill_figures")
+        return out
+
+    def foreground_to_slot(self, models, frames, params, slot=0, learning_rate=0):
+        """extract_foreground_mask of every camera's BGR frame straight into carve slot `slot` (background_subtraction.py:129-208
+        as assignment.py:98-109 calls it), the frames becoming the slot's images.  models: one background model per camera
+        (BackgroundSubtractorMOG of this engine, or a model id); params: per camera [figure_threshold, figure_inner_threshold,
+        opening_pre, closing_pre, ...] (the rows of assignment.cam_bg_model_params).  The 2x2 post-filter is set_mask_postfilter's.
+        Asynchronous: the next carve on the slot waits for it on the device."""
+        ids = np.array([int(getattr(m, "_model", m)) for m in models], dtype=np.uint32)
+        f = np.ascontiguousarray(np.stack([np.asarray(x) for x in frames]), dtype=np.uint8)
+        if f.ndim != 4 or f.shape[3] != 3:
+            raise ValueError("frames shape %s, expected [C, H, W, 3]" % (f.shape,))
+        n = f.shape[0]
+        if n != self.n_cameras or len(params) < n:
+            raise ValueError("%d frames and %d parameter rows for %d cameras" % (n, len(params), self.n_cameras))
+        ft = np.array([float(params[c][0]) for c in range(n)], dtype=np.float64)
+        it = np.array([float(params[c][1]) for c in range(n)], dtype=np.float64)
+        op = np.array([bool(params[c][2]) for c in range(n)], dtype=np.uint8)
+        cl = np.array([bool(params[c][3]) for c in range(n)], dtype=np.uint8)
+        self._check(self._L.vc_foreground_to_slot(self._ctx, slot, _ptr(ids, ctypes.c_uint32), len(ids), _ptr(f, ctypes.c_uint8),
+                                                  f.shape[1], f.shape[2], float(learning_rate), _ptr(ft, ctypes.c_double),
+                                                  _ptr(it, ctypes.c_double), _ptr(op, ctypes.c_uint8), _ptr(cl, ctypes.c_uint8)),
+                    "vc_foreground_to_slot")
+
     def mog_destroy(self, model):
         self._check(self._L.vc_mog_destroy(self._ctx, int(model)), "vc_mog_destroy")
 
