@@ -221,9 +221,32 @@ int vc_mog_create(vc_ctx *ctx, int history, int nmixtures, double background_rat
 int vc_mog_apply(vc_ctx *ctx, uint32_t model, const uint8_t *image, uint32_t H, uint32_t W, double learning_rate, uint8_t *fgmask);
 int vc_mog_state(vc_ctx *ctx, uint32_t model, float *state, uint64_t capacity, uint32_t *H, uint32_t *W, uint32_t *nmixtures, uint32_t *nframes);
 int vc_mog_destroy(vc_ctx *ctx, uint32_t model);
+/* The MOG2 model: cv2.createBackgroundSubtractorMOG2(history, varThreshold, detectShadows) (background_subtraction.py:90-127, the
+ * comparison script :398-401 with history = frame count, varThreshold 650, detectShadows false) and its apply(image, None,
+ * learningRate) on uint8 [H,W,3] -> uint8 [H,W] {0, shadow_value, 255}.  Non-positive history / var_threshold select OpenCV's
+ * 500 / 16; the other arguments are the model's fixed defaults in OpenCV (5 mixtures, backgroundRatio 0.9, varThresholdGen 9,
+ * varInit 15, varMin 4, varMax 75, complexityReductionThreshold 0.05, shadowValue 127, shadowThreshold 0.5), stored as OpenCV
+ * stores them (float; varThreshold as double((float)v)).  nmixtures must lie in 1..8 (a limit of this build, VC_ERR_ARG beyond)
+ * and shadow_value in 0..255.  The model starts over on its first frame, on a learning rate >= 1 and when the image size changes;
+ * a negative learning rate means 1 / min(2 frames seen, history).  Unlike MOG, learning rate 0 still writes the model (weights
+ * renormalised).  Handles are VC_MOG2_MODEL_TAG | index (at most VC_MAX_MOG_MODELS of them); vc_foreground_front and
+ * vc_foreground_to_slot take either kind, the vc_mog_* calls only MOG handles and the vc_mog2_* calls only MOG2 handles.
+ * vc_mog2_state copies the model out: state [5 nmixtures][H W] float planes (plane 5 k + f = field f of component k; f: 0
+ * weight, 1 variance, 2..4 mean), nmodes [H W] u8 (components in use per pixel; those beyond keep their last values); either
+ * buffer may be null, both null asks for the sizes only.  Restated from the published CPU path of OpenCV's bgfg_gaussmix2.cpp;
+ * parity with cv2 unpinned (tests/mog2_np.py). */
+#define VC_MOG2_MODEL_TAG 0x10000u
+int vc_mog2_create(vc_ctx *ctx, int history, double var_threshold, int detect_shadows, int nmixtures, double background_ratio,
+                   double var_threshold_gen, double var_init, double var_min, double var_max, double complexity_reduction_threshold,
+                   int shadow_value, double shadow_threshold, uint32_t *model);
+int vc_mog2_apply(vc_ctx *ctx, uint32_t model, const uint8_t *image, uint32_t H, uint32_t W, double learning_rate, uint8_t *fgmask);
+int vc_mog2_state(vc_ctx *ctx, uint32_t model, float *state, uint64_t capacity, uint8_t *nmodes, uint64_t nmodes_capacity, uint32_t *H,
+                  uint32_t *W, uint32_t *nmixtures, uint32_t *nframes);
+int vc_mog2_destroy(vc_ctx *ctx, uint32_t model);
 /* Everything of extract_foreground_mask in front of the contour stage in one call, one copy each way: BGR -> HSV where to_hsv
  * (:155; the reference always does), the model's apply with `learning_rate` (:158), the 3x3 opening / closing where asked
- * (:161-168).  bgr uint8 [H,W,3] in, the model's mask uint8 [H,W] out. */
+ * (:161-168).  bgr uint8 [H,W,3] in, the model's mask uint8 [H,W] out (a MOG2 model's shadows stay shadow_value: the
+ * 3x3 filter keeps grey levels, and every later stage takes != 0 as foreground, as cv2.findContours does). */
 int vc_foreground_front(vc_ctx *ctx, uint32_t model, const uint8_t *bgr, uint32_t H, uint32_t W, int to_hsv, double learning_rate,
                         int open, int close, uint8_t *mask);
 /* The contour stage, background_subtraction.py:171-193: cv2.findContours(mask, RETR_TREE, CHAIN_APPROX_SIMPLE), every contour

@@ -16,6 +16,8 @@ VC_FLAG_VIEWMASK = 1
 VC_FLAG_NO_RECORDS = 2
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
+VC_MAX_MOG_MODELS = 64
+VC_MOG2_MODEL_TAG = 0x10000
 
 STATUS_NAMES = {0: "VC_OK", -1: "VC_ERR_ARG", -2: "VC_ERR_HIP", -3: "VC_ERR_RCCL",
                 -4: "VC_ERR_OOM", -5: "VC_ERR_NODEV"}
@@ -73,6 +75,14 @@ SIGNATURES = {
     "vc_mog_state": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32),
                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "vc_mog_destroy": (ctypes.c_int, [c_ctx, ctypes.c_uint32]),
+    "vc_mog2_create": (ctypes.c_int, [c_ctx, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
+                                      ctypes.POINTER(ctypes.c_uint32)]),
+    "vc_mog2_apply": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, c_u8p]),
+    "vc_mog2_state": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_uint64, c_u8p, ctypes.c_uint64,
+                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                     ctypes.POINTER(ctypes.c_uint32)]),
+    "vc_mog2_destroy": (ctypes.c_int, [c_ctx, ctypes.c_uint32]),
     "vc_foreground_front": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_double,
                                            ctypes.c_int, ctypes.c_int, c_u8p]),
     "vc_fill_figures": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, c_u8p]),

@@ -89,18 +89,23 @@ class ReferenceVideoSource:
 
 
 class DeviceVideoSource:
-    """Reference acquisition (assignment.py:68-82, 93-109) on the GPU: one BackgroundSubtractorMOG per camera trained with
-    the reference's parameters (history = number of background frames, 50 mixtures (the model keeps at most 8),
-    backgroundRatio 0.90, noiseSigma 0), then every frame set through extract_foreground_mask straight into the carve slot
+    """Reference acquisition (assignment.py:68-82, 93-109) on the GPU: one background model per camera trained with the
+    reference's parameters, then every frame set through extract_foreground_mask straight into the carve slot
     (CarveEngine.foreground_to_slot with cam_bg_model_params; the 2x2 post-filter is the slot's, set by set_voxel_positions).
     Nothing returns to the host before the survivors do, and cv2 is needed only to decode videos (from_videos).
 
     frames_per_camera[c]: camera c's BGR video frames (uint8 [H, W, 3] each); background_frames_per_camera[c]: its
-    background video's frames."""
+    background video's frames.  model: "MOG" (the default, assignment.py:79): BackgroundSubtractorMOG with history = number
+    of background frames, 50 mixtures (the model keeps at most 8), backgroundRatio 0.90, noiseSigma 0; "MOG2": a
+    BackgroundSubtractorMOG2 as the reference's comparison script trains it (background_subtraction.py:400-401): history =
+    number of background frames, varThreshold 650, no shadow detection."""
 
     post_on_device = True
 
-    def __init__(self, frames_per_camera, background_frames_per_camera, num_cameras=4):
+    def __init__(self, frames_per_camera, background_frames_per_camera, num_cameras=4, model="MOG"):
+        if model not in ("MOG", "MOG2"):
+            raise ValueError("DeviceVideoSource: model %r, expected \"MOG\" or \"MOG2\"" % (model,))
+        self.model = model
         self.num_cameras = num_cameras
         self._frames = [list(frames_per_camera[c]) for c in range(num_cameras)]
         self._bg = [list(background_frames_per_camera[c]) for c in range(num_cameras)]
@@ -111,7 +116,7 @@ class DeviceVideoSource:
         self.image_size = (int(H), int(W))
 
     @classmethod
-    def from_videos(cls, data_path="data", num_cameras=4):
+    def from_videos(cls, data_path="data", num_cameras=4, model="MOG"):
         """Decodes data_path/cam<c>/video.avi and background.avi with cv2 (which must be importable)."""
         from .background_subtraction import _video_frames
         fr, bg = [], []
@@ -123,13 +128,18 @@ class DeviceVideoSource:
                 raise VoxcarveError("DeviceVideoSource: cannot open the videos of %s" % directory)
             fr.append(list(f))
             bg.append(list(b))
-        return cls(fr, bg, num_cameras)
+        return cls(fr, bg, num_cameras, model)
 
     def _train(self, engine):
-        from .background_subtraction import train_MOG_background_model
-        self._models = [train_MOG_background_model(use_hsv=True, history=len(self._bg[c]), n_mixtures=50, bg_ratio=0.90,
-                                                   noise_sigma=0, engine=engine, frames=self._bg[c])
-                        for c in range(self.num_cameras)]
+        from .background_subtraction import train_MOG_background_model, train_MOG2_background_model
+        if self.model == "MOG2":
+            self._models = [train_MOG2_background_model(use_hsv=True, history=len(self._bg[c]), var_threshold=650, detect_shadows=False,
+                                                        engine=engine, frames=self._bg[c])
+                            for c in range(self.num_cameras)]
+        else:
+            self._models = [train_MOG_background_model(use_hsv=True, history=len(self._bg[c]), n_mixtures=50, bg_ratio=0.90,
+                                                       noise_sigma=0, engine=engine, frames=self._bg[c])
+                            for c in range(self.num_cameras)]
         self._engine = engine
 
     def fill_slot(self, engine, slot=0):

@@ -1,12 +1,14 @@
-"""The reference's ``extract_foreground_mask`` (background_subtraction.py:129-208) and its MOG background model
-(``train_MOG_background_model``, :49-92) with their data-parallel stages on the GPU.
+"""The reference's ``extract_foreground_mask`` (background_subtraction.py:129-208) and its MOG and MOG2 background models
+(``train_MOG_background_model``, :49-92; ``train_MOG2_background_model``, :90-127) with their data-parallel stages on the GPU.
 
 SURVEY 8(f)-2, the step BEFORE the carve path.  Same names, parameters and defaults as the reference's functions.  What runs where:
 
   BGR -> HSV (:155)                      GPU   CarveEngine.bgr_to_hsv          (OpenCV's 8-bit fixed-point conversion)
   bg_model.apply (:158)                  GPU   BackgroundSubtractorMOG.apply   (the model assignment.py:79 trains; per pixel mixture
-                                               of Gaussians, state in HBM) -- or whatever model the caller hands in (a cv2 MOG2 / KNN
-                                               object works as before, on the CPU)
+                                               of Gaussians, state in HBM)
+                                         GPU   BackgroundSubtractorMOG2.apply  (Zivkovic's adaptive mixture, cv2's MOG2; shadows
+                                               marked shadowValue, 127 by default, state in HBM)
+                                         CPU   whatever other model the caller hands in (a cv2 KNN object works as before)
   3x3 open / close before the contours   GPU   CarveEngine.mask_morphology(.., 3, ..)
   contours: fill the figures, re-open
   their large holes (:171-193)           GPU   CarveEngine.fill_figures (contour_stage="device"): components, their containment
@@ -20,7 +22,8 @@ CarveEngine.foreground_to_slot runs the whole function for every camera into a c
 (assignment.DeviceVideoSource).
 The cv2 stage needs cv2 (as the reference does), and so does decoding the training video; without it those calls fail by name.
 Parity of the GPU stages with cv2 is unpinned: the contour stage is held to a literal restatement of the published border
-following, fillPoly and drawContours (tests/contour_literal.py), the others to oracle/foreground_np.py and oracle/mog_np.py."""
+following, fillPoly and drawContours (tests/contour_literal.py), the others to oracle/foreground_np.py, oracle/mog_np.py and
+tests/mog2_np.py."""
 import numpy as np
 
 from ._lib import VoxcarveError
@@ -67,12 +70,69 @@ class BackgroundSubtractorMOG:
             pass
 
 
-def _video_frames(path):
+class BackgroundSubtractorMOG2:
+    """cv2.createBackgroundSubtractorMOG2(history, varThreshold, detectShadows) with the model on the device
+    (background_subtraction.py:110-111).  The keyword-only arguments are the values cv2 fixes at construction (settable there
+    through setters before the first frame); nmixtures may be 1..8 here.  ``apply(image, fgmask=None, learningRate=-1)`` as
+    cv2's: uint8 [H,W,3] in, uint8 [H,W] {0, shadowValue, 255} out; -1 = 1 / min(2 frames seen, history).  Unlike MOG, learning
+    rate 0 still writes the model (its weights are renormalised)."""
+
+    def __init__(self, history=500, varThreshold=16, detectShadows=True, *, nmixtures=5, backgroundRatio=0.9, varThresholdGen=9,
+                 varInit=15, varMin=4, varMax=75, complexityReductionThreshold=0.05, shadowValue=127, shadowThreshold=0.5,
+                 engine=None):
+        self._eng = engine if engine is not None else _default_engine()
+        self._model = None
+        self._model = self._eng.mog2_create(history, varThreshold, detectShadows, nmixtures, backgroundRatio, varThresholdGen, varInit,
+                                            varMin, varMax, complexityReductionThreshold, shadowValue, shadowThreshold)
+        f = lambda v: float(np.float32(v))                     # cv2 keeps these as float and hands them back as double
+        self._params = dict(history=int(history) if history > 0 else 500, varThreshold=f(varThreshold if varThreshold > 0 else 16),
+                            detectShadows=bool(detectShadows), nmixtures=int(nmixtures), backgroundRatio=f(backgroundRatio),
+                            varThresholdGen=f(varThresholdGen), varInit=f(varInit), varMin=f(varMin), varMax=f(varMax),
+                            complexityReductionThreshold=f(complexityReductionThreshold), shadowValue=int(shadowValue),
+                            shadowThreshold=f(shadowThreshold))
+
+    def apply(self, image, fgmask=None, learningRate=-1):
+        out = self._eng.mog2_apply(self._model, image, learningRate)
+        if fgmask is not None:
+            fgmask[...] = out
+            return fgmask
+        return out
+
+    def getHistory(self): return self._params["history"]
+    def getNMixtures(self): return self._params["nmixtures"]
+    def getVarThreshold(self): return self._params["varThreshold"]
+    def getDetectShadows(self): return self._params["detectShadows"]
+    def getShadowValue(self): return self._params["shadowValue"]
+    def getShadowThreshold(self): return self._params["shadowThreshold"]
+    def getBackgroundRatio(self): return self._params["backgroundRatio"]
+    def getVarThresholdGen(self): return self._params["varThresholdGen"]
+    def getVarInit(self): return self._params["varInit"]
+    def getVarMin(self): return self._params["varMin"]
+    def getVarMax(self): return self._params["varMax"]
+    def getComplexityReductionThreshold(self): return self._params["complexityReductionThreshold"]
+
+    def state(self):
+        """(state float32 [5 nmixtures, H W], nmodes uint8 [H W], (H, W), frames seen): CarveEngine.mog2_state."""
+        return self._eng.mog2_state(self._model)
+
+    def close(self):
+        if self._model is not None:
+            self._eng.mog2_destroy(self._model)
+            self._model = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _video_frames(path, who="train_MOG_background_model"):
     try:
         import cv2
     except ImportError as exc:
-        raise VoxcarveError("train_MOG_background_model: decoding %s runs on cv2.VideoCapture, which is not importable here (%s); "
-                            "pass the frames themselves (frames=...)" % (path, exc))
+        raise VoxcarveError("%s: decoding %s runs on cv2.VideoCapture, which is not importable here (%s); "
+                            "pass the frames themselves (frames=...)" % (who, path, exc))
     cap = cv2.VideoCapture(path)
     if not cap.isOpened():
         return None
@@ -97,6 +157,24 @@ def train_MOG_background_model(bg_video_input_path="data/cam", bg_video_input_fi
             return None
     eng = engine if engine is not None else _default_engine()
     model = BackgroundSubtractorMOG(history=history, nmixtures=n_mixtures, backgroundRatio=bg_ratio, noiseSigma=noise_sigma, engine=eng)
+    for frame in frames:
+        if use_hsv:
+            frame = eng.bgr_to_hsv(frame)
+        model.apply(frame, None, learning_rate)
+    return model
+
+
+def train_MOG2_background_model(bg_video_input_path="data/cam", bg_video_input_filename="background.avi", use_hsv=True,
+                                history=500, var_threshold=16, detect_shadows=True, learning_rate=-1, engine=None, frames=None):
+    """A MOG2 model trained on a background video; reference background_subtraction.py:90-127, same parameters (None if the video
+    cannot be opened, as there).  ``frames``: an iterable of BGR frames instead of the video file (no cv2 needed then)."""
+    import os
+    if frames is None:
+        frames = _video_frames(os.path.join(bg_video_input_path, bg_video_input_filename), "train_MOG2_background_model")
+        if frames is None:
+            return None
+    eng = engine if engine is not None else _default_engine()
+    model = BackgroundSubtractorMOG2(history=history, varThreshold=var_threshold, detectShadows=detect_shadows, engine=eng)
     for frame in frames:
         if use_hsv:
             frame = eng.bgr_to_hsv(frame)
@@ -145,7 +223,7 @@ def extract_foreground_mask(image, bg_model, learning_rate=0, figure_threshold=5
     eng = engine if engine is not None else _default_engine()
     if contour_stage == "device":
         contour_stage = lambda m, ft, fit: fill_figures_device(m, ft, fit, eng)
-    if isinstance(bg_model, BackgroundSubtractorMOG) and bg_model._eng is eng:
+    if isinstance(bg_model, (BackgroundSubtractorMOG, BackgroundSubtractorMOG2)) and bg_model._eng is eng:
         # the model lives on this device: colour conversion, apply and pre-filter without leaving it
         model_mask = eng.foreground_front(bg_model._model, image, learning_rate, apply_opening_pre, apply_closing_pre)
     else:

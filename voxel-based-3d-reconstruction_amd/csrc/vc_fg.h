@@ -3,8 +3,10 @@
 //   k_bgr2hsv        cv2.cvtColor(image, cv2.COLOR_BGR2HSV) on uint8 (:155) -- OpenCV's 8-bit fixed-point path (RGB2HSV_b, hrange 180)
 //   k_morph3x3       one pass of cv2.erode / cv2.dilate with the 3x3 MORPH_RECT element of the pre open / close (:161-168)
 //   k_mog_apply      bg_model.apply of the MOG model assignment.py trains (:158; training background_subtraction.py:75-92)
+//   k_mog2_apply     bg_model.apply of a MOG2 model (training background_subtraction.py:90-127, the comparison script :398-401)
 // findContours / fill (:171-193) is vc_contour.h.
-// PARITY UNPINNED (no cv2 here, no intermediate image in the reference): checked against oracle/foreground_np.py.
+// PARITY UNPINNED (no cv2 here, no intermediate image in the reference): checked against oracle/foreground_np.py, oracle/mog_np.py
+// and tests/mog2_np.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -205,6 +207,160 @@ __global__ __launch_bounds__(256) void k_mog_apply(const uint8_t *__restrict__ i
             }
         }
         fg[i] = (kHit < 0 || kHit >= kFg) ? 255 : 0;
+    }
+}
+
+
+// cv2.createBackgroundSubtractorMOG2(history, varThreshold, detectShadows).apply(image, None, learningRate) on an 8-bit 3-channel
+// image: Zivkovic's adaptive mixture as OpenCV's bgfg_gaussmix2.cpp implements it on the CPU (MOG2Invoker, detectShadowGMM), one
+// thread per pixel, float32, that code's order of operations (no contraction).  Per pixel nmodes <= K <= 8 live components
+// {weight, variance (one, isotropic), mean[3]}, sorted by weight, strongest first:
+//   every live component decays (weight = alpha1 w + prune); the first within varThresholdGen of the pixel takes it (weight,
+//   mean, variance pulled towards it, variance clamped to [varMin, varMax] by OpenCV's MAX / MIN macros, so NaN goes through) and
+//   bubbles up; a component whose weight drops below -prune is pruned (weight 0, nmodes - 1: the LAST one leaves the count);
+//   weights renormalised; with no match and alphaT > 0 a new component {alphaT, pixel, varInit} is appended or replaces the last.
+//   The pixel is background iff a component within varThreshold was met while the weight ahead of it was < backgroundRatio;
+//   otherwise shadowValue if detectShadows and it is a darker copy of a background component (detectShadowGMM), else 255.
+// learningRate 0 still writes: the weights are renormalised and equal weights can swap.
+// State in HBM as planes: plane (5 k + f) holds field f of component k (f: 0 weight, 1 variance, 2..4 mean), so that a wave's 64
+// pixels read 256 contiguous bytes per field, plus one u8 plane of nmodes.  Only components < nmodes are read; components
+// < max(old nmodes, new nmodes) are written back (the ones the code above may have moved or re-weighted), nothing beyond them.
+// PARITY UNPINNED (tests/mog2_np.py).
+struct Mog2Params {
+    float alphaT, alpha1, prune, Tb, TB, Tg, varInit, varMin, varMax, tau;
+    uint32_t K, npix, shadows, shadowValue;
+};
+constexpr int kMog2MaxMixtures = 8;
+
+__global__ __launch_bounds__(256) void k_mog2_apply(const uint8_t *__restrict__ img, uint8_t *__restrict__ fg, float *__restrict__ state,
+                                                   uint8_t *__restrict__ nmodes, const Mog2Params p)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= p.npix) return;
+    const int K = (int)p.K;
+    int n0 = nmodes[i];
+    n0 = n0 < K ? n0 : K;
+    const float data[3] = {(float)img[3 * i], (float)img[3 * i + 1], (float)img[3 * i + 2]};
+    float w[kMog2MaxMixtures], var[kMog2MaxMixtures], mu[kMog2MaxMixtures][3];
+#pragma unroll
+    for (int k = 0; k < kMog2MaxMixtures; ++k) {
+        if (k < n0) {
+            const float *f = state + (size_t)(5 * k) * p.npix + i;
+            w[k] = f[0]; var[k] = f[(size_t)p.npix];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) mu[k][c] = f[(size_t)(2 + c) * p.npix];
+        } else {
+            w[k] = var[k] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) mu[k][c] = 0.f;
+        }
+    }
+    auto cswap = [](float &x, float &y, bool on) { const float t = x; x = on ? y : x; y = on ? t : y; };
+    auto swap_down = [&](int a, bool on) {                     // components a and a - 1 trade places where `on`
+        cswap(w[a], w[a - 1], on);
+        cswap(var[a], var[a - 1], on);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) cswap(mu[a][c], mu[a - 1][c], on);
+    };
+    bool background = false, fits = false;
+    int n = n0;
+    float total = 0.f;
+#pragma unroll
+    for (int m = 0; m < kMog2MaxMixtures; ++m) {
+        if (m < n) {                                            // n only shrinks: the code's `for (mode = 0; mode < nmodes; ...)`
+            float weight = p.alpha1 * w[m] + p.prune;
+            int swaps = 0;
+            if (!fits) {
+                const float vm = var[m];
+                const float d[3] = {mu[m][0] - data[0], mu[m][1] - data[1], mu[m][2] - data[2]};
+                const float dist2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+                if (total < p.TB && dist2 < p.Tb * vm) background = true;
+                if (dist2 < p.Tg * vm) {
+                    fits = true;
+                    weight += p.alphaT;
+                    const float k = p.alphaT / weight;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) mu[m][c] -= k * d[c];
+                    float vn = vm + k * (dist2 - vm);
+                    vn = vn < p.varMin ? p.varMin : vn;           // MAX(vn, varMin)
+                    vn = vn > p.varMax ? p.varMax : vn;           // MIN(vn, varMax)
+                    var[m] = vn;
+                    bool moving = true;
+#pragma unroll
+                    for (int a = m; a > 0; --a) {
+                        moving = moving && !(weight < w[a - 1]);
+                        swaps += moving ? 1 : 0;
+                        swap_down(a, moving);
+                    }
+                }
+            }
+            if (weight < -p.prune) { weight = 0.f; --n; }
+#pragma unroll
+            for (int j = 0; j <= m; ++j) if (j == m - swaps) w[j] = weight;
+            total += weight;
+        }
+    }
+    const float inv = fabsf(total) > kMogEps ? 1.f / total : 0.f;
+#pragma unroll
+    for (int m = 0; m < kMog2MaxMixtures; ++m) if (m < n) w[m] *= inv;
+    if (!fits && p.alphaT > 0.f) {
+        const int mn = n == K ? K - 1 : n++;
+#pragma unroll
+        for (int j = 0; j < kMog2MaxMixtures; ++j) {
+            if (j == mn) {
+                w[j] = n == 1 ? 1.f : p.alphaT;
+                var[j] = p.varInit;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) mu[j][c] = data[c];
+            } else if (n != 1 && j < n - 1) {
+                w[j] *= p.alpha1;
+            }
+        }
+        bool moving = true;
+#pragma unroll
+        for (int a = kMog2MaxMixtures - 1; a > 0; --a) {
+            if (a <= n - 1) {
+                moving = moving && !(p.alphaT < w[a - 1]);
+                swap_down(a, moving);
+            }
+        }
+    }
+    uint8_t out = background ? 0 : 255;
+    if (!background && p.shadows) {                             // detectShadowGMM(data, n, ...)
+        float tw = 0.f;
+        bool done = false, shadow = false;
+#pragma unroll
+        for (int m = 0; m < kMog2MaxMixtures; ++m) {
+            if (m < n && !done) {
+                float num = 0.f, den = 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { num += data[c] * mu[m][c]; den += mu[m][c] * mu[m][c]; }
+                if (den == 0.f) done = true;
+                else {
+                    if (num <= den && num >= p.tau * den) {
+                        const float a = num / den;
+                        float d2a = 0.f;
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) { const float dd = a * mu[m][c] - data[c]; d2a += dd * dd; }
+                        if (d2a < p.Tb * var[m] * a * a) { shadow = true; done = true; }
+                    }
+                    if (!done) { tw += w[m]; if (tw > p.TB) done = true; }
+                }
+            }
+        }
+        if (shadow) out = (uint8_t)p.shadowValue;
+    }
+    fg[i] = out;
+    nmodes[i] = (uint8_t)n;
+    const int nw = n > n0 ? n : n0;
+#pragma unroll
+    for (int k = 0; k < kMog2MaxMixtures; ++k) {
+        if (k < nw) {
+            float *f = state + (size_t)(5 * k) * p.npix + i;
+            f[0] = w[k]; f[(size_t)p.npix] = var[k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[(size_t)(2 + c) * p.npix] = mu[k][c];
+        }
     }
 }
 

@@ -342,6 +342,16 @@ struct vc_ctx {
         uint32_t H = 0, W = 0, nframes = 0;
         DevBuf<float> state;         // [8 nmixtures][H W] planes, see k_mog_apply
     } mog[VC_MAX_MOG_MODELS];
+    struct Mog2Model {               // vc_mog2_*: one MOG2 background model, handle VC_MOG2_MODEL_TAG | index
+        bool used = false;
+        int history = 500, nmixtures = 5, shadow_value = 127;
+        bool shadows = true;
+        double var_threshold = 16;   // double((float)varThreshold), as OpenCV's constructor stores it
+        float background_ratio = 0.9f, var_threshold_gen = 9.f, var_init = 15.f, var_min = 4.f, var_max = 75.f, ct = 0.05f, tau = 0.5f;
+        uint32_t H = 0, W = 0, nframes = 0;
+        DevBuf<float> state;         // [5 nmixtures][H W] planes, see k_mog2_apply
+        DevBuf<uint8_t> nmodes;      // [H W]
+    } mog2[VC_MAX_MOG_MODELS];
     vc_timing_t tm;
     StepBuf *kev_sb = nullptr;       // timing_detail: the step whose kernels are being queued (their launches carry its per-kind events)
     DevBuf<unsigned long long> d_stats;   // timing_detail: the kernels' work counters, [VC_WORK_KINDS][kShards][kStatStride]
@@ -1160,6 +1170,7 @@ int vc_destroy(vc_ctx *ctx)
     }
     release(ctx->d_stats); release(ctx->d_fg); release(ctx->d_hsvdiv);
     for (auto &m : ctx->mog) release(m.state);
+    for (auto &m : ctx->mog2) { release(m.state); release(m.nmodes); }
     release(ctx->d_cc);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xcnt); release(ctx->d_xoff); release(ctx->d_xbsum);
@@ -2215,6 +2226,95 @@ static int mog_enqueue(vc_ctx *ctx, uint32_t model, const uint8_t *d_img, uint32
     return VC_OK;
 }
 
+// MOG2 handles carry VC_MOG2_MODEL_TAG over their own table; a MOG handle is the bare index.
+static vc_ctx::Mog2Model *mog2_model(vc_ctx *ctx, uint32_t model)
+{
+    if ((model & ~(uint32_t)(VC_MOG2_MODEL_TAG - 1)) != VC_MOG2_MODEL_TAG) return nullptr;
+    const uint32_t i = model & (VC_MOG2_MODEL_TAG - 1);
+    return i < VC_MAX_MOG_MODELS && ctx->mog2[i].used ? &ctx->mog2[i] : nullptr;
+}
+
+static bool any_model(vc_ctx *ctx, uint32_t model)
+{
+    return (model < VC_MAX_MOG_MODELS && ctx->mog[model].used) || mog2_model(ctx, model) != nullptr;
+}
+
+int vc_mog2_create(vc_ctx *ctx, int history, double var_threshold, int detect_shadows, int nmixtures, double background_ratio,
+                   double var_threshold_gen, double var_init, double var_min, double var_max, double complexity_reduction_threshold,
+                   int shadow_value, double shadow_threshold, uint32_t *model)
+{
+    if (!ctx || !model) return VC_ERR_ARG;
+    if (nmixtures < 1 || nmixtures > kMog2MaxMixtures)
+        return fail(ctx, VC_ERR_ARG, "MOG2 with %d mixtures: this build keeps 1..%d per pixel", nmixtures, kMog2MaxMixtures);
+    if (shadow_value < 0 || shadow_value > 255) return fail(ctx, VC_ERR_ARG, "MOG2 shadow value %d not in [0,255]", shadow_value);
+    for (uint32_t i = 0; i < VC_MAX_MOG_MODELS; ++i) {
+        vc_ctx::Mog2Model &m = ctx->mog2[i];
+        if (m.used) continue;
+        // the constructor (bgfg_gaussmix2.cpp, BackgroundSubtractorMOG2Impl): non-positive history / varThreshold select the defaults
+        m.history = history > 0 ? history : 500;
+        m.var_threshold = (double)(float)(var_threshold > 0 ? var_threshold : 16.0);
+        m.shadows = detect_shadows != 0;
+        m.nmixtures = nmixtures;
+        m.background_ratio = (float)background_ratio;
+        m.var_threshold_gen = (float)var_threshold_gen;
+        m.var_init = (float)var_init; m.var_min = (float)var_min; m.var_max = (float)var_max;
+        m.ct = (float)complexity_reduction_threshold;
+        m.shadow_value = shadow_value;
+        m.tau = (float)shadow_threshold;
+        m.H = m.W = m.nframes = 0;
+        m.used = true;
+        *model = VC_MOG2_MODEL_TAG | i;
+        return VC_OK;
+    }
+    return fail(ctx, VC_ERR_ARG, "all %d MOG2 background models of this context are in use", VC_MAX_MOG_MODELS);
+}
+
+int vc_mog2_destroy(vc_ctx *ctx, uint32_t model)
+{
+    if (!ctx) return VC_ERR_ARG;
+    vc_ctx::Mog2Model *m = mog2_model(ctx, model);
+    if (!m) return fail(ctx, VC_ERR_ARG, "no MOG2 background model %u", model);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream_up));
+    release(m->state);
+    release(m->nmodes);
+    m->used = false;
+    return VC_OK;
+}
+
+// One frame through a MOG2 model: d_img (device, [H W 3]) -> d_mask (device, [H W]) on the upload stream.
+static int mog2_enqueue(vc_ctx *ctx, vc_ctx::Mog2Model &m, const uint8_t *d_img, uint32_t H, uint32_t W, double learning_rate, uint8_t *d_mask)
+{
+    const size_t npix = (size_t)H * W;
+    hipStream_t st = ctx->stream_up;
+    // apply(): the model starts over on its first frame, on a learning rate >= 1 and when the image size changes
+    if (m.nframes == 0 || learning_rate >= 1 || m.H != H || m.W != W) {
+        VC_TRY(ensure(ctx, m.state, npix * 5 * (size_t)m.nmixtures));
+        VC_TRY(ensure(ctx, m.nmodes, npix));
+        VC_HIP(ctx, hipMemsetAsync(m.state.ptr, 0, npix * 5 * (size_t)m.nmixtures * sizeof(float), st));
+        VC_HIP(ctx, hipMemsetAsync(m.nmodes.ptr, 0, npix, st));
+        m.H = H; m.W = W; m.nframes = 0;
+    }
+    ++m.nframes;
+    const uint32_t two_n = 2 * m.nframes;
+    const double lr = learning_rate >= 0 && m.nframes > 1 ? learning_rate : 1.0 / (double)(two_n < (uint32_t)m.history ? two_n : (uint32_t)m.history);
+    Mog2Params p;
+    p.alphaT = (float)lr; p.alpha1 = 1.f - p.alphaT; p.prune = (float)(-lr * (double)m.ct);
+    p.Tb = (float)m.var_threshold; p.TB = m.background_ratio; p.Tg = m.var_threshold_gen;
+    p.varInit = m.var_init; p.varMin = m.var_min; p.varMax = m.var_max; p.tau = m.tau;
+    p.K = (uint32_t)m.nmixtures; p.npix = (uint32_t)npix; p.shadows = m.shadows ? 1u : 0u; p.shadowValue = (uint32_t)m.shadow_value;
+    hipLaunchKernelGGL(k_mog2_apply, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, d_img, d_mask, m.state.ptr, m.nmodes.ptr, p);
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
+// Either kind of background model (checked by any_model).
+static int model_enqueue(vc_ctx *ctx, uint32_t model, const uint8_t *d_img, uint32_t H, uint32_t W, double learning_rate, uint8_t *d_mask)
+{
+    if (vc_ctx::Mog2Model *m2 = mog2_model(ctx, model)) return mog2_enqueue(ctx, *m2, d_img, H, W, learning_rate, d_mask);
+    return mog_enqueue(ctx, model, d_img, H, W, learning_rate, d_mask);
+}
+
 static int hsv_tables(vc_ctx *ctx)
 {
     if (ctx->d_hsvdiv.ptr) return VC_OK;
@@ -2247,11 +2347,53 @@ int vc_mog_apply(vc_ctx *ctx, uint32_t model, const uint8_t *image, uint32_t H, 
     return VC_OK;
 }
 
+int vc_mog2_apply(vc_ctx *ctx, uint32_t model, const uint8_t *image, uint32_t H, uint32_t W, double learning_rate, uint8_t *fgmask)
+{
+    if (!ctx || !image || !fgmask) return VC_ERR_ARG;
+    vc_ctx::Mog2Model *m = mog2_model(ctx, model);
+    if (!m) return fail(ctx, VC_ERR_ARG, "no MOG2 background model %u", model);
+    if (H == 0 || W == 0 || (uint64_t)H * W > 0x0fffffffull) return fail(ctx, VC_ERR_ARG, "image size %u x %u", H, W);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npix = (size_t)H * W;
+    hipStream_t st = ctx->stream_up;
+    VC_TRY(ensure(ctx, ctx->d_fg, npix * 6 + 64));
+    uint8_t *d_in = ctx->d_fg.ptr, *d_out = d_in + npix * 3;
+    VC_HIP(ctx, hipMemcpyAsync(d_in, image, npix * 3, hipMemcpyHostToDevice, st));
+    VC_TRY(mog2_enqueue(ctx, *m, d_in, H, W, learning_rate, d_out));
+    VC_HIP(ctx, hipMemcpyAsync(fgmask, d_out, npix, hipMemcpyDeviceToHost, st));
+    VC_HIP(ctx, hipStreamSynchronize(st));
+    return VC_OK;
+}
+
+int vc_mog2_state(vc_ctx *ctx, uint32_t model, float *state, uint64_t capacity, uint8_t *nmodes, uint64_t nmodes_capacity, uint32_t *H,
+                  uint32_t *W, uint32_t *nmixtures, uint32_t *nframes)
+{
+    if (!ctx) return VC_ERR_ARG;
+    const vc_ctx::Mog2Model *m = mog2_model(ctx, model);
+    if (!m) return fail(ctx, VC_ERR_ARG, "no MOG2 background model %u", model);
+    if (H) *H = m->H;
+    if (W) *W = m->W;
+    if (nmixtures) *nmixtures = (uint32_t)m->nmixtures;
+    if (nframes) *nframes = m->nframes;
+    if (!state && !nmodes) return VC_OK;
+    const size_t npix = (size_t)m->H * m->W, nfloat = npix * 5 * (size_t)m->nmixtures;
+    if (state && capacity < nfloat)
+        return fail(ctx, VC_ERR_ARG, "state buffer holds %llu floats, the model has %llu", (unsigned long long)capacity, (unsigned long long)nfloat);
+    if (nmodes && nmodes_capacity < npix)
+        return fail(ctx, VC_ERR_ARG, "nmodes buffer holds %llu bytes, the model has %llu pixels", (unsigned long long)nmodes_capacity, (unsigned long long)npix);
+    if (npix == 0) return VC_OK;
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream_up));
+    if (state) VC_HIP(ctx, hipMemcpy(state, m->state.ptr, nfloat * sizeof(float), hipMemcpyDeviceToHost));
+    if (nmodes) VC_HIP(ctx, hipMemcpy(nmodes, m->nmodes.ptr, npix, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
 int vc_foreground_front(vc_ctx *ctx, uint32_t model, const uint8_t *bgr, uint32_t H, uint32_t W, int to_hsv, double learning_rate,
                         int open, int close, uint8_t *mask)
 {
     if (!ctx || !bgr || !mask) return VC_ERR_ARG;
-    if (model >= VC_MAX_MOG_MODELS || !ctx->mog[model].used) return fail(ctx, VC_ERR_ARG, "no background model %u", model);
+    if (!any_model(ctx, model)) return fail(ctx, VC_ERR_ARG, "no background model %u", model);
     if (H == 0 || W == 0 || (uint64_t)H * W > 0x0fffffffull) return fail(ctx, VC_ERR_ARG, "image size %u x %u", H, W);
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t npix = (size_t)H * W;
@@ -2266,7 +2408,7 @@ int vc_foreground_front(vc_ctx *ctx, uint32_t model, const uint8_t *bgr, uint32_
                            (const int32_t *)(ctx->d_hsvdiv.ptr + 256));
         VC_HIP(ctx, hipGetLastError());
     }
-    VC_TRY(mog_enqueue(ctx, model, to_hsv ? d_hsv : d_in, H, W, learning_rate, a));
+    VC_TRY(model_enqueue(ctx, model, to_hsv ? d_hsv : d_in, H, W, learning_rate, a));
     auto pass = [&](bool dilate) {
         if (dilate) hipLaunchKernelGGL(k_morph3x3<true>, g, blk, 0, st, (const uint8_t *)a, b, H, W);
         else hipLaunchKernelGGL(k_morph3x3<false>, g, blk, 0, st, (const uint8_t *)a, b, H, W);
@@ -2342,7 +2484,7 @@ int vc_foreground_to_slot(vc_ctx *ctx, uint32_t slot, const uint32_t *models, ui
     const uint32_t C = ctx->C;
     if (n_models < C) return fail(ctx, VC_ERR_ARG, "vc_foreground_to_slot: %u background models for %u cameras", n_models, C);
     for (uint32_t c = 0; c < C; ++c)
-        if (models[c] >= VC_MAX_MOG_MODELS || !ctx->mog[models[c]].used)
+        if (!any_model(ctx, models[c]))
             return fail(ctx, VC_ERR_ARG, "vc_foreground_to_slot: camera %u: no background model %u", c, models[c]);
     if (H != ctx->H || W != ctx->W)
         return fail(ctx, VC_ERR_ARG, "vc_foreground_to_slot: images of %u x %u, the cameras were set for %u x %u", H, W, ctx->H, ctx->W);
@@ -2368,7 +2510,7 @@ int vc_foreground_to_slot(vc_ctx *ctx, uint32_t slot, const uint32_t *models, ui
         hipLaunchKernelGGL(k_bgr2hsv, g, blk, 0, st, img, d_hsv, (uint32_t)HW, (const int32_t *)ctx->d_hsvdiv.ptr,
                            (const int32_t *)(ctx->d_hsvdiv.ptr + 256));
         uint8_t *a = ma, *b = mb;
-        VC_TRY(mog_enqueue(ctx, models[c], d_hsv, H, W, learning_rate, a));
+        VC_TRY(model_enqueue(ctx, models[c], d_hsv, H, W, learning_rate, a));
         const bool op = open_pre && open_pre[c], cl = close_pre && close_pre[c];
         const int passes = (op ? 2 : 0) + (cl ? 2 : 0);
         int k = 0;

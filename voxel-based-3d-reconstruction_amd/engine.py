@@ -201,8 +201,9 @@ class CarveEngine:
     def foreground_to_slot(self, models, frames, params, slot=0, learning_rate=0):
         """extract_foreground_mask of every camera's BGR frame straight into carve slot `slot` (background_subtraction.py:129-208
         as assignment.py:98-109 calls it), the frames becoming the slot's images.  models: one background model per camera
-        (BackgroundSubtractorMOG of this engine, or a model id); params: per camera [figure_threshold, figure_inner_threshold,
-        opening_pre, closing_pre, ...] (the rows of assignment.cam_bg_model_params).  The 2x2 post-filter is set_mask_postfilter's.
+        (BackgroundSubtractorMOG / BackgroundSubtractorMOG2 of this engine, or a model handle; the kinds may be mixed); params:
+        per camera [figure_threshold, figure_inner_threshold, opening_pre, closing_pre, ...] (the rows of
+        assignment.cam_bg_model_params).  The 2x2 post-filter is set_mask_postfilter's.
         Asynchronous: the next carve on the slot waits for it on the device."""
         ids = np.array([int(getattr(m, "_model", m)) for m in models], dtype=np.uint32)
         f = np.ascontiguousarray(np.stack([np.asarray(x) for x in frames]), dtype=np.uint8)
@@ -222,6 +223,42 @@ class CarveEngine:
 
     def mog_destroy(self, model):
         self._check(self._L.vc_mog_destroy(self._ctx, int(model)), "vc_mog_destroy")
+
+    # ---- the MOG2 background model (cv2.createBackgroundSubtractorMOG2; background_subtraction.py:90-127, :158)
+    def mog2_create(self, history=500, var_threshold=16, detect_shadows=True, nmixtures=5, background_ratio=0.9, var_threshold_gen=9,
+                    var_init=15, var_min=4, var_max=75, complexity_reduction_threshold=0.05, shadow_value=127, shadow_threshold=0.5):
+        """A MOG2 model on this device; returns its handle (VC_MOG2_MODEL_TAG | index).  nmixtures: 1..8."""
+        model = ctypes.c_uint32(0)
+        self._check(self._L.vc_mog2_create(self._ctx, int(history), float(var_threshold), int(bool(detect_shadows)), int(nmixtures),
+                                           float(background_ratio), float(var_threshold_gen), float(var_init), float(var_min),
+                                           float(var_max), float(complexity_reduction_threshold), int(shadow_value),
+                                           float(shadow_threshold), ctypes.byref(model)), "vc_mog2_create")
+        return model.value
+
+    def mog2_apply(self, model, image, learning_rate=-1):
+        a = np.ascontiguousarray(image, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("image shape %s, expected [H, W, 3]" % (a.shape,))
+        out = np.empty(a.shape[:2], dtype=np.uint8)
+        self._check(self._L.vc_mog2_apply(self._ctx, int(model), _ptr(a, ctypes.c_uint8), a.shape[0], a.shape[1], float(learning_rate),
+                                          _ptr(out, ctypes.c_uint8)), "vc_mog2_apply")
+        return out
+
+    def mog2_state(self, model):
+        """(state float32 [5 nmixtures, H W] planes -- plane 5 k + f: field f (weight, variance, mean[3]) of component k --,
+        nmodes uint8 [H W], (H, W), frames seen)."""
+        H, W, K, nf = (ctypes.c_uint32(0) for _ in range(4))
+        self._check(self._L.vc_mog2_state(self._ctx, int(model), None, 0, None, 0, ctypes.byref(H), ctypes.byref(W), ctypes.byref(K),
+                                          ctypes.byref(nf)), "vc_mog2_state")
+        state = np.zeros((5 * K.value, H.value * W.value), dtype=np.float32)
+        nmodes = np.zeros(H.value * W.value, dtype=np.uint8)
+        if nmodes.size:
+            self._check(self._L.vc_mog2_state(self._ctx, int(model), _ptr(state, ctypes.c_float), state.size, _ptr(nmodes, ctypes.c_uint8),
+                                              nmodes.size, None, None, None, None), "vc_mog2_state")
+        return state, nmodes, (H.value, W.value), nf.value
+
+    def mog2_destroy(self, model):
+        self._check(self._L.vc_mog2_destroy(self._ctx, int(model)), "vc_mog2_destroy")
 
     def fetch_mask(self, cam, slot=0):
         out = np.empty(self.image_size, dtype=np.uint8)
