@@ -102,6 +102,7 @@ typedef struct {
     /* work[VC_WORK_*]: what the kernels of those steps actually touched (counted on the device, lanes that really asked);
      * valid when no step is in flight */
     uint64_t work[VC_WORK_KINDS];
+    float visible_ms;   /* last vc_color_visible: its kernels, fill of the maps to the last colour (HIP events on the context's stream) */
 } vc_timing_t;
 
 /* ---- lifetime ------------------------------------------------------------------ */
@@ -194,6 +195,38 @@ int vc_fetch_viewmask(vc_ctx *ctx, uint16_t *viewmask);
 /* Dense occupancy of the last carve: ceil(n/64)*8 bytes, bit (j & 7) of byte j >> 3 for
  * slab-local voxel j (consumer shape of assignment.py:143-146). */
 int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits);
+
+/* ---- occlusion-aware colouring (no reference counterpart: the reference colours every survivor from camera key 2,
+ *      assignment.py:133) ----------------------------------------------------------------------------------------------
+ * vc_color_visible recolours the records of the current carve result IN PLACE from every camera that sees each surface voxel,
+ * using the images of frame set `slot` (every camera needs one: vc_upload_frame or vc_foreground_to_slot), and keeps per survivor
+ * the mask of those cameras.  Opt-in: nothing else changes, and the next carve produces the colour camera's colours again.
+ * The contract, bit for bit (tests/visible_np.py restates it; projection = the carve's float64 projection, same operation order,
+ * no contraction; xs, ys, zs = the grid's linspace axes):
+ *   1 surface: a survivor with at least one of its 6 face neighbours (iy +- 1 = index i +- 1, ix +- 1 = i +- ny, iz +- 1 =
+ *     i +- nx ny) not a survivor or outside the grid.  Other survivors are never visible.
+ *   2 voxel box: half extents hx = ((x_max - x_min) / (nx - 1)) / 2 (0 when nx = 1), likewise hy, hz; the 8 corners are
+ *     xs[ix] +- hx, ys[iy] +- hy, zs[iz] +- hz, one float64 add or subtract each.
+ *   3 depth maps: one u32 [H W] per camera, filled with the bits of +inf.  For surface voxel v and camera c: d = camera z of the
+ *     centre, R20 X + R21 Y + R22 Z + t2 left to right in float64.  Unless d > 0 and every corner's camera z > 0, v does not
+ *     splat into c; nor does it when any of umin, umax, vmin, vmax over the 8 projected corners is not finite.  Otherwise the
+ *     pixels x0 = max(floor(umin), 0) .. x1 = min(floor(umax), W - 1), y0 = max(floor(vmin), 0) .. y1 = min(floor(vmax), H - 1)
+ *     (if any) each take atomicMin with bits((float)d) -- positive floats order like their bits: the maps are deterministic.
+ *   4 visibility: surface voxel v is visible in camera c when d > 0, its centre (u, v) passes the carve's in-image test
+ *     (0 <= v < H and 0 <= u < W on the floats) and (float)d <= zmap_c[int(v) W + int(u)] + tol (the add in float32).
+ *   5 colour: a survivor visible in a non-empty set V of cameras gets, per channel, (sum over V of ch_c + |V| / 2) / |V| in
+ *     integers, ch_c = camera c's pixel int(v) W + int(u); with V empty the record keeps its RGB.  The seen byte never changes.
+ * depth_tolerance (tol) >= 0; CarveEngine.color_visible's default is the voxel diagonal (float)sqrt((2hx)^2 + (2hy)^2 + (2hz)^2).
+ * flags must be 0.  VC_ERR_ARG (with a message) when: there is no carve result, steps are in flight, the carve ran with
+ * VC_FLAG_NO_RECORDS, a camera of the slot has no image, tol is negative or NaN, the slab is narrower than the grid or a
+ * communicator of more than one rank is attached (multi-GPU visibility is out of scope).  S = 0 is no error.  Synchronous: the
+ * records are recoloured when the call returns.
+ * vc_fetch_visibility: u16 [S] in record order, bit c = visible in camera c (0 for survivors that are not surface voxels).
+ * vc_fetch_depth: camera cam's map as float [H W] (+inf where nothing splatted).  Both fail until vc_color_visible has run on
+ * the current carve result; the next carve invalidates them. */
+int vc_color_visible(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t flags);
+int vc_fetch_visibility(vc_ctx *ctx, uint16_t *vis);
+int vc_fetch_depth(vc_ctx *ctx, uint32_t cam, float *out);
 
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
@@ -310,6 +343,8 @@ int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces);
  *                   refine_b (8), refine_blocks_per_cu (8), fused_blocks_per_cu (8)
  *   streams         overlap (1)  scan + record expansion of a step on a second stream, beside the next step's carve
  *                                  (single stream while a communicator is attached)
+ *   colouring       visible_check (1)  vc_color_visible's splats read the stored depth and skip the atomic when it is already at or
+ *                                  below theirs; visible_big_rect (64)  splat rectangles of more pixels get a workgroup each
  *   experiments     dbg (0)  bit 0: skip the per-voxel level (undecided words count as alive), bit 1: skip the word level
  *                                  too -- WRONG results on purpose, to time the levels apart (scripts/exp_bricks.py); bit 2:
  *                                  no word-level tests, every word of a listed brick goes to the per-voxel level (right results)

@@ -49,7 +49,7 @@ class VcTiming(ctypes.Structure):
                 ("preps_timed", ctypes.c_uint32), ("emit_ms", ctypes.c_float), ("emit_ms_sum", ctypes.c_float),
                 ("emit_launches", ctypes.c_uint32),
                 ("kernel_ms_sum", ctypes.c_float * VC_KERNEL_KINDS), ("kernel_launches", ctypes.c_uint32 * VC_KERNEL_KINDS),
-                ("work", ctypes.c_uint64 * VC_WORK_KINDS)]
+                ("work", ctypes.c_uint64 * VC_WORK_KINDS), ("visible_ms", ctypes.c_float)]
 
 
 # name -> (restype, argtypes); every symbol include/voxcarve.h declares.
@@ -103,6 +103,9 @@ SIGNATURES = {
     "vc_host_free": (ctypes.c_int, [c_ctx, ctypes.c_void_p]),
     "vc_fetch_viewmask": (ctypes.c_int, [c_ctx, c_u16p]),
     "vc_fetch_occupancy": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_color_visible": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32]),
+    "vc_fetch_visibility": (ctypes.c_int, [c_ctx, c_u16p]),
+    "vc_fetch_depth": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
     "vc_marching_cubes": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_u64p, c_u64p]),
     "vc_fetch_mesh": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_float), c_u32p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),

@@ -160,15 +160,21 @@ frame_count = 0
 _engine = None
 _source = None
 _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused",
-             "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS}
+             "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
+             "color_mode": "camera"}
+COLOR_MODES = ("camera", "visible")
 
 
 def configure(frame_source=None, **settings):
-    """Install a frame source / override data_path, num_cameras, device, mode, ...; resets state."""
+    """Install a frame source / override data_path, num_cameras, device, mode, ...; resets state.
+    color_mode: "camera" (default) colours every survivor from the colour camera, as the reference does (assignment.py:133);
+    "visible" recolours the surface voxels from every camera that sees them (CarveEngine.color_visible)."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
         raise TypeError("unknown settings: %s" % sorted(unknown))
+    if settings.get("color_mode", _settings["color_mode"]) not in COLOR_MODES:
+        raise ValueError("color_mode %r, expected one of %s" % (settings["color_mode"], COLOR_MODES))
     _settings.update(settings)
     _source = frame_source
     if _engine is not None:
@@ -216,14 +222,18 @@ def set_voxel_positions(width, height, depth):
             _engine.build_lut()
         _engine._sized = (H, W)
     cc = _settings["color_camera"]
+    visible = _settings["color_mode"] == "visible"
     if device_source:
         if not _source.fill_slot(_engine, 0):                                   # masks and images made on the device
             return [], []
         frame_count += 1
     else:
         _engine.upload_masks(masks, slot=0)
-        _engine.upload_frame(cc, frames[cc], slot=0)
+        for c in (range(len(frames)) if visible else (cc,)):                   # "visible": every camera's image
+            _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"])
+    if visible:
+        _engine.color_visible(slot=0)
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)

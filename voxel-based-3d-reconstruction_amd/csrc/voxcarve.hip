@@ -34,6 +34,7 @@
 #include "vc_mc.h"
 #include "vc_fg.h"
 #include "vc_contour.h"
+#include "vc_visible.h"
 
 #pragma clang fp contract(off)
 
@@ -303,6 +304,13 @@ struct vc_ctx {
     uint64_t *h_total = nullptr;     // pinned scalar (all-gather count)
     bool viewmask_valid = false, carved = false;
     uint64_t survivors = 0;
+    // vc_color_visible: depth maps [C][H W] (float32 bits), camera mask per survivor, surface list + counters, large-rectangle queue
+    DevBuf<uint32_t> d_vis_zmap, d_vis_list, d_vis_ctr;
+    DevBuf<uint16_t> d_vis_mask;
+    DevBuf<uint4> d_vis_queue;
+    bool vis_valid = false;          // the maps and masks belong to the current carve result
+    int visible_check = 1;           // splats look at the stored depth before their atomic
+    int visible_big_rect = 64;       // pixels above which a splat rectangle gets a workgroup of its own
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1172,6 +1180,7 @@ int vc_destroy(vc_ctx *ctx)
     for (auto &m : ctx->mog) release(m.state);
     for (auto &m : ctx->mog2) { release(m.state); release(m.nmodes); }
     release(ctx->d_cc);
+    release(ctx->d_vis_zmap); release(ctx->d_vis_list); release(ctx->d_vis_ctr); release(ctx->d_vis_mask); release(ctx->d_vis_queue);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xcnt); release(ctx->d_xoff); release(ctx->d_xbsum);
     release(ctx->d_xboff); release(ctx->d_lut_color);
@@ -1223,7 +1232,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->have_grid = true;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1236,7 +1245,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1280,7 +1289,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1541,6 +1550,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
+    ctx->vis_valid = false;                      // the next carve invalidates what vc_color_visible left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -1874,7 +1884,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2035,6 +2045,113 @@ int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
         cur.sparse_words = false;
     }
     if (nwords) VC_HIP(ctx, hipMemcpy(bits, cur.words.ptr, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+// ---- occlusion-aware colouring of the current carve result (vc_visible.h; contract in include/voxcarve.h) ----
+int vc_color_visible(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t flags)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_color_visible: flags must be 0 (got %u)", flags);
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "vc_color_visible: no carve result");
+    StepBuf &cur = ctx->sb[ctx->cur];
+    if (cur.no_records) return fail(ctx, VC_ERR_ARG, "vc_color_visible: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to colour");
+    if (!(depth_tolerance >= 0.0f)) return fail(ctx, VC_ERR_ARG, "vc_color_visible: depth tolerance %g is negative or NaN", (double)depth_tolerance);
+    if (ctx->comm && ctx->n_ranks > 1)
+        return fail(ctx, VC_ERR_ARG, "vc_color_visible: a communicator of %d ranks is attached (multi-GPU visibility is not supported)", ctx->n_ranks);
+    if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
+        return fail(ctx, VC_ERR_ARG, "vc_color_visible: the slab [%u,%u) is narrower than the grid's %u layers", ctx->z0, ctx->z1, ctx->nz);
+    if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks) return fail(ctx, VC_ERR_ARG, "vc_color_visible: no frame set in slot %u", slot);
+    Slot &s = ctx->slots[slot];
+    for (uint32_t c = 0; c < ctx->C; ++c)
+        if (c >= s.have_frame.size() || !s.have_frame[c]) return fail(ctx, VC_ERR_ARG, "vc_color_visible: camera %u has no frame in slot %u", c, slot);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->vis_valid = false;
+    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    const size_t HW = (size_t)ctx->H * ctx->W, nmap = HW * ctx->C;
+    VC_TRY(ensure(ctx, ctx->d_vis_zmap, nmap));
+    VC_TRY(ensure(ctx, ctx->d_vis_ctr, 4));
+    VC_TRY(ensure(ctx, ctx->d_vis_mask, (size_t)S));
+    VC_TRY(ensure(ctx, ctx->d_vis_list, (size_t)S));
+    if (!s.bits_valid) VC_TRY(ensure_prepared(ctx, s, false, nullptr));   // images uploaded after the carve: into the record layout
+    if (s.prep_pending) { VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.e_prep, 0)); s.prep_pending = false; }
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    const dim3 block(kVisBlock);
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    hipLaunchKernelGGL(k_vis_fill, dim3((uint32_t)((nmap + 4 * kVisBlock - 1) / (4 * kVisBlock))), block, 0, ctx->stream,
+                       ctx->d_vis_zmap.ptr, (uint64_t)nmap, ctx->d_vis_ctr.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    if (S) {
+        const uint64_t nwords = (n + 63) / 64;
+        if (cur.sparse_words) {                  // the hierarchical kernels skip the words of groups without survivors
+            const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
+            hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
+                               ngroups, cur.groupcnt.ptr);
+            VC_HIP(ctx, hipGetLastError());
+            cur.sparse_words = false;
+        }
+        VC_TRY(ensure(ctx, ctx->d_vis_queue, (size_t)kVisQueue));
+        VisParams p;
+        memset(&p, 0, sizeof p);
+        p.xs = ctx->d_axes.ptr; p.ys = p.xs + ctx->nx; p.zs = p.ys + ctx->ny;
+        p.words = cur.words.ptr;
+        p.records = cur.records.ptr;
+        p.S = S;
+        p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.C = ctx->C; p.H = ctx->H; p.W = ctx->W;
+        const double *b = ctx->bounds;                 // half the linspace step; 0 on an axis of one voxel
+        p.hx = ctx->nx > 1 ? ((b[1] - b[0]) / (double)(ctx->nx - 1)) / 2.0 : 0.0;
+        p.hy = ctx->ny > 1 ? ((b[3] - b[2]) / (double)(ctx->ny - 1)) / 2.0 : 0.0;
+        p.hz = ctx->nz > 1 ? ((b[5] - b[4]) / (double)(ctx->nz - 1)) / 2.0 : 0.0;
+        p.tol = depth_tolerance;
+        p.zmap = ctx->d_vis_zmap.ptr;
+        p.frames = s.frames.ptr;
+        p.vis = ctx->d_vis_mask.ptr;
+        p.list = ctx->d_vis_list.ptr;
+        p.ctr = ctx->d_vis_ctr.ptr;
+        p.queue = ctx->d_vis_queue.ptr;
+        p.big = (uint32_t)ctx->visible_big_rect;
+        memcpy(p.cam, ctx->cams, sizeof(CamDev) * ctx->C);
+        const uint64_t sblocks = (S + kVisBlock - 1) / kVisBlock;
+        hipLaunchKernelGGL(k_vis_surface, dim3((uint32_t)((S + kVisBlock * kVisSurfPer - 1) / (kVisBlock * kVisSurfPer))), block, 0,
+                           ctx->stream, p);
+        // the surface count stays on the device: the list kernels stride over it with a grid sized for all survivors, capped
+        const uint32_t lb = (uint32_t)(sblocks < 2048 ? sblocks : 2048);
+        if (ctx->visible_check) {
+            hipLaunchKernelGGL(k_vis_splat<true>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
+            hipLaunchKernelGGL(k_vis_splat_big<true>, dim3(1024), block, 0, ctx->stream, p);
+        } else {
+            hipLaunchKernelGGL(k_vis_splat<false>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
+            hipLaunchKernelGGL(k_vis_splat_big<false>, dim3(1024), block, 0, ctx->stream, p);
+        }
+        hipLaunchKernelGGL(k_vis_color, dim3(lb), block, 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.visible_ms, ctx->ev[0], ctx->ev[1]));
+    ctx->vis_valid = true;
+    return VC_OK;
+}
+
+int vc_fetch_visibility(vc_ctx *ctx, uint16_t *vis)
+{
+    if (!ctx || !vis) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->vis_valid) return fail(ctx, VC_ERR_ARG, "no visibility: call vc_color_visible on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->survivors) VC_HIP(ctx, hipMemcpy(vis, ctx->d_vis_mask.ptr, ctx->survivors * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_depth(vc_ctx *ctx, uint32_t cam, float *out)
+{
+    if (!ctx || !out) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->vis_valid) return fail(ctx, VC_ERR_ARG, "no depth maps: call vc_color_visible on the current carve result");
+    if (cam >= ctx->C) return fail(ctx, VC_ERR_ARG, "camera %u not in [0,%u)", cam, ctx->C);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t HW = (size_t)ctx->H * ctx->W;
+    VC_HIP(ctx, hipMemcpy(out, ctx->d_vis_zmap.ptr + (size_t)cam * HW, HW * sizeof(float), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -2579,6 +2696,8 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
         (k == "stream_priority" ? ctx->stream_priority : ctx->reserve_cus) = value;
         VC_HIP(ctx, make_streams(ctx));
     }
+    else if (k == "visible_check") ctx->visible_check = value != 0;
+    else if (k == "visible_big_rect" && value >= 1) ctx->visible_big_rect = value;
     else if (k == "cull") ctx->cull = value != 0;
     else if (k == "bricks") ctx->bricks = value != 0;
     else if (k == "dbg") ctx->dbg = value;

@@ -407,6 +407,33 @@ class CarveEngine:
         self._check(self._L.vc_fetch_occupancy(self._ctx, _ptr(raw, ctypes.c_uint8)), "vc_fetch_occupancy")
         return np.unpackbits(raw, bitorder="little")[:n].astype(bool)
 
+    # -- occlusion-aware colouring (vc_color_visible) ----------------------------------------------------------------------------
+    def default_depth_tolerance(self):
+        """The voxel diagonal as float32: sqrt((2hx)^2 + (2hy)^2 + (2hz)^2), h = half the grid step (0 on an axis of one voxel)."""
+        h = [((self.bounds[2 * a + 1] - self.bounds[2 * a]) / (n - 1)) / 2 if n > 1 else 0.0 for a, n in enumerate(self.grid)]
+        return float(np.float32(np.sqrt((2 * h[0]) ** 2 + (2 * h[1]) ** 2 + (2 * h[2]) ** 2)))
+
+    def color_visible(self, slot=0, depth_tolerance=None):
+        """Recolours the current carve result in place: every surface survivor takes the rounded mean colour of the cameras that
+        see it past the per-camera depth maps of the surface voxels (contract: include/voxcarve.h).  Every camera of `slot`
+        needs an image.  fetch() / fetch_records() then return the new colours; the next carve the colour camera's again."""
+        if depth_tolerance is None:
+            depth_tolerance = self.default_depth_tolerance() if self.grid is not None else 0.0   # (no grid: the call reports it)
+        tol = float(depth_tolerance)
+        self._check(self._L.vc_color_visible(self._ctx, int(slot), tol, 0), "vc_color_visible")
+
+    def fetch_visibility(self):
+        """u16 [S] in record order: bit c set = the survivor is visible in camera c (after color_visible)."""
+        vis = np.empty(self.count, dtype=np.uint16)
+        self._check(self._L.vc_fetch_visibility(self._ctx, _ptr(vis, ctypes.c_uint16)), "vc_fetch_visibility")
+        return vis
+
+    def fetch_depth(self, cam):
+        """Camera cam's depth map of the surface voxels, float32 [H, W] (+inf where none splatted; after color_visible)."""
+        out = np.empty(self.image_size, dtype=np.float32)
+        self._check(self._L.vc_fetch_depth(self._ctx, int(cam), _ptr(out, ctypes.c_float)), "vc_fetch_depth")
+        return out
+
     def marching_cubes(self, volume=None, level=0.0, axes="reference"):
         """Triangle mesh of an ON/OFF volume on the device -> (verts float32 [V, 3], faces uint32 [F, 3]).
         volume: 3-D boolean array (what the reference hands to skimage.measure.marching_cubes, voxel_reconstruction.py:141);
