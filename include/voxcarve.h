@@ -228,6 +228,42 @@ int vc_color_visible(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t
 int vc_fetch_visibility(vc_ctx *ctx, uint16_t *vis);
 int vc_fetch_depth(vc_ctx *ctx, uint32_t cam, float *out);
 
+/* ---- photo-consistency carving (no reference counterpart: the reference keeps the visual hull) ------------------------------
+ * vc_photo_carve refines the current carve result A1 (S0 records in ascending index order) by space carving in the style of
+ * voxel colouring / GVC: a surface voxel that the cameras seeing it see in clearly different colours is removed, which exposes
+ * the voxels behind it, and the test repeats.  Opt-in; the next carve restores the visual hull.  The contract, bit for bit
+ * (tests/photo_np.py restates it).  Inputs: frame set `slot` (every camera needs an image), tol (depth_tolerance, meaning and
+ * default as vc_color_visible's), T = var_threshold (u32, squared 8-bit levels), m = min_views (2 <= m <= C), R = max_rounds
+ * (1 <= R <= 255).  For round r = 1 .. R:
+ *   1 the surface, the depth maps and the visible set V of every surface voxel of A_r: items 1-4 of vc_color_visible applied to A_r;
+ *   2 for a surface voxel with n = |V|, ch_c = camera c's RGB at pixel int(v) W + int(u) (item 5's sample), per channel k
+ *     s_k = sum over V of ch, q_k = sum over V of ch^2, and D = sum_k (n q_k - s_k^2) in exact integers (= n^2 x the sum of the
+ *     per-channel population variances);
+ *   3 the voxel is inconsistent iff n >= m and D > T n^2 (64-bit integers, no floating point); I_r = the inconsistent voxels;
+ *   4 I_r empty: converged at round r, stop.  Otherwise A_{r+1} = A_r \ I_r and every voxel of I_r gets round number r.  All
+ *     removals of a round are decided from A_r alone (Jacobi); the order voxels are visited in never matters.
+ * F = A_r when the loop converged at round r, else A_{R+1}.  After the call:
+ *   records: F's records in ascending index order, coloured exactly as vc_color_visible colours the input records restricted to F
+ *     (interior voxels keep their RGB, the seen byte never changes); vc_fetch_visibility / vc_fetch_depth return what
+ *     vc_color_visible on F gives; vc_fetch_occupancy returns F; vc_fetch, vc_fetch_records and the survivor count give |F|;
+ *     vc_pack_entries / vc_allgather (one rank) pack F.  vc_fetch_viewmask and vc_expand_entries stay the silhouette carve's
+ *     (the view mask of every voxel; colours from the colour camera).
+ *   vc_fetch_photo_rounds: u8 [S0], the round number of each input record in input order, 0 = kept.  It fails until a photo carve
+ *     has run on the current result; the next carve invalidates it.  vc_photo_carve may run again on F, with F as its input.
+ * stats: rounds = rounds evaluated (the empty round that shows convergence counts), converged = 1 if the loop stopped on an
+ * empty round, survivors_before = S0, survivors_after = |F|, photo_ms = HIP events around the whole call.  One 4-byte read-back
+ * per round (the round's removal count).  VC_ERR_ARG (with a message) in every case vc_color_visible refuses, and when m < 2,
+ * m > C, R = 0, R > 255, flags != 0 or stats == NULL.  S0 = 0 is no error (converged at round 1).  Synchronous. */
+typedef struct {
+    uint32_t rounds;
+    uint32_t converged;
+    uint64_t survivors_before, survivors_after;
+    float photo_ms;
+} vc_photo_stats_t;
+int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t var_threshold,
+                   uint32_t min_views, uint32_t max_rounds, uint32_t flags, vc_photo_stats_t *stats);
+int vc_fetch_photo_rounds(vc_ctx *ctx, uint8_t *rounds);   /* u8 [survivors_before] */
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own

@@ -1,7 +1,8 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
-viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible]
-(`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible"))."""
+viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo]
+(`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+`photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo"))."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -12,10 +13,12 @@ from voxcarve import assignment
 g = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 out = sys.argv[2] if len(sys.argv) > 2 else "hull.ply"
 color_mode = sys.argv[3] if len(sys.argv) > 3 else "camera"
+hull = "photo" if color_mode == "photo" else "visual"
+color_mode = "visible" if color_mode == "photo" else color_mode
 masks = fx.golden_masks()
 frames = [np.dstack([m // 2 + 60, m // 3 + 40, 255 - m // 2]).astype(np.uint8) for m in masks]   # any BGR image
 assignment.configure(frame_source=assignment.StaticFrameSource([(frames, masks)]),
-                     data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode)
+                     data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
 with open(out, "w") as f:

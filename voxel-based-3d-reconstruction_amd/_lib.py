@@ -52,6 +52,11 @@ class VcTiming(ctypes.Structure):
                 ("work", ctypes.c_uint64 * VC_WORK_KINDS), ("visible_ms", ctypes.c_float)]
 
 
+class VcPhotoStats(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("survivors_before", ctypes.c_uint64),
+                ("survivors_after", ctypes.c_uint64), ("photo_ms", ctypes.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/voxcarve.h declares.
 SIGNATURES = {
     "vc_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
@@ -106,6 +111,9 @@ SIGNATURES = {
     "vc_color_visible": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32]),
     "vc_fetch_visibility": (ctypes.c_int, [c_ctx, c_u16p]),
     "vc_fetch_depth": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float)]),
+    "vc_photo_carve": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                      ctypes.c_uint32, ctypes.POINTER(VcPhotoStats)]),
+    "vc_fetch_photo_rounds": (ctypes.c_int, [c_ctx, c_u8p]),
     "vc_marching_cubes": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_u64p, c_u64p]),
     "vc_fetch_mesh": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_float), c_u32p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),

@@ -161,20 +161,26 @@ _engine = None
 _source = None
 _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused",
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
-             "color_mode": "camera"}
+             "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200}
 COLOR_MODES = ("camera", "visible")
+HULLS = ("visual", "photo")
 
 
 def configure(frame_source=None, **settings):
     """Install a frame source / override data_path, num_cameras, device, mode, ...; resets state.
     color_mode: "camera" (default) colours every survivor from the colour camera, as the reference does (assignment.py:133);
-    "visible" recolours the surface voxels from every camera that sees them (CarveEngine.color_visible)."""
+    "visible" recolours the surface voxels from every camera that sees them (CarveEngine.color_visible).
+    hull: "visual" (default) is the carve's visual hull; "photo" refines it by photo-consistency after every carve
+    (CarveEngine.photo_carve with var_threshold=photo_var_threshold), which needs every camera's image and colours the result as
+    "visible" does; voxels_status() then describes the photo hull."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
         raise TypeError("unknown settings: %s" % sorted(unknown))
     if settings.get("color_mode", _settings["color_mode"]) not in COLOR_MODES:
         raise ValueError("color_mode %r, expected one of %s" % (settings["color_mode"], COLOR_MODES))
+    if settings.get("hull", _settings["hull"]) not in HULLS:
+        raise ValueError("hull %r, expected one of %s" % (settings["hull"], HULLS))
     _settings.update(settings)
     _source = frame_source
     if _engine is not None:
@@ -222,7 +228,8 @@ def set_voxel_positions(width, height, depth):
             _engine.build_lut()
         _engine._sized = (H, W)
     cc = _settings["color_camera"]
-    visible = _settings["color_mode"] == "visible"
+    photo = _settings["hull"] == "photo"
+    visible = _settings["color_mode"] == "visible" or photo
     if device_source:
         if not _source.fill_slot(_engine, 0):                                   # masks and images made on the device
             return [], []
@@ -232,7 +239,9 @@ def set_voxel_positions(width, height, depth):
         for c in (range(len(frames)) if visible else (cc,)):                   # "visible": every camera's image
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"])
-    if visible:
+    if photo:
+        _engine.photo_carve(slot=0, var_threshold=_settings["photo_var_threshold"])
+    elif visible:
         _engine.color_visible(slot=0)
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())

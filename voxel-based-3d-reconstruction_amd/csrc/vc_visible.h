@@ -5,6 +5,7 @@
 //   k_vis_fill      maps := +inf bits; counters := 0
 //   k_vis_surface   lane = 16 survivor records: the surface test on the occupancy words, the surface survivors compacted into
 //                   a list (one atomic per workgroup, order irrelevant), every survivor's camera mask := 0
+//                   (<true>: records a photo-consistency round has removed are skipped -- vc_photo.h)
 //   k_vis_splat     lane = surface survivor, grid y = camera: camera z of the centre and the 8 corners, the corners' pixel
 //                   rectangle; small rectangles pixel by pixel, large ones queued
 //   k_vis_splat_big a workgroup per queued rectangle
@@ -40,6 +41,7 @@ struct VisParams {
     uint4 *queue;               // {camera, key, x0 | y0 << 16, x1 | y1 << 16}
     uint32_t big;               // rectangles of more pixels than this are queued for a workgroup each (option visible_big_rect)
     CamDev cam[kMaxCameras];
+    const uint8_t *rounds;      // [S] round that removed the record, 0 = kept (k_vis_surface<true> only; vc_photo.h)
 };
 
 __device__ __forceinline__ bool vis_alive(const uint64_t *__restrict__ words, uint64_t j)
@@ -84,6 +86,8 @@ __device__ __forceinline__ bool vis_surface(const VisParams &p, uint32_t i)
 // A workgroup takes kVisBlock x kVisSurfPer consecutive records (lane t: records base + r kVisBlock + t, coalesced) and appends
 // its surface survivors to the list with ONE atomic: one per wave of 64 records put 470 000 atomics on a single address at
 // 1024^3 (2.3 ms, measured), one per 4096 records puts 7 300.
+// SKIP: records with rounds[s] != 0 are no survivors any more (their bits have left the words) and never join the list.
+template <bool SKIP>
 __global__ __launch_bounds__(kVisBlock) void k_vis_surface(const VisParams p)
 {
     __shared__ uint32_t s_wave[kVisBlock / 64], s_base;
@@ -94,7 +98,7 @@ __global__ __launch_bounds__(kVisBlock) void k_vis_surface(const VisParams p)
     for (uint32_t r = 0; r < kVisSurfPer; ++r) {
         const uint64_t s = base + (uint64_t)r * kVisBlock + t;
         if (s < p.S) {
-            if (vis_surface(p, (uint32_t)p.records[s])) bits |= 1u << r;
+            if ((!SKIP || p.rounds[s] == 0) && vis_surface(p, (uint32_t)p.records[s])) bits |= 1u << r;
             p.vis[s] = 0;
         }
     }

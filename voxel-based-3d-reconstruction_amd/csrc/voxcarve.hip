@@ -27,6 +27,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/voxcarve.h"
@@ -35,6 +36,7 @@
 #include "vc_fg.h"
 #include "vc_contour.h"
 #include "vc_visible.h"
+#include "vc_photo.h"
 
 #pragma clang fp contract(off)
 
@@ -311,6 +313,14 @@ struct vc_ctx {
     bool vis_valid = false;          // the maps and masks belong to the current carve result
     int visible_check = 1;           // splats look at the stored depth before their atomic
     int visible_big_rect = 64;       // pixels above which a splat rectangle gets a workgroup of its own
+    // vc_photo_carve: round per input record, removal counter per round, compaction counts / offsets / block sums, the records'
+    // second buffer (the compaction's target, swapped with the step's), pinned scalars (removal count, compaction total)
+    DevBuf<uint8_t> d_photo_rounds;
+    DevBuf<uint32_t> d_photo_removed, d_photo_cnt, d_photo_off;
+    DevBuf<uint64_t> d_photo_bsum, d_photo_boff, d_photo_rec;
+    uint64_t *h_photo = nullptr;     // pinned: [0] removal count of the round (low 32 bits), [1] compaction total
+    bool photo_valid = false;        // d_photo_rounds belongs to the photo carve that produced the current result
+    uint64_t photo_n = 0;            // its input survivors
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1181,6 +1191,9 @@ int vc_destroy(vc_ctx *ctx)
     for (auto &m : ctx->mog2) { release(m.state); release(m.nmodes); }
     release(ctx->d_cc);
     release(ctx->d_vis_zmap); release(ctx->d_vis_list); release(ctx->d_vis_ctr); release(ctx->d_vis_mask); release(ctx->d_vis_queue);
+    release(ctx->d_photo_rounds); release(ctx->d_photo_removed); release(ctx->d_photo_cnt); release(ctx->d_photo_off);
+    release(ctx->d_photo_bsum); release(ctx->d_photo_boff); release(ctx->d_photo_rec);
+    if (ctx->h_photo) (void)hipHostFree(ctx->h_photo);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xcnt); release(ctx->d_xoff); release(ctx->d_xbsum);
     release(ctx->d_xboff); release(ctx->d_lut_color);
@@ -1232,7 +1245,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->have_grid = true;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1245,7 +1258,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1289,7 +1302,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1550,7 +1563,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false;                      // the next carve invalidates what vc_color_visible left
+    ctx->vis_valid = false; ctx->photo_valid = false;   // the next carve invalidates what vc_color_visible / vc_photo_carve left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -1884,7 +1897,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2049,89 +2062,237 @@ int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
 }
 
 // ---- occlusion-aware colouring of the current carve result (vc_visible.h; contract in include/voxcarve.h) ----
-int vc_color_visible(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t flags)
+// The refusals vc_color_visible and vc_photo_carve share; `what` names the call in the message.
+static int visible_refusals(vc_ctx *ctx, const char *what, uint32_t slot, float depth_tolerance)
 {
-    if (!ctx) return VC_ERR_ARG;
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_color_visible: flags must be 0 (got %u)", flags);
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "vc_color_visible: no carve result");
-    StepBuf &cur = ctx->sb[ctx->cur];
-    if (cur.no_records) return fail(ctx, VC_ERR_ARG, "vc_color_visible: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to colour");
-    if (!(depth_tolerance >= 0.0f)) return fail(ctx, VC_ERR_ARG, "vc_color_visible: depth tolerance %g is negative or NaN", (double)depth_tolerance);
+    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "%s: no carve result", what);
+    if (ctx->sb[ctx->cur].no_records) return fail(ctx, VC_ERR_ARG, "%s: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to colour", what);
+    if (!(depth_tolerance >= 0.0f)) return fail(ctx, VC_ERR_ARG, "%s: depth tolerance %g is negative or NaN", what, (double)depth_tolerance);
     if (ctx->comm && ctx->n_ranks > 1)
-        return fail(ctx, VC_ERR_ARG, "vc_color_visible: a communicator of %d ranks is attached (multi-GPU visibility is not supported)", ctx->n_ranks);
+        return fail(ctx, VC_ERR_ARG, "%s: a communicator of %d ranks is attached (multi-GPU visibility is not supported)", what, ctx->n_ranks);
     if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
-        return fail(ctx, VC_ERR_ARG, "vc_color_visible: the slab [%u,%u) is narrower than the grid's %u layers", ctx->z0, ctx->z1, ctx->nz);
-    if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks) return fail(ctx, VC_ERR_ARG, "vc_color_visible: no frame set in slot %u", slot);
-    Slot &s = ctx->slots[slot];
+        return fail(ctx, VC_ERR_ARG, "%s: the slab [%u,%u) is narrower than the grid's %u layers", what, ctx->z0, ctx->z1, ctx->nz);
+    if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks) return fail(ctx, VC_ERR_ARG, "%s: no frame set in slot %u", what, slot);
+    const Slot &s = ctx->slots[slot];
     for (uint32_t c = 0; c < ctx->C; ++c)
-        if (c >= s.have_frame.size() || !s.have_frame[c]) return fail(ctx, VC_ERR_ARG, "vc_color_visible: camera %u has no frame in slot %u", c, slot);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->vis_valid = false;
-    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+        if (c >= s.have_frame.size() || !s.have_frame[c]) return fail(ctx, VC_ERR_ARG, "%s: camera %u has no frame in slot %u", what, c, slot);
+    return VC_OK;
+}
+
+// The slot's images in the record layout, and the context's stream behind the step's record expansion.
+static int visible_prepare(vc_ctx *ctx, Slot &s, StepBuf &cur)
+{
+    if (!s.bits_valid) VC_TRY(ensure_prepared(ctx, s, false, nullptr));   // images uploaded after the carve: into the record layout
+    if (s.prep_pending) { VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.e_prep, 0)); s.prep_pending = false; }
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (ctx->survivors && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    return VC_OK;
+}
+
+// Queues items 1-4 of the colouring contract over records[0, S) of the current result on the context's stream: fill of the maps,
+// surface list, splats.  rounds != null: records with rounds[s] != 0 are skipped (vc_photo_carve).  p is left filled for the
+// kernel that follows (k_vis_color, k_photo_test), *lb with the grid those list kernels take.  No host synchronisation.
+static int enqueue_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, uint64_t *records, uint64_t S, float tol, const uint8_t *rounds,
+                           VisParams &p, uint32_t &lb)
+{
+    const uint64_t n = ctx->n_voxels();
     const size_t HW = (size_t)ctx->H * ctx->W, nmap = HW * ctx->C;
     VC_TRY(ensure(ctx, ctx->d_vis_zmap, nmap));
     VC_TRY(ensure(ctx, ctx->d_vis_ctr, 4));
     VC_TRY(ensure(ctx, ctx->d_vis_mask, (size_t)S));
     VC_TRY(ensure(ctx, ctx->d_vis_list, (size_t)S));
-    if (!s.bits_valid) VC_TRY(ensure_prepared(ctx, s, false, nullptr));   // images uploaded after the carve: into the record layout
-    if (s.prep_pending) { VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.e_prep, 0)); s.prep_pending = false; }
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
     const dim3 block(kVisBlock);
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     hipLaunchKernelGGL(k_vis_fill, dim3((uint32_t)((nmap + 4 * kVisBlock - 1) / (4 * kVisBlock))), block, 0, ctx->stream,
                        ctx->d_vis_zmap.ptr, (uint64_t)nmap, ctx->d_vis_ctr.ptr);
     VC_HIP(ctx, hipGetLastError());
-    if (S) {
-        const uint64_t nwords = (n + 63) / 64;
-        if (cur.sparse_words) {                  // the hierarchical kernels skip the words of groups without survivors
-            const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
-            hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
-                               ngroups, cur.groupcnt.ptr);
-            VC_HIP(ctx, hipGetLastError());
-            cur.sparse_words = false;
-        }
-        VC_TRY(ensure(ctx, ctx->d_vis_queue, (size_t)kVisQueue));
-        VisParams p;
-        memset(&p, 0, sizeof p);
-        p.xs = ctx->d_axes.ptr; p.ys = p.xs + ctx->nx; p.zs = p.ys + ctx->ny;
-        p.words = cur.words.ptr;
-        p.records = cur.records.ptr;
-        p.S = S;
-        p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.C = ctx->C; p.H = ctx->H; p.W = ctx->W;
-        const double *b = ctx->bounds;                 // half the linspace step; 0 on an axis of one voxel
-        p.hx = ctx->nx > 1 ? ((b[1] - b[0]) / (double)(ctx->nx - 1)) / 2.0 : 0.0;
-        p.hy = ctx->ny > 1 ? ((b[3] - b[2]) / (double)(ctx->ny - 1)) / 2.0 : 0.0;
-        p.hz = ctx->nz > 1 ? ((b[5] - b[4]) / (double)(ctx->nz - 1)) / 2.0 : 0.0;
-        p.tol = depth_tolerance;
-        p.zmap = ctx->d_vis_zmap.ptr;
-        p.frames = s.frames.ptr;
-        p.vis = ctx->d_vis_mask.ptr;
-        p.list = ctx->d_vis_list.ptr;
-        p.ctr = ctx->d_vis_ctr.ptr;
-        p.queue = ctx->d_vis_queue.ptr;
-        p.big = (uint32_t)ctx->visible_big_rect;
-        memcpy(p.cam, ctx->cams, sizeof(CamDev) * ctx->C);
-        const uint64_t sblocks = (S + kVisBlock - 1) / kVisBlock;
-        hipLaunchKernelGGL(k_vis_surface, dim3((uint32_t)((S + kVisBlock * kVisSurfPer - 1) / (kVisBlock * kVisSurfPer))), block, 0,
-                           ctx->stream, p);
-        // the surface count stays on the device: the list kernels stride over it with a grid sized for all survivors, capped
-        const uint32_t lb = (uint32_t)(sblocks < 2048 ? sblocks : 2048);
-        if (ctx->visible_check) {
-            hipLaunchKernelGGL(k_vis_splat<true>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
-            hipLaunchKernelGGL(k_vis_splat_big<true>, dim3(1024), block, 0, ctx->stream, p);
-        } else {
-            hipLaunchKernelGGL(k_vis_splat<false>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
-            hipLaunchKernelGGL(k_vis_splat_big<false>, dim3(1024), block, 0, ctx->stream, p);
-        }
-        hipLaunchKernelGGL(k_vis_color, dim3(lb), block, 0, ctx->stream, p);
+    lb = 0;
+    if (!S) return VC_OK;
+    const uint64_t nwords = (n + 63) / 64;
+    if (cur.sparse_words) {                      // the hierarchical kernels skip the words of groups without survivors
+        const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
+        hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
+                           ngroups, cur.groupcnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        cur.sparse_words = false;
+    }
+    VC_TRY(ensure(ctx, ctx->d_vis_queue, (size_t)kVisQueue));
+    memset(&p, 0, sizeof p);
+    p.xs = ctx->d_axes.ptr; p.ys = p.xs + ctx->nx; p.zs = p.ys + ctx->ny;
+    p.words = cur.words.ptr;
+    p.records = records;
+    p.S = S;
+    p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.C = ctx->C; p.H = ctx->H; p.W = ctx->W;
+    const double *b = ctx->bounds;                 // half the linspace step; 0 on an axis of one voxel
+    p.hx = ctx->nx > 1 ? ((b[1] - b[0]) / (double)(ctx->nx - 1)) / 2.0 : 0.0;
+    p.hy = ctx->ny > 1 ? ((b[3] - b[2]) / (double)(ctx->ny - 1)) / 2.0 : 0.0;
+    p.hz = ctx->nz > 1 ? ((b[5] - b[4]) / (double)(ctx->nz - 1)) / 2.0 : 0.0;
+    p.tol = tol;
+    p.zmap = ctx->d_vis_zmap.ptr;
+    p.frames = s.frames.ptr;
+    p.vis = ctx->d_vis_mask.ptr;
+    p.list = ctx->d_vis_list.ptr;
+    p.ctr = ctx->d_vis_ctr.ptr;
+    p.queue = ctx->d_vis_queue.ptr;
+    p.big = (uint32_t)ctx->visible_big_rect;
+    memcpy(p.cam, ctx->cams, sizeof(CamDev) * ctx->C);
+    p.rounds = rounds;
+    const uint64_t sblocks = (S + kVisBlock - 1) / kVisBlock;
+    const dim3 sgrid((uint32_t)((S + kVisBlock * kVisSurfPer - 1) / (kVisBlock * kVisSurfPer)));
+    if (rounds) hipLaunchKernelGGL(k_vis_surface<true>, sgrid, block, 0, ctx->stream, p);
+    else hipLaunchKernelGGL(k_vis_surface<false>, sgrid, block, 0, ctx->stream, p);
+    // the surface count stays on the device: the list kernels stride over it with a grid sized for all survivors, capped
+    lb = (uint32_t)(sblocks < 2048 ? sblocks : 2048);
+    if (ctx->visible_check) {
+        hipLaunchKernelGGL(k_vis_splat<true>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
+        hipLaunchKernelGGL(k_vis_splat_big<true>, dim3(1024), block, 0, ctx->stream, p);
+    } else {
+        hipLaunchKernelGGL(k_vis_splat<false>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
+        hipLaunchKernelGGL(k_vis_splat_big<false>, dim3(1024), block, 0, ctx->stream, p);
+    }
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
+// The whole colouring pass (items 1-5) over the current result's records; no host synchronisation.
+static int enqueue_color_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, float tol)
+{
+    VisParams p;
+    uint32_t lb = 0;
+    VC_TRY(enqueue_visible(ctx, s, cur, cur.records.ptr, ctx->survivors, tol, nullptr, p, lb));
+    if (lb) {
+        hipLaunchKernelGGL(k_vis_color, dim3(lb), dim3(kVisBlock), 0, ctx->stream, p);
         VC_HIP(ctx, hipGetLastError());
     }
+    return VC_OK;
+}
+
+int vc_color_visible(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t flags)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_color_visible: flags must be 0 (got %u)", flags);
+    VC_TRY(visible_refusals(ctx, "vc_color_visible", slot, depth_tolerance));
+    Slot &s = ctx->slots[slot];
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->vis_valid = false;
+    VC_TRY(visible_prepare(ctx, s, cur));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(enqueue_color_visible(ctx, s, cur, depth_tolerance));
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.visible_ms, ctx->ev[0], ctx->ev[1]));
     ctx->vis_valid = true;
+    return VC_OK;
+}
+
+// ---- photo-consistency carving of the current carve result (vc_photo.h; contract in include/voxcarve.h) ----
+int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t var_threshold, uint32_t min_views,
+                   uint32_t max_rounds, uint32_t flags, vc_photo_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_photo_carve: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_photo_carve: flags must be 0 (got %u)", flags);
+    VC_TRY(visible_refusals(ctx, "vc_photo_carve", slot, depth_tolerance));
+    if (min_views < 2 || min_views > ctx->C)
+        return fail(ctx, VC_ERR_ARG, "vc_photo_carve: min_views %u not in [2, %u] (2 .. the number of cameras)", min_views, ctx->C);
+    if (max_rounds < 1 || max_rounds > kPhotoMaxRounds)
+        return fail(ctx, VC_ERR_ARG, "vc_photo_carve: max_rounds %u not in [1, %u]", max_rounds, kPhotoMaxRounds);
+    Slot &s = ctx->slots[slot];
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->vis_valid = false; ctx->photo_valid = false;
+    const uint64_t S0 = ctx->survivors;
+    VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
+    VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
+    if (!ctx->h_photo)
+        VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_photo), 2 * sizeof(uint64_t), hipHostMallocDefault));
+    VC_TRY(visible_prepare(ctx, s, cur));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (S0) VC_HIP(ctx, hipMemsetAsync(ctx->d_photo_rounds.ptr, 0, (size_t)S0, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_photo_removed.ptr, 0, (kPhotoMaxRounds + 1) * sizeof(uint32_t), ctx->stream));
+    PhotoParams q;
+    memset(&q, 0, sizeof q);
+    q.rounds = ctx->d_photo_rounds.ptr;
+    q.words = cur.words.ptr;
+    q.thr = var_threshold;
+    q.min_views = min_views;
+    uint64_t left = S0;
+    uint32_t r = 0;
+    bool converged = false;
+    while (r < max_rounds) {
+        ++r;
+        VisParams p;
+        uint32_t lb = 0;
+        VC_TRY(enqueue_visible(ctx, s, cur, cur.records.ptr, S0, depth_tolerance, q.rounds, p, lb));
+        q.removed = ctx->d_photo_removed.ptr + r;
+        q.round = r;
+        if (lb) {
+            hipLaunchKernelGGL(k_photo_test, dim3(lb), dim3(kVisBlock), 0, ctx->stream, p, q);
+            VC_HIP(ctx, hipGetLastError());
+        }
+        // 4 bytes back per round: the loop ends on the first round without removals
+        ctx->h_photo[0] = 0;
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_photo, q.removed, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const uint32_t gone = (uint32_t)ctx->h_photo[0];
+        if (gone > left) return fail(ctx, VC_ERR_HIP, "vc_photo_carve: round %u removed %u of %llu survivors", r, gone, (unsigned long long)left);
+        if (gone == 0) { converged = true; break; }
+        left -= gone;
+    }
+    if (left != S0) {
+        // stable compaction of the kept records into the second buffer, which then becomes the step's
+        const uint32_t ngroups = (uint32_t)((S0 + kPhotoGroup - 1) / kPhotoGroup);
+        const uint32_t nscan = (ngroups + kScanBlock - 1) / kScanBlock;
+        VC_TRY(ensure(ctx, ctx->d_photo_cnt, ngroups));
+        VC_TRY(ensure(ctx, ctx->d_photo_off, ngroups));
+        VC_TRY(ensure(ctx, ctx->d_photo_bsum, kMaxScanBlocks));
+        VC_TRY(ensure(ctx, ctx->d_photo_boff, kMaxScanBlocks + 1));
+        VC_TRY(ensure(ctx, ctx->d_photo_rec, cur.records.cap));
+        hipLaunchKernelGGL(k_photo_count, dim3(ngroups), dim3(kVisBlock), 0, ctx->stream, (const uint8_t *)ctx->d_photo_rounds.ptr, S0,
+                           ctx->d_photo_cnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_photo_cnt.ptr, ngroups, ctx->d_photo_off.ptr, ctx->d_photo_bsum.ptr,
+                           ctx->d_photo_boff.ptr, ctx->h_photo + 1));
+        hipLaunchKernelGGL(k_photo_scatter, dim3(ngroups), dim3(kVisBlock), 0, ctx->stream, (const uint64_t *)cur.records.ptr,
+                           (const uint8_t *)ctx->d_photo_rounds.ptr, S0, (const uint32_t *)ctx->d_photo_off.ptr,
+                           (const uint64_t *)ctx->d_photo_boff.ptr, ctx->d_photo_rec.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        std::swap(cur.records, ctx->d_photo_rec);
+        // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
+        const uint64_t n = cur.n, n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
+        const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
+        VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_photo_boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+        cur.nz_valid = false;                    // non-zero word counts per group: counted again by the next packing
+        ctx->survivors = cur.survivors = left;
+        ctx->gathered = false; ctx->packed = false;
+    }
+    VC_TRY(enqueue_color_visible(ctx, s, cur, depth_tolerance));   // the colouring of F: its maps, masks and colours
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (left != S0 && ctx->h_photo[1] != left)
+        return fail(ctx, VC_ERR_HIP, "vc_photo_carve: the compaction kept %llu records, the rounds left %llu",
+                    (unsigned long long)ctx->h_photo[1], (unsigned long long)left);
+    VC_HIP(ctx, hipEventElapsedTime(&stats->photo_ms, ctx->ev[0], ctx->ev[1]));
+    stats->rounds = r;
+    stats->converged = converged ? 1u : 0u;
+    stats->survivors_before = S0;
+    stats->survivors_after = left;
+    ctx->vis_valid = true;
+    ctx->photo_valid = true;
+    ctx->photo_n = S0;
+    return VC_OK;
+}
+
+int vc_fetch_photo_rounds(vc_ctx *ctx, uint8_t *rounds)
+{
+    if (!ctx || !rounds) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->photo_valid) return fail(ctx, VC_ERR_ARG, "no photo rounds: call vc_photo_carve on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->photo_n) VC_HIP(ctx, hipMemcpy(rounds, ctx->d_photo_rounds.ptr, (size_t)ctx->photo_n, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 

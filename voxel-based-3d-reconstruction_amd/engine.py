@@ -434,6 +434,30 @@ class CarveEngine:
         self._check(self._L.vc_fetch_depth(self._ctx, int(cam), _ptr(out, ctypes.c_float)), "vc_fetch_depth")
         return out
 
+    # -- photo-consistency carving (vc_photo_carve) -------------------------------------------------------------------------------
+    def photo_carve(self, slot=0, var_threshold=1200, min_views=2, max_rounds=32, depth_tolerance=None):
+        """Refines the current carve result by photo-consistency (contract: include/voxcarve.h): rounds of the visibility pass of
+        color_visible, every surface voxel whose visible cameras (at least min_views of them) disagree on its colour by more than
+        var_threshold (sum of the per-channel variances, squared 8-bit levels) removed, until a round removes nothing or
+        max_rounds have run.  Every camera of `slot` needs an image.  The records, the count, the occupancy, the visibility and
+        the depth maps then describe the photo hull, coloured as color_visible colours it; the next carve restores the visual
+        hull.  Returns the stats as a dict: rounds, converged, survivors_before, survivors_after, photo_ms."""
+        if depth_tolerance is None:
+            depth_tolerance = self.default_depth_tolerance() if self.grid is not None else 0.0   # (no grid: the call reports it)
+        st = _lib.VcPhotoStats()
+        self._check(self._L.vc_photo_carve(self._ctx, int(slot), float(depth_tolerance), int(var_threshold), int(min_views),
+                                           int(max_rounds), 0, ctypes.byref(st)), "vc_photo_carve")
+        self.count = int(st.survivors_after)
+        self._photo_n = int(st.survivors_before)
+        return {"rounds": int(st.rounds), "converged": bool(st.converged), "survivors_before": int(st.survivors_before),
+                "survivors_after": int(st.survivors_after), "photo_ms": float(st.photo_ms)}
+
+    def fetch_photo_rounds(self):
+        """u8 [survivors_before]: per record of the last photo_carve's input, in its order, the round that removed it (0 = kept)."""
+        out = np.empty(getattr(self, "_photo_n", 0), dtype=np.uint8)
+        self._check(self._L.vc_fetch_photo_rounds(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_photo_rounds")
+        return out
+
     def marching_cubes(self, volume=None, level=0.0, axes="reference"):
         """Triangle mesh of an ON/OFF volume on the device -> (verts float32 [V, 3], faces uint32 [F, 3]).
         volume: 3-D boolean array (what the reference hands to skimage.measure.marching_cubes, voxel_reconstruction.py:141);
