@@ -264,6 +264,45 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
                    uint32_t min_views, uint32_t max_rounds, uint32_t flags, vc_photo_stats_t *stats);
 int vc_fetch_photo_rounds(vc_ctx *ctx, uint8_t *rounds);   /* u8 [survivors_before] */
 
+/* ---- connected components of the hull (no reference counterpart: the reference keeps every survivor) ---------------------------
+ * vc_hull_components labels the connected components of the current carve result A (S0 records in ascending linear index i) and
+ * removes the survivors of the components that fail a size rule: specks of mask noise that every camera happens to agree on
+ * survive the carve as small clumps beside the figure.  Opt-in; the next carve restores the visual hull.  The contract, bit for
+ * bit (tests/components_np.py restates it).  Inputs: connectivity N in {6, 18, 26} (the neighbourhood of
+ * scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3): face, + edge, + corner neighbours), min_voxels (0 and 1: no floor),
+ * keep_largest (0: no limit), flags = 0.
+ *   1 two survivors are connected when they are N-neighbours in (ix, iy, iz), no wrap-around (i and i + 1 are not neighbours
+ *     when (i + 1) % ny == 0);
+ *   2 a component's label is its smallest linear index (the index of its first record), its size the number of its voxels,
+ *     its box the inclusive lo[3], hi[3] of its (ix, iy, iz);
+ *   3 rank orders the components by size descending, then label ascending; a component is kept iff size >= min_voxels and,
+ *     when keep_largest > 0, rank < keep_largest.
+ * After the call:
+ *   records, count, occupancy: the kept survivors only, records in ascending order with colour and seen byte unchanged;
+ *     vc_fetch_occupancy, vc_fetch, vc_fetch_records, vc_pack_entries / vc_allgather (one rank), vc_marching_cubes(volume NULL)
+ *     see the filtered hull.  vc_fetch_viewmask and vc_expand_entries stay the silhouette carve's.  Visibility, depth maps and
+ *     photo rounds of an earlier vc_color_visible / vc_photo_carve fail until those run again.
+ *   vc_fetch_component_labels: u32 [S0], the label of each input record in input order.
+ *   vc_fetch_components: vc_component_t [components] in ascending label.
+ *   Both fail until the pass has run on the current result; vc_hull_components may run again on its own output.
+ * stats: components, components_kept, survivors_before = S0, survivors_after, largest (size of the largest component, 0 on an
+ * empty hull), components_ms = HIP events around the whole call.  One read-back in the middle (the number of components).
+ * VC_ERR_ARG (with a message) when there is no carve result, steps are in flight, the carve ran with VC_FLAG_NO_RECORDS, a
+ * communicator of more than one rank is attached, the slab is narrower than the grid, N is not 6, 18 or 26, flags != 0 or
+ * stats == NULL.  S0 = 0 is no error (no components).  Synchronous. */
+typedef struct {
+    uint32_t components, components_kept;
+    uint64_t survivors_before, survivors_after;
+    uint32_t largest;          /* size of the largest component, 0 on an empty hull */
+    float    components_ms;    /* HIP events around the whole call */
+} vc_component_stats_t;
+typedef struct { uint32_t label, size, lo[3], hi[3], kept, reserved; } vc_component_t;
+
+int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, uint32_t keep_largest,
+                       uint32_t flags, vc_component_stats_t *stats);
+int vc_fetch_component_labels(vc_ctx *ctx, uint32_t *labels);      /* u32 [survivors_before], input record order */
+int vc_fetch_components(vc_ctx *ctx, vc_component_t *out);         /* [components], ascending label */
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own

@@ -57,6 +57,16 @@ class VcPhotoStats(ctypes.Structure):
                 ("survivors_after", ctypes.c_uint64), ("photo_ms", ctypes.c_float)]
 
 
+class VcComponentStats(ctypes.Structure):
+    _fields_ = [("components", ctypes.c_uint32), ("components_kept", ctypes.c_uint32), ("survivors_before", ctypes.c_uint64),
+                ("survivors_after", ctypes.c_uint64), ("largest", ctypes.c_uint32), ("components_ms", ctypes.c_float)]
+
+
+class VcComponent(ctypes.Structure):
+    _fields_ = [("label", ctypes.c_uint32), ("size", ctypes.c_uint32), ("lo", ctypes.c_uint32 * 3), ("hi", ctypes.c_uint32 * 3),
+                ("kept", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 # name -> (restype, argtypes); every symbol include/voxcarve.h declares.
 SIGNATURES = {
     "vc_device_count": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int)]),
@@ -114,6 +124,10 @@ SIGNATURES = {
     "vc_photo_carve": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                       ctypes.c_uint32, ctypes.POINTER(VcPhotoStats)]),
     "vc_fetch_photo_rounds": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_hull_components": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.POINTER(VcComponentStats)]),
+    "vc_fetch_component_labels": (ctypes.c_int, [c_ctx, c_u32p]),
+    "vc_fetch_components": (ctypes.c_int, [c_ctx, ctypes.c_void_p]),
     "vc_marching_cubes": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_u64p, c_u64p]),
     "vc_fetch_mesh": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_float), c_u32p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),

@@ -161,7 +161,8 @@ _engine = None
 _source = None
 _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused",
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
-             "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200}
+             "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
+             "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26}
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -172,7 +173,11 @@ def configure(frame_source=None, **settings):
     "visible" recolours the surface voxels from every camera that sees them (CarveEngine.color_visible).
     hull: "visual" (default) is the carve's visual hull; "photo" refines it by photo-consistency after every carve
     (CarveEngine.photo_carve with var_threshold=photo_var_threshold), which needs every camera's image and colours the result as
-    "visible" does; voxels_status() then describes the photo hull."""
+    "visible" does; voxels_status() then describes the photo hull.
+    min_component_voxels, keep_components: when either is non-zero, every carve is followed by CarveEngine.filter_components
+    (connectivity=component_connectivity), before any colouring or photo carve: components smaller than min_component_voxels,
+    or beyond the keep_components largest, leave the hull (floating specks of mask noise); voxels_status() describes what is
+    kept.  0 and 0 (the default) keep every survivor."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -239,6 +244,9 @@ def set_voxel_positions(width, height, depth):
         for c in (range(len(frames)) if visible else (cc,)):                   # "visible": every camera's image
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"])
+    if _settings["min_component_voxels"] or _settings["keep_components"]:
+        _engine.filter_components(connectivity=_settings["component_connectivity"], min_voxels=_settings["min_component_voxels"],
+                                  keep_largest=_settings["keep_components"])
     if photo:
         _engine.photo_carve(slot=0, var_threshold=_settings["photo_var_threshold"])
     elif visible:

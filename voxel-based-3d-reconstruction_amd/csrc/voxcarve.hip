@@ -37,6 +37,7 @@
 #include "vc_contour.h"
 #include "vc_visible.h"
 #include "vc_photo.h"
+#include "vc_components.h"
 
 #pragma clang fp contract(off)
 
@@ -321,6 +322,17 @@ struct vc_ctx {
     uint64_t *h_photo = nullptr;     // pinned: [0] removal count of the round (low 32 bits), [1] compaction total
     bool photo_valid = false;        // d_photo_rounds belongs to the photo carve that produced the current result
     uint64_t photo_n = 0;            // its input survivors
+    // vc_hull_components: word / record / root compaction counts, offsets and block sums, survivors before each word, the
+    // union-find forest, labels, component numbers of the roots, the root list, sizes, boxes, keep flags, component entries,
+    // [kept components, largest], the select threshold, the records' second buffer, pinned scalars (roots, kept records, misc)
+    DevBuf<uint32_t> d_cc_cnt, d_cc_off, d_cc_woff, d_cc_parent, d_cc_label, d_cc_cid, d_cc_roots, d_cc_size, d_cc_box, d_cc_comp,
+        d_cc_misc;
+    DevBuf<uint8_t> d_cc_kept;
+    DevBuf<uint64_t> d_cc_bsum, d_cc_boff, d_cc_thr, d_cc_rec;
+    uint64_t *h_cc = nullptr;        // pinned: [0] components, [1] kept records, [2] misc (kept components | largest << 32)
+    bool cc_valid = false;           // labels and components belong to the pass that produced the current result
+    uint64_t cc_n = 0;               // its input survivors
+    uint32_t cc_k = 0;               // its components
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1194,6 +1206,11 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_photo_rounds); release(ctx->d_photo_removed); release(ctx->d_photo_cnt); release(ctx->d_photo_off);
     release(ctx->d_photo_bsum); release(ctx->d_photo_boff); release(ctx->d_photo_rec);
     if (ctx->h_photo) (void)hipHostFree(ctx->h_photo);
+    release(ctx->d_cc_cnt); release(ctx->d_cc_off); release(ctx->d_cc_woff); release(ctx->d_cc_parent); release(ctx->d_cc_label);
+    release(ctx->d_cc_cid); release(ctx->d_cc_roots); release(ctx->d_cc_size); release(ctx->d_cc_box); release(ctx->d_cc_comp);
+    release(ctx->d_cc_misc); release(ctx->d_cc_kept); release(ctx->d_cc_bsum); release(ctx->d_cc_boff); release(ctx->d_cc_thr);
+    release(ctx->d_cc_rec);
+    if (ctx->h_cc) (void)hipHostFree(ctx->h_cc);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xcnt); release(ctx->d_xoff); release(ctx->d_xbsum);
     release(ctx->d_xboff); release(ctx->d_lut_color);
@@ -1245,7 +1262,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->have_grid = true;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1258,7 +1275,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1302,7 +1319,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1563,7 +1580,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false;   // the next carve invalidates what vc_color_visible / vc_photo_carve left
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -1897,7 +1914,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2203,7 +2220,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
@@ -2293,6 +2310,183 @@ int vc_fetch_photo_rounds(vc_ctx *ctx, uint8_t *rounds)
     if (!ctx->carved || !ctx->photo_valid) return fail(ctx, VC_ERR_ARG, "no photo rounds: call vc_photo_carve on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->photo_n) VC_HIP(ctx, hipMemcpy(rounds, ctx->d_photo_rounds.ptr, (size_t)ctx->photo_n, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+// ---- connected components of the current carve result (vc_components.h; contract in include/voxcarve.h) ----
+int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, uint32_t keep_largest, uint32_t flags,
+                       vc_component_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_components: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_components: flags must be 0 (got %u)", flags);
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_components: connectivity %u, expected 6, 18 or 26", connectivity);
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "vc_hull_components: no carve result");
+    if (ctx->sb[ctx->cur].no_records)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_components: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to label");
+    if (ctx->comm && ctx->n_ranks > 1)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_components: a communicator of %d ranks is attached (multi-GPU labelling is not supported)",
+                    ctx->n_ranks);
+    if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_components: the slab [%u,%u) is narrower than the grid's %u layers", ctx->z0, ctx->z1, ctx->nz);
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
+    if (!ctx->h_cc) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_cc), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    uint32_t K = 0;
+    uint64_t kept_records = 0;
+    if (S0) {
+        const uint64_t nwords = (n + 63) / 64;
+        if (cur.sparse_words) {                  // the hierarchical kernels skip the words of groups without survivors
+            const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
+            hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
+                               ngroups, cur.groupcnt.ptr);
+            VC_HIP(ctx, hipGetLastError());
+            cur.sparse_words = false;
+        }
+        const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);                  // 64 words per group: <= 2^20 groups
+        const uint32_t rgroups = (uint32_t)((S0 + kCcGroup - 1) / kCcGroup);
+        const uint32_t cgroups = wgroups > rgroups ? wgroups : rgroups;
+        VC_TRY(ensure(ctx, ctx->d_cc_cnt, cgroups));
+        VC_TRY(ensure(ctx, ctx->d_cc_off, cgroups));
+        VC_TRY(ensure(ctx, ctx->d_cc_bsum, kMaxScanBlocks));
+        VC_TRY(ensure(ctx, ctx->d_cc_boff, kMaxScanBlocks + 1));
+        VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
+        VC_TRY(ensure(ctx, ctx->d_cc_parent, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->d_cc_label, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->d_cc_cid, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->d_cc_misc, 2));
+        VC_TRY(ensure(ctx, ctx->d_cc_thr, 1));
+        VC_TRY(ensure(ctx, ctx->d_cc_rec, cur.records.cap));
+        // 1 survivors before each word: popcounts per 64 words, their scan, the wave scan inside each group
+        const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), block(kCcBlock);
+        hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_cc_cnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_cc_cnt.ptr, wgroups, ctx->d_cc_off.ptr, ctx->d_cc_bsum.ptr, ctx->d_cc_boff.ptr,
+                           ctx->h_cc + 1));
+        hipLaunchKernelGGL(k_cc_woff, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
+                           (const uint32_t *)ctx->d_cc_off.ptr, (const uint64_t *)ctx->d_cc_boff.ptr, ctx->d_cc_woff.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        CcParams p;
+        memset(&p, 0, sizeof p);
+        p.records = cur.records.ptr;
+        p.words = cur.words.ptr;
+        p.woff = ctx->d_cc_woff.ptr;
+        p.parent = ctx->d_cc_parent.ptr;
+        p.label = ctx->d_cc_label.ptr;
+        p.cid = ctx->d_cc_cid.ptr;
+        p.S = S0;
+        p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
+        // 2-4 runs, unions across runs, compression
+        const dim3 sgrid((uint32_t)((S0 + kCcBlock - 1) / kCcBlock));
+        hipLaunchKernelGGL(k_cc_init, sgrid, block, 0, ctx->stream, p);
+        if (connectivity == 6) hipLaunchKernelGGL(k_cc_union<6>, sgrid, block, 0, ctx->stream, p);
+        else if (connectivity == 18) hipLaunchKernelGGL(k_cc_union<18>, sgrid, block, 0, ctx->stream, p);
+        else hipLaunchKernelGGL(k_cc_union<26>, sgrid, block, 0, ctx->stream, p);
+        hipLaunchKernelGGL(k_cc_compress, sgrid, block, 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+        // 6 the roots, compacted stably: the component list in ascending label
+        hipLaunchKernelGGL(k_cc_count<true>, dim3(rgroups), block, 0, ctx->stream, p, ctx->d_cc_cnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_cc_cnt.ptr, rgroups, ctx->d_cc_off.ptr, ctx->d_cc_bsum.ptr, ctx->d_cc_boff.ptr,
+                           ctx->h_cc + 0));
+        VC_TRY(ensure(ctx, ctx->d_cc_roots, (size_t)S0));        // (K <= S0: sized before the count is known)
+        hipLaunchKernelGGL(k_cc_scatter<true>, dim3(rgroups), block, 0, ctx->stream, p, (const uint32_t *)ctx->d_cc_off.ptr,
+                           (const uint64_t *)ctx->d_cc_boff.ptr, ctx->d_cc_roots.ptr, (uint64_t *)nullptr);
+        VC_HIP(ctx, hipGetLastError());
+        // the one read-back before the end: the number of components sizes their arrays
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const uint64_t K64 = ctx->h_cc[0];
+        if (K64 == 0 || K64 > S0)
+            return fail(ctx, VC_ERR_HIP, "vc_hull_components: %llu components among %llu survivors", (unsigned long long)K64,
+                        (unsigned long long)S0);
+        K = (uint32_t)K64;
+        VC_TRY(ensure(ctx, ctx->d_cc_size, K));
+        VC_TRY(ensure(ctx, ctx->d_cc_box, (size_t)K * 6));
+        VC_TRY(ensure(ctx, ctx->d_cc_kept, K));
+        VC_TRY(ensure(ctx, ctx->d_cc_comp, (size_t)K * kCcCompWords));
+        p.roots = ctx->d_cc_roots.ptr;
+        p.size = ctx->d_cc_size.ptr;
+        p.box = ctx->d_cc_box.ptr;
+        p.kept = ctx->d_cc_kept.ptr;
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_cc_misc.ptr, 0, 2 * sizeof(uint32_t), ctx->stream));
+        // 5 sizes and boxes; 7 the keep rule
+        hipLaunchKernelGGL(k_cc_clear, dim3((K + kCcBlock - 1) / kCcBlock), block, 0, ctx->stream, p, K);
+        hipLaunchKernelGGL(k_cc_stats, dim3(rgroups), block, 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+        const uint32_t want = keep_largest < K ? keep_largest : 0u;             // keep_largest >= K: no component is out of rank
+        hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(kCcSelectBlock), 0, ctx->stream, (const uint32_t *)p.size, K, want, ctx->d_cc_thr.ptr);
+        hipLaunchKernelGGL(k_cc_mark, dim3((K + kCcBlock - 1) / kCcBlock), block, 0, ctx->stream, p, K, min_voxels,
+                           (const uint64_t *)ctx->d_cc_thr.ptr, ctx->d_cc_kept.ptr, ctx->d_cc_comp.ptr, ctx->d_cc_misc.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        // 8 stable compaction of the kept records into the second buffer (the dropped ones leave the words), which then
+        // becomes the step's
+        hipLaunchKernelGGL(k_cc_count<false>, dim3(rgroups), block, 0, ctx->stream, p, ctx->d_cc_cnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_cc_cnt.ptr, rgroups, ctx->d_cc_off.ptr, ctx->d_cc_bsum.ptr, ctx->d_cc_boff.ptr,
+                           ctx->h_cc + 1));
+        hipLaunchKernelGGL(k_cc_scatter<false>, dim3(rgroups), block, 0, ctx->stream, p, (const uint32_t *)ctx->d_cc_off.ptr,
+                           (const uint64_t *)ctx->d_cc_boff.ptr, (uint32_t *)nullptr, ctx->d_cc_rec.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
+        const uint32_t nscan = (rgroups + kScanBlock - 1) / kScanBlock;
+        const uint64_t n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
+        const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
+        VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_cc_boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                                   ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_cc + 2, ctx->d_cc_misc.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t kept_components = 0, largest = 0;
+    if (S0) {
+        std::swap(cur.records, ctx->d_cc_rec);
+        kept_records = ctx->h_cc[1];
+        kept_components = (uint32_t)ctx->h_cc[2];
+        largest = (uint32_t)(ctx->h_cc[2] >> 32);
+        cur.nz_valid = false;                    // non-zero word counts per group: counted again by the next packing
+        ctx->survivors = cur.survivors = kept_records;
+        ctx->gathered = false; ctx->packed = false;
+        if (kept_records > S0 || kept_components > K)
+            return fail(ctx, VC_ERR_HIP, "vc_hull_components: kept %llu of %llu records, %u of %u components", (unsigned long long)kept_records,
+                        (unsigned long long)S0, kept_components, K);
+    }
+    VC_HIP(ctx, hipEventElapsedTime(&stats->components_ms, ctx->ev[0], ctx->ev[1]));
+    stats->components = K;
+    stats->components_kept = kept_components;
+    stats->survivors_before = S0;
+    stats->survivors_after = kept_records;
+    stats->largest = largest;
+    ctx->cc_valid = true;
+    ctx->cc_n = S0;
+    ctx->cc_k = K;
+    return VC_OK;
+}
+
+int vc_fetch_component_labels(vc_ctx *ctx, uint32_t *labels)
+{
+    if (!ctx || !labels) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->cc_valid) return fail(ctx, VC_ERR_ARG, "no component labels: call vc_hull_components on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->cc_n) VC_HIP(ctx, hipMemcpy(labels, ctx->d_cc_label.ptr, (size_t)ctx->cc_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_components(vc_ctx *ctx, vc_component_t *out)
+{
+    if (!ctx || !out) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->cc_valid) return fail(ctx, VC_ERR_ARG, "no components: call vc_hull_components on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    static_assert(sizeof(vc_component_t) == kCcCompWords * sizeof(uint32_t), "vc_component_t is the device's entry");
+    if (ctx->cc_k) VC_HIP(ctx, hipMemcpy(out, ctx->d_cc_comp.ptr, (size_t)ctx->cc_k * sizeof(vc_component_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 

@@ -458,6 +458,37 @@ class CarveEngine:
         self._check(self._L.vc_fetch_photo_rounds(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_photo_rounds")
         return out
 
+    # -- connected components of the hull (vc_hull_components) ------------------------------------------------------------------
+    def filter_components(self, connectivity=26, min_voxels=0, keep_largest=0):
+        """Labels the connected components of the current carve result (face / + edge / + corner neighbours for connectivity 6 /
+        18 / 26) and removes the survivors of every component smaller than min_voxels or, when keep_largest > 0, not among the
+        keep_largest largest (size descending, then label ascending) -- contract: include/voxcarve.h.  The records, the count
+        and the occupancy then describe the kept survivors; the next carve restores the visual hull.  Returns the stats as a
+        dict: components, components_kept, survivors_before, survivors_after, largest, components_ms."""
+        st = _lib.VcComponentStats()
+        self._check(self._L.vc_hull_components(self._ctx, int(connectivity), int(min_voxels), int(keep_largest), 0,
+                                               ctypes.byref(st)), "vc_hull_components")
+        self.count = int(st.survivors_after)
+        self._cc_n, self._cc_k = int(st.survivors_before), int(st.components)
+        return {"components": int(st.components), "components_kept": int(st.components_kept),
+                "survivors_before": int(st.survivors_before), "survivors_after": int(st.survivors_after),
+                "largest": int(st.largest), "components_ms": float(st.components_ms)}
+
+    def fetch_component_labels(self):
+        """u32 [survivors_before]: per record of the last filter_components' input, in its order, the label of its component
+        (the smallest linear index in it)."""
+        out = np.empty(getattr(self, "_cc_n", 0), dtype=np.uint32)
+        self._check(self._L.vc_fetch_component_labels(self._ctx, _ptr(out, ctypes.c_uint32)), "vc_fetch_component_labels")
+        return out
+
+    def fetch_components(self):
+        """The components of the last filter_components in ascending label: dict of numpy arrays label u32 [K], size u32 [K],
+        lo / hi u32 [K, 3] (inclusive box in (ix, iy, iz)), kept bool [K]."""
+        raw = np.empty((getattr(self, "_cc_k", 0), 10), dtype=np.uint32)
+        self._check(self._L.vc_fetch_components(self._ctx, raw.ctypes.data_as(ctypes.c_void_p)), "vc_fetch_components")
+        return {"label": raw[:, 0].copy(), "size": raw[:, 1].copy(), "lo": raw[:, 2:5].copy(), "hi": raw[:, 5:8].copy(),
+                "kept": raw[:, 8] != 0}
+
     def marching_cubes(self, volume=None, level=0.0, axes="reference"):
         """Triangle mesh of an ON/OFF volume on the device -> (verts float32 [V, 3], faces uint32 [F, 3]).
         volume: 3-D boolean array (what the reference hands to skimage.measure.marching_cubes, voxel_reconstruction.py:141);
