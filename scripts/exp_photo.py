@@ -4,8 +4,9 @@ pit standing on the floor in front of them, default bounds), and 16 ring cameras
 volume centre).  Per configuration: survivors before and after, rounds, whether the loop converged, photo_ms (HIP events around
 the whole call, median of the repetitions), ms per round, the host clock around the call, and one vc_color_visible pass over the
 visual hull of the same frame set for comparison (vc_timing_t::visible_ms).  Run it under
-`rocprofv3 --kernel-trace --stats -- python scripts/exp_photo.py` for the kernels one by one (the compaction is k_photo_count,
-k_scan_groups / k_scan_blocks and k_photo_scatter); --out FILE keeps the numbers as JSON.  Needs an MI355X."""
+`rocprofv3 --kernel-trace --stats -- python scripts/exp_photo.py` for the kernels one by one (the compaction is
+k_compact_count<PhotoKept>, k_scan_groups / k_scan_blocks and k_compact_scatter<PhotoKept>); --out FILE keeps the numbers as JSON.
+Needs an MI355X."""
 import json
 import os
 import sys

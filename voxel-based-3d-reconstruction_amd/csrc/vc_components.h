@@ -13,27 +13,24 @@
 //                    predecessor in its column is occupied in the same word: the record before it in the run has made that
 //                    union already
 //   k_cc_compress    lane = record: parent[s] = root, label[s] = the root's linear index (the smallest of the component)
-//   k_cc_count<R>    workgroup = kCcGroup records: roots (R) or kept records (!R; the dropped ones leave their word)
-//   k_cc_scatter<R>  the same records, stably to their scanned positions: the root list (ascending label) and cid[root], or
-//                    the kept records
+//   k_compact_count<CcRoots>, k_compact_scatter<CcRoots>   (vc_compact.h) the root list (ascending label) and cid[root]
 //   k_cc_clear       lane = component: size 0, empty box
-//   k_cc_stats       workgroup = kCcGroup records: size and box of each component by integer atomics, reduced over a lane's
+//   k_cc_stats       workgroup = kCompactGroup records: size and box of each component by integer atomics, reduced over a lane's
 //                    records, then a wave, then the workgroup while they lie in one component (the body holds nearly every
 //                    voxel: unreduced atomics would all hit one address)
 //   k_cc_select      one workgroup: radix select of the keep_largest-th key, key = size << 32 | ~k (size descending, then
 //                    label ascending; unique)
 //   k_cc_mark        lane = component: the keep rule, the vc_component_t entry, the kept count and the largest size
+//   k_compact_count<CcKept>, k_compact_scatter<CcKept>     the kept records, stably (the dropped ones leave their word)
 // Parents only ever decrease (parent[s] <= s, inside s's set), so every root is its component's first record whatever order
 // the unions run in: labels, lists and boxes are exact and bit-reproducible.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "vc_compact.h"          // kCompactGroup, k_compact_count, k_compact_scatter (vc_kernels.h: decompose, uf_*, wave_*)
 
 namespace vc {
 
 constexpr uint32_t kCcBlock = 256;
-constexpr uint32_t kCcPer = 16;                              // records per lane in the count / scatter kernels
-constexpr uint32_t kCcGroup = kCcBlock * kCcPer;             // records per compaction group (<= 4096: the scan's u32 block sums hold)
+static_assert(kCcBlock * kCompactPer == kCompactGroup, "k_cc_stats takes the compaction's groups");
 constexpr uint32_t kCcSelectBlock = 1024;
 constexpr uint32_t kCcCompWords = 10;                        // u32 per vc_component_t
 
@@ -57,51 +54,6 @@ __device__ __forceinline__ uint32_t cc_load(const uint32_t *a, uint32_t s)
     return __hip_atomic_load(a + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__device__ __forceinline__ uint32_t cc_find(const uint32_t *parent, uint32_t a)
-{
-    uint32_t n = cc_load(parent, a);
-    while (n != a) {
-        a = n;
-        n = cc_load(parent, a);
-    }
-    return a;
-}
-
-// The smaller root wins (atomic min): parents only decrease, and the result does not depend on the order of the unions.
-__device__ __forceinline__ void cc_union(uint32_t *parent, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
-__device__ __forceinline__ uint32_t cc_wave_sum(uint32_t x)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d);
-    return x;
-}
-
-__device__ __forceinline__ uint32_t cc_wave_min(uint32_t x)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x = min(x, (uint32_t)__shfl_xor((int)x, d));
-    return x;
-}
-
-__device__ __forceinline__ uint32_t cc_wave_max(uint32_t x)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, d));
-    return x;
-}
-
 __device__ __forceinline__ uint64_t cc_below(uint32_t b) { return (1ull << b) - 1ull; }    // b < 64
 
 // wave g of the grid: words 64 g .. 64 g + 63, one per lane
@@ -111,7 +63,7 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_wcount(const uint64_t *__restri
     const uint32_t g = blockIdx.x * (kCcBlock / 64) + (threadIdx.x >> 6);
     if (g >= ngroups) return;                                    // (whole waves)
     const uint64_t w = (uint64_t)g * 64 + (threadIdx.x & 63u);
-    const uint32_t c = cc_wave_sum(w < nwords ? (uint32_t)__popcll(words[w]) : 0u);
+    const uint32_t c = wave_sum_u32(w < nwords ? (uint32_t)__popcll(words[w]) : 0u);
     if ((threadIdx.x & 63u) == 0) cnt[g] = c;
 }
 
@@ -178,7 +130,7 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_union(const CcParams p)
                 if (!((wj >> bj) & 1ull)) continue;
                 // the record before s in its run has neighbour j - 1 at the same offset; when j - 1 is in j's run that union is made
                 if (inrun && (dz != 0 || dx != 0) && bj != 0 && jy != 0 && ((wj >> (bj - 1)) & 1ull)) continue;
-                cc_union(p.parent, (uint32_t)s, p.woff[j >> 6] + (uint32_t)__popcll(wj & cc_below(bj)));
+                uf_union(p.parent, (uint32_t)s, p.woff[j >> 6] + (uint32_t)__popcll(wj & cc_below(bj)));
             }
 }
 
@@ -186,91 +138,36 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_compress(const CcParams p)
 {
     const uint64_t s = (uint64_t)blockIdx.x * kCcBlock + threadIdx.x;
     if (s >= p.S) return;
-    const uint32_t r = cc_find(p.parent, (uint32_t)s);
+    const uint32_t r = uf_find(p.parent, (uint32_t)s);
     p.parent[s] = r;                                             // (a valid ancestor for every concurrent find)
     p.label[s] = (uint32_t)p.records[r];
 }
 
-__device__ __forceinline__ bool cc_pick(const CcParams &p, uint64_t s, bool roots)
-{
-    if (roots) return p.parent[s] == (uint32_t)s;
-    return p.kept[p.cid[p.parent[s]]] != 0;
-}
+// Selectors of the compactions (vc_compact.h).  The roots, stably: roots[k] = s and cid[s] = k for the k-th root s.
+struct CcRoots {
+    const uint32_t *parent;
+    uint32_t *roots, *cid;
+    __device__ bool pick(uint64_t s) const { return parent[s] == (uint32_t)s; }
+    __device__ void drop(uint64_t) const {}
+    __device__ void put(uint64_t s, uint64_t d) const { roots[d] = (uint32_t)s; cid[s] = (uint32_t)d; }
+};
 
-// lane t of workgroup g looks at records g kCcGroup + r kCcBlock + t, r = 0 .. kCcPer - 1 (coalesced).  !ROOTS: the records
-// that are dropped leave their occupancy word (64-bit atomicAnd: neighbours share words).
-template <bool ROOTS>
-__global__ __launch_bounds__(kCcBlock) void k_cc_count(const CcParams p, uint32_t *__restrict__ cnt)
-{
-    __shared__ uint32_t s_wave[kCcBlock / 64];
-    const uint32_t t = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * kCcGroup;
-    uint32_t n = 0;
-#pragma unroll 4
-    for (uint32_t r = 0; r < kCcPer; ++r) {
-        const uint64_t s = base + (uint64_t)r * kCcBlock + t;
-        if (s >= p.S) continue;
-        if (cc_pick(p, s, ROOTS)) {
-            n += 1;
-        } else if (!ROOTS) {
-            const uint32_t i = (uint32_t)p.records[s];
-            atomicAnd((unsigned long long *)(p.words + (i >> 6)), ~(1ull << (i & 63u)));
-        }
+// The records of the kept components, copied to out; a dropped record leaves its occupancy word (64-bit atomicAnd: neighbours
+// share words).
+struct CcKept {
+    const uint32_t *parent, *cid;
+    const uint8_t *kept;
+    const uint64_t *records;
+    uint64_t *words;
+    uint64_t *out;
+    __device__ bool pick(uint64_t s) const { return kept[cid[parent[s]]] != 0; }
+    __device__ void drop(uint64_t s) const
+    {
+        const uint32_t i = (uint32_t)records[s];
+        atomicAnd((unsigned long long *)(words + (i >> 6)), ~(1ull << (i & 63u)));
     }
-    const uint32_t w = cc_wave_sum(n);
-    if ((t & 63u) == 0) s_wave[t >> 6] = w;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t total = 0;
-        for (uint32_t k = 0; k < kCcBlock / 64; ++k) total += s_wave[k];
-        cnt[blockIdx.x] = total;
-    }
-}
-
-// The picked records of workgroup g go to boff[g / kScanBlock] + off[g] + (picked records of the group before them): order is
-// r-major, then wave, then lane, which is ascending s -- the compaction is stable.  ROOTS: roots[k] = s and cid[s] = k;
-// otherwise out[k] = records[s].
-template <bool ROOTS>
-__global__ __launch_bounds__(kCcBlock) void k_cc_scatter(const CcParams p, const uint32_t *__restrict__ off,
-                                                          const uint64_t *__restrict__ boff, uint32_t *__restrict__ roots,
-                                                          uint64_t *__restrict__ out)
-{
-    __shared__ uint32_t s_pos[kCcPer][kCcBlock / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * kCcGroup;
-    uint32_t pick = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kCcPer; ++r) {
-        const uint64_t s = base + (uint64_t)r * kCcBlock + t;
-        const bool k = s < p.S && cc_pick(p, s, ROOTS);
-        pick |= (uint32_t)k << r;
-        const uint64_t b = __ballot(k);
-        if (lane == 0) s_pos[r][wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-    if (t == 0) {                                                // exclusive scan over (r, wave), r-major
-        uint32_t run = 0;
-        for (uint32_t r = 0; r < kCcPer; ++r)
-            for (uint32_t w = 0; w < kCcBlock / 64; ++w) { const uint32_t v = s_pos[r][w]; s_pos[r][w] = run; run += v; }
-    }
-    __syncthreads();
-    const uint64_t o = boff[blockIdx.x / kScanBlock] + off[blockIdx.x];
-    const uint64_t below = cc_below(lane);
-#pragma unroll
-    for (uint32_t r = 0; r < kCcPer; ++r) {
-        const bool k = (pick >> r) & 1u;
-        const uint64_t b = __ballot(k);
-        if (!k) continue;
-        const uint64_t s = base + (uint64_t)r * kCcBlock + t;
-        const uint64_t d = o + s_pos[r][wave] + (uint32_t)__popcll(b & below);
-        if (ROOTS) {
-            roots[d] = (uint32_t)s;
-            p.cid[s] = (uint32_t)d;
-        } else {
-            out[d] = p.records[s];
-        }
-    }
-}
+    __device__ void put(uint64_t s, uint64_t d) const { out[d] = records[s]; }
+};
 
 __global__ __launch_bounds__(kCcBlock) void k_cc_clear(const CcParams p, uint32_t K)
 {
@@ -298,16 +195,16 @@ __device__ __forceinline__ void cc_flush(const CcParams &p, uint32_t k, uint32_t
 }
 
 // Component sizes and boxes (size zeroed, box lo at 0xffffffff, hi at 0 beforehand).  Workgroup g takes records
-// g kCcGroup + r kCcBlock + t, r = 0 .. kCcPer - 1; a lane sums while its records stay in one component, a wave whose lanes
+// g kCompactGroup + r kCcBlock + t, r = 0 .. kCompactPer - 1; a lane sums while its records stay in one component, a wave whose lanes
 // all hold the same one reduces, and the workgroup's waves that agree merge in LDS: the body, which holds nearly every
 // voxel, takes one set of atomics per workgroup (unreduced, every record's atomics would hit one address).
 __global__ __launch_bounds__(kCcBlock) void k_cc_stats(const CcParams p)
 {
     __shared__ uint32_t s_k[kCcBlock / 64], s_v[kCcBlock / 64][7];
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * kCcGroup;
+    const uint64_t base = (uint64_t)blockIdx.x * kCompactGroup;
     uint32_t kc = 0xffffffffu, n = 0, lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0, 0, 0};
-    for (uint32_t r = 0; r < kCcPer; ++r) {
+    for (uint32_t r = 0; r < kCompactPer; ++r) {
         const uint64_t s = base + (uint64_t)r * kCcBlock + t;
         if (s >= p.S) break;
         const uint32_t k = p.cid[p.parent[s]];
@@ -323,16 +220,16 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_stats(const CcParams p)
         for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], c[a]); hi[a] = max(hi[a], c[a]); }
     }
     // lanes without records hold n = 0 and neutral values: they agree with any component
-    const uint32_t k0 = cc_wave_min(n ? kc : 0xffffffffu);
+    const uint32_t k0 = wave_min_u32(n ? kc : 0xffffffffu);
     const bool uniform = __ballot(n != 0 && kc != k0) == 0;
     if (!uniform) {
         cc_flush(p, kc, n, lo, hi);
         if (lane == 0) s_k[wave] = 0xffffffffu;
     } else {
-        const uint32_t wn = cc_wave_sum(n);
+        const uint32_t wn = wave_sum_u32(n);
         uint32_t wl[3], wh[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { wl[a] = cc_wave_min(lo[a]); wh[a] = cc_wave_max(hi[a]); }
+        for (int a = 0; a < 3; ++a) { wl[a] = wave_min_u32(lo[a]); wh[a] = wave_max_u32(hi[a]); }
         if (lane == 0) {
             s_k[wave] = wn ? k0 : 0xffffffffu;
             s_v[wave][0] = wn;
@@ -420,7 +317,7 @@ __global__ __launch_bounds__(kCcBlock) void k_cc_mark(const CcParams p, uint32_t
         c[9] = 0u;
     }
     const uint32_t n = (uint32_t)__popcll(__ballot(keep));
-    const uint32_t m = cc_wave_max(sz);
+    const uint32_t m = wave_max_u32(sz);
     if ((threadIdx.x & 63u) == 0) {
         if (n) atomicAdd(misc + 0, n);
         if (m) atomicMax(misc + 1, m);

@@ -20,8 +20,7 @@
 // (area attributed to a root, half units), tot (subtree sum of own; then the root's output code), par (parent of a root).
 // Everything runs on one stream without host synchronisation; counts of components never leave the device.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdint>
+#include "vc_kernels.h"          // uf_find, uf_union
 
 namespace vc {
 
@@ -45,35 +44,6 @@ __device__ __forceinline__ bool fill_fg(const uint8_t *m, const FillParams &p, u
     const uint32_t y = q / p.Wp, x = q - y * p.Wp;
     if (y == 0 || x == 0 || y > p.H || x > p.W) return false;
     return m[(size_t)(y - 1) * p.W + (x - 1)] != 0;
-}
-
-__device__ __forceinline__ uint32_t fill_find(uint32_t *L, uint32_t a)
-{
-    uint32_t n = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (n != a) {
-        a = n;
-        n = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return a;
-}
-
-// Union of the sets of a and b; the smaller root wins (atomic min), so the final labels do not depend on the order.
-__device__ __forceinline__ void fill_union(uint32_t *L, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = fill_find(L, a);
-        b = fill_find(L, b);
-        if (a == b) return;
-        if (a < b) {
-            const uint32_t old = atomicMin(&L[b], a);
-            if (old == b) return;
-            b = old;
-        } else {
-            const uint32_t old = atomicMin(&L[a], b);
-            if (old == a) return;
-            a = old;
-        }
-    }
 }
 
 // Every padded pixel its own set; the area planes cleared.
@@ -100,34 +70,6 @@ __device__ __forceinline__ bool fill_same(const uint8_t *m, const FillParams &p,
     return fill_fg(m, p, gy * p.Wp + gx) == f;
 }
 
-__device__ __forceinline__ uint32_t lds_find(uint32_t *S, uint32_t a)
-{
-    uint32_t n = __hip_atomic_load(&S[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (n != a) {
-        a = n;
-        n = __hip_atomic_load(&S[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return a;
-}
-
-__device__ __forceinline__ void lds_union(uint32_t *S, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = lds_find(S, a);
-        b = lds_find(S, b);
-        if (a == b) return;
-        if (a < b) {
-            const uint32_t old = atomicMin(&S[b], a);
-            if (old == b) return;
-            b = old;
-        } else {
-            const uint32_t old = atomicMin(&S[a], b);
-            if (old == a) return;
-            a = old;
-        }
-    }
-}
-
 // Grid (ceil(Wp / kTile), ceil(Hp / kTile), cams), kFillBlock lanes.
 __global__ __launch_bounds__(kFillBlock) void k_fill_local(const FillParams p)
 {
@@ -140,18 +82,18 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_local(const FillParams p)
     __syncthreads();
     if (valid) {
         const bool f = fill_fg(m, p, gy * p.Wp + gx);
-        if (lx > 0 && fill_same(m, p, gy, gx - 1, f)) lds_union(S, t, t - 1);
+        if (lx > 0 && fill_same(m, p, gy, gx - 1, f)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(S, t, t - 1);
         if (ly > 0) {
-            if (fill_same(m, p, gy - 1, gx, f)) lds_union(S, t, t - kTile);
+            if (fill_same(m, p, gy - 1, gx, f)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(S, t, t - kTile);
             if (f) {
-                if (lx > 0 && fill_fg(m, p, (gy - 1) * p.Wp + gx - 1)) lds_union(S, t, t - kTile - 1);
-                if (lx + 1 < kTile && gx + 1 < p.Wp && fill_fg(m, p, (gy - 1) * p.Wp + gx + 1)) lds_union(S, t, t - kTile + 1);
+                if (lx > 0 && fill_fg(m, p, (gy - 1) * p.Wp + gx - 1)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(S, t, t - kTile - 1);
+                if (lx + 1 < kTile && gx + 1 < p.Wp && fill_fg(m, p, (gy - 1) * p.Wp + gx + 1)) uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(S, t, t - kTile + 1);
             }
         }
     }
     __syncthreads();
     if (!valid) return;
-    const uint32_t r = lds_find(S, t), ry = r / kTile, rx = r - ry * kTile;
+    const uint32_t r = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(S, t), ry = r / kTile, rx = r - ry * kTile;
     p.lab[(size_t)blockIdx.z * p.Np + gy * p.Wp + gx] = (blockIdx.y * kTile + ry) * p.Wp + blockIdx.x * kTile + rx;
 }
 
@@ -167,12 +109,12 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_merge(const FillParams p)
     const uint8_t *m = p.mask + (size_t)blockIdx.z * p.H * p.W;
     uint32_t *L = p.lab + (size_t)blockIdx.z * p.Np;
     const bool f = fill_fg(m, p, q);
-    if (lx == 0 && x > 0 && fill_fg(m, p, q - 1) == f) fill_union(L, q, q - 1);
+    if (lx == 0 && x > 0 && fill_fg(m, p, q - 1) == f) uf_union(L, q, q - 1);
     if (y > 0) {
-        if (ly == 0 && fill_fg(m, p, q - p.Wp) == f) fill_union(L, q, q - p.Wp);
+        if (ly == 0 && fill_fg(m, p, q - p.Wp) == f) uf_union(L, q, q - p.Wp);
         if (f) {
-            if ((ly == 0 || lx == 0) && x > 0 && fill_fg(m, p, q - p.Wp - 1)) fill_union(L, q, q - p.Wp - 1);
-            if ((ly == 0 || lx == kTile - 1) && x + 1 < p.Wp && fill_fg(m, p, q - p.Wp + 1)) fill_union(L, q, q - p.Wp + 1);
+            if ((ly == 0 || lx == 0) && x > 0 && fill_fg(m, p, q - p.Wp - 1)) uf_union(L, q, q - p.Wp - 1);
+            if ((ly == 0 || lx == kTile - 1) && x + 1 < p.Wp && fill_fg(m, p, q - p.Wp + 1)) uf_union(L, q, q - p.Wp + 1);
         }
     }
 }
@@ -183,7 +125,7 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_compress(const FillParams p
     const uint32_t q = blockIdx.x * kFillBlock + threadIdx.x;
     if (q >= p.Np) return;
     uint32_t *L = p.lab + (size_t)blockIdx.z * p.Np;
-    const uint32_t r = fill_find(L, q);
+    const uint32_t r = uf_find(L, q);
     __hip_atomic_store(&L[q], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

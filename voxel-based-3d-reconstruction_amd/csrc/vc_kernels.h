@@ -1050,6 +1050,34 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
     return v;
 }
 
+// Union-find over a forest of u32 parents, SCOPE = __HIP_MEMORY_SCOPE_AGENT in global memory, __HIP_MEMORY_SCOPE_WORKGROUP in
+// LDS.  A union links the larger root under the smaller (atomic min): parents only decrease (every parent <= its index, inside
+// its set), so every root is its set's minimum whatever order the unions run in.
+template <int SCOPE = __HIP_MEMORY_SCOPE_AGENT>
+__device__ __forceinline__ uint32_t uf_find(const uint32_t *parent, uint32_t a)
+{
+    uint32_t n = __hip_atomic_load(parent + a, __ATOMIC_RELAXED, SCOPE);
+    while (n != a) {
+        a = n;
+        n = __hip_atomic_load(parent + a, __ATOMIC_RELAXED, SCOPE);
+    }
+    return a;
+}
+
+template <int SCOPE = __HIP_MEMORY_SCOPE_AGENT>
+__device__ __forceinline__ void uf_union(uint32_t *parent, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = uf_find<SCOPE>(parent, a);
+        b = uf_find<SCOPE>(parent, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = __hip_atomic_fetch_min(parent + a, b, __ATOMIC_RELAXED, SCOPE);
+        if (old == a) return;
+        a = old;
+    }
+}
+
 // TILE: thread t is element t % 64 of tile word t / 64 (4 x-rows x 16 y) instead of linear voxel t, so the
 // boxes (and the table, when one is asked for) come out in tile order.  lut or bbox may be null: the
 // table-free kernel only wants the boxes.

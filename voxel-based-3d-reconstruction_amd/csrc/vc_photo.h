@@ -8,18 +8,18 @@
 //   k_photo_test    lane = surface survivor: the visibility test of k_vis_color, integer sums and sums of squares of the visible
 //                   cameras' RGB, the variance test; a removed voxel gets rounds[s] = r and its bit leaves its word (64-bit
 //                   atomicAnd: face neighbours share words); one atomic per workgroup on the round's removal counter
-//   k_photo_count   workgroup = kPhotoGroup records: how many are kept (rounds[s] == 0)
-//   k_photo_scatter the same records, the kept ones to their scanned positions in record order (stable compaction)
+//   k_compact_count<PhotoKept>, k_compact_scatter<PhotoKept>   (vc_compact.h) the kept records (rounds[s] == 0) to their
+//                   scanned positions in record order (stable compaction)
 // Jacobi: the words are read only by k_vis_surface, which runs before the round's tests; the removals of round r are first seen
 // by the surface test of round r + 1.  The maps, the list and the tests never depend on the order in which lanes run.
 #pragma once
-#include "vc_visible.h"          // VisParams, kVisBlock, kVisSurfPer
+#include "vc_compact.h"          // k_compact_count, k_compact_scatter
+#include "vc_visible.h"          // VisParams, kVisBlock
 
 #pragma clang fp contract(off)
 
 namespace vc {
 
-constexpr uint32_t kPhotoGroup = kVisBlock * kVisSurfPer;    // records per compaction group (<= 4096: the scan's u32 block sums hold)
 constexpr uint32_t kPhotoMaxRounds = 255;                    // rounds[] is u8
 
 struct PhotoParams {
@@ -30,13 +30,6 @@ struct PhotoParams {
     uint32_t min_views;         // m
     uint32_t round;             // r, 1-based
 };
-
-__device__ __forceinline__ uint32_t photo_wave_sum(uint32_t x)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d);
-    return x;
-}
 
 __global__ __launch_bounds__(kVisBlock) void k_photo_test(const VisParams p, const PhotoParams q)
 {
@@ -79,7 +72,7 @@ __global__ __launch_bounds__(kVisBlock) void k_photo_test(const VisParams p, con
         }
     }
     const uint32_t t = threadIdx.x;
-    const uint32_t w = photo_wave_sum(gone);
+    const uint32_t w = wave_sum_u32(gone);
     if ((t & 63u) == 0) s_wave[t >> 6] = w;
     __syncthreads();
     if (t == 0) {
@@ -89,61 +82,14 @@ __global__ __launch_bounds__(kVisBlock) void k_photo_test(const VisParams p, con
     }
 }
 
-// lane t of workgroup g looks at records g kPhotoGroup + r kVisBlock + t, r = 0 .. kVisSurfPer - 1 (coalesced)
-__global__ __launch_bounds__(kVisBlock) void k_photo_count(const uint8_t *__restrict__ rounds, uint64_t S, uint32_t *__restrict__ cnt)
-{
-    __shared__ uint32_t s_wave[kVisBlock / 64];
-    const uint32_t t = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * kPhotoGroup;
-    uint32_t kept = 0;
-#pragma unroll 4
-    for (uint32_t r = 0; r < kVisSurfPer; ++r) {
-        const uint64_t s = base + (uint64_t)r * kVisBlock + t;
-        if (s < S && rounds[s] == 0) kept += 1;
-    }
-    const uint32_t w = photo_wave_sum(kept);
-    if ((t & 63u) == 0) s_wave[t >> 6] = w;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t total = 0;
-        for (uint32_t k = 0; k < kVisBlock / 64; ++k) total += s_wave[k];
-        cnt[blockIdx.x] = total;
-    }
-}
-
-// The kept records of workgroup g go to boff[g / kScanBlock] + off[g] + (kept records of the group before them): record order is
-// r-major, then wave, then lane, which is ascending s -- the compaction is stable.
-__global__ __launch_bounds__(kVisBlock) void k_photo_scatter(const uint64_t *__restrict__ records, const uint8_t *__restrict__ rounds,
-                                                             uint64_t S, const uint32_t *__restrict__ off,
-                                                             const uint64_t *__restrict__ boff, uint64_t *__restrict__ out)
-{
-    __shared__ uint32_t s_pos[kVisSurfPer][kVisBlock / 64];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    const uint64_t base = (uint64_t)blockIdx.x * kPhotoGroup;
-    uint32_t keep = 0;
-#pragma unroll
-    for (uint32_t r = 0; r < kVisSurfPer; ++r) {
-        const uint64_t s = base + (uint64_t)r * kVisBlock + t;
-        const bool k = s < S && rounds[s] == 0;
-        keep |= (uint32_t)k << r;
-        const uint64_t b = __ballot(k);
-        if (lane == 0) s_pos[r][wave] = (uint32_t)__popcll(b);
-    }
-    __syncthreads();
-    if (t == 0) {                                                // exclusive scan over (r, wave), r-major
-        uint32_t run = 0;
-        for (uint32_t r = 0; r < kVisSurfPer; ++r)
-            for (uint32_t w = 0; w < kVisBlock / 64; ++w) { const uint32_t v = s_pos[r][w]; s_pos[r][w] = run; run += v; }
-    }
-    __syncthreads();
-    const uint64_t o = boff[blockIdx.x / kScanBlock] + off[blockIdx.x];
-    const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (uint32_t r = 0; r < kVisSurfPer; ++r) {
-        const bool k = (keep >> r) & 1u;
-        const uint64_t b = __ballot(k);
-        if (k) out[o + s_pos[r][wave] + (uint32_t)__popcll(b & below)] = records[base + (uint64_t)r * kVisBlock + t];
-    }
-}
+// Selector of the compaction after the rounds: the records no round removed, copied to out
+struct PhotoKept {
+    const uint8_t *rounds;
+    const uint64_t *records;
+    uint64_t *out;
+    __device__ bool pick(uint64_t s) const { return rounds[s] == 0; }
+    __device__ void drop(uint64_t) const {}
+    __device__ void put(uint64_t s, uint64_t d) const { out[d] = records[s]; }
+};
 
 }  // namespace vc

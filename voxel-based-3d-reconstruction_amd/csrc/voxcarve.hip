@@ -36,6 +36,7 @@
 #include "vc_fg.h"
 #include "vc_contour.h"
 #include "vc_visible.h"
+#include "vc_compact.h"
 #include "vc_photo.h"
 #include "vc_components.h"
 
@@ -91,6 +92,12 @@ template <typename T>
 struct DevBuf {
     T *ptr = nullptr;
     size_t cap = 0;     // elements
+};
+
+// Scratch of one scan_counts: counts and exclusive offsets per group, sums and offsets of the scan blocks
+struct ScanBufs {
+    DevBuf<uint32_t> cnt, off;
+    DevBuf<uint64_t> bsum, boff;
 };
 
 // One resident frame set.  The uploaded bytes stay on the device (bytes / fbytes), so the derived state (bit masks,
@@ -257,8 +264,8 @@ struct vc_ctx {
     uint32_t *h_lists = nullptr;     // pinned [4]: list lengths of an earlier step, to size launches by
     // marching cubes (vc_marching_cubes)
     DevBuf<uint64_t> d_mcbits, d_mcx;
-    DevBuf<uint32_t> d_mcwbase, d_mcgv, d_mcgt, d_mcgvoff, d_mcgtoff, d_mcfaces;
-    DevBuf<uint64_t> d_mcbv, d_mcbvoff, d_mcbt, d_mcbtoff;
+    DevBuf<uint32_t> d_mcwbase, d_mcfaces;
+    ScanBufs d_mcv, d_mct;           // scans of the vertex and triangle counts per group
     DevBuf<float> d_mcverts;
     uint64_t mc_verts = 0, mc_faces = 0;
     bool mc_valid = false;
@@ -314,22 +321,22 @@ struct vc_ctx {
     bool vis_valid = false;          // the maps and masks belong to the current carve result
     int visible_check = 1;           // splats look at the stored depth before their atomic
     int visible_big_rect = 64;       // pixels above which a splat rectangle gets a workgroup of its own
-    // vc_photo_carve: round per input record, removal counter per round, compaction counts / offsets / block sums, the records'
-    // second buffer (the compaction's target, swapped with the step's), pinned scalars (removal count, compaction total)
+    // vc_photo_carve and vc_hull_components, one after the other on the context's stream: scan scratch, the records' second
+    // buffer (a compaction's target, swapped with the step's), pinned scalars (photo: [0] removal count of the round, low 32 bits,
+    // [1] compaction total; components: [0] components, [1] kept records, [2] misc = kept components | largest << 32)
+    ScanBufs d_rscan;
+    DevBuf<uint64_t> d_rec_spare;
+    uint64_t *h_res = nullptr;
+    // vc_photo_carve: round per input record, removal counter per round
     DevBuf<uint8_t> d_photo_rounds;
-    DevBuf<uint32_t> d_photo_removed, d_photo_cnt, d_photo_off;
-    DevBuf<uint64_t> d_photo_bsum, d_photo_boff, d_photo_rec;
-    uint64_t *h_photo = nullptr;     // pinned: [0] removal count of the round (low 32 bits), [1] compaction total
+    DevBuf<uint32_t> d_photo_removed;
     bool photo_valid = false;        // d_photo_rounds belongs to the photo carve that produced the current result
     uint64_t photo_n = 0;            // its input survivors
-    // vc_hull_components: word / record / root compaction counts, offsets and block sums, survivors before each word, the
-    // union-find forest, labels, component numbers of the roots, the root list, sizes, boxes, keep flags, component entries,
-    // [kept components, largest], the select threshold, the records' second buffer, pinned scalars (roots, kept records, misc)
-    DevBuf<uint32_t> d_cc_cnt, d_cc_off, d_cc_woff, d_cc_parent, d_cc_label, d_cc_cid, d_cc_roots, d_cc_size, d_cc_box, d_cc_comp,
-        d_cc_misc;
+    // vc_hull_components: survivors before each word, the union-find forest, labels, component numbers of the roots, the root
+    // list, sizes, boxes, keep flags, component entries, [kept components, largest], the select threshold
+    DevBuf<uint32_t> d_cc_woff, d_cc_parent, d_cc_label, d_cc_cid, d_cc_roots, d_cc_size, d_cc_box, d_cc_comp, d_cc_misc;
     DevBuf<uint8_t> d_cc_kept;
-    DevBuf<uint64_t> d_cc_bsum, d_cc_boff, d_cc_thr, d_cc_rec;
-    uint64_t *h_cc = nullptr;        // pinned: [0] components, [1] kept records, [2] misc (kept components | largest << 32)
+    DevBuf<uint64_t> d_cc_thr;
     bool cc_valid = false;           // labels and components belong to the pass that produced the current result
     uint64_t cc_n = 0;               // its input survivors
     uint32_t cc_k = 0;               // its components
@@ -352,10 +359,8 @@ struct vc_ctx {
     uint64_t gexpect[2] = {0, 0};
     uint32_t gseq = 0;               // compact gathers issued
     DevBuf<uint64_t> d_ent_all[2];
-    DevBuf<uint32_t> d_xcnt, d_xoff;         // scan scratch of the pack pass ...
-    DevBuf<uint64_t> d_xbsum, d_xboff;
-    DevBuf<uint32_t> d_ycnt, d_yoff;         // ... and of the expansion, which may run on the second stream beside a pack
-    DevBuf<uint64_t> d_ybsum, d_yboff;
+    ScanBufs d_xscan;                        // scan scratch of the pack pass ...
+    ScanBufs d_yscan;                        // ... and of the expansion, which may run on the second stream beside a pack
     uint64_t *h_xtotal = nullptr;            // pinned
     uint64_t packed_entries = 0;
     bool packed = false;
@@ -525,6 +530,11 @@ void release(DevBuf<T> &b)
     b.cap = 0;
 }
 
+void release(ScanBufs &b)
+{
+    release(b.cnt); release(b.off); release(b.bsum); release(b.boff);
+}
+
 #define VC_TRY(expr)              \
     do {                          \
         int rc_ = (expr);         \
@@ -564,6 +574,15 @@ constexpr size_t kMaxFirstLds = 64 * 1024; // static limit of one workgroup's dy
 constexpr size_t kWideGridBytes = 20 * 1024; // grids above this: 1024-thread workgroups share a copy, the brick level reads coarser blocks
 constexpr size_t kMaxWideLds = 152 * 1024; // what the brick pipeline's grid-staging kernels may take (one 1024-thread workgroup per CU)
 constexpr uint32_t kEstimateSamples = 1u << 16;
+
+int ensure(vc_ctx *ctx, ScanBufs &b, uint32_t ngroups)
+{
+    VC_TRY(ensure(ctx, b.cnt, ngroups));
+    VC_TRY(ensure(ctx, b.off, ngroups));
+    VC_TRY(ensure(ctx, b.bsum, kMaxScanBlocks));
+    VC_TRY(ensure(ctx, b.boff, kMaxScanBlocks + 1));
+    return VC_OK;
+}
 
 // The bricks' pixel boxes and the brick-major copy of the word boxes (once per grid / slab / camera set, right behind the
 // tile boxes).
@@ -901,27 +920,61 @@ int launch_emit(vc_ctx *ctx, StepBuf &sb, hipStream_t st, hipEvent_t start = nul
 }
 
 
-// counts -> exclusive offsets (two levels) on the context's stream; the total also lands in *total_host
-int scan_counts(vc_ctx *ctx, hipStream_t st, const uint32_t *cnt, uint32_t ngroups, uint32_t *off, uint64_t *bsum, uint64_t *boff,
-                uint64_t *total_host)
+// counts cnt (usually b.cnt) -> exclusive offsets b.off / b.boff (two levels) on stream st; the total also lands in *total_host and
+// in b.boff[nscan]
+int scan_counts(vc_ctx *ctx, hipStream_t st, ScanBufs &b, const uint32_t *cnt, uint32_t ngroups, uint64_t *total_host)
 {
     const uint32_t nscan = (ngroups + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(k_scan_groups, dim3(nscan), dim3(kScanThreads), 0, st, cnt, ngroups, off, bsum, boff, total_host,
+    hipLaunchKernelGGL(k_scan_groups, dim3(nscan), dim3(kScanThreads), 0, st, cnt, ngroups, b.off.ptr, b.bsum.ptr, b.boff.ptr, total_host,
                        (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u);
     VC_HIP(ctx, hipGetLastError());
     if (nscan > 1) {
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanThreads), 0, st, bsum, nscan, boff, total_host);
+        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanThreads), 0, st, b.bsum.ptr, nscan, b.boff.ptr, total_host);
         VC_HIP(ctx, hipGetLastError());
     }
     return VC_OK;
 }
 
+// Stable compaction of records [0, S) by sel (vc_compact.h) on the context's stream, in the scan scratch of the passes over the
+// result (ctx->d_rscan); the count lands in *total_host once the stream has drained, and in d_rscan.boff[nscan].
+template <class Sel>
+int compact(vc_ctx *ctx, const Sel &sel, uint64_t S, uint64_t *total_host)
+{
+    const uint32_t ngroups = (uint32_t)((S + kCompactGroup - 1) / kCompactGroup);
+    VC_TRY(ensure(ctx, ctx->d_rscan, ngroups));
+    hipLaunchKernelGGL(k_compact_count<Sel>, dim3(ngroups), dim3(kCompactBlock), 0, ctx->stream, S, ctx->d_rscan.cnt.ptr, sel);
+    VC_HIP(ctx, hipGetLastError());
+    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, ngroups, total_host));
+    hipLaunchKernelGGL(k_compact_scatter<Sel>, dim3(ngroups), dim3(kCompactBlock), 0, ctx->stream, S,
+                       (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, sel);
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
+// The records of the current result that sel keeps (sel.out: the copy's target) become the result, in record order: compacted
+// into the spare buffer, which is then swapped with the step's.  The caller sets the survivors to the count, which lands in
+// *total_host once the stream has drained.
+template <class Sel>
+int compact_records(vc_ctx *ctx, StepBuf &cur, Sel sel, uint64_t S, uint64_t *total_host)
+{
+    VC_TRY(ensure(ctx, ctx->d_rec_spare, cur.records.cap));
+    sel.out = ctx->d_rec_spare.ptr;
+    VC_TRY(compact(ctx, sel, S, total_host));
+    std::swap(cur.records, ctx->d_rec_spare);
+    // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
+    const uint32_t nscan = (uint32_t)(((S + kCompactGroup - 1) / kCompactGroup + kScanBlock - 1) / kScanBlock);
+    const uint64_t n_pad = (cur.n + kLutPad - 1) / kLutPad * kLutPad;
+    const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
+    VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_rscan.boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                               ctx->stream));
+    cur.nz_valid = false;                        // non-zero word counts per group: counted again by the next packing
+    ctx->gathered = false; ctx->packed = false;
+    return VC_OK;
+}
+
 int ensure_exchange_scratch(vc_ctx *ctx, uint32_t ngroups)
 {
-    VC_TRY(ensure(ctx, ctx->d_xcnt, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_xoff, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_xbsum, kMaxScanBlocks));
-    VC_TRY(ensure(ctx, ctx->d_xboff, kMaxScanBlocks + 1));
+    VC_TRY(ensure(ctx, ctx->d_xscan, ngroups));
     if (!ctx->h_xtotal)
         VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_xtotal), 4 * sizeof(uint64_t), hipHostMallocDefault));   // [2], [3]: the two gathers in flight
     return VC_OK;
@@ -970,19 +1023,19 @@ int enqueue_pack(vc_ctx *ctx, StepBuf &cur, hipStream_t st)
     if (cur.nz_valid && cur.busy) {
         // the carve left the counts of non-zero words and the list of groups with survivors: no counting pass, and the packing
         // strides over the list (5 of 6 groups are empty; a launch over all of them is dispatch bound)
-        VC_TRY(scan_counts(ctx, st, cur.groupnz.ptr, ngroups, ctx->d_xoff.ptr, ctx->d_xbsum.ptr, ctx->d_xboff.ptr, ctx->h_xtotal));
+        VC_TRY(scan_counts(ctx, st, ctx->d_xscan, cur.groupnz.ptr, ngroups, ctx->h_xtotal));
         hipLaunchKernelGGL(k_pack_busy, dim3(1024), block, 0, st, (const uint64_t *)cur.words.ptr, nwords, (const uint32_t *)cur.busylist.ptr,
-                           (const uint32_t *)cur.busyblock.ptr, (const uint32_t *)ctx->d_xoff.ptr, (const uint64_t *)ctx->d_xboff.ptr, nscan, ctx->i0(),
+                           (const uint32_t *)cur.busyblock.ptr, (const uint32_t *)ctx->d_xscan.off.ptr, (const uint64_t *)ctx->d_xscan.boff.ptr, nscan, ctx->i0(),
                            (const uint64_t *)(cur.blockoff.ptr + nscan), cur.ent.ptr, cur.mine.ptr);
         VC_HIP(ctx, hipGetLastError());
         return VC_OK;
     }
     hipLaunchKernelGGL(k_count_nz, grid, block, 0, st, cur.words.ptr, nwords, ngroups, cur.groupcnt.ptr,
-                       ctx->d_xcnt.ptr);
+                       ctx->d_xscan.cnt.ptr);
     VC_HIP(ctx, hipGetLastError());
-    VC_TRY(scan_counts(ctx, st, ctx->d_xcnt.ptr, ngroups, ctx->d_xoff.ptr, ctx->d_xbsum.ptr, ctx->d_xboff.ptr, ctx->h_xtotal));
-    hipLaunchKernelGGL(k_pack_entries, grid, block, 0, st, cur.words.ptr, nwords, ngroups, cur.groupcnt.ptr, ctx->d_xoff.ptr,
-                       ctx->d_xboff.ptr, nscan, ctx->i0(), cur.blockoff.ptr + nscan, cur.ent.ptr, cur.mine.ptr);
+    VC_TRY(scan_counts(ctx, st, ctx->d_xscan, ctx->d_xscan.cnt.ptr, ngroups, ctx->h_xtotal));
+    hipLaunchKernelGGL(k_pack_entries, grid, block, 0, st, cur.words.ptr, nwords, ngroups, cur.groupcnt.ptr, ctx->d_xscan.off.ptr,
+                       ctx->d_xscan.boff.ptr, nscan, ctx->i0(), cur.blockoff.ptr + nscan, cur.ent.ptr, cur.mine.ptr);
     VC_HIP(ctx, hipGetLastError());
     return VC_OK;
 }
@@ -1056,10 +1109,7 @@ int enqueue_expand(vc_ctx *ctx, hipStream_t st, const uint64_t *d_entries, uint6
     const uint32_t chunk = M <= (1ull << 24) ? 16u : kGroupWords;   // entries per wave (the scan takes 2^20 groups at most)
     const uint32_t ngroups = (uint32_t)((M + chunk - 1) / chunk);
     VC_TRY(ensure_exchange_scratch(ctx, 1));
-    VC_TRY(ensure(ctx, ctx->d_ycnt, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_yoff, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_ybsum, kMaxScanBlocks));
-    VC_TRY(ensure(ctx, ctx->d_yboff, kMaxScanBlocks + 1));
+    VC_TRY(ensure(ctx, ctx->d_yscan, ngroups));
     // (the table-free mode colours from the colour camera's table too, unless fused_color_table is off: the whole-grid table the
     // expansion of other ranks' words needs is the very one)
     const bool from_lut = (cur.mode == VC_MODE_LUT || ctx->fused_color_table) && cur.color_cam >= 0;
@@ -1068,9 +1118,9 @@ int enqueue_expand(vc_ctx *ctx, hipStream_t st, const uint64_t *d_entries, uint6
         if (st != ctx->stream) VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     const dim3 grid((ngroups + 3) / 4), block(kBlock);
-    hipLaunchKernelGGL(k_count_entries, chunk == 16u ? dim3((ngroups + 15) / 16) : grid, block, 0, st, d_entries, M, ngroups, ctx->d_ycnt.ptr, chunk);
+    hipLaunchKernelGGL(k_count_entries, chunk == 16u ? dim3((ngroups + 15) / 16) : grid, block, 0, st, d_entries, M, ngroups, ctx->d_yscan.cnt.ptr, chunk);
     VC_HIP(ctx, hipGetLastError());
-    VC_TRY(scan_counts(ctx, st, ctx->d_ycnt.ptr, ngroups, ctx->d_yoff.ptr, ctx->d_ybsum.ptr, ctx->d_yboff.ptr, h_total));
+    VC_TRY(scan_counts(ctx, st, ctx->d_yscan, ctx->d_yscan.cnt.ptr, ngroups, h_total));
     if (S_hint == 0) {
         VC_HIP(ctx, hipStreamSynchronize(st));
         S_hint = *h_total;
@@ -1089,7 +1139,7 @@ int enqueue_expand(vc_ctx *ctx, hipStream_t st, const uint64_t *d_entries, uint6
         if (s.frames.ptr && s.have_frame[cur.color_cam]) e.frame = s.frames.ptr + (size_t)cur.color_cam * ctx->H * ctx->W;
     }
     e.entries = d_entries;
-    e.groupcnt = ctx->d_ycnt.ptr; e.groupoff = ctx->d_yoff.ptr; e.blockoff = ctx->d_yboff.ptr;
+    e.groupcnt = ctx->d_yscan.cnt.ptr; e.groupoff = ctx->d_yscan.off.ptr; e.blockoff = ctx->d_yscan.boff.ptr;
     e.n = M * 64; e.i0 = 0; e.z0 = 0; e.ngroups = ngroups; e.entry_chunk = chunk;
     e.records = ctx->d_gathered.ptr; e.capacity = ctx->d_gathered.cap;
     e.lut = from_lut ? ctx->d_lut_color.ptr : nullptr;
@@ -1182,8 +1232,7 @@ int vc_destroy(vc_ctx *ctx)
     for (uint32_t r = 0; r < kStepRing; ++r)
         for (int i = 0; i < 3; ++i) if (ctx->step_ev[r][i]) (void)hipEventDestroy(ctx->step_ev[r][i]);
     release(ctx->d_axes); release(ctx->d_morph); release(ctx->d_lut); release(ctx->d_bbox); release(ctx->d_lut_tile); release(ctx->d_tbox); release(ctx->d_kbox); release(ctx->d_live); release(ctx->d_wbox); release(ctx->d_bm); release(ctx->d_blist); release(ctx->d_wlist);
-    release(ctx->d_mcbits); release(ctx->d_mcx); release(ctx->d_mcwbase); release(ctx->d_mcgv); release(ctx->d_mcgt); release(ctx->d_mcgvoff);
-    release(ctx->d_mcgtoff); release(ctx->d_mcfaces); release(ctx->d_mcbv); release(ctx->d_mcbvoff); release(ctx->d_mcbt); release(ctx->d_mcbtoff);
+    release(ctx->d_mcbits); release(ctx->d_mcx); release(ctx->d_mcwbase); release(ctx->d_mcfaces); release(ctx->d_mcv); release(ctx->d_mct);
     release(ctx->d_mcverts);
     for (StepBuf &b : ctx->sb) {
         release(b.words); release(b.groupcnt); release(b.groupoff); release(b.groupnz); release(b.blocksum); release(b.blockoff); release(b.records);
@@ -1203,18 +1252,14 @@ int vc_destroy(vc_ctx *ctx)
     for (auto &m : ctx->mog2) { release(m.state); release(m.nmodes); }
     release(ctx->d_cc);
     release(ctx->d_vis_zmap); release(ctx->d_vis_list); release(ctx->d_vis_ctr); release(ctx->d_vis_mask); release(ctx->d_vis_queue);
-    release(ctx->d_photo_rounds); release(ctx->d_photo_removed); release(ctx->d_photo_cnt); release(ctx->d_photo_off);
-    release(ctx->d_photo_bsum); release(ctx->d_photo_boff); release(ctx->d_photo_rec);
-    if (ctx->h_photo) (void)hipHostFree(ctx->h_photo);
-    release(ctx->d_cc_cnt); release(ctx->d_cc_off); release(ctx->d_cc_woff); release(ctx->d_cc_parent); release(ctx->d_cc_label);
-    release(ctx->d_cc_cid); release(ctx->d_cc_roots); release(ctx->d_cc_size); release(ctx->d_cc_box); release(ctx->d_cc_comp);
-    release(ctx->d_cc_misc); release(ctx->d_cc_kept); release(ctx->d_cc_bsum); release(ctx->d_cc_boff); release(ctx->d_cc_thr);
-    release(ctx->d_cc_rec);
-    if (ctx->h_cc) (void)hipHostFree(ctx->h_cc);
+    release(ctx->d_rscan); release(ctx->d_rec_spare);
+    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
+    release(ctx->d_photo_rounds); release(ctx->d_photo_removed);
+    release(ctx->d_cc_woff); release(ctx->d_cc_parent); release(ctx->d_cc_label); release(ctx->d_cc_cid); release(ctx->d_cc_roots);
+    release(ctx->d_cc_size); release(ctx->d_cc_box); release(ctx->d_cc_comp); release(ctx->d_cc_misc); release(ctx->d_cc_kept);
+    release(ctx->d_cc_thr);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
-    release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xcnt); release(ctx->d_xoff); release(ctx->d_xbsum);
-    release(ctx->d_xboff); release(ctx->d_lut_color);
-    release(ctx->d_ycnt); release(ctx->d_yoff); release(ctx->d_ybsum); release(ctx->d_yboff);
+    release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
     if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
     if (ctx->h_lists) (void)hipHostFree(ctx->h_lists);
     if (ctx->h_total) (void)hipHostFree(ctx->h_total);
@@ -2059,6 +2104,20 @@ int vc_fetch_viewmask(vc_ctx *ctx, uint16_t *viewmask)
     return VC_OK;
 }
 
+// The hierarchical kernels skip the words of groups without survivors (cur.sparse_words): their words are zeroed on the context's
+// stream before anything reads the words whole.
+static int densify_words(vc_ctx *ctx, StepBuf &cur)
+{
+    const uint64_t nwords = (ctx->n_voxels() + 63) / 64;
+    if (!cur.sparse_words || !nwords) return VC_OK;
+    const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
+    hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords, ngroups,
+                       cur.groupcnt.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    cur.sparse_words = false;
+    return VC_OK;
+}
+
 int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
 {
     if (!ctx || !bits) return VC_ERR_ARG;
@@ -2066,15 +2125,26 @@ int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t nwords = (ctx->n_voxels() + 63) / 64;
     StepBuf &cur = ctx->sb[ctx->cur];
-    if (nwords && cur.sparse_words) {            // the hierarchical kernels skip the words of groups without survivors
-        const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
-        hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
-                           ngroups, cur.groupcnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
+    if (cur.sparse_words) {
+        VC_TRY(densify_words(ctx, cur));
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        cur.sparse_words = false;
     }
     if (nwords) VC_HIP(ctx, hipMemcpy(bits, cur.words.ptr, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+// The refusals of every pass over the current carve result (colour, photo, components).  `what` names the call in the message,
+// `use` what the call does with the records and `multi` what it cannot do across ranks.
+static int result_refusals(vc_ctx *ctx, const char *what, const char *use, const char *multi)
+{
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "%s: no carve result", what);
+    if (ctx->sb[ctx->cur].no_records)
+        return fail(ctx, VC_ERR_ARG, "%s: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to %s", what, use);
+    if (ctx->comm && ctx->n_ranks > 1)
+        return fail(ctx, VC_ERR_ARG, "%s: a communicator of %d ranks is attached (multi-GPU %s is not supported)", what, ctx->n_ranks, multi);
+    if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
+        return fail(ctx, VC_ERR_ARG, "%s: the slab [%u,%u) is narrower than the grid's %u layers", what, ctx->z0, ctx->z1, ctx->nz);
     return VC_OK;
 }
 
@@ -2082,14 +2152,8 @@ int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
 // The refusals vc_color_visible and vc_photo_carve share; `what` names the call in the message.
 static int visible_refusals(vc_ctx *ctx, const char *what, uint32_t slot, float depth_tolerance)
 {
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "%s: no carve result", what);
-    if (ctx->sb[ctx->cur].no_records) return fail(ctx, VC_ERR_ARG, "%s: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to colour", what);
+    VC_TRY(result_refusals(ctx, what, "colour", "visibility"));
     if (!(depth_tolerance >= 0.0f)) return fail(ctx, VC_ERR_ARG, "%s: depth tolerance %g is negative or NaN", what, (double)depth_tolerance);
-    if (ctx->comm && ctx->n_ranks > 1)
-        return fail(ctx, VC_ERR_ARG, "%s: a communicator of %d ranks is attached (multi-GPU visibility is not supported)", what, ctx->n_ranks);
-    if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
-        return fail(ctx, VC_ERR_ARG, "%s: the slab [%u,%u) is narrower than the grid's %u layers", what, ctx->z0, ctx->z1, ctx->nz);
     if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks) return fail(ctx, VC_ERR_ARG, "%s: no frame set in slot %u", what, slot);
     const Slot &s = ctx->slots[slot];
     for (uint32_t c = 0; c < ctx->C; ++c)
@@ -2113,7 +2177,6 @@ static int visible_prepare(vc_ctx *ctx, Slot &s, StepBuf &cur)
 static int enqueue_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, uint64_t *records, uint64_t S, float tol, const uint8_t *rounds,
                            VisParams &p, uint32_t &lb)
 {
-    const uint64_t n = ctx->n_voxels();
     const size_t HW = (size_t)ctx->H * ctx->W, nmap = HW * ctx->C;
     VC_TRY(ensure(ctx, ctx->d_vis_zmap, nmap));
     VC_TRY(ensure(ctx, ctx->d_vis_ctr, 4));
@@ -2125,14 +2188,7 @@ static int enqueue_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, uint64_t *records
     VC_HIP(ctx, hipGetLastError());
     lb = 0;
     if (!S) return VC_OK;
-    const uint64_t nwords = (n + 63) / 64;
-    if (cur.sparse_words) {                      // the hierarchical kernels skip the words of groups without survivors
-        const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
-        hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
-                           ngroups, cur.groupcnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        cur.sparse_words = false;
-    }
+    VC_TRY(densify_words(ctx, cur));
     VC_TRY(ensure(ctx, ctx->d_vis_queue, (size_t)kVisQueue));
     memset(&p, 0, sizeof p);
     p.xs = ctx->d_axes.ptr; p.ys = p.xs + ctx->nx; p.zs = p.ys + ctx->ny;
@@ -2224,8 +2280,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
-    if (!ctx->h_photo)
-        VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_photo), 2 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     VC_TRY(visible_prepare(ctx, s, cur));
     VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     if (S0) VC_HIP(ctx, hipMemsetAsync(ctx->d_photo_rounds.ptr, 0, (size_t)S0, ctx->stream));
@@ -2251,48 +2306,24 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
             VC_HIP(ctx, hipGetLastError());
         }
         // 4 bytes back per round: the loop ends on the first round without removals
-        ctx->h_photo[0] = 0;
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_photo, q.removed, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        ctx->h_res[0] = 0;
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, q.removed, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t gone = (uint32_t)ctx->h_photo[0];
+        const uint32_t gone = (uint32_t)ctx->h_res[0];
         if (gone > left) return fail(ctx, VC_ERR_HIP, "vc_photo_carve: round %u removed %u of %llu survivors", r, gone, (unsigned long long)left);
         if (gone == 0) { converged = true; break; }
         left -= gone;
     }
     if (left != S0) {
-        // stable compaction of the kept records into the second buffer, which then becomes the step's
-        const uint32_t ngroups = (uint32_t)((S0 + kPhotoGroup - 1) / kPhotoGroup);
-        const uint32_t nscan = (ngroups + kScanBlock - 1) / kScanBlock;
-        VC_TRY(ensure(ctx, ctx->d_photo_cnt, ngroups));
-        VC_TRY(ensure(ctx, ctx->d_photo_off, ngroups));
-        VC_TRY(ensure(ctx, ctx->d_photo_bsum, kMaxScanBlocks));
-        VC_TRY(ensure(ctx, ctx->d_photo_boff, kMaxScanBlocks + 1));
-        VC_TRY(ensure(ctx, ctx->d_photo_rec, cur.records.cap));
-        hipLaunchKernelGGL(k_photo_count, dim3(ngroups), dim3(kVisBlock), 0, ctx->stream, (const uint8_t *)ctx->d_photo_rounds.ptr, S0,
-                           ctx->d_photo_cnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_photo_cnt.ptr, ngroups, ctx->d_photo_off.ptr, ctx->d_photo_bsum.ptr,
-                           ctx->d_photo_boff.ptr, ctx->h_photo + 1));
-        hipLaunchKernelGGL(k_photo_scatter, dim3(ngroups), dim3(kVisBlock), 0, ctx->stream, (const uint64_t *)cur.records.ptr,
-                           (const uint8_t *)ctx->d_photo_rounds.ptr, S0, (const uint32_t *)ctx->d_photo_off.ptr,
-                           (const uint64_t *)ctx->d_photo_boff.ptr, ctx->d_photo_rec.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        std::swap(cur.records, ctx->d_photo_rec);
-        // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
-        const uint64_t n = cur.n, n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
-        const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
-        VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_photo_boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-        cur.nz_valid = false;                    // non-zero word counts per group: counted again by the next packing
+        VC_TRY(compact_records(ctx, cur, PhotoKept{q.rounds, cur.records.ptr, nullptr}, S0, ctx->h_res + 1));
         ctx->survivors = cur.survivors = left;
-        ctx->gathered = false; ctx->packed = false;
     }
     VC_TRY(enqueue_color_visible(ctx, s, cur, depth_tolerance));   // the colouring of F: its maps, masks and colours
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (left != S0 && ctx->h_photo[1] != left)
+    if (left != S0 && ctx->h_res[1] != left)
         return fail(ctx, VC_ERR_HIP, "vc_photo_carve: the compaction kept %llu records, the rounds left %llu",
-                    (unsigned long long)ctx->h_photo[1], (unsigned long long)left);
+                    (unsigned long long)ctx->h_res[1], (unsigned long long)left);
     VC_HIP(ctx, hipEventElapsedTime(&stats->photo_ms, ctx->ev[0], ctx->ev[1]));
     stats->rounds = r;
     stats->converged = converged ? 1u : 0u;
@@ -2323,21 +2354,13 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_components: flags must be 0 (got %u)", flags);
     if (connectivity != 6 && connectivity != 18 && connectivity != 26)
         return fail(ctx, VC_ERR_ARG, "vc_hull_components: connectivity %u, expected 6, 18 or 26", connectivity);
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "vc_hull_components: no carve result");
-    if (ctx->sb[ctx->cur].no_records)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_components: the last carve ran with VC_FLAG_NO_RECORDS, there are no records to label");
-    if (ctx->comm && ctx->n_ranks > 1)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_components: a communicator of %d ranks is attached (multi-GPU labelling is not supported)",
-                    ctx->n_ranks);
-    if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_components: the slab [%u,%u) is narrower than the grid's %u layers", ctx->z0, ctx->z1, ctx->nz);
+    VC_TRY(result_refusals(ctx, "vc_hull_components", "label", "labelling"));
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
     ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
     const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
-    if (!ctx->h_cc) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_cc), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
     if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
     VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
@@ -2345,35 +2368,24 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     uint64_t kept_records = 0;
     if (S0) {
         const uint64_t nwords = (n + 63) / 64;
-        if (cur.sparse_words) {                  // the hierarchical kernels skip the words of groups without survivors
-            const uint32_t ngroups = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
-            hipLaunchKernelGGL(k_zero_dead_groups, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, nwords,
-                               ngroups, cur.groupcnt.ptr);
-            VC_HIP(ctx, hipGetLastError());
-            cur.sparse_words = false;
-        }
+        VC_TRY(densify_words(ctx, cur));
         const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);                  // 64 words per group: <= 2^20 groups
-        const uint32_t rgroups = (uint32_t)((S0 + kCcGroup - 1) / kCcGroup);
-        const uint32_t cgroups = wgroups > rgroups ? wgroups : rgroups;
-        VC_TRY(ensure(ctx, ctx->d_cc_cnt, cgroups));
-        VC_TRY(ensure(ctx, ctx->d_cc_off, cgroups));
-        VC_TRY(ensure(ctx, ctx->d_cc_bsum, kMaxScanBlocks));
-        VC_TRY(ensure(ctx, ctx->d_cc_boff, kMaxScanBlocks + 1));
+        const uint32_t rgroups = (uint32_t)((S0 + kCompactGroup - 1) / kCompactGroup);
+        VC_TRY(ensure(ctx, ctx->d_rscan, wgroups > rgroups ? wgroups : rgroups));
         VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
         VC_TRY(ensure(ctx, ctx->d_cc_parent, (size_t)S0));
         VC_TRY(ensure(ctx, ctx->d_cc_label, (size_t)S0));
         VC_TRY(ensure(ctx, ctx->d_cc_cid, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->d_cc_roots, (size_t)S0));        // (K <= S0: sized before the count is known)
         VC_TRY(ensure(ctx, ctx->d_cc_misc, 2));
         VC_TRY(ensure(ctx, ctx->d_cc_thr, 1));
-        VC_TRY(ensure(ctx, ctx->d_cc_rec, cur.records.cap));
         // 1 survivors before each word: popcounts per 64 words, their scan, the wave scan inside each group
         const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), block(kCcBlock);
-        hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_cc_cnt.ptr);
+        hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
         VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_cc_cnt.ptr, wgroups, ctx->d_cc_off.ptr, ctx->d_cc_bsum.ptr, ctx->d_cc_boff.ptr,
-                           ctx->h_cc + 1));
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, ctx->h_res + 1));
         hipLaunchKernelGGL(k_cc_woff, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
-                           (const uint32_t *)ctx->d_cc_off.ptr, (const uint64_t *)ctx->d_cc_boff.ptr, ctx->d_cc_woff.ptr);
+                           (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_cc_woff.ptr);
         VC_HIP(ctx, hipGetLastError());
         CcParams p;
         memset(&p, 0, sizeof p);
@@ -2394,17 +2406,10 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
         hipLaunchKernelGGL(k_cc_compress, sgrid, block, 0, ctx->stream, p);
         VC_HIP(ctx, hipGetLastError());
         // 6 the roots, compacted stably: the component list in ascending label
-        hipLaunchKernelGGL(k_cc_count<true>, dim3(rgroups), block, 0, ctx->stream, p, ctx->d_cc_cnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_cc_cnt.ptr, rgroups, ctx->d_cc_off.ptr, ctx->d_cc_bsum.ptr, ctx->d_cc_boff.ptr,
-                           ctx->h_cc + 0));
-        VC_TRY(ensure(ctx, ctx->d_cc_roots, (size_t)S0));        // (K <= S0: sized before the count is known)
-        hipLaunchKernelGGL(k_cc_scatter<true>, dim3(rgroups), block, 0, ctx->stream, p, (const uint32_t *)ctx->d_cc_off.ptr,
-                           (const uint64_t *)ctx->d_cc_boff.ptr, ctx->d_cc_roots.ptr, (uint64_t *)nullptr);
-        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(compact(ctx, CcRoots{p.parent, ctx->d_cc_roots.ptr, p.cid}, S0, ctx->h_res + 0));
         // the one read-back before the end: the number of components sizes their arrays
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const uint64_t K64 = ctx->h_cc[0];
+        const uint64_t K64 = ctx->h_res[0];
         if (K64 == 0 || K64 > S0)
             return fail(ctx, VC_ERR_HIP, "vc_hull_components: %llu components among %llu survivors", (unsigned long long)K64,
                         (unsigned long long)S0);
@@ -2427,34 +2432,18 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
         hipLaunchKernelGGL(k_cc_mark, dim3((K + kCcBlock - 1) / kCcBlock), block, 0, ctx->stream, p, K, min_voxels,
                            (const uint64_t *)ctx->d_cc_thr.ptr, ctx->d_cc_kept.ptr, ctx->d_cc_comp.ptr, ctx->d_cc_misc.ptr);
         VC_HIP(ctx, hipGetLastError());
-        // 8 stable compaction of the kept records into the second buffer (the dropped ones leave the words), which then
-        // becomes the step's
-        hipLaunchKernelGGL(k_cc_count<false>, dim3(rgroups), block, 0, ctx->stream, p, ctx->d_cc_cnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_cc_cnt.ptr, rgroups, ctx->d_cc_off.ptr, ctx->d_cc_bsum.ptr, ctx->d_cc_boff.ptr,
-                           ctx->h_cc + 1));
-        hipLaunchKernelGGL(k_cc_scatter<false>, dim3(rgroups), block, 0, ctx->stream, p, (const uint32_t *)ctx->d_cc_off.ptr,
-                           (const uint64_t *)ctx->d_cc_boff.ptr, (uint32_t *)nullptr, ctx->d_cc_rec.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
-        const uint32_t nscan = (rgroups + kScanBlock - 1) / kScanBlock;
-        const uint64_t n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
-        const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
-        VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_cc_boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_cc + 2, ctx->d_cc_misc.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        // 8 the kept records, stably, become the step's (the dropped ones leave the words)
+        VC_TRY(compact_records(ctx, cur, CcKept{p.parent, p.cid, p.kept, p.records, p.words, nullptr}, S0, ctx->h_res + 1));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_cc_misc.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint32_t kept_components = 0, largest = 0;
     if (S0) {
-        std::swap(cur.records, ctx->d_cc_rec);
-        kept_records = ctx->h_cc[1];
-        kept_components = (uint32_t)ctx->h_cc[2];
-        largest = (uint32_t)(ctx->h_cc[2] >> 32);
-        cur.nz_valid = false;                    // non-zero word counts per group: counted again by the next packing
+        kept_records = ctx->h_res[1];
+        kept_components = (uint32_t)ctx->h_res[2];
+        largest = (uint32_t)(ctx->h_res[2] >> 32);
         ctx->survivors = cur.survivors = kept_records;
-        ctx->gathered = false; ctx->packed = false;
         if (kept_records > S0 || kept_components > K)
             return fail(ctx, VC_ERR_HIP, "vc_hull_components: kept %llu of %llu records, %u of %u components", (unsigned long long)kept_records,
                         (unsigned long long)S0, kept_components, K);
@@ -2537,30 +2526,23 @@ int vc_marching_cubes(vc_ctx *ctx, const uint8_t *volume_bits, uint32_t d0, uint
         if (n != ctx->n_voxels()) return fail(ctx, VC_ERR_ARG, "%u x %u x %u is not the %llu voxels of the carved slab", d0, d1, d2,
                                               (unsigned long long)ctx->n_voxels());
         StepBuf &cur = ctx->sb[ctx->cur];
-        if (cur.sparse_words) {                  // the hierarchical kernels skip the words of groups without survivors
-            const uint32_t cg = (uint32_t)((nwords + kGroupWords - 1) / kGroupWords);
-            hipLaunchKernelGGL(k_zero_dead_groups, dim3((cg + 3) / 4), dim3(kBlock), 0, ctx->stream, cur.words.ptr, (uint64_t)nwords, cg, cur.groupcnt.ptr);
-            VC_HIP(ctx, hipGetLastError());
-            cur.sparse_words = false;
-        }
+        VC_TRY(densify_words(ctx, cur));
         p.bits = cur.words.ptr;
     }
     VC_TRY(ensure(ctx, ctx->d_mcx, (size_t)nwords * 3));
     VC_TRY(ensure(ctx, ctx->d_mcwbase, (size_t)nwords));
-    VC_TRY(ensure(ctx, ctx->d_mcgv, ngroups)); VC_TRY(ensure(ctx, ctx->d_mcgt, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_mcgvoff, ngroups)); VC_TRY(ensure(ctx, ctx->d_mcgtoff, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_mcbv, kMaxScanBlocks)); VC_TRY(ensure(ctx, ctx->d_mcbt, kMaxScanBlocks));
-    VC_TRY(ensure(ctx, ctx->d_mcbvoff, kMaxScanBlocks + 1)); VC_TRY(ensure(ctx, ctx->d_mcbtoff, kMaxScanBlocks + 1));
+    VC_TRY(ensure(ctx, ctx->d_mcv, ngroups));
+    VC_TRY(ensure(ctx, ctx->d_mct, ngroups));
     VC_TRY(ensure_exchange_scratch(ctx, 1));
     p.n = n; p.d0 = d0; p.d1 = d1; p.d2 = d2; p.nwords = nwords; p.ngroups = ngroups;
-    p.x = ctx->d_mcx.ptr; p.wbase = ctx->d_mcwbase.ptr; p.gv = ctx->d_mcgv.ptr; p.gt = ctx->d_mcgt.ptr;
-    p.gvoff = ctx->d_mcgvoff.ptr; p.gtoff = ctx->d_mcgtoff.ptr; p.bvoff = ctx->d_mcbvoff.ptr; p.btoff = ctx->d_mcbtoff.ptr;
+    p.x = ctx->d_mcx.ptr; p.wbase = ctx->d_mcwbase.ptr; p.gv = ctx->d_mcv.cnt.ptr; p.gt = ctx->d_mct.cnt.ptr;
+    p.gvoff = ctx->d_mcv.off.ptr; p.gtoff = ctx->d_mct.off.ptr; p.bvoff = ctx->d_mcv.boff.ptr; p.btoff = ctx->d_mct.boff.ptr;
     p.level = level;
     const dim3 grid((ngroups + 3) / 4), block(kBlock);
     hipLaunchKernelGGL(k_mc_count, grid, block, 0, ctx->stream, p);
     VC_HIP(ctx, hipGetLastError());
-    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mcgv.ptr, ngroups, ctx->d_mcgvoff.ptr, ctx->d_mcbv.ptr, ctx->d_mcbvoff.ptr, ctx->h_xtotal));
-    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mcgt.ptr, ngroups, ctx->d_mcgtoff.ptr, ctx->d_mcbt.ptr, ctx->d_mcbtoff.ptr, ctx->h_xtotal + 1));
+    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mcv, ctx->d_mcv.cnt.ptr, ngroups, ctx->h_xtotal));
+    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mct, ctx->d_mct.cnt.ptr, ngroups, ctx->h_xtotal + 1));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     (void)nscan;
     const uint64_t V = ctx->h_xtotal[0], F = ctx->h_xtotal[1];
