@@ -391,7 +391,11 @@ int vc_marching_cubes(vc_ctx *ctx, const uint8_t *volume_bits, uint32_t d0, uint
 int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces);
 
 /* Tuning knobs: which of the equivalent kernels runs and with what launch geometry; NEVER changes results
- * (tests/test_gpu_parity.py runs every family against the oracle).  Defaults are the measured best on MI355X.
+ * (tests/test_gpu_parity.py::test_every_kernel_family_agrees_with_oracle runs every kernel family against the oracle at 4
+ * cameras; tests/test_gpu_camera_counts.py runs the same list at 6, 7, 9, 11, 13 and 15 cameras, voxel_pairs and dbg 8192 /
+ * 16384 at 1 to 16 cameras, grid_lds_kb on both sides of every LDS edge of the brick pipeline at 4, 5, 9 and 16 cameras, and
+ * the launch-shape knobs, voxel_batches and overlap at their limits on a grid whose minimum launches stride).  Defaults are
+ * the measured best on MI355X.
  *   kernel choice   lut_hier (1)  hierarchical lookup-table kernel, 0 = stream the table (k_lut_first + refine)
  *                   lut_tile, fused_tile (1)  words of 4 x-rows x 16 y where nx % 4 == 0 and ny % 64 == 0
  *                   bricks (1)  ny in {256, 512, 1024, 2048, 4096}: the brick pipeline (whole 16^3-voxel bricks decided from their pixel

@@ -134,6 +134,61 @@ def test_numpy_vs_c_on_random_scenes(built, seed):
         assert np.array_equal(a["offsets"], b["offsets"]) and np.array_equal(a["bgr"], b["bgr"])
 
 
+def _ring_scene(C, H, W, seed):
+    """C ring cameras around the default volume, the ellipsoid's silhouettes with per-camera salt noise of different density
+    (camera C-1 noise-free, camera 0 the densest) and random frames."""
+    from voxcarve import synthetic
+    cams = synthetic.ring_cameras(C, H, W)
+    masks = synthetic.ellipsoid_masks(cams, H, W, noise=0.0)
+    rng = np.random.default_rng(seed)
+    for c, m in enumerate(masks):
+        m[rng.random((H, W)) < 0.3 * (C - 1 - c) / max(C - 1, 1)] = 255
+    frames = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for _ in range(C)]
+    return cams, masks, frames
+
+
+@pytest.mark.parametrize("C", range(5, 17))
+def test_numpy_vs_c_at_5_to_16_cameras(built, C):
+    """The two oracles at every camera count the GPU rows above 4 cameras rest on: survivors, the u16 camera mask (bits up to
+    15), the table, the colour camera's samples and its seen flag, at thresholds 1, ceil(C/2), C-1 and C, colour camera C-1."""
+    grids = [(9, 17, 11), (6, 64, 5), (13, 7, 8)]
+    scenes = [fx.random_scene(300 + C, C=C, fg=0.75), _ring_scene(C, 40, 56, 400 + C)]
+    top = 0
+    for k, (cams, masks, frames) in enumerate(scenes):
+        oc = fx.oracle_cams(cams)
+        grid = grids[(C + k) % 3]
+        for mv in sorted({1, (C + 1) // 2, C - 1, C}):
+            a = carve_np.carve(*grid, oc, masks, frames, min_views=mv, color_cam=C - 1)
+            b = carve_c.carve(*grid, oc, masks, frames, min_views=mv, color_cam=C - 1, want_viewmask=True, want_lut=True)
+            assert np.array_equal(a["idx"], b["idx"]) and b["count"] == a["idx"].size, (k, mv)
+            assert np.array_equal(a["viewmask"], b["viewmask"]) and np.array_equal(a["offsets"], b["offsets"]), (k, mv)
+            assert np.array_equal(a["bgr"], b["bgr"]), (k, mv)
+            assert np.array_equal(a["color_seen"], ((b["viewmask"][b["idx"]] >> (C - 1)) & 1).astype(bool)), (k, mv)
+            nviews = np.bitwise_count(a["viewmask"][a["idx"]])
+            assert (nviews >= mv).all() and int((np.bitwise_count(a["viewmask"]) >= mv).sum()) == a["idx"].size
+        top = max(top, int(a["viewmask"].max()))
+        assert (a["viewmask"] >> (C - 1)).any(), k                 # the top camera's bit is set somewhere
+    assert top.bit_length() == C
+
+
+def test_literal_restatement_at_16_cameras(built):
+    """The dict / loop mirror of the reference's Python at the camera cap: the same list, in order, as the numpy oracle and
+    the C oracle, every voxel seen by all 16 cameras (the reference's threshold); colour camera key 2 as in the reference."""
+    cams, masks, frames = _ring_scene(16, 30, 40, 16)
+    for m in masks:
+        m[:] = np.where(m > 0, 255, 0)
+    oc = fx.oracle_cams(cams)
+    n, half = 10, 6
+    data, cols = carve_literal.set_voxel_positions(n, half, n, oc, masks, frames)
+    res = carve_np.carve(n, 2 * half, n, oc, masks, frames)
+    resc = carve_c.carve(n, 2 * half, n, oc, masks, frames, want_viewmask=True)
+    assert len(data) == res["idx"].size > 0 and np.array_equal(res["idx"], resc["idx"]) and np.array_equal(res["bgr"], resc["bgr"])
+    assert int(resc["viewmask"].max()) == 0xffff
+    keys = carve_np.voxel_keys(res["idx"], n, 2 * half, n)
+    assert np.array_equal(np.array(data), carve_np.viewer_positions(keys))
+    assert np.array_equal(np.array(cols), carve_np.viewer_colors(res["bgr"]))
+
+
 def test_degenerate_depth_zero_and_behind_camera(built):
     """z == 0 takes the `z ? 1/z : 1` branch; points behind the camera are not culled."""
     from voxcarve.camera import Camera
