@@ -303,6 +303,56 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
 int vc_fetch_component_labels(vc_ctx *ctx, uint32_t *labels);      /* u32 [survivors_before], input record order */
 int vc_fetch_components(vc_ctx *ctx, vc_component_t *out);         /* [components], ascending label */
 
+/* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
+ *      executable.py) -----------------------------------------------------------------------------------------------------------
+ * vc_render casts one ray per pixel of each view through the current carve result and keeps, per pixel, the first survivor the
+ * ray meets.  The result is read as vc_fetch_occupancy and vc_fetch_records see it, so it includes vc_color_visible,
+ * vc_photo_carve and vc_hull_components.  The contract, bit for bit (tests/render_np.py restates it).  Everything is float64
+ * with no contraction, evaluated in the order written:
+ *   1 grid: every axis has n >= 2; along axis a, s = (max - min) / (n - 1), e = min - 0.5 * s, voxel boundary k is
+ *     b(k) = e + (double)k * s, voxel c spans [b(c), b(c + 1)]; x <-> ix, y <-> iy, z <-> iz; i = (iz nx + ix) ny + iy.
+ *   2 pixel ray of (u, v), 0 <= u < W, 0 <= v < H: xd = ((u + 0.5) - cx) / fx, yd = ((v + 0.5) - cy) / fy; x = xd, y = yd;
+ *     then exactly 8 fixed-point undistortion steps, each from the previous x, y:
+ *       r2 = x*x + y*y;  cd = ((1 + k1*r2) + (k2*r2)*r2) + ((k3*r2)*r2)*r2;
+ *       dx = ((2*p1)*x)*y + p2*(r2 + (2*x)*x);  dy = p1*(r2 + (2*y)*y) + ((2*p2)*x)*y;  x, y = (xd - dx)/cd, (yd - dy)/cd.
+ *     Direction d_j = (x*R[0][j] + y*R[1][j]) + R[2][j]; origin o_j = -((R[0][j]*t0 + R[1][j]*t1) + R[2][j]*t2) (element by
+ *     element: the camera z of d is 1, so t below is the camera depth up to rounding).
+ *   3 entry: for an axis with d_a != 0, inv_a = 1.0 / d_a and the slab parameters (b(0) - o_a) * inv_a, (b(n_a) - o_a) * inv_a;
+ *     near_a is their min, far_a their max.  An axis with d_a == 0 (either sign) is a miss if o_a < b(0) or o_a >= b(n_a), else
+ *     its near is -inf and its far +inf.  t_in = max(0, near_0, near_1, near_2), t_out = min(far); a miss if t_in >= t_out.
+ *     If t_in > 0 the entry axis a* is the lowest axis with near_a == t_in, and its cell is 0 if d > 0, else n - 1.  Every other
+ *     axis (all of them when t_in == 0) takes clamp(floor(((o_a + t_in * d_a) - e_a) / s_a), 0, n_a - 1).
+ *   4 walk: a survivor cell is a hit at parameter t (t_in at first, then the t of the last step).  Otherwise each axis with
+ *     d_a != 0 has its next boundary at tn_a = (b(c_a + (d_a > 0)) - o_a) * inv_a, an axis with d_a == 0 tn_a = +inf; the walk
+ *     steps along the axis of the smallest tn (ties: the lowest axis), t = tn_a, c_a moves by +1 if d_a > 0 else -1; a c_a out
+ *     of [0, n_a) is a miss.  At most nx + ny + nz steps.
+ *   5 per pixel, on a hit: idx = the linear index; depth = (float)t; face = 2a + (d_a > 0 ? 0 : 1) for the axis a of the last
+ *     step (or of entry), 6 when the walk starts inside a survivor; rgb_k = (rec_rgb_k * shade[face] + 127) / 255 in integers,
+ *     rec_rgb = the RGB of the voxel's record.  On a miss: idx = 0xFFFFFFFF, depth = +inf, face = 255, rgb = background.
+ * shade: u8 [7] per face (NULL = all 255); background: RGB (NULL = 0, 0, 0).  flags must be 0.  VC_ERR_ARG (with a message)
+ * when there is no carve result, steps are in flight, the carve ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid,
+ * a communicator of more than one rank is attached, a grid axis is shorter than 2, n_views == 0, H or W is outside 1..16384,
+ * n_views * H * W > 2^28, a view parameter is not finite, fx <= 0 or fy <= 0, or flags != 0; a refused call leaves the images of
+ * the last render as they were.  S = 0 is no error (every pixel a miss).  Synchronous.
+ * The images stay valid until the next vc_render or vc_destroy; a new carve does not touch them.  vc_fetch_render copies one
+ * view of them out ([H W] each, rgb [H W 3]; any pointer may be NULL); it fails before the first render and for view >= n_views.
+ * stats (may be NULL): pixels = n_views H W, hits = pixels with a hit (both contract); cells_visited, blocks_skipped are
+ * diagnostics of the walk the device took (option render_blocks); render_ms = HIP events around the whole call. */
+typedef struct {
+    double K[4];      /* fx, fy, cx, cy (no skew) */
+    double dist[5];   /* k1, k2, p1, p2, k3; all zero = plain pinhole */
+    double R[9];      /* world -> camera, row-major, as vc_set_cameras */
+    double t[3];      /* mm */
+} vc_view_t;
+typedef struct {
+    uint64_t pixels, hits;                    /* contract */
+    uint64_t cells_visited, blocks_skipped;   /* diagnostics, implementation-defined */
+    float render_ms;                          /* HIP events around the whole call */
+} vc_render_stats_t;
+int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H, uint32_t W, const uint8_t *shade,
+              const uint8_t *background, uint32_t flags, vc_render_stats_t *stats);
+int vc_fetch_render(vc_ctx *ctx, uint32_t view, uint32_t *idx, float *depth, uint8_t *rgb, uint8_t *face);
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own
@@ -424,6 +474,7 @@ int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces);
  *                                  (single stream while a communicator is attached)
  *   colouring       visible_check (1)  vc_color_visible's splats read the stored depth and skip the atomic when it is already at or
  *                                  below theirs; visible_big_rect (64)  splat rectangles of more pixels get a workgroup each
+ *   rendering       render_blocks (1)  vc_render skips empty blocks of 8^3 voxels whole; 0: one cell per step everywhere
  *   experiments     dbg (0)  bit 0: skip the per-voxel level (undecided words count as alive), bit 1: skip the word level
  *                                  too -- WRONG results on purpose, to time the levels apart (scripts/exp_bricks.py); bit 2:
  *                                  no word-level tests, every word of a listed brick goes to the per-voxel level (right results)

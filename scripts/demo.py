@@ -1,8 +1,10 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
-viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo]
+viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
 (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
-`photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo"))."""
+`photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
+out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
+cameras at mask size, as PNG when Pillow is importable, else binary PPM)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,6 +12,11 @@ import numpy as np
 import fixtures_util as fx
 from voxcarve import assignment
 
+render_dir = None
+if "--render" in sys.argv:
+    k = sys.argv.index("--render")
+    render_dir = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
 g = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 out = sys.argv[2] if len(sys.argv) > 2 else "hull.ply"
 color_mode = sys.argv[3] if len(sys.argv) > 3 else "camera"
@@ -21,10 +28,36 @@ assignment.configure(frame_source=assignment.StaticFrameSource([(frames, masks)]
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
-with open(out, "w") as f:
-    f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pos))
-    for p, c in zip(pos, rgb):
-        f.write("%g %g %g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
+if out != "-":
+    with open(out, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pos))
+        for p, c in zip(pos, rgb):
+            f.write("%g %g %g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
 print("%d voxels of the %dx%dx%d grid survive all 4 views -> %s; extent x %.2f..%.2f, y %.2f..%.2f, z %.2f..%.2f" %
       (len(pos), g, g, g, out, pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max(), pos[:, 2].min(), pos[:, 2].max()))
+
+
+def write_image(path, img):
+    try:
+        from PIL import Image
+    except ImportError:
+        with open(path + ".ppm", "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+            f.write(np.ascontiguousarray(img).tobytes())
+        return path + ".ppm"
+    Image.fromarray(img).save(path + ".png")
+    return path + ".png"
+
+
+if render_dir:
+    from voxcarve import camera
+    os.makedirs(render_dir, exist_ok=True)
+    shade = (200, 200, 225, 225, 255, 150, 255)        # x sides, y sides, top (rays along +z: up is -z), bottom, inside
+    orbit = camera.orbit(8, 4500.0, 25.0, 1500.0, 1080, 1920)
+    r = assignment.render_views(orbit, 1920, 1080, shade=shade)
+    c = assignment.render_views(shade=shade)
+    paths = [write_image(os.path.join(render_dir, "orbit_%d" % k), img) for k, img in enumerate(r["rgb"])]
+    paths += [write_image(os.path.join(render_dir, "cam%d" % (k + 1)), img) for k, img in enumerate(c["rgb"])]
+    print("%d images -> %s (orbit: %.2f ms for 8 views, %d of %d pixels hit)" % (len(paths), render_dir, r["stats"]["render_ms"],
+                                                                              r["stats"]["hits"], r["stats"]["pixels"]))

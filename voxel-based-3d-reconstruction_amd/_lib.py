@@ -57,6 +57,15 @@ class VcPhotoStats(ctypes.Structure):
                 ("survivors_after", ctypes.c_uint64), ("photo_ms", ctypes.c_float)]
 
 
+class VcView(ctypes.Structure):
+    _fields_ = [("K", ctypes.c_double * 4), ("dist", ctypes.c_double * 5), ("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3)]
+
+
+class VcRenderStats(ctypes.Structure):
+    _fields_ = [("pixels", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("cells_visited", ctypes.c_uint64),
+                ("blocks_skipped", ctypes.c_uint64), ("render_ms", ctypes.c_float)]
+
+
 class VcComponentStats(ctypes.Structure):
     _fields_ = [("components", ctypes.c_uint32), ("components_kept", ctypes.c_uint32), ("survivors_before", ctypes.c_uint64),
                 ("survivors_after", ctypes.c_uint64), ("largest", ctypes.c_uint32), ("components_ms", ctypes.c_float)]
@@ -128,6 +137,9 @@ SIGNATURES = {
                                           ctypes.POINTER(VcComponentStats)]),
     "vc_fetch_component_labels": (ctypes.c_int, [c_ctx, c_u32p]),
     "vc_fetch_components": (ctypes.c_int, [c_ctx, ctypes.c_void_p]),
+    "vc_render": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, c_u8p, c_u8p,
+                                 ctypes.c_uint32, ctypes.c_void_p]),
+    "vc_fetch_render": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.POINTER(ctypes.c_float), c_u8p, c_u8p]),
     "vc_marching_cubes": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_u64p, c_u64p]),
     "vc_fetch_mesh": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_float), c_u32p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),

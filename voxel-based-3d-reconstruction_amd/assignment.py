@@ -266,3 +266,15 @@ def voxels_status():
     nx, ny, nz = _engine.grid
     return _engine.fetch_occupancy().reshape(nx, ny, nz)
 
+
+
+def render_views(views=None, width=None, height=None, shade=None):
+    """Images of the hull of the last set_voxel_positions call, after whatever configure(...) asked for (component filter,
+    photo carve, colouring), ray-cast on the device (CarveEngine.render): views = a list of camera.Camera (default: the
+    calibrated cameras), width x height pixels (default: the mask size).  Returns the dict of CarveEngine.render: rgb
+    [V, H, W, 3], depth, index, face and stats."""
+    if _engine is None or not initialized or _engine._sized is None:
+        raise RuntimeError("set_voxel_positions has not run")
+    H, W = _engine.image_size
+    return _engine.render(_engine._cameras if views is None else views, H if height is None else height,
+                          W if width is None else width, shade=shade)

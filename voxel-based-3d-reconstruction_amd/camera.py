@@ -94,3 +94,37 @@ def load_cameras(cam_input_path="data", num_cameras=4, config_input_filename="co
     """Cameras cam1..camN under cam_input_path (reference voxel_reconstruction.py:76-78)."""
     return [Camera.from_config(os.path.join(cam_input_path, "cam" + str(c)), config_input_filename)
             for c in range(1, num_cameras + 1)]
+
+
+def look_at(eye, target, fx, H, W, up=(0.0, 0.0, -1.0)):
+    """A pinhole Camera (no distortion, fx = fy, principal point at the image centre) at `eye` looking at `target`, with
+    `up` showing up in the image (the reference volume's up is -z).  R's rows are the camera's x (right), y (down) and z
+    (forward) axes in world coordinates, t = -R eye."""
+    eye = np.asarray(eye, dtype=np.float64).reshape(3)
+    fwd = np.asarray(target, dtype=np.float64).reshape(3) - eye
+    norm = np.linalg.norm(fwd)
+    if not norm > 0:
+        raise ValueError("look_at: eye and target coincide")
+    fwd = fwd / norm
+    right = np.cross(fwd, np.asarray(up, dtype=np.float64).reshape(3))
+    rn = np.linalg.norm(right)
+    if not rn > 1e-12:
+        raise ValueError("look_at: the viewing direction is parallel to up")
+    right = right / rn
+    down = np.cross(fwd, right)
+    R = np.stack([right, down, fwd])
+    K = np.array([[float(fx), 0.0, W / 2.0], [0.0, float(fx), H / 2.0], [0.0, 0.0, 1.0]])
+    return Camera(K, np.zeros(5), None, -(R @ eye), R=R)
+
+
+def orbit(n, radius, elevation_deg, fx, H, W, centre=(256.0, 0.0, -768.0)):
+    """n look_at cameras evenly spaced on a circle of `radius` around `centre` (azimuth 0, 360/n, ... degrees about the
+    vertical axis), raised by elevation_deg towards up = -z, all looking at `centre`."""
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    el = math.radians(float(elevation_deg))
+    cams = []
+    for k in range(int(n)):
+        az = 2.0 * math.pi * k / int(n)
+        eye = c + float(radius) * np.array([math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), -math.sin(el)])
+        cams.append(look_at(eye, c, fx, H, W))
+    return cams

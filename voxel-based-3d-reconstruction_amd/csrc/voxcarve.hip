@@ -39,6 +39,7 @@
 #include "vc_compact.h"
 #include "vc_photo.h"
 #include "vc_components.h"
+#include "vc_render.h"
 
 #pragma clang fp contract(off)
 
@@ -340,6 +341,15 @@ struct vc_ctx {
     bool cc_valid = false;           // labels and components belong to the pass that produced the current result
     uint64_t cc_n = 0;               // its input survivors
     uint32_t cc_k = 0;               // its components
+    // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
+    DevBuf<uint32_t> d_rn_idx, d_rn_rgbf;
+    DevBuf<float> d_rn_depth;
+    DevBuf<RenderView> d_rn_views;
+    DevBuf<uint64_t> d_rn_map;
+    DevBuf<unsigned long long> d_rn_ctr;
+    bool rn_valid = false;           // images of a finished render (a new carve leaves them alone)
+    uint32_t rn_views = 0, rn_H = 0, rn_W = 0;
+    int render_blocks = 1;           // vc_render skips empty 8^3 blocks (same results)
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1258,6 +1268,8 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_cc_woff); release(ctx->d_cc_parent); release(ctx->d_cc_label); release(ctx->d_cc_cid); release(ctx->d_cc_roots);
     release(ctx->d_cc_size); release(ctx->d_cc_box); release(ctx->d_cc_comp); release(ctx->d_cc_misc); release(ctx->d_cc_kept);
     release(ctx->d_cc_thr);
+    release(ctx->d_rn_idx); release(ctx->d_rn_rgbf); release(ctx->d_rn_depth); release(ctx->d_rn_views); release(ctx->d_rn_map);
+    release(ctx->d_rn_ctr);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
     if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
@@ -2479,6 +2491,116 @@ int vc_fetch_components(vc_ctx *ctx, vc_component_t *out)
     return VC_OK;
 }
 
+// ---- ray-cast images of the current carve result (vc_render.h; contract in include/voxcarve.h) ----
+int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H, uint32_t W, const uint8_t *shade,
+              const uint8_t *background, uint32_t flags, vc_render_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_render: flags must be 0 (got %u)", flags);
+    if (n_views == 0 || !views) return fail(ctx, VC_ERR_ARG, "vc_render: no views");
+    if (H < 1 || H > 16384 || W < 1 || W > 16384) return fail(ctx, VC_ERR_ARG, "vc_render: image size %ux%u not in 1..16384", H, W);
+    const uint64_t npix = (uint64_t)n_views * H * W;
+    if (npix > (1ull << 28)) return fail(ctx, VC_ERR_ARG, "vc_render: %u views of %ux%u are %llu pixels, more than 2^28", n_views, H, W,
+                                         (unsigned long long)npix);
+    for (uint32_t k = 0; k < n_views; ++k) {
+        const double *q = views[k].K;                               // the 21 doubles of the view
+        for (int j = 0; j < 21; ++j)
+            if (!std::isfinite(q[j])) return fail(ctx, VC_ERR_ARG, "vc_render: view %u has a parameter that is not finite", k);
+        if (!(views[k].K[0] > 0.0) || !(views[k].K[1] > 0.0))
+            return fail(ctx, VC_ERR_ARG, "vc_render: view %u has fx %g, fy %g (both must be > 0)", k, views[k].K[0], views[k].K[1]);
+    }
+    VC_TRY(result_refusals(ctx, "vc_render", "render", "rendering"));
+    if (ctx->nx < 2 || ctx->ny < 2 || ctx->nz < 2)
+        return fail(ctx, VC_ERR_ARG, "vc_render: grid %ux%ux%u has an axis shorter than 2", ctx->nx, ctx->ny, ctx->nz);
+    static_assert(sizeof(vc_view_t) == sizeof(RenderView), "vc_view_t is the device's view");
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->rn_valid = false;
+    VC_TRY(ensure(ctx, ctx->d_rn_idx, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->d_rn_depth, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->d_rn_rgbf, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->d_rn_views, n_views));
+    VC_TRY(ensure(ctx, ctx->d_rn_ctr, 3));
+    const uint32_t nb[3] = {(ctx->nx + kRenderB - 1) / kRenderB, (ctx->ny + kRenderB - 1) / kRenderB, (ctx->nz + kRenderB - 1) / kRenderB};
+    const uint64_t nblocks = (uint64_t)nb[0] * nb[1] * nb[2];
+    VC_TRY(ensure(ctx, ctx->d_rn_map, (size_t)((nblocks + 63) / 64)));
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (ctx->survivors && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(densify_words(ctx, cur));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->d_rn_views.ptr, views, (size_t)n_views * sizeof(vc_view_t), hipMemcpyHostToDevice, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_rn_ctr.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    RenderParams p;
+    memset(&p, 0, sizeof p);
+    p.words = cur.words.ptr;
+    p.bmap = ctx->d_rn_map.ptr;
+    p.records = cur.records.ptr;
+    p.S = ctx->survivors;
+    p.views = ctx->d_rn_views.ptr;
+    p.idx = ctx->d_rn_idx.ptr; p.depth = ctx->d_rn_depth.ptr; p.rgbf = ctx->d_rn_rgbf.ptr;
+    p.ctr = ctx->d_rn_ctr.ptr;
+    const uint32_t n3[3] = {ctx->nx, ctx->ny, ctx->nz};
+    for (int a = 0; a < 3; ++a) {                // item 1 (this file is built without contraction too)
+        p.n[a] = n3[a];
+        p.nb[a] = nb[a];
+        p.s[a] = (ctx->bounds[2 * a + 1] - ctx->bounds[2 * a]) / (double)(n3[a] - 1);
+        p.e[a] = ctx->bounds[2 * a] - 0.5 * p.s[a];
+    }
+    p.H = H; p.W = W;
+    p.tiles_x = (W + 7) / 8;
+    p.tiles_per_view = p.tiles_x * ((H + 7) / 8);
+    p.n_tiles = p.tiles_per_view * n_views;      // <= 2^28 views x tiles of one pixel
+    for (int f = 0; f < 7; ++f) p.shade[f] = shade ? shade[f] : 255u;
+    p.bg = background ? (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16) : 0u;
+    p.skip = ctx->render_blocks ? 1u : 0u;
+    if (p.skip) {
+        hipLaunchKernelGGL(k_render_map, dim3((uint32_t)((nblocks + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, ctx->stream,
+                           (const uint64_t *)cur.words.ptr, ctx->d_rn_map.ptr, ctx->nx, ctx->ny, ctx->nz, nb[0], nb[1], nblocks);
+        VC_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_render, dim3((p.n_tiles + kRenderBlock / 64 - 1) / (kRenderBlock / 64)), dim3(kRenderBlock), 0, ctx->stream, p);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_rn_ctr.ptr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->rn_valid = true;
+    ctx->rn_views = n_views; ctx->rn_H = H; ctx->rn_W = W;
+    if (ctx->h_res[0] > npix) return fail(ctx, VC_ERR_HIP, "vc_render: %llu hits among %llu pixels", (unsigned long long)ctx->h_res[0],
+                                          (unsigned long long)npix);
+    if (stats) {
+        stats->pixels = npix;
+        stats->hits = ctx->h_res[0];
+        stats->cells_visited = ctx->h_res[1];
+        stats->blocks_skipped = ctx->h_res[2];
+        VC_HIP(ctx, hipEventElapsedTime(&stats->render_ms, ctx->ev[0], ctx->ev[1]));
+    }
+    return VC_OK;
+}
+
+int vc_fetch_render(vc_ctx *ctx, uint32_t view, uint32_t *idx, float *depth, uint8_t *rgb, uint8_t *face)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!ctx->rn_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: no images: call vc_render first");
+    if (view >= ctx->rn_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: view %u not in [0,%u)", view, ctx->rn_views);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t HW = (size_t)ctx->rn_H * ctx->rn_W, off = (size_t)view * HW;
+    if (idx) VC_HIP(ctx, hipMemcpy(idx, ctx->d_rn_idx.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (depth) VC_HIP(ctx, hipMemcpy(depth, ctx->d_rn_depth.ptr + off, HW * sizeof(float), hipMemcpyDeviceToHost));
+    if (rgb || face) {
+        std::vector<uint32_t> px(HW);
+        VC_HIP(ctx, hipMemcpy(px.data(), ctx->d_rn_rgbf.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < HW; ++k) {
+            const uint32_t q = px[k];
+            if (rgb) { rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16); }
+            if (face) face[k] = (uint8_t)(q >> 24);
+        }
+    }
+    return VC_OK;
+}
+
 int vc_fetch_visibility(vc_ctx *ctx, uint16_t *vis)
 {
     if (!ctx || !vis) return VC_ERR_ARG;
@@ -3035,6 +3157,7 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
     }
     else if (k == "visible_check") ctx->visible_check = value != 0;
     else if (k == "visible_big_rect" && value >= 1) ctx->visible_big_rect = value;
+    else if (k == "render_blocks") ctx->render_blocks = value != 0;
     else if (k == "cull") ctx->cull = value != 0;
     else if (k == "bricks") ctx->bricks = value != 0;
     else if (k == "dbg") ctx->dbg = value;

@@ -489,6 +489,59 @@ class CarveEngine:
         return {"label": raw[:, 0].copy(), "size": raw[:, 1].copy(), "lo": raw[:, 2:5].copy(), "hi": raw[:, 5:8].copy(),
                 "kept": raw[:, 8] != 0}
 
+    # -- ray-cast images of the current result (vc_render) --------------------------------------------------------------------------
+    def render(self, views, H, W, shade=None, background=(0, 0, 0)):
+        """Ray-casts the current carve result (after color_visible / photo_carve / filter_components, as fetch sees it) from each
+        camera.Camera of `views` (lens distortion included; self._cams are the calibrated ones) at H x W pixels -- contract:
+        include/voxcarve.h.  shade: 7 u8, one per face (2a: entered while moving along +axis a, 2a + 1: along -a, 6: the
+        camera sits inside the voxel; None = all 255) scaling the records' RGB; background: RGB of the misses.
+        Returns a dict: rgb u8 [V, H, W, 3], depth f32 [V, H, W] (+inf on a miss), index u32 [V, H, W] (0xFFFFFFFF on a miss),
+        face u8 [V, H, W] (255 on a miss) and stats (pixels, hits, cells_visited, blocks_skipped, render_ms)."""
+        views = list(views)
+        if not views:
+            raise ValueError("render: no views")
+        arr = (_lib.VcView * len(views))()
+        for k, cam in enumerate(views):
+            K = np.asarray(cam.K, dtype=np.float64).reshape(3, 3)
+            if K[0, 1] != 0.0:
+                raise ValueError("render: view %d has a skewed camera matrix (K[0,1] = %r)" % (k, float(K[0, 1])))
+            arr[k].K[:] = [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])]
+            arr[k].dist[:] = [float(v) for v in np.asarray(cam.dist, dtype=np.float64).reshape(5)]
+            arr[k].R[:] = [float(v) for v in np.asarray(cam.R, dtype=np.float64).reshape(9)]
+            arr[k].t[:] = [float(v) for v in np.asarray(cam.tvec, dtype=np.float64).reshape(3)]
+        sh = None if shade is None else np.ascontiguousarray(shade, dtype=np.uint8).reshape(7)
+        bg = np.ascontiguousarray(background, dtype=np.uint8).reshape(3)
+        st = _lib.VcRenderStats()
+        self._check(self._L.vc_render(self._ctx, len(views), ctypes.cast(arr, ctypes.c_void_p), int(H), int(W),
+                                      None if sh is None else _ptr(sh, ctypes.c_uint8), _ptr(bg, ctypes.c_uint8), 0,
+                                      ctypes.byref(st)), "vc_render")
+        V, H, W = len(views), int(H), int(W)
+        out = {"rgb": np.empty((V, H, W, 3), dtype=np.uint8), "depth": np.empty((V, H, W), dtype=np.float32),
+               "index": np.empty((V, H, W), dtype=np.uint32), "face": np.empty((V, H, W), dtype=np.uint8)}
+        for k in range(V):
+            self._check(self._L.vc_fetch_render(self._ctx, k, _ptr(out["index"][k], ctypes.c_uint32), _ptr(out["depth"][k], ctypes.c_float),
+                                                _ptr(out["rgb"][k], ctypes.c_uint8), _ptr(out["face"][k], ctypes.c_uint8)),
+                        "vc_fetch_render")
+        out["stats"] = {"pixels": int(st.pixels), "hits": int(st.hits), "cells_visited": int(st.cells_visited),
+                        "blocks_skipped": int(st.blocks_skipped), "render_ms": float(st.render_ms)}
+        return out
+
+    def silhouette_agreement(self, slot=0):
+        """Renders the current result as each calibrated camera at mask size and compares the hit pixels with that camera's
+        device mask of `slot`.  Returns one dict per camera: mask_px (mask pixels), hull_px (pixels the hull covers), both, and
+        iou = both / (mask_px + hull_px - both) (1.0 when both are empty).  Mask pixels the hull leaves empty show where the
+        other cameras disagree with this one (calibration error, mask noise)."""
+        H, W = self.image_size
+        idx = self.render(self._cams, H, W)["index"]
+        out = []
+        for c in range(self.n_cameras):
+            hull = idx[c] != 0xFFFFFFFF
+            mask = self.fetch_mask(c, slot) > 0
+            m, h, b = int(mask.sum()), int(hull.sum()), int((mask & hull).sum())
+            union = m + h - b
+            out.append({"mask_px": m, "hull_px": h, "both": b, "iou": b / union if union else 1.0})
+        return out
+
     def marching_cubes(self, volume=None, level=0.0, axes="reference"):
         """Triangle mesh of an ON/OFF volume on the device -> (verts float32 [V, 3], faces uint32 [F, 3]).
         volume: 3-D boolean array (what the reference hands to skimage.measure.marching_cubes, voxel_reconstruction.py:141);
