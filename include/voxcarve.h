@@ -440,6 +440,41 @@ int vc_marching_cubes(vc_ctx *ctx, const uint8_t *volume_bits, uint32_t d0, uint
 /* verts: float [n_verts][3], faces: u32 [n_faces][3] of the last vc_marching_cubes; either may be NULL. */
 int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces);
 
+/* ---- silhouette-refined, coloured surface mesh of the current result (no reference counterpart) ---------------------------------
+ * vc_surface_mesh meshes the current carve result as vc_fetch_occupancy sees it (vc_color_visible, vc_photo_carve and
+ * vc_hull_components included) in world millimetres, each vertex moved along its grid edge to where the silhouettes cross it.
+ * The contract, bit for bit (tests/surface_np.py restates it); float64 with no contraction, in the order written:
+ *   1 topology: the vertices and faces of vc_marching_cubes(NULL, nz, nx, ny) on the same result, same order; vertex axes
+ *     (iz, ix, iy) -> (z, x, y), a cyclic permutation, so faces stay oriented from ON to OFF (outward, positive signed volume).
+ *   2 point test: T(P) = the cameras c with off = pixel_offset(project_point(cam_c, P), H, W) >= 0 and mask_bit(bits_c, off),
+ *     bits_c = camera c's mask of the carve's frame set after its 2x2 post-filter (what the carve read); P is inside iff
+ *     T(P) >= m, m = the carve's min_views after its clamp to >= 1.
+ *   3 edge points: a vertex's edge joins an ON and an OFF element; P_on and P_off are their voxel centres on the carve's
+ *     linspace axes, differing in one coordinate a.  P(s)_a = on_a + s * (off_a - on_a) (two roundings), the other two
+ *     coordinates the shared ones; P(0) = P_on and P(1) = P_off by definition (the centres the carve tested).
+ *   4 bisection: a vertex is refined iff T(P_on) >= m and T(P_off) < m.  Then lo = 0, hi = 1 and for k = 1 .. steps:
+ *     mid = (lo + hi) * 0.5, lo = mid if P(mid) is inside else hi = mid; s = (lo + hi) * 0.5.  Otherwise (a photo carve or a
+ *     foreign lookup table made the occupancy disagree with the point test) s = 0.5.  steps = 0 gives s = 0.5 everywhere.
+ *     Every s is dyadic: the arithmetic on it is exact.
+ *   5 outputs, fetched by vc_fetch_surface_mesh (any pointer may be NULL): verts f64 [V][3] = P(s) as world (x, y, z) mm;
+ *     faces u32 [F][3]; rgb u8 [V][3] = the RGB of the ON element's record; refined u8 [V] (0 / 1).
+ * stats (required): n_verts, n_faces, refined, unrefined (contract); point_tests = camera tests the device evaluated (a
+ * diagnostic: it stops a vertex's test once T >= m or T < m is decided; option surface_order); surface_ms = HIP events
+ * around the whole call.  VC_ERR_ARG (with a message) when there is no carve result, steps are in flight, the carve ran with
+ * VC_FLAG_NO_RECORDS, a communicator of more than one rank is attached, the slab is narrower than the grid, steps > 24,
+ * flags != 0, stats == NULL, or the carve's frame set has been prepared again since the carve (its masks are no longer the
+ * ones the occupancy came from).  An empty hull is no error (V = F = 0).  Synchronous, one read-back (the counts) in the middle.
+ * The mesh stays valid until the next vc_surface_mesh (a refused one included) or vc_destroy; a new carve does not touch it, and
+ * vc_fetch_mesh still returns the last vc_marching_cubes mesh.  vc_fetch_surface_mesh fails when there is no mesh. */
+typedef struct {
+    uint64_t n_verts, n_faces;      /* contract */
+    uint64_t refined, unrefined;    /* contract: refined + unrefined = n_verts */
+    uint64_t point_tests;           /* diagnostic, implementation-defined */
+    float surface_ms;               /* HIP events around the whole call */
+} vc_surface_stats_t;
+int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stats_t *stats);
+int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *rgb, uint8_t *refined);
+
 /* Tuning knobs: which of the equivalent kernels runs and with what launch geometry; NEVER changes results
  * (tests/test_gpu_parity.py::test_every_kernel_family_agrees_with_oracle runs every kernel family against the oracle at 4
  * cameras; tests/test_gpu_camera_counts.py runs the same list at 6, 7, 9, 11, 13 and 15 cameras, voxel_pairs and dbg 8192 /
@@ -475,6 +510,7 @@ int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces);
  *   colouring       visible_check (1)  vc_color_visible's splats read the stored depth and skip the atomic when it is already at or
  *                                  below theirs; visible_big_rect (64)  splat rectangles of more pixels get a workgroup each
  *   rendering       render_blocks (1)  vc_render skips empty blocks of 8^3 voxels whole; 0: one cell per step everywhere
+ *   meshing         surface_order (1)  vc_surface_mesh's bisection tries the cameras that rejected P_off first; 0: camera order
  *   experiments     dbg (0)  bit 0: skip the per-voxel level (undecided words count as alive), bit 1: skip the word level
  *                                  too -- WRONG results on purpose, to time the levels apart (scripts/exp_bricks.py); bit 2:
  *                                  no word-level tests, every word of a listed brick goes to the per-voxel level (right results)

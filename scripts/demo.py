@@ -1,10 +1,11 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-(`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--mesh PATH] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
-cameras at mask size, as PNG when Pillow is importable, else binary PPM)."""
+cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
+its vertices refined against the silhouettes on the device and coloured by the voxels, as binary PLY)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -16,6 +17,11 @@ render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
     render_dir = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
+mesh_path = None
+if "--mesh" in sys.argv:
+    k = sys.argv.index("--mesh")
+    mesh_path = sys.argv[k + 1]
     del sys.argv[k:k + 2]
 g = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 out = sys.argv[2] if len(sys.argv) > 2 else "hull.ply"
@@ -61,3 +67,11 @@ if render_dir:
     paths += [write_image(os.path.join(render_dir, "cam%d" % (k + 1)), img) for k, img in enumerate(c["rgb"])]
     print("%d images -> %s (orbit: %.2f ms for 8 views, %d of %d pixels hit)" % (len(paths), render_dir, r["stats"]["render_ms"],
                                                                               r["stats"]["hits"], r["stats"]["pixels"]))
+
+if mesh_path:
+    from voxcarve.voxel_reconstruction import write_ply
+    m = assignment.surface_mesh(8)
+    write_ply(mesh_path, m["verts"], m["faces"], m["rgb"])
+    st = m["stats"]
+    print("mesh: %d vertices (%d refined), %d faces -> %s (%.2f ms on the device)" % (st["n_verts"], st["refined"], st["n_faces"],
+                                                                                  mesh_path, st["surface_ms"]))

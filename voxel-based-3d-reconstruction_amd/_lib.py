@@ -71,6 +71,11 @@ class VcComponentStats(ctypes.Structure):
                 ("survivors_after", ctypes.c_uint64), ("largest", ctypes.c_uint32), ("components_ms", ctypes.c_float)]
 
 
+class VcSurfaceStats(ctypes.Structure):
+    _fields_ = [("n_verts", ctypes.c_uint64), ("n_faces", ctypes.c_uint64), ("refined", ctypes.c_uint64),
+                ("unrefined", ctypes.c_uint64), ("point_tests", ctypes.c_uint64), ("surface_ms", ctypes.c_float)]
+
+
 class VcComponent(ctypes.Structure):
     _fields_ = [("label", ctypes.c_uint32), ("size", ctypes.c_uint32), ("lo", ctypes.c_uint32 * 3), ("hi", ctypes.c_uint32 * 3),
                 ("kept", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
@@ -142,6 +147,8 @@ SIGNATURES = {
     "vc_fetch_render": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.POINTER(ctypes.c_float), c_u8p, c_u8p]),
     "vc_marching_cubes": (ctypes.c_int, [c_ctx, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, c_u64p, c_u64p]),
     "vc_fetch_mesh": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_float), c_u32p]),
+    "vc_surface_mesh": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcSurfaceStats)]),
+    "vc_fetch_surface_mesh": (ctypes.c_int, [c_ctx, c_f64p, c_u32p, c_u8p, c_u8p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

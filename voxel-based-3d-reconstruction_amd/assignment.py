@@ -278,3 +278,13 @@ def render_views(views=None, width=None, height=None, shade=None):
     H, W = _engine.image_size
     return _engine.render(_engine._cameras if views is None else views, H if height is None else height,
                           W if width is None else width, shade=shade)
+
+
+def surface_mesh(refine_steps=8):
+    """Surface mesh of the hull of the last set_voxel_positions call, after whatever configure(...) asked for (component filter,
+    photo carve, colouring), refined against the silhouettes on the device (CarveEngine.surface_mesh): world millimetres,
+    outward faces, the voxels' colours.  Returns the dict of CarveEngine.surface_mesh: verts [V, 3] float64, faces [F, 3], rgb
+    [V, 3], refined [V] and stats; voxel_reconstruction.write_ply writes it out."""
+    if _engine is None or not initialized or _engine._sized is None:
+        raise RuntimeError("set_voxel_positions has not run")
+    return _engine.surface_mesh(refine_steps)

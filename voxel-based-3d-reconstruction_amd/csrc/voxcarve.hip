@@ -40,6 +40,7 @@
 #include "vc_photo.h"
 #include "vc_components.h"
 #include "vc_render.h"
+#include "vc_surface.h"
 
 #pragma clang fp contract(off)
 
@@ -193,6 +194,7 @@ struct StepBuf {
     bool counts_exchanged = false;           // vc_carve_begin already packed and all-gathered the counts
     int mode = 0, color_cam = -1;            // what the step was run with (vc_expand_entries colours the same way)
     uint32_t slot = 0, slot_gen = 0;         // frame set the step read, and which preparation of it
+    uint32_t min_views = 1;                  // the threshold it ran with, after the clamp to >= 1 (vc_surface_mesh's point test)
     uint64_t n = 0, survivors = 0;
 };
 
@@ -350,6 +352,15 @@ struct vc_ctx {
     bool rn_valid = false;           // images of a finished render (a new carve leaves them alone)
     uint32_t rn_views = 0, rn_H = 0, rn_W = 0;
     int render_blocks = 1;           // vc_render skips empty 8^3 blocks (same results)
+    // vc_surface_mesh: edge entries, the mesh of the last call (world vertices, faces, colours, refined flags), counters
+    DevBuf<uint64_t> d_sf_edges;
+    DevBuf<double> d_sf_verts;
+    DevBuf<uint32_t> d_sf_faces;
+    DevBuf<uint8_t> d_sf_rgb, d_sf_refined;
+    DevBuf<unsigned long long> d_sf_ctr;
+    uint64_t sf_verts = 0, sf_faces = 0;
+    bool sf_valid = false;
+    int surface_order = 1;           // vc_surface_mesh tries the cameras that rejected P_off first (same results)
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1270,6 +1281,8 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_cc_thr);
     release(ctx->d_rn_idx); release(ctx->d_rn_rgbf); release(ctx->d_rn_depth); release(ctx->d_rn_views); release(ctx->d_rn_map);
     release(ctx->d_rn_ctr);
+    release(ctx->d_sf_edges); release(ctx->d_sf_verts); release(ctx->d_sf_faces); release(ctx->d_sf_rgb); release(ctx->d_sf_refined);
+    release(ctx->d_sf_ctr);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
     if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
@@ -1650,6 +1663,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     ctx->step_next = (ctx->step_next + 1) % kStepRing;
     sb.n = n; sb.survivors = 0; sb.want_vm = want_vm; sb.has_first = false;
     sb.allseen = min_views == ctx->C;
+    sb.min_views = min_views;
     sb.no_records = (flags & VC_FLAG_NO_RECORDS) != 0;
     sb.sparse_words = false;
     sb.mode = mode; sb.color_cam = color_cam; sb.slot = slot;
@@ -2691,6 +2705,114 @@ int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces)
     return VC_OK;
 }
 
+// ---- silhouette-refined surface mesh of the current carve result (vc_surface.h; contract in include/voxcarve.h) ----
+int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    ctx->sf_valid = false;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: flags must be 0 (got %u)", flags);
+    if (steps > kSurfMaxSteps) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: steps %u not in [0, %u]", steps, kSurfMaxSteps);
+    VC_TRY(result_refusals(ctx, "vc_surface_mesh", "colour the mesh from", "meshing"));
+    StepBuf &cur = ctx->sb[ctx->cur];
+    if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
+        return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: frame set %u has been prepared again since the carve: its masks are not the ones "
+                    "the occupancy came from", cur.slot);
+    const uint64_t n = ctx->n_voxels();
+    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: %llu voxels exceed the u32 index", (unsigned long long)n);
+    const Slot &s = ctx->slots[cur.slot];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (ctx->survivors && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    uint64_t V = 0, F = 0;
+    McParams p;
+    memset(&p, 0, sizeof p);
+    if (n) {
+        // 1 topology: vc_marching_cubes(NULL, nz, nx, ny)'s counts and scans (its scratch, not its mesh)
+        VC_TRY(densify_words(ctx, cur));
+        const uint32_t nwords = (uint32_t)((n + 63) / 64), ngroups = (nwords + 63) / 64;
+        VC_TRY(ensure(ctx, ctx->d_mcx, (size_t)nwords * 3));
+        VC_TRY(ensure(ctx, ctx->d_mcwbase, (size_t)nwords));
+        VC_TRY(ensure(ctx, ctx->d_mcv, ngroups));
+        VC_TRY(ensure(ctx, ctx->d_mct, ngroups));
+        p.bits = cur.words.ptr;
+        p.n = n; p.d0 = ctx->nz; p.d1 = ctx->nx; p.d2 = ctx->ny; p.nwords = nwords; p.ngroups = ngroups;
+        p.x = ctx->d_mcx.ptr; p.wbase = ctx->d_mcwbase.ptr; p.gv = ctx->d_mcv.cnt.ptr; p.gt = ctx->d_mct.cnt.ptr;
+        p.gvoff = ctx->d_mcv.off.ptr; p.gtoff = ctx->d_mct.off.ptr; p.bvoff = ctx->d_mcv.boff.ptr; p.btoff = ctx->d_mct.boff.ptr;
+        hipLaunchKernelGGL(k_mc_count, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mcv, ctx->d_mcv.cnt.ptr, ngroups, ctx->h_res));
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mct, ctx->d_mct.cnt.ptr, ngroups, ctx->h_res + 1));
+        // the one read-back in the middle: the counts size the mesh
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        V = ctx->h_res[0]; F = ctx->h_res[1];
+        if (V > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: %llu vertices exceed the u32 vertex number", (unsigned long long)V);
+    }
+    VC_TRY(ensure(ctx, ctx->d_sf_edges, (size_t)(V + 1)));
+    VC_TRY(ensure(ctx, ctx->d_sf_verts, (size_t)(3 * V + 3)));
+    VC_TRY(ensure(ctx, ctx->d_sf_faces, (size_t)(3 * F + 3)));
+    VC_TRY(ensure(ctx, ctx->d_sf_rgb, (size_t)(3 * V + 3)));
+    VC_TRY(ensure(ctx, ctx->d_sf_refined, (size_t)(V + 1)));
+    VC_TRY(ensure(ctx, ctx->d_sf_ctr, 2));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_sf_ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    if (V) {
+        // 2 edge entries in vertex order, the faces (k_mc_faces reads the word bases k_surf_edges writes)
+        p.faces = ctx->d_sf_faces.ptr; p.vcap = V; p.fcap = F;
+        const dim3 grid((p.ngroups + 3) / 4), block(kBlock);
+        hipLaunchKernelGGL(k_surf_edges, grid, block, 0, ctx->stream, p, ctx->d_sf_edges.ptr);
+        hipLaunchKernelGGL(k_mc_faces, grid, block, 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+        // 3 the refinement and the colours
+        SurfParams q;
+        memset(&q, 0, sizeof q);
+        q.edges = ctx->d_sf_edges.ptr;
+        q.records = cur.records.ptr;
+        q.S = ctx->survivors;
+        q.V = V;
+        q.xs = ctx->d_axes.ptr; q.ys = q.xs + ctx->nx; q.zs = q.ys + ctx->ny;
+        q.bits = s.bits.ptr;
+        q.mwords = ctx->mwords; q.C = ctx->C; q.H = ctx->H; q.W = ctx->W;
+        q.m = cur.min_views; q.steps = steps; q.order = ctx->surface_order ? 1u : 0u;
+        q.nx = ctx->nx; q.ny = ctx->ny;
+        q.verts = ctx->d_sf_verts.ptr; q.rgb = ctx->d_sf_rgb.ptr; q.refined = ctx->d_sf_refined.ptr;
+        q.ctr = ctx->d_sf_ctr.ptr;
+        memcpy(q.cam, ctx->cams, sizeof(CamDev) * ctx->C);
+        hipLaunchKernelGGL(k_surf_refine, dim3((uint32_t)((V + kSurfBlock - 1) / kSurfBlock)), dim3(kSurfBlock), 0, ctx->stream, q);
+        VC_HIP(ctx, hipGetLastError());
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_sf_ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t refined = ctx->h_res[0];
+    if (refined > V) return fail(ctx, VC_ERR_HIP, "vc_surface_mesh: %llu refined among %llu vertices", (unsigned long long)refined,
+                                 (unsigned long long)V);
+    ctx->sf_verts = V; ctx->sf_faces = F; ctx->sf_valid = true;
+    stats->n_verts = V;
+    stats->n_faces = F;
+    stats->refined = refined;
+    stats->unrefined = V - refined;
+    stats->point_tests = ctx->h_res[1];
+    VC_HIP(ctx, hipEventElapsedTime(&stats->surface_ms, ctx->ev[0], ctx->ev[1]));
+    return VC_OK;
+}
+
+int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *rgb, uint8_t *refined)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!ctx->sf_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_surface_mesh: no mesh: call vc_surface_mesh first");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t V = (size_t)ctx->sf_verts, F = (size_t)ctx->sf_faces;
+    if (verts && V) VC_HIP(ctx, hipMemcpy(verts, ctx->d_sf_verts.ptr, V * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (faces && F) VC_HIP(ctx, hipMemcpy(faces, ctx->d_sf_faces.ptr, F * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (rgb && V) VC_HIP(ctx, hipMemcpy(rgb, ctx->d_sf_rgb.ptr, V * 3, hipMemcpyDeviceToHost));
+    if (refined && V) VC_HIP(ctx, hipMemcpy(refined, ctx->d_sf_refined.ptr, V, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
 // ---- the step before the path, its data-parallel part (reference background_subtraction.py:153-168) ----
 static int hsv_tables(vc_ctx *ctx);
 
@@ -3158,6 +3280,7 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
     else if (k == "visible_check") ctx->visible_check = value != 0;
     else if (k == "visible_big_rect" && value >= 1) ctx->visible_big_rect = value;
     else if (k == "render_blocks") ctx->render_blocks = value != 0;
+    else if (k == "surface_order") ctx->surface_order = value != 0;
     else if (k == "cull") ctx->cull = value != 0;
     else if (k == "bricks") ctx->bricks = value != 0;
     else if (k == "dbg") ctx->dbg = value;

@@ -567,6 +567,27 @@ class CarveEngine:
         self._check(self._L.vc_fetch_mesh(self._ctx, _ptr(verts, ctypes.c_float), _ptr(faces, ctypes.c_uint32)), "vc_fetch_mesh")
         return verts, faces
 
+    def surface_mesh(self, refine_steps=8):
+        """Surface mesh of the current carve result (after color_visible / photo_carve / filter_components, as fetch sees it) in
+        world millimetres: the marching-cubes topology of marching_cubes(axes="grid"), each vertex moved along its grid edge by
+        refine_steps bisection steps of the carve's own point test (its cameras, post-filtered masks and min_views) to where the
+        silhouettes cross the edge -- contract: include/voxcarve.h.  Returns a dict: verts float64 [V, 3] (x, y, z mm), faces
+        uint32 [F, 3] (outward), rgb uint8 [V, 3] (the ON voxel's record), refined bool [V] (False: the edge's ends disagree with
+        the occupancy, the vertex sits at the edge midpoint) and stats (n_verts, n_faces, refined, unrefined, point_tests,
+        surface_ms)."""
+        st = _lib.VcSurfaceStats()
+        self._check(self._L.vc_surface_mesh(self._ctx, int(refine_steps), 0, ctypes.byref(st)), "vc_surface_mesh")
+        V, F = int(st.n_verts), int(st.n_faces)
+        verts = np.empty((V, 3), dtype=np.float64)
+        faces = np.empty((F, 3), dtype=np.uint32)
+        rgb = np.empty((V, 3), dtype=np.uint8)
+        refined = np.empty(V, dtype=np.uint8)
+        self._check(self._L.vc_fetch_surface_mesh(self._ctx, _ptr(verts, ctypes.c_double), _ptr(faces, ctypes.c_uint32),
+                                                  _ptr(rgb, ctypes.c_uint8), _ptr(refined, ctypes.c_uint8)), "vc_fetch_surface_mesh")
+        return {"verts": verts, "faces": faces, "rgb": rgb, "refined": refined != 0,
+                "stats": {"n_verts": V, "n_faces": F, "refined": int(st.refined), "unrefined": int(st.unrefined),
+                          "point_tests": int(st.point_tests), "surface_ms": float(st.surface_ms)}}
+
     def set_option(self, name, value):
         """Launch-geometry tuning knobs (never change results); see vc_set_option."""
         self._check(self._L.vc_set_option(self._ctx, name.encode(), int(value)), "vc_set_option")
