@@ -43,6 +43,11 @@ typedef enum {
 } vc_mode;
 
 enum {
+    VC_FOOT_ANY = 1u,        /* vc_carve_footprint: a camera passes when any pixel of the voxel's box is foreground   */
+    VC_FOOT_COVER = 2u       /* ... when at least q / 256 of the box is (q = 256: the whole box, inside the image)     */
+};
+
+enum {
     VC_FLAG_VIEWMASK = 1u,   /* also keep the per-voxel camera bitmask (compat dicts) */
     VC_FLAG_NO_RECORDS = 2u  /* count + occupancy only: the records are produced by vc_allgather /
                                 vc_expand_entries (a rank of a multi-GPU job never reads its own slab's list).
@@ -57,15 +62,20 @@ enum {
 typedef enum {
     VC_K_PREP_PACK = 0, VC_K_PREP_GRID, VC_K_CULL_BRICKS, VC_K_BRICK_WORDS, VC_K_VOXEL_WORDS, VC_K_ASSEMBLE,
     VC_K_SCAN_GROUPS, VC_K_FINISH_SCAN, VC_K_EMIT, VC_K_CARVE_ONE_LAUNCH /* k_lut_refine, k_carve_fused*, k_carve_generic, k_lut_first */,
-    VC_K_CULL /* in front of a one-launch kernel */, VC_K_COUNT_GROUPS
+    VC_K_CULL /* in front of a one-launch kernel */, VC_K_COUNT_GROUPS,
+    VC_K_FOOT_TABLE /* k_foot_rows + k_foot_cols */, VC_K_FOOT_CARVE /* k_carve_foot */
 } vc_kernel_kind;
-#define VC_KERNEL_KINDS 12
+#define VC_KERNEL_KINDS 14
 enum {
     VC_WORK_WORD_BOXES = 0,   /* 8-byte word boxes k_brick_words read (listed bricks x 64 words x cameras asked)           */
     VC_WORK_TABLE_ENTRIES,    /* 4-byte table entries the per-voxel level read (VC_MODE_LUT)                                */
     VC_WORK_PROJECTIONS,      /* float64 projections the per-voxel level did (VC_MODE_FUSED)                                */
     VC_WORK_EMIT_PROJECTIONS, /* float64 projections the record expansion did (VC_MODE_FUSED without the colour table)      */
-    VC_WORK_BRICK_BOXES       /* 8-byte brick boxes k_cull_bricks read                                                      */
+    VC_WORK_BRICK_BOXES,      /* 8-byte brick boxes k_cull_bricks read                                                      */
+    VC_WORK_FOOT_PROJECTIONS, /* float64 projections k_carve_foot did (vc_carve_footprint)                                  */
+    VC_WORK_FOOT_UNION_SKIPS, /* (word, camera) visits of k_carve_foot that the union-box count ended: no foreground under  */
+                              /* the whole word, the camera fails its 64 voxels at once                                     */
+    VC_WORK_FOOT_WORDS        /* occupancy words k_carve_foot took                                                          */
 };
 #define VC_WORK_KINDS 8
 
@@ -181,6 +191,33 @@ int vc_carve(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int 
  * min_views > n_cameras is legal and yields the empty result (as the reference's threshold test would). */
 int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int mode, uint32_t flags);
 int vc_carve_end(vc_ctx *ctx, uint64_t *n_out);
+/* Footprint carve: a camera passes a voxel by the foreground count of the pixel box its whole CELL projects to, not by the one
+ * pixel under its centre (vc_carve, which stays the default rule and is untouched by this call).  No counterpart in the
+ * reference; restated in tests/footprint_np.py.  Projection is the carve's float64 projection (csrc/vc_device.h), no
+ * behind-camera cull.
+ *  1. Cell.  Per axis with n cells, bounds lo, hi and centres c[k] (vc_get_axes): h = 0.5 * ((hi - lo) / (n - 1)) (0 when
+ *     n == 1); lattice L[k] = c[k] - h for k < n, L[n] = c[n-1] + h.  Voxel (ix, iy, iz) has the 8 corners L[i], L[i+1] per
+ *     axis: neighbours share corners bit for bit.
+ *  2. Box.  The 8 corners and the centre are projected; u_lo, u_hi, v_lo, v_hi are the per-coordinate min / max over the 9
+ *     points with NaNs ignored (fmin / fmax).  A camera for which the centre's u or v is NaN does not see the voxel.
+ *     bx0 = clamp(floor(u_lo), -1, W), bx1 = clamp(floor(u_hi), -1, W), by0, by1 likewise with H (clamped in float64, then
+ *     converted).  area = (bx1 - bx0 + 1) * (by1 - by0 + 1); cnt = foreground pixels of the slot's prepared mask (what
+ *     vc_fetch_mask returns) inside the box intersected with the image.
+ *  3. Test.  VC_FOOT_ANY: cnt > 0.  VC_FOOT_COVER: cnt * 256 >= q * area in 64-bit integers, q in 1..256; q = 256 ("all") asks
+ *     for a box inside the image that is all foreground.  For every camera set any >= centre >= all as sets of voxels.
+ *  4. T = cameras that pass; a voxel is kept when T >= min_views and T >= 1.  Records in ascending linear index, 8 bytes as
+ *     vc_carve's.  Colour and seen: the colour camera's pixel under the voxel's CENTRE whenever the centre is inside its image
+ *     (the mask is not consulted), seen = 1; else 0, 0, 0 and seen = 0.  Occupancy words and, with VC_FLAG_VIEWMASK, the per-
+ *     voxel camera bits (bit c = camera c passes) as vc_carve leaves them; vc_set_slab is honoured.
+ * The count of a box is four loads from a summed-area table per camera ((H+1) x (W+1) u32, built on the device from the slot's
+ * prepared bits the first time a footprint carve uses that preparation of the slot, kept until the slot is prepared again;
+ * callers of vc_carve alone never allocate one).  Synchronous; the result is what every vc_fetch_* and post-carve pass reads,
+ * exactly as after vc_carve (vc_surface_mesh keeps testing the CENTRE rule: vertices it cannot bracket stay at the midpoint).
+ * flags: VC_FLAG_VIEWMASK | VC_FLAG_NO_RECORDS.  VC_ERR_ARG (with a message, nothing launched) for a rule other than
+ * VC_FOOT_ANY / VC_FOOT_COVER, q outside 1..256, steps in flight, no grid / cameras / masks in the slot, a colour camera out of
+ * range. */
+int vc_carve_footprint(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, uint32_t rule, uint32_t q, uint32_t flags,
+                       uint64_t *n_out);
 /* Survivors of the last carve: idx u32 [S] (global linear index, ascending), rgb u8 [S,3]
  * (RGB order, i.e. the reference's BGR[::-1]) and seen u8 [S] (1 if the colour camera
  * sees the voxel -- the reference raises KeyError when it does not).  Any may be NULL. */

@@ -14,6 +14,8 @@ VC_MODE_FUSED = 0
 VC_MODE_LUT = 1
 VC_FLAG_VIEWMASK = 1
 VC_FLAG_NO_RECORDS = 2
+VC_FOOT_ANY = 1
+VC_FOOT_COVER = 2
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
 VC_MAX_MOG_MODELS = 64
@@ -31,10 +33,11 @@ c_f64p = ctypes.POINTER(ctypes.c_double)
 c_ctx = ctypes.c_void_p
 
 
-VC_KERNEL_KINDS, VC_WORK_KINDS = 12, 8
+VC_KERNEL_KINDS, VC_WORK_KINDS = 14, 8
 KERNEL_KINDS = ("k_prep_pack", "k_prep_grid", "k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble", "k_scan_groups",
-                "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups")
-WORK_KINDS = ("word_boxes", "table_entries", "projections", "emit_projections", "brick_boxes")
+                "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups", "foot_table", "k_carve_foot")
+WORK_KINDS = ("word_boxes", "table_entries", "projections", "emit_projections", "brick_boxes", "foot_projections", "foot_union_skips",
+              "foot_words")
 
 
 class VcTiming(ctypes.Structure):
@@ -124,6 +127,8 @@ SIGNATURES = {
     "vc_project": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_f64p, ctypes.c_uint64, c_f64p]),
     "vc_carve": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                 ctypes.c_uint32, c_u64p]),
+    "vc_carve_footprint": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_uint32, c_u64p]),
     "vc_carve_begin": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_uint32]),
     "vc_carve_end": (ctypes.c_int, [c_ctx, c_u64p]),
     "vc_fetch": (ctypes.c_int, [c_ctx, c_u32p, c_u8p, c_u8p]),

@@ -16,7 +16,7 @@ import numpy as np
 
 from ._lib import VoxcarveError
 from .camera import load_cameras
-from .engine import (COLOR_CAMERA_INDEX, DEFAULT_BOUNDS, CarveEngine, viewer_colors, viewer_positions,
+from .engine import (COLOR_CAMERA_INDEX, DEFAULT_BOUNDS, CarveEngine, footprint_rule, viewer_colors, viewer_positions,
                      voxel_keys)
 
 # reference assignment.py:28-33: figure_threshold, figure_inner_threshold, opening/closing pre/post
@@ -162,7 +162,7 @@ _source = None
 _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused",
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
              "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
-             "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26}
+             "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre"}
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -177,7 +177,10 @@ def configure(frame_source=None, **settings):
     min_component_voxels, keep_components: when either is non-zero, every carve is followed by CarveEngine.filter_components
     (connectivity=component_connectivity), before any colouring or photo carve: components smaller than min_component_voxels,
     or beyond the keep_components largest, leave the hull (floating specks of mask noise); voxels_status() describes what is
-    kept.  0 and 0 (the default) keep every survivor."""
+    kept.  0 and 0 (the default) keep every survivor.
+    footprint: "centre" (default) asks, as the reference does, whether the pixel under a voxel's centre is foreground; "any",
+    "all" and ("cover", q) test the pixel box the voxel's whole cell projects to (CarveEngine.carve(footprint=...)): "any" keeps
+    what is thinner than a voxel (the outer hull), "all" gives the inner hull."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -186,6 +189,7 @@ def configure(frame_source=None, **settings):
         raise ValueError("color_mode %r, expected one of %s" % (settings["color_mode"], COLOR_MODES))
     if settings.get("hull", _settings["hull"]) not in HULLS:
         raise ValueError("hull %r, expected one of %s" % (settings["hull"], HULLS))
+    footprint_rule(settings.get("footprint", _settings["footprint"]))          # raises ValueError on anything else
     _settings.update(settings)
     _source = frame_source
     if _engine is not None:
@@ -243,7 +247,8 @@ def set_voxel_positions(width, height, depth):
         _engine.upload_masks(masks, slot=0)
         for c in (range(len(frames)) if visible else (cc,)):                   # "visible": every camera's image
             _engine.upload_frame(c, frames[c], slot=0)
-    _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"])
+    _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"],
+                  footprint=_settings["footprint"])
     if _settings["min_component_voxels"] or _settings["keep_components"]:
         _engine.filter_components(connectivity=_settings["component_connectivity"], min_voxels=_settings["min_component_voxels"],
                                   keep_largest=_settings["keep_components"])

@@ -41,6 +41,7 @@
 #include "vc_components.h"
 #include "vc_render.h"
 #include "vc_surface.h"
+#include "vc_footprint.h"
 
 #pragma clang fp contract(off)
 
@@ -138,6 +139,9 @@ struct Slot {
     hipEvent_t e_carve = nullptr, e_emit = nullptr;
     bool up_pending = false, carve_pending = false, emit_pending = false;
     uint32_t gen = 0;           // preparations so far: a step remembers the one it ran on (vc_carve_end's regrow path)
+    DevBuf<uint32_t> sat;       // vc_carve_footprint: [C][(H+1)(W+1)] summed-area tables of `bits`, made by the first footprint carve
+    uint32_t sat_gen = 0;       // ... that runs on a preparation of the slot, and the preparation they belong to
+    bool sat_valid = false;
 };
 
 // np.linspace(lo, hi, num=n) in float64: y[k] = k*step + lo (two roundings), y[n-1] = hi
@@ -311,6 +315,9 @@ struct vc_ctx {
     int lut_hier = 1;                // VC_MODE_LUT: hierarchical kernel (boxes + block grid) instead of stream + refine
     int timing_detail = 0;           // also time preparation and carve kernels of pipelined steps (three more events on the carve stream)
     int kernel_events = 0;           // every launch of a step carries begin / end events of its own (no packet of their own: vc_timing_t::kernel_ms_sum)
+    uint32_t foot_rule = 0, foot_q = 0;   // inside vc_carve_footprint: the step's carve kernel is k_carve_foot with this rule (0: the centre rule)
+    DevBuf<double> d_foot_axes;      // the cell lattices lx | ly | lz (nx + 1, ny + 1, nz + 1 values), made by the first footprint carve on a grid
+    bool foot_axes_valid = false;
     bool sync_call = false;          // inside vc_carve: the step is collected at once, events between its kernels cost nothing that matters
     DevBuf<uint16_t> d_viewmask;
     DevBuf<double> d_scratch;
@@ -772,7 +779,8 @@ void release_slot(Slot &s)
         if (s.h_fbytes[c]) { (void)hipHostFree(s.h_fbytes[c]); s.h_fbytes[c] = nullptr; }
     }
     if (s.h_bytes) { (void)hipHostFree(s.h_bytes); s.h_bytes = nullptr; s.h_bytes_cap = 0; }
-    release(s.bgr_all);
+    release(s.bgr_all); release(s.sat);
+    s.sat_valid = false;
     if (s.h_bgr_all) { (void)hipHostFree(s.h_bgr_all); s.h_bgr_all = nullptr; s.h_bgr_all_cap = 0; }
     s.have_masks = s.bits_valid = s.grids_valid = false;
     s.have_frame.clear(); s.frame_dirty.clear();
@@ -909,6 +917,39 @@ int ensure_prepared(vc_ctx *ctx, Slot &s, bool want_grids, const CarveParams *cp
 }
 
 uint32_t grid_for(uint64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
+
+// vc_carve_footprint, on the carve stream in front of k_carve_foot: the grid's cell lattices (once per vc_set_grid) and the
+// slot's summed-area tables (once per preparation of the slot; the caller has made the stream wait for that preparation).
+// Lattice of an axis with n cells (include/voxcarve.h): h = 0.5 * ((hi - lo) / (n - 1)), 0 when n == 1; L[k] = c[k] - h, L[n] = c[n-1] + h
+int ensure_footprint(vc_ctx *ctx, Slot &s)
+{
+    if (!ctx->foot_axes_valid) {
+        const std::vector<double> *ax[3] = {&ctx->xs, &ctx->ys, &ctx->zs};
+        std::vector<double> lat;
+        for (int a = 0; a < 3; ++a) {
+            const std::vector<double> &c = *ax[a];
+            const size_t n = c.size();
+            const double h = n > 1 ? 0.5 * ((ctx->bounds[2 * a + 1] - ctx->bounds[2 * a]) / (double)(n - 1)) : 0.0;
+            for (size_t k = 0; k < n; ++k) lat.push_back(c[k] - h);
+            lat.push_back(c[n - 1] + h);
+        }
+        VC_TRY(ensure(ctx, ctx->d_foot_axes, lat.size()));
+        VC_HIP(ctx, hipMemcpy(ctx->d_foot_axes.ptr, lat.data(), lat.size() * sizeof(double), hipMemcpyHostToDevice));   // (pageable: synchronous)
+        ctx->foot_axes_valid = true;
+    }
+    if (s.sat_valid && s.sat_gen == s.gen) return VC_OK;
+    const uint32_t C = ctx->C, H = ctx->H, W = ctx->W;
+    VC_TRY(ensure(ctx, s.sat, (size_t)C * (H + 1) * (W + 1)));
+    hipEvent_t ks, ke;
+    kev_pick(ctx, VC_K_FOOT_TABLE, ks, ke);                      // begin rides on the row pass, end on the column pass
+    hipExtLaunchKernelGGL(k_foot_rows, dim3((C * H + 3) / 4), dim3(kBlock), 0, ctx->stream, ks, nullptr, 0, (const uint32_t *)s.bits.ptr,
+                          s.sat.ptr, C, H, W, ctx->mwords);
+    hipExtLaunchKernelGGL(k_foot_cols, dim3(grid_for((uint64_t)C * (W + 1))), dim3(kBlock), 0, ctx->stream, nullptr, ke, 0, s.sat.ptr, C, H, W);
+    VC_HIP(ctx, hipGetLastError());
+    s.sat_valid = true;
+    s.sat_gen = s.gen;
+    return VC_OK;
+}
 
 constexpr int kEmitBatch = 4;              // survivors per lane in flight together in k_emit_words
 
@@ -1268,7 +1309,7 @@ int vc_destroy(vc_ctx *ctx)
         for (int kk = 0; kk < VC_KERNEL_KINDS; ++kk)
             for (int i = 0; i < 2; ++i) if (b.kev[kk][i]) (void)hipEventDestroy(b.kev[kk][i]);
     }
-    release(ctx->d_stats); release(ctx->d_fg); release(ctx->d_hsvdiv);
+    release(ctx->d_stats); release(ctx->d_fg); release(ctx->d_hsvdiv); release(ctx->d_foot_axes);
     for (auto &m : ctx->mog) release(m.state);
     for (auto &m : ctx->mog2) { release(m.state); release(m.nmodes); }
     release(ctx->d_cc);
@@ -1330,6 +1371,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     VC_HIP(ctx, hipMemcpyAsync(ctx->d_axes.ptr + nx + ny, ctx->zs.data(), sizeof(double) * nz, hipMemcpyHostToDevice, ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->have_grid = true;
+    ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
     ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
@@ -1662,7 +1704,8 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     sb.e_emit0 = ctx->step_ev[ctx->step_next][2];
     ctx->step_next = (ctx->step_next + 1) % kStepRing;
     sb.n = n; sb.survivors = 0; sb.want_vm = want_vm; sb.has_first = false;
-    sb.allseen = min_views == ctx->C;
+    const bool foot = ctx->foot_rule != 0;                       // vc_carve_footprint: colour and seen by the centre's pixel alone
+    sb.allseen = foot || min_views == ctx->C;
     sb.min_views = min_views;
     sb.no_records = (flags & VC_FLAG_NO_RECORDS) != 0;
     sb.sparse_words = false;
@@ -1716,7 +1759,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     // The chunked kernels cover the reference's case (seen by ALL cameras); the one-thread-per-voxel kernels cover
     // thresholds below C, the camera bitmask, and thresholds above C (no voxel can be seen by more cameras than
     // there are: the reference's sum(views.values()) >= views_threshold is never true, the result is empty).
-    bool fast = !ctx->force_generic && !want_vm && min_views == ctx->C;
+    bool fast = !foot && !ctx->force_generic && !want_vm && min_views == ctx->C;
     // k_lut_first keeps one camera's mask bits in LDS; larger masks take the generic kernel.
     if (mode == VC_MODE_LUT && !ctx->lut_hier && (size_t)ctx->mwords * sizeof(uint32_t) > kMaxFirstLds) fast = false;
     // per-frame preparation, on the device, in front of the carve (nothing to do when the slot has been used before)
@@ -1736,6 +1779,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     }
     sb.slot_gen = s.gen;
     if (s.prep_pending) { VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.e_prep, 0)); s.prep_pending = false; }
+    if (foot) VC_TRY(ensure_footprint(ctx, s));                  // lattices + the slot's tables, on the carve stream behind the preparation
     p.maskbits = s.bits.ptr;
     p.blockgrid = s.grid.ptr;
     p.coarsegrid = s.has_coarse ? s.coarse.ptr : nullptr;
@@ -1754,7 +1798,14 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     if (mode == VC_MODE_FUSED && ctx->fused_color_table && color_cam >= 0 && !sb.no_records) VC_TRY(ensure_color_table(ctx, color_cam));
     if (sb.carve_timed) VC_HIP(ctx, hipEventRecord(sb.e0, ctx->stream));
     const dim3 block(kBlock);
-    if (fast) {
+    if (foot) {
+        FootParams f;
+        f.lx = ctx->d_foot_axes.ptr; f.ly = f.lx + ctx->nx + 1; f.lz = f.ly + ctx->ny + 1;
+        f.sat = s.sat.ptr; f.rule = ctx->foot_rule; f.q = ctx->foot_q;
+        const dim3 grid((uint32_t)((nwords + 3) / 4));
+        if (want_vm) VC_KLAUNCH(VC_K_FOOT_CARVE, (k_carve_foot<true>), grid, block, 0, ctx->stream, p, f);
+        else VC_KLAUNCH(VC_K_FOOT_CARVE, (k_carve_foot<false>), grid, block, 0, ctx->stream, p, f);
+    } else if (fast) {
         const uint64_t nchunks = (n + 64 * kSub - 1) / (64 * kSub);
         const uint64_t want = (nchunks + 3) / 4;
         const uint64_t gmax = 256ull * (uint64_t)ctx->fused_blocks_per_cu;
@@ -2068,6 +2119,26 @@ int vc_carve(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int 
     ctx->sync_call = true;
     const int rc = vc_carve_begin(ctx, slot, min_views, color_cam, mode, flags);
     ctx->sync_call = false;
+    if (rc != VC_OK) return rc;
+    return vc_carve_end(ctx, n_out);
+}
+
+// The footprint rule (include/voxcarve.h, csrc/vc_footprint.h): the synchronous step of vc_carve with k_carve_foot as its carve
+// kernel.  Everything behind the words -- group counts, scan, record expansion, the result hand-over -- is the step's own.
+int vc_carve_footprint(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, uint32_t rule, uint32_t q, uint32_t flags,
+                       uint64_t *n_out)
+{
+    if (!ctx || !n_out) return VC_ERR_ARG;
+    *n_out = 0;
+    if (ctx->npending != 0) return fail(ctx, VC_ERR_ARG, "vc_carve_footprint with steps in flight: drain them with vc_carve_end");
+    if (rule != VC_FOOT_ANY && rule != VC_FOOT_COVER) return fail(ctx, VC_ERR_ARG, "unknown footprint rule %u (VC_FOOT_ANY, VC_FOOT_COVER)", rule);
+    if (rule == VC_FOOT_COVER && (q < 1 || q > 256)) return fail(ctx, VC_ERR_ARG, "footprint cover q = %u not in 1..256", q);
+    if (flags & ~(uint32_t)(VC_FLAG_VIEWMASK | VC_FLAG_NO_RECORDS)) return fail(ctx, VC_ERR_ARG, "unknown flags 0x%x", flags);
+    ctx->sync_call = true;
+    ctx->foot_rule = rule; ctx->foot_q = rule == VC_FOOT_COVER ? q : 1u;
+    const int rc = vc_carve_begin(ctx, slot, min_views, color_cam, VC_MODE_FUSED, flags);
+    ctx->sync_call = false;
+    ctx->foot_rule = 0;
     if (rc != VC_OK) return rc;
     return vc_carve_end(ctx, n_out);
 }

@@ -17,6 +17,23 @@ SCALING_FACTOR = 64          # reference assignment.py:118
 COLOR_CAMERA_INDEX = 1       # reference assignment.py:133 uses camera key 2 (1-based)
 
 MODES = {"fused": _lib.VC_MODE_FUSED, "lut": _lib.VC_MODE_LUT}
+FOOTPRINTS = ("centre", "any", "all")
+
+
+def footprint_rule(footprint):
+    """"centre" -> None; "any" | "all" | ("cover", q), q an integer in 1..256 -> (rule, q) of vc_carve_footprint."""
+    if isinstance(footprint, str):
+        if footprint == "centre":
+            return None
+        if footprint == "any":
+            return (_lib.VC_FOOT_ANY, 0)
+        if footprint == "all":
+            return (_lib.VC_FOOT_COVER, 256)
+    elif isinstance(footprint, (tuple, list)) and len(footprint) == 2 and footprint[0] == "cover":
+        q = footprint[1]
+        if isinstance(q, (int, np.integer)) and not isinstance(q, bool) and 1 <= int(q) <= 256:
+            return (_lib.VC_FOOT_COVER, int(q))
+    raise ValueError('footprint %r, expected "centre", "any", "all" or ("cover", q) with an integer q in 1..256' % (footprint,))
 
 
 def _ptr(a, ctype):
@@ -334,13 +351,23 @@ class CarveEngine:
         return uv
 
     # -- hot path -------------------------------------------------------------------
-    def carve(self, slot=0, min_views=None, color_cam=COLOR_CAMERA_INDEX, mode="fused", viewmask=False, records=True):
+    def carve(self, slot=0, min_views=None, color_cam=COLOR_CAMERA_INDEX, mode="fused", viewmask=False, records=True,
+              footprint="centre"):
         """Runs the carve; returns the survivor count (records stay on the device).  records=False keeps
-        only the count and the occupancy words (multi-GPU ranks: allgather() / expand_entries() make the list)."""
+        only the count and the occupancy words (multi-GPU ranks: allgather() / expand_entries() make the list).
+        footprint: "centre" (default, the reference's rule: the pixel under the voxel's centre), or a test of the pixel box
+        the voxel's whole cell projects to -- "any" (outer hull: some pixel is foreground), "all" (inner hull: the box lies
+        in the image and is all foreground), ("cover", q) (at least q / 256 of it); see vc_carve_footprint.  `mode` does
+        not apply to those: they project in the kernel."""
         n = ctypes.c_uint64(0)
         mv = self.n_cameras if min_views is None else int(min_views)
         cc = -1 if color_cam is None else int(color_cam)
         flags = (_lib.VC_FLAG_VIEWMASK if viewmask else 0) | (0 if records else _lib.VC_FLAG_NO_RECORDS)
+        foot = footprint_rule(footprint)
+        if foot is not None:
+            self._check(self._L.vc_carve_footprint(self._ctx, slot, mv, cc, foot[0], foot[1], flags, ctypes.byref(n)), "vc_carve_footprint")
+            self.count = int(n.value)
+            return self.count
         self._check(self._L.vc_carve(self._ctx, slot, mv, cc, MODES[mode], flags, ctypes.byref(n)), "vc_carve")
         self.count = int(n.value)
         return self.count
