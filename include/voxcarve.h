@@ -63,9 +63,11 @@ typedef enum {
     VC_K_PREP_PACK = 0, VC_K_PREP_GRID, VC_K_CULL_BRICKS, VC_K_BRICK_WORDS, VC_K_VOXEL_WORDS, VC_K_ASSEMBLE,
     VC_K_SCAN_GROUPS, VC_K_FINISH_SCAN, VC_K_EMIT, VC_K_CARVE_ONE_LAUNCH /* k_lut_refine, k_carve_fused*, k_carve_generic, k_lut_first */,
     VC_K_CULL /* in front of a one-launch kernel */, VC_K_COUNT_GROUPS,
-    VC_K_FOOT_TABLE /* k_foot_rows + k_foot_cols */, VC_K_FOOT_CARVE /* k_carve_foot */
+    VC_K_FOOT_TABLE /* k_foot_rows + k_foot_cols */, VC_K_FOOT_CARVE /* k_carve_foot */,
+    VC_K_DIST_BOX /* k_dist_box */, VC_K_DIST_Y /* k_dist_y */, VC_K_DIST_ENV /* k_dist_env, along x and along z */,
+    VC_K_DIST_RECORDS /* k_dist_records */
 } vc_kernel_kind;
-#define VC_KERNEL_KINDS 14
+#define VC_KERNEL_KINDS 18
 enum {
     VC_WORK_WORD_BOXES = 0,   /* 8-byte word boxes k_brick_words read (listed bricks x 64 words x cameras asked)           */
     VC_WORK_TABLE_ENTRIES,    /* 4-byte table entries the per-voxel level read (VC_MODE_LUT)                                */
@@ -75,9 +77,12 @@ enum {
     VC_WORK_FOOT_PROJECTIONS, /* float64 projections k_carve_foot did (vc_carve_footprint)                                  */
     VC_WORK_FOOT_UNION_SKIPS, /* (word, camera) visits of k_carve_foot that the union-box count ended: no foreground under  */
                               /* the whole word, the camera fails its 64 voxels at once                                     */
-    VC_WORK_FOOT_WORDS        /* occupancy words k_carve_foot took                                                          */
+    VC_WORK_FOOT_WORDS,       /* occupancy words k_carve_foot took                                                          */
+    VC_WORK_DIST_CELLS,       /* cells of the boxes the distance transforms ran over (vc_hull_distance, vc_hull_morphology),   */
+                              /* one count per transform: each of its three passes reads and writes that many 8-byte values   */
+    VC_WORK_DIST_LINES        /* lines k_dist_y and k_dist_env walked                                                        */
 };
-#define VC_WORK_KINDS 8
+#define VC_WORK_KINDS 10
 
 typedef struct {
     float carve_ms;     /* the carve kernels alone (HIP events on the context's stream).  carve_ms, first_ms, compact_ms
@@ -339,6 +344,58 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
                        uint32_t flags, vc_component_stats_t *stats);
 int vc_fetch_component_labels(vc_ctx *ctx, uint32_t *labels);      /* u32 [survivors_before], input record order */
 int vc_fetch_components(vc_ctx *ctx, vc_component_t *out);         /* [components], ascending label */
+
+/* ---- Euclidean distance field of the hull; erosion and opening by a ball in world units (no reference counterpart) ------------
+ * vc_hull_distance computes the exact squared Euclidean distance transform of the current carve result as vc_fetch_occupancy sees
+ * it (vc_photo_carve, vc_hull_components and the footprint rules included); vc_hull_morphology erodes or opens the hull by a ball
+ * given in world units, which an index-space structuring element cannot do on an anisotropic grid.  The contract, bit for bit
+ * (tests/distance_np.py restates it).  Everything is unsigned 64-bit integer arithmetic and a minimum over a set, so the result
+ * does not depend on evaluation order.
+ *   1 input: a voxel is (ix, iy, iz) with i = (iz nx + ix) ny + iy; ON = survivor, OFF = any other voxel of the grid.
+ *   2 metric: per axis a, s_a = (max_a - min_a) / (n_a - 1) in float64 and q_a = llrint(s_a * 1000.0) micrometres.
+ *     VC_ERR_ARG when an axis is shorter than 2, some q_a lies outside 1 .. 2^20 or (n_a + 1) q_a > 2^30 for some axis; with
+ *     those bounds every d2 below is < 2^62.  VC_ERR_ARG also when an axis is longer than 4096 cells (a limit of this build: the
+ *     kernels hold a line's positions in 16 bits and a y line's site words in shared memory).  d2(v, w) = (q_x dix)^2 + (q_y diy)^2 + (q_z diz)^2 in um^2.
+ *   3 inside field: D_in(v) = min over sites w of d2(v, w).  The sites are the OFF voxels and, with VC_DIST_BORDER_OFF, one virtual
+ *     OFF layer around the grid: every position with exactly one coordinate equal to -1 or n_a and the other two inside the grid.
+ *     D_in of an OFF voxel is 0; with no site at all (a full grid, border open) D_in is UINT64_MAX.
+ *   4 outside field (only with VC_DIST_OUTSIDE): D_out(v) = min over ON voxels w of d2(v, w); 0 on ON voxels, UINT64_MAX when the
+ *     hull is empty; the border never contributes.
+ *   5 erosion by r2 (um^2): E = { v ON : D_in(v) > r2 }.
+ *   6 opening by r2: O = { v ON : min over e in E of d2(v, e) <= r2 }; empty when E is; r2 = 0 is the identity whenever a site
+ *     exists.
+ *   7 after vc_hull_morphology: records, count and occupancy hold the kept survivors only (E for VC_MORPH_ERODE, O for
+ *     VC_MORPH_OPEN), records in ascending order with colour and seen byte unchanged -- the hand-over vc_hull_components makes.
+ *     vc_fetch_viewmask and vc_expand_entries stay the silhouette carve's.  Visibility, depth maps, photo rounds, component labels
+ *     and a stored distance field fail until their pass runs again.  The next carve restores the visual hull.
+ * vc_fetch_record_distance: u64 [S], D_in of each record in record order.  vc_fetch_distance: the dense field, u64 [N] in linear
+ * index, which = 0 inside, 1 outside (needs VC_DIST_OUTSIDE).  The fetch calls fail until vc_hull_distance has run on the current
+ * result, and again after anything that changes the result.  vc_hull_morphology computes what it needs itself.
+ * stats (required): survivors; sites_inside_box (a diagnostic: site cells of the box the inside transform ran over, the hull's
+ * index box grown by one cell per side); max_d2 = max D_in over ON, 0 on an empty hull; q = q_x, q_y, q_z; eroded = |E|;
+ * distance_ms / morph_ms = HIP events around the whole call.  flags of vc_hull_morphology: VC_DIST_BORDER_OFF only.
+ * VC_ERR_ARG (with a message) when there is no carve result, steps are in flight, the carve ran with VC_FLAG_NO_RECORDS, the slab
+ * is narrower than the grid, a communicator of more than one rank is attached, flags or op are unknown, stats == NULL or the
+ * metric is out of range (2).  An allocation failure returns VC_ERR_OOM and leaves the result untouched.  S = 0 is no error.
+ * Synchronous, one read-back in the middle (the survivors' box). */
+#define VC_DIST_BORDER_OFF 1u
+#define VC_DIST_OUTSIDE    2u
+#define VC_MORPH_ERODE 0u
+#define VC_MORPH_OPEN  1u
+typedef struct {
+    uint64_t survivors, sites_inside_box /* diagnostic */, max_d2 /* max D_in over ON, 0 if none */;
+    uint64_t q[3];                  /* x, y, z in um */
+    float distance_ms;              /* HIP events around the whole call */
+} vc_distance_stats_t;
+typedef struct {
+    uint64_t survivors_before, eroded /* |E| */, survivors_after, max_d2;
+    uint64_t q[3];
+    float morph_ms;
+} vc_morph_stats_t;
+int vc_hull_distance(vc_ctx *ctx, uint32_t flags, vc_distance_stats_t *stats);
+int vc_fetch_record_distance(vc_ctx *ctx, uint64_t *d2);           /* [S], D_in of each record, record order */
+int vc_fetch_distance(vc_ctx *ctx, uint32_t which, uint64_t *d2);  /* dense [N] in linear index; 0 = inside, 1 = outside */
+int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_morph_stats_t *stats);
 
 /* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
  *      executable.py) -----------------------------------------------------------------------------------------------------------

@@ -16,6 +16,10 @@ VC_FLAG_VIEWMASK = 1
 VC_FLAG_NO_RECORDS = 2
 VC_FOOT_ANY = 1
 VC_FOOT_COVER = 2
+VC_DIST_BORDER_OFF = 1
+VC_DIST_OUTSIDE = 2
+VC_MORPH_ERODE = 0
+VC_MORPH_OPEN = 1
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
 VC_MAX_MOG_MODELS = 64
@@ -33,11 +37,12 @@ c_f64p = ctypes.POINTER(ctypes.c_double)
 c_ctx = ctypes.c_void_p
 
 
-VC_KERNEL_KINDS, VC_WORK_KINDS = 14, 8
+VC_KERNEL_KINDS, VC_WORK_KINDS = 18, 10
 KERNEL_KINDS = ("k_prep_pack", "k_prep_grid", "k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble", "k_scan_groups",
-                "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups", "foot_table", "k_carve_foot")
+                "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups", "foot_table", "k_carve_foot",
+                "k_dist_box", "k_dist_y", "k_dist_env", "k_dist_records")
 WORK_KINDS = ("word_boxes", "table_entries", "projections", "emit_projections", "brick_boxes", "foot_projections", "foot_union_skips",
-              "foot_words")
+              "foot_words", "dist_cells", "dist_lines")
 
 
 class VcTiming(ctypes.Structure):
@@ -72,6 +77,16 @@ class VcRenderStats(ctypes.Structure):
 class VcComponentStats(ctypes.Structure):
     _fields_ = [("components", ctypes.c_uint32), ("components_kept", ctypes.c_uint32), ("survivors_before", ctypes.c_uint64),
                 ("survivors_after", ctypes.c_uint64), ("largest", ctypes.c_uint32), ("components_ms", ctypes.c_float)]
+
+
+class VcDistanceStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("sites_inside_box", ctypes.c_uint64), ("max_d2", ctypes.c_uint64),
+                ("q", ctypes.c_uint64 * 3), ("distance_ms", ctypes.c_float)]
+
+
+class VcMorphStats(ctypes.Structure):
+    _fields_ = [("survivors_before", ctypes.c_uint64), ("eroded", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64),
+                ("max_d2", ctypes.c_uint64), ("q", ctypes.c_uint64 * 3), ("morph_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -154,6 +169,10 @@ SIGNATURES = {
     "vc_fetch_mesh": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_float), c_u32p]),
     "vc_surface_mesh": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcSurfaceStats)]),
     "vc_fetch_surface_mesh": (ctypes.c_int, [c_ctx, c_f64p, c_u32p, c_u8p, c_u8p]),
+    "vc_hull_distance": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.POINTER(VcDistanceStats)]),
+    "vc_fetch_record_distance": (ctypes.c_int, [c_ctx, c_u64p]),
+    "vc_fetch_distance": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u64p]),
+    "vc_hull_morphology": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcMorphStats)]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

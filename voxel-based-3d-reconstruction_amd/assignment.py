@@ -162,7 +162,8 @@ _source = None
 _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused",
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
              "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
-             "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre"}
+             "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
+             "hull_open_mm": 0.0, "hull_border": "open"}
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -180,7 +181,11 @@ def configure(frame_source=None, **settings):
     kept.  0 and 0 (the default) keep every survivor.
     footprint: "centre" (default) asks, as the reference does, whether the pixel under a voxel's centre is foreground; "any",
     "all" and ("cover", q) test the pixel box the voxel's whole cell projects to (CarveEngine.carve(footprint=...)): "any" keeps
-    what is thinner than a voxel (the outer hull), "all" gives the inner hull."""
+    what is thinner than a voxel (the outer hull), "all" gives the inner hull.
+    hull_open_mm, hull_border: when hull_open_mm > 0, every carve is followed by CarveEngine.open_hull(hull_open_mm,
+    border=hull_border), before the component filter, any photo carve and any colouring: what is thinner than a ball of that
+    radius in world millimetres leaves the hull (spurs, fins and specks of mask noise, attached to the figure or not);
+    voxels_status() describes what is kept.  0 (the default) keeps every survivor."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -190,6 +195,8 @@ def configure(frame_source=None, **settings):
     if settings.get("hull", _settings["hull"]) not in HULLS:
         raise ValueError("hull %r, expected one of %s" % (settings["hull"], HULLS))
     footprint_rule(settings.get("footprint", _settings["footprint"]))          # raises ValueError on anything else
+    CarveEngine.radius_r2(settings.get("hull_open_mm", _settings["hull_open_mm"]))   # ... on a negative or non-finite radius
+    CarveEngine._dist_flags(settings.get("hull_border", _settings["hull_border"]))
     _settings.update(settings)
     _source = frame_source
     if _engine is not None:
@@ -249,6 +256,8 @@ def set_voxel_positions(width, height, depth):
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"],
                   footprint=_settings["footprint"])
+    if _settings["hull_open_mm"] > 0:
+        _engine.open_hull(_settings["hull_open_mm"], border=_settings["hull_border"])
     if _settings["min_component_voxels"] or _settings["keep_components"]:
         _engine.filter_components(connectivity=_settings["component_connectivity"], min_voxels=_settings["min_component_voxels"],
                                   keep_largest=_settings["keep_components"])

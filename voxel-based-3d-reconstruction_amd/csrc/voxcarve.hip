@@ -42,6 +42,7 @@
 #include "vc_render.h"
 #include "vc_surface.h"
 #include "vc_footprint.h"
+#include "vc_distance.h"
 
 #pragma clang fp contract(off)
 
@@ -350,6 +351,18 @@ struct vc_ctx {
     bool cc_valid = false;           // labels and components belong to the pass that produced the current result
     uint64_t cc_n = 0;               // its input survivors
     uint32_t cc_k = 0;               // its components
+    // vc_hull_distance and vc_hull_morphology: the inside field over the hull's box, the outside field over the grid, the other
+    // field of an envelope pass, the envelope stacks, the records' values, the survivors' box, [max, records above r2] x 2
+    DevBuf<uint64_t> d_dist_in, d_dist_out, d_dist_tmp, d_dist_rec;
+    DevBuf<uint32_t> d_dist_st, d_dist_box;
+    DevBuf<unsigned long long> d_dist_acc;
+    bool dist_valid = false;         // the fields belong to the vc_hull_distance that ran on the current result
+    bool dist_outside = false;       // ... with VC_DIST_OUTSIDE
+    uint64_t dist_n = 0;             // its survivors
+    DistBox dist_box = {};           // the box of d_dist_in
+    std::vector<hipEvent_t> dist_ev; // timing_detail: begin / end events of the passes' launches, made on first use
+    std::vector<int> dist_ev_kind;   // the kernel kind of each pair the running call has used
+    uint64_t dist_work[2] = {0, 0};  // VC_WORK_DIST_CELLS, VC_WORK_DIST_LINES since vc_timing_reset
     // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
     DevBuf<uint32_t> d_rn_idx, d_rn_rgbf;
     DevBuf<float> d_rn_depth;
@@ -1320,6 +1333,9 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_cc_woff); release(ctx->d_cc_parent); release(ctx->d_cc_label); release(ctx->d_cc_cid); release(ctx->d_cc_roots);
     release(ctx->d_cc_size); release(ctx->d_cc_box); release(ctx->d_cc_comp); release(ctx->d_cc_misc); release(ctx->d_cc_kept);
     release(ctx->d_cc_thr);
+    release(ctx->d_dist_in); release(ctx->d_dist_out); release(ctx->d_dist_tmp); release(ctx->d_dist_rec); release(ctx->d_dist_st);
+    release(ctx->d_dist_box); release(ctx->d_dist_acc);
+    for (hipEvent_t e : ctx->dist_ev) (void)hipEventDestroy(e);
     release(ctx->d_rn_idx); release(ctx->d_rn_rgbf); release(ctx->d_rn_depth); release(ctx->d_rn_views); release(ctx->d_rn_map);
     release(ctx->d_rn_ctr);
     release(ctx->d_sf_edges); release(ctx->d_sf_verts); release(ctx->d_sf_faces); release(ctx->d_sf_rgb); release(ctx->d_sf_refined);
@@ -1374,7 +1390,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1387,7 +1403,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1431,7 +1447,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1692,7 +1708,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;   // the next carve invalidates what the post-carve passes left
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -2036,7 +2052,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2373,7 +2389,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
@@ -2455,7 +2471,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
     const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
     if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
@@ -2573,6 +2589,288 @@ int vc_fetch_components(vc_ctx *ctx, vc_component_t *out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     static_assert(sizeof(vc_component_t) == kCcCompWords * sizeof(uint32_t), "vc_component_t is the device's entry");
     if (ctx->cc_k) VC_HIP(ctx, hipMemcpy(out, ctx->d_cc_comp.ptr, (size_t)ctx->cc_k * sizeof(vc_component_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+// ---- distance field of the current carve result; erosion and opening (vc_distance.h; contract in include/voxcarve.h) ----
+// timing_detail: the begin / end events a launch of the distance passes is to carry (null otherwise: an ordinary launch)
+static void dist_events(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
+{
+    start = stop = nullptr;
+    if (!ctx->timing_detail) return;
+    const size_t at = 2 * ctx->dist_ev_kind.size();
+    while (ctx->dist_ev.size() < at + 2) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) return;
+        ctx->dist_ev.push_back(e);
+    }
+    start = ctx->dist_ev[at]; stop = ctx->dist_ev[at + 1];
+    ctx->dist_ev_kind.push_back(kind);
+}
+#define VC_DLAUNCH(kind, kernel, grid, block, ...)                                                      \
+    do {                                                                                                \
+        hipEvent_t ks_, ke_;                                                                            \
+        dist_events(ctx, kind, ks_, ke_);                                                               \
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ks_, ke_, 0, __VA_ARGS__);           \
+    } while (0)
+
+// after the call's stream has drained: the launches' times into vc_timing_t
+static void dist_harvest(vc_ctx *ctx)
+{
+    for (size_t k = 0; k < ctx->dist_ev_kind.size(); ++k) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ctx->dist_ev[2 * k], ctx->dist_ev[2 * k + 1]) == hipSuccess) {
+            ctx->tm.kernel_ms_sum[ctx->dist_ev_kind[k]] += ms;
+            ctx->tm.kernel_launches[ctx->dist_ev_kind[k]] += 1;
+        }
+    }
+    ctx->dist_ev_kind.clear();
+}
+
+// Item 2 of the contract: the steps in micrometres, q = x, y, z.
+static int dist_metric(vc_ctx *ctx, const char *what, uint64_t q[3])
+{
+    const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
+    for (int a = 0; a < 3; ++a) {
+        if (n[a] < 2) return fail(ctx, VC_ERR_ARG, "%s: axis %c has %u cells, a step needs 2", what, "xyz"[a], n[a]);
+        const double s = (ctx->bounds[2 * a + 1] - ctx->bounds[2 * a]) / (double)(n[a] - 1);
+        const long long v = llrint(s * 1000.0);
+        if (!(s * 1000.0 >= 0.5) || !(s * 1000.0 < 2097152.0) || v < 1 || v > (1ll << 20))
+            return fail(ctx, VC_ERR_ARG, "%s: the step of axis %c is %g mm, outside 1 um .. 2^20 um", what, "xyz"[a], s);
+        if ((uint64_t)(n[a] + 1) * (uint64_t)v > (1ull << 30))
+            return fail(ctx, VC_ERR_ARG, "%s: axis %c spans (%u + 1) x %lld um, above 2^30 um", what, "xyz"[a], n[a], v);
+        if (n[a] + 2 > kDistMaxLine)
+            return fail(ctx, VC_ERR_ARG, "%s: axis %c has %u cells, lines hold at most %u", what, "xyz"[a], n[a], kDistMaxLine - 2);
+        q[a] = (uint64_t)v;
+    }
+    return VC_OK;
+}
+
+static uint64_t dist_cells(const DistBox &bx) { return (uint64_t)bx.b[0] * bx.b[1] * bx.b[2]; }
+
+// Sizes the fields of a transform over bx: f, the other field of the envelope passes and the stacks.
+static int dist_ensure(vc_ctx *ctx, DevBuf<uint64_t> &f, const DistBox &bx)
+{
+    const uint64_t cells = dist_cells(bx);
+    VC_TRY(ensure(ctx, f, (size_t)cells));
+    VC_TRY(ensure(ctx, ctx->d_dist_tmp, (size_t)cells));
+    VC_TRY(ensure(ctx, ctx->d_dist_st, (size_t)cells));
+    return VC_OK;
+}
+
+// Queues one transform over bx on the context's stream: f = squared distance to the nearest site of `mode` (kDistSiteAbove: the
+// cells of f itself above r2).  Buffers sized by dist_ensure.
+static int dist_transform(vc_ctx *ctx, const DistBox &bx, int mode, const uint64_t *words, uint64_t *f, uint64_t r2, const uint64_t q[3])
+{
+    const uint64_t plane = (uint64_t)bx.b[0] * bx.b[1], ylines = (uint64_t)bx.b[0] * bx.b[2], xlines = (uint64_t)bx.b[1] * bx.b[2];
+    const dim3 block(kDistBlock), ygrid((uint32_t)((ylines + kDistBlock / 64 - 1) / (kDistBlock / 64)));
+    if (mode == kDistSiteOff) VC_DLAUNCH(VC_K_DIST_Y, k_dist_y<kDistSiteOff>, ygrid, block, bx, words, f, r2, q[1]);
+    else if (mode == kDistSiteOn) VC_DLAUNCH(VC_K_DIST_Y, k_dist_y<kDistSiteOn>, ygrid, block, bx, words, f, r2, q[1]);
+    else VC_DLAUNCH(VC_K_DIST_Y, k_dist_y<kDistSiteAbove>, ygrid, block, bx, words, f, r2, q[1]);
+    // along x: line (lz, ly) from f into the other field; along z: line (lx, ly) back into f
+    VC_DLAUNCH(VC_K_DIST_ENV, k_dist_env, dim3((uint32_t)((xlines + kDistBlock - 1) / kDistBlock)), block, (const uint64_t *)f,
+               ctx->d_dist_tmp.ptr, ctx->d_dist_st.ptr, xlines, (uint64_t)bx.b[1], plane, (uint64_t)bx.b[1], bx.b[0], q[0] * q[0]);
+    VC_DLAUNCH(VC_K_DIST_ENV, k_dist_env, dim3((uint32_t)((plane + kDistBlock - 1) / kDistBlock)), block,
+               (const uint64_t *)ctx->d_dist_tmp.ptr, f, ctx->d_dist_st.ptr, plane, plane, (uint64_t)0, plane, bx.b[2], q[2] * q[2]);
+    VC_HIP(ctx, hipGetLastError());
+    ctx->dist_work[0] += dist_cells(bx);
+    ctx->dist_work[1] += ylines + xlines + plane;
+    return VC_OK;
+}
+
+// Queues the records' values of the box field f: d_dist_rec[s], and acc[0] = their maximum, acc[1] = how many lie above r2.
+static int dist_records(vc_ctx *ctx, StepBuf &cur, const DistBox &bx, const uint64_t *f, uint64_t S, uint64_t r2, unsigned long long *acc)
+{
+    VC_HIP(ctx, hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    VC_DLAUNCH(VC_K_DIST_RECORDS, k_dist_records, dim3((uint32_t)((S + kDistGroup - 1) / kDistGroup)), dim3(kDistBlock), bx,
+               (const uint64_t *)cur.records.ptr, S, f, r2, ctx->d_dist_rec.ptr, acc);
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
+// The inside field of the current result's S > 0 records: their index box (one read-back), grown by a cell per side and, with
+// the border open, clipped to the grid; the transform into d_dist_in over that box; the records' values and acc[0..1] against r2.
+static int dist_inside(vc_ctx *ctx, StepBuf &cur, uint32_t flags, uint64_t S, uint64_t r2, const uint64_t q[3], DistBox &bx)
+{
+    VC_TRY(ensure(ctx, ctx->d_dist_box, 6));
+    VC_TRY(ensure(ctx, ctx->d_dist_acc, 4));
+    VC_TRY(ensure(ctx, ctx->d_dist_rec, (size_t)S));
+    uint32_t *hb = reinterpret_cast<uint32_t *>(ctx->h_res);
+    hb[0] = hb[1] = hb[2] = 0xffffffffu; hb[3] = hb[4] = hb[5] = 0;
+    VC_HIP(ctx, hipMemcpyAsync(ctx->d_dist_box.ptr, hb, 6 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VC_DLAUNCH(VC_K_DIST_BOX, k_dist_box, dim3((uint32_t)((S + kDistGroup - 1) / kDistGroup)), dim3(kDistBlock),
+               (const uint64_t *)cur.records.ptr, S, ctx->nx, ctx->ny, ctx->d_dist_box.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipMemcpyAsync(hb, ctx->d_dist_box.ptr, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
+    memset(&bx, 0, sizeof bx);
+    bx.nx = ctx->nx; bx.ny = ctx->ny; bx.nz = ctx->nz;
+    for (int a = 0; a < 3; ++a) {
+        if (hb[a] > hb[3 + a] || hb[3 + a] >= n[a])
+            return fail(ctx, VC_ERR_HIP, "the survivors' box [%u, %u] on axis %c of %u cells", hb[a], hb[3 + a], "xyz"[a], n[a]);
+        int32_t lo = (int32_t)hb[a] - 1, hi = (int32_t)hb[3 + a] + 1;
+        if (!(flags & VC_DIST_BORDER_OFF)) { lo = lo < 0 ? 0 : lo; hi = hi >= (int32_t)n[a] ? (int32_t)n[a] - 1 : hi; }
+        bx.o[a] = lo;
+        bx.b[a] = (uint32_t)(hi - lo + 1);
+    }
+    VC_TRY(dist_ensure(ctx, ctx->d_dist_in, bx));
+    VC_TRY(dist_transform(ctx, bx, kDistSiteOff, cur.words.ptr, ctx->d_dist_in.ptr, 0, q));
+    VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S, r2, ctx->d_dist_acc.ptr));
+    return VC_OK;
+}
+
+int vc_hull_distance(vc_ctx *ctx, uint32_t flags, vc_distance_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_distance: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags & ~(VC_DIST_BORDER_OFF | VC_DIST_OUTSIDE))
+        return fail(ctx, VC_ERR_ARG, "vc_hull_distance: unknown flags %u (VC_DIST_BORDER_OFF | VC_DIST_OUTSIDE)", flags);
+    VC_TRY(result_refusals(ctx, "vc_hull_distance", "measure", "distance transforms"));
+    uint64_t q[3];
+    VC_TRY(dist_metric(ctx, "vc_hull_distance", q));
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->dist_valid = false;
+    ctx->dist_ev_kind.clear();
+    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    const bool outside = (flags & VC_DIST_OUTSIDE) != 0;
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    DistBox bx;
+    memset(&bx, 0, sizeof bx);
+    if (S) {
+        VC_TRY(densify_words(ctx, cur));
+        VC_TRY(dist_inside(ctx, cur, flags, S, 0, q, bx));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_dist_acc.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (outside) {
+        if (S) {
+            DistBox all;
+            memset(&all, 0, sizeof all);
+            all.nx = all.b[0] = ctx->nx; all.ny = all.b[1] = ctx->ny; all.nz = all.b[2] = ctx->nz;
+            VC_TRY(dist_ensure(ctx, ctx->d_dist_out, all));
+            VC_TRY(dist_transform(ctx, all, kDistSiteOn, cur.words.ptr, ctx->d_dist_out.ptr, 0, q));
+        } else {
+            VC_TRY(ensure(ctx, ctx->d_dist_out, (size_t)n));
+            VC_HIP(ctx, hipMemsetAsync(ctx->d_dist_out.ptr, 0xff, (size_t)n * sizeof(uint64_t), ctx->stream));
+        }
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    dist_harvest(ctx);
+    VC_HIP(ctx, hipEventElapsedTime(&stats->distance_ms, ctx->ev[0], ctx->ev[1]));
+    stats->survivors = S;
+    stats->sites_inside_box = S ? dist_cells(bx) - S : 0;
+    stats->max_d2 = S ? ctx->h_res[0] : 0;
+    for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
+    ctx->dist_valid = true;
+    ctx->dist_outside = outside;
+    ctx->dist_n = S;
+    ctx->dist_box = bx;
+    return VC_OK;
+}
+
+int vc_fetch_record_distance(vc_ctx *ctx, uint64_t *d2)
+{
+    if (!ctx || !d2) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->dist_valid) return fail(ctx, VC_ERR_ARG, "no distance field: call vc_hull_distance on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->dist_n) VC_HIP(ctx, hipMemcpy(d2, ctx->d_dist_rec.ptr, (size_t)ctx->dist_n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_distance(vc_ctx *ctx, uint32_t which, uint64_t *d2)
+{
+    if (!ctx || !d2) return VC_ERR_ARG;
+    if (which > 1) return fail(ctx, VC_ERR_ARG, "vc_fetch_distance: which = %u, expected 0 (inside) or 1 (outside)", which);
+    if (!ctx->carved || !ctx->dist_valid) return fail(ctx, VC_ERR_ARG, "no distance field: call vc_hull_distance on the current carve result");
+    if (which == 1 && !ctx->dist_outside)
+        return fail(ctx, VC_ERR_ARG, "no outside field: the last vc_hull_distance ran without VC_DIST_OUTSIDE");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t n = ctx->n_voxels();
+    if (which == 1) {
+        if (n) VC_HIP(ctx, hipMemcpy(d2, ctx->d_dist_out.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        return VC_OK;
+    }
+    memset(d2, 0, (size_t)n * sizeof(uint64_t));                 // zero off the box: every voxel there is OFF
+    if (!ctx->dist_n) return VC_OK;
+    const DistBox &bx = ctx->dist_box;
+    std::vector<uint64_t> h((size_t)dist_cells(bx));
+    VC_HIP(ctx, hipMemcpy(h.data(), ctx->d_dist_in.ptr, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    // the rows of the box that lie in the grid, cut to the grid along y
+    const int32_t y0 = bx.o[1] < 0 ? 0 : bx.o[1], y1 = std::min<int32_t>(bx.o[1] + (int32_t)bx.b[1], (int32_t)bx.ny);
+    for (uint32_t lz = 0; lz < bx.b[2]; ++lz) {
+        const int32_t gz = bx.o[2] + (int32_t)lz;
+        if (gz < 0 || gz >= (int32_t)bx.nz) continue;
+        for (uint32_t lx = 0; lx < bx.b[0]; ++lx) {
+            const int32_t gx = bx.o[0] + (int32_t)lx;
+            if (gx < 0 || gx >= (int32_t)bx.nx) continue;
+            const uint64_t *src = h.data() + ((size_t)lz * bx.b[0] + lx) * bx.b[1] + (size_t)(y0 - bx.o[1]);
+            memcpy(d2 + ((size_t)gz * bx.nx + (size_t)gx) * bx.ny + (size_t)y0, src, (size_t)(y1 - y0) * sizeof(uint64_t));
+        }
+    }
+    return VC_OK;
+}
+
+int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_morph_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_morphology: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (op != VC_MORPH_ERODE && op != VC_MORPH_OPEN)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_morphology: unknown op %u (VC_MORPH_ERODE, VC_MORPH_OPEN)", op);
+    if (flags & ~VC_DIST_BORDER_OFF) return fail(ctx, VC_ERR_ARG, "vc_hull_morphology: unknown flags %u (VC_DIST_BORDER_OFF)", flags);
+    VC_TRY(result_refusals(ctx, "vc_hull_morphology", "keep", "morphology"));
+    uint64_t q[3];
+    VC_TRY(dist_metric(ctx, "vc_hull_morphology", q));
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->dist_ev_kind.clear();
+    const uint64_t S0 = ctx->survivors;
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    if (S0) {                                    // every buffer of the hand-over before anything is queued: a failure leaves the result
+        VC_TRY(ensure(ctx, ctx->d_rec_spare, cur.records.cap));
+        VC_TRY(ensure(ctx, ctx->d_rscan, (uint32_t)((S0 + kCompactGroup - 1) / kCompactGroup)));
+    }
+    if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (S0) {
+        DistBox bx;
+        VC_TRY(densify_words(ctx, cur));
+        VC_TRY(dist_inside(ctx, cur, flags, S0, r2, q, bx));     // 5: d_dist_rec = D_in, acc = [max D_in, |E|]
+        if (op == VC_MORPH_OPEN) {                               // 6: the same transform with sites = E, over the same box
+            VC_TRY(dist_transform(ctx, bx, kDistSiteAbove, cur.words.ptr, ctx->d_dist_in.ptr, r2, q));
+            VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S0, r2, ctx->d_dist_acc.ptr + 2));
+        }
+        // the result changes from here on
+        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+        VC_TRY(compact_records(ctx, cur, DistKept{ctx->d_dist_rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
+                               S0, ctx->h_res + 1));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->d_dist_acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_dist_acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    dist_harvest(ctx);
+    uint64_t kept = 0;
+    if (S0) {
+        kept = ctx->h_res[1];
+        if (kept > S0) return fail(ctx, VC_ERR_HIP, "vc_hull_morphology: kept %llu of %llu records", (unsigned long long)kept, (unsigned long long)S0);
+        ctx->survivors = cur.survivors = kept;
+        stats->max_d2 = ctx->h_res[0];
+        stats->eroded = ctx->h_res[2];
+    }
+    VC_HIP(ctx, hipEventElapsedTime(&stats->morph_ms, ctx->ev[0], ctx->ev[1]));
+    stats->survivors_before = S0;
+    stats->survivors_after = kept;
+    for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
     return VC_OK;
 }
 
@@ -3421,6 +3719,8 @@ int vc_timing(vc_ctx *ctx, vc_timing_t *out)
         for (int w = 0; w < VC_WORK_KINDS; ++w)
             for (uint32_t k = 0; k < kShards; ++k) ctx->tm.work[w] += h[((size_t)w * kShards + k) * kStatStride];
     }
+    ctx->tm.work[VC_WORK_DIST_CELLS] += ctx->dist_work[0];       // (counted on the host: the boxes are known there)
+    ctx->tm.work[VC_WORK_DIST_LINES] += ctx->dist_work[1];
     *out = ctx->tm;
     return VC_OK;
 }
@@ -3442,6 +3742,7 @@ int vc_timing_reset(vc_ctx *ctx)
     ctx->tm.emit_launches = 0;
     memset(ctx->tm.kernel_ms_sum, 0, sizeof ctx->tm.kernel_ms_sum);
     memset(ctx->tm.kernel_launches, 0, sizeof ctx->tm.kernel_launches);
+    ctx->dist_work[0] = ctx->dist_work[1] = 0;
     if (ctx->d_stats.ptr && ctx->npending == 0) {
         VC_HIP(ctx, hipSetDevice(ctx->device));
         VC_HIP(ctx, hipMemset(ctx->d_stats.ptr, 0, ctx->d_stats.cap * sizeof(unsigned long long)));

@@ -516,6 +516,82 @@ class CarveEngine:
         return {"label": raw[:, 0].copy(), "size": raw[:, 1].copy(), "lo": raw[:, 2:5].copy(), "hi": raw[:, 5:8].copy(),
                 "kept": raw[:, 8] != 0}
 
+    # -- distance field of the hull, erosion and opening by a ball in mm (vc_hull_distance, vc_hull_morphology) -------------------
+    @staticmethod
+    def _dist_flags(border, outside=False):
+        if border not in ("open", "off"):
+            raise ValueError('border %r, expected "open" or "off"' % (border,))
+        return (_lib.VC_DIST_BORDER_OFF if border == "off" else 0) | (_lib.VC_DIST_OUTSIDE if outside else 0)
+
+    def hull_distance(self, border="open", outside=False):
+        """The exact squared Euclidean distance transform of the current carve result in um^2 (contract: include/voxcarve.h):
+        for every survivor the distance to the nearest voxel that is not one (border="off": or to one virtual layer of such
+        voxels around the grid) and, with outside=True, for every voxel of the grid the distance to the nearest survivor.  The
+        grid steps are rounded to whole micrometres; everything is integer and exact.  Returns the stats as a dict: survivors,
+        sites_inside_box, max_d2, q (x, y, z in um), distance_ms.  The fetch_* calls below read the fields."""
+        st = _lib.VcDistanceStats()
+        self._check(self._L.vc_hull_distance(self._ctx, self._dist_flags(border, outside), ctypes.byref(st)), "vc_hull_distance")
+        return {"survivors": int(st.survivors), "sites_inside_box": int(st.sites_inside_box), "max_d2": int(st.max_d2),
+                "q": tuple(int(v) for v in st.q), "distance_ms": float(st.distance_ms)}
+
+    def fetch_record_distance(self):
+        """u64 [S] in record order: the squared inside distance of each survivor in um^2 (after hull_distance, which leaves
+        the records alone: S is the current count; the call fails once anything has changed the result)."""
+        out = np.empty(self.count, dtype=np.uint64)
+        self._check(self._L.vc_fetch_record_distance(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_fetch_record_distance")
+        return out
+
+    def fetch_record_depth(self):
+        """float64 [S] in record order: how deep inside the hull each survivor lies, in mm (its local half-thickness)."""
+        return np.sqrt(self.fetch_record_distance().astype(np.float64)) / 1000
+
+    def fetch_distance_raw(self, which="inside"):
+        """u64 [nz, nx, ny]: the dense squared field in um^2, which = "inside" | "outside"; 2^64 - 1 where there is no site."""
+        if which not in ("inside", "outside"):
+            raise ValueError('which %r, expected "inside" or "outside"' % (which,))
+        out = np.empty(self.n_voxels, dtype=np.uint64)
+        self._check(self._L.vc_fetch_distance(self._ctx, 1 if which == "outside" else 0, _ptr(out, ctypes.c_uint64)), "vc_fetch_distance")
+        nx, ny, nz = self.grid
+        return out.reshape(nz, nx, ny)
+
+    def fetch_distance_field(self, which="inside"):
+        """float64 [nz, nx, ny] in mm: which = "inside" (depth of the survivors, 0 elsewhere), "outside" (distance to the hull,
+        0 on it; needs hull_distance(outside=True)) or "signed" (outside minus inside)."""
+        if which == "signed":
+            return self.fetch_distance_field("outside") - self.fetch_distance_field("inside")
+        return np.sqrt(self.fetch_distance_raw(which).astype(np.float64)) / 1000
+
+    @staticmethod
+    def radius_r2(radius_mm):
+        """r2 in um^2 of a ball of radius_mm: round(radius_mm * 1000) squared."""
+        r = float(radius_mm)
+        if not np.isfinite(r) or r < 0:
+            raise ValueError("radius %r mm, expected a finite value >= 0" % (radius_mm,))
+        r_um = int(round(r * 1000.0))
+        return r_um * r_um
+
+    def _morphology(self, op, r2, border):
+        if r2 >= 1 << 64:
+            raise ValueError("radius^2 = %d um^2 does not fit 64 bits" % r2)
+        st = _lib.VcMorphStats()
+        self._check(self._L.vc_hull_morphology(self._ctx, op, int(r2), self._dist_flags(border), ctypes.byref(st)), "vc_hull_morphology")
+        self.count = int(st.survivors_after)
+        return {"survivors_before": int(st.survivors_before), "eroded": int(st.eroded), "survivors_after": int(st.survivors_after),
+                "max_d2": int(st.max_d2), "q": tuple(int(v) for v in st.q), "morph_ms": float(st.morph_ms)}
+
+    def erode_hull(self, radius_mm, border="open"):
+        """Erodes the current carve result by a ball of radius_mm millimetres (a Euclidean ball in world units, whatever the grid's
+        anisotropy): the survivors whose inside distance is above the radius stay, r2 = round(radius_mm * 1000)^2 um^2.  The
+        records, the count and the occupancy then describe the eroded hull; the next carve restores the visual hull.  Returns
+        the stats as a dict: survivors_before, eroded, survivors_after, max_d2, q, morph_ms."""
+        return self._morphology(_lib.VC_MORPH_ERODE, self.radius_r2(radius_mm), border)
+
+    def open_hull(self, radius_mm, border="open"):
+        """Opens the current carve result by a ball of radius_mm millimetres: what is thinner than the ball -- spurs, fins, thin
+        bridges and specks of mask noise, attached to the figure or not -- leaves the hull, the rest keeps its shape (the
+        survivors within the radius of the eroded set stay).  Arguments, effects and stats as erode_hull."""
+        return self._morphology(_lib.VC_MORPH_OPEN, self.radius_r2(radius_mm), border)
+
     # -- ray-cast images of the current result (vc_render) --------------------------------------------------------------------------
     def render(self, views, H, W, shade=None, background=(0, 0, 0)):
         """Ray-casts the current carve result (after color_visible / photo_carve / filter_components, as fetch sees it) from each
