@@ -65,9 +65,11 @@ typedef enum {
     VC_K_CULL /* in front of a one-launch kernel */, VC_K_COUNT_GROUPS,
     VC_K_FOOT_TABLE /* k_foot_rows + k_foot_cols */, VC_K_FOOT_CARVE /* k_carve_foot */,
     VC_K_DIST_BOX /* k_dist_box */, VC_K_DIST_Y /* k_dist_y */, VC_K_DIST_ENV /* k_dist_env, along x and along z */,
-    VC_K_DIST_RECORDS /* k_dist_records */
+    VC_K_DIST_RECORDS /* k_dist_records */,
+    VC_K_GROW_MARK /* k_grow_mark: the new set's bits and counts */, VC_K_GROW_RANK /* k_grow_apply, k_count_groups, k_cc_wcount, k_cc_woff */,
+    VC_K_GROW_MERGE /* k_grow_old + k_grow_new */
 } vc_kernel_kind;
-#define VC_KERNEL_KINDS 18
+#define VC_KERNEL_KINDS 21
 enum {
     VC_WORK_WORD_BOXES = 0,   /* 8-byte word boxes k_brick_words read (listed bricks x 64 words x cameras asked)           */
     VC_WORK_TABLE_ENTRIES,    /* 4-byte table entries the per-voxel level read (VC_MODE_LUT)                                */
@@ -78,7 +80,8 @@ enum {
     VC_WORK_FOOT_UNION_SKIPS, /* (word, camera) visits of k_carve_foot that the union-box count ended: no foreground under  */
                               /* the whole word, the camera fails its 64 voxels at once                                     */
     VC_WORK_FOOT_WORDS,       /* occupancy words k_carve_foot took                                                          */
-    VC_WORK_DIST_CELLS,       /* cells of the boxes the distance transforms ran over (vc_hull_distance, vc_hull_morphology),   */
+    VC_WORK_DIST_CELLS,       /* cells of the boxes the distance transforms ran over (vc_hull_distance, vc_hull_morphology,    */
+                              /* vc_hull_grow),                                                                               */
                               /* one count per transform: each of its three passes reads and writes that many 8-byte values   */
     VC_WORK_DIST_LINES        /* lines k_dist_y and k_dist_env walked                                                        */
 };
@@ -396,6 +399,53 @@ int vc_hull_distance(vc_ctx *ctx, uint32_t flags, vc_distance_stats_t *stats);
 int vc_fetch_record_distance(vc_ctx *ctx, uint64_t *d2);           /* [S], D_in of each record, record order */
 int vc_fetch_distance(vc_ctx *ctx, uint32_t which, uint64_t *d2);  /* dense [N] in linear index; 0 = inside, 1 = outside */
 int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_morph_stats_t *stats);
+
+/* ---- dilation and closing of the hull by a ball in world units: the growing half of the morphology (no reference counterpart) --
+ * Every other pass over a carve result can only take voxels away.  vc_hull_grow ADDS survivors: it dilates or closes the current
+ * carve result, as vc_fetch_occupancy sees it, by a ball of squared radius r2 in um^2, and creates the records of the voxels it
+ * adds.  A closing fills what is narrower than the ball -- the tunnel that a hole in one camera's mask carves through the figure --
+ * and leaves the rest of the hull as it is.  The contract, bit for bit (tests/closing_np.py restates it).  Unsigned 64-bit integers
+ * only; the metric q_a and d2 are exactly those of vc_hull_distance (items 1 and 2 above), with the same refusals.
+ *   1 dilation: Dl = { v in the grid : min over ON voxels w of d2(v, w) <= r2 }.  Empty for an empty hull.  Clipped to the grid:
+ *     there are no voxels outside it.
+ *   2 closing: C = { v in Dl : min over grid voxels u not in Dl of d2(v, u) > r2 }; when every grid voxel is in Dl the condition
+ *     holds and C is the whole grid.  The border is open: nothing outside the grid is a site.  With these two definitions dilation
+ *     and erosion are an adjunction on the subsets of the grid, so hull <= C <= Dl, the closing is idempotent (closing C again
+ *     adds nothing) and increasing (A <= B gives C(A) <= C(B)), and r2 = 0 is the identity for both ops.
+ *   3 records after the call: records, count and occupancy describe Dl (VC_GROW_DILATE) or C (VC_GROW_CLOSE), in ascending linear
+ *     index.  A record that existed keeps its 8 bytes.  An added voxel's record takes item 4 of vc_carve_footprint: the colour
+ *     camera's pixel under the voxel's CENTRE whenever the centre is inside its image, by the carve's float64 projection and
+ *     in-image test (the mask is not consulted), seen = 1; otherwise 0, 0, 0 and seen = 0, which is also what a carve without a
+ *     colour camera gives.  The colour comes from the images of the carve's frame set as that carve saw them: when the slot has
+ *     been prepared again since (new masks or images and a later preparation), the call is refused, as vc_surface_mesh is.
+ *   4 other readers: vc_fetch_viewmask and vc_expand_entries stay the silhouette carve's.  Visibility, depth maps, photo rounds,
+ *     component labels and a stored distance field fail until their pass runs again; a call that adds nothing (r2 = 0, a second
+ *     closing, an empty hull) leaves the result and with it the first four valid, and drops only the stored distance field,
+ *     whose buffer the transforms use.  The next carve restores the visual hull.
+ *     Everything that reads the step sees the grown hull exactly as it sees an opened one.  vc_surface_mesh keeps its own
+ *     contract: edges at added voxels are not bracketed by the centre test and stay at the midpoint, as for VC_FOOT_ANY.
+ *   5 VC_ERR_ARG (with a message, nothing launched) when there is no carve result, steps are in flight, the carve ran with
+ *     VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached, op is unknown,
+ *     flags != 0, stats == NULL, the metric is out of range or the slot has been prepared again.  An allocation failure returns
+ *     VC_ERR_OOM and leaves the result untouched: the added voxels are counted, and every buffer sized, before anything changes.
+ *     (The result: records, count, occupancy.  A stored distance field and an earlier call's added bytes are gone after a
+ *     failed call too: vc_fetch_distance and vc_fetch_grown fail until their pass runs again.)
+ *     S = 0 is no error and stays empty.
+ * The transforms run over the survivors' index box grown per axis by g_a + 1 cells, g_a = isqrt(r2) / q_a, and clipped to the
+ * grid (DESIGN.md section 8 item 13 has the argument); a large radius makes the box the grid.
+ * stats (required): survivors_before; dilated = |Dl|; survivors_after; added = survivors_after - survivors_before; box_cells =
+ * cells of that box; q; grow_ms = HIP events around the whole call.  vc_fetch_grown: u8 [survivors_after] in record order, 1 =
+ * the record was created by the last vc_hull_grow; fails once a carve or a pass that removes survivors has run since.
+ * Synchronous, two read-backs in the middle (the survivors' box, the count of added voxels). */
+#define VC_GROW_DILATE 0u
+#define VC_GROW_CLOSE  1u
+typedef struct {
+    uint64_t survivors_before, dilated /* |Dl| */, survivors_after, added, box_cells;
+    uint64_t q[3];
+    float grow_ms;
+} vc_grow_stats_t;
+int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags /* must be 0 */, vc_grow_stats_t *stats);
+int vc_fetch_grown(vc_ctx *ctx, uint8_t *added);   /* u8 [S_after], record order: 1 = created by the last vc_hull_grow */
 
 /* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
  *      executable.py) -----------------------------------------------------------------------------------------------------------

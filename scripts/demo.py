@@ -1,15 +1,20 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--mesh PATH] [--footprint centre|any|all] [--open MM] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--mesh PATH] [--footprint centre|any|all] [--close MM] [--open MM] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
 its vertices refined against the silhouettes on the device and coloured by the voxels, as binary PLY; --footprint: the carve's rule, assignment.configure(footprint=...) -- `any` keeps a
 voxel when any pixel its whole cell projects to is foreground (the outer hull), `all` when all of them are (the inner hull);
 --open MM: the hull opened by a ball of MM millimetres on the device after the carve, assignment.configure(hull_open_mm=MM) --
-what is thinner than the ball leaves the hull)."""
+what is thinner than the ball leaves the hull; --close MM: the hull closed by a ball of MM millimetres on the device after the
+carve and before any opening, assignment.configure(hull_close_mm=MM) -- tunnels and dents narrower than the ball are filled, which
+is what a hole in one camera's mask carves; --help: this text)."""
 import os, sys
+if "--help" in sys.argv or "-h" in sys.argv:
+    print(__doc__)
+    sys.exit(0)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
@@ -36,6 +41,11 @@ if "--open" in sys.argv:
     k = sys.argv.index("--open")
     open_mm = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
+close_mm = 0.0
+if "--close" in sys.argv:
+    k = sys.argv.index("--close")
+    close_mm = float(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
 g = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 out = sys.argv[2] if len(sys.argv) > 2 else "hull.ply"
 color_mode = sys.argv[3] if len(sys.argv) > 3 else "camera"
@@ -45,7 +55,7 @@ masks = fx.golden_masks()
 frames = [np.dstack([m // 2 + 60, m // 3 + 40, 255 - m // 2]).astype(np.uint8) for m in masks]   # any BGR image
 assignment.configure(frame_source=assignment.StaticFrameSource([(frames, masks)]),
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
-                     hull_open_mm=open_mm)
+                     hull_open_mm=open_mm, hull_close_mm=close_mm)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
 if out != "-":
@@ -54,8 +64,8 @@ if out != "-":
                 "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pos))
         for p, c in zip(pos, rgb):
             f.write("%g %g %g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
-print("%d voxels of the %dx%dx%d grid survive all 4 views (footprint %s, opened by %g mm) -> %s; extent x %.2f..%.2f, y %.2f..%.2f, z %.2f..%.2f" %
-      (len(pos), g, g, g, footprint, open_mm, out, pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max(), pos[:, 2].min(), pos[:, 2].max()))
+print("%d voxels of the %dx%dx%d grid survive all 4 views (footprint %s, %sopened by %g mm) -> %s; extent x %.2f..%.2f, y %.2f..%.2f, z %.2f..%.2f" %
+      (len(pos), g, g, g, footprint, "closed by %g mm, " % close_mm if close_mm > 0 else "", open_mm, out, pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max(), pos[:, 2].min(), pos[:, 2].max()))
 
 
 def write_image(path, img):

@@ -20,6 +20,8 @@ VC_DIST_BORDER_OFF = 1
 VC_DIST_OUTSIDE = 2
 VC_MORPH_ERODE = 0
 VC_MORPH_OPEN = 1
+VC_GROW_DILATE = 0
+VC_GROW_CLOSE = 1
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
 VC_MAX_MOG_MODELS = 64
@@ -37,10 +39,10 @@ c_f64p = ctypes.POINTER(ctypes.c_double)
 c_ctx = ctypes.c_void_p
 
 
-VC_KERNEL_KINDS, VC_WORK_KINDS = 18, 10
+VC_KERNEL_KINDS, VC_WORK_KINDS = 21, 10
 KERNEL_KINDS = ("k_prep_pack", "k_prep_grid", "k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble", "k_scan_groups",
                 "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups", "foot_table", "k_carve_foot",
-                "k_dist_box", "k_dist_y", "k_dist_env", "k_dist_records")
+                "k_dist_box", "k_dist_y", "k_dist_env", "k_dist_records", "k_grow_mark", "grow_rank", "grow_merge")
 WORK_KINDS = ("word_boxes", "table_entries", "projections", "emit_projections", "brick_boxes", "foot_projections", "foot_union_skips",
               "foot_words", "dist_cells", "dist_lines")
 
@@ -87,6 +89,11 @@ class VcDistanceStats(ctypes.Structure):
 class VcMorphStats(ctypes.Structure):
     _fields_ = [("survivors_before", ctypes.c_uint64), ("eroded", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64),
                 ("max_d2", ctypes.c_uint64), ("q", ctypes.c_uint64 * 3), ("morph_ms", ctypes.c_float)]
+
+
+class VcGrowStats(ctypes.Structure):
+    _fields_ = [("survivors_before", ctypes.c_uint64), ("dilated", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64),
+                ("added", ctypes.c_uint64), ("box_cells", ctypes.c_uint64), ("q", ctypes.c_uint64 * 3), ("grow_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -173,6 +180,8 @@ SIGNATURES = {
     "vc_fetch_record_distance": (ctypes.c_int, [c_ctx, c_u64p]),
     "vc_fetch_distance": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u64p]),
     "vc_hull_morphology": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcMorphStats)]),
+    "vc_hull_grow": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcGrowStats)]),
+    "vc_fetch_grown": (ctypes.c_int, [c_ctx, c_u8p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

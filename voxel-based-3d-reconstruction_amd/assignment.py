@@ -163,7 +163,7 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
              "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
              "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
-             "hull_open_mm": 0.0, "hull_border": "open"}
+             "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0}
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -185,7 +185,11 @@ def configure(frame_source=None, **settings):
     hull_open_mm, hull_border: when hull_open_mm > 0, every carve is followed by CarveEngine.open_hull(hull_open_mm,
     border=hull_border), before the component filter, any photo carve and any colouring: what is thinner than a ball of that
     radius in world millimetres leaves the hull (spurs, fins and specks of mask noise, attached to the figure or not);
-    voxels_status() describes what is kept.  0 (the default) keeps every survivor."""
+    voxels_status() describes what is kept.  0 (the default) keeps every survivor.
+    hull_close_mm: when > 0, every carve is followed by CarveEngine.close_hull(hull_close_mm), before hull_open_mm, the component
+    filter, any photo carve and any colouring (close, then open, is the usual clean-up order): tunnels and dents narrower than a
+    ball of that radius in world millimetres are filled -- what a hole in one camera's mask carves through the figure; the added
+    voxels are coloured from the colour camera.  voxels_status() describes the closed hull.  0 (the default) adds nothing."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -197,6 +201,7 @@ def configure(frame_source=None, **settings):
     footprint_rule(settings.get("footprint", _settings["footprint"]))          # raises ValueError on anything else
     CarveEngine.radius_r2(settings.get("hull_open_mm", _settings["hull_open_mm"]))   # ... on a negative or non-finite radius
     CarveEngine._dist_flags(settings.get("hull_border", _settings["hull_border"]))
+    CarveEngine.radius_r2(settings.get("hull_close_mm", _settings["hull_close_mm"]))
     _settings.update(settings)
     _source = frame_source
     if _engine is not None:
@@ -256,6 +261,8 @@ def set_voxel_positions(width, height, depth):
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"],
                   footprint=_settings["footprint"])
+    if _settings["hull_close_mm"] > 0:
+        _engine.close_hull(_settings["hull_close_mm"])
     if _settings["hull_open_mm"] > 0:
         _engine.open_hull(_settings["hull_open_mm"], border=_settings["hull_border"])
     if _settings["min_component_voxels"] or _settings["keep_components"]:

@@ -43,6 +43,7 @@
 #include "vc_surface.h"
 #include "vc_footprint.h"
 #include "vc_distance.h"
+#include "vc_grow.h"
 
 #pragma clang fp contract(off)
 
@@ -363,6 +364,11 @@ struct vc_ctx {
     std::vector<hipEvent_t> dist_ev; // timing_detail: begin / end events of the passes' launches, made on first use
     std::vector<int> dist_ev_kind;   // the kernel kind of each pair the running call has used
     uint64_t dist_work[2] = {0, 0};  // VC_WORK_DIST_CELLS, VC_WORK_DIST_LINES since vc_timing_reset
+    // vc_hull_grow: the added bits of the word range its box spans, [added, |Dl|], the `added` byte of each record
+    DevBuf<unsigned long long> d_grow_addw, d_grow_ctr;
+    DevBuf<uint8_t> d_grow_added;
+    bool grow_valid = false;         // d_grow_added belongs to the vc_hull_grow that produced the current result
+    uint64_t grow_n = 0;             // its survivors_after
     // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
     DevBuf<uint32_t> d_rn_idx, d_rn_rgbf;
     DevBuf<float> d_rn_depth;
@@ -1335,6 +1341,7 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_cc_thr);
     release(ctx->d_dist_in); release(ctx->d_dist_out); release(ctx->d_dist_tmp); release(ctx->d_dist_rec); release(ctx->d_dist_st);
     release(ctx->d_dist_box); release(ctx->d_dist_acc);
+    release(ctx->d_grow_addw); release(ctx->d_grow_ctr); release(ctx->d_grow_added);
     for (hipEvent_t e : ctx->dist_ev) (void)hipEventDestroy(e);
     release(ctx->d_rn_idx); release(ctx->d_rn_rgbf); release(ctx->d_rn_depth); release(ctx->d_rn_views); release(ctx->d_rn_map);
     release(ctx->d_rn_ctr);
@@ -1390,7 +1397,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1403,7 +1410,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1447,7 +1454,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1708,7 +1715,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;   // the next carve invalidates what the post-carve passes left
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -2052,7 +2059,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2389,7 +2396,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
@@ -2471,7 +2478,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
     if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
@@ -2688,14 +2695,12 @@ static int dist_records(vc_ctx *ctx, StepBuf &cur, const DistBox &bx, const uint
     return VC_OK;
 }
 
-// The inside field of the current result's S > 0 records: their index box (one read-back), grown by a cell per side and, with
-// the border open, clipped to the grid; the transform into d_dist_in over that box; the records' values and acc[0..1] against r2.
-static int dist_inside(vc_ctx *ctx, StepBuf &cur, uint32_t flags, uint64_t S, uint64_t r2, const uint64_t q[3], DistBox &bx)
+// The inclusive index box of the current result's S > 0 records (one read-back): hb[0..2] = min ix, iy, iz, hb[3..5] = max,
+// hb = the pinned scalars.
+static int dist_survivor_box(vc_ctx *ctx, StepBuf &cur, uint64_t S, uint32_t *&hb)
 {
     VC_TRY(ensure(ctx, ctx->d_dist_box, 6));
-    VC_TRY(ensure(ctx, ctx->d_dist_acc, 4));
-    VC_TRY(ensure(ctx, ctx->d_dist_rec, (size_t)S));
-    uint32_t *hb = reinterpret_cast<uint32_t *>(ctx->h_res);
+    hb = reinterpret_cast<uint32_t *>(ctx->h_res);
     hb[0] = hb[1] = hb[2] = 0xffffffffu; hb[3] = hb[4] = hb[5] = 0;
     VC_HIP(ctx, hipMemcpyAsync(ctx->d_dist_box.ptr, hb, 6 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     VC_DLAUNCH(VC_K_DIST_BOX, k_dist_box, dim3((uint32_t)((S + kDistGroup - 1) / kDistGroup)), dim3(kDistBlock),
@@ -2704,11 +2709,24 @@ static int dist_inside(vc_ctx *ctx, StepBuf &cur, uint32_t flags, uint64_t S, ui
     VC_HIP(ctx, hipMemcpyAsync(hb, ctx->d_dist_box.ptr, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
+    for (int a = 0; a < 3; ++a)
+        if (hb[a] > hb[3 + a] || hb[3 + a] >= n[a])
+            return fail(ctx, VC_ERR_HIP, "the survivors' box [%u, %u] on axis %c of %u cells", hb[a], hb[3 + a], "xyz"[a], n[a]);
+    return VC_OK;
+}
+
+// The inside field of the current result's S > 0 records: their index box, grown by a cell per side and, with the border open,
+// clipped to the grid; the transform into d_dist_in over that box; the records' values and acc[0..1] against r2.
+static int dist_inside(vc_ctx *ctx, StepBuf &cur, uint32_t flags, uint64_t S, uint64_t r2, const uint64_t q[3], DistBox &bx)
+{
+    VC_TRY(ensure(ctx, ctx->d_dist_acc, 4));
+    VC_TRY(ensure(ctx, ctx->d_dist_rec, (size_t)S));
+    uint32_t *hb = nullptr;
+    VC_TRY(dist_survivor_box(ctx, cur, S, hb));
+    const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
     memset(&bx, 0, sizeof bx);
     bx.nx = ctx->nx; bx.ny = ctx->ny; bx.nz = ctx->nz;
     for (int a = 0; a < 3; ++a) {
-        if (hb[a] > hb[3 + a] || hb[3 + a] >= n[a])
-            return fail(ctx, VC_ERR_HIP, "the survivors' box [%u, %u] on axis %c of %u cells", hb[a], hb[3 + a], "xyz"[a], n[a]);
         int32_t lo = (int32_t)hb[a] - 1, hi = (int32_t)hb[3 + a] + 1;
         if (!(flags & VC_DIST_BORDER_OFF)) { lo = lo < 0 ? 0 : lo; hi = hi >= (int32_t)n[a] ? (int32_t)n[a] - 1 : hi; }
         bx.o[a] = lo;
@@ -2849,13 +2867,13 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
             VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S0, r2, ctx->d_dist_acc.ptr + 2));
         }
         // the result changes from here on
-        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
         VC_TRY(compact_records(ctx, cur, DistKept{ctx->d_dist_rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
                                S0, ctx->h_res + 1));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->d_dist_acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_dist_acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     dist_harvest(ctx);
@@ -2871,6 +2889,179 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
     stats->survivors_before = S0;
     stats->survivors_after = kept;
     for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
+    return VC_OK;
+}
+
+// ---- dilation and closing of the current carve result (vc_grow.h; contract in include/voxcarve.h) ----
+// floor(sqrt(v)) exactly
+static uint64_t isqrt_u64(uint64_t v)
+{
+    uint64_t r = (uint64_t)std::sqrt((long double)v);
+    while (r > 0xffffffffull || r * r > v) --r;
+    while (r < 0xffffffffull && (r + 1) * (r + 1) <= v) ++r;
+    return r;
+}
+
+int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_grow: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (op != VC_GROW_DILATE && op != VC_GROW_CLOSE)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_grow: unknown op %u (VC_GROW_DILATE, VC_GROW_CLOSE)", op);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_grow: flags must be 0 (got %u)", flags);
+    VC_TRY(result_refusals(ctx, "vc_hull_grow", "merge the added voxels into", "morphology"));
+    uint64_t q[3];
+    VC_TRY(dist_metric(ctx, "vc_hull_grow", q));
+    StepBuf &cur = ctx->sb[ctx->cur];
+    if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_grow: frame set %u has been prepared again since the carve: its images are not the ones "
+                    "the records' colours came from", cur.slot);
+    const uint64_t n = ctx->n_voxels(), nwords = (n + 63) / 64;
+    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_grow: %llu voxels exceed the u32 index", (unsigned long long)n);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->dist_ev_kind.clear();
+    const uint64_t S0 = ctx->survivors;
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    uint64_t S1 = S0, added = 0, dilated = 0;
+    DistBox bx;
+    memset(&bx, 0, sizeof bx);
+    if (S0) {
+        VC_TRY(densify_words(ctx, cur));
+        // the survivors' index box, grown per axis by g_a + 1 cells and clipped to the grid: Dl lies inside the g-grown box, and the
+        // extra layer (where no grid face cuts it off) is outside Dl, which makes the second transform over the box exact
+        uint32_t *hb = nullptr;
+        VC_TRY(dist_survivor_box(ctx, cur, S0, hb));
+        const uint32_t dims[3] = {ctx->nx, ctx->ny, ctx->nz};
+        const uint64_t root = isqrt_u64(r2);
+        bx.nx = ctx->nx; bx.ny = ctx->ny; bx.nz = ctx->nz;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t g = (int64_t)(root / q[a]) + 1;
+            const int64_t lo = std::max<int64_t>((int64_t)hb[a] - g, 0), hi = std::min<int64_t>((int64_t)hb[3 + a] + g, (int64_t)dims[a] - 1);
+            bx.o[a] = (int32_t)lo;
+            bx.b[a] = (uint32_t)(hi - lo + 1);
+        }
+        // the occupancy words the box spans: the added bits are collected in a zeroed copy of that range
+        const uint64_t i_lo = ((uint64_t)bx.o[2] * ctx->nx + (uint32_t)bx.o[0]) * ctx->ny + (uint32_t)bx.o[1];
+        const uint64_t i_hi = ((uint64_t)(bx.o[2] + (int32_t)bx.b[2] - 1) * ctx->nx + (uint32_t)(bx.o[0] + (int32_t)bx.b[0] - 1)) * ctx->ny +
+                              (uint32_t)(bx.o[1] + (int32_t)bx.b[1] - 1);
+        const uint64_t w0 = i_lo >> 6, nrange = (i_hi >> 6) - w0 + 1;
+        ctx->dist_valid = false;                 // the field's buffer is the transforms' from here on, whether the call succeeds or not
+        VC_TRY(dist_ensure(ctx, ctx->d_dist_in, bx));
+        VC_TRY(ensure(ctx, ctx->d_grow_addw, (size_t)nrange));
+        VC_TRY(ensure(ctx, ctx->d_grow_ctr, 2));
+        uint64_t *f = ctx->d_dist_in.ptr;
+        const uint64_t ylines = (uint64_t)bx.b[0] * bx.b[2];
+        const dim3 block(kDistBlock), mgrid((uint32_t)((ylines + (kDistBlock / 64) * kGrowLines - 1) / ((kDistBlock / 64) * kGrowLines)));
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_addw.ptr, 0, (size_t)nrange * sizeof(unsigned long long), ctx->stream));
+        // 1: D_out over the box; 2: for the closing |Dl|, then the same transform with sites = the box's cells outside Dl
+        VC_TRY(dist_transform(ctx, bx, kDistSiteOn, cur.words.ptr, f, 0, q));
+        if (op == VC_GROW_CLOSE) {
+            VC_DLAUNCH(VC_K_GROW_MARK, k_grow_mark<kGrowCount>, mgrid, block, bx, (const uint64_t *)f, r2, (const uint64_t *)cur.words.ptr, nwords,
+                       ctx->d_grow_addw.ptr, w0, nrange, ctx->d_grow_ctr.ptr + 1);
+            VC_TRY(dist_transform(ctx, bx, kDistSiteAbove, cur.words.ptr, f, r2, q));
+            VC_DLAUNCH(VC_K_GROW_MARK, k_grow_mark<kGrowClose>, mgrid, block, bx, (const uint64_t *)f, r2, (const uint64_t *)cur.words.ptr, nwords,
+                       ctx->d_grow_addw.ptr, w0, nrange, ctx->d_grow_ctr.ptr + 0);
+        } else {
+            VC_DLAUNCH(VC_K_GROW_MARK, k_grow_mark<kGrowDilate>, mgrid, block, bx, (const uint64_t *)f, r2, (const uint64_t *)cur.words.ptr, nwords,
+                       ctx->d_grow_addw.ptr, w0, nrange, ctx->d_grow_ctr.ptr + 0);
+        }
+        VC_HIP(ctx, hipGetLastError());
+        // the read-back in the middle: the added voxels size the records
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_grow_ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        added = ctx->h_res[0];
+        S1 = S0 + added;
+        dilated = op == VC_GROW_CLOSE ? ctx->h_res[1] : S1;
+        if (S1 > n || dilated < S1 || dilated > n)
+            return fail(ctx, VC_ERR_HIP, "vc_hull_grow: %llu added to %llu survivors, %llu dilated, in a grid of %llu voxels", (unsigned long long)added,
+                        (unsigned long long)S0, (unsigned long long)dilated, (unsigned long long)n);
+        // every buffer of the hand-over before anything changes: a failure leaves the result
+        const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);
+        ctx->grow_valid = false;                 // (the added bytes of an earlier call go with their buffer)
+        VC_TRY(ensure(ctx, ctx->d_grow_added, (size_t)S1));
+        if (added) {
+            VC_TRY(ensure(ctx, ctx->d_rec_spare, std::max<size_t>(cur.records.cap, (size_t)S1)));
+            VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
+            VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
+        }
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_added.ptr, 0, (size_t)S1, ctx->stream));
+        if (added) {
+            // the result changes from here on
+            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+            const dim3 gblock(kGrowBlock), rgrid((uint32_t)((nrange + kGrowBlock - 1) / kGrowBlock));
+            VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->d_grow_addw.ptr, w0, nrange);
+            // survivors per group of the step, counted again: the packing skips the groups whose count is zero, and an added voxel
+            // may be the first of its group
+            const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
+            VC_DLAUNCH(VC_K_GROW_RANK, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups,
+                       cur.groupcnt.ptr);
+            // ranks of the new occupancy: popcounts per 64 words, their scan, the wave scan inside each group
+            const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), cblock(kCcBlock);
+            VC_DLAUNCH(VC_K_GROW_RANK, k_cc_wcount, wgrid, cblock, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+            VC_HIP(ctx, hipGetLastError());
+            VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, ctx->h_res + 2));
+            VC_DLAUNCH(VC_K_GROW_RANK, k_cc_woff, wgrid, cblock, (const uint64_t *)cur.words.ptr, nwords, wgroups,
+                       (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_cc_woff.ptr);
+            // the merged list into the spare buffer: every old record to its new rank, a fresh record for every added voxel
+            GrowParams p;
+            memset(&p, 0, sizeof p);
+            p.xs = cur.emit.xs; p.ys = cur.emit.ys; p.zs = cur.emit.zs;
+            p.has_cam = cur.emit.has_cam && cur.emit.xs ? 1 : 0;
+            p.cam = cur.emit.cam;
+            p.frame = cur.emit.frame;
+            p.words = cur.words.ptr; p.woff = ctx->d_cc_woff.ptr; p.addw = ctx->d_grow_addw.ptr;
+            p.out = ctx->d_rec_spare.ptr; p.added = ctx->d_grow_added.ptr;
+            p.w0 = w0; p.nrange = nrange; p.S1 = S1;
+            p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.H = ctx->H; p.W = ctx->W;
+            VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_old, dim3((uint32_t)((S0 + kGrowBlock - 1) / kGrowBlock)), gblock, p, (const uint64_t *)cur.records.ptr, S0, nwords);
+            VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_new, rgrid, gblock, p, nwords);
+            VC_HIP(ctx, hipGetLastError());
+            std::swap(cur.records, ctx->d_rec_spare);
+            // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
+            const uint32_t nscan = (wgroups + kScanBlock - 1) / kScanBlock;
+            const uint64_t n_pad = (cur.n + kLutPad - 1) / kLutPad * kLutPad;
+            const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
+            VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_rscan.boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                                       ctx->stream));
+            cur.nz_valid = false;                // non-zero word counts per group: counted again by the next packing
+            ctx->gathered = false; ctx->packed = false;
+        }
+    }
+    // a call that adds nothing (r2 = 0, a second closing, the empty hull) leaves the result as it is, and with it the visibility,
+    // the photo rounds and the component labels; the stored distance field went with its buffer above
+    ctx->grow_valid = false;
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    dist_harvest(ctx);
+    if (added) {
+        ctx->survivors = cur.survivors = S1;
+        if (ctx->h_res[2] != S1)
+            return fail(ctx, VC_ERR_HIP, "vc_hull_grow: the new occupancy holds %llu voxels, %llu records were merged", (unsigned long long)ctx->h_res[2],
+                        (unsigned long long)S1);
+    }
+    VC_HIP(ctx, hipEventElapsedTime(&stats->grow_ms, ctx->ev[0], ctx->ev[1]));
+    stats->survivors_before = S0;
+    stats->dilated = dilated;
+    stats->survivors_after = S1;
+    stats->added = added;
+    stats->box_cells = S0 ? dist_cells(bx) : 0;
+    for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
+    ctx->grow_valid = true;
+    ctx->grow_n = S1;
+    return VC_OK;
+}
+
+int vc_fetch_grown(vc_ctx *ctx, uint8_t *added)
+{
+    if (!ctx || !added) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->grow_valid) return fail(ctx, VC_ERR_ARG, "no added flags: call vc_hull_grow on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->grow_n) VC_HIP(ctx, hipMemcpy(added, ctx->d_grow_added.ptr, (size_t)ctx->grow_n, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 

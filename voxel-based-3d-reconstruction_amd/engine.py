@@ -592,6 +592,38 @@ class CarveEngine:
         survivors within the radius of the eroded set stay).  Arguments, effects and stats as erode_hull."""
         return self._morphology(_lib.VC_MORPH_OPEN, self.radius_r2(radius_mm), border)
 
+    # -- dilation and closing of the hull by a ball in mm (vc_hull_grow): the passes that ADD survivors -----------------------------
+    def _grow(self, op, r2):
+        if r2 >= 1 << 64:
+            raise ValueError("radius^2 = %d um^2 does not fit 64 bits" % r2)
+        st = _lib.VcGrowStats()
+        self._check(self._L.vc_hull_grow(self._ctx, op, int(r2), 0, ctypes.byref(st)), "vc_hull_grow")
+        self.count = int(st.survivors_after)
+        return {"survivors_before": int(st.survivors_before), "dilated": int(st.dilated), "survivors_after": int(st.survivors_after),
+                "added": int(st.added), "box_cells": int(st.box_cells), "q": tuple(int(v) for v in st.q), "grow_ms": float(st.grow_ms)}
+
+    def dilate_hull(self, radius_mm):
+        """Dilates the current carve result by a ball of radius_mm millimetres (a Euclidean ball in world units, clipped to the
+        grid): every voxel within the radius of a survivor becomes one, r2 = round(radius_mm * 1000)^2 um^2.  The records, the
+        count and the occupancy then describe the dilated hull: old records keep their bytes, an added voxel is coloured by the
+        colour camera's pixel under its centre (contract: include/voxcarve.h).  The next carve restores the visual hull.  Returns
+        the stats as a dict: survivors_before, dilated, survivors_after, added, box_cells, q, grow_ms."""
+        return self._grow(_lib.VC_GROW_DILATE, self.radius_r2(radius_mm))
+
+    def close_hull(self, radius_mm):
+        """Closes the current carve result by a ball of radius_mm millimetres: tunnels, holes and dents narrower than the ball are
+        filled -- what a hole in one camera's foreground mask carves through the figure -- and the rest of the hull keeps its
+        shape (dilation, then the erosion of the dilated set).  The result holds the hull; closing it again adds nothing.
+        Arguments, effects and stats as dilate_hull."""
+        return self._grow(_lib.VC_GROW_CLOSE, self.radius_r2(radius_mm))
+
+    def fetch_added(self):
+        """u8 [S] in record order: 1 where the record was created by the last dilate_hull / close_hull (fails once a carve or a
+        pass that removes survivors has run since)."""
+        out = np.empty(self.count, dtype=np.uint8)
+        self._check(self._L.vc_fetch_grown(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_grown")
+        return out
+
     # -- ray-cast images of the current result (vc_render) --------------------------------------------------------------------------
     def render(self, views, H, W, shade=None, background=(0, 0, 0)):
         """Ray-casts the current carve result (after color_visible / photo_carve / filter_components, as fetch sees it) from each
