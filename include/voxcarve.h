@@ -497,6 +497,58 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
               const uint8_t *background, uint32_t flags, vc_render_stats_t *stats);
 int vc_fetch_render(vc_ctx *ctx, uint32_t view, uint32_t *idx, float *depth, uint8_t *rgb, uint8_t *face);
 
+/* ---- surface normals of the hull; smooth-shaded renders and mesh normals (no reference counterpart) -----------------------------
+ * vc_hull_normals gives every surface record of the current carve result, as vc_fetch_occupancy and vc_fetch_records see it, the
+ * direction its surface faces: minus the sum of the offsets to the survivors inside a ball in world units.  The contract, bit for
+ * bit (tests/normals_np.py restates it).  Signed 64-bit integers only, and a sum over a set: the result does not depend on
+ * evaluation order.
+ *   1 input, metric: items 1 and 2 of vc_hull_distance, with the same refusals; q_a in um.
+ *   2 ball: B(r2) = { (dx, dy, dz) != 0 : (q_x dx)^2 + (q_y dy)^2 + (q_z dz)^2 <= r2 }, r2 in um^2; ext_a = the largest k with
+ *     (k q_a)^2 <= r2.  VC_ERR_ARG when B is empty or some ext_a > 15 (a voxel's y window then fits in 31 bits).
+ *   3 surface: a record is SURFACE iff one of its 6 face neighbours is not a survivor or lies outside the grid (rule 1 of
+ *     vc_color_visible's surface test).
+ *   4 gradient of a surface record v: g(v) = sum over d in B with v + d inside the grid and ON of (q_x dx, q_y dy, q_z dz).  The
+ *     border is open: outside the grid is OFF, nothing wraps around.  The normal is n = -g: from solid to empty, in world
+ *     (x, y, z), in um-weighted units; |n_a| < 2^39.
+ *   5 stored form, int16 [4] per record in record order: m = max |n_a|, n16_a = (n_a * 32767) / m truncated toward zero (C's /),
+ *     w = 1.  A surface record with n = 0 stores (0, 0, 0, 1), a record that is not surface (0, 0, 0, 0).
+ *   6 lifetime: the call leaves the result alone.  The normals stay valid across vc_color_visible (colours only) and fail to
+ *     fetch after anything that changes which voxels survive: a carve, vc_photo_carve, vc_hull_components, vc_hull_morphology,
+ *     a vc_hull_grow that adds something.
+ *   7 VC_ERR_ARG (with a message, nothing launched) when there is no carve result, steps are in flight, the carve ran with
+ *     VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached, flags != 0,
+ *     stats == NULL, the metric is out of range or item 2 refuses.  S = 0 is no error.  Synchronous.
+ * stats (required): survivors; surface = surface records; zero = surface records with n = 0; offsets = |B|; q; ext; normals_ms =
+ * HIP events around the whole call.  vc_fetch_record_normals: int16 [S][4] in record order; with n4 == NULL it copies nothing and
+ * only tells whether the normals are valid (VC_OK) or stale (VC_ERR_ARG).
+ *
+ * vc_shade_render shades the images of the last vc_render with the normals; it needs valid normals and a render that ran on the
+ * current result (a render made before a carve or a pass of item 6 is refused).  vc_fetch_render and its images are untouched.
+ * Per pixel, idx from the render: a miss keeps the render's background.  A hit's record is the first with index >= idx (binary
+ * search, as the render finds it); if its w = 0 or n16 = 0 the pixel keeps the render's own rgb.  Otherwise, in float64 with no
+ * contraction and in this order, L = light[view] (from the surface towards the light, world coordinates):
+ *     dot = ((double)n0*L0 + (double)n1*L1) + (double)n2*L2;  nn = (double)(n0*n0 + n1*n1 + n2*n2) (the integer is exact);
+ *     ll = (L0*L0 + L1*L1) + L2*L2;  c = dot > 0 ? min(dot / sqrt(nn * ll), 1.0) : 0.0;
+ *     s = ambient + (uint32_t)floor((double)(255 - ambient) * c + 0.5);  rgb_k = (rec_rgb_k * s + 127) / 255 in integers,
+ * rec_rgb = the record's RGB as it is at this call.  VC_ERR_ARG when a light component is not finite, ll is not a finite normal
+ * number, ambient > 255, flags != 0, the normals are stale, or the render is stale or missing.  vc_fetch_shaded: rgb [H W 3] of
+ * one view; fails before the first vc_shade_render on the last render and for view >= n_views.
+ *
+ * vc_surface_normals: per vertex of the last vc_surface_mesh, the stored quadruple of the ON element's record (the vertex's edge
+ * entry holds the element; same search), int16 [V][4].  VC_ERR_ARG unless the mesh was made on the current result and the
+ * normals are valid. */
+typedef struct {
+    uint64_t survivors, surface, zero /* surface records with n = 0 */, offsets /* |B| */;
+    uint64_t q[3];                  /* x, y, z in um */
+    uint32_t ext[3];
+    float normals_ms;               /* HIP events around the whole call */
+} vc_normals_stats_t;
+int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags /* must be 0 */, vc_normals_stats_t *stats);
+int vc_fetch_record_normals(vc_ctx *ctx, int16_t *n4);             /* [S][4], record order */
+int vc_shade_render(vc_ctx *ctx, const double *light /* [n_views][3] */, uint32_t ambient /* 0..255 */, uint32_t flags /* must be 0 */);
+int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb);     /* [H W 3] */
+int vc_surface_normals(vc_ctx *ctx, int16_t *n4);                  /* [V][4], vertex order of vc_fetch_surface_mesh */
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--mesh PATH] [--footprint centre|any|all] [--close MM] [--open MM] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--close MM] [--open MM] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -10,7 +10,9 @@ voxel when any pixel its whole cell projects to is foreground (the outer hull), 
 --open MM: the hull opened by a ball of MM millimetres on the device after the carve, assignment.configure(hull_open_mm=MM) --
 what is thinner than the ball leaves the hull; --close MM: the hull closed by a ball of MM millimetres on the device after the
 carve and before any opening, assignment.configure(hull_close_mm=MM) -- tunnels and dents narrower than the ball are filled, which
-is what a hole in one camera's mask carves; --help: this text)."""
+is what a hole in one camera's mask carves; --smooth (with --render): every hit shaded by the hull's surface normal under a
+headlight, assignment.render_views(smooth=True), instead of the six face brightnesses; --normals (with --mesh): the PLY carries
+nx, ny, nz per vertex, assignment.surface_mesh(normals=True); --help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
     print(__doc__)
@@ -21,6 +23,12 @@ import numpy as np
 import fixtures_util as fx
 from voxcarve import assignment
 
+smooth = "--smooth" in sys.argv
+if smooth:
+    sys.argv.remove("--smooth")
+with_normals = "--normals" in sys.argv
+if with_normals:
+    sys.argv.remove("--normals")
 render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
@@ -85,8 +93,12 @@ if render_dir:
     os.makedirs(render_dir, exist_ok=True)
     shade = (200, 200, 225, 225, 255, 150, 255)        # x sides, y sides, top (rays along +z: up is -z), bottom, inside
     orbit = camera.orbit(8, 4500.0, 25.0, 1500.0, 1080, 1920)
-    r = assignment.render_views(orbit, 1920, 1080, shade=shade)
-    c = assignment.render_views(shade=shade)
+    if smooth:
+        r = assignment.render_views(orbit, 1920, 1080, smooth=True)
+        c = assignment.render_views(smooth=True)
+    else:
+        r = assignment.render_views(orbit, 1920, 1080, shade=shade)
+        c = assignment.render_views(shade=shade)
     paths = [write_image(os.path.join(render_dir, "orbit_%d" % k), img) for k, img in enumerate(r["rgb"])]
     paths += [write_image(os.path.join(render_dir, "cam%d" % (k + 1)), img) for k, img in enumerate(c["rgb"])]
     print("%d images -> %s (orbit: %.2f ms for 8 views, %d of %d pixels hit)" % (len(paths), render_dir, r["stats"]["render_ms"],
@@ -94,8 +106,8 @@ if render_dir:
 
 if mesh_path:
     from voxcarve.voxel_reconstruction import write_ply
-    m = assignment.surface_mesh(8)
-    write_ply(mesh_path, m["verts"], m["faces"], m["rgb"])
+    m = assignment.surface_mesh(8, normals=with_normals)
+    write_ply(mesh_path, m["verts"], m["faces"], m["rgb"], normals=m.get("normals"))
     st = m["stats"]
     print("mesh: %d vertices (%d refined), %d faces -> %s (%.2f ms on the device)" % (st["n_verts"], st["refined"], st["n_faces"],
                                                                                   mesh_path, st["surface_ms"]))

@@ -33,6 +33,7 @@ STATUS_NAMES = {0: "VC_OK", -1: "VC_ERR_ARG", -2: "VC_ERR_HIP", -3: "VC_ERR_RCCL
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u16p = ctypes.POINTER(ctypes.c_uint16)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
+c_i16p = ctypes.POINTER(ctypes.c_int16)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_u64p = ctypes.POINTER(ctypes.c_uint64)
 c_f64p = ctypes.POINTER(ctypes.c_double)
@@ -94,6 +95,11 @@ class VcMorphStats(ctypes.Structure):
 class VcGrowStats(ctypes.Structure):
     _fields_ = [("survivors_before", ctypes.c_uint64), ("dilated", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64),
                 ("added", ctypes.c_uint64), ("box_cells", ctypes.c_uint64), ("q", ctypes.c_uint64 * 3), ("grow_ms", ctypes.c_float)]
+
+
+class VcNormalsStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("surface", ctypes.c_uint64), ("zero", ctypes.c_uint64), ("offsets", ctypes.c_uint64),
+                ("q", ctypes.c_uint64 * 3), ("ext", ctypes.c_uint32 * 3), ("normals_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -182,6 +188,11 @@ SIGNATURES = {
     "vc_hull_morphology": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcMorphStats)]),
     "vc_hull_grow": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcGrowStats)]),
     "vc_fetch_grown": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_hull_normals": (ctypes.c_int, [c_ctx, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcNormalsStats)]),
+    "vc_fetch_record_normals": (ctypes.c_int, [c_ctx, c_i16p]),
+    "vc_shade_render": (ctypes.c_int, [c_ctx, c_f64p, ctypes.c_uint32, ctypes.c_uint32]),
+    "vc_fetch_shaded": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
+    "vc_surface_normals": (ctypes.c_int, [c_ctx, c_i16p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

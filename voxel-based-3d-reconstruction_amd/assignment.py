@@ -163,7 +163,7 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
              "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
              "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
-             "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0}
+             "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None}
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -189,7 +189,9 @@ def configure(frame_source=None, **settings):
     hull_close_mm: when > 0, every carve is followed by CarveEngine.close_hull(hull_close_mm), before hull_open_mm, the component
     filter, any photo carve and any colouring (close, then open, is the usual clean-up order): tunnels and dents narrower than a
     ball of that radius in world millimetres are filled -- what a hole in one camera's mask carves through the figure; the added
-    voxels are coloured from the colour camera.  voxels_status() describes the closed hull.  0 (the default) adds nothing."""
+    voxels are coloured from the colour camera.  voxels_status() describes the closed hull.  0 (the default) adds nothing.
+    normal_radius_mm: the radius of the ball that render_views(smooth=True) and surface_mesh(normals=True) estimate the hull's
+    surface normals from (CarveEngine.hull_normals); None (the default) is 3 x the largest grid step."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -202,6 +204,8 @@ def configure(frame_source=None, **settings):
     CarveEngine.radius_r2(settings.get("hull_open_mm", _settings["hull_open_mm"]))   # ... on a negative or non-finite radius
     CarveEngine._dist_flags(settings.get("hull_border", _settings["hull_border"]))
     CarveEngine.radius_r2(settings.get("hull_close_mm", _settings["hull_close_mm"]))
+    if settings.get("normal_radius_mm", _settings["normal_radius_mm"]) is not None:
+        CarveEngine.radius_r2(settings.get("normal_radius_mm", _settings["normal_radius_mm"]))
     _settings.update(settings)
     _source = frame_source
     if _engine is not None:
@@ -289,23 +293,43 @@ def voxels_status():
 
 
 
-def render_views(views=None, width=None, height=None, shade=None):
+def _ensure_normals():
+    if not _engine.normals_valid():
+        _engine.hull_normals(_settings["normal_radius_mm"])
+
+
+def render_views(views=None, width=None, height=None, shade=None, smooth=False, ambient=64):
     """Images of the hull of the last set_voxel_positions call, after whatever configure(...) asked for (component filter,
     photo carve, colouring), ray-cast on the device (CarveEngine.render): views = a list of camera.Camera (default: the
     calibrated cameras), width x height pixels (default: the mask size).  Returns the dict of CarveEngine.render: rgb
-    [V, H, W, 3], depth, index, face and stats."""
+    [V, H, W, 3], depth, index, face and stats.  smooth=True shades every hit by the hull's surface normal under a headlight
+    per view instead of the six face brightnesses of `shade` (CarveEngine.render_shaded: rgb is the shaded image, rgb_flat the
+    unshaded one; ambient 0..255 is the brightness of a surface that faces away)."""
     if _engine is None or not initialized or _engine._sized is None:
         raise RuntimeError("set_voxel_positions has not run")
     H, W = _engine.image_size
-    return _engine.render(_engine._cameras if views is None else views, H if height is None else height,
-                          W if width is None else width, shade=shade)
+    views = _engine._cameras if views is None else views
+    H, W = H if height is None else height, W if width is None else width
+    if smooth:
+        if shade is not None:
+            raise ValueError("render_views: shade is the flat render's; smooth=True shades by the normals")
+        _ensure_normals()
+        return _engine.render_shaded(views, H, W, ambient=ambient)
+    return _engine.render(views, H, W, shade=shade)
 
 
-def surface_mesh(refine_steps=8):
+def surface_mesh(refine_steps=8, normals=False):
     """Surface mesh of the hull of the last set_voxel_positions call, after whatever configure(...) asked for (component filter,
     photo carve, colouring), refined against the silhouettes on the device (CarveEngine.surface_mesh): world millimetres,
     outward faces, the voxels' colours.  Returns the dict of CarveEngine.surface_mesh: verts [V, 3] float64, faces [F, 3], rgb
-    [V, 3], refined [V] and stats; voxel_reconstruction.write_ply writes it out."""
+    [V, 3], refined [V] and stats; voxel_reconstruction.write_ply writes it out.  normals=True adds "normals": float64 [V, 3]
+    unit vectors, the surface normal of the voxel each vertex takes its colour from (zero where that voxel has none)."""
     if _engine is None or not initialized or _engine._sized is None:
         raise RuntimeError("set_voxel_positions has not run")
-    return _engine.surface_mesh(refine_steps)
+    mesh = _engine.surface_mesh(refine_steps)
+    if normals:
+        _ensure_normals()
+        v = _engine.surface_normals()[:, :3].astype(np.float64)
+        l = np.sqrt((v * v).sum(axis=1))
+        mesh["normals"] = v / np.where(l == 0.0, 1.0, l)[:, None]
+    return mesh

@@ -44,6 +44,7 @@
 #include "vc_footprint.h"
 #include "vc_distance.h"
 #include "vc_grow.h"
+#include "vc_normals.h"
 
 #pragma clang fp contract(off)
 
@@ -387,6 +388,17 @@ struct vc_ctx {
     uint64_t sf_verts = 0, sf_faces = 0;
     bool sf_valid = false;
     int surface_order = 1;           // vc_surface_mesh tries the cameras that rejected P_off first (same results)
+    // vc_hull_normals: survivors before each word, the ball's rows, the records' quadruples, [surface, zero]; the shaded images of
+    // vc_shade_render ([V][H W] R | G << 8 | B << 16) and its lights; the quadruples of the last mesh's vertices
+    DevBuf<uint32_t> d_nrm_woff, d_nrm_rows, d_sh_rgb;
+    DevBuf<short4> d_nrm_out, d_nrm_verts;
+    DevBuf<unsigned long long> d_nrm_ctr;
+    DevBuf<double> d_sh_light;
+    bool nrm_valid = false;          // the quadruples belong to the vc_hull_normals that ran on the current result
+    uint64_t nrm_n = 0;              // its survivors
+    bool rn_current = false;         // the images of the last render show the current result (rn_valid outlives a carve)
+    bool sf_current = false;         // the last surface mesh was made on the current result (sf_valid outlives a carve)
+    bool sh_valid = false;           // shaded images of the last render exist
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1347,6 +1359,8 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_rn_ctr);
     release(ctx->d_sf_edges); release(ctx->d_sf_verts); release(ctx->d_sf_faces); release(ctx->d_sf_rgb); release(ctx->d_sf_refined);
     release(ctx->d_sf_ctr);
+    release(ctx->d_nrm_woff); release(ctx->d_nrm_rows); release(ctx->d_sh_rgb); release(ctx->d_nrm_out); release(ctx->d_nrm_verts);
+    release(ctx->d_nrm_ctr); release(ctx->d_sh_light);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
     if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
@@ -1397,7 +1411,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1410,7 +1424,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1454,7 +1468,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1715,7 +1729,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;   // the next carve invalidates what the post-carve passes left
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -2059,7 +2073,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2396,7 +2410,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
@@ -2478,7 +2492,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
     if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
@@ -2867,13 +2881,13 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
             VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S0, r2, ctx->d_dist_acc.ptr + 2));
         }
         // the result changes from here on
-        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
         VC_TRY(compact_records(ctx, cur, DistKept{ctx->d_dist_rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
                                S0, ctx->h_res + 1));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->d_dist_acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_dist_acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     dist_harvest(ctx);
@@ -2992,7 +3006,7 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
         VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_added.ptr, 0, (size_t)S1, ctx->stream));
         if (added) {
             // the result changes from here on
-            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false;
+            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
             const dim3 gblock(kGrowBlock), rgrid((uint32_t)((nrange + kGrowBlock - 1) / kGrowBlock));
             VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->d_grow_addw.ptr, w0, nrange);
             // survivors per group of the step, counted again: the packing skips the groups whose count is zero, and an added voxel
@@ -3091,7 +3105,7 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->rn_valid = false;
+    ctx->rn_valid = false; ctx->rn_current = false; ctx->sh_valid = false;
     VC_TRY(ensure(ctx, ctx->d_rn_idx, (size_t)npix));
     VC_TRY(ensure(ctx, ctx->d_rn_depth, (size_t)npix));
     VC_TRY(ensure(ctx, ctx->d_rn_rgbf, (size_t)npix));
@@ -3140,7 +3154,7 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_rn_ctr.ptr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->rn_valid = true;
+    ctx->rn_valid = true; ctx->rn_current = true;
     ctx->rn_views = n_views; ctx->rn_H = H; ctx->rn_W = W;
     if (ctx->h_res[0] > npix) return fail(ctx, VC_ERR_HIP, "vc_render: %llu hits among %llu pixels", (unsigned long long)ctx->h_res[0],
                                           (unsigned long long)npix);
@@ -3269,7 +3283,7 @@ int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces)
 int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stats_t *stats)
 {
     if (!ctx) return VC_ERR_ARG;
-    ctx->sf_valid = false;
+    ctx->sf_valid = false; ctx->sf_current = false;
     if (!stats) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: stats must not be NULL");
     memset(stats, 0, sizeof *stats);
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: flags must be 0 (got %u)", flags);
@@ -3350,7 +3364,7 @@ int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stat
     const uint64_t refined = ctx->h_res[0];
     if (refined > V) return fail(ctx, VC_ERR_HIP, "vc_surface_mesh: %llu refined among %llu vertices", (unsigned long long)refined,
                                  (unsigned long long)V);
-    ctx->sf_verts = V; ctx->sf_faces = F; ctx->sf_valid = true;
+    ctx->sf_verts = V; ctx->sf_faces = F; ctx->sf_valid = true; ctx->sf_current = true;
     stats->n_verts = V;
     stats->n_faces = F;
     stats->refined = refined;
@@ -3370,6 +3384,186 @@ int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *
     if (faces && F) VC_HIP(ctx, hipMemcpy(faces, ctx->d_sf_faces.ptr, F * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (rgb && V) VC_HIP(ctx, hipMemcpy(rgb, ctx->d_sf_rgb.ptr, V * 3, hipMemcpyDeviceToHost));
     if (refined && V) VC_HIP(ctx, hipMemcpy(refined, ctx->d_sf_refined.ptr, V, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+// ---- surface normals of the current carve result, shaded renders, mesh normals (vc_normals.h; contract in include/voxcarve.h) ----
+int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags, vc_normals_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: flags must be 0 (got %u)", flags);
+    VC_TRY(result_refusals(ctx, "vc_hull_normals", "give normals to", "normal estimation"));
+    uint64_t q[3];
+    VC_TRY(dist_metric(ctx, "vc_hull_normals", q));
+    // item 2: the ball's extents and its rows (dx, dz) with their y half-extent
+    const uint64_t root = isqrt_u64(r2);
+    uint32_t ext[3];
+    for (int a = 0; a < 3; ++a) {
+        const uint64_t e = root / q[a];
+        if (e > kNrmMaxExt)
+            return fail(ctx, VC_ERR_ARG, "vc_hull_normals: r2 = %llu um^2 reaches %llu cells along %c, more than %u", (unsigned long long)r2,
+                        (unsigned long long)e, "xyz"[a], kNrmMaxExt);
+        ext[a] = (uint32_t)e;
+    }
+    if (!(ext[0] | ext[1] | ext[2])) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: the ball of r2 = %llu um^2 holds no voxel offset", (unsigned long long)r2);
+    std::vector<uint32_t> rows;
+    uint64_t offsets = 0;
+    for (int32_t dz = -(int32_t)ext[2]; dz <= (int32_t)ext[2]; ++dz)
+        for (int32_t dx = -(int32_t)ext[0]; dx <= (int32_t)ext[0]; ++dx) {
+            const uint64_t used = (q[0] * (uint64_t)std::abs(dx)) * (q[0] * (uint64_t)std::abs(dx)) +
+                                  (q[2] * (uint64_t)std::abs(dz)) * (q[2] * (uint64_t)std::abs(dz));
+            if (used > r2) continue;
+            const uint32_t ky = (uint32_t)(isqrt_u64(r2 - used) / q[1]);         // <= ext[1]
+            if (ky == 0 && dx == 0 && dz == 0) continue;                          // the voxel itself alone
+            rows.push_back(((uint32_t)dx & 255u) | (((uint32_t)dz & 255u) << 8) | (ky << 16));
+            offsets += 2ull * ky + ((dx == 0 && dz == 0) ? 0u : 1u);
+        }
+    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: %llu voxels exceed the u32 index", (unsigned long long)n);
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->nrm_valid = false;
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    const uint64_t nwords = (n + 63) / 64;
+    const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);
+    if (S) {
+        VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
+        VC_TRY(ensure(ctx, ctx->d_nrm_woff, (size_t)nwords));
+        VC_TRY(ensure(ctx, ctx->d_nrm_rows, rows.size()));
+        VC_TRY(ensure(ctx, ctx->d_nrm_out, (size_t)S));
+        VC_TRY(ensure(ctx, ctx->d_nrm_ctr, 2));
+    }
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    ctx->h_res[0] = ctx->h_res[1] = 0;
+    if (S) {
+        VC_TRY(densify_words(ctx, cur));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->d_nrm_rows.ptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_nrm_out.ptr, 0, (size_t)S * sizeof(short4), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_nrm_ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), cblock(kCcBlock);
+        hipLaunchKernelGGL(k_cc_wcount, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, ctx->h_res + 2));
+        hipLaunchKernelGGL(k_cc_woff, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
+                           (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_nrm_woff.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        NrmParams p;
+        memset(&p, 0, sizeof p);
+        p.words = cur.words.ptr; p.woff = ctx->d_nrm_woff.ptr; p.rows = ctx->d_nrm_rows.ptr;
+        p.out = ctx->d_nrm_out.ptr; p.ctr = ctx->d_nrm_ctr.ptr;
+        p.nwords = nwords; p.n = n; p.S = S;
+        for (int a = 0; a < 3; ++a) p.q[a] = (long long)q[a];
+        p.nrows = (uint32_t)rows.size(); p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
+        const uint64_t per_block = (uint64_t)(kNrmBlock / 64) * kNrmWords;
+        hipLaunchKernelGGL(k_normals, dim3((uint32_t)((nwords + per_block - 1) / per_block)), dim3(kNrmBlock), 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_nrm_ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (S && ctx->h_res[2] != S)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_normals: the occupancy holds %llu voxels, the result %llu records", (unsigned long long)ctx->h_res[2],
+                    (unsigned long long)S);
+    if (ctx->h_res[0] > S || ctx->h_res[1] > ctx->h_res[0])
+        return fail(ctx, VC_ERR_HIP, "vc_hull_normals: %llu surface records, %llu of them without a normal, among %llu", (unsigned long long)ctx->h_res[0],
+                    (unsigned long long)ctx->h_res[1], (unsigned long long)S);
+    VC_HIP(ctx, hipEventElapsedTime(&stats->normals_ms, ctx->ev[0], ctx->ev[1]));
+    stats->survivors = S;
+    stats->surface = ctx->h_res[0];
+    stats->zero = ctx->h_res[1];
+    stats->offsets = offsets;
+    for (int a = 0; a < 3; ++a) { stats->q[a] = q[a]; stats->ext[a] = ext[a]; }
+    ctx->nrm_valid = true;
+    ctx->nrm_n = S;
+    return VC_OK;
+}
+
+int vc_fetch_record_normals(vc_ctx *ctx, int16_t *n4)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->nrm_valid) return fail(ctx, VC_ERR_ARG, "no normals: call vc_hull_normals on the current carve result");
+    if (!n4) return VC_OK;                       // only asked whether the normals are valid
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->nrm_n) VC_HIP(ctx, hipMemcpy(n4, ctx->d_nrm_out.ptr, (size_t)ctx->nrm_n * sizeof(short4), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_shade_render(vc_ctx *ctx, const double *light, uint32_t ambient, uint32_t flags)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_shade_render: flags must be 0 (got %u)", flags);
+    if (!light) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no lights");
+    if (ambient > 255) return fail(ctx, VC_ERR_ARG, "vc_shade_render: ambient %u not in 0..255", ambient);
+    if (!ctx->carved || !ctx->nrm_valid) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no normals: call vc_hull_normals on the current carve result");
+    if (!ctx->rn_valid || !ctx->rn_current)
+        return fail(ctx, VC_ERR_ARG, "vc_shade_render: no images of the current carve result: call vc_render first");
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    for (uint32_t v = 0; v < ctx->rn_views; ++v) {
+        const double *L = light + 3 * (size_t)v;
+        if (!std::isfinite(L[0]) || !std::isfinite(L[1]) || !std::isfinite(L[2]))
+            return fail(ctx, VC_ERR_ARG, "vc_shade_render: the light of view %u has a component that is not finite", v);
+        const double ll = (L[0] * L[0] + L[1] * L[1]) + L[2] * L[2];
+        if (!std::isnormal(ll)) return fail(ctx, VC_ERR_ARG, "vc_shade_render: the light of view %u has squared length %g", v, ll);
+    }
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->sh_valid = false;
+    const uint64_t view_pix = (uint64_t)ctx->rn_H * ctx->rn_W, npix = view_pix * ctx->rn_views;
+    VC_TRY(ensure(ctx, ctx->d_sh_rgb, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->d_sh_light, 3 * (size_t)ctx->rn_views));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->d_sh_light.ptr, light, 3 * (size_t)ctx->rn_views * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ShadeParams p;
+    memset(&p, 0, sizeof p);
+    p.idx = ctx->d_rn_idx.ptr; p.rgbf = ctx->d_rn_rgbf.ptr;
+    p.records = cur.records.ptr; p.normals = ctx->d_nrm_out.ptr; p.light = ctx->d_sh_light.ptr;
+    p.out = ctx->d_sh_rgb.ptr;
+    p.S = ctx->survivors; p.npix = npix; p.view_pix = view_pix; p.ambient = ambient;
+    hipLaunchKernelGGL(k_shade, dim3((uint32_t)((npix + kNrmBlock - 1) / kNrmBlock)), dim3(kNrmBlock), 0, ctx->stream, p);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));             // (the lights are the caller's memory)
+    ctx->sh_valid = true;
+    return VC_OK;
+}
+
+int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb)
+{
+    if (!ctx || !rgb) return VC_ERR_ARG;
+    if (!ctx->rn_valid || !ctx->sh_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: no shaded images: call vc_shade_render first");
+    if (view >= ctx->rn_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: view %u not in [0,%u)", view, ctx->rn_views);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t HW = (size_t)ctx->rn_H * ctx->rn_W, off = (size_t)view * HW;
+    std::vector<uint32_t> px(HW);
+    VC_HIP(ctx, hipMemcpy(px.data(), ctx->d_sh_rgb.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < HW; ++k) {
+        const uint32_t q = px[k];
+        rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16);
+    }
+    return VC_OK;
+}
+
+int vc_surface_normals(vc_ctx *ctx, int16_t *n4)
+{
+    if (!ctx || !n4) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->nrm_valid) return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no normals: call vc_hull_normals on the current carve result");
+    if (!ctx->sf_valid || !ctx->sf_current)
+        return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no mesh of the current carve result: call vc_surface_mesh first");
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    const uint64_t V = ctx->sf_verts;
+    if (!V) return VC_OK;
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(ensure(ctx, ctx->d_nrm_verts, (size_t)V));
+    hipLaunchKernelGGL(k_surf_normals, dim3((uint32_t)((V + kNrmBlock - 1) / kNrmBlock)), dim3(kNrmBlock), 0, ctx->stream,
+                       (const uint64_t *)ctx->d_sf_edges.ptr, V, (const uint64_t *)cur.records.ptr, ctx->survivors,
+                       (const short4 *)ctx->d_nrm_out.ptr, ctx->nx, ctx->ny, ctx->d_nrm_verts.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipMemcpyAsync(n4, ctx->d_nrm_verts.ptr, (size_t)V * sizeof(short4), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VC_OK;
 }
 

@@ -51,6 +51,8 @@ class CarveEngine:
         self.n_cameras = 0
         self.image_size = None
         self.count = 0
+        self._render_shape = (0, (0, 0))     # views and size of the last render()
+        self._mesh_verts = 0                 # vertices of the last surface_mesh()
 
     # -- lifetime -----------------------------------------------------------------
     def close(self):
@@ -651,6 +653,7 @@ class CarveEngine:
                                       None if sh is None else _ptr(sh, ctypes.c_uint8), _ptr(bg, ctypes.c_uint8), 0,
                                       ctypes.byref(st)), "vc_render")
         V, H, W = len(views), int(H), int(W)
+        self._render_shape = (V, (H, W))
         out = {"rgb": np.empty((V, H, W, 3), dtype=np.uint8), "depth": np.empty((V, H, W), dtype=np.float32),
                "index": np.empty((V, H, W), dtype=np.uint32), "face": np.empty((V, H, W), dtype=np.uint8)}
         for k in range(V):
@@ -713,6 +716,7 @@ class CarveEngine:
         st = _lib.VcSurfaceStats()
         self._check(self._L.vc_surface_mesh(self._ctx, int(refine_steps), 0, ctypes.byref(st)), "vc_surface_mesh")
         V, F = int(st.n_verts), int(st.n_faces)
+        self._mesh_verts = V
         verts = np.empty((V, 3), dtype=np.float64)
         faces = np.empty((F, 3), dtype=np.uint32)
         rgb = np.empty((V, 3), dtype=np.uint8)
@@ -722,6 +726,87 @@ class CarveEngine:
         return {"verts": verts, "faces": faces, "rgb": rgb, "refined": refined != 0,
                 "stats": {"n_verts": V, "n_faces": F, "refined": int(st.refined), "unrefined": int(st.unrefined),
                           "point_tests": int(st.point_tests), "surface_ms": float(st.surface_ms)}}
+
+    # -- surface normals of the hull, smooth-shaded renders, mesh normals (vc_hull_normals, vc_shade_render, vc_surface_normals) ----
+    def grid_steps_um(self):
+        """(q_x, q_y, q_z): the grid steps rounded to whole micrometres, the metric of the distance and normal passes (0 on an
+        axis of one cell, which those passes refuse)."""
+        return tuple(int(np.rint(((self.bounds[2 * a + 1] - self.bounds[2 * a]) / float(n - 1)) * 1000.0)) if n > 1 else 0
+                     for a, n in enumerate(self.grid))
+
+    def normals_r2(self, radius_mm=None):
+        """r2 in um^2 of the normals' ball: radius_r2(radius_mm), or (3 x the largest grid step in um)^2 for None."""
+        if radius_mm is None:
+            return (3 * max(self.grid_steps_um())) ** 2
+        return self.radius_r2(radius_mm)
+
+    def hull_normals(self, radius_mm=None):
+        """Surface normals of the current carve result (contract: include/voxcarve.h): every survivor with a face neighbour that is
+        not one gets minus the sum of the offsets, in um, to the survivors inside a ball of radius_mm millimetres around it
+        (None: 3 x the largest grid step) -- a direction from solid to empty in world (x, y, z), integer and exact.  The result
+        stays as it is.  Returns the stats as a dict: survivors, surface, zero (surface records whose sum is 0), offsets (cells
+        of the ball), q, ext (the ball's reach in cells per axis), normals_ms."""
+        r2 = self.normals_r2(radius_mm)
+        if r2 >= 1 << 64:
+            raise ValueError("radius^2 = %d um^2 does not fit 64 bits" % r2)
+        st = _lib.VcNormalsStats()
+        self._check(self._L.vc_hull_normals(self._ctx, int(r2), 0, ctypes.byref(st)), "vc_hull_normals")
+        return {"survivors": int(st.survivors), "surface": int(st.surface), "zero": int(st.zero), "offsets": int(st.offsets),
+                "q": tuple(int(v) for v in st.q), "ext": tuple(int(v) for v in st.ext), "normals_ms": float(st.normals_ms)}
+
+    def fetch_record_normals(self):
+        """int16 [S, 4] in record order: (n_x, n_y, n_z, w), the normal scaled so that its largest component is +-32767; w = 1 on
+        surface records (whose normal may still be 0, 0, 0), a zero row elsewhere.  Fails once anything has changed the hull."""
+        out = np.empty((self.count, 4), dtype=np.int16)
+        self._check(self._L.vc_fetch_record_normals(self._ctx, _ptr(out, ctypes.c_int16)), "vc_fetch_record_normals")
+        return out
+
+    def record_normals_unit(self):
+        """float64 [S, 3] in record order: unit normals; rows without a normal stay zero."""
+        v = self.fetch_record_normals()[:, :3].astype(np.float64)
+        l = np.sqrt((v * v).sum(axis=1))
+        return v / np.where(l == 0.0, 1.0, l)[:, None]
+
+    def shade_render(self, light, ambient=64):
+        """Shades the images of the last render() with the normals (needs hull_normals() and a render of the current result):
+        light float64 [V, 3], per view the direction from the surface towards the light in world coordinates; ambient 0..255 is
+        the brightness of a surface facing away.  Returns rgb u8 [V, H, W, 3]."""
+        L = np.ascontiguousarray(light, dtype=np.float64)
+        V, (H, W) = self._render_shape
+        if L.shape != (V, 3):
+            raise ValueError("shade_render: light of shape %r, expected %r" % (L.shape, (V, 3)))
+        if not 0 <= int(ambient) <= 255:
+            raise ValueError("shade_render: ambient %r not in 0..255" % (ambient,))
+        self._check(self._L.vc_shade_render(self._ctx, _ptr(L, ctypes.c_double), int(ambient), 0), "vc_shade_render")
+        rgb = np.empty((V, H, W, 3), dtype=np.uint8)
+        for k in range(V):
+            self._check(self._L.vc_fetch_shaded(self._ctx, k, _ptr(rgb[k], ctypes.c_uint8)), "vc_fetch_shaded")
+        return rgb
+
+    def normals_valid(self):
+        """True while the normals of the last hull_normals() describe the current hull."""
+        return self._L.vc_fetch_record_normals(self._ctx, None) == _lib.VC_OK
+
+    def render_shaded(self, views, H, W, ambient=64, light=None, background=(0, 0, 0)):
+        """render() with Lambert shading from the hull's normals instead of the six face brightnesses: runs hull_normals() when
+        the normals are stale, then render(), then shade_render().  light: float64 [V, 3] (see shade_render); None = a headlight
+        per view, the direction towards the camera, -R[2, :].  Returns render()'s dict with rgb shaded and rgb_flat render's own."""
+        views = list(views)
+        if light is None:
+            light = [-np.asarray(cam.R, dtype=np.float64).reshape(3, 3)[2, :] for cam in views]
+        if not self.normals_valid():
+            self.hull_normals()
+        out = self.render(views, H, W, background=background)
+        out["rgb_flat"] = out["rgb"]
+        out["rgb"] = self.shade_render(light, ambient)
+        return out
+
+    def surface_normals(self):
+        """int16 [V, 4]: per vertex of the last surface_mesh() the stored normal of the voxel its colour comes from (the ON end
+        of its grid edge).  Needs hull_normals() and a mesh of the current result."""
+        out = np.empty((self._mesh_verts, 4), dtype=np.int16)
+        self._check(self._L.vc_surface_normals(self._ctx, _ptr(out, ctypes.c_int16)), "vc_surface_normals")
+        return out
 
     def set_option(self, name, value):
         """Launch-geometry tuning knobs (never change results); see vc_set_option."""

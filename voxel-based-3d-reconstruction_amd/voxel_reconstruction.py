@@ -163,15 +163,21 @@ def plot_marching_cubes(voxels_status, rotate=True, plot_output_path="plots", pl
     return verts, faces
 
 
-def write_ply(path, verts, faces, rgb=None):
-    """Writes a triangle mesh as binary little-endian PLY (MeshLab, Blender): float32 x, y, z per vertex, u8 red, green, blue
-    when rgb ([V, 3]) is given, and one list of three u32 vertex numbers per face.  Data only: the header names the
+def write_ply(path, verts, faces, rgb=None, normals=None):
+    """Writes a triangle mesh as binary little-endian PLY (MeshLab, Blender): float32 x, y, z per vertex, float32 nx, ny, nz
+    when normals ([V, 3]) are given, u8 red, green, blue when rgb ([V, 3]) is given, and one list of three u32 vertex numbers
+    per face.  Data only: the header names the
     elements and their properties, nothing else.  Returns the path."""
     v = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
     f = np.ascontiguousarray(faces, dtype=np.int64).reshape(-1, 3)
     if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
         raise ValueError("write_ply: a face names a vertex outside [0, %d)" % v.shape[0])
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nv = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, 3)
+        if nv.shape[0] != v.shape[0]:
+            raise ValueError("write_ply: %d normals for %d vertices" % (nv.shape[0], v.shape[0]))
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if rgb is not None:
         c = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
         if c.shape[0] != v.shape[0]:
@@ -179,6 +185,8 @@ def write_ply(path, verts, faces, rgb=None):
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     vrec = np.empty(v.shape[0], dtype=fields)
     vrec["x"], vrec["y"], vrec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vrec["nx"], vrec["ny"], vrec["nz"] = nv[:, 0], nv[:, 1], nv[:, 2]
     if rgb is not None:
         vrec["red"], vrec["green"], vrec["blue"] = c[:, 0], c[:, 1], c[:, 2]
     frec = np.empty(f.shape[0], dtype=[("n", "u1"), ("v", "<u4", (3,))])
@@ -186,6 +194,8 @@ def write_ply(path, verts, faces, rgb=None):
     frec["v"] = f
     head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0],
             "property float x", "property float y", "property float z"]
+    if normals is not None:
+        head += ["property float nx", "property float ny", "property float nz"]
     if rgb is not None:
         head += ["property uchar red", "property uchar green", "property uchar blue"]
     head += ["element face %d" % f.shape[0], "property list uchar uint vertex_indices", "end_header"]
