@@ -549,6 +549,64 @@ int vc_shade_render(vc_ctx *ctx, const double *light /* [n_views][3] */, uint32_
 int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb);     /* [H W 3] */
 int vc_surface_normals(vc_ctx *ctx, int16_t *n4);                  /* [V][4], vertex order of vc_fetch_surface_mesh */
 
+/* ---- the hull split into K figures on the floor plane (no reference counterpart) --------------------------------------------------
+ * vc_hull_clusters runs K-means over the columns of the current carve result, as vc_fetch_occupancy and vc_fetch_records see it
+ * (photo carve, components, morphology, grow and footprint rules included): world "up" is -z, so a floor position is a column
+ * (ix, iy).  The result is left exactly as it is.  The contract, bit for bit (tests/clusters_np.py restates it).  Integers only, and
+ * every sum is a sum over a set: the outputs do not depend on evaluation order.
+ *   inputs: K in 1..16; max_iters in 1..255; min_column (0 and 1: no floor); hist_iz_lo <= hist_iz_hi < nz, the inclusive band of
+ *     layers of the colour signature; init NULL or int64 [K][2], centres in um from the grid's (x_min, y_min) corner, every
+ *     component within +-2^30 (d2 then fits int64); flags = 0; stats (required).
+ *   1 metric: q_x, q_y = item 2 of vc_hull_distance for the x and y axes only, llrint(((max - min) / (n - 1)) * 1000.0) with that
+ *     item's refusals for those two axes.  Column (ix, iy) has index col = ix ny + iy and position P = (q_x ix, q_y iy);
+ *     d2(P, c) = (P_x - c_x)^2 + (P_y - c_y)^2 in int64.
+ *   2 floor map: n[col] = the number of survivors i with i mod (nx ny) = col (u32); weight w = n if n >= min_column, else 0;
+ *     Wtot = sum w.  With Wtot = 0 (S = 0, for example) there are no rounds: iterations = 0, converged = 1, every label is 0, the
+ *     centres are init, or zeros.
+ *   3 seeding when init is NULL: M = ((sum w P_x + Wtot / 2) div Wtot, the same for y); c_0 = the position of the weighted column
+ *     (w > 0) with the smallest d2(P, M); for j = 1 .. K - 1, c_j = the position of the weighted column that maximises
+ *     min_{i<j} d2(P, c_i) (farthest first).  Every tie goes to the lowest col.  Fewer weighted columns than K give duplicate
+ *     centres, and the duplicates end up empty under item 4.
+ *   4 round r = 1, 2, ...: every column with n > 0 takes label = argmin_k d2(P, c_k), a tie the lowest k; then every k with
+ *     W_k = sum over label = k of w > 0 takes c_k = ((sum w P_x + W_k / 2) div W_k, the same for y); a cluster with W_k = 0 keeps
+ *     its centre.  The rounds stop after the one in which no centre changed (converged = 1, iterations = r), else after
+ *     max_iters (converged = 0).  Every sum stays below 2^62.
+ *   5 outputs.  vc_fetch_cluster_labels: u8 [S], each record its column's label of the last round.  vc_fetch_clusters:
+ *     vc_cluster_t [K] -- centre_um; voxels = the records with that label; weight = W_k of the last round; columns = the columns
+ *     with n > 0 and that label; lo / hi = the inclusive box of its records in (ix, iy, iz), and lo = 0xffffffff, hi = 0 on every
+ *     axis (lo > hi) for a cluster without a record.  vc_fetch_cluster_histograms: u32 [K][512], bin (r >> 5) << 6 | (g >> 5) << 3
+ *     | (b >> 5) over the records of label k whose seen byte is 1 and whose iz lies in the band, with the colours the records have
+ *     at the call.  vc_fetch_floor_map: u32 [nx ny], n.  vc_fetch_floor_labels: u8 [nx ny], 255 where n = 0.
+ *   6 vc_paint_clusters(rgb u8 [K][3]): every record's RGB becomes its label's entry; index and seen byte stay, as
+ *     vc_color_visible recolours in place.  The next carve gives the camera colours again.
+ *   7 VC_ERR_ARG (with a message, nothing launched) when there is no carve result, steps are in flight, the carve ran with
+ *     VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached, K, max_iters, the
+ *     band, init or the metric is out of range, flags != 0, stats == NULL.  S = 0 is no error.  Synchronous.
+ *   8 lifetime: the fetch calls and vc_paint_clusters fail until the pass has run on the current result and again after anything
+ *     that changes which voxels survive (a carve, vc_photo_carve, vc_hull_components, vc_hull_morphology, a vc_hull_grow that adds
+ *     something), as vc_fetch_component_labels does; colour passes (vc_color_visible, vc_paint_clusters) leave them valid.
+ * stats (required): survivors; columns = columns with n > 0; weight = Wtot; iterations; converged; q; clusters_ms = HIP events
+ * around the whole call. */
+typedef struct {
+    int64_t centre_um[2];
+    uint64_t voxels, weight;
+    uint32_t columns, lo[3], hi[3];
+} vc_cluster_t;
+typedef struct {
+    uint64_t survivors, columns, weight;
+    uint64_t q[2];                  /* x, y in um */
+    uint32_t iterations, converged;
+    float clusters_ms;              /* HIP events around the whole call */
+} vc_cluster_stats_t;
+int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_column, uint32_t hist_iz_lo, uint32_t hist_iz_hi,
+                     const int64_t *init /* [K][2] um, or NULL */, uint32_t flags /* must be 0 */, vc_cluster_stats_t *stats);
+int vc_fetch_cluster_labels(vc_ctx *ctx, uint8_t *labels);                 /* [S], record order */
+int vc_fetch_clusters(vc_ctx *ctx, vc_cluster_t *out);                     /* [K] */
+int vc_fetch_cluster_histograms(vc_ctx *ctx, uint32_t *hist);              /* [K][512] */
+int vc_fetch_floor_map(vc_ctx *ctx, uint32_t *n);                          /* [nx ny] */
+int vc_fetch_floor_labels(vc_ctx *ctx, uint8_t *labels);                   /* [nx ny] */
+int vc_paint_clusters(vc_ctx *ctx, const uint8_t *rgb /* [K][3] */);
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own
@@ -707,6 +765,8 @@ int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *
  *                                  below theirs; visible_big_rect (64)  splat rectangles of more pixels get a workgroup each
  *   rendering       render_blocks (1)  vc_render skips empty blocks of 8^3 voxels whole; 0: one cell per step everywhere
  *   meshing         surface_order (1)  vc_surface_mesh's bisection tries the cameras that rejected P_off first; 0: camera order
+ *   clusters        cluster_floor_records (1)  vc_hull_clusters builds its floor map by one atomic per record, the faster way
+ *                                  as measured; 0: from the occupancy words (the same map; scripts/exp_clusters.py times both)
  *   experiments     dbg (0)  bit 0: skip the per-voxel level (undecided words count as alive), bit 1: skip the word level
  *                                  too -- WRONG results on purpose, to time the levels apart (scripts/exp_bricks.py); bit 2:
  *                                  no word-level tests, every word of a listed brick goes to the per-voxel level (right results)

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--close MM] [--open MM] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -12,7 +12,10 @@ what is thinner than the ball leaves the hull; --close MM: the hull closed by a 
 carve and before any opening, assignment.configure(hull_close_mm=MM) -- tunnels and dents narrower than the ball are filled, which
 is what a hole in one camera's mask carves; --smooth (with --render): every hit shaded by the hull's surface normal under a
 headlight, assignment.render_views(smooth=True), instead of the six face brightnesses; --normals (with --mesh): the PLY carries
-nx, ny, nz per vertex, assignment.surface_mesh(normals=True); --help: this text)."""
+nx, ny, nz per vertex, assignment.surface_mesh(normals=True); --clusters K: the hull split into K figures on the floor plane on
+the device, assignment.configure(clusters=K) -- their floor positions in world mm and their sizes are printed; --cluster-paint
+(with --clusters): every voxel in its figure's colour, in the PLY, the --render images and the --mesh;
+--help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
     print(__doc__)
@@ -29,6 +32,14 @@ if smooth:
 with_normals = "--normals" in sys.argv
 if with_normals:
     sys.argv.remove("--normals")
+clusters = 0
+if "--clusters" in sys.argv:
+    k = sys.argv.index("--clusters")
+    clusters = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+cluster_paint = "--cluster-paint" in sys.argv
+if cluster_paint:
+    sys.argv.remove("--cluster-paint")
 render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
@@ -63,7 +74,7 @@ masks = fx.golden_masks()
 frames = [np.dstack([m // 2 + 60, m // 3 + 40, 255 - m // 2]).astype(np.uint8) for m in masks]   # any BGR image
 assignment.configure(frame_source=assignment.StaticFrameSource([(frames, masks)]),
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
-                     hull_open_mm=open_mm, hull_close_mm=close_mm)
+                     hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
 if out != "-":
@@ -74,6 +85,13 @@ if out != "-":
             f.write("%g %g %g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
 print("%d voxels of the %dx%dx%d grid survive all 4 views (footprint %s, %sopened by %g mm) -> %s; extent x %.2f..%.2f, y %.2f..%.2f, z %.2f..%.2f" %
       (len(pos), g, g, g, footprint, "closed by %g mm, " % close_mm if close_mm > 0 else "", open_mm, out, pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max(), pos[:, 2].min(), pos[:, 2].max()))
+if clusters:
+    cl = assignment.clusters()
+    print("clusters: %d figures in %d rounds (%s, %.3f ms on the device)" % (clusters, cl["iterations"],
+                                                                              "converged" if cl["converged"] else "not converged", cl["clusters_ms"]))
+    for k in range(clusters):
+        print("  figure %d: floor position x %.1f y %.1f mm, %d voxels in %d columns" % (k, cl["figures"]["centre_mm"][k, 0], cl["figures"]["centre_mm"][k, 1],
+                                                                                 cl["figures"]["voxels"][k], cl["figures"]["columns"][k]))
 
 
 def write_image(path, img):

@@ -36,6 +36,7 @@ c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_i16p = ctypes.POINTER(ctypes.c_int16)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 c_u64p = ctypes.POINTER(ctypes.c_uint64)
+c_i64p = ctypes.POINTER(ctypes.c_int64)
 c_f64p = ctypes.POINTER(ctypes.c_double)
 c_ctx = ctypes.c_void_p
 
@@ -100,6 +101,16 @@ class VcGrowStats(ctypes.Structure):
 class VcNormalsStats(ctypes.Structure):
     _fields_ = [("survivors", ctypes.c_uint64), ("surface", ctypes.c_uint64), ("zero", ctypes.c_uint64), ("offsets", ctypes.c_uint64),
                 ("q", ctypes.c_uint64 * 3), ("ext", ctypes.c_uint32 * 3), ("normals_ms", ctypes.c_float)]
+
+
+class VcCluster(ctypes.Structure):
+    _fields_ = [("centre_um", ctypes.c_int64 * 2), ("voxels", ctypes.c_uint64), ("weight", ctypes.c_uint64),
+                ("columns", ctypes.c_uint32), ("lo", ctypes.c_uint32 * 3), ("hi", ctypes.c_uint32 * 3)]
+
+
+class VcClusterStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("columns", ctypes.c_uint64), ("weight", ctypes.c_uint64), ("q", ctypes.c_uint64 * 2),
+                ("iterations", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("clusters_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -193,6 +204,14 @@ SIGNATURES = {
     "vc_shade_render": (ctypes.c_int, [c_ctx, c_f64p, ctypes.c_uint32, ctypes.c_uint32]),
     "vc_fetch_shaded": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
     "vc_surface_normals": (ctypes.c_int, [c_ctx, c_i16p]),
+    "vc_hull_clusters": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                        c_i64p, ctypes.c_uint32, ctypes.POINTER(VcClusterStats)]),
+    "vc_fetch_cluster_labels": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_fetch_clusters": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcCluster)]),
+    "vc_fetch_cluster_histograms": (ctypes.c_int, [c_ctx, c_u32p]),
+    "vc_fetch_floor_map": (ctypes.c_int, [c_ctx, c_u32p]),
+    "vc_fetch_floor_labels": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_paint_clusters": (ctypes.c_int, [c_ctx, c_u8p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

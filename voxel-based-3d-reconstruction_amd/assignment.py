@@ -163,7 +163,9 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
              "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
              "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
-             "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None}
+             "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None,
+             "clusters": 0, "cluster_min_column": 1, "cluster_paint": False}
+_cluster_state = {"centres_mm": None, "references": None, "last": None}
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -191,7 +193,13 @@ def configure(frame_source=None, **settings):
     ball of that radius in world millimetres are filled -- what a hole in one camera's mask carves through the figure; the added
     voxels are coloured from the colour camera.  voxels_status() describes the closed hull.  0 (the default) adds nothing.
     normal_radius_mm: the radius of the ball that render_views(smooth=True) and surface_mesh(normals=True) estimate the hull's
-    surface normals from (CarveEngine.hull_normals); None (the default) is 3 x the largest grid step."""
+    surface normals from (CarveEngine.hull_normals); None (the default) is 3 x the largest grid step.
+    clusters, cluster_min_column, cluster_paint: when clusters = K > 0 (at most 16), every frame ends -- after all hull passes
+    and the colouring -- with CarveEngine.cluster_hull(K, min_column=cluster_min_column): the hull split into K figures on the
+    floor plane.  The first frame seeds itself and keeps its colour signatures as the references; every later frame starts from
+    the previous frame's centres, so label k stays the same figure while the figures keep apart.  clusters() returns the last
+    frame's split.  cluster_paint=True paints every voxel in its figure's colour (voxcarve.clusters.PALETTE) before the
+    positions and colours are returned.  0 (the default) runs nothing."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -206,7 +214,13 @@ def configure(frame_source=None, **settings):
     CarveEngine.radius_r2(settings.get("hull_close_mm", _settings["hull_close_mm"]))
     if settings.get("normal_radius_mm", _settings["normal_radius_mm"]) is not None:
         CarveEngine.radius_r2(settings.get("normal_radius_mm", _settings["normal_radius_mm"]))
+    k = settings.get("clusters", _settings["clusters"])
+    if not isinstance(k, (int, np.integer)) or not 0 <= k <= 16:
+        raise ValueError("clusters %r, expected an integer in 0..16" % (k,))
+    if int(settings.get("cluster_min_column", _settings["cluster_min_column"])) < 0:
+        raise ValueError("cluster_min_column %r is negative" % (settings["cluster_min_column"],))
     _settings.update(settings)
+    _cluster_state.update(centres_mm=None, references=None, last=None)
     _source = frame_source
     if _engine is not None:
         _engine.close()
@@ -276,9 +290,38 @@ def set_voxel_positions(width, height, depth):
         _engine.photo_carve(slot=0, var_threshold=_settings["photo_var_threshold"])
     elif visible:
         _engine.color_visible(slot=0)
+    if _settings["clusters"] > 0:
+        _cluster_frame()
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)
+
+
+def _cluster_frame():
+    """The frame's split into figures, warm-started from the previous frame's centres (see configure)."""
+    from .clusters import MATCH_MAX_K, match
+    K = int(_settings["clusters"])
+    out = _engine.cluster_hull(K, min_column=int(_settings["cluster_min_column"]), init_mm=_cluster_state["centres_mm"])
+    out["figures"] = _engine.fetch_clusters()
+    out["histograms"] = _engine.fetch_cluster_histograms()
+    if _cluster_state["references"] is None:
+        _cluster_state["references"] = out["histograms"].copy()
+    out["identity"] = match(_cluster_state["references"], out["histograms"]) if K <= MATCH_MAX_K else None
+    _cluster_state["centres_mm"] = out["centres_mm"]
+    _cluster_state["last"] = out
+    if _settings["cluster_paint"]:
+        _engine.paint_clusters()
+
+
+def clusters():
+    """The split of the last set_voxel_positions call's hull into figures (configure(clusters=K)): the dict of
+    CarveEngine.cluster_hull (survivors, columns, weight, iterations, converged, q, clusters_ms, k, centres_mm) with figures: the
+    dict of CarveEngine.fetch_clusters (per figure centre_um, centre_mm, voxels, weight, columns, lo, hi), histograms u32
+    [K, 512] and identity: the permutation voxcarve.clusters.match finds between the first frame's colour signatures and this
+    frame's (identity[k] = the label that looks like the first frame's figure k; None above 8 figures)."""
+    if _engine is None or not initialized or _cluster_state["last"] is None:
+        raise RuntimeError("no clusters: configure(clusters=K) and set_voxel_positions have not run")
+    return _cluster_state["last"]
 
 
 def voxels_status():

@@ -45,6 +45,7 @@
 #include "vc_distance.h"
 #include "vc_grow.h"
 #include "vc_normals.h"
+#include "vc_clusters.h"
 
 #pragma clang fp contract(off)
 
@@ -399,6 +400,17 @@ struct vc_ctx {
     bool rn_current = false;         // the images of the last render show the current result (rn_valid outlives a carve)
     bool sf_current = false;         // the last surface mesh was made on the current result (sf_valid outlives a carve)
     bool sh_valid = false;           // shaded images of the last render exist
+    // vc_hull_clusters: survivors per column, the columns' and the records' labels, the histograms [K][512], the boxes [K][6],
+    // the accumulators (kClAccTotal u64, layout at vc_hull_clusters), the seeds' columns; the clusters as the host assembled them
+    DevBuf<uint32_t> d_cl_fmap, d_cl_hist, d_cl_box, d_cl_seed;
+    DevBuf<uint8_t> d_cl_flab, d_cl_lab;
+    DevBuf<unsigned long long> d_cl_acc;
+    uint64_t *h_cl = nullptr;        // page-locked read-back of the accumulators
+    std::vector<vc_cluster_t> cl_out;
+    bool cl_valid = false;           // labels, clusters and maps belong to the vc_hull_clusters that ran on the current result
+    uint64_t cl_n = 0;               // its survivors
+    uint32_t cl_k = 0, cl_ncol = 0;  // its K and nx ny
+    int cluster_floor_records = 1;   // the floor map by one atomic per record (measured the faster way); 0: from the occupancy words
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1361,6 +1373,9 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_sf_ctr);
     release(ctx->d_nrm_woff); release(ctx->d_nrm_rows); release(ctx->d_sh_rgb); release(ctx->d_nrm_out); release(ctx->d_nrm_verts);
     release(ctx->d_nrm_ctr); release(ctx->d_sh_light);
+    release(ctx->d_cl_fmap); release(ctx->d_cl_hist); release(ctx->d_cl_box); release(ctx->d_cl_seed); release(ctx->d_cl_flab);
+    release(ctx->d_cl_lab); release(ctx->d_cl_acc);
+    if (ctx->h_cl) (void)hipHostFree(ctx->h_cl);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
     if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
@@ -1411,7 +1426,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1424,7 +1439,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1468,7 +1483,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1729,7 +1744,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;   // the next carve invalidates what the post-carve passes left
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -2073,7 +2088,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2410,7 +2425,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
@@ -2492,7 +2507,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
     if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
@@ -2648,11 +2663,11 @@ static void dist_harvest(vc_ctx *ctx)
     ctx->dist_ev_kind.clear();
 }
 
-// Item 2 of the contract: the steps in micrometres, q = x, y, z.
-static int dist_metric(vc_ctx *ctx, const char *what, uint64_t q[3])
+// Item 2 of the contract: the steps in micrometres, q = x, y, z (the first `axes` of them: vc_hull_clusters takes x and y).
+static int dist_metric(vc_ctx *ctx, const char *what, uint64_t *q, int axes = 3)
 {
     const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < axes; ++a) {
         if (n[a] < 2) return fail(ctx, VC_ERR_ARG, "%s: axis %c has %u cells, a step needs 2", what, "xyz"[a], n[a]);
         const double s = (ctx->bounds[2 * a + 1] - ctx->bounds[2 * a]) / (double)(n[a] - 1);
         const long long v = llrint(s * 1000.0);
@@ -2881,13 +2896,13 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
             VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S0, r2, ctx->d_dist_acc.ptr + 2));
         }
         // the result changes from here on
-        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
         VC_TRY(compact_records(ctx, cur, DistKept{ctx->d_dist_rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
                                S0, ctx->h_res + 1));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->d_dist_acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_dist_acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     dist_harvest(ctx);
@@ -3006,7 +3021,7 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
         VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_added.ptr, 0, (size_t)S1, ctx->stream));
         if (added) {
             // the result changes from here on
-            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
             const dim3 gblock(kGrowBlock), rgrid((uint32_t)((nrange + kGrowBlock - 1) / kGrowBlock));
             VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->d_grow_addw.ptr, w0, nrange);
             // survivors per group of the step, counted again: the packing skips the groups whose count is zero, and an added voxel
@@ -3567,6 +3582,261 @@ int vc_surface_normals(vc_ctx *ctx, int16_t *n4)
     return VC_OK;
 }
 
+// ---- the hull split into K figures on the floor plane (vc_clusters.h; contract in include/voxcarve.h) ----
+// d_cl_acc: [0, 4) Wtot, sum w Px, sum w Py, columns; [4, 20) the seeds' largest keys; [20, 36) voxels per cluster; [36, 100) the
+// round's {W_k, sum w Px, sum w Py, columns}.  d_cl_box: lo [K][3], then hi [K][3].
+constexpr uint32_t kClAccSeed = 4, kClAccVoxels = 20, kClAccRound = 36, kClAccTotal = kClAccRound + kClMaxK * kClAcc;
+constexpr uint32_t kClHostBox = kClMaxK * 6 / 2;               // the boxes read back behind the accumulators, as u64
+
+int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_column, uint32_t hist_iz_lo, uint32_t hist_iz_hi,
+                     const int64_t *init, uint32_t flags, vc_cluster_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: flags must be 0 (got %u)", flags);
+    VC_TRY(result_refusals(ctx, "vc_hull_clusters", "label", "clustering"));
+    if (K < 1 || K > kClMaxK) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: K = %u not in [1, %u]", K, kClMaxK);
+    if (max_iters < 1 || max_iters > 255) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: max_iters %u not in [1, 255]", max_iters);
+    if (hist_iz_lo > hist_iz_hi || hist_iz_hi >= ctx->nz)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: the band [%u, %u] of the colour signature is not inside the grid's %u layers",
+                    hist_iz_lo, hist_iz_hi, ctx->nz);
+    if (init)
+        for (uint32_t k = 0; k < 2 * K; ++k)
+            if (init[k] > (1ll << 30) || init[k] < -(1ll << 30))
+                return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: init centre %u has %c = %lld um, beyond +-2^30", k / 2, "xy"[k & 1], (long long)init[k]);
+    uint64_t q[2];
+    VC_TRY(dist_metric(ctx, "vc_hull_clusters", q, 2));
+    const uint64_t S = ctx->survivors, n = ctx->n_voxels(), ncol64 = (uint64_t)ctx->nx * ctx->ny;
+    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: %llu voxels exceed the u32 index", (unsigned long long)n);
+    const uint32_t ncol = (uint32_t)ncol64;
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->cl_valid = false;
+    if (!ctx->h_cl) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_cl), (kClAccTotal + kClHostBox) * sizeof(uint64_t), hipHostMallocDefault));
+    VC_TRY(ensure(ctx, ctx->d_cl_fmap, (size_t)ncol));
+    VC_TRY(ensure(ctx, ctx->d_cl_flab, (size_t)ncol));
+    VC_TRY(ensure(ctx, ctx->d_cl_lab, (size_t)S));
+    VC_TRY(ensure(ctx, ctx->d_cl_hist, (size_t)kClMaxK * kClBins));
+    VC_TRY(ensure(ctx, ctx->d_cl_box, (size_t)kClMaxK * 6));
+    VC_TRY(ensure(ctx, ctx->d_cl_seed, (size_t)kClMaxK));
+    VC_TRY(ensure(ctx, ctx->d_cl_acc, (size_t)kClAccTotal));
+    uint32_t *blo = ctx->d_cl_box.ptr, *bhi = blo + kClMaxK * 3;
+    uint64_t *h = ctx->h_cl;
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_fmap.ptr, 0, (size_t)ncol * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_flab.ptr, 0xff, (size_t)ncol, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_hist.ptr, 0, (size_t)kClMaxK * kClBins * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(blo, 0xff, (size_t)kClMaxK * 3 * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(bhi, 0, (size_t)kClMaxK * 3 * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_seed.ptr, 0xff, (size_t)kClMaxK * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_acc.ptr, 0, (size_t)kClAccTotal * sizeof(uint64_t), ctx->stream));
+    ClCols cols;
+    memset(&cols, 0, sizeof cols);
+    cols.fmap = ctx->d_cl_fmap.ptr; cols.ncol = ncol; cols.ny = ctx->ny; cols.min_column = min_column;
+    cols.qx = (long long)q[0]; cols.qy = (long long)q[1];
+    const dim3 block(kClBlock);
+    const uint64_t cblocks = (ncol64 + kClBlock - 1) / kClBlock;
+    const dim3 cgrid((uint32_t)(cblocks < kClMaxBlocks ? cblocks : kClMaxBlocks));
+    unsigned long long *acc = ctx->d_cl_acc.ptr;
+    memset(h, 0, (kClAccTotal + kClHostBox) * sizeof(uint64_t));
+    if (S) {
+        // item 2: the floor map and its moments
+        if (ctx->cluster_floor_records) {
+            hipLaunchKernelGGL(k_cl_floor_records, dim3((uint32_t)((S + kClBlock - 1) / kClBlock)), block, 0, ctx->stream,
+                               (const uint64_t *)cur.records.ptr, S, ncol, ctx->d_cl_fmap.ptr);
+        } else {
+            VC_TRY(densify_words(ctx, cur));
+            const uint32_t ngroups = (uint32_t)((ncol64 + 63) / 64), nchunks = (ctx->nz + kClLayers - 1) / kClLayers;
+            const uint64_t waves = (uint64_t)ngroups * nchunks;
+            hipLaunchKernelGGL(k_cl_floor, dim3((uint32_t)((waves + kClBlock / 64 - 1) / (kClBlock / 64))), block, 0, ctx->stream,
+                               (const uint64_t *)cur.words.ptr, (n + 63) / 64, ncol, ctx->nz, ngroups, nchunks, ctx->d_cl_fmap.ptr);
+        }
+        VC_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_cl_moments, cgrid, block, 0, ctx->stream, cols, acc);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(h, acc, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    const uint64_t Wtot = h[0], columns = h[3];
+    if (Wtot > S || columns > S || h[1] >= (1ull << 62) || h[2] >= (1ull << 62))
+        return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: the floor map weighs %llu in %llu columns, the result has %llu records",
+                    (unsigned long long)Wtot, (unsigned long long)columns, (unsigned long long)S);
+    ClCentres c;
+    memset(&c, 0, sizeof c);
+    if (init) for (uint32_t k = 0; k < K; ++k) { c.c[k][0] = init[2 * k]; c.c[k][1] = init[2 * k + 1]; }
+    if (Wtot && !init) {
+        // item 3: two launches per seed, the seeds' columns stay on the device until all are picked
+        ClSeed sd;
+        memset(&sd, 0, sizeof sd);
+        sd.seedcol = ctx->d_cl_seed.ptr; sd.pick = ctx->d_cl_seed.ptr; sd.best = acc + kClAccSeed;
+        sd.mx = (long long)((h[1] + Wtot / 2) / Wtot); sd.my = (long long)((h[2] + Wtot / 2) / Wtot);
+        for (uint32_t j = 0; j < K; ++j) {
+            sd.j = j;
+            hipLaunchKernelGGL(k_cl_seed_best, cgrid, block, 0, ctx->stream, cols, sd);
+            hipLaunchKernelGGL(k_cl_seed_pick, cgrid, block, 0, ctx->stream, cols, sd);
+            VC_HIP(ctx, hipGetLastError());
+        }
+        VC_HIP(ctx, hipMemcpyAsync(h + 4, ctx->d_cl_seed.ptr, kClMaxK * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const uint32_t *sc = reinterpret_cast<const uint32_t *>(h + 4);
+        for (uint32_t k = 0; k < K; ++k) {
+            if (sc[k] >= ncol) return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: seed %u fell on column %u of %u", k, sc[k], ncol);
+            c.c[k][0] = (long long)q[0] * (sc[k] / ctx->ny); c.c[k][1] = (long long)q[1] * (sc[k] % ctx->ny);
+        }
+    }
+    // item 4: one launch and 8 K words back per round
+    uint32_t r = 0;
+    bool converged = Wtot == 0;
+    uint64_t *hr = h + kClAccRound;
+    memset(hr, 0, kClMaxK * kClAcc * sizeof(uint64_t));
+    while (Wtot && r < max_iters) {
+        ++r;
+        VC_HIP(ctx, hipMemsetAsync(acc + kClAccRound, 0, kClMaxK * kClAcc * sizeof(uint64_t), ctx->stream));
+        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, K, c, ctx->d_cl_flab.ptr, acc + kClAccRound);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(hr, acc + kClAccRound, kClMaxK * kClAcc * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        bool changed = false;
+        for (uint32_t k = 0; k < K; ++k) {
+            const uint64_t W = hr[kClAcc * k];
+            if (!W) continue;
+            if (W > Wtot) return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: cluster %u weighs %llu of %llu", k, (unsigned long long)W, (unsigned long long)Wtot);
+            const long long x = (long long)((hr[kClAcc * k + 1] + W / 2) / W), y = (long long)((hr[kClAcc * k + 2] + W / 2) / W);
+            changed |= x != c.c[k][0] || y != c.c[k][1];
+            c.c[k][0] = x; c.c[k][1] = y;
+        }
+        if (!changed) { converged = true; break; }
+    }
+    if (S && !Wtot) {
+        // no column reaches min_column: no rounds, every record takes label 0 (one cluster's launch; its weights are zero)
+        VC_HIP(ctx, hipMemsetAsync(acc + kClAccRound, 0, kClMaxK * kClAcc * sizeof(uint64_t), ctx->stream));
+        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, 1u, c, ctx->d_cl_flab.ptr, acc + kClAccRound);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(hr, acc + kClAccRound, kClMaxK * kClAcc * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (S) {
+        // item 5: voxels and boxes from the columns, labels, histograms and iz ranges from the records
+        hipLaunchKernelGGL(k_cl_columns, cgrid, block, 0, ctx->stream, cols, K, (const uint8_t *)ctx->d_cl_flab.ptr, acc + kClAccVoxels, blo, bhi);
+        VC_HIP(ctx, hipGetLastError());
+        ClRecords p;
+        memset(&p, 0, sizeof p);
+        p.records = cur.records.ptr; p.flab = ctx->d_cl_flab.ptr; p.lab = ctx->d_cl_lab.ptr; p.hist = ctx->d_cl_hist.ptr;
+        p.blo = blo; p.bhi = bhi;
+        p.S = S; p.ncol = ncol; p.K = K; p.zlo = hist_iz_lo; p.zhi = hist_iz_hi;
+        const uint64_t rblocks = (S + kClBlock - 1) / kClBlock, rgrid = rblocks < kClMaxBlocks ? rblocks : kClMaxBlocks;
+        p.per = ((S + rgrid - 1) / rgrid + kClBlock - 1) / kClBlock * kClBlock;
+        hipLaunchKernelGGL(k_cl_records, dim3((uint32_t)rgrid), block, 0, ctx->stream, p);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(h + kClAccVoxels, acc + kClAccVoxels, kClMaxK * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(h + kClAccTotal, blo, kClMaxK * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VC_HIP(ctx, hipEventElapsedTime(&stats->clusters_ms, ctx->ev[0], ctx->ev[1]));
+    const uint32_t *hb = reinterpret_cast<const uint32_t *>(h + kClAccTotal);     // lo [kClMaxK][3], hi [kClMaxK][3] (zeros when S = 0)
+    ctx->cl_out.assign(K, vc_cluster_t{});
+    uint64_t labelled = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+        vc_cluster_t &o = ctx->cl_out[k];
+        o.centre_um[0] = c.c[k][0]; o.centre_um[1] = c.c[k][1];
+        o.voxels = S ? h[kClAccVoxels + k] : 0;
+        o.weight = hr[kClAcc * k];
+        o.columns = (uint32_t)hr[kClAcc * k + 3];
+        for (int a = 0; a < 3; ++a) {
+            o.lo[a] = o.voxels ? hb[3 * k + a] : 0xffffffffu;
+            o.hi[a] = o.voxels ? hb[kClMaxK * 3 + 3 * k + a] : 0u;
+        }
+        labelled += o.voxels;
+    }
+    if (labelled != S)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: the occupancy holds %llu voxels, the result %llu records", (unsigned long long)labelled,
+                    (unsigned long long)S);
+    stats->survivors = S;
+    stats->columns = columns;
+    stats->weight = Wtot;
+    stats->iterations = r;
+    stats->converged = converged ? 1u : 0u;
+    stats->q[0] = q[0]; stats->q[1] = q[1];
+    ctx->cl_valid = true;
+    ctx->cl_n = S; ctx->cl_k = K; ctx->cl_ncol = ncol;
+    return VC_OK;
+}
+
+// The refusal the fetch calls and vc_paint_clusters share.
+static int clusters_current(vc_ctx *ctx)
+{
+    if (!ctx->carved || !ctx->cl_valid) return fail(ctx, VC_ERR_ARG, "no clusters: call vc_hull_clusters on the current carve result");
+    return VC_OK;
+}
+
+int vc_fetch_cluster_labels(vc_ctx *ctx, uint8_t *labels)
+{
+    if (!ctx) return VC_ERR_ARG;
+    VC_TRY(clusters_current(ctx));
+    if (!labels) return VC_OK;                   // only asked whether the clustering is valid
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->cl_n) VC_HIP(ctx, hipMemcpy(labels, ctx->d_cl_lab.ptr, (size_t)ctx->cl_n, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_clusters(vc_ctx *ctx, vc_cluster_t *out)
+{
+    if (!ctx || !out) return VC_ERR_ARG;
+    VC_TRY(clusters_current(ctx));
+    memcpy(out, ctx->cl_out.data(), ctx->cl_out.size() * sizeof(vc_cluster_t));
+    return VC_OK;
+}
+
+int vc_fetch_cluster_histograms(vc_ctx *ctx, uint32_t *hist)
+{
+    if (!ctx || !hist) return VC_ERR_ARG;
+    VC_TRY(clusters_current(ctx));
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_HIP(ctx, hipMemcpy(hist, ctx->d_cl_hist.ptr, (size_t)ctx->cl_k * kClBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_floor_map(vc_ctx *ctx, uint32_t *n)
+{
+    if (!ctx || !n) return VC_ERR_ARG;
+    VC_TRY(clusters_current(ctx));
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_HIP(ctx, hipMemcpy(n, ctx->d_cl_fmap.ptr, (size_t)ctx->cl_ncol * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_floor_labels(vc_ctx *ctx, uint8_t *labels)
+{
+    if (!ctx || !labels) return VC_ERR_ARG;
+    VC_TRY(clusters_current(ctx));
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_HIP(ctx, hipMemcpy(labels, ctx->d_cl_flab.ptr, (size_t)ctx->cl_ncol, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_paint_clusters(vc_ctx *ctx, const uint8_t *rgb)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!rgb) return fail(ctx, VC_ERR_ARG, "vc_paint_clusters: no palette");
+    VC_TRY(clusters_current(ctx));
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if (!ctx->cl_n) return VC_OK;
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    ClPalette pal;
+    memset(&pal, 0, sizeof pal);
+    for (uint32_t k = 0; k < ctx->cl_k; ++k) pal.rgb[k] = (uint32_t)rgb[3 * k] | ((uint32_t)rgb[3 * k + 1] << 8) | ((uint32_t)rgb[3 * k + 2] << 16);
+    hipLaunchKernelGGL(k_cl_paint, dim3((uint32_t)((ctx->cl_n + kClBlock - 1) / kClBlock)), dim3(kClBlock), 0, ctx->stream, cur.records.ptr,
+                       ctx->cl_n, (const uint8_t *)ctx->d_cl_lab.ptr, pal);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VC_OK;
+}
+
 // ---- the step before the path, its data-parallel part (reference background_subtraction.py:153-168) ----
 static int hsv_tables(vc_ctx *ctx);
 
@@ -4035,6 +4305,7 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
     else if (k == "visible_big_rect" && value >= 1) ctx->visible_big_rect = value;
     else if (k == "render_blocks") ctx->render_blocks = value != 0;
     else if (k == "surface_order") ctx->surface_order = value != 0;
+    else if (k == "cluster_floor_records") ctx->cluster_floor_records = value != 0;
     else if (k == "cull") ctx->cull = value != 0;
     else if (k == "bricks") ctx->bricks = value != 0;
     else if (k == "dbg") ctx->dbg = value;

@@ -808,6 +808,92 @@ class CarveEngine:
         self._check(self._L.vc_surface_normals(self._ctx, _ptr(out, ctypes.c_int16)), "vc_surface_normals")
         return out
 
+    # -- the hull split into K figures on the floor plane (vc_hull_clusters, vc_paint_clusters) ------------------------------------
+    def cluster_hull(self, k, max_iters=32, min_column=1, init_mm=None, hist_iz=None):
+        """Splits the current carve result into k figures by K-means over its columns on the floor plane (world "up" is -z;
+        contract: include/voxcarve.h): every column (ix, iy) weighs the survivors above it, columns with fewer than min_column
+        weigh nothing (specks).  init_mm: k world (x, y) positions in mm to start from (the previous frame's centres: label k then
+        stays the same figure); None seeds farthest-first.  hist_iz = (lo, hi): the inclusive band of layers the colour signatures
+        (fetch_cluster_histograms) are taken from; None is every layer.  Integers only and exact; the result stays as it is.
+        Returns the stats as a dict: survivors, columns, weight, iterations, converged, q, clusters_ms, k and centres_mm (float64
+        [k, 2], world mm)."""
+        init = None
+        if init_mm is not None:
+            c = np.asarray(init_mm, dtype=np.float64)
+            if c.shape != (int(k), 2) or not np.isfinite(c).all():
+                raise ValueError("cluster_hull: init_mm of shape %r, expected %r finite values" % (c.shape, (int(k), 2)))
+            init = np.ascontiguousarray(np.rint((c - np.array([self.bounds[0], self.bounds[2]])) * 1000.0).astype(np.int64))
+        lo, hi = (0, self.grid[2] - 1) if hist_iz is None else (int(hist_iz[0]), int(hist_iz[1]))
+        if lo < 0 or hi < 0:
+            raise ValueError("cluster_hull: hist_iz %r is negative" % (hist_iz,))
+        st = _lib.VcClusterStats()
+        self._check(self._L.vc_hull_clusters(self._ctx, int(k), int(max_iters), int(min_column), lo, hi,
+                                             None if init is None else _ptr(init, ctypes.c_int64), 0, ctypes.byref(st)),
+                    "vc_hull_clusters")
+        self._cl_k = int(k)
+        return {"survivors": int(st.survivors), "columns": int(st.columns), "weight": int(st.weight),
+                "iterations": int(st.iterations), "converged": bool(st.converged), "q": tuple(int(v) for v in st.q),
+                "clusters_ms": float(st.clusters_ms), "k": int(k), "centres_mm": self.fetch_clusters()["centre_mm"]}
+
+    def clusters_valid(self):
+        """True while the clustering of the last cluster_hull() describes the current hull."""
+        return self._L.vc_fetch_cluster_labels(self._ctx, None) == _lib.VC_OK
+
+    def fetch_cluster_labels(self):
+        """u8 [S] in record order: the figure each survivor belongs to.  Fails once anything has changed the hull."""
+        out = np.empty(self.count, dtype=np.uint8)
+        self._check(self._L.vc_fetch_cluster_labels(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_cluster_labels")
+        return out
+
+    def fetch_clusters(self):
+        """The figures of the last cluster_hull: dict of numpy arrays centre_um int64 [K, 2] (from the grid's (x_min, y_min)
+        corner), centre_mm float64 [K, 2] (world), voxels u64 [K], weight u64 [K], columns u32 [K], lo / hi u32 [K, 3] (inclusive
+        box in (ix, iy, iz); lo = 0xffffffff > hi = 0 for a figure without a voxel)."""
+        K = getattr(self, "_cl_k", 0)
+        raw = (_lib.VcCluster * max(K, 1))()
+        self._check(self._L.vc_fetch_clusters(self._ctx, raw), "vc_fetch_clusters")
+        um = np.array([[int(v) for v in raw[k].centre_um] for k in range(K)], dtype=np.int64).reshape(K, 2)
+        mm = np.array([self.bounds[0], self.bounds[2]]) + um.astype(np.float64) / 1000.0
+        return {"centre_um": um, "centre_mm": mm, "voxels": np.array([raw[k].voxels for k in range(K)], dtype=np.uint64),
+                "weight": np.array([raw[k].weight for k in range(K)], dtype=np.uint64),
+                "columns": np.array([raw[k].columns for k in range(K)], dtype=np.uint32),
+                "lo": np.array([list(raw[k].lo) for k in range(K)], dtype=np.uint32).reshape(K, 3),
+                "hi": np.array([list(raw[k].hi) for k in range(K)], dtype=np.uint32).reshape(K, 3)}
+
+    def fetch_cluster_histograms(self):
+        """u32 [K, 512]: per figure the histogram of its seen records' colours in the band of cluster_hull's hist_iz, bin
+        (r >> 5) << 6 | (g >> 5) << 3 | (b >> 5), with the colours the records had at that call."""
+        out = np.empty((getattr(self, "_cl_k", 0), 512), dtype=np.uint32)
+        self._check(self._L.vc_fetch_cluster_histograms(self._ctx, _ptr(out, ctypes.c_uint32)), "vc_fetch_cluster_histograms")
+        return out
+
+    def fetch_floor_map(self):
+        """u32 [nx, ny]: the survivors above each floor position."""
+        nx, ny, _ = self.grid
+        out = np.empty((nx, ny), dtype=np.uint32)
+        self._check(self._L.vc_fetch_floor_map(self._ctx, _ptr(out, ctypes.c_uint32)), "vc_fetch_floor_map")
+        return out
+
+    def fetch_floor_labels(self):
+        """u8 [nx, ny]: the figure of each floor position, 255 where no voxel stands."""
+        nx, ny, _ = self.grid
+        out = np.empty((nx, ny), dtype=np.uint8)
+        self._check(self._L.vc_fetch_floor_labels(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_floor_labels")
+        return out
+
+    def paint_clusters(self, palette=None):
+        """Recolours the current result in place: every survivor takes its figure's colour, palette u8 [K, 3] RGB (None: the
+        first K of voxcarve.clusters.PALETTE).  fetch() / fetch_records(), render and mesh then show the split; the next carve
+        gives the camera colours again."""
+        from .clusters import PALETTE
+        K = getattr(self, "_cl_k", 0)
+        pal = np.ascontiguousarray(PALETTE[:K] if palette is None else palette, dtype=np.uint8)
+        if pal.shape != (K, 3):
+            raise ValueError("paint_clusters: palette of shape %r, expected %r" % (pal.shape, (K, 3)))
+        if K == 0:
+            pal = np.zeros((1, 3), dtype=np.uint8)               # (the call reports the missing clustering)
+        self._check(self._L.vc_paint_clusters(self._ctx, _ptr(pal, ctypes.c_uint8)), "vc_paint_clusters")
+
     def set_option(self, name, value):
         """Launch-geometry tuning knobs (never change results); see vc_set_option."""
         self._check(self._L.vc_set_option(self._ctx, name.encode(), int(value)), "vc_set_option")
