@@ -34,7 +34,8 @@ typedef enum {
     VC_ERR_HIP = -2,    /* HIP runtime error (message has hipGetErrorString) */
     VC_ERR_RCCL = -3,   /* RCCL missing or failed */
     VC_ERR_OOM = -4,    /* device allocation failed */
-    VC_ERR_NODEV = -5   /* no usable GPU: there is NO CPU fallback */
+    VC_ERR_NODEV = -5,  /* no usable GPU: there is NO CPU fallback */
+    VC_ERR_INTERNAL = -6 /* a bound the library sets for itself was exceeded (vc_hull_geodesic's rounds) */
 } vc_status;
 
 typedef enum {
@@ -66,10 +67,12 @@ typedef enum {
     VC_K_FOOT_TABLE /* k_foot_rows + k_foot_cols */, VC_K_FOOT_CARVE /* k_carve_foot */,
     VC_K_DIST_BOX /* k_dist_box */, VC_K_DIST_Y /* k_dist_y */, VC_K_DIST_ENV /* k_dist_env, along x and along z */,
     VC_K_DIST_RECORDS /* k_dist_records */,
+    VC_K_GEO_SEED /* k_geo_seed_list, k_geo_seed_layers, k_geo_source */, VC_K_GEO_TILES /* k_geo_tiles */,
+    VC_K_GEO_SWEEP /* k_geo_sweep */, VC_K_GEO_ARGMAX /* k_geo_best + k_geo_pick */,
     VC_K_GROW_MARK /* k_grow_mark: the new set's bits and counts */, VC_K_GROW_RANK /* k_grow_apply, k_count_groups, k_cc_wcount, k_cc_woff */,
     VC_K_GROW_MERGE /* k_grow_old + k_grow_new */
 } vc_kernel_kind;
-#define VC_KERNEL_KINDS 21
+#define VC_KERNEL_KINDS 25
 enum {
     VC_WORK_WORD_BOXES = 0,   /* 8-byte word boxes k_brick_words read (listed bricks x 64 words x cameras asked)           */
     VC_WORK_TABLE_ENTRIES,    /* 4-byte table entries the per-voxel level read (VC_MODE_LUT)                                */
@@ -607,6 +610,84 @@ int vc_fetch_floor_map(vc_ctx *ctx, uint32_t *n);                          /* [n
 int vc_fetch_floor_labels(vc_ctx *ctx, uint8_t *labels);                   /* [nx ny] */
 int vc_paint_clusters(vc_ctx *ctx, const uint8_t *rgb /* [K][3] */);
 
+/* ---- geodesic distances through the hull, its extremities, their regions and paths (no reference counterpart) ---------------------
+ * vc_hull_geodesic measures every survivor's distance to a seed set along paths that stay inside the current carve result, as
+ * vc_fetch_occupancy and vc_fetch_records see it, then picks K extremities by repeated farthest-point selection: head, hands,
+ * feet.  The result is left exactly as it is.  The contract, bit for bit (tests/geodesic_np.py restates it).  Integers only.
+ *   1 graph: the nodes are the survivors; an edge joins two survivors that are `connectivity`-neighbours (6, 18 or 26: offsets
+ *     (dx, dy, dz) in {-1, 0, 1}^3 with 1, up to 2 or up to 3 non-zero components, as in vc_hull_components).  With q_x, q_y, q_z =
+ *     item 2 of vc_hull_distance (its refusals included), the edge of offset (dx, dy, dz) has length w = (isqrt(4 s) + 1) div 2 um,
+ *     s = (q_x dx)^2 + (q_y dy)^2 + (q_z dz)^2: the Euclidean length rounded to the nearest um.  The 7 lengths are computed on the
+ *     host; stats.edge_um[m - 1] is that of m = |dx| | |dy| << 1 | |dz| << 2.
+ *   2 sources and keys: the seed set is source 0.  Every voxel has a key (d, label), compared lexicographically: the minimum over
+ *     all paths from any source of (path length in um as u64, that source's label).  Nothing saturates (S w < 2^53).  An unreached
+ *     voxel has (2^64 - 1, 255).  Packed, a key is d << 8 | label, and relaxing key(v) = min(key(v), key(u) + (w << 8)) over the
+ *     edges reaches this fixpoint from any schedule and from any start whose keys are lengths of real paths.
+ *     seed_mode VC_GEO_SEEDS_LIST: seeds = n_seeds linear indices (duplicates allowed; n_seeds = 0 seeds nothing; `layers` is
+ *     ignored).  VC_GEO_SEEDS_IZ_MAX: every survivor of the layers iz_max - layers + 1 .. iz_max, iz_max = the highest layer that
+ *     holds a survivor (world "up" is -z: the floor contact); VC_GEO_SEEDS_IZ_MIN: of iz_min .. iz_min + layers - 1 (the top);
+ *     layers >= 1, `seeds` is ignored.  stats.seeds = the distinct seed voxels.
+ *   3 extremities, for k = 1 .. K (K <= VC_GEO_MAX_K): E_k = the reached voxel with the largest d, a tie the lowest linear index;
+ *     the selection stops when that d is 0 (or nothing is reached).  vc_extremum_t records (d, voxel, record, ix, iy, iz, label =
+ *     k).  E_k then becomes the source of label k (its key is (0, k)) and the relaxation goes on from the keys as they are.  After
+ *     the last one label(v) is the region of v and d(v) the distance to its nearest source.  stats.extremities = how many were found.
+ *   4 paths: next(v) = the lowest-index neighbour u with key(u) + (w << 8) == key(v).  Following next from any reached voxel ends
+ *     at a voxel with d = 0; the path is the list of linear indices, v first.  vc_geodesic_path walks it through the final keys
+ *     (from an extremity that is just that voxel: it is a source).  With VC_GEO_PATHS in flags, the path of every E_k is walked
+ *     when E_k is picked, before it becomes a source -- back to the nearest of the seed set and E_1 .. E_(k-1): the stick figure;
+ *     vc_fetch_extremum_path(k) returns it.
+ *   5 vc_paint_geodesic(mode, palette): every record's RGB becomes palette[label] (mode VC_GEO_PAINT_LABELS; palette u8
+ *     [VC_GEO_MAX_K + 1][3]) or the grey 255 d div max_d (mode VC_GEO_PAINT_DISTANCE, max_d = stats.max_d, grey 0 when it is 0; the
+ *     palette may be NULL); an unreached voxel takes VC_GEO_UNREACHED_R / _G / _B in both.  Index and seen byte stay, as
+ *     vc_paint_clusters recolours in place; the next carve gives the camera colours again.
+ *   6 VC_ERR_ARG (with a message, nothing launched that changes an output) when there is no carve result, steps are in flight,
+ *     the carve ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached,
+ *     flags has a bit other than VC_GEO_PATHS, stats == NULL, connectivity is not 6, 18 or 26, K > VC_GEO_MAX_K, seed_mode is
+ *     unknown, layers = 0 with a layer mode, seeds == NULL with n_seeds > 0, the metric is out of range, or a seed is no survivor
+ *     (the message names the first such seed and its voxel).  S = 0 is no error.  Synchronous.  VC_ERR_INTERNAL when a relaxation
+ *     has not settled after S + 1 launches of its rounds (it cannot: every round but the last lowers a key).
+ *   7 lifetime: the fetch calls, vc_geodesic_path and vc_paint_geodesic fail until the pass has run on the current result and
+ *     again after anything that changes which voxels survive, as vc_fetch_component_labels does; colour passes (vc_color_visible,
+ *     vc_paint_clusters, vc_paint_geodesic) leave them valid.
+ * Two routes relax, with equal bytes: tiles of VC_GEO_TILE_X x _Y x _Z cells laid from the low corner of the survivors' index box,
+ * one workgroup per listed tile and launch (option geodesic_tiles = 1), or sweeps of one lane per record over the whole hull
+ * (geodesic_tiles = 0).  stats: survivors, seeds, reached, unreached, max_d (the largest d of a reached voxel after the last
+ * relaxation), tile_visits (tiles taken by a workgroup, summed over the launches; 0 on the sweep route), tiles (of the box),
+ * extremities, rounds (tile route: launches of a tile list; sweep route: read-backs of the change flag), launches (relaxation
+ * kernels launched), edge_um, q, geodesic_ms = HIP events around the whole call. */
+#define VC_GEO_SEEDS_LIST   0u
+#define VC_GEO_SEEDS_IZ_MAX 1u
+#define VC_GEO_SEEDS_IZ_MIN 2u
+#define VC_GEO_PATHS 1u
+#define VC_GEO_MAX_K 32
+#define VC_GEO_TILE_X 4
+#define VC_GEO_TILE_Y 64
+#define VC_GEO_TILE_Z 4
+#define VC_GEO_PAINT_LABELS   0u
+#define VC_GEO_PAINT_DISTANCE 1u
+#define VC_GEO_UNREACHED_R 255
+#define VC_GEO_UNREACHED_G 0
+#define VC_GEO_UNREACHED_B 255
+typedef struct {
+    uint64_t d;                     /* um, at the moment it was picked */
+    uint32_t voxel, record, ix, iy, iz, label;
+} vc_extremum_t;
+typedef struct {
+    uint64_t survivors, seeds, reached, unreached, max_d, tile_visits, tiles;
+    uint64_t edge_um[7];
+    uint64_t q[3];
+    uint32_t extremities, rounds, launches;
+    float geodesic_ms;              /* HIP events around the whole call */
+} vc_geodesic_stats_t;
+int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, const uint32_t *seeds, uint64_t n_seeds, uint32_t layers,
+                     uint32_t K, uint32_t flags /* 0 or VC_GEO_PATHS */, vc_geodesic_stats_t *stats);
+int vc_fetch_geodesic(vc_ctx *ctx, uint64_t *d);                           /* [S] um, 2^64 - 1 where unreached */
+int vc_fetch_geodesic_labels(vc_ctx *ctx, uint8_t *labels);                /* [S], 255 where unreached */
+int vc_fetch_extrema(vc_ctx *ctx, vc_extremum_t *out);                     /* [stats.extremities] */
+int vc_geodesic_path(vc_ctx *ctx, uint32_t voxel, uint32_t *out, uint32_t capacity, uint32_t *n);
+int vc_fetch_extremum_path(vc_ctx *ctx, uint32_t k /* 1 .. extremities */, uint32_t *out, uint32_t capacity, uint32_t *n);
+int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette /* [VC_GEO_MAX_K + 1][3] */);
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own
@@ -767,6 +848,9 @@ int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *
  *   meshing         surface_order (1)  vc_surface_mesh's bisection tries the cameras that rejected P_off first; 0: camera order
  *   clusters        cluster_floor_records (1)  vc_hull_clusters builds its floor map by one atomic per record, the faster way
  *                                  as measured; 0: from the occupancy words (the same map; scripts/exp_clusters.py times both)
+ *   geodesic        geodesic_tiles (1)  vc_hull_geodesic relaxes by tiles held in LDS, one workgroup per listed tile and launch;
+ *                                  0: by sweeps of one lane per record over the whole hull (the same bytes;
+ *                                  scripts/exp_geodesic.py times both)
  *   experiments     dbg (0)  bit 0: skip the per-voxel level (undecided words count as alive), bit 1: skip the word level
  *                                  too -- WRONG results on purpose, to time the levels apart (scripts/exp_bricks.py); bit 2:
  *                                  no word-level tests, every word of a listed brick goes to the per-voxel level (right results)

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -15,6 +15,10 @@ headlight, assignment.render_views(smooth=True), instead of the six face brightn
 nx, ny, nz per vertex, assignment.surface_mesh(normals=True); --clusters K: the hull split into K figures on the floor plane on
 the device, assignment.configure(clusters=K) -- their floor positions in world mm and their sizes are printed; --cluster-paint
 (with --clusters): every voxel in its figure's colour, in the PLY, the --render images and the --mesh;
+--extremities K: geodesic distances through the hull from its floor contact and its K extremities by farthest-point selection on
+the device, assignment.configure(extremities=K) -- their world positions and distances are printed; --geodesic-paint
+labels|distance (with --extremities): every voxel in its region's colour or a grey ramp of its distance, in the PLY, the --render
+images and the --mesh;
 --help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
@@ -40,6 +44,16 @@ if "--clusters" in sys.argv:
 cluster_paint = "--cluster-paint" in sys.argv
 if cluster_paint:
     sys.argv.remove("--cluster-paint")
+extremities = 0
+if "--extremities" in sys.argv:
+    k = sys.argv.index("--extremities")
+    extremities = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
+geodesic_paint = None
+if "--geodesic-paint" in sys.argv:
+    k = sys.argv.index("--geodesic-paint")
+    geodesic_paint = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
 render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
@@ -74,7 +88,8 @@ masks = fx.golden_masks()
 frames = [np.dstack([m // 2 + 60, m // 3 + 40, 255 - m // 2]).astype(np.uint8) for m in masks]   # any BGR image
 assignment.configure(frame_source=assignment.StaticFrameSource([(frames, masks)]),
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
-                     hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint)
+                     hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
+                     extremities=extremities, geodesic_paint=geodesic_paint if extremities else None)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
 if out != "-":
@@ -92,6 +107,14 @@ if clusters:
     for k in range(clusters):
         print("  figure %d: floor position x %.1f y %.1f mm, %d voxels in %d columns" % (k, cl["figures"]["centre_mm"][k, 0], cl["figures"]["centre_mm"][k, 1],
                                                                                  cl["figures"]["voxels"][k], cl["figures"]["columns"][k]))
+if extremities:
+    ge = assignment.extremities()
+    print("extremities: %d found from %d floor voxels, %d of %d voxels reached, farthest %.1f mm (%d rounds, %.3f ms on the device)" %
+          (ge["extremities"], ge["seeds"], ge["reached"], ge["survivors"], ge["max_d"] / 1000.0, ge["rounds"], ge["geodesic_ms"]))
+    for k in range(ge["extremities"]):
+        w = ge["extrema"]["world_mm"][k]
+        print("  extremity %d: voxel %d at x %.1f y %.1f z %.1f mm, %.1f mm along the hull, path of %d voxels" %
+              (k + 1, ge["extrema"]["voxel"][k], w[0], w[1], w[2], ge["extrema"]["d_mm"][k], len(ge["paths"][k])))
 
 
 def write_image(path, img):

@@ -22,13 +22,19 @@ VC_MORPH_ERODE = 0
 VC_MORPH_OPEN = 1
 VC_GROW_DILATE = 0
 VC_GROW_CLOSE = 1
+VC_GEO_SEEDS_LIST, VC_GEO_SEEDS_IZ_MAX, VC_GEO_SEEDS_IZ_MIN = 0, 1, 2
+VC_GEO_PATHS = 1
+VC_GEO_MAX_K = 32
+VC_GEO_TILE = (4, 64, 4)
+VC_GEO_PAINT_LABELS, VC_GEO_PAINT_DISTANCE = 0, 1
+VC_GEO_UNREACHED_RGB = (255, 0, 255)
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
 VC_MAX_MOG_MODELS = 64
 VC_MOG2_MODEL_TAG = 0x10000
 
 STATUS_NAMES = {0: "VC_OK", -1: "VC_ERR_ARG", -2: "VC_ERR_HIP", -3: "VC_ERR_RCCL",
-                -4: "VC_ERR_OOM", -5: "VC_ERR_NODEV"}
+                -4: "VC_ERR_OOM", -5: "VC_ERR_NODEV", -6: "VC_ERR_INTERNAL"}
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u16p = ctypes.POINTER(ctypes.c_uint16)
@@ -41,10 +47,11 @@ c_f64p = ctypes.POINTER(ctypes.c_double)
 c_ctx = ctypes.c_void_p
 
 
-VC_KERNEL_KINDS, VC_WORK_KINDS = 21, 10
+VC_KERNEL_KINDS, VC_WORK_KINDS = 25, 10
 KERNEL_KINDS = ("k_prep_pack", "k_prep_grid", "k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble", "k_scan_groups",
                 "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups", "foot_table", "k_carve_foot",
-                "k_dist_box", "k_dist_y", "k_dist_env", "k_dist_records", "k_grow_mark", "grow_rank", "grow_merge")
+                "k_dist_box", "k_dist_y", "k_dist_env", "k_dist_records", "geo_seed", "k_geo_tiles", "k_geo_sweep", "geo_argmax",
+                "k_grow_mark", "grow_rank", "grow_merge")
 WORK_KINDS = ("word_boxes", "table_entries", "projections", "emit_projections", "brick_boxes", "foot_projections", "foot_union_skips",
               "foot_words", "dist_cells", "dist_lines")
 
@@ -111,6 +118,18 @@ class VcCluster(ctypes.Structure):
 class VcClusterStats(ctypes.Structure):
     _fields_ = [("survivors", ctypes.c_uint64), ("columns", ctypes.c_uint64), ("weight", ctypes.c_uint64), ("q", ctypes.c_uint64 * 2),
                 ("iterations", ctypes.c_uint32), ("converged", ctypes.c_uint32), ("clusters_ms", ctypes.c_float)]
+
+
+class VcExtremum(ctypes.Structure):
+    _fields_ = [("d", ctypes.c_uint64), ("voxel", ctypes.c_uint32), ("record", ctypes.c_uint32), ("ix", ctypes.c_uint32),
+                ("iy", ctypes.c_uint32), ("iz", ctypes.c_uint32), ("label", ctypes.c_uint32)]
+
+
+class VcGeodesicStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("seeds", ctypes.c_uint64), ("reached", ctypes.c_uint64), ("unreached", ctypes.c_uint64),
+                ("max_d", ctypes.c_uint64), ("tile_visits", ctypes.c_uint64), ("tiles", ctypes.c_uint64), ("edge_um", ctypes.c_uint64 * 7),
+                ("q", ctypes.c_uint64 * 3), ("extremities", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("launches", ctypes.c_uint32),
+                ("geodesic_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -212,6 +231,14 @@ SIGNATURES = {
     "vc_fetch_floor_map": (ctypes.c_int, [c_ctx, c_u32p]),
     "vc_fetch_floor_labels": (ctypes.c_int, [c_ctx, c_u8p]),
     "vc_paint_clusters": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_hull_geodesic": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, c_u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                        ctypes.c_uint32, ctypes.POINTER(VcGeodesicStats)]),
+    "vc_fetch_geodesic": (ctypes.c_int, [c_ctx, c_u64p]),
+    "vc_fetch_geodesic_labels": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_fetch_extrema": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcExtremum)]),
+    "vc_geodesic_path": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, c_u32p]),
+    "vc_fetch_extremum_path": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, c_u32p]),
+    "vc_paint_geodesic": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

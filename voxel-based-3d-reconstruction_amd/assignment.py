@@ -164,8 +164,11 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
              "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
              "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None,
-             "clusters": 0, "cluster_min_column": 1, "cluster_paint": False}
+             "clusters": 0, "cluster_min_column": 1, "cluster_paint": False,
+             "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None}
 _cluster_state = {"centres_mm": None, "references": None, "last": None}
+_geodesic_state = {"last": None}
+GEODESIC_PAINTS = (None, "labels", "distance")
 COLOR_MODES = ("camera", "visible")
 HULLS = ("visual", "photo")
 
@@ -199,7 +202,13 @@ def configure(frame_source=None, **settings):
     floor plane.  The first frame seeds itself and keeps its colour signatures as the references; every later frame starts from
     the previous frame's centres, so label k stays the same figure while the figures keep apart.  clusters() returns the last
     frame's split.  cluster_paint=True paints every voxel in its figure's colour (voxcarve.clusters.PALETTE) before the
-    positions and colours are returned.  0 (the default) runs nothing."""
+    positions and colours are returned.  0 (the default) runs nothing.
+    extremities, geodesic_seeds, geodesic_paint: when extremities = K > 0 (at most 32), every frame ends -- after all hull passes,
+    the colouring and the clusters -- with CarveEngine.hull_geodesic(seeds=geodesic_seeds, extrema=K, paths=True): geodesic
+    distances through the hull from the seed set ("floor", the default, "top", or an array of voxel indices) and the K
+    extremities by farthest-point selection (head, hands, feet).  extremities() returns the last frame's.  geodesic_paint =
+    "labels" | "distance" paints every voxel by its region or its distance (CarveEngine.paint_geodesic) before the positions and
+    colours are returned; None (the default) leaves the colours.  0 (the default) runs nothing."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -219,8 +228,17 @@ def configure(frame_source=None, **settings):
         raise ValueError("clusters %r, expected an integer in 0..16" % (k,))
     if int(settings.get("cluster_min_column", _settings["cluster_min_column"])) < 0:
         raise ValueError("cluster_min_column %r is negative" % (settings["cluster_min_column"],))
+    k = settings.get("extremities", _settings["extremities"])
+    if not isinstance(k, (int, np.integer)) or not 0 <= k <= 32:
+        raise ValueError("extremities %r, expected an integer in 0..32" % (k,))
+    if settings.get("geodesic_paint", _settings["geodesic_paint"]) not in GEODESIC_PAINTS:
+        raise ValueError("geodesic_paint %r, expected one of %s" % (settings["geodesic_paint"], GEODESIC_PAINTS))
+    g = settings.get("geodesic_seeds", _settings["geodesic_seeds"])
+    if isinstance(g, str) and g not in ("floor", "top"):
+        raise ValueError("geodesic_seeds %r, expected \"floor\", \"top\" or an array of voxel indices" % (g,))
     _settings.update(settings)
     _cluster_state.update(centres_mm=None, references=None, last=None)
+    _geodesic_state.update(last=None)
     _source = frame_source
     if _engine is not None:
         _engine.close()
@@ -292,6 +310,8 @@ def set_voxel_positions(width, height, depth):
         _engine.color_visible(slot=0)
     if _settings["clusters"] > 0:
         _cluster_frame()
+    if _settings["extremities"] > 0:
+        _geodesic_frame()
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)
@@ -311,6 +331,26 @@ def _cluster_frame():
     _cluster_state["last"] = out
     if _settings["cluster_paint"]:
         _engine.paint_clusters()
+
+
+def _geodesic_frame():
+    """The frame's geodesic distances and extremities (see configure)."""
+    out = _engine.hull_geodesic(seeds=_settings["geodesic_seeds"], extrema=int(_settings["extremities"]), paths=True)
+    out["extrema"] = _engine.fetch_extrema()
+    out["paths"] = _engine.stick_figure()
+    _geodesic_state["last"] = out
+    if _settings["geodesic_paint"] is not None:
+        _engine.paint_geodesic(_settings["geodesic_paint"])
+
+
+def extremities():
+    """The extremities of the last set_voxel_positions call's hull (configure(extremities=K)): the dict of
+    CarveEngine.hull_geodesic (survivors, seeds, reached, unreached, max_d, extremities, ...) with extrema: the dict of
+    CarveEngine.fetch_extrema (label, voxel, record, d, d_mm, index, world_mm, in the order they were picked) and paths: the list
+    of CarveEngine.stick_figure (world mm, one per extremity)."""
+    if _engine is None or not initialized or _geodesic_state["last"] is None:
+        raise RuntimeError("no extremities: configure(extremities=K) and set_voxel_positions have not run")
+    return _geodesic_state["last"]
 
 
 def clusters():

@@ -46,6 +46,7 @@
 #include "vc_grow.h"
 #include "vc_normals.h"
 #include "vc_clusters.h"
+#include "vc_geodesic.h"
 
 #pragma clang fp contract(off)
 
@@ -411,6 +412,18 @@ struct vc_ctx {
     uint64_t cl_n = 0;               // its survivors
     uint32_t cl_k = 0, cl_ncol = 0;  // its K and nx ny
     int cluster_floor_records = 1;   // the floor map by one atomic per record (measured the faster way); 0: from the occupancy words
+    // vc_hull_geodesic: a key per record, the words' record offsets, the tile lists and their flags (two parities), the counters
+    // (kGeoCnt* u32), the accumulators (kGeoAcc* u64), the seeds as given, a path; what the host keeps of the last call
+    DevBuf<unsigned long long> d_geo_key, d_geo_acc;
+    DevBuf<uint32_t> d_geo_woff, d_geo_flag, d_geo_list, d_geo_cnt, d_geo_seeds, d_geo_path;
+    uint64_t *h_geo = nullptr;       // page-locked read-back of counters and accumulators
+    std::vector<vc_extremum_t> geo_ext;
+    std::vector<std::vector<uint32_t>> geo_paths;   // [extremities] with VC_GEO_PATHS, else empty
+    GeoParams geo_p = {};            // the launch parameters of the last call (vc_geodesic_path walks with them)
+    bool geo_valid = false;          // keys and extremities belong to the vc_hull_geodesic that ran on the current result
+    uint64_t geo_n = 0, geo_max_d = 0;   // its survivors and stats.max_d
+    uint32_t geo_conn = 0;           // its connectivity
+    int geodesic_tiles = 1;          // the relaxation by tiles in LDS; 0: by sweeps over all records (the same bytes)
 
     // comm
     ncclComm_t comm = nullptr;
@@ -1376,6 +1389,9 @@ int vc_destroy(vc_ctx *ctx)
     release(ctx->d_cl_fmap); release(ctx->d_cl_hist); release(ctx->d_cl_box); release(ctx->d_cl_seed); release(ctx->d_cl_flab);
     release(ctx->d_cl_lab); release(ctx->d_cl_acc);
     if (ctx->h_cl) (void)hipHostFree(ctx->h_cl);
+    release(ctx->d_geo_key); release(ctx->d_geo_acc); release(ctx->d_geo_woff); release(ctx->d_geo_flag); release(ctx->d_geo_list);
+    release(ctx->d_geo_cnt); release(ctx->d_geo_seeds); release(ctx->d_geo_path);
+    if (ctx->h_geo) (void)hipHostFree(ctx->h_geo);
     release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
     release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
     if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
@@ -1426,7 +1442,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1439,7 +1455,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->packed = false;
     return VC_OK;
 }
@@ -1483,7 +1499,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1744,7 +1760,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;   // the next carve invalidates what the post-carve passes left
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -2088,7 +2104,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2425,7 +2441,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     const uint64_t S0 = ctx->survivors;
     VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
     VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
@@ -2507,7 +2523,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
     if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
     // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
@@ -2896,13 +2912,13 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
             VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S0, r2, ctx->d_dist_acc.ptr + 2));
         }
         // the result changes from here on
-        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
         VC_TRY(compact_records(ctx, cur, DistKept{ctx->d_dist_rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
                                S0, ctx->h_res + 1));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->d_dist_acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_dist_acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
     VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     dist_harvest(ctx);
@@ -3021,7 +3037,7 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
         VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_added.ptr, 0, (size_t)S1, ctx->stream));
         if (added) {
             // the result changes from here on
-            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
             const dim3 gblock(kGrowBlock), rgrid((uint32_t)((nrange + kGrowBlock - 1) / kGrowBlock));
             VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->d_grow_addw.ptr, w0, nrange);
             // survivors per group of the step, counted again: the packing skips the groups whose count is zero, and an added voxel
@@ -3837,6 +3853,381 @@ int vc_paint_clusters(vc_ctx *ctx, const uint8_t *rgb)
     return VC_OK;
 }
 
+// ---- geodesic distances through the hull, its extremities and paths (vc_geodesic.h; contract in include/voxcarve.h) ----
+// d_geo_acc: [0] the largest d, [1] the reached records, [2] the distinct seeds, [3] the first seed that is no survivor,
+// [4, 6) k_geo_source's answer.  d_geo_cnt: [0, 2) the entries of the two tile lists, [2] the picked record, [3] the sweeps' change
+// flag, [4, 6) k_geo_path's answer.  h_geo: [0, 8) accumulators, [8] two counters (u32), [10] the word scan's total.
+constexpr uint32_t kGeoAccBest = 0, kGeoAccSeeds = 2, kGeoAccBad = 3, kGeoAccOut = 4, kGeoAccTotal = 6;
+constexpr uint32_t kGeoCntPick = 2, kGeoCntFlag = 3, kGeoCntPath = 4, kGeoCntTotal = 6;
+constexpr uint32_t kGeoSweepsPerRound = 8;
+constexpr uint32_t kGeoMaxBlocks = 4096;
+
+// (isqrt(4 s) + 1) div 2: sqrt(s) rounded to the nearest integer (s < 2^42)
+static uint64_t geo_edge_um(uint64_t s)
+{
+    const uint64_t t = 4 * s;
+    uint64_t r = (uint64_t)sqrtl((long double)t);
+    while (r * r > t) --r;
+    while ((r + 1) * (r + 1) <= t) ++r;
+    return (r + 1) / 2;
+}
+
+// Relaxes from the keys as they are until nothing falls.  Tile route: list 0 holds n0 tiles.  Counts into stats.
+static int geo_relax(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint32_t n0, vc_geodesic_stats_t *stats)
+{
+    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->h_geo + 8);
+    const dim3 block(kGeoBlock);
+    uint64_t rounds = 0;
+    if (ctx->geodesic_tiles) {
+        uint32_t par = 0, n = n0;
+        while (n) {
+            if (++rounds > p.S + 1) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_geodesic: the tiles have not settled after %llu rounds", (unsigned long long)(p.S + 1));
+            if (connectivity == 6) VC_DLAUNCH(VC_K_GEO_TILES, k_geo_tiles<6>, dim3(n), block, p, par);
+            else if (connectivity == 18) VC_DLAUNCH(VC_K_GEO_TILES, k_geo_tiles<18>, dim3(n), block, p, par);
+            else VC_DLAUNCH(VC_K_GEO_TILES, k_geo_tiles<26>, dim3(n), block, p, par);
+            VC_HIP(ctx, hipGetLastError());
+            VC_HIP(ctx, hipMemcpyAsync(hc, p.count + (par ^ 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VC_HIP(ctx, hipMemsetAsync(p.count + par, 0, sizeof(uint32_t), ctx->stream));
+            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            stats->tile_visits += n;
+            stats->launches += 1;
+            n = hc[0];
+            if ((uint64_t)n > stats->tiles) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %u tiles listed of %llu", n, (unsigned long long)stats->tiles);
+            par ^= 1u;
+        }
+        // (both lists are empty and every flag is clear: the next relaxation starts at parity 0 again)
+    } else {
+        const dim3 sgrid((uint32_t)((p.S + kGeoBlock - 1) / kGeoBlock));
+        uint32_t *flag = ctx->d_geo_cnt.ptr + kGeoCntFlag;
+        for (;;) {
+            if (++rounds > p.S + 1) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_geodesic: the sweeps have not settled after %llu rounds", (unsigned long long)(p.S + 1));
+            VC_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(uint32_t), ctx->stream));
+            for (uint32_t k = 0; k < kGeoSweepsPerRound; ++k) {
+                if (connectivity == 6) VC_DLAUNCH(VC_K_GEO_SWEEP, k_geo_sweep<6>, sgrid, block, p, flag);
+                else if (connectivity == 18) VC_DLAUNCH(VC_K_GEO_SWEEP, k_geo_sweep<18>, sgrid, block, p, flag);
+                else VC_DLAUNCH(VC_K_GEO_SWEEP, k_geo_sweep<26>, sgrid, block, p, flag);
+            }
+            VC_HIP(ctx, hipGetLastError());
+            VC_HIP(ctx, hipMemcpyAsync(hc, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            stats->launches += kGeoSweepsPerRound;
+            if (!hc[0]) break;
+        }
+    }
+    stats->rounds += (uint32_t)rounds;
+    return VC_OK;
+}
+
+// Walks the path from `voxel` into `out` (host), growing d_geo_path when the path is longer than nx + ny + nz voxels.
+// status = kGeoPath*.
+static int geo_walk(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint32_t voxel, std::vector<uint32_t> &out, uint32_t &status)
+{
+    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->h_geo + 8);
+    uint32_t *res = ctx->d_geo_cnt.ptr + kGeoCntPath;
+    const uint64_t hops = (uint64_t)p.nx + p.ny + p.nz;
+    uint64_t cap = hops < p.S ? hops : p.S;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        VC_TRY(ensure(ctx, ctx->d_geo_path, (size_t)(cap ? cap : 1)));
+        hipLaunchKernelGGL(k_geo_path, dim3(1), dim3(64), 0, ctx->stream, p, connectivity, voxel, ctx->d_geo_path.ptr, (uint32_t)cap, p.S, res);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(hc, res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        status = hc[1];
+        out.clear();
+        if (status != kGeoPathOk) return VC_OK;
+        if ((uint64_t)hc[0] <= cap) break;
+        if (attempt == 1 || (uint64_t)hc[0] > p.S) return fail(ctx, VC_ERR_HIP, "a path of %u voxels through %llu survivors", hc[0], (unsigned long long)p.S);
+        cap = hc[0];
+    }
+    out.resize(hc[0]);
+    if (hc[0]) VC_HIP(ctx, hipMemcpy(out.data(), ctx->d_geo_path.ptr, (size_t)hc[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, const uint32_t *seeds, uint64_t n_seeds, uint32_t layers,
+                     uint32_t K, uint32_t flags, vc_geodesic_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags & ~VC_GEO_PATHS) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: unknown flags %u (VC_GEO_PATHS)", flags);
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: connectivity %u, expected 6, 18 or 26", connectivity);
+    VC_TRY(result_refusals(ctx, "vc_hull_geodesic", "measure", "geodesic distances"));
+    if (K > VC_GEO_MAX_K) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: K = %u not in [0, %d]", K, VC_GEO_MAX_K);
+    if (seed_mode > VC_GEO_SEEDS_IZ_MIN) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed mode %u, expected 0 (list), 1 (iz max) or 2 (iz min)", seed_mode);
+    if (seed_mode == VC_GEO_SEEDS_LIST && n_seeds && !seeds) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu seeds and no list", (unsigned long long)n_seeds);
+    if (seed_mode != VC_GEO_SEEDS_LIST && layers < 1) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: layers = 0, a layer mode seeds at least one");
+    uint64_t q[3];
+    VC_TRY(dist_metric(ctx, "vc_hull_geodesic", q));
+    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu voxels exceed the u32 index", (unsigned long long)n);
+    if (seed_mode != VC_GEO_SEEDS_LIST) n_seeds = 0;
+    if (!S && n_seeds) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed 0 (voxel %u) is no survivor", seeds[0]);
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    ctx->geo_valid = false;
+    ctx->dist_ev_kind.clear();
+    ctx->geo_ext.clear();
+    ctx->geo_paths.clear();
+    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!ctx->h_geo) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_geo), 12 * sizeof(uint64_t), hipHostMallocDefault));
+    uint64_t *h = ctx->h_geo;
+    uint32_t *hc = reinterpret_cast<uint32_t *>(h + 8);
+    memset(h, 0, 12 * sizeof(uint64_t));
+    stats->survivors = S;
+    for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
+    GeoParams p;
+    memset(&p, 0, sizeof p);
+    for (uint32_t m = 1; m < 8; ++m) {
+        const uint64_t s2 = (m & 1 ? q[0] * q[0] : 0) + (m & 2 ? q[1] * q[1] : 0) + (m & 4 ? q[2] * q[2] : 0);
+        stats->edge_um[m - 1] = geo_edge_um(s2);
+        p.w8[m] = (unsigned long long)stats->edge_um[m - 1] << 8;
+    }
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (S) {
+        const uint64_t nwords = (n + 63) / 64;
+        VC_TRY(densify_words(ctx, cur));
+        // survivors before each word, as vc_hull_components counts them
+        const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);
+        VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
+        VC_TRY(ensure(ctx, ctx->d_geo_woff, (size_t)nwords));
+        const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), cblock(kCcBlock);
+        hipLaunchKernelGGL(k_cc_wcount, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, h + 10));          // (the total is not read; h_res holds the box next)
+        hipLaunchKernelGGL(k_cc_woff, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
+                           (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_geo_woff.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        // the survivors' box: the tiles are laid from its low corner, the layer modes seed from its iz range
+        uint32_t *hb = nullptr;
+        VC_TRY(dist_survivor_box(ctx, cur, S, hb));
+        uint64_t tiles = 1;
+        const uint32_t tdim[3] = {kGeoTX, kGeoTY, kGeoTZ};
+        for (int a = 0; a < 3; ++a) {
+            p.lo[a] = hb[a];
+            p.nt[a] = (hb[3 + a] - hb[a]) / tdim[a] + 1;
+            tiles *= p.nt[a];
+        }
+        const uint32_t zlo = hb[2], zhi = hb[5];
+        stats->tiles = tiles;
+        if (tiles > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu tiles exceed the u32 index", (unsigned long long)tiles);
+        p.tiles = (uint32_t)tiles;
+        VC_TRY(ensure(ctx, ctx->d_geo_key, (size_t)S));
+        VC_TRY(ensure(ctx, ctx->d_geo_acc, kGeoAccTotal));
+        VC_TRY(ensure(ctx, ctx->d_geo_cnt, kGeoCntTotal));
+        VC_TRY(ensure(ctx, ctx->d_geo_flag, (size_t)(2 * tiles)));
+        VC_TRY(ensure(ctx, ctx->d_geo_list, (size_t)(2 * tiles)));
+        if (n_seeds) VC_TRY(ensure(ctx, ctx->d_geo_seeds, (size_t)n_seeds));
+        p.records = cur.records.ptr; p.words = cur.words.ptr; p.woff = ctx->d_geo_woff.ptr; p.key = ctx->d_geo_key.ptr;
+        p.S = S; p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
+        p.flag[0] = ctx->d_geo_flag.ptr; p.flag[1] = ctx->d_geo_flag.ptr + tiles;
+        p.list[0] = ctx->d_geo_list.ptr; p.list[1] = ctx->d_geo_list.ptr + tiles;
+        p.count = ctx->d_geo_cnt.ptr;
+        unsigned long long *acc = ctx->d_geo_acc.ptr;
+        uint32_t *pick = ctx->d_geo_cnt.ptr + kGeoCntPick;
+        VC_HIP(ctx, hipMemsetAsync(p.key, 0xff, (size_t)S * sizeof(uint64_t), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_geo_flag.ptr, 0, (size_t)(2 * tiles) * sizeof(uint32_t), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->d_geo_cnt.ptr, 0, kGeoCntTotal * sizeof(uint32_t), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(acc, 0, kGeoAccTotal * sizeof(uint64_t), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBad, 0xff, sizeof(uint64_t), ctx->stream));
+        const dim3 block(kGeoBlock);
+        // item 2: the seed set
+        if (seed_mode == VC_GEO_SEEDS_LIST) {
+            if (n_seeds) {
+                VC_HIP(ctx, hipMemcpyAsync(ctx->d_geo_seeds.ptr, seeds, (size_t)n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+                VC_DLAUNCH(VC_K_GEO_SEED, k_geo_seed_list, dim3((uint32_t)((n_seeds + kGeoBlock - 1) / kGeoBlock)), block, p,
+                           (const uint32_t *)ctx->d_geo_seeds.ptr, n_seeds, n, acc + kGeoAccSeeds);
+            }
+        } else {
+            const uint32_t span = layers - 1 < zhi - zlo ? layers - 1 : zhi - zlo;
+            const uint32_t z0 = seed_mode == VC_GEO_SEEDS_IZ_MAX ? zhi - span : zlo, z1 = seed_mode == VC_GEO_SEEDS_IZ_MAX ? zhi : zlo + span;
+            VC_DLAUNCH(VC_K_GEO_SEED, k_geo_seed_layers, dim3((uint32_t)((S + kGeoBlock - 1) / kGeoBlock)), block, p, z0, z1, acc + kGeoAccSeeds);
+        }
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccSeeds, acc + kGeoAccSeeds, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(hc, p.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (h[kGeoAccBad] != ~0ull) {
+            dist_harvest(ctx);
+            const uint64_t bad = h[kGeoAccBad];
+            return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed %llu (voxel %u) is no survivor", (unsigned long long)bad, bad < n_seeds ? seeds[bad] : 0u);
+        }
+        stats->seeds = h[kGeoAccSeeds];
+        if (stats->seeds > S || (uint64_t)hc[0] > tiles)
+            return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %llu seeds in %u tiles of %llu survivors", (unsigned long long)stats->seeds, hc[0], (unsigned long long)S);
+        VC_TRY(geo_relax(ctx, p, connectivity, hc[0], stats));
+        // item 3: farthest point, two passes; the path back before the point becomes a source
+        const uint64_t gblocks = (S + kGeoBlock - 1) / kGeoBlock;
+        const dim3 ggrid((uint32_t)(gblocks < kGeoMaxBlocks ? gblocks : kGeoMaxBlocks));
+        for (uint32_t k = 1; k <= K && stats->seeds; ++k) {
+            VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBest, 0, 2 * sizeof(uint64_t), ctx->stream));
+            VC_HIP(ctx, hipMemsetAsync(pick, 0xff, sizeof(uint32_t), ctx->stream));
+            VC_DLAUNCH(VC_K_GEO_ARGMAX, k_geo_best, ggrid, block, (const unsigned long long *)p.key, S, acc + kGeoAccBest);
+            VC_DLAUNCH(VC_K_GEO_ARGMAX, k_geo_pick, ggrid, block, (const unsigned long long *)p.key, S, (const unsigned long long *)(acc + kGeoAccBest), pick);
+            VC_HIP(ctx, hipGetLastError());
+            std::vector<uint32_t> way;
+            if (flags & VC_GEO_PATHS) {
+                VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccBest, acc + kGeoAccBest, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+                VC_HIP(ctx, hipMemcpyAsync(hc, pick, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+                VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                if (h[kGeoAccBest] == 0 || (uint64_t)hc[0] >= S) break;
+                uint64_t rec = 0;
+                VC_HIP(ctx, hipMemcpy(&rec, cur.records.ptr + hc[0], sizeof rec, hipMemcpyDeviceToHost));
+                uint32_t status = kGeoPathOk;
+                VC_TRY(geo_walk(ctx, p, connectivity, (uint32_t)rec, way, status));
+                if (status != kGeoPathOk) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: the path of extremity %u ended with status %u", k, status);
+            }
+            VC_DLAUNCH(VC_K_GEO_SEED, k_geo_source, dim3(1), dim3(64), p, (const unsigned long long *)(acc + kGeoAccBest), (const uint32_t *)pick, k,
+                       acc + kGeoAccOut);
+            VC_HIP(ctx, hipGetLastError());
+            VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccOut, acc + kGeoAccOut, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+            VC_HIP(ctx, hipMemcpyAsync(hc, p.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            const uint64_t d = h[kGeoAccOut];
+            const uint32_t rec = (uint32_t)h[kGeoAccOut + 1], voxel = (uint32_t)(h[kGeoAccOut + 1] >> 32);
+            if (d == 0 || rec == 0xffffffffu) break;
+            vc_extremum_t e;
+            memset(&e, 0, sizeof e);
+            e.d = d; e.voxel = voxel; e.record = rec; e.label = k;
+            e.iy = voxel % ctx->ny; e.ix = (voxel / ctx->ny) % ctx->nx; e.iz = voxel / (ctx->ny * ctx->nx);
+            ctx->geo_ext.push_back(e);
+            if (flags & VC_GEO_PATHS) ctx->geo_paths.push_back(std::move(way));
+            VC_TRY(geo_relax(ctx, p, connectivity, hc[0], stats));
+        }
+        VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBest, 0, 2 * sizeof(uint64_t), ctx->stream));
+        VC_DLAUNCH(VC_K_GEO_ARGMAX, k_geo_best, ggrid, block, (const unsigned long long *)p.key, S, acc + kGeoAccBest);
+        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccBest, acc + kGeoAccBest, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    dist_harvest(ctx);
+    VC_HIP(ctx, hipEventElapsedTime(&stats->geodesic_ms, ctx->ev[0], ctx->ev[1]));
+    if (h[kGeoAccBest + 1] > S) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %llu reached of %llu survivors", (unsigned long long)h[kGeoAccBest + 1], (unsigned long long)S);
+    stats->max_d = S ? h[kGeoAccBest] : 0;
+    stats->reached = S ? h[kGeoAccBest + 1] : 0;
+    stats->unreached = S - stats->reached;
+    stats->extremities = (uint32_t)ctx->geo_ext.size();
+    ctx->geo_p = p;
+    ctx->geo_valid = true;
+    ctx->geo_n = S; ctx->geo_max_d = stats->max_d; ctx->geo_conn = connectivity;
+    return VC_OK;
+}
+
+// The refusal the readers of the geodesic outputs share.
+static int geodesic_current(vc_ctx *ctx)
+{
+    if (!ctx->carved || !ctx->geo_valid) return fail(ctx, VC_ERR_ARG, "no geodesic distances: call vc_hull_geodesic on the current carve result");
+    return VC_OK;
+}
+
+// The keys of the last call, on the host.
+static int geo_fetch_keys(vc_ctx *ctx, std::vector<uint64_t> &keys)
+{
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    keys.resize((size_t)ctx->geo_n);
+    if (ctx->geo_n) VC_HIP(ctx, hipMemcpy(keys.data(), ctx->d_geo_key.ptr, (size_t)ctx->geo_n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_geodesic(vc_ctx *ctx, uint64_t *d)
+{
+    if (!ctx) return VC_ERR_ARG;
+    VC_TRY(geodesic_current(ctx));
+    if (!d) return VC_OK;                        // only asked whether the distances are valid
+    std::vector<uint64_t> keys;
+    VC_TRY(geo_fetch_keys(ctx, keys));
+    for (size_t s = 0; s < keys.size(); ++s) d[s] = keys[s] == kGeoNone ? kGeoNone : keys[s] >> 8;
+    return VC_OK;
+}
+
+int vc_fetch_geodesic_labels(vc_ctx *ctx, uint8_t *labels)
+{
+    if (!ctx || !labels) return VC_ERR_ARG;
+    VC_TRY(geodesic_current(ctx));
+    std::vector<uint64_t> keys;
+    VC_TRY(geo_fetch_keys(ctx, keys));
+    for (size_t s = 0; s < keys.size(); ++s) labels[s] = (uint8_t)(keys[s] & 255u);     // (2^64 - 1 gives 255)
+    return VC_OK;
+}
+
+int vc_fetch_extrema(vc_ctx *ctx, vc_extremum_t *out)
+{
+    if (!ctx) return VC_ERR_ARG;
+    VC_TRY(geodesic_current(ctx));
+    if (!ctx->geo_ext.empty()) {
+        if (!out) return VC_ERR_ARG;
+        memcpy(out, ctx->geo_ext.data(), ctx->geo_ext.size() * sizeof(vc_extremum_t));
+    }
+    return VC_OK;
+}
+
+// *n = the path's length; out takes it when capacity holds it.
+static int geo_path_out(vc_ctx *ctx, const char *what, const std::vector<uint32_t> &way, uint32_t *out, uint32_t capacity, uint32_t *n)
+{
+    *n = (uint32_t)way.size();
+    if (way.size() > capacity) return fail(ctx, VC_ERR_ARG, "%s: the path has %zu voxels, the capacity is %u", what, way.size(), capacity);
+    if (!way.empty()) {
+        if (!out) return VC_ERR_ARG;
+        memcpy(out, way.data(), way.size() * sizeof(uint32_t));
+    }
+    return VC_OK;
+}
+
+int vc_geodesic_path(vc_ctx *ctx, uint32_t voxel, uint32_t *out, uint32_t capacity, uint32_t *n)
+{
+    if (!ctx || !n) return VC_ERR_ARG;
+    *n = 0;
+    VC_TRY(geodesic_current(ctx));
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if ((uint64_t)voxel >= ctx->n_voxels() || !ctx->geo_n) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> way;
+    uint32_t status = kGeoPathOk;
+    VC_TRY(geo_walk(ctx, ctx->geo_p, ctx->geo_conn, voxel, way, status));
+    if (status == kGeoPathNoSurvivor) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
+    if (status == kGeoPathUnreached) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is unreached", voxel);
+    if (status != kGeoPathOk) return fail(ctx, VC_ERR_HIP, "vc_geodesic_path: the walk from voxel %u found no next voxel", voxel);
+    return geo_path_out(ctx, "vc_geodesic_path", way, out, capacity, n);
+}
+
+int vc_fetch_extremum_path(vc_ctx *ctx, uint32_t k, uint32_t *out, uint32_t capacity, uint32_t *n)
+{
+    if (!ctx || !n) return VC_ERR_ARG;
+    *n = 0;
+    VC_TRY(geodesic_current(ctx));
+    if (ctx->geo_paths.size() != ctx->geo_ext.size() || (ctx->geo_ext.size() && ctx->geo_paths.empty()))
+        return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: vc_hull_geodesic ran without VC_GEO_PATHS");
+    if (k < 1 || k > ctx->geo_paths.size()) return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: k = %u not in [1, %zu]", k, ctx->geo_paths.size());
+    return geo_path_out(ctx, "vc_fetch_extremum_path", ctx->geo_paths[k - 1], out, capacity, n);
+}
+
+int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (mode > VC_GEO_PAINT_DISTANCE) return fail(ctx, VC_ERR_ARG, "vc_paint_geodesic: mode %u, expected 0 (labels) or 1 (distance)", mode);
+    if (mode == VC_GEO_PAINT_LABELS && !palette) return fail(ctx, VC_ERR_ARG, "vc_paint_geodesic: no palette");
+    VC_TRY(geodesic_current(ctx));
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if (!ctx->geo_n) return VC_OK;
+    StepBuf &cur = ctx->sb[ctx->cur];
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    GeoPalette pal;
+    memset(&pal, 0, sizeof pal);
+    if (palette)
+        for (uint32_t k = 0; k <= kGeoMaxK; ++k) pal.rgb[k] = (uint32_t)palette[3 * k] | ((uint32_t)palette[3 * k + 1] << 8) | ((uint32_t)palette[3 * k + 2] << 16);
+    const uint32_t none = (uint32_t)VC_GEO_UNREACHED_R | ((uint32_t)VC_GEO_UNREACHED_G << 8) | ((uint32_t)VC_GEO_UNREACHED_B << 16);
+    hipLaunchKernelGGL(k_geo_paint, dim3((uint32_t)((ctx->geo_n + kGeoBlock - 1) / kGeoBlock)), dim3(kGeoBlock), 0, ctx->stream, cur.records.ptr,
+                       ctx->geo_n, (const unsigned long long *)ctx->d_geo_key.ptr, mode, (unsigned long long)ctx->geo_max_d, none, pal);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VC_OK;
+}
+
 // ---- the step before the path, its data-parallel part (reference background_subtraction.py:153-168) ----
 static int hsv_tables(vc_ctx *ctx);
 
@@ -4306,6 +4697,7 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
     else if (k == "render_blocks") ctx->render_blocks = value != 0;
     else if (k == "surface_order") ctx->surface_order = value != 0;
     else if (k == "cluster_floor_records") ctx->cluster_floor_records = value != 0;
+    else if (k == "geodesic_tiles") ctx->geodesic_tiles = value != 0;
     else if (k == "cull") ctx->cull = value != 0;
     else if (k == "bricks") ctx->bricks = value != 0;
     else if (k == "dbg") ctx->dbg = value;

@@ -894,6 +894,126 @@ class CarveEngine:
             pal = np.zeros((1, 3), dtype=np.uint8)               # (the call reports the missing clustering)
         self._check(self._L.vc_paint_clusters(self._ctx, _ptr(pal, ctypes.c_uint8)), "vc_paint_clusters")
 
+    # -- geodesic distances through the hull, extremities, regions, paths (vc_hull_geodesic, vc_paint_geodesic) ------------------
+    def hull_geodesic(self, seeds="floor", layers=1, extrema=0, connectivity=26, paths=False):
+        """Measures every survivor's distance to the seed set along paths inside the current carve result, in whole micrometres
+        (contract: include/voxcarve.h), and picks `extrema` extremities by repeated farthest-point selection: each becomes a
+        source of its own, so that fetch_geodesic_labels() cuts the hull into the regions nearest to the seed set (0) and to
+        extremity k (k).  seeds: "floor" (the survivors of the `layers` highest iz layers that hold any: world "up" is -z), "top"
+        (the lowest iz layers) or an array of linear voxel indices, each a survivor.  paths=True also keeps the path of every
+        extremity back to the nearest earlier source (stick_figure).  The result stays as it is.  Returns the stats as a dict:
+        survivors, seeds, reached, unreached, max_d, tile_visits, tiles, edge_um, q, extremities, rounds, launches,
+        geodesic_ms."""
+        lst, n = None, 0
+        if isinstance(seeds, str):
+            if seeds not in ("floor", "top"):
+                raise ValueError("hull_geodesic: seeds %r, expected \"floor\", \"top\" or an array of voxel indices" % (seeds,))
+            mode = _lib.VC_GEO_SEEDS_IZ_MAX if seeds == "floor" else _lib.VC_GEO_SEEDS_IZ_MIN
+        else:
+            v = np.asarray(seeds).reshape(-1)
+            if v.size and (not np.issubdtype(v.dtype, np.integer) or int(v.min()) < 0 or int(v.max()) > 0xffffffff):
+                raise ValueError("hull_geodesic: seeds must be voxel indices in 0 .. 2^32 - 1")
+            lst, n, mode = np.ascontiguousarray(v, dtype=np.uint32), int(v.size), _lib.VC_GEO_SEEDS_LIST
+        if int(layers) < 0 or int(extrema) < 0:
+            raise ValueError("hull_geodesic: layers %r, extrema %r" % (layers, extrema))
+        st = _lib.VcGeodesicStats()
+        self._check(self._L.vc_hull_geodesic(self._ctx, int(connectivity), mode, _ptr(lst, ctypes.c_uint32) if n else None, n, int(layers),
+                                             int(extrema), _lib.VC_GEO_PATHS if paths else 0, ctypes.byref(st)), "vc_hull_geodesic")
+        self._geo_k = int(st.extremities)
+        return {"survivors": int(st.survivors), "seeds": int(st.seeds), "reached": int(st.reached), "unreached": int(st.unreached),
+                "max_d": int(st.max_d), "tile_visits": int(st.tile_visits), "tiles": int(st.tiles),
+                "edge_um": tuple(int(v) for v in st.edge_um), "q": tuple(int(v) for v in st.q), "extremities": int(st.extremities),
+                "rounds": int(st.rounds), "launches": int(st.launches), "geodesic_ms": float(st.geodesic_ms)}
+
+    def geodesic_valid(self):
+        """True while the outputs of the last hull_geodesic() describe the current hull."""
+        return self._L.vc_fetch_geodesic(self._ctx, None) == _lib.VC_OK
+
+    def fetch_geodesic(self):
+        """u64 [S] in record order: the distance to the nearest source in um, 2^64 - 1 where unreached."""
+        out = np.empty(self.count, dtype=np.uint64)
+        self._check(self._L.vc_fetch_geodesic(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_fetch_geodesic")
+        return out
+
+    def fetch_geodesic_mm(self):
+        """float64 [S]: the same in mm, inf where unreached."""
+        d = self.fetch_geodesic()
+        return np.where(d == np.uint64(0xffffffffffffffff), np.inf, d.astype(np.float64) / 1000.0)
+
+    def fetch_geodesic_labels(self):
+        """u8 [S]: the region of every survivor -- 0 nearest to the seed set, k nearest to extremity k, 255 unreached."""
+        out = np.empty(self.count, dtype=np.uint8)
+        self._check(self._L.vc_fetch_geodesic_labels(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_geodesic_labels")
+        return out
+
+    def fetch_extrema(self):
+        """The extremities of the last hull_geodesic, in the order they were picked: dict of numpy arrays label u32 [E] (1 .. E),
+        voxel u32, record u32, d u64 (um, when picked), d_mm float64, index u32 [E, 3] (ix, iy, iz), world_mm float64 [E, 3]."""
+        E = getattr(self, "_geo_k", 0)
+        raw = (_lib.VcExtremum * max(E, 1))()
+        self._check(self._L.vc_fetch_extrema(self._ctx, raw), "vc_fetch_extrema")
+        index = np.array([[raw[k].ix, raw[k].iy, raw[k].iz] for k in range(E)], dtype=np.uint32).reshape(E, 3)
+        d = np.array([raw[k].d for k in range(E)], dtype=np.uint64)
+        return {"label": np.array([raw[k].label for k in range(E)], dtype=np.uint32),
+                "voxel": np.array([raw[k].voxel for k in range(E)], dtype=np.uint32),
+                "record": np.array([raw[k].record for k in range(E)], dtype=np.uint32), "d": d, "d_mm": d.astype(np.float64) / 1000.0,
+                "index": index, "world_mm": self.voxel_world_mm(index[:, 0], index[:, 1], index[:, 2])}
+
+    def voxel_world_mm(self, ix, iy, iz):
+        """float64 [n, 3]: the world position in mm of the voxels (ix, iy, iz)."""
+        xs, ys, zs = self.axes()
+        return np.stack([xs[np.asarray(ix, dtype=np.int64)], ys[np.asarray(iy, dtype=np.int64)], zs[np.asarray(iz, dtype=np.int64)]],
+                        axis=1).reshape(-1, 3)
+
+    def _path(self, call, what, arg):
+        n = ctypes.c_uint32(0)
+        cap = sum(self.grid)
+        for _ in range(2):
+            out = np.empty(max(cap, 1), dtype=np.uint32)
+            rc = call(self._ctx, int(arg), _ptr(out, ctypes.c_uint32), cap, ctypes.byref(n))
+            if rc == _lib.VC_OK or n.value <= cap:
+                break
+            cap = n.value                                         # (the call said how long the path is)
+        self._check(rc, what)
+        return out[:n.value].copy()
+
+    def geodesic_path(self, voxel):
+        """u32 [n]: the linear indices of the shortest path from `voxel` (a reached survivor) to a voxel with d = 0, `voxel` first,
+        through the keys as the last hull_geodesic left them."""
+        return self._path(self._L.vc_geodesic_path, "vc_geodesic_path", voxel)
+
+    def stick_figure(self):
+        """The paths of all extremities of the last hull_geodesic(paths=True), each back to the nearest source that existed when
+        it was picked (the seed set or an earlier extremity): a list of float64 [n, 3] arrays in world mm, extremity first."""
+        nx, ny, _ = self.grid
+        out = []
+        for k in range(1, getattr(self, "_geo_k", 0) + 1):
+            i = self._path(self._L.vc_fetch_extremum_path, "vc_fetch_extremum_path", k).astype(np.int64)
+            out.append(self.voxel_world_mm((i // ny) % nx, i % ny, i // (nx * ny)))
+        if not out:
+            self._check(self._L.vc_fetch_extrema(self._ctx, None), "vc_fetch_extrema")       # (reports a missing pass)
+        return out
+
+    def fetch_extremum_path(self, k):
+        """u32 [n]: the linear indices of stick_figure()'s path k (1-based)."""
+        return self._path(self._L.vc_fetch_extremum_path, "vc_fetch_extremum_path", k)
+
+    def paint_geodesic(self, mode="labels", palette=None):
+        """Recolours the current result in place: mode "labels" gives every survivor its region's colour, palette u8 [>= regions, 3]
+        RGB (None: voxcarve.geodesic.PALETTE); mode "distance" a grey ramp 255 d div max_d.  Unreached voxels take
+        voxcarve.geodesic.UNREACHED_RGB.  fetch() / fetch_records(), render and mesh then show it; the next carve gives the
+        camera colours again."""
+        from .geodesic import MAX_K, PALETTE
+        if mode not in ("labels", "distance"):
+            raise ValueError("paint_geodesic: mode %r, expected \"labels\" or \"distance\"" % (mode,))
+        pal = np.zeros((MAX_K + 1, 3), dtype=np.uint8)
+        src = np.asarray(PALETTE if palette is None else palette, dtype=np.uint8)
+        if src.ndim != 2 or src.shape[1] != 3 or src.shape[0] > MAX_K + 1 or (mode == "labels" and src.shape[0] < getattr(self, "_geo_k", 0) + 1):
+            raise ValueError("paint_geodesic: palette of shape %r, expected [%d .. %d, 3]" % (src.shape, getattr(self, "_geo_k", 0) + 1, MAX_K + 1))
+        pal[:src.shape[0]] = src
+        self._check(self._L.vc_paint_geodesic(self._ctx, _lib.VC_GEO_PAINT_LABELS if mode == "labels" else _lib.VC_GEO_PAINT_DISTANCE,
+                                              _ptr(pal, ctypes.c_uint8)), "vc_paint_geodesic")
+
     def set_option(self, name, value):
         """Launch-geometry tuning knobs (never change results); see vc_set_option."""
         self._check(self._L.vc_set_option(self._ctx, name.encode(), int(value)), "vc_set_option")
