@@ -47,6 +47,7 @@
 #include "vc_normals.h"
 #include "vc_clusters.h"
 #include "vc_geodesic.h"
+#include "vc_owned.h"
 
 #pragma clang fp contract(off)
 
@@ -96,12 +97,6 @@ bool load_rccl(std::string &err)
     return true;
 }
 
-template <typename T>
-struct DevBuf {
-    T *ptr = nullptr;
-    size_t cap = 0;     // elements
-};
-
 // Scratch of one scan_counts: counts and exclusive offsets per group, sums and offsets of the scan blocks
 struct ScanBufs {
     DevBuf<uint32_t> cnt, off;
@@ -113,13 +108,11 @@ struct ScanBufs {
 // the first carve that uses the slot) can be re-derived without another transfer (vc_touch_masks).
 struct Slot {
     DevBuf<uint8_t> bytes;      // [C][H*W] byte masks as uploaded
-    uint8_t *h_bytes = nullptr; // page-locked staging of the same size: uploads are asynchronous
-    size_t h_bytes_cap = 0;
+    Pinned<uint8_t> h_bytes;    // page-locked staging of the same size: uploads are asynchronous
     DevBuf<uint8_t> fbytes[VC_MAX_CAMERAS];   // [H*W*3] BGR image of a camera as uploaded
-    uint8_t *h_fbytes[VC_MAX_CAMERAS] = {nullptr};
+    Pinned<uint8_t> h_fbytes[VC_MAX_CAMERAS];
     DevBuf<uint8_t> bgr_all;    // [C][H*W*3] the images of vc_foreground_to_slot as copied (one staged copy for all cameras)
-    uint8_t *h_bgr_all = nullptr;
-    size_t h_bgr_all_cap = 0;
+    Pinned<uint8_t> h_bgr_all;
     DevBuf<uint32_t> bits;      // [C][mwords]
     DevBuf<uint32_t> frames;    // [C][H*W] one dword per pixel: R | G << 8 | B << 16 | seen << 24 (a record's upper half)
     std::vector<uint8_t> have_frame, frame_dirty;
@@ -133,10 +126,10 @@ struct Slot {
     uint32_t budget_words = 0;  // LDS budget the plan was made for (fixes the dynamic LDS size of the carve launch)
     uint32_t parity = 0;        // which of the header's two foreground-box sets the current frame filled
     bool counts_zero = false;   // the header's sample counts are zero (k_prep_pack just ran)
-    hipEvent_t e_up = nullptr;  // last upload into this slot (owned; upload stream)
+    Event e_up;                 // last upload into this slot (owned; upload stream)
     // The per-frame preparation runs on the UPLOAD stream, right behind the copy it works on and beside whatever the carve
     // stream is doing for the step before; e_prep (owned) marks its end, the carve waits for it.  e_p0: its start when timed.
-    hipEvent_t e_prep = nullptr, e_p0 = nullptr;
+    Event e_prep, e_p0;
     bool prep_pending = false, prep_timed = false;
     // borrowed from the step that used the slot last (recording an event between two kernels costs ~10 us of stream time,
     // so the slot rides on events a step records anyway): behind the last carve kernels that read the slot's bits / grids,
@@ -178,13 +171,13 @@ struct StepBuf {
     bool nz_valid = false;
     DevBuf<uint64_t> blocksum, blockoff;     // blockoff[nscan] = total
     DevBuf<uint64_t> records;
-    uint64_t *h_total = nullptr;             // pinned
-    hipEvent_t e0 = nullptr, e_first = nullptr, e1 = nullptr, e_prep = nullptr;
+    Pinned<uint64_t> h_total;                // one scalar
+    Event e0, e_first, e1, e_prep;
     hipEvent_t e2 = nullptr, e_scan = nullptr, e_emit0 = nullptr;   // borrowed from vc_ctx::step_ev for the step in this set (see there)
     bool emit_ridden = false;                // e_emit0 / e2 are the expansion launch's own begin and end
     // option timing_detail: begin / end events of this step's kernels by kind (owned, made on first use; they ride on the launches),
     // which pair each kind used (the expansion and k_finish_scan may carry the step's own events instead), and which kinds ran
-    hipEvent_t kev[VC_KERNEL_KINDS][2] = {};
+    Event kev[VC_KERNEL_KINDS][2];
     hipEvent_t kused[VC_KERNEL_KINDS][2] = {};
     uint32_t kmask = 0;
     bool prepped = false, prep_timed = false; // this step queued preparation kernels in front of its carve (timed: e_prep .. e0)
@@ -199,7 +192,7 @@ struct StepBuf {
     bool busy = false;
     // compact exchange form of this step: non-zero words as {bits, global index of bit 0} pairs
     DevBuf<uint64_t> ent, mine, counts;      // pairs | {entries, survivors} of this rank | of all ranks
-    uint64_t *h_counts = nullptr;            // pinned, 2 per rank
+    Pinned<uint64_t> h_counts;               // 2 per rank
     bool counts_exchanged = false;           // vc_carve_begin already packed and all-gathered the counts
     int mode = 0, color_cam = -1;            // what the step was run with (vc_expand_entries colours the same way)
     uint32_t slot = 0, slot_gen = 0;         // frame set the step read, and which preparation of it
@@ -211,6 +204,7 @@ constexpr int kDepth = 3;                   // sets of result buffers = carve st
                                             // before it has collected step i - 1, whose expansion ends when the carve of step i does -- the carve
                                             // stream then idles for the host's round trip (20 us of a 155 us step)
 constexpr uint32_t kStepRing = 64;
+constexpr uint64_t kNever = 0;              // the stamp of a product that was never made, or was dropped (vc_ctx::result_gen starts above it)
 constexpr uint32_t kGatherRing = 32;        // steps before a gather's events are recorded again (more than the resident frame sets a stream cycles through)
 struct vc_ctx {
     int device = 0;
@@ -219,7 +213,7 @@ struct vc_ctx {
     hipStream_t stream_up = nullptr; // host-to-device copies of masks and images (overlap the carve in flight)
     hipStream_t stream_x = nullptr;  // a rank of a communicator: packing + collectives of step i, beside the carve of step i + 1 (they waited in
                                      // line on the carve stream: three launches, two collectives and their events, ~60 us per step)
-    hipEvent_t ev_h[2] = {nullptr, nullptr};   // around the last mask upload (h2d_ms)
+    Event ev_h[2];                   // around the last mask upload (h2d_ms)
     bool h2d_pending = false;
     int overlap = 1;                 // (one stream when a communicator is attached: its collectives order everything)
     // How the streams share the chip.  The record expansion fills every wave slot (65 536 waves of streaming work); the carve
@@ -234,14 +228,14 @@ struct vc_ctx {
     int event_scope = 1;             // 1: the events the streams exchange release to the DEVICE only (no system-scope write-back)
     StepBuf sb[kDepth];
     int head = 0, npending = 0, cur = -1;    // next set to issue into, steps in flight, set holding the fetched result
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
     // the compact all-gather's events {start, expansion done, payload arrived}, a RING of them: a frame set's next preparation
     // waits for the expansion that read it (Slot::e_emit), many steps later -- one event re-recorded every step would make it
     // wait for the newest expansion instead and put carve, exchange, expansion and preparation in one line
-    hipEvent_t gx[kGatherRing][3] = {};
+    Event gx[kGatherRing][3];
     // the same for a step's {scan done, step done}: frame sets remember them (Slot::e_carve, e_emit) for their next preparation,
     // kStepRing steps of distance keep that wait on the step that read the frame set and not on a newer one
-    hipEvent_t step_ev[kStepRing][3] = {};      // {scan done, step done, expansion begun}
+    Event step_ev[kStepRing][3];                // {scan done, step done, expansion begun}
     uint32_t step_next = 0;
     uint32_t gx_next = 0;
     std::string err;
@@ -273,7 +267,7 @@ struct vc_ctx {
     DevBuf<uint64_t> d_bm;           // [n_pad / 64] tile-word results of the current step, tile order
     DevBuf<uint32_t> d_blist;        // counters [8] | brick list [nbrick_pad] | column list
     DevBuf<uint64_t> d_wlist;        // undecided words (worst case: every word of the slab)
-    uint32_t *h_lists = nullptr;     // pinned [4]: list lengths of an earlier step, to size launches by
+    Pinned<uint32_t> h_lists;        // [4]: list lengths of an earlier step, to size launches by
     // marching cubes (vc_marching_cubes)
     DevBuf<uint64_t> d_mcbits, d_mcx;
     DevBuf<uint32_t> d_mcwbase, d_mcfaces;
@@ -326,110 +320,136 @@ struct vc_ctx {
     bool sync_call = false;          // inside vc_carve: the step is collected at once, events between its kernels cost nothing that matters
     DevBuf<uint16_t> d_viewmask;
     DevBuf<double> d_scratch;
-    uint64_t *h_total = nullptr;     // pinned scalar (all-gather count)
+    Pinned<uint64_t> h_total;        // one scalar (all-gather count)
     bool viewmask_valid = false, carved = false;
     uint64_t survivors = 0;
+    // The generation of the current result.  Whatever changes the records or the occupancy advances it (result_changed); a product
+    // of a post-carve pass keeps the generation it was made on as its stamp and is valid / current while the two are equal.  A pass
+    // sets its own stamp to kNever when it starts and to result_gen when it has finished, and touches nobody else's.
+    uint64_t result_gen = 1;
+    bool current(uint64_t stamp) const { return stamp == result_gen; }
+    // Scratch the passes over the result share, one after the other on the context's stream.  h_res holds each pass's own read-backs
+    // (photo: [0] removal count of the round, low 32 bits, [1] compaction total; components: [0] components, [1] kept records, [2] misc)
+    ScanBufs d_rscan;                // scans of the compactions (photo, components, morphology) and of word_offsets (components, grow, normals, geodesic)
+    DevBuf<uint64_t> d_rec_spare;    // the records' second buffer: a compaction's or the grow merge's target, then swapped with the step's
+    Pinned<uint64_t> h_res;          // three pinned scalars (pass_begin makes them)
+    DevBuf<uint32_t> d_cc_woff;      // survivors before each word: the components', borrowed by vc_hull_grow for the ranks of the new occupancy
+    std::vector<Event> dist_ev;      // timing_detail: begin / end events of the launches of distance, morphology, grow and geodesic (VC_DLAUNCH), made on first use
+    std::vector<int> dist_ev_kind;   // the kernel kind of each pair the running call has used
+    // What each pass over the result keeps: its buffers, its stamp (see result_gen), its counts, its options.
     // vc_color_visible: depth maps [C][H W] (float32 bits), camera mask per survivor, surface list + counters, large-rectangle queue
-    DevBuf<uint32_t> d_vis_zmap, d_vis_list, d_vis_ctr;
-    DevBuf<uint16_t> d_vis_mask;
-    DevBuf<uint4> d_vis_queue;
-    bool vis_valid = false;          // the maps and masks belong to the current carve result
-    int visible_check = 1;           // splats look at the stored depth before their atomic
-    int visible_big_rect = 64;       // pixels above which a splat rectangle gets a workgroup of its own
-    // vc_photo_carve and vc_hull_components, one after the other on the context's stream: scan scratch, the records' second
-    // buffer (a compaction's target, swapped with the step's), pinned scalars (photo: [0] removal count of the round, low 32 bits,
-    // [1] compaction total; components: [0] components, [1] kept records, [2] misc = kept components | largest << 32)
-    ScanBufs d_rscan;
-    DevBuf<uint64_t> d_rec_spare;
-    uint64_t *h_res = nullptr;
+    struct Visible {
+        DevBuf<uint32_t> zmap, list, ctr;
+        DevBuf<uint16_t> mask;
+        DevBuf<uint4> queue;
+        uint64_t stamp = kNever;         // the maps and masks belong to the current carve result
+        int check = 1;                   // splats look at the stored depth before their atomic
+        int big_rect = 64;               // pixels above which a splat rectangle gets a workgroup of its own
+    } visible;
     // vc_photo_carve: round per input record, removal counter per round
-    DevBuf<uint8_t> d_photo_rounds;
-    DevBuf<uint32_t> d_photo_removed;
-    bool photo_valid = false;        // d_photo_rounds belongs to the photo carve that produced the current result
-    uint64_t photo_n = 0;            // its input survivors
-    // vc_hull_components: survivors before each word, the union-find forest, labels, component numbers of the roots, the root
-    // list, sizes, boxes, keep flags, component entries, [kept components, largest], the select threshold
-    DevBuf<uint32_t> d_cc_woff, d_cc_parent, d_cc_label, d_cc_cid, d_cc_roots, d_cc_size, d_cc_box, d_cc_comp, d_cc_misc;
-    DevBuf<uint8_t> d_cc_kept;
-    DevBuf<uint64_t> d_cc_thr;
-    bool cc_valid = false;           // labels and components belong to the pass that produced the current result
-    uint64_t cc_n = 0;               // its input survivors
-    uint32_t cc_k = 0;               // its components
+    struct Photo {
+        DevBuf<uint8_t> rounds;
+        DevBuf<uint32_t> removed;
+        uint64_t stamp = kNever;         // rounds belongs to the photo carve that produced the current result
+        uint64_t n = 0;                  // its input survivors
+    } photo;
+    // vc_hull_components: the union-find forest, labels, component numbers of the roots, the root list, sizes, boxes, keep flags,
+    // component entries, [kept components, largest], the select threshold (the survivors before each word: vc_ctx::d_cc_woff)
+    struct Components {
+        DevBuf<uint32_t> parent, label, cid, roots, size, box, comp, misc;
+        DevBuf<uint8_t> kept;
+        DevBuf<uint64_t> thr;
+        uint64_t stamp = kNever;         // labels and components belong to the pass that produced the current result
+        uint64_t n = 0;                  // its input survivors
+        uint32_t k = 0;                  // its components
+    } components;
     // vc_hull_distance and vc_hull_morphology: the inside field over the hull's box, the outside field over the grid, the other
     // field of an envelope pass, the envelope stacks, the records' values, the survivors' box, [max, records above r2] x 2
-    DevBuf<uint64_t> d_dist_in, d_dist_out, d_dist_tmp, d_dist_rec;
-    DevBuf<uint32_t> d_dist_st, d_dist_box;
-    DevBuf<unsigned long long> d_dist_acc;
-    bool dist_valid = false;         // the fields belong to the vc_hull_distance that ran on the current result
-    bool dist_outside = false;       // ... with VC_DIST_OUTSIDE
-    uint64_t dist_n = 0;             // its survivors
-    DistBox dist_box = {};           // the box of d_dist_in
-    std::vector<hipEvent_t> dist_ev; // timing_detail: begin / end events of the passes' launches, made on first use
-    std::vector<int> dist_ev_kind;   // the kernel kind of each pair the running call has used
-    uint64_t dist_work[2] = {0, 0};  // VC_WORK_DIST_CELLS, VC_WORK_DIST_LINES since vc_timing_reset
+    struct Distance {
+        DevBuf<uint64_t> in, out, tmp, rec;
+        DevBuf<uint32_t> st, d_box;
+        DevBuf<unsigned long long> acc;
+        uint64_t stamp = kNever;         // the fields belong to the vc_hull_distance that ran on the current result
+        bool outside = false;            // ... with VC_DIST_OUTSIDE
+        uint64_t n = 0;                  // its survivors
+        DistBox box = {};                // the box of `in`
+        uint64_t work[2] = {0, 0};       // VC_WORK_DIST_CELLS, VC_WORK_DIST_LINES since vc_timing_reset
+    } distance;
     // vc_hull_grow: the added bits of the word range its box spans, [added, |Dl|], the `added` byte of each record
-    DevBuf<unsigned long long> d_grow_addw, d_grow_ctr;
-    DevBuf<uint8_t> d_grow_added;
-    bool grow_valid = false;         // d_grow_added belongs to the vc_hull_grow that produced the current result
-    uint64_t grow_n = 0;             // its survivors_after
+    struct Grow {
+        DevBuf<unsigned long long> addw, ctr;
+        DevBuf<uint8_t> added;
+        uint64_t stamp = kNever;         // added belongs to the vc_hull_grow that produced the current result
+        uint64_t n = 0;                  // its survivors_after
+    } grow;
     // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
-    DevBuf<uint32_t> d_rn_idx, d_rn_rgbf;
-    DevBuf<float> d_rn_depth;
-    DevBuf<RenderView> d_rn_views;
-    DevBuf<uint64_t> d_rn_map;
-    DevBuf<unsigned long long> d_rn_ctr;
-    bool rn_valid = false;           // images of a finished render (a new carve leaves them alone)
-    uint32_t rn_views = 0, rn_H = 0, rn_W = 0;
-    int render_blocks = 1;           // vc_render skips empty 8^3 blocks (same results)
+    struct Render {
+        DevBuf<uint32_t> idx, rgbf;
+        DevBuf<float> depth;
+        DevBuf<RenderView> views;
+        DevBuf<uint64_t> map;
+        DevBuf<unsigned long long> ctr;
+        bool valid = false;              // images of a finished render (a new carve leaves them alone)
+        uint64_t stamp = kNever;         // the images of the last render show the current result (valid outlives a carve)
+        uint32_t n_views = 0, H = 0, W = 0;
+        int blocks = 1;                  // vc_render skips empty 8^3 blocks (same results)
+    } render;
     // vc_surface_mesh: edge entries, the mesh of the last call (world vertices, faces, colours, refined flags), counters
-    DevBuf<uint64_t> d_sf_edges;
-    DevBuf<double> d_sf_verts;
-    DevBuf<uint32_t> d_sf_faces;
-    DevBuf<uint8_t> d_sf_rgb, d_sf_refined;
-    DevBuf<unsigned long long> d_sf_ctr;
-    uint64_t sf_verts = 0, sf_faces = 0;
-    bool sf_valid = false;
-    int surface_order = 1;           // vc_surface_mesh tries the cameras that rejected P_off first (same results)
+    struct Surface {
+        DevBuf<uint64_t> edges;
+        DevBuf<double> verts;
+        DevBuf<uint32_t> faces;
+        DevBuf<uint8_t> rgb, refined;
+        DevBuf<unsigned long long> ctr;
+        uint64_t n_verts = 0, n_faces = 0;
+        bool valid = false;
+        uint64_t stamp = kNever;         // the last surface mesh was made on the current result (valid outlives a carve)
+        int order = 1;                   // vc_surface_mesh tries the cameras that rejected P_off first (same results)
+    } surface;
     // vc_hull_normals: survivors before each word, the ball's rows, the records' quadruples, [surface, zero]; the shaded images of
     // vc_shade_render ([V][H W] R | G << 8 | B << 16) and its lights; the quadruples of the last mesh's vertices
-    DevBuf<uint32_t> d_nrm_woff, d_nrm_rows, d_sh_rgb;
-    DevBuf<short4> d_nrm_out, d_nrm_verts;
-    DevBuf<unsigned long long> d_nrm_ctr;
-    DevBuf<double> d_sh_light;
-    bool nrm_valid = false;          // the quadruples belong to the vc_hull_normals that ran on the current result
-    uint64_t nrm_n = 0;              // its survivors
-    bool rn_current = false;         // the images of the last render show the current result (rn_valid outlives a carve)
-    bool sf_current = false;         // the last surface mesh was made on the current result (sf_valid outlives a carve)
-    bool sh_valid = false;           // shaded images of the last render exist
+    struct Normals {
+        DevBuf<uint32_t> woff, rows, sh_rgb;
+        DevBuf<short4> out, verts;
+        DevBuf<unsigned long long> ctr;
+        DevBuf<double> sh_light;
+        uint64_t stamp = kNever;         // the quadruples belong to the vc_hull_normals that ran on the current result
+        uint64_t n = 0;                  // its survivors
+        bool sh_valid = false;           // shaded images of the last render exist
+    } normals;
     // vc_hull_clusters: survivors per column, the columns' and the records' labels, the histograms [K][512], the boxes [K][6],
     // the accumulators (kClAccTotal u64, layout at vc_hull_clusters), the seeds' columns; the clusters as the host assembled them
-    DevBuf<uint32_t> d_cl_fmap, d_cl_hist, d_cl_box, d_cl_seed;
-    DevBuf<uint8_t> d_cl_flab, d_cl_lab;
-    DevBuf<unsigned long long> d_cl_acc;
-    uint64_t *h_cl = nullptr;        // page-locked read-back of the accumulators
-    std::vector<vc_cluster_t> cl_out;
-    bool cl_valid = false;           // labels, clusters and maps belong to the vc_hull_clusters that ran on the current result
-    uint64_t cl_n = 0;               // its survivors
-    uint32_t cl_k = 0, cl_ncol = 0;  // its K and nx ny
-    int cluster_floor_records = 1;   // the floor map by one atomic per record (measured the faster way); 0: from the occupancy words
+    struct Clusters {
+        DevBuf<uint32_t> fmap, hist, box, seed;
+        DevBuf<uint8_t> flab, lab;
+        DevBuf<unsigned long long> acc;
+        Pinned<uint64_t> h;              // page-locked read-back of the accumulators
+        std::vector<vc_cluster_t> out;
+        uint64_t stamp = kNever;         // labels, clusters and maps belong to the vc_hull_clusters that ran on the current result
+        uint64_t n = 0;                  // its survivors
+        uint32_t k = 0, ncol = 0;        // its K and nx ny
+        int floor_records = 1;           // the floor map by one atomic per record (measured the faster way); 0: from the occupancy words
+    } clusters;
     // vc_hull_geodesic: a key per record, the words' record offsets, the tile lists and their flags (two parities), the counters
     // (kGeoCnt* u32), the accumulators (kGeoAcc* u64), the seeds as given, a path; what the host keeps of the last call
-    DevBuf<unsigned long long> d_geo_key, d_geo_acc;
-    DevBuf<uint32_t> d_geo_woff, d_geo_flag, d_geo_list, d_geo_cnt, d_geo_seeds, d_geo_path;
-    uint64_t *h_geo = nullptr;       // page-locked read-back of counters and accumulators
-    std::vector<vc_extremum_t> geo_ext;
-    std::vector<std::vector<uint32_t>> geo_paths;   // [extremities] with VC_GEO_PATHS, else empty
-    GeoParams geo_p = {};            // the launch parameters of the last call (vc_geodesic_path walks with them)
-    bool geo_valid = false;          // keys and extremities belong to the vc_hull_geodesic that ran on the current result
-    uint64_t geo_n = 0, geo_max_d = 0;   // its survivors and stats.max_d
-    uint32_t geo_conn = 0;           // its connectivity
-    int geodesic_tiles = 1;          // the relaxation by tiles in LDS; 0: by sweeps over all records (the same bytes)
+    struct Geodesic {
+        DevBuf<unsigned long long> key, acc;
+        DevBuf<uint32_t> woff, flag, list, cnt, seeds, path;
+        Pinned<uint64_t> h;              // page-locked read-back of counters and accumulators
+        std::vector<vc_extremum_t> ext;
+        std::vector<std::vector<uint32_t>> paths;   // [extremities] with VC_GEO_PATHS, else empty
+        GeoParams p = {};                // the launch parameters of the last call (vc_geodesic_path walks with them)
+        uint64_t stamp = kNever;         // keys and extremities belong to the vc_hull_geodesic that ran on the current result
+        uint64_t n = 0, max_d = 0;       // its survivors and stats.max_d
+        uint32_t conn = 0;               // its connectivity
+        int tiles = 1;                   // the relaxation by tiles in LDS; 0: by sweeps over all records (the same bytes)
+    } geodesic;
 
     // comm
     ncclComm_t comm = nullptr;
     int n_ranks = 1, rank = 0;
     DevBuf<uint64_t> d_counts, d_gathered;
-    uint64_t *h_counts = nullptr;    // pinned, n_ranks
+    Pinned<uint64_t> h_counts;       // n_ranks
     uint64_t gathered_total = 0;
     bool gathered = false;
     // compact exchange: non-zero words of the slab as {bits, global index of bit 0} pairs
@@ -445,7 +465,7 @@ struct vc_ctx {
     DevBuf<uint64_t> d_ent_all[2];
     ScanBufs d_xscan;                        // scan scratch of the pack pass ...
     ScanBufs d_yscan;                        // ... and of the expansion, which may run on the second stream beside a pack
-    uint64_t *h_xtotal = nullptr;            // pinned
+    Pinned<uint64_t> h_xtotal;               // [4]
     uint64_t packed_entries = 0;
     bool packed = false;
     DevBuf<int32_t> d_lut_color;             // colour camera's table over the WHOLE grid (expansion of remote words)
@@ -483,6 +503,35 @@ namespace {
 
 int fail(vc_ctx *ctx, int code, const char *fmt, ...);
 
+// The result is another from here on: every product of a post-carve pass is stale (their stamps no longer equal the generation).
+void result_changed(vc_ctx *ctx) { ++ctx->result_gen; }
+
+// Grid, slab or cameras are others from here on: tables and boxes are to be built again, and there is no carve result.
+void geometry_changed(vc_ctx *ctx)
+{
+    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false;
+    ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
+    result_changed(ctx);
+}
+
+// (Re)creates an owned event with `flags`; page-locked host memory of at least `elems` elements (the "first use" allocations; a
+// larger request replaces the block).
+hipError_t make_event(Event &ev, unsigned flags = hipEventDefault)
+{
+    ev.reset();
+    return hipEventCreateWithFlags(&ev.e, flags);
+}
+
+template <typename T>
+hipError_t ensure_pinned(Pinned<T> &b, size_t elems)
+{
+    if (b.ptr && elems <= b.cap) return hipSuccess;
+    b.reset();
+    hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&b.ptr), elems * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) b.cap = elems;
+    return e;
+}
+
 // timing_detail: the begin / end events launch `kind` of the step being queued is to carry (null otherwise: an ordinary launch)
 void kev_pick(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
 {
@@ -490,7 +539,7 @@ void kev_pick(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
     StepBuf *sb = ctx->kev_sb;
     if (!sb) return;
     for (int i = 0; i < 2; ++i)
-        if (!sb->kev[kind][i] && hipEventCreate(&sb->kev[kind][i]) != hipSuccess) return;
+        if (!sb->kev[kind][i] && make_event(sb->kev[kind][i]) != hipSuccess) return;
     start = sb->kev[kind][0]; stop = sb->kev[kind][1];
     sb->kused[kind][0] = start; sb->kused[kind][1] = stop;
     sb->kmask |= 1u << kind;
@@ -552,17 +601,14 @@ hipError_t make_events(vc_ctx *ctx)
 {
     for (uint32_t r = 0; r < kStepRing; ++r) {
         for (int i = 0; i < 3; ++i) {
-            if (ctx->step_ev[r][i]) { hipError_t e = hipEventDestroy(ctx->step_ev[r][i]); if (e != hipSuccess) return e; ctx->step_ev[r][i] = nullptr; }
             const bool dev = ctx->event_scope >= (i == 1 ? 2 : 1);
-            hipError_t e = hipEventCreateWithFlags(&ctx->step_ev[r][i], dev ? hipEventReleaseToDevice : hipEventDefault);
+            hipError_t e = make_event(ctx->step_ev[r][i], dev ? hipEventReleaseToDevice : hipEventDefault);
             if (e != hipSuccess) return e;
         }
     }
     for (Slot &s : ctx->slots) {
         if (!s.e_prep) continue;
-        hipError_t e = hipEventDestroy(s.e_prep);
-        if (e != hipSuccess) return e;
-        e = hipEventCreateWithFlags(&s.e_prep, ctx->event_scope >= 1 ? hipEventReleaseToDevice : hipEventDefault);
+        hipError_t e = make_event(s.e_prep, ctx->event_scope >= 1 ? hipEventReleaseToDevice : hipEventDefault);
         if (e != hipSuccess) return e;
         s.prep_pending = s.carve_pending = s.emit_pending = false;   // (everything has drained: nothing to wait for)
     }
@@ -606,18 +652,6 @@ int ensure(vc_ctx *ctx, DevBuf<T> &b, size_t elems)
     return VC_OK;
 }
 
-template <typename T>
-void release(DevBuf<T> &b)
-{
-    if (b.ptr) (void)hipFree(b.ptr);
-    b.ptr = nullptr;
-    b.cap = 0;
-}
-
-void release(ScanBufs &b)
-{
-    release(b.cnt); release(b.off); release(b.bsum); release(b.boff);
-}
 
 #define VC_TRY(expr)              \
     do {                          \
@@ -727,7 +761,7 @@ int launch_bricks(vc_ctx *ctx, CarveParams &p, size_t lds, uint32_t ngroups)
         ctx->list_parity = 0;
     }
     if (!ctx->h_lists) {
-        VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_lists), 4 * sizeof(uint32_t), hipHostMallocDefault));
+        VC_HIP(ctx, ensure_pinned(ctx->h_lists, 4));
         ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = ctx->h_lists[3] = 0xffffffffu;       // unknown yet
     }
     bl.counters = ctx->d_blist.ptr;
@@ -818,9 +852,9 @@ int slot_at(vc_ctx *ctx, uint32_t slot, Slot **out)
     Slot &s = ctx->slots[slot];
     if (s.have_frame.size() != ctx->C) { s.have_frame.assign(ctx->C, 0); s.frame_dirty.assign(ctx->C, 0); }
     if (!s.e_up) {
-        VC_HIP(ctx, hipEventCreateWithFlags(&s.e_up, hipEventDisableTiming));
-        VC_HIP(ctx, hipEventCreateWithFlags(&s.e_prep, ctx->event_scope >= 1 ? hipEventReleaseToDevice : hipEventDefault));
-        VC_HIP(ctx, hipEventCreate(&s.e_p0));
+        VC_HIP(ctx, make_event(s.e_up, hipEventDisableTiming));
+        VC_HIP(ctx, make_event(s.e_prep, ctx->event_scope >= 1 ? hipEventReleaseToDevice : hipEventDefault));
+        VC_HIP(ctx, make_event(s.e_p0));
     }
     *out = &s;
     return VC_OK;
@@ -828,21 +862,16 @@ int slot_at(vc_ctx *ctx, uint32_t slot, Slot **out)
 
 void release_slot(Slot &s)
 {
-    release(s.bytes); release(s.bits); release(s.frames); release(s.grid); release(s.coarse); release(s.boxes);
+    s.bytes.reset(); s.bits.reset(); s.frames.reset(); s.grid.reset(); s.coarse.reset(); s.boxes.reset();
     s.has_coarse = false;
-    for (int c = 0; c < VC_MAX_CAMERAS; ++c) {
-        release(s.fbytes[c]);
-        if (s.h_fbytes[c]) { (void)hipHostFree(s.h_fbytes[c]); s.h_fbytes[c] = nullptr; }
-    }
-    if (s.h_bytes) { (void)hipHostFree(s.h_bytes); s.h_bytes = nullptr; s.h_bytes_cap = 0; }
-    release(s.bgr_all); release(s.sat);
+    for (int c = 0; c < VC_MAX_CAMERAS; ++c) { s.fbytes[c].reset(); s.h_fbytes[c].reset(); }
+    s.h_bytes.reset();
+    s.bgr_all.reset(); s.sat.reset();
     s.sat_valid = false;
-    if (s.h_bgr_all) { (void)hipHostFree(s.h_bgr_all); s.h_bgr_all = nullptr; s.h_bgr_all_cap = 0; }
+    s.h_bgr_all.reset();
     s.have_masks = s.bits_valid = s.grids_valid = false;
     s.have_frame.clear(); s.frame_dirty.clear();
 }
-
-uint32_t grid_for(uint64_t n);
 
 // Queues, on the UPLOAD stream (behind the copy of the bytes it reads, beside the carve stream's work for the step before),
 // whatever the slot's derived state is missing: bit masks + record-layout images + grid plan (k_prep_pack, after the optional 2x2
@@ -1069,18 +1098,13 @@ int compact(vc_ctx *ctx, const Sel &sel, uint64_t S, uint64_t *total_host)
     return VC_OK;
 }
 
-// The records of the current result that sel keeps (sel.out: the copy's target) become the result, in record order: compacted
-// into the spare buffer, which is then swapped with the step's.  The caller sets the survivors to the count, which lands in
-// *total_host once the stream has drained.
-template <class Sel>
-int compact_records(vc_ctx *ctx, StepBuf &cur, Sel sel, uint64_t S, uint64_t *total_host)
+// The spare buffer holds the new records of the current result, d_rscan the scan (over ngroups groups) whose total is their number:
+// the buffers are swapped, and the readers of the step's scan (vc_pack_entries / the compact gather report blockoff[nscan] as
+// this rank's survivors) get that total.
+int records_handed_over(vc_ctx *ctx, StepBuf &cur, uint32_t ngroups)
 {
-    VC_TRY(ensure(ctx, ctx->d_rec_spare, cur.records.cap));
-    sel.out = ctx->d_rec_spare.ptr;
-    VC_TRY(compact(ctx, sel, S, total_host));
     std::swap(cur.records, ctx->d_rec_spare);
-    // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
-    const uint32_t nscan = (uint32_t)(((S + kCompactGroup - 1) / kCompactGroup + kScanBlock - 1) / kScanBlock);
+    const uint32_t nscan = (ngroups + kScanBlock - 1) / kScanBlock;
     const uint64_t n_pad = (cur.n + kLutPad - 1) / kLutPad * kLutPad;
     const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
     VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_rscan.boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
@@ -1090,11 +1114,22 @@ int compact_records(vc_ctx *ctx, StepBuf &cur, Sel sel, uint64_t S, uint64_t *to
     return VC_OK;
 }
 
+// The records of the current result that sel keeps (sel.out: the copy's target) become the result, in record order: compacted
+// into the spare buffer, which is then swapped with the step's.  The caller sets the survivors to the count, which lands in
+// *total_host once the stream has drained.
+template <class Sel>
+int compact_records(vc_ctx *ctx, StepBuf &cur, Sel sel, uint64_t S, uint64_t *total_host)
+{
+    VC_TRY(ensure(ctx, ctx->d_rec_spare, cur.records.cap));
+    sel.out = ctx->d_rec_spare.ptr;
+    VC_TRY(compact(ctx, sel, S, total_host));
+    return records_handed_over(ctx, cur, (uint32_t)((S + kCompactGroup - 1) / kCompactGroup));
+}
+
 int ensure_exchange_scratch(vc_ctx *ctx, uint32_t ngroups)
 {
     VC_TRY(ensure(ctx, ctx->d_xscan, ngroups));
-    if (!ctx->h_xtotal)
-        VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_xtotal), 4 * sizeof(uint64_t), hipHostMallocDefault));   // [2], [3]: the two gathers in flight
+    VC_HIP(ctx, ensure_pinned(ctx->h_xtotal, 4));                // [2], [3]: the two gathers in flight
     return VC_OK;
 }
 
@@ -1163,8 +1198,7 @@ int enqueue_counts_exchange(vc_ctx *ctx, StepBuf &cur, hipStream_t st)
 {
     const int G = ctx->n_ranks;
     VC_TRY(ensure(ctx, cur.counts, (size_t)2 * G));
-    if (!cur.h_counts)
-        VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&cur.h_counts), sizeof(uint64_t) * 2 * VC_MAX_RANKS, hipHostMallocDefault));
+    VC_HIP(ctx, ensure_pinned(cur.h_counts, 2 * VC_MAX_RANKS));
     VC_NCCL(ctx, g_rccl.AllGather(cur.mine.ptr, cur.counts.ptr, 2, ncclUint64, ctx->comm, st));
     VC_HIP(ctx, hipMemcpyAsync(cur.h_counts, cur.counts.ptr, sizeof(uint64_t) * 2 * G, hipMemcpyDeviceToHost, st));
     return VC_OK;
@@ -1195,7 +1229,7 @@ static int finish_one(vc_ctx *ctx, uint32_t half)
 {
     if (!ctx->gpend[half]) return VC_OK;
     ctx->gpend[half] = false;
-    hipEvent_t *E = ctx->gx[ctx->gx_idx[half]];
+    Event *E = ctx->gx[ctx->gx_idx[half]];
     VC_HIP(ctx, hipEventSynchronize(E[1]));
     VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.gather_ms, E[0], E[1]));
     VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.exchange_ms, E[0], E[2]));
@@ -1304,20 +1338,18 @@ int vc_create(int device, vc_ctx **out)
     ctx->device = device;
     memset(&ctx->tm, 0, sizeof ctx->tm);
     hipError_t e1 = make_streams(ctx);
-    for (int k = 0; k < 2 && e1 == hipSuccess; ++k) e1 = hipEventCreate(&ctx->ev_h[k]);
+    for (int k = 0; k < 2 && e1 == hipSuccess; ++k) e1 = make_event(ctx->ev_h[k]);
     for (int k = 0; k < kDepth && e1 == hipSuccess; ++k) {
         StepBuf &b = ctx->sb[k];
-        e1 = hipEventCreate(&b.e0);
-        if (e1 == hipSuccess) e1 = hipEventCreate(&b.e_first);
-        if (e1 == hipSuccess) e1 = hipEventCreate(&b.e1);
-            if (e1 == hipSuccess) e1 = hipEventCreate(&b.e_prep);
-        if (e1 == hipSuccess) e1 = hipHostMalloc(reinterpret_cast<void **>(&b.h_total), sizeof(uint64_t), hipHostMallocDefault);
+        for (Event *ev : {&b.e0, &b.e_first, &b.e1, &b.e_prep})
+            if (e1 == hipSuccess) e1 = make_event(*ev);
+        if (e1 == hipSuccess) e1 = ensure_pinned(b.h_total, 1);
     }
-    for (int i = 0; i < 4 && e1 == hipSuccess; ++i) e1 = hipEventCreate(&ctx->ev[i]);
+    for (int i = 0; i < 4 && e1 == hipSuccess; ++i) e1 = make_event(ctx->ev[i]);
     for (uint32_t r = 0; r < kGatherRing && e1 == hipSuccess; ++r)
-        for (int i = 0; i < 3 && e1 == hipSuccess; ++i) e1 = hipEventCreate(&ctx->gx[r][i]);
+        for (int i = 0; i < 3 && e1 == hipSuccess; ++i) e1 = make_event(ctx->gx[r][i]);
     if (e1 == hipSuccess) e1 = make_events(ctx);
-    if (e1 == hipSuccess) e1 = hipHostMalloc(reinterpret_cast<void **>(&ctx->h_total), sizeof(uint64_t), hipHostMallocDefault);
+    if (e1 == hipSuccess) e1 = ensure_pinned(ctx->h_total, 1);
     const char *fg = getenv("VOXCARVE_FORCE_GENERIC");
     ctx->force_generic = fg && fg[0] == '1';
     if (e1 != hipSuccess) {
@@ -1333,77 +1365,12 @@ int vc_destroy(vc_ctx *ctx)
 {
     if (!ctx) return VC_OK;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
-    if (ctx->stream_up) (void)hipStreamSynchronize(ctx->stream_up);
-    if (ctx->stream_x) (void)hipStreamSynchronize(ctx->stream_x);
+    hipStream_t streams[4] = {ctx->stream2, ctx->stream_up, ctx->stream_x, ctx->stream};
+    for (hipStream_t st : streams) if (st) (void)hipStreamSynchronize(st);
     if (ctx->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(ctx->comm);
-    for (Slot &s : ctx->slots) {
-        release_slot(s);
-        if (s.e_up) (void)hipEventDestroy(s.e_up);
-        if (s.e_prep) (void)hipEventDestroy(s.e_prep);
-        if (s.e_p0) (void)hipEventDestroy(s.e_p0);
-    }
-    for (int k = 0; k < 2; ++k) if (ctx->ev_h[k]) (void)hipEventDestroy(ctx->ev_h[k]);
-    for (uint32_t r = 0; r < kGatherRing; ++r)
-        for (int i = 0; i < 3; ++i) if (ctx->gx[r][i]) (void)hipEventDestroy(ctx->gx[r][i]);
-    for (uint32_t r = 0; r < kStepRing; ++r)
-        for (int i = 0; i < 3; ++i) if (ctx->step_ev[r][i]) (void)hipEventDestroy(ctx->step_ev[r][i]);
-    release(ctx->d_axes); release(ctx->d_morph); release(ctx->d_lut); release(ctx->d_bbox); release(ctx->d_lut_tile); release(ctx->d_tbox); release(ctx->d_kbox); release(ctx->d_live); release(ctx->d_wbox); release(ctx->d_bm); release(ctx->d_blist); release(ctx->d_wlist);
-    release(ctx->d_mcbits); release(ctx->d_mcx); release(ctx->d_mcwbase); release(ctx->d_mcfaces); release(ctx->d_mcv); release(ctx->d_mct);
-    release(ctx->d_mcverts);
-    for (StepBuf &b : ctx->sb) {
-        release(b.words); release(b.groupcnt); release(b.groupoff); release(b.groupnz); release(b.blocksum); release(b.blockoff); release(b.records);
-        release(b.ent); release(b.mine); release(b.counts);
-        release(b.busyoff); release(b.busysum); release(b.busyblock); release(b.busylist);
-        if (b.h_counts) (void)hipHostFree(b.h_counts);
-        if (b.h_total) (void)hipHostFree(b.h_total);
-        if (b.e0) (void)hipEventDestroy(b.e0);
-        if (b.e_first) (void)hipEventDestroy(b.e_first);
-        if (b.e1) (void)hipEventDestroy(b.e1);
-        if (b.e_prep) (void)hipEventDestroy(b.e_prep);
-        for (int kk = 0; kk < VC_KERNEL_KINDS; ++kk)
-            for (int i = 0; i < 2; ++i) if (b.kev[kk][i]) (void)hipEventDestroy(b.kev[kk][i]);
-    }
-    release(ctx->d_stats); release(ctx->d_fg); release(ctx->d_hsvdiv); release(ctx->d_foot_axes);
-    for (auto &m : ctx->mog) release(m.state);
-    for (auto &m : ctx->mog2) { release(m.state); release(m.nmodes); }
-    release(ctx->d_cc);
-    release(ctx->d_vis_zmap); release(ctx->d_vis_list); release(ctx->d_vis_ctr); release(ctx->d_vis_mask); release(ctx->d_vis_queue);
-    release(ctx->d_rscan); release(ctx->d_rec_spare);
-    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    release(ctx->d_photo_rounds); release(ctx->d_photo_removed);
-    release(ctx->d_cc_woff); release(ctx->d_cc_parent); release(ctx->d_cc_label); release(ctx->d_cc_cid); release(ctx->d_cc_roots);
-    release(ctx->d_cc_size); release(ctx->d_cc_box); release(ctx->d_cc_comp); release(ctx->d_cc_misc); release(ctx->d_cc_kept);
-    release(ctx->d_cc_thr);
-    release(ctx->d_dist_in); release(ctx->d_dist_out); release(ctx->d_dist_tmp); release(ctx->d_dist_rec); release(ctx->d_dist_st);
-    release(ctx->d_dist_box); release(ctx->d_dist_acc);
-    release(ctx->d_grow_addw); release(ctx->d_grow_ctr); release(ctx->d_grow_added);
-    for (hipEvent_t e : ctx->dist_ev) (void)hipEventDestroy(e);
-    release(ctx->d_rn_idx); release(ctx->d_rn_rgbf); release(ctx->d_rn_depth); release(ctx->d_rn_views); release(ctx->d_rn_map);
-    release(ctx->d_rn_ctr);
-    release(ctx->d_sf_edges); release(ctx->d_sf_verts); release(ctx->d_sf_faces); release(ctx->d_sf_rgb); release(ctx->d_sf_refined);
-    release(ctx->d_sf_ctr);
-    release(ctx->d_nrm_woff); release(ctx->d_nrm_rows); release(ctx->d_sh_rgb); release(ctx->d_nrm_out); release(ctx->d_nrm_verts);
-    release(ctx->d_nrm_ctr); release(ctx->d_sh_light);
-    release(ctx->d_cl_fmap); release(ctx->d_cl_hist); release(ctx->d_cl_box); release(ctx->d_cl_seed); release(ctx->d_cl_flab);
-    release(ctx->d_cl_lab); release(ctx->d_cl_acc);
-    if (ctx->h_cl) (void)hipHostFree(ctx->h_cl);
-    release(ctx->d_geo_key); release(ctx->d_geo_acc); release(ctx->d_geo_woff); release(ctx->d_geo_flag); release(ctx->d_geo_list);
-    release(ctx->d_geo_cnt); release(ctx->d_geo_seeds); release(ctx->d_geo_path);
-    if (ctx->h_geo) (void)hipHostFree(ctx->h_geo);
-    release(ctx->d_viewmask); release(ctx->d_scratch); release(ctx->d_counts); release(ctx->d_gathered);
-    release(ctx->d_ent_all[0]); release(ctx->d_ent_all[1]); release(ctx->d_xscan); release(ctx->d_yscan); release(ctx->d_lut_color);
-    if (ctx->h_xtotal) (void)hipHostFree(ctx->h_xtotal);
-    if (ctx->h_lists) (void)hipHostFree(ctx->h_lists);
-    if (ctx->h_total) (void)hipHostFree(ctx->h_total);
-    if (ctx->h_counts) (void)hipHostFree(ctx->h_counts);
-    for (int i = 0; i < 4; ++i) if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    if (ctx->stream_up) (void)hipStreamDestroy(ctx->stream_up);
-    if (ctx->stream_x) (void)hipStreamDestroy(ctx->stream_x);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    // every stream has drained: the context's members free their buffers, page-locked memory and events; the streams go last
     delete ctx;
+    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
     return VC_OK;
 }
 
@@ -1442,7 +1409,7 @@ int vc_set_grid(vc_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, const double
     ctx->foot_axes_valid = false;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;       // the camera order was sampled on the old geometry
     if (ctx->h_lists) ctx->h_lists[0] = ctx->h_lists[1] = ctx->h_lists[2] = 0xffffffffu;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    geometry_changed(ctx);
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1455,7 +1422,7 @@ int vc_set_slab(vc_ctx *ctx, uint32_t z0, uint32_t z1)
     if (z0 > z1 || z1 > ctx->nz) return fail(ctx, VC_ERR_ARG, "slab [%u,%u) outside [0,%u]", z0, z1, ctx->nz);
     ctx->z0 = z0; ctx->z1 = z1;
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    geometry_changed(ctx);
     ctx->packed = false;
     return VC_OK;
 }
@@ -1499,7 +1466,7 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
         for (Slot &s : ctx->slots) release_slot(s);
     }
     for (Slot &sl : ctx->slots) sl.grids_valid = false;
-    ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    geometry_changed(ctx);
     ctx->lut_color_cam = -1; ctx->packed = false;
     return VC_OK;
 }
@@ -1507,21 +1474,16 @@ int vc_set_cameras(vc_ctx *ctx, uint32_t C, const double *K9, const double *dist
 // Host -> device copy of `bytes` into dst through the page-locked buffer *h_stage (grown on demand), on the upload
 // stream.  The host only ever waits for ITS OWN previous copy out of that staging buffer; the copy itself waits (on
 // the device) for the kernels that still read the bytes it replaces.
-static int stage_upload(vc_ctx *ctx, Slot &s, uint8_t **h_stage, size_t *h_cap, uint8_t *dst, const uint8_t *src, size_t bytes, bool timed)
+static int stage_upload(vc_ctx *ctx, Slot &s, Pinned<uint8_t> &h_stage, uint8_t *dst, const uint8_t *src, size_t bytes, bool timed)
 {
     if (s.up_pending) { VC_HIP(ctx, hipEventSynchronize(s.e_up)); s.up_pending = false; }
-    if (!*h_stage || (h_cap && *h_cap < bytes)) {
-        if (*h_stage) VC_HIP(ctx, hipHostFree(*h_stage));
-        *h_stage = nullptr;
-        VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(h_stage), bytes, hipHostMallocDefault));
-        if (h_cap) *h_cap = bytes;
-    }
-    memcpy(*h_stage, src, bytes);
+    VC_HIP(ctx, ensure_pinned(h_stage, bytes));
+    memcpy(h_stage, src, bytes);
     if (timed) {
         if (ctx->h2d_pending) { (void)hipEventSynchronize(ctx->ev_h[1]); (void)hipEventElapsedTime(&ctx->tm.h2d_ms, ctx->ev_h[0], ctx->ev_h[1]); }
         VC_HIP(ctx, hipEventRecord(ctx->ev_h[0], ctx->stream_up));
     }
-    VC_HIP(ctx, hipMemcpyAsync(dst, *h_stage, bytes, hipMemcpyHostToDevice, ctx->stream_up));
+    VC_HIP(ctx, hipMemcpyAsync(dst, h_stage, bytes, hipMemcpyHostToDevice, ctx->stream_up));
     if (timed) { VC_HIP(ctx, hipEventRecord(ctx->ev_h[1], ctx->stream_up)); ctx->h2d_pending = true; }
     VC_HIP(ctx, hipEventRecord(s.e_up, ctx->stream_up));
     s.up_pending = true;
@@ -1536,7 +1498,7 @@ int vc_upload_masks(vc_ctx *ctx, uint32_t slot, const uint8_t *masks)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t HW = (size_t)ctx->H * ctx->W;
     VC_TRY(ensure(ctx, s->bytes, HW * ctx->C + 64));
-    VC_TRY(stage_upload(ctx, *s, &s->h_bytes, &s->h_bytes_cap, s->bytes.ptr, masks, HW * ctx->C, true));
+    VC_TRY(stage_upload(ctx, *s, s->h_bytes, s->bytes.ptr, masks, HW * ctx->C, true));
     s->have_masks = true;
     s->bits_valid = false;           // the next carve on this slot re-derives bits, grids and camera order on the device
     s->grids_valid = false;
@@ -1591,7 +1553,7 @@ int vc_upload_frame(vc_ctx *ctx, uint32_t slot, uint32_t cam, const uint8_t *bgr
     const size_t npix = (size_t)ctx->H * ctx->W;
     VC_TRY(ensure(ctx, s->frames, npix * ctx->C));
     VC_TRY(ensure(ctx, s->fbytes[cam], npix * 3 + 64));
-    VC_TRY(stage_upload(ctx, *s, &s->h_fbytes[cam], nullptr, s->fbytes[cam].ptr, bgr, npix * 3, false));
+    VC_TRY(stage_upload(ctx, *s, s->h_fbytes[cam], s->fbytes[cam].ptr, bgr, npix * 3, false));
     s->have_frame[cam] = 1;
     s->frame_dirty[cam] = 1;
     s->bits_valid = false;           // the image expansion rides in the same launch as the bit-packing
@@ -1696,7 +1658,7 @@ int vc_upload_lut(vc_ctx *ctx, uint32_t cam, const int32_t *lut)
             VC_TRY(build_brick_boxes(ctx));
         }
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        release(ctx->d_lut);                                     // one table, as after vc_build_lut
+        ctx->d_lut.reset();                                      // one table, as after vc_build_lut
     } else {
         VC_TRY(ensure(ctx, ctx->d_bbox, (size_t)(n_pad / 64) * ctx->C));
         if (n) {
@@ -1760,7 +1722,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     const uint64_t n = ctx->n_voxels();
     const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
     ctx->gathered = false;
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;   // the next carve invalidates what the post-carve passes left
+    result_changed(ctx);   // the next carve invalidates what the post-carve passes left
     ctx->tm.voxels = n;
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
@@ -2007,7 +1969,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
         VC_TRY(ensure(ctx, sb.busyblock, 1));                    // the count of busy groups
     }
     VC_KLAUNCH(VC_K_SCAN_GROUPS, k_scan_groups, dim3(nscan), dim3(kScanThreads), 0, s2, (const uint32_t *)sb.groupcnt.ptr, ngroups, sb.groupoff.ptr,
-               sb.blocksum.ptr, sb.blockoff.ptr, sb.h_total, sb.busy ? sb.busyoff.ptr : (uint32_t *)nullptr, sb.busysum.ptr,
+               sb.blocksum.ptr, sb.blockoff.ptr, sb.h_total.ptr, sb.busy ? sb.busyoff.ptr : (uint32_t *)nullptr, sb.busysum.ptr,
                sb.busyblock.ptr, (uint32_t)ctx->dbg);
     VC_HIP(ctx, hipGetLastError());
     // the two events a pipelined step hands from stream to stream ride on the launches in front of them where those are the
@@ -2024,11 +1986,11 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
         kev_pick(ctx, VC_K_FINISH_SCAN, fs0, fs1);
         if (scan_ridden) { fs1 = sb.e_scan; if (fs0) sb.kused[VC_K_FINISH_SCAN][1] = fs1; }
         hipExtLaunchKernelGGL(k_finish_scan, dim3(grid_for(ngroups)), block, 0, s2, fs0, fs1, 0,
-                              (const uint64_t *)sb.blocksum.ptr, nscan, sb.blockoff.ptr, sb.h_total, (const uint32_t *)sb.busysum.ptr, sb.busyblock.ptr,
+                              (const uint64_t *)sb.blocksum.ptr, nscan, sb.blockoff.ptr, sb.h_total.ptr, (const uint32_t *)sb.busysum.ptr, sb.busyblock.ptr,
                               (const uint32_t *)sb.groupcnt.ptr, ngroups, (const uint32_t *)sb.busyoff.ptr, sb.busylist.ptr, (uint32_t)ctx->dbg);
         VC_HIP(ctx, hipGetLastError());
     } else if (nscan > 1) {
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanThreads), 0, s2, sb.blocksum.ptr, nscan, sb.blockoff.ptr, sb.h_total);
+        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanThreads), 0, s2, sb.blocksum.ptr, nscan, sb.blockoff.ptr, sb.h_total.ptr);
         VC_HIP(ctx, hipGetLastError());
     }
 
@@ -2104,7 +2066,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const int k = (ctx->head - ctx->npending + kDepth) % kDepth;           // oldest pending set
     StepBuf &sb = ctx->sb[k];
-    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+    ctx->carved = false; ctx->viewmask_valid = false; ctx->gathered = false; ctx->packed = false; result_changed(ctx);
     if (sb.n != 0) {
         VC_HIP(ctx, hipEventSynchronize(sb.e2));
         uint64_t total = *sb.h_total;
@@ -2298,9 +2260,60 @@ int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
     return VC_OK;
 }
 
-// The refusals of every pass over the current carve result (colour, photo, components).  `what` names the call in the message,
-// `use` what the call does with the records and `multi` what it cannot do across ranks.
-static int result_refusals(vc_ctx *ctx, const char *what, const char *use, const char *multi)
+// timing_detail: the begin / end events a launch of the distance passes is to carry (null otherwise: an ordinary launch)
+static void dist_events(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
+{
+    start = stop = nullptr;
+    if (!ctx->timing_detail) return;
+    const size_t at = 2 * ctx->dist_ev_kind.size();
+    while (ctx->dist_ev.size() < at + 2) {
+        Event e;
+        if (make_event(e) != hipSuccess) return;
+        ctx->dist_ev.push_back(std::move(e));
+    }
+    start = ctx->dist_ev[at]; stop = ctx->dist_ev[at + 1];
+    ctx->dist_ev_kind.push_back(kind);
+}
+#define VC_DLAUNCH(kind, kernel, grid, block, ...)                                                      \
+    do {                                                                                                \
+        hipEvent_t ks_, ke_;                                                                            \
+        dist_events(ctx, kind, ks_, ke_);                                                               \
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ks_, ke_, 0, __VA_ARGS__);           \
+    } while (0)
+
+// after the call's stream has drained: the launches' times into vc_timing_t
+static void dist_harvest(vc_ctx *ctx)
+{
+    for (size_t k = 0; k < ctx->dist_ev_kind.size(); ++k) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ctx->dist_ev[2 * k], ctx->dist_ev[2 * k + 1]) == hipSuccess) {
+            ctx->tm.kernel_ms_sum[ctx->dist_ev_kind[k]] += ms;
+            ctx->tm.kernel_launches[ctx->dist_ev_kind[k]] += 1;
+        }
+    }
+    ctx->dist_ev_kind.clear();
+}
+
+// ---- the frame around a pass over the current carve result ----
+// Every call that reads or rewrites the current result (colour, photo, components, distance, morphology, grow, render, surface
+// mesh, normals, clusters, geodesic) keeps this order; the frame is the one place where it is written down:
+//   pass_open    the refusals all passes share; hands back the step, S, n and nwords
+//                (then the pass's own argument checks, in the order its contract gives them)
+//   pass_begin   the host's side: device, a gather still in flight, the pinned scalars, no launch events left from a failed call
+//                (then the pass drops its own stamp and sizes its buffers: nothing is queued yet, a failure leaves the result)
+//   pass_start   the device's side: behind the step's record expansion, ev[0], the occupancy words whole
+//                (then the pass's launches, memsets and copies)
+//   pass_end     ev[1], the stream drained, the launches' own events harvested, the elapsed time
+enum PassWords { kWordsLater, kWordsIfRecords, kWordsAlways };   // pass_start: who makes the occupancy words whole, and when
+
+struct Pass {
+    StepBuf *cur = nullptr;          // the step that holds the result
+    uint64_t S = 0, n = 0, nwords = 0;   // its records, the slab's voxels, their occupancy words
+    bool stopped = false;            // ev[1] is recorded (pass_stop: a pass that queues a read-back behind its timed part)
+};
+
+// `what` names the call in the message, `use` what the call does with the records and `multi` what it cannot do across ranks.
+static int pass_open(vc_ctx *ctx, const char *what, const char *use, const char *multi, Pass &pass)
 {
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
     if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "%s: no carve result", what);
@@ -2310,14 +2323,71 @@ static int result_refusals(vc_ctx *ctx, const char *what, const char *use, const
         return fail(ctx, VC_ERR_ARG, "%s: a communicator of %d ranks is attached (multi-GPU %s is not supported)", what, ctx->n_ranks, multi);
     if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
         return fail(ctx, VC_ERR_ARG, "%s: the slab [%u,%u) is narrower than the grid's %u layers", what, ctx->z0, ctx->z1, ctx->nz);
+    pass = Pass{&ctx->sb[ctx->cur], ctx->survivors, ctx->n_voxels(), (ctx->n_voxels() + 63) / 64, false};
+    return VC_OK;
+}
+
+static int pass_begin(vc_ctx *ctx)
+{
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
+    VC_HIP(ctx, ensure_pinned(ctx->h_res, 3));
+    ctx->dist_ev_kind.clear();
+    return VC_OK;
+}
+
+static int pass_start(vc_ctx *ctx, Pass &pass, PassWords words = kWordsIfRecords)
+{
+    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
+    if (pass.S && pass.cur->n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, pass.cur->e2, 0));
+    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (words == kWordsAlways || (words == kWordsIfRecords && pass.S)) VC_TRY(densify_words(ctx, *pass.cur));
+    return VC_OK;
+}
+
+static int pass_stop(vc_ctx *ctx, Pass &pass)
+{
+    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    pass.stopped = true;
+    return VC_OK;
+}
+
+static int pass_end(vc_ctx *ctx, Pass &pass, float *ms)              // ms: where the elapsed time of ev[0] .. ev[1] goes (null: nowhere)
+{
+    if (!pass.stopped) VC_TRY(pass_stop(ctx, pass));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    dist_harvest(ctx);
+    if (ms) VC_HIP(ctx, hipEventElapsedTime(ms, ctx->ev[0], ctx->ev[1]));
+    return VC_OK;
+}
+
+// Survivors before each occupancy word of the step, as vc_components.h counts them, into woff[nwords]: popcounts per 64 words,
+// their scan in ctx->d_rscan, the wave scan inside each group.  The survivor total lands in *total_host once the stream has
+// drained.  kind >= 0: the launches carry that kind's events (VC_DLAUNCH).  Buffers sized by the caller (d_rscan: word_groups).
+static uint32_t word_groups(uint64_t nwords) { return (uint32_t)((nwords + 63) / 64); }   // 64 words per group: <= 2^20 groups
+
+static int word_offsets(vc_ctx *ctx, const StepBuf &cur, uint64_t nwords, DevBuf<uint32_t> &woff, uint64_t *total_host, int kind = -1)
+{
+    const uint32_t wgroups = word_groups(nwords);
+    const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), block(kCcBlock);
+    const uint64_t *words = cur.words.ptr;
+    if (kind >= 0) VC_DLAUNCH(kind, k_cc_wcount, wgrid, block, words, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+    else hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, words, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, total_host));
+    const uint32_t *off = ctx->d_rscan.off.ptr;                  // (read-only to k_cc_woff, as the words are)
+    const uint64_t *boff = ctx->d_rscan.boff.ptr;
+    if (kind >= 0) VC_DLAUNCH(kind, k_cc_woff, wgrid, block, words, nwords, wgroups, off, boff, woff.ptr);
+    else hipLaunchKernelGGL(k_cc_woff, wgrid, block, 0, ctx->stream, words, nwords, wgroups, off, boff, woff.ptr);
+    VC_HIP(ctx, hipGetLastError());
     return VC_OK;
 }
 
 // ---- occlusion-aware colouring of the current carve result (vc_visible.h; contract in include/voxcarve.h) ----
 // The refusals vc_color_visible and vc_photo_carve share; `what` names the call in the message.
-static int visible_refusals(vc_ctx *ctx, const char *what, uint32_t slot, float depth_tolerance)
+static int visible_refusals(vc_ctx *ctx, const char *what, uint32_t slot, float depth_tolerance, Pass &pass)
 {
-    VC_TRY(result_refusals(ctx, what, "colour", "visibility"));
+    VC_TRY(pass_open(ctx, what, "colour", "visibility", pass));
     if (!(depth_tolerance >= 0.0f)) return fail(ctx, VC_ERR_ARG, "%s: depth tolerance %g is negative or NaN", what, (double)depth_tolerance);
     if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks) return fail(ctx, VC_ERR_ARG, "%s: no frame set in slot %u", what, slot);
     const Slot &s = ctx->slots[slot];
@@ -2326,14 +2396,13 @@ static int visible_refusals(vc_ctx *ctx, const char *what, uint32_t slot, float 
     return VC_OK;
 }
 
-// The slot's images in the record layout, and the context's stream behind the step's record expansion.
-static int visible_prepare(vc_ctx *ctx, Slot &s, StepBuf &cur)
+// The slot's images in the record layout, and the context's stream behind their preparation; then the pass starts (the occupancy
+// words are made whole by enqueue_visible, behind the fill of the maps).
+static int visible_start(vc_ctx *ctx, Slot &s, Pass &pass)
 {
     if (!s.bits_valid) VC_TRY(ensure_prepared(ctx, s, false, nullptr));   // images uploaded after the carve: into the record layout
     if (s.prep_pending) { VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.e_prep, 0)); s.prep_pending = false; }
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (ctx->survivors && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    return VC_OK;
+    return pass_start(ctx, pass, kWordsLater);
 }
 
 // Queues items 1-4 of the colouring contract over records[0, S) of the current result on the context's stream: fill of the maps,
@@ -2343,18 +2412,18 @@ static int enqueue_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, uint64_t *records
                            VisParams &p, uint32_t &lb)
 {
     const size_t HW = (size_t)ctx->H * ctx->W, nmap = HW * ctx->C;
-    VC_TRY(ensure(ctx, ctx->d_vis_zmap, nmap));
-    VC_TRY(ensure(ctx, ctx->d_vis_ctr, 4));
-    VC_TRY(ensure(ctx, ctx->d_vis_mask, (size_t)S));
-    VC_TRY(ensure(ctx, ctx->d_vis_list, (size_t)S));
+    VC_TRY(ensure(ctx, ctx->visible.zmap, nmap));
+    VC_TRY(ensure(ctx, ctx->visible.ctr, 4));
+    VC_TRY(ensure(ctx, ctx->visible.mask, (size_t)S));
+    VC_TRY(ensure(ctx, ctx->visible.list, (size_t)S));
     const dim3 block(kVisBlock);
     hipLaunchKernelGGL(k_vis_fill, dim3((uint32_t)((nmap + 4 * kVisBlock - 1) / (4 * kVisBlock))), block, 0, ctx->stream,
-                       ctx->d_vis_zmap.ptr, (uint64_t)nmap, ctx->d_vis_ctr.ptr);
+                       ctx->visible.zmap.ptr, (uint64_t)nmap, ctx->visible.ctr.ptr);
     VC_HIP(ctx, hipGetLastError());
     lb = 0;
     if (!S) return VC_OK;
     VC_TRY(densify_words(ctx, cur));
-    VC_TRY(ensure(ctx, ctx->d_vis_queue, (size_t)kVisQueue));
+    VC_TRY(ensure(ctx, ctx->visible.queue, (size_t)kVisQueue));
     memset(&p, 0, sizeof p);
     p.xs = ctx->d_axes.ptr; p.ys = p.xs + ctx->nx; p.zs = p.ys + ctx->ny;
     p.words = cur.words.ptr;
@@ -2366,13 +2435,13 @@ static int enqueue_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, uint64_t *records
     p.hy = ctx->ny > 1 ? ((b[3] - b[2]) / (double)(ctx->ny - 1)) / 2.0 : 0.0;
     p.hz = ctx->nz > 1 ? ((b[5] - b[4]) / (double)(ctx->nz - 1)) / 2.0 : 0.0;
     p.tol = tol;
-    p.zmap = ctx->d_vis_zmap.ptr;
+    p.zmap = ctx->visible.zmap.ptr;
     p.frames = s.frames.ptr;
-    p.vis = ctx->d_vis_mask.ptr;
-    p.list = ctx->d_vis_list.ptr;
-    p.ctr = ctx->d_vis_ctr.ptr;
-    p.queue = ctx->d_vis_queue.ptr;
-    p.big = (uint32_t)ctx->visible_big_rect;
+    p.vis = ctx->visible.mask.ptr;
+    p.list = ctx->visible.list.ptr;
+    p.ctr = ctx->visible.ctr.ptr;
+    p.queue = ctx->visible.queue.ptr;
+    p.big = (uint32_t)ctx->visible.big_rect;
     memcpy(p.cam, ctx->cams, sizeof(CamDev) * ctx->C);
     p.rounds = rounds;
     const uint64_t sblocks = (S + kVisBlock - 1) / kVisBlock;
@@ -2381,7 +2450,7 @@ static int enqueue_visible(vc_ctx *ctx, Slot &s, StepBuf &cur, uint64_t *records
     else hipLaunchKernelGGL(k_vis_surface<false>, sgrid, block, 0, ctx->stream, p);
     // the surface count stays on the device: the list kernels stride over it with a grid sized for all survivors, capped
     lb = (uint32_t)(sblocks < 2048 ? sblocks : 2048);
-    if (ctx->visible_check) {
+    if (ctx->visible.check) {
         hipLaunchKernelGGL(k_vis_splat<true>, dim3(lb, ctx->C), block, 0, ctx->stream, p);
         hipLaunchKernelGGL(k_vis_splat_big<true>, dim3(1024), block, 0, ctx->stream, p);
     } else {
@@ -2409,18 +2478,16 @@ int vc_color_visible(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t
 {
     if (!ctx) return VC_ERR_ARG;
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_color_visible: flags must be 0 (got %u)", flags);
-    VC_TRY(visible_refusals(ctx, "vc_color_visible", slot, depth_tolerance));
+    Pass pass;
+    VC_TRY(visible_refusals(ctx, "vc_color_visible", slot, depth_tolerance, pass));
     Slot &s = ctx->slots[slot];
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->vis_valid = false;
-    VC_TRY(visible_prepare(ctx, s, cur));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    ctx->visible.stamp = kNever;
+    VC_TRY(visible_start(ctx, s, pass));
     VC_TRY(enqueue_color_visible(ctx, s, cur, depth_tolerance));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.visible_ms, ctx->ev[0], ctx->ev[1]));
-    ctx->vis_valid = true;
+    VC_TRY(pass_end(ctx, pass, &ctx->tm.visible_ms));
+    ctx->visible.stamp = ctx->result_gen;
     return VC_OK;
 }
 
@@ -2432,27 +2499,25 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
     if (!stats) return fail(ctx, VC_ERR_ARG, "vc_photo_carve: stats must not be NULL");
     memset(stats, 0, sizeof *stats);
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_photo_carve: flags must be 0 (got %u)", flags);
-    VC_TRY(visible_refusals(ctx, "vc_photo_carve", slot, depth_tolerance));
+    Pass pass;
+    VC_TRY(visible_refusals(ctx, "vc_photo_carve", slot, depth_tolerance, pass));
     if (min_views < 2 || min_views > ctx->C)
         return fail(ctx, VC_ERR_ARG, "vc_photo_carve: min_views %u not in [2, %u] (2 .. the number of cameras)", min_views, ctx->C);
     if (max_rounds < 1 || max_rounds > kPhotoMaxRounds)
         return fail(ctx, VC_ERR_ARG, "vc_photo_carve: max_rounds %u not in [1, %u]", max_rounds, kPhotoMaxRounds);
     Slot &s = ctx->slots[slot];
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
-    const uint64_t S0 = ctx->survivors;
-    VC_TRY(ensure(ctx, ctx->d_photo_rounds, (size_t)S0));
-    VC_TRY(ensure(ctx, ctx->d_photo_removed, kPhotoMaxRounds + 1));
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    VC_TRY(visible_prepare(ctx, s, cur));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    if (S0) VC_HIP(ctx, hipMemsetAsync(ctx->d_photo_rounds.ptr, 0, (size_t)S0, ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_photo_removed.ptr, 0, (kPhotoMaxRounds + 1) * sizeof(uint32_t), ctx->stream));
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    result_changed(ctx);
+    const uint64_t S0 = pass.S;
+    VC_TRY(ensure(ctx, ctx->photo.rounds, (size_t)S0));
+    VC_TRY(ensure(ctx, ctx->photo.removed, kPhotoMaxRounds + 1));
+    VC_TRY(visible_start(ctx, s, pass));
+    if (S0) VC_HIP(ctx, hipMemsetAsync(ctx->photo.rounds.ptr, 0, (size_t)S0, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->photo.removed.ptr, 0, (kPhotoMaxRounds + 1) * sizeof(uint32_t), ctx->stream));
     PhotoParams q;
     memset(&q, 0, sizeof q);
-    q.rounds = ctx->d_photo_rounds.ptr;
+    q.rounds = ctx->photo.rounds.ptr;
     q.words = cur.words.ptr;
     q.thr = var_threshold;
     q.min_views = min_views;
@@ -2464,7 +2529,7 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
         VisParams p;
         uint32_t lb = 0;
         VC_TRY(enqueue_visible(ctx, s, cur, cur.records.ptr, S0, depth_tolerance, q.rounds, p, lb));
-        q.removed = ctx->d_photo_removed.ptr + r;
+        q.removed = ctx->photo.removed.ptr + r;
         q.round = r;
         if (lb) {
             hipLaunchKernelGGL(k_photo_test, dim3(lb), dim3(kVisBlock), 0, ctx->stream, p, q);
@@ -2484,28 +2549,26 @@ int vc_photo_carve(vc_ctx *ctx, uint32_t slot, float depth_tolerance, uint32_t v
         ctx->survivors = cur.survivors = left;
     }
     VC_TRY(enqueue_color_visible(ctx, s, cur, depth_tolerance));   // the colouring of F: its maps, masks and colours
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VC_TRY(pass_end(ctx, pass, &stats->photo_ms));
     if (left != S0 && ctx->h_res[1] != left)
         return fail(ctx, VC_ERR_HIP, "vc_photo_carve: the compaction kept %llu records, the rounds left %llu",
                     (unsigned long long)ctx->h_res[1], (unsigned long long)left);
-    VC_HIP(ctx, hipEventElapsedTime(&stats->photo_ms, ctx->ev[0], ctx->ev[1]));
     stats->rounds = r;
     stats->converged = converged ? 1u : 0u;
     stats->survivors_before = S0;
     stats->survivors_after = left;
-    ctx->vis_valid = true;
-    ctx->photo_valid = true;
-    ctx->photo_n = S0;
+    ctx->visible.stamp = ctx->result_gen;
+    ctx->photo.stamp = ctx->result_gen;
+    ctx->photo.n = S0;
     return VC_OK;
 }
 
 int vc_fetch_photo_rounds(vc_ctx *ctx, uint8_t *rounds)
 {
     if (!ctx || !rounds) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->photo_valid) return fail(ctx, VC_ERR_ARG, "no photo rounds: call vc_photo_carve on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->photo.stamp)) return fail(ctx, VC_ERR_ARG, "no photo rounds: call vc_photo_carve on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->photo_n) VC_HIP(ctx, hipMemcpy(rounds, ctx->d_photo_rounds.ptr, (size_t)ctx->photo_n, hipMemcpyDeviceToHost));
+    if (ctx->photo.n) VC_HIP(ctx, hipMemcpy(rounds, ctx->photo.rounds.ptr, (size_t)ctx->photo.n, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -2519,47 +2582,37 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_components: flags must be 0 (got %u)", flags);
     if (connectivity != 6 && connectivity != 18 && connectivity != 26)
         return fail(ctx, VC_ERR_ARG, "vc_hull_components: connectivity %u, expected 6, 18 or 26", connectivity);
-    VC_TRY(result_refusals(ctx, "vc_hull_components", "label", "labelling"));
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
-    const uint64_t S0 = ctx->survivors, n = ctx->n_voxels();
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_components", "label", "labelling", pass));
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    result_changed(ctx);
+    const uint64_t S0 = pass.S, nwords = pass.nwords;
+    VC_TRY(pass_start(ctx, pass));
     uint32_t K = 0;
     uint64_t kept_records = 0;
     if (S0) {
-        const uint64_t nwords = (n + 63) / 64;
-        VC_TRY(densify_words(ctx, cur));
-        const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);                  // 64 words per group: <= 2^20 groups
+        const uint32_t wgroups = word_groups(nwords);
         const uint32_t rgroups = (uint32_t)((S0 + kCompactGroup - 1) / kCompactGroup);
         VC_TRY(ensure(ctx, ctx->d_rscan, wgroups > rgroups ? wgroups : rgroups));
         VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
-        VC_TRY(ensure(ctx, ctx->d_cc_parent, (size_t)S0));
-        VC_TRY(ensure(ctx, ctx->d_cc_label, (size_t)S0));
-        VC_TRY(ensure(ctx, ctx->d_cc_cid, (size_t)S0));
-        VC_TRY(ensure(ctx, ctx->d_cc_roots, (size_t)S0));        // (K <= S0: sized before the count is known)
-        VC_TRY(ensure(ctx, ctx->d_cc_misc, 2));
-        VC_TRY(ensure(ctx, ctx->d_cc_thr, 1));
-        // 1 survivors before each word: popcounts per 64 words, their scan, the wave scan inside each group
-        const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), block(kCcBlock);
-        hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, ctx->h_res + 1));
-        hipLaunchKernelGGL(k_cc_woff, wgrid, block, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
-                           (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_cc_woff.ptr);
-        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(ensure(ctx, ctx->components.parent, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->components.label, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->components.cid, (size_t)S0));
+        VC_TRY(ensure(ctx, ctx->components.roots, (size_t)S0));        // (K <= S0: sized before the count is known)
+        VC_TRY(ensure(ctx, ctx->components.misc, 2));
+        VC_TRY(ensure(ctx, ctx->components.thr, 1));
+        // 1 survivors before each word
+        const dim3 block(kCcBlock);
+        VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_cc_woff, ctx->h_res + 1));
         CcParams p;
         memset(&p, 0, sizeof p);
         p.records = cur.records.ptr;
         p.words = cur.words.ptr;
         p.woff = ctx->d_cc_woff.ptr;
-        p.parent = ctx->d_cc_parent.ptr;
-        p.label = ctx->d_cc_label.ptr;
-        p.cid = ctx->d_cc_cid.ptr;
+        p.parent = ctx->components.parent.ptr;
+        p.label = ctx->components.label.ptr;
+        p.cid = ctx->components.cid.ptr;
         p.S = S0;
         p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
         // 2-4 runs, unions across runs, compression
@@ -2571,7 +2624,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
         hipLaunchKernelGGL(k_cc_compress, sgrid, block, 0, ctx->stream, p);
         VC_HIP(ctx, hipGetLastError());
         // 6 the roots, compacted stably: the component list in ascending label
-        VC_TRY(compact(ctx, CcRoots{p.parent, ctx->d_cc_roots.ptr, p.cid}, S0, ctx->h_res + 0));
+        VC_TRY(compact(ctx, CcRoots{p.parent, ctx->components.roots.ptr, p.cid}, S0, ctx->h_res + 0));
         // the one read-back before the end: the number of components sizes their arrays
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const uint64_t K64 = ctx->h_res[0];
@@ -2579,30 +2632,29 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
             return fail(ctx, VC_ERR_HIP, "vc_hull_components: %llu components among %llu survivors", (unsigned long long)K64,
                         (unsigned long long)S0);
         K = (uint32_t)K64;
-        VC_TRY(ensure(ctx, ctx->d_cc_size, K));
-        VC_TRY(ensure(ctx, ctx->d_cc_box, (size_t)K * 6));
-        VC_TRY(ensure(ctx, ctx->d_cc_kept, K));
-        VC_TRY(ensure(ctx, ctx->d_cc_comp, (size_t)K * kCcCompWords));
-        p.roots = ctx->d_cc_roots.ptr;
-        p.size = ctx->d_cc_size.ptr;
-        p.box = ctx->d_cc_box.ptr;
-        p.kept = ctx->d_cc_kept.ptr;
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_cc_misc.ptr, 0, 2 * sizeof(uint32_t), ctx->stream));
+        VC_TRY(ensure(ctx, ctx->components.size, K));
+        VC_TRY(ensure(ctx, ctx->components.box, (size_t)K * 6));
+        VC_TRY(ensure(ctx, ctx->components.kept, K));
+        VC_TRY(ensure(ctx, ctx->components.comp, (size_t)K * kCcCompWords));
+        p.roots = ctx->components.roots.ptr;
+        p.size = ctx->components.size.ptr;
+        p.box = ctx->components.box.ptr;
+        p.kept = ctx->components.kept.ptr;
+        VC_HIP(ctx, hipMemsetAsync(ctx->components.misc.ptr, 0, 2 * sizeof(uint32_t), ctx->stream));
         // 5 sizes and boxes; 7 the keep rule
         hipLaunchKernelGGL(k_cc_clear, dim3((K + kCcBlock - 1) / kCcBlock), block, 0, ctx->stream, p, K);
         hipLaunchKernelGGL(k_cc_stats, dim3(rgroups), block, 0, ctx->stream, p);
         VC_HIP(ctx, hipGetLastError());
         const uint32_t want = keep_largest < K ? keep_largest : 0u;             // keep_largest >= K: no component is out of rank
-        hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(kCcSelectBlock), 0, ctx->stream, (const uint32_t *)p.size, K, want, ctx->d_cc_thr.ptr);
+        hipLaunchKernelGGL(k_cc_select, dim3(1), dim3(kCcSelectBlock), 0, ctx->stream, (const uint32_t *)p.size, K, want, ctx->components.thr.ptr);
         hipLaunchKernelGGL(k_cc_mark, dim3((K + kCcBlock - 1) / kCcBlock), block, 0, ctx->stream, p, K, min_voxels,
-                           (const uint64_t *)ctx->d_cc_thr.ptr, ctx->d_cc_kept.ptr, ctx->d_cc_comp.ptr, ctx->d_cc_misc.ptr);
+                           (const uint64_t *)ctx->components.thr.ptr, ctx->components.kept.ptr, ctx->components.comp.ptr, ctx->components.misc.ptr);
         VC_HIP(ctx, hipGetLastError());
         // 8 the kept records, stably, become the step's (the dropped ones leave the words)
         VC_TRY(compact_records(ctx, cur, CcKept{p.parent, p.cid, p.kept, p.records, p.words, nullptr}, S0, ctx->h_res + 1));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_cc_misc.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->components.misc.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VC_TRY(pass_end(ctx, pass, &stats->components_ms));
     uint32_t kept_components = 0, largest = 0;
     if (S0) {
         kept_records = ctx->h_res[1];
@@ -2613,72 +2665,37 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
             return fail(ctx, VC_ERR_HIP, "vc_hull_components: kept %llu of %llu records, %u of %u components", (unsigned long long)kept_records,
                         (unsigned long long)S0, kept_components, K);
     }
-    VC_HIP(ctx, hipEventElapsedTime(&stats->components_ms, ctx->ev[0], ctx->ev[1]));
     stats->components = K;
     stats->components_kept = kept_components;
     stats->survivors_before = S0;
     stats->survivors_after = kept_records;
     stats->largest = largest;
-    ctx->cc_valid = true;
-    ctx->cc_n = S0;
-    ctx->cc_k = K;
+    ctx->components.stamp = ctx->result_gen;
+    ctx->components.n = S0;
+    ctx->components.k = K;
     return VC_OK;
 }
 
 int vc_fetch_component_labels(vc_ctx *ctx, uint32_t *labels)
 {
     if (!ctx || !labels) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->cc_valid) return fail(ctx, VC_ERR_ARG, "no component labels: call vc_hull_components on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->components.stamp)) return fail(ctx, VC_ERR_ARG, "no component labels: call vc_hull_components on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->cc_n) VC_HIP(ctx, hipMemcpy(labels, ctx->d_cc_label.ptr, (size_t)ctx->cc_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (ctx->components.n) VC_HIP(ctx, hipMemcpy(labels, ctx->components.label.ptr, (size_t)ctx->components.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
 int vc_fetch_components(vc_ctx *ctx, vc_component_t *out)
 {
     if (!ctx || !out) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->cc_valid) return fail(ctx, VC_ERR_ARG, "no components: call vc_hull_components on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->components.stamp)) return fail(ctx, VC_ERR_ARG, "no components: call vc_hull_components on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
     static_assert(sizeof(vc_component_t) == kCcCompWords * sizeof(uint32_t), "vc_component_t is the device's entry");
-    if (ctx->cc_k) VC_HIP(ctx, hipMemcpy(out, ctx->d_cc_comp.ptr, (size_t)ctx->cc_k * sizeof(vc_component_t), hipMemcpyDeviceToHost));
+    if (ctx->components.k) VC_HIP(ctx, hipMemcpy(out, ctx->components.comp.ptr, (size_t)ctx->components.k * sizeof(vc_component_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
 // ---- distance field of the current carve result; erosion and opening (vc_distance.h; contract in include/voxcarve.h) ----
-// timing_detail: the begin / end events a launch of the distance passes is to carry (null otherwise: an ordinary launch)
-static void dist_events(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
-{
-    start = stop = nullptr;
-    if (!ctx->timing_detail) return;
-    const size_t at = 2 * ctx->dist_ev_kind.size();
-    while (ctx->dist_ev.size() < at + 2) {
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) return;
-        ctx->dist_ev.push_back(e);
-    }
-    start = ctx->dist_ev[at]; stop = ctx->dist_ev[at + 1];
-    ctx->dist_ev_kind.push_back(kind);
-}
-#define VC_DLAUNCH(kind, kernel, grid, block, ...)                                                      \
-    do {                                                                                                \
-        hipEvent_t ks_, ke_;                                                                            \
-        dist_events(ctx, kind, ks_, ke_);                                                               \
-        hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ks_, ke_, 0, __VA_ARGS__);           \
-    } while (0)
-
-// after the call's stream has drained: the launches' times into vc_timing_t
-static void dist_harvest(vc_ctx *ctx)
-{
-    for (size_t k = 0; k < ctx->dist_ev_kind.size(); ++k) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ctx->dist_ev[2 * k], ctx->dist_ev[2 * k + 1]) == hipSuccess) {
-            ctx->tm.kernel_ms_sum[ctx->dist_ev_kind[k]] += ms;
-            ctx->tm.kernel_launches[ctx->dist_ev_kind[k]] += 1;
-        }
-    }
-    ctx->dist_ev_kind.clear();
-}
-
 // Item 2 of the contract: the steps in micrometres, q = x, y, z (the first `axes` of them: vc_hull_clusters takes x and y).
 static int dist_metric(vc_ctx *ctx, const char *what, uint64_t *q, int axes = 3)
 {
@@ -2705,8 +2722,8 @@ static int dist_ensure(vc_ctx *ctx, DevBuf<uint64_t> &f, const DistBox &bx)
 {
     const uint64_t cells = dist_cells(bx);
     VC_TRY(ensure(ctx, f, (size_t)cells));
-    VC_TRY(ensure(ctx, ctx->d_dist_tmp, (size_t)cells));
-    VC_TRY(ensure(ctx, ctx->d_dist_st, (size_t)cells));
+    VC_TRY(ensure(ctx, ctx->distance.tmp, (size_t)cells));
+    VC_TRY(ensure(ctx, ctx->distance.st, (size_t)cells));
     return VC_OK;
 }
 
@@ -2721,12 +2738,12 @@ static int dist_transform(vc_ctx *ctx, const DistBox &bx, int mode, const uint64
     else VC_DLAUNCH(VC_K_DIST_Y, k_dist_y<kDistSiteAbove>, ygrid, block, bx, words, f, r2, q[1]);
     // along x: line (lz, ly) from f into the other field; along z: line (lx, ly) back into f
     VC_DLAUNCH(VC_K_DIST_ENV, k_dist_env, dim3((uint32_t)((xlines + kDistBlock - 1) / kDistBlock)), block, (const uint64_t *)f,
-               ctx->d_dist_tmp.ptr, ctx->d_dist_st.ptr, xlines, (uint64_t)bx.b[1], plane, (uint64_t)bx.b[1], bx.b[0], q[0] * q[0]);
+               ctx->distance.tmp.ptr, ctx->distance.st.ptr, xlines, (uint64_t)bx.b[1], plane, (uint64_t)bx.b[1], bx.b[0], q[0] * q[0]);
     VC_DLAUNCH(VC_K_DIST_ENV, k_dist_env, dim3((uint32_t)((plane + kDistBlock - 1) / kDistBlock)), block,
-               (const uint64_t *)ctx->d_dist_tmp.ptr, f, ctx->d_dist_st.ptr, plane, plane, (uint64_t)0, plane, bx.b[2], q[2] * q[2]);
+               (const uint64_t *)ctx->distance.tmp.ptr, f, ctx->distance.st.ptr, plane, plane, (uint64_t)0, plane, bx.b[2], q[2] * q[2]);
     VC_HIP(ctx, hipGetLastError());
-    ctx->dist_work[0] += dist_cells(bx);
-    ctx->dist_work[1] += ylines + xlines + plane;
+    ctx->distance.work[0] += dist_cells(bx);
+    ctx->distance.work[1] += ylines + xlines + plane;
     return VC_OK;
 }
 
@@ -2735,7 +2752,7 @@ static int dist_records(vc_ctx *ctx, StepBuf &cur, const DistBox &bx, const uint
 {
     VC_HIP(ctx, hipMemsetAsync(acc, 0, 2 * sizeof(unsigned long long), ctx->stream));
     VC_DLAUNCH(VC_K_DIST_RECORDS, k_dist_records, dim3((uint32_t)((S + kDistGroup - 1) / kDistGroup)), dim3(kDistBlock), bx,
-               (const uint64_t *)cur.records.ptr, S, f, r2, ctx->d_dist_rec.ptr, acc);
+               (const uint64_t *)cur.records.ptr, S, f, r2, ctx->distance.rec.ptr, acc);
     VC_HIP(ctx, hipGetLastError());
     return VC_OK;
 }
@@ -2744,14 +2761,14 @@ static int dist_records(vc_ctx *ctx, StepBuf &cur, const DistBox &bx, const uint
 // hb = the pinned scalars.
 static int dist_survivor_box(vc_ctx *ctx, StepBuf &cur, uint64_t S, uint32_t *&hb)
 {
-    VC_TRY(ensure(ctx, ctx->d_dist_box, 6));
-    hb = reinterpret_cast<uint32_t *>(ctx->h_res);
+    VC_TRY(ensure(ctx, ctx->distance.d_box, 6));
+    hb = reinterpret_cast<uint32_t *>(ctx->h_res.ptr);
     hb[0] = hb[1] = hb[2] = 0xffffffffu; hb[3] = hb[4] = hb[5] = 0;
-    VC_HIP(ctx, hipMemcpyAsync(ctx->d_dist_box.ptr, hb, 6 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->distance.d_box.ptr, hb, 6 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     VC_DLAUNCH(VC_K_DIST_BOX, k_dist_box, dim3((uint32_t)((S + kDistGroup - 1) / kDistGroup)), dim3(kDistBlock),
-               (const uint64_t *)cur.records.ptr, S, ctx->nx, ctx->ny, ctx->d_dist_box.ptr);
+               (const uint64_t *)cur.records.ptr, S, ctx->nx, ctx->ny, ctx->distance.d_box.ptr);
     VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipMemcpyAsync(hb, ctx->d_dist_box.ptr, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(hb, ctx->distance.d_box.ptr, 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
     for (int a = 0; a < 3; ++a)
@@ -2764,8 +2781,8 @@ static int dist_survivor_box(vc_ctx *ctx, StepBuf &cur, uint64_t S, uint32_t *&h
 // clipped to the grid; the transform into d_dist_in over that box; the records' values and acc[0..1] against r2.
 static int dist_inside(vc_ctx *ctx, StepBuf &cur, uint32_t flags, uint64_t S, uint64_t r2, const uint64_t q[3], DistBox &bx)
 {
-    VC_TRY(ensure(ctx, ctx->d_dist_acc, 4));
-    VC_TRY(ensure(ctx, ctx->d_dist_rec, (size_t)S));
+    VC_TRY(ensure(ctx, ctx->distance.acc, 4));
+    VC_TRY(ensure(ctx, ctx->distance.rec, (size_t)S));
     uint32_t *hb = nullptr;
     VC_TRY(dist_survivor_box(ctx, cur, S, hb));
     const uint32_t n[3] = {ctx->nx, ctx->ny, ctx->nz};
@@ -2777,9 +2794,9 @@ static int dist_inside(vc_ctx *ctx, StepBuf &cur, uint32_t flags, uint64_t S, ui
         bx.o[a] = lo;
         bx.b[a] = (uint32_t)(hi - lo + 1);
     }
-    VC_TRY(dist_ensure(ctx, ctx->d_dist_in, bx));
-    VC_TRY(dist_transform(ctx, bx, kDistSiteOff, cur.words.ptr, ctx->d_dist_in.ptr, 0, q));
-    VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S, r2, ctx->d_dist_acc.ptr));
+    VC_TRY(dist_ensure(ctx, ctx->distance.in, bx));
+    VC_TRY(dist_transform(ctx, bx, kDistSiteOff, cur.words.ptr, ctx->distance.in.ptr, 0, q));
+    VC_TRY(dist_records(ctx, cur, bx, ctx->distance.in.ptr, S, r2, ctx->distance.acc.ptr));
     return VC_OK;
 }
 
@@ -2790,60 +2807,52 @@ int vc_hull_distance(vc_ctx *ctx, uint32_t flags, vc_distance_stats_t *stats)
     memset(stats, 0, sizeof *stats);
     if (flags & ~(VC_DIST_BORDER_OFF | VC_DIST_OUTSIDE))
         return fail(ctx, VC_ERR_ARG, "vc_hull_distance: unknown flags %u (VC_DIST_BORDER_OFF | VC_DIST_OUTSIDE)", flags);
-    VC_TRY(result_refusals(ctx, "vc_hull_distance", "measure", "distance transforms"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_distance", "measure", "distance transforms", pass));
     uint64_t q[3];
     VC_TRY(dist_metric(ctx, "vc_hull_distance", q));
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->dist_valid = false;
-    ctx->dist_ev_kind.clear();
-    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    ctx->distance.stamp = kNever;
+    const uint64_t S = pass.S, n = pass.n;
     const bool outside = (flags & VC_DIST_OUTSIDE) != 0;
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(pass_start(ctx, pass));
     DistBox bx;
     memset(&bx, 0, sizeof bx);
     if (S) {
-        VC_TRY(densify_words(ctx, cur));
         VC_TRY(dist_inside(ctx, cur, flags, S, 0, q, bx));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_dist_acc.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->distance.acc.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     if (outside) {
         if (S) {
             DistBox all;
             memset(&all, 0, sizeof all);
             all.nx = all.b[0] = ctx->nx; all.ny = all.b[1] = ctx->ny; all.nz = all.b[2] = ctx->nz;
-            VC_TRY(dist_ensure(ctx, ctx->d_dist_out, all));
-            VC_TRY(dist_transform(ctx, all, kDistSiteOn, cur.words.ptr, ctx->d_dist_out.ptr, 0, q));
+            VC_TRY(dist_ensure(ctx, ctx->distance.out, all));
+            VC_TRY(dist_transform(ctx, all, kDistSiteOn, cur.words.ptr, ctx->distance.out.ptr, 0, q));
         } else {
-            VC_TRY(ensure(ctx, ctx->d_dist_out, (size_t)n));
-            VC_HIP(ctx, hipMemsetAsync(ctx->d_dist_out.ptr, 0xff, (size_t)n * sizeof(uint64_t), ctx->stream));
+            VC_TRY(ensure(ctx, ctx->distance.out, (size_t)n));
+            VC_HIP(ctx, hipMemsetAsync(ctx->distance.out.ptr, 0xff, (size_t)n * sizeof(uint64_t), ctx->stream));
         }
     }
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dist_harvest(ctx);
-    VC_HIP(ctx, hipEventElapsedTime(&stats->distance_ms, ctx->ev[0], ctx->ev[1]));
+    VC_TRY(pass_end(ctx, pass, &stats->distance_ms));
     stats->survivors = S;
     stats->sites_inside_box = S ? dist_cells(bx) - S : 0;
     stats->max_d2 = S ? ctx->h_res[0] : 0;
     for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
-    ctx->dist_valid = true;
-    ctx->dist_outside = outside;
-    ctx->dist_n = S;
-    ctx->dist_box = bx;
+    ctx->distance.stamp = ctx->result_gen;
+    ctx->distance.outside = outside;
+    ctx->distance.n = S;
+    ctx->distance.box = bx;
     return VC_OK;
 }
 
 int vc_fetch_record_distance(vc_ctx *ctx, uint64_t *d2)
 {
     if (!ctx || !d2) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->dist_valid) return fail(ctx, VC_ERR_ARG, "no distance field: call vc_hull_distance on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->distance.stamp)) return fail(ctx, VC_ERR_ARG, "no distance field: call vc_hull_distance on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->dist_n) VC_HIP(ctx, hipMemcpy(d2, ctx->d_dist_rec.ptr, (size_t)ctx->dist_n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (ctx->distance.n) VC_HIP(ctx, hipMemcpy(d2, ctx->distance.rec.ptr, (size_t)ctx->distance.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -2851,20 +2860,20 @@ int vc_fetch_distance(vc_ctx *ctx, uint32_t which, uint64_t *d2)
 {
     if (!ctx || !d2) return VC_ERR_ARG;
     if (which > 1) return fail(ctx, VC_ERR_ARG, "vc_fetch_distance: which = %u, expected 0 (inside) or 1 (outside)", which);
-    if (!ctx->carved || !ctx->dist_valid) return fail(ctx, VC_ERR_ARG, "no distance field: call vc_hull_distance on the current carve result");
-    if (which == 1 && !ctx->dist_outside)
+    if (!ctx->carved || !ctx->current(ctx->distance.stamp)) return fail(ctx, VC_ERR_ARG, "no distance field: call vc_hull_distance on the current carve result");
+    if (which == 1 && !ctx->distance.outside)
         return fail(ctx, VC_ERR_ARG, "no outside field: the last vc_hull_distance ran without VC_DIST_OUTSIDE");
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = ctx->n_voxels();
     if (which == 1) {
-        if (n) VC_HIP(ctx, hipMemcpy(d2, ctx->d_dist_out.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (n) VC_HIP(ctx, hipMemcpy(d2, ctx->distance.out.ptr, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
         return VC_OK;
     }
     memset(d2, 0, (size_t)n * sizeof(uint64_t));                 // zero off the box: every voxel there is OFF
-    if (!ctx->dist_n) return VC_OK;
-    const DistBox &bx = ctx->dist_box;
+    if (!ctx->distance.n) return VC_OK;
+    const DistBox &bx = ctx->distance.box;
     std::vector<uint64_t> h((size_t)dist_cells(bx));
-    VC_HIP(ctx, hipMemcpy(h.data(), ctx->d_dist_in.ptr, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    VC_HIP(ctx, hipMemcpy(h.data(), ctx->distance.in.ptr, h.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     // the rows of the box that lie in the grid, cut to the grid along y
     const int32_t y0 = bx.o[1] < 0 ? 0 : bx.o[1], y1 = std::min<int32_t>(bx.o[1] + (int32_t)bx.b[1], (int32_t)bx.ny);
     for (uint32_t lz = 0; lz < bx.b[2]; ++lz) {
@@ -2888,40 +2897,34 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
     if (op != VC_MORPH_ERODE && op != VC_MORPH_OPEN)
         return fail(ctx, VC_ERR_ARG, "vc_hull_morphology: unknown op %u (VC_MORPH_ERODE, VC_MORPH_OPEN)", op);
     if (flags & ~VC_DIST_BORDER_OFF) return fail(ctx, VC_ERR_ARG, "vc_hull_morphology: unknown flags %u (VC_DIST_BORDER_OFF)", flags);
-    VC_TRY(result_refusals(ctx, "vc_hull_morphology", "keep", "morphology"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_morphology", "keep", "morphology", pass));
     uint64_t q[3];
     VC_TRY(dist_metric(ctx, "vc_hull_morphology", q));
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->dist_ev_kind.clear();
-    const uint64_t S0 = ctx->survivors;
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    const uint64_t S0 = pass.S;
     if (S0) {                                    // every buffer of the hand-over before anything is queued: a failure leaves the result
         VC_TRY(ensure(ctx, ctx->d_rec_spare, cur.records.cap));
         VC_TRY(ensure(ctx, ctx->d_rscan, (uint32_t)((S0 + kCompactGroup - 1) / kCompactGroup)));
     }
-    if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(pass_start(ctx, pass));
     if (S0) {
         DistBox bx;
-        VC_TRY(densify_words(ctx, cur));
         VC_TRY(dist_inside(ctx, cur, flags, S0, r2, q, bx));     // 5: d_dist_rec = D_in, acc = [max D_in, |E|]
         if (op == VC_MORPH_OPEN) {                               // 6: the same transform with sites = E, over the same box
-            VC_TRY(dist_transform(ctx, bx, kDistSiteAbove, cur.words.ptr, ctx->d_dist_in.ptr, r2, q));
-            VC_TRY(dist_records(ctx, cur, bx, ctx->d_dist_in.ptr, S0, r2, ctx->d_dist_acc.ptr + 2));
+            VC_TRY(dist_transform(ctx, bx, kDistSiteAbove, cur.words.ptr, ctx->distance.in.ptr, r2, q));
+            VC_TRY(dist_records(ctx, cur, bx, ctx->distance.in.ptr, S0, r2, ctx->distance.acc.ptr + 2));
         }
         // the result changes from here on
-        ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
-        VC_TRY(compact_records(ctx, cur, DistKept{ctx->d_dist_rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
+        result_changed(ctx);
+        VC_TRY(compact_records(ctx, cur, DistKept{ctx->distance.rec.ptr, r2, op == VC_MORPH_OPEN ? 1u : 0u, cur.records.ptr, cur.words.ptr, nullptr},
                                S0, ctx->h_res + 1));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->d_dist_acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->d_dist_acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 0, ctx->distance.acc.ptr + 0, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res + 2, ctx->distance.acc.ptr + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dist_harvest(ctx);
+    result_changed(ctx);
+    VC_TRY(pass_end(ctx, pass, &stats->morph_ms));
     uint64_t kept = 0;
     if (S0) {
         kept = ctx->h_res[1];
@@ -2930,7 +2933,6 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
         stats->max_d2 = ctx->h_res[0];
         stats->eroded = ctx->h_res[2];
     }
-    VC_HIP(ctx, hipEventElapsedTime(&stats->morph_ms, ctx->ev[0], ctx->ev[1]));
     stats->survivors_before = S0;
     stats->survivors_after = kept;
     for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
@@ -2955,27 +2957,23 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
     if (op != VC_GROW_DILATE && op != VC_GROW_CLOSE)
         return fail(ctx, VC_ERR_ARG, "vc_hull_grow: unknown op %u (VC_GROW_DILATE, VC_GROW_CLOSE)", op);
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_grow: flags must be 0 (got %u)", flags);
-    VC_TRY(result_refusals(ctx, "vc_hull_grow", "merge the added voxels into", "morphology"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_grow", "merge the added voxels into", "morphology", pass));
     uint64_t q[3];
     VC_TRY(dist_metric(ctx, "vc_hull_grow", q));
-    StepBuf &cur = ctx->sb[ctx->cur];
+    StepBuf &cur = *pass.cur;
     if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
         return fail(ctx, VC_ERR_ARG, "vc_hull_grow: frame set %u has been prepared again since the carve: its images are not the ones "
                     "the records' colours came from", cur.slot);
-    const uint64_t n = ctx->n_voxels(), nwords = (n + 63) / 64;
+    const uint64_t n = pass.n, nwords = pass.nwords;
     if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_grow: %llu voxels exceed the u32 index", (unsigned long long)n);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->dist_ev_kind.clear();
-    const uint64_t S0 = ctx->survivors;
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    if (S0 && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(pass_begin(ctx));
+    const uint64_t S0 = pass.S;
+    VC_TRY(pass_start(ctx, pass));
     uint64_t S1 = S0, added = 0, dilated = 0;
     DistBox bx;
     memset(&bx, 0, sizeof bx);
     if (S0) {
-        VC_TRY(densify_words(ctx, cur));
         // the survivors' index box, grown per axis by g_a + 1 cells and clipped to the grid: Dl lies inside the g-grown box, and the
         // extra layer (where no grid face cuts it off) is outside Dl, which makes the second transform over the box exact
         uint32_t *hb = nullptr;
@@ -2994,30 +2992,30 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
         const uint64_t i_hi = ((uint64_t)(bx.o[2] + (int32_t)bx.b[2] - 1) * ctx->nx + (uint32_t)(bx.o[0] + (int32_t)bx.b[0] - 1)) * ctx->ny +
                               (uint32_t)(bx.o[1] + (int32_t)bx.b[1] - 1);
         const uint64_t w0 = i_lo >> 6, nrange = (i_hi >> 6) - w0 + 1;
-        ctx->dist_valid = false;                 // the field's buffer is the transforms' from here on, whether the call succeeds or not
-        VC_TRY(dist_ensure(ctx, ctx->d_dist_in, bx));
-        VC_TRY(ensure(ctx, ctx->d_grow_addw, (size_t)nrange));
-        VC_TRY(ensure(ctx, ctx->d_grow_ctr, 2));
-        uint64_t *f = ctx->d_dist_in.ptr;
+        ctx->distance.stamp = kNever;            // the field's buffer is the transforms' from here on, whether the call succeeds or not
+        VC_TRY(dist_ensure(ctx, ctx->distance.in, bx));
+        VC_TRY(ensure(ctx, ctx->grow.addw, (size_t)nrange));
+        VC_TRY(ensure(ctx, ctx->grow.ctr, 2));
+        uint64_t *f = ctx->distance.in.ptr;
         const uint64_t ylines = (uint64_t)bx.b[0] * bx.b[2];
         const dim3 block(kDistBlock), mgrid((uint32_t)((ylines + (kDistBlock / 64) * kGrowLines - 1) / ((kDistBlock / 64) * kGrowLines)));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_addw.ptr, 0, (size_t)nrange * sizeof(unsigned long long), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->grow.ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->grow.addw.ptr, 0, (size_t)nrange * sizeof(unsigned long long), ctx->stream));
         // 1: D_out over the box; 2: for the closing |Dl|, then the same transform with sites = the box's cells outside Dl
         VC_TRY(dist_transform(ctx, bx, kDistSiteOn, cur.words.ptr, f, 0, q));
         if (op == VC_GROW_CLOSE) {
             VC_DLAUNCH(VC_K_GROW_MARK, k_grow_mark<kGrowCount>, mgrid, block, bx, (const uint64_t *)f, r2, (const uint64_t *)cur.words.ptr, nwords,
-                       ctx->d_grow_addw.ptr, w0, nrange, ctx->d_grow_ctr.ptr + 1);
+                       ctx->grow.addw.ptr, w0, nrange, ctx->grow.ctr.ptr + 1);
             VC_TRY(dist_transform(ctx, bx, kDistSiteAbove, cur.words.ptr, f, r2, q));
             VC_DLAUNCH(VC_K_GROW_MARK, k_grow_mark<kGrowClose>, mgrid, block, bx, (const uint64_t *)f, r2, (const uint64_t *)cur.words.ptr, nwords,
-                       ctx->d_grow_addw.ptr, w0, nrange, ctx->d_grow_ctr.ptr + 0);
+                       ctx->grow.addw.ptr, w0, nrange, ctx->grow.ctr.ptr + 0);
         } else {
             VC_DLAUNCH(VC_K_GROW_MARK, k_grow_mark<kGrowDilate>, mgrid, block, bx, (const uint64_t *)f, r2, (const uint64_t *)cur.words.ptr, nwords,
-                       ctx->d_grow_addw.ptr, w0, nrange, ctx->d_grow_ctr.ptr + 0);
+                       ctx->grow.addw.ptr, w0, nrange, ctx->grow.ctr.ptr + 0);
         }
         VC_HIP(ctx, hipGetLastError());
         // the read-back in the middle: the added voxels size the records
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_grow_ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->grow.ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         added = ctx->h_res[0];
         S1 = S0 + added;
@@ -3026,32 +3024,27 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
             return fail(ctx, VC_ERR_HIP, "vc_hull_grow: %llu added to %llu survivors, %llu dilated, in a grid of %llu voxels", (unsigned long long)added,
                         (unsigned long long)S0, (unsigned long long)dilated, (unsigned long long)n);
         // every buffer of the hand-over before anything changes: a failure leaves the result
-        const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);
-        ctx->grow_valid = false;                 // (the added bytes of an earlier call go with their buffer)
-        VC_TRY(ensure(ctx, ctx->d_grow_added, (size_t)S1));
+        const uint32_t wgroups = word_groups(nwords);
+        ctx->grow.stamp = kNever;                // (the added bytes of an earlier call go with their buffer)
+        VC_TRY(ensure(ctx, ctx->grow.added, (size_t)S1));
         if (added) {
             VC_TRY(ensure(ctx, ctx->d_rec_spare, std::max<size_t>(cur.records.cap, (size_t)S1)));
             VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
             VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
         }
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_grow_added.ptr, 0, (size_t)S1, ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->grow.added.ptr, 0, (size_t)S1, ctx->stream));
         if (added) {
             // the result changes from here on
-            ctx->vis_valid = false; ctx->photo_valid = false; ctx->cc_valid = false; ctx->cl_valid = false; ctx->geo_valid = false; ctx->dist_valid = false; ctx->grow_valid = false; ctx->nrm_valid = false; ctx->rn_current = false; ctx->sf_current = false;
+            result_changed(ctx);
             const dim3 gblock(kGrowBlock), rgrid((uint32_t)((nrange + kGrowBlock - 1) / kGrowBlock));
-            VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->d_grow_addw.ptr, w0, nrange);
+            VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->grow.addw.ptr, w0, nrange);
             // survivors per group of the step, counted again: the packing skips the groups whose count is zero, and an added voxel
             // may be the first of its group
             const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
             VC_DLAUNCH(VC_K_GROW_RANK, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups,
                        cur.groupcnt.ptr);
-            // ranks of the new occupancy: popcounts per 64 words, their scan, the wave scan inside each group
-            const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), cblock(kCcBlock);
-            VC_DLAUNCH(VC_K_GROW_RANK, k_cc_wcount, wgrid, cblock, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
-            VC_HIP(ctx, hipGetLastError());
-            VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, ctx->h_res + 2));
-            VC_DLAUNCH(VC_K_GROW_RANK, k_cc_woff, wgrid, cblock, (const uint64_t *)cur.words.ptr, nwords, wgroups,
-                       (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_cc_woff.ptr);
+            // ranks of the new occupancy (in the components' offsets: their labels went stale with the result)
+            VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_cc_woff, ctx->h_res + 2, VC_K_GROW_RANK));
             // the merged list into the spare buffer: every old record to its new rank, a fresh record for every added voxel
             GrowParams p;
             memset(&p, 0, sizeof p);
@@ -3059,54 +3052,43 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
             p.has_cam = cur.emit.has_cam && cur.emit.xs ? 1 : 0;
             p.cam = cur.emit.cam;
             p.frame = cur.emit.frame;
-            p.words = cur.words.ptr; p.woff = ctx->d_cc_woff.ptr; p.addw = ctx->d_grow_addw.ptr;
-            p.out = ctx->d_rec_spare.ptr; p.added = ctx->d_grow_added.ptr;
+            p.words = cur.words.ptr; p.woff = ctx->d_cc_woff.ptr; p.addw = ctx->grow.addw.ptr;
+            p.out = ctx->d_rec_spare.ptr; p.added = ctx->grow.added.ptr;
             p.w0 = w0; p.nrange = nrange; p.S1 = S1;
             p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.H = ctx->H; p.W = ctx->W;
             VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_old, dim3((uint32_t)((S0 + kGrowBlock - 1) / kGrowBlock)), gblock, p, (const uint64_t *)cur.records.ptr, S0, nwords);
             VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_new, rgrid, gblock, p, nwords);
             VC_HIP(ctx, hipGetLastError());
-            std::swap(cur.records, ctx->d_rec_spare);
-            // the readers of the step's scan: vc_pack_entries / the compact gather report blockoff[nscan] as this rank's survivors
-            const uint32_t nscan = (wgroups + kScanBlock - 1) / kScanBlock;
-            const uint64_t n_pad = (cur.n + kLutPad - 1) / kLutPad * kLutPad;
-            const uint32_t cscan = (uint32_t)((n_pad / (64 * kGroupWords) + kScanBlock - 1) / kScanBlock);
-            VC_HIP(ctx, hipMemcpyAsync(cur.blockoff.ptr + cscan, ctx->d_rscan.boff.ptr + nscan, sizeof(uint64_t), hipMemcpyDeviceToDevice,
-                                       ctx->stream));
-            cur.nz_valid = false;                // non-zero word counts per group: counted again by the next packing
-            ctx->gathered = false; ctx->packed = false;
+            VC_TRY(records_handed_over(ctx, cur, wgroups));
         }
     }
     // a call that adds nothing (r2 = 0, a second closing, the empty hull) leaves the result as it is, and with it the visibility,
     // the photo rounds and the component labels; the stored distance field went with its buffer above
-    ctx->grow_valid = false;
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dist_harvest(ctx);
+    ctx->grow.stamp = kNever;
+    VC_TRY(pass_end(ctx, pass, &stats->grow_ms));
     if (added) {
         ctx->survivors = cur.survivors = S1;
         if (ctx->h_res[2] != S1)
             return fail(ctx, VC_ERR_HIP, "vc_hull_grow: the new occupancy holds %llu voxels, %llu records were merged", (unsigned long long)ctx->h_res[2],
                         (unsigned long long)S1);
     }
-    VC_HIP(ctx, hipEventElapsedTime(&stats->grow_ms, ctx->ev[0], ctx->ev[1]));
     stats->survivors_before = S0;
     stats->dilated = dilated;
     stats->survivors_after = S1;
     stats->added = added;
     stats->box_cells = S0 ? dist_cells(bx) : 0;
     for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
-    ctx->grow_valid = true;
-    ctx->grow_n = S1;
+    ctx->grow.stamp = ctx->result_gen;
+    ctx->grow.n = S1;
     return VC_OK;
 }
 
 int vc_fetch_grown(vc_ctx *ctx, uint8_t *added)
 {
     if (!ctx || !added) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->grow_valid) return fail(ctx, VC_ERR_ARG, "no added flags: call vc_hull_grow on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->grow.stamp)) return fail(ctx, VC_ERR_ARG, "no added flags: call vc_hull_grow on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->grow_n) VC_HIP(ctx, hipMemcpy(added, ctx->d_grow_added.ptr, (size_t)ctx->grow_n, hipMemcpyDeviceToHost));
+    if (ctx->grow.n) VC_HIP(ctx, hipMemcpy(added, ctx->grow.added.ptr, (size_t)ctx->grow.n, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3129,38 +3111,34 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
         if (!(views[k].K[0] > 0.0) || !(views[k].K[1] > 0.0))
             return fail(ctx, VC_ERR_ARG, "vc_render: view %u has fx %g, fy %g (both must be > 0)", k, views[k].K[0], views[k].K[1]);
     }
-    VC_TRY(result_refusals(ctx, "vc_render", "render", "rendering"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_render", "render", "rendering", pass));
     if (ctx->nx < 2 || ctx->ny < 2 || ctx->nz < 2)
         return fail(ctx, VC_ERR_ARG, "vc_render: grid %ux%ux%u has an axis shorter than 2", ctx->nx, ctx->ny, ctx->nz);
     static_assert(sizeof(vc_view_t) == sizeof(RenderView), "vc_view_t is the device's view");
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->rn_valid = false; ctx->rn_current = false; ctx->sh_valid = false;
-    VC_TRY(ensure(ctx, ctx->d_rn_idx, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->d_rn_depth, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->d_rn_rgbf, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->d_rn_views, n_views));
-    VC_TRY(ensure(ctx, ctx->d_rn_ctr, 3));
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    ctx->render.valid = false; ctx->render.stamp = kNever; ctx->normals.sh_valid = false;
+    VC_TRY(ensure(ctx, ctx->render.idx, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->render.depth, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->render.rgbf, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->render.views, n_views));
+    VC_TRY(ensure(ctx, ctx->render.ctr, 3));
     const uint32_t nb[3] = {(ctx->nx + kRenderB - 1) / kRenderB, (ctx->ny + kRenderB - 1) / kRenderB, (ctx->nz + kRenderB - 1) / kRenderB};
     const uint64_t nblocks = (uint64_t)nb[0] * nb[1] * nb[2];
-    VC_TRY(ensure(ctx, ctx->d_rn_map, (size_t)((nblocks + 63) / 64)));
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (ctx->survivors && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    VC_TRY(densify_words(ctx, cur));
-    VC_HIP(ctx, hipMemcpyAsync(ctx->d_rn_views.ptr, views, (size_t)n_views * sizeof(vc_view_t), hipMemcpyHostToDevice, ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_rn_ctr.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
+    VC_TRY(ensure(ctx, ctx->render.map, (size_t)((nblocks + 63) / 64)));
+    VC_TRY(pass_start(ctx, pass, kWordsAlways));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->render.views.ptr, views, (size_t)n_views * sizeof(vc_view_t), hipMemcpyHostToDevice, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->render.ctr.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
     RenderParams p;
     memset(&p, 0, sizeof p);
     p.words = cur.words.ptr;
-    p.bmap = ctx->d_rn_map.ptr;
+    p.bmap = ctx->render.map.ptr;
     p.records = cur.records.ptr;
     p.S = ctx->survivors;
-    p.views = ctx->d_rn_views.ptr;
-    p.idx = ctx->d_rn_idx.ptr; p.depth = ctx->d_rn_depth.ptr; p.rgbf = ctx->d_rn_rgbf.ptr;
-    p.ctr = ctx->d_rn_ctr.ptr;
+    p.views = ctx->render.views.ptr;
+    p.idx = ctx->render.idx.ptr; p.depth = ctx->render.depth.ptr; p.rgbf = ctx->render.rgbf.ptr;
+    p.ctr = ctx->render.ctr.ptr;
     const uint32_t n3[3] = {ctx->nx, ctx->ny, ctx->nz};
     for (int a = 0; a < 3; ++a) {                // item 1 (this file is built without contraction too)
         p.n[a] = n3[a];
@@ -3174,19 +3152,19 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
     p.n_tiles = p.tiles_per_view * n_views;      // <= 2^28 views x tiles of one pixel
     for (int f = 0; f < 7; ++f) p.shade[f] = shade ? shade[f] : 255u;
     p.bg = background ? (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16) : 0u;
-    p.skip = ctx->render_blocks ? 1u : 0u;
+    p.skip = ctx->render.blocks ? 1u : 0u;
     if (p.skip) {
         hipLaunchKernelGGL(k_render_map, dim3((uint32_t)((nblocks + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, ctx->stream,
-                           (const uint64_t *)cur.words.ptr, ctx->d_rn_map.ptr, ctx->nx, ctx->ny, ctx->nz, nb[0], nb[1], nblocks);
+                           (const uint64_t *)cur.words.ptr, ctx->render.map.ptr, ctx->nx, ctx->ny, ctx->nz, nb[0], nb[1], nblocks);
         VC_HIP(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(k_render, dim3((p.n_tiles + kRenderBlock / 64 - 1) / (kRenderBlock / 64)), dim3(kRenderBlock), 0, ctx->stream, p);
     VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_rn_ctr.ptr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->rn_valid = true; ctx->rn_current = true;
-    ctx->rn_views = n_views; ctx->rn_H = H; ctx->rn_W = W;
+    VC_TRY(pass_stop(ctx, pass));                   // (the counters' read-back is not part of the render's time)
+    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->render.ctr.ptr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_TRY(pass_end(ctx, pass, stats ? &stats->render_ms : nullptr));
+    ctx->render.valid = true; ctx->render.stamp = ctx->result_gen;
+    ctx->render.n_views = n_views; ctx->render.H = H; ctx->render.W = W;
     if (ctx->h_res[0] > npix) return fail(ctx, VC_ERR_HIP, "vc_render: %llu hits among %llu pixels", (unsigned long long)ctx->h_res[0],
                                           (unsigned long long)npix);
     if (stats) {
@@ -3194,7 +3172,6 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
         stats->hits = ctx->h_res[0];
         stats->cells_visited = ctx->h_res[1];
         stats->blocks_skipped = ctx->h_res[2];
-        VC_HIP(ctx, hipEventElapsedTime(&stats->render_ms, ctx->ev[0], ctx->ev[1]));
     }
     return VC_OK;
 }
@@ -3202,15 +3179,15 @@ int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H,
 int vc_fetch_render(vc_ctx *ctx, uint32_t view, uint32_t *idx, float *depth, uint8_t *rgb, uint8_t *face)
 {
     if (!ctx) return VC_ERR_ARG;
-    if (!ctx->rn_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: no images: call vc_render first");
-    if (view >= ctx->rn_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: view %u not in [0,%u)", view, ctx->rn_views);
+    if (!ctx->render.valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: no images: call vc_render first");
+    if (view >= ctx->render.n_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: view %u not in [0,%u)", view, ctx->render.n_views);
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->rn_H * ctx->rn_W, off = (size_t)view * HW;
-    if (idx) VC_HIP(ctx, hipMemcpy(idx, ctx->d_rn_idx.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (depth) VC_HIP(ctx, hipMemcpy(depth, ctx->d_rn_depth.ptr + off, HW * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t HW = (size_t)ctx->render.H * ctx->render.W, off = (size_t)view * HW;
+    if (idx) VC_HIP(ctx, hipMemcpy(idx, ctx->render.idx.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (depth) VC_HIP(ctx, hipMemcpy(depth, ctx->render.depth.ptr + off, HW * sizeof(float), hipMemcpyDeviceToHost));
     if (rgb || face) {
         std::vector<uint32_t> px(HW);
-        VC_HIP(ctx, hipMemcpy(px.data(), ctx->d_rn_rgbf.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        VC_HIP(ctx, hipMemcpy(px.data(), ctx->render.rgbf.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < HW; ++k) {
             const uint32_t q = px[k];
             if (rgb) { rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16); }
@@ -3223,20 +3200,20 @@ int vc_fetch_render(vc_ctx *ctx, uint32_t view, uint32_t *idx, float *depth, uin
 int vc_fetch_visibility(vc_ctx *ctx, uint16_t *vis)
 {
     if (!ctx || !vis) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->vis_valid) return fail(ctx, VC_ERR_ARG, "no visibility: call vc_color_visible on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->visible.stamp)) return fail(ctx, VC_ERR_ARG, "no visibility: call vc_color_visible on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->survivors) VC_HIP(ctx, hipMemcpy(vis, ctx->d_vis_mask.ptr, ctx->survivors * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (ctx->survivors) VC_HIP(ctx, hipMemcpy(vis, ctx->visible.mask.ptr, ctx->survivors * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
 int vc_fetch_depth(vc_ctx *ctx, uint32_t cam, float *out)
 {
     if (!ctx || !out) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->vis_valid) return fail(ctx, VC_ERR_ARG, "no depth maps: call vc_color_visible on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->visible.stamp)) return fail(ctx, VC_ERR_ARG, "no depth maps: call vc_color_visible on the current carve result");
     if (cam >= ctx->C) return fail(ctx, VC_ERR_ARG, "camera %u not in [0,%u)", cam, ctx->C);
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t HW = (size_t)ctx->H * ctx->W;
-    VC_HIP(ctx, hipMemcpy(out, ctx->d_vis_zmap.ptr + (size_t)cam * HW, HW * sizeof(float), hipMemcpyDeviceToHost));
+    VC_HIP(ctx, hipMemcpy(out, ctx->visible.zmap.ptr + (size_t)cam * HW, HW * sizeof(float), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3314,31 +3291,27 @@ int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces)
 int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stats_t *stats)
 {
     if (!ctx) return VC_ERR_ARG;
-    ctx->sf_valid = false; ctx->sf_current = false;
+    ctx->surface.valid = false; ctx->surface.stamp = kNever;
     if (!stats) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: stats must not be NULL");
     memset(stats, 0, sizeof *stats);
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: flags must be 0 (got %u)", flags);
     if (steps > kSurfMaxSteps) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: steps %u not in [0, %u]", steps, kSurfMaxSteps);
-    VC_TRY(result_refusals(ctx, "vc_surface_mesh", "colour the mesh from", "meshing"));
-    StepBuf &cur = ctx->sb[ctx->cur];
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_surface_mesh", "colour the mesh from", "meshing", pass));
+    StepBuf &cur = *pass.cur;
     if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
         return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: frame set %u has been prepared again since the carve: its masks are not the ones "
                     "the occupancy came from", cur.slot);
-    const uint64_t n = ctx->n_voxels();
+    const uint64_t n = pass.n;
     if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: %llu voxels exceed the u32 index", (unsigned long long)n);
     const Slot &s = ctx->slots[cur.slot];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (ctx->survivors && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(pass_begin(ctx));
+    VC_TRY(pass_start(ctx, pass, kWordsAlways));
     uint64_t V = 0, F = 0;
     McParams p;
     memset(&p, 0, sizeof p);
     if (n) {
         // 1 topology: vc_marching_cubes(NULL, nz, nx, ny)'s counts and scans (its scratch, not its mesh)
-        VC_TRY(densify_words(ctx, cur));
         const uint32_t nwords = (uint32_t)((n + 63) / 64), ngroups = (nwords + 63) / 64;
         VC_TRY(ensure(ctx, ctx->d_mcx, (size_t)nwords * 3));
         VC_TRY(ensure(ctx, ctx->d_mcwbase, (size_t)nwords));
@@ -3357,64 +3330,63 @@ int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stat
         V = ctx->h_res[0]; F = ctx->h_res[1];
         if (V > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: %llu vertices exceed the u32 vertex number", (unsigned long long)V);
     }
-    VC_TRY(ensure(ctx, ctx->d_sf_edges, (size_t)(V + 1)));
-    VC_TRY(ensure(ctx, ctx->d_sf_verts, (size_t)(3 * V + 3)));
-    VC_TRY(ensure(ctx, ctx->d_sf_faces, (size_t)(3 * F + 3)));
-    VC_TRY(ensure(ctx, ctx->d_sf_rgb, (size_t)(3 * V + 3)));
-    VC_TRY(ensure(ctx, ctx->d_sf_refined, (size_t)(V + 1)));
-    VC_TRY(ensure(ctx, ctx->d_sf_ctr, 2));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_sf_ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    VC_TRY(ensure(ctx, ctx->surface.edges, (size_t)(V + 1)));
+    VC_TRY(ensure(ctx, ctx->surface.verts, (size_t)(3 * V + 3)));
+    VC_TRY(ensure(ctx, ctx->surface.faces, (size_t)(3 * F + 3)));
+    VC_TRY(ensure(ctx, ctx->surface.rgb, (size_t)(3 * V + 3)));
+    VC_TRY(ensure(ctx, ctx->surface.refined, (size_t)(V + 1)));
+    VC_TRY(ensure(ctx, ctx->surface.ctr, 2));
+    VC_HIP(ctx, hipMemsetAsync(ctx->surface.ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
     if (V) {
         // 2 edge entries in vertex order, the faces (k_mc_faces reads the word bases k_surf_edges writes)
-        p.faces = ctx->d_sf_faces.ptr; p.vcap = V; p.fcap = F;
+        p.faces = ctx->surface.faces.ptr; p.vcap = V; p.fcap = F;
         const dim3 grid((p.ngroups + 3) / 4), block(kBlock);
-        hipLaunchKernelGGL(k_surf_edges, grid, block, 0, ctx->stream, p, ctx->d_sf_edges.ptr);
+        hipLaunchKernelGGL(k_surf_edges, grid, block, 0, ctx->stream, p, ctx->surface.edges.ptr);
         hipLaunchKernelGGL(k_mc_faces, grid, block, 0, ctx->stream, p);
         VC_HIP(ctx, hipGetLastError());
         // 3 the refinement and the colours
         SurfParams q;
         memset(&q, 0, sizeof q);
-        q.edges = ctx->d_sf_edges.ptr;
+        q.edges = ctx->surface.edges.ptr;
         q.records = cur.records.ptr;
         q.S = ctx->survivors;
         q.V = V;
         q.xs = ctx->d_axes.ptr; q.ys = q.xs + ctx->nx; q.zs = q.ys + ctx->ny;
         q.bits = s.bits.ptr;
         q.mwords = ctx->mwords; q.C = ctx->C; q.H = ctx->H; q.W = ctx->W;
-        q.m = cur.min_views; q.steps = steps; q.order = ctx->surface_order ? 1u : 0u;
+        q.m = cur.min_views; q.steps = steps; q.order = ctx->surface.order ? 1u : 0u;
         q.nx = ctx->nx; q.ny = ctx->ny;
-        q.verts = ctx->d_sf_verts.ptr; q.rgb = ctx->d_sf_rgb.ptr; q.refined = ctx->d_sf_refined.ptr;
-        q.ctr = ctx->d_sf_ctr.ptr;
+        q.verts = ctx->surface.verts.ptr; q.rgb = ctx->surface.rgb.ptr; q.refined = ctx->surface.refined.ptr;
+        q.ctr = ctx->surface.ctr.ptr;
         memcpy(q.cam, ctx->cams, sizeof(CamDev) * ctx->C);
         hipLaunchKernelGGL(k_surf_refine, dim3((uint32_t)((V + kSurfBlock - 1) / kSurfBlock)), dim3(kSurfBlock), 0, ctx->stream, q);
         VC_HIP(ctx, hipGetLastError());
     }
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_sf_ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VC_TRY(pass_stop(ctx, pass));                   // (the counters' read-back is not part of the mesh's time)
+    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->surface.ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_TRY(pass_end(ctx, pass, &stats->surface_ms));
     const uint64_t refined = ctx->h_res[0];
     if (refined > V) return fail(ctx, VC_ERR_HIP, "vc_surface_mesh: %llu refined among %llu vertices", (unsigned long long)refined,
                                  (unsigned long long)V);
-    ctx->sf_verts = V; ctx->sf_faces = F; ctx->sf_valid = true; ctx->sf_current = true;
+    ctx->surface.n_verts = V; ctx->surface.n_faces = F; ctx->surface.valid = true; ctx->surface.stamp = ctx->result_gen;
     stats->n_verts = V;
     stats->n_faces = F;
     stats->refined = refined;
     stats->unrefined = V - refined;
     stats->point_tests = ctx->h_res[1];
-    VC_HIP(ctx, hipEventElapsedTime(&stats->surface_ms, ctx->ev[0], ctx->ev[1]));
     return VC_OK;
 }
 
 int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *rgb, uint8_t *refined)
 {
     if (!ctx) return VC_ERR_ARG;
-    if (!ctx->sf_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_surface_mesh: no mesh: call vc_surface_mesh first");
+    if (!ctx->surface.valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_surface_mesh: no mesh: call vc_surface_mesh first");
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t V = (size_t)ctx->sf_verts, F = (size_t)ctx->sf_faces;
-    if (verts && V) VC_HIP(ctx, hipMemcpy(verts, ctx->d_sf_verts.ptr, V * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (faces && F) VC_HIP(ctx, hipMemcpy(faces, ctx->d_sf_faces.ptr, F * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (rgb && V) VC_HIP(ctx, hipMemcpy(rgb, ctx->d_sf_rgb.ptr, V * 3, hipMemcpyDeviceToHost));
-    if (refined && V) VC_HIP(ctx, hipMemcpy(refined, ctx->d_sf_refined.ptr, V, hipMemcpyDeviceToHost));
+    const size_t V = (size_t)ctx->surface.n_verts, F = (size_t)ctx->surface.n_faces;
+    if (verts && V) VC_HIP(ctx, hipMemcpy(verts, ctx->surface.verts.ptr, V * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (faces && F) VC_HIP(ctx, hipMemcpy(faces, ctx->surface.faces.ptr, F * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (rgb && V) VC_HIP(ctx, hipMemcpy(rgb, ctx->surface.rgb.ptr, V * 3, hipMemcpyDeviceToHost));
+    if (refined && V) VC_HIP(ctx, hipMemcpy(refined, ctx->surface.refined.ptr, V, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3425,7 +3397,8 @@ int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags, vc_normals_stats_t
     if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: stats must not be NULL");
     memset(stats, 0, sizeof *stats);
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: flags must be 0 (got %u)", flags);
-    VC_TRY(result_refusals(ctx, "vc_hull_normals", "give normals to", "normal estimation"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_normals", "give normals to", "normal estimation", pass));
     uint64_t q[3];
     VC_TRY(dist_metric(ctx, "vc_hull_normals", q));
     // item 2: the ball's extents and its rows (dx, dz) with their y half-extent
@@ -3451,76 +3424,61 @@ int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags, vc_normals_stats_t
             rows.push_back(((uint32_t)dx & 255u) | (((uint32_t)dz & 255u) << 8) | (ky << 16));
             offsets += 2ull * ky + ((dx == 0 && dz == 0) ? 0u : 1u);
         }
-    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
     if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: %llu voxels exceed the u32 index", (unsigned long long)n);
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->nrm_valid = false;
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    const uint64_t nwords = (n + 63) / 64;
-    const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    ctx->normals.stamp = kNever;
     if (S) {
-        VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
-        VC_TRY(ensure(ctx, ctx->d_nrm_woff, (size_t)nwords));
-        VC_TRY(ensure(ctx, ctx->d_nrm_rows, rows.size()));
-        VC_TRY(ensure(ctx, ctx->d_nrm_out, (size_t)S));
-        VC_TRY(ensure(ctx, ctx->d_nrm_ctr, 2));
+        VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
+        VC_TRY(ensure(ctx, ctx->normals.woff, (size_t)nwords));
+        VC_TRY(ensure(ctx, ctx->normals.rows, rows.size()));
+        VC_TRY(ensure(ctx, ctx->normals.out, (size_t)S));
+        VC_TRY(ensure(ctx, ctx->normals.ctr, 2));
     }
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(pass_start(ctx, pass));
     ctx->h_res[0] = ctx->h_res[1] = 0;
     if (S) {
-        VC_TRY(densify_words(ctx, cur));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->d_nrm_rows.ptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_nrm_out.ptr, 0, (size_t)S * sizeof(short4), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_nrm_ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), cblock(kCcBlock);
-        hipLaunchKernelGGL(k_cc_wcount, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, ctx->h_res + 2));
-        hipLaunchKernelGGL(k_cc_woff, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
-                           (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_nrm_woff.ptr);
-        VC_HIP(ctx, hipGetLastError());
+        VC_HIP(ctx, hipMemcpyAsync(ctx->normals.rows.ptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->normals.out.ptr, 0, (size_t)S * sizeof(short4), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->normals.ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        VC_TRY(word_offsets(ctx, cur, nwords, ctx->normals.woff, ctx->h_res + 2));
         NrmParams p;
         memset(&p, 0, sizeof p);
-        p.words = cur.words.ptr; p.woff = ctx->d_nrm_woff.ptr; p.rows = ctx->d_nrm_rows.ptr;
-        p.out = ctx->d_nrm_out.ptr; p.ctr = ctx->d_nrm_ctr.ptr;
+        p.words = cur.words.ptr; p.woff = ctx->normals.woff.ptr; p.rows = ctx->normals.rows.ptr;
+        p.out = ctx->normals.out.ptr; p.ctr = ctx->normals.ctr.ptr;
         p.nwords = nwords; p.n = n; p.S = S;
         for (int a = 0; a < 3; ++a) p.q[a] = (long long)q[a];
         p.nrows = (uint32_t)rows.size(); p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
         const uint64_t per_block = (uint64_t)(kNrmBlock / 64) * kNrmWords;
         hipLaunchKernelGGL(k_normals, dim3((uint32_t)((nwords + per_block - 1) / per_block)), dim3(kNrmBlock), 0, ctx->stream, p);
         VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->d_nrm_ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->normals.ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VC_TRY(pass_end(ctx, pass, &stats->normals_ms));
     if (S && ctx->h_res[2] != S)
         return fail(ctx, VC_ERR_HIP, "vc_hull_normals: the occupancy holds %llu voxels, the result %llu records", (unsigned long long)ctx->h_res[2],
                     (unsigned long long)S);
     if (ctx->h_res[0] > S || ctx->h_res[1] > ctx->h_res[0])
         return fail(ctx, VC_ERR_HIP, "vc_hull_normals: %llu surface records, %llu of them without a normal, among %llu", (unsigned long long)ctx->h_res[0],
                     (unsigned long long)ctx->h_res[1], (unsigned long long)S);
-    VC_HIP(ctx, hipEventElapsedTime(&stats->normals_ms, ctx->ev[0], ctx->ev[1]));
     stats->survivors = S;
     stats->surface = ctx->h_res[0];
     stats->zero = ctx->h_res[1];
     stats->offsets = offsets;
     for (int a = 0; a < 3; ++a) { stats->q[a] = q[a]; stats->ext[a] = ext[a]; }
-    ctx->nrm_valid = true;
-    ctx->nrm_n = S;
+    ctx->normals.stamp = ctx->result_gen;
+    ctx->normals.n = S;
     return VC_OK;
 }
 
 int vc_fetch_record_normals(vc_ctx *ctx, int16_t *n4)
 {
     if (!ctx) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->nrm_valid) return fail(ctx, VC_ERR_ARG, "no normals: call vc_hull_normals on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->normals.stamp)) return fail(ctx, VC_ERR_ARG, "no normals: call vc_hull_normals on the current carve result");
     if (!n4) return VC_OK;                       // only asked whether the normals are valid
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->nrm_n) VC_HIP(ctx, hipMemcpy(n4, ctx->d_nrm_out.ptr, (size_t)ctx->nrm_n * sizeof(short4), hipMemcpyDeviceToHost));
+    if (ctx->normals.n) VC_HIP(ctx, hipMemcpy(n4, ctx->normals.out.ptr, (size_t)ctx->normals.n * sizeof(short4), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3530,11 +3488,11 @@ int vc_shade_render(vc_ctx *ctx, const double *light, uint32_t ambient, uint32_t
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_shade_render: flags must be 0 (got %u)", flags);
     if (!light) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no lights");
     if (ambient > 255) return fail(ctx, VC_ERR_ARG, "vc_shade_render: ambient %u not in 0..255", ambient);
-    if (!ctx->carved || !ctx->nrm_valid) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no normals: call vc_hull_normals on the current carve result");
-    if (!ctx->rn_valid || !ctx->rn_current)
+    if (!ctx->carved || !ctx->current(ctx->normals.stamp)) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no normals: call vc_hull_normals on the current carve result");
+    if (!ctx->render.valid || !ctx->current(ctx->render.stamp))
         return fail(ctx, VC_ERR_ARG, "vc_shade_render: no images of the current carve result: call vc_render first");
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    for (uint32_t v = 0; v < ctx->rn_views; ++v) {
+    for (uint32_t v = 0; v < ctx->render.n_views; ++v) {
         const double *L = light + 3 * (size_t)v;
         if (!std::isfinite(L[0]) || !std::isfinite(L[1]) || !std::isfinite(L[2]))
             return fail(ctx, VC_ERR_ARG, "vc_shade_render: the light of view %u has a component that is not finite", v);
@@ -3543,33 +3501,33 @@ int vc_shade_render(vc_ctx *ctx, const double *light, uint32_t ambient, uint32_t
     }
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->sh_valid = false;
-    const uint64_t view_pix = (uint64_t)ctx->rn_H * ctx->rn_W, npix = view_pix * ctx->rn_views;
-    VC_TRY(ensure(ctx, ctx->d_sh_rgb, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->d_sh_light, 3 * (size_t)ctx->rn_views));
-    VC_HIP(ctx, hipMemcpyAsync(ctx->d_sh_light.ptr, light, 3 * (size_t)ctx->rn_views * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    ctx->normals.sh_valid = false;
+    const uint64_t view_pix = (uint64_t)ctx->render.H * ctx->render.W, npix = view_pix * ctx->render.n_views;
+    VC_TRY(ensure(ctx, ctx->normals.sh_rgb, (size_t)npix));
+    VC_TRY(ensure(ctx, ctx->normals.sh_light, 3 * (size_t)ctx->render.n_views));
+    VC_HIP(ctx, hipMemcpyAsync(ctx->normals.sh_light.ptr, light, 3 * (size_t)ctx->render.n_views * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     ShadeParams p;
     memset(&p, 0, sizeof p);
-    p.idx = ctx->d_rn_idx.ptr; p.rgbf = ctx->d_rn_rgbf.ptr;
-    p.records = cur.records.ptr; p.normals = ctx->d_nrm_out.ptr; p.light = ctx->d_sh_light.ptr;
-    p.out = ctx->d_sh_rgb.ptr;
+    p.idx = ctx->render.idx.ptr; p.rgbf = ctx->render.rgbf.ptr;
+    p.records = cur.records.ptr; p.normals = ctx->normals.out.ptr; p.light = ctx->normals.sh_light.ptr;
+    p.out = ctx->normals.sh_rgb.ptr;
     p.S = ctx->survivors; p.npix = npix; p.view_pix = view_pix; p.ambient = ambient;
     hipLaunchKernelGGL(k_shade, dim3((uint32_t)((npix + kNrmBlock - 1) / kNrmBlock)), dim3(kNrmBlock), 0, ctx->stream, p);
     VC_HIP(ctx, hipGetLastError());
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));             // (the lights are the caller's memory)
-    ctx->sh_valid = true;
+    ctx->normals.sh_valid = true;
     return VC_OK;
 }
 
 int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb)
 {
     if (!ctx || !rgb) return VC_ERR_ARG;
-    if (!ctx->rn_valid || !ctx->sh_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: no shaded images: call vc_shade_render first");
-    if (view >= ctx->rn_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: view %u not in [0,%u)", view, ctx->rn_views);
+    if (!ctx->render.valid || !ctx->normals.sh_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: no shaded images: call vc_shade_render first");
+    if (view >= ctx->render.n_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: view %u not in [0,%u)", view, ctx->render.n_views);
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->rn_H * ctx->rn_W, off = (size_t)view * HW;
+    const size_t HW = (size_t)ctx->render.H * ctx->render.W, off = (size_t)view * HW;
     std::vector<uint32_t> px(HW);
-    VC_HIP(ctx, hipMemcpy(px.data(), ctx->d_sh_rgb.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VC_HIP(ctx, hipMemcpy(px.data(), ctx->normals.sh_rgb.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < HW; ++k) {
         const uint32_t q = px[k];
         rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16);
@@ -3580,20 +3538,20 @@ int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb)
 int vc_surface_normals(vc_ctx *ctx, int16_t *n4)
 {
     if (!ctx || !n4) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->nrm_valid) return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no normals: call vc_hull_normals on the current carve result");
-    if (!ctx->sf_valid || !ctx->sf_current)
+    if (!ctx->carved || !ctx->current(ctx->normals.stamp)) return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no normals: call vc_hull_normals on the current carve result");
+    if (!ctx->surface.valid || !ctx->current(ctx->surface.stamp))
         return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no mesh of the current carve result: call vc_surface_mesh first");
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    const uint64_t V = ctx->sf_verts;
+    const uint64_t V = ctx->surface.n_verts;
     if (!V) return VC_OK;
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(ensure(ctx, ctx->d_nrm_verts, (size_t)V));
+    VC_TRY(ensure(ctx, ctx->normals.verts, (size_t)V));
     hipLaunchKernelGGL(k_surf_normals, dim3((uint32_t)((V + kNrmBlock - 1) / kNrmBlock)), dim3(kNrmBlock), 0, ctx->stream,
-                       (const uint64_t *)ctx->d_sf_edges.ptr, V, (const uint64_t *)cur.records.ptr, ctx->survivors,
-                       (const short4 *)ctx->d_nrm_out.ptr, ctx->nx, ctx->ny, ctx->d_nrm_verts.ptr);
+                       (const uint64_t *)ctx->surface.edges.ptr, V, (const uint64_t *)cur.records.ptr, ctx->survivors,
+                       (const short4 *)ctx->normals.out.ptr, ctx->nx, ctx->ny, ctx->normals.verts.ptr);
     VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipMemcpyAsync(n4, ctx->d_nrm_verts.ptr, (size_t)V * sizeof(short4), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(n4, ctx->normals.verts.ptr, (size_t)V * sizeof(short4), hipMemcpyDeviceToHost, ctx->stream));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VC_OK;
 }
@@ -3611,7 +3569,8 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
     if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: stats must not be NULL");
     memset(stats, 0, sizeof *stats);
     if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: flags must be 0 (got %u)", flags);
-    VC_TRY(result_refusals(ctx, "vc_hull_clusters", "label", "clustering"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_clusters", "label", "clustering", pass));
     if (K < 1 || K > kClMaxK) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: K = %u not in [1, %u]", K, kClMaxK);
     if (max_iters < 1 || max_iters > 255) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: max_iters %u not in [1, 255]", max_iters);
     if (hist_iz_lo > hist_iz_hi || hist_iz_hi >= ctx->nz)
@@ -3623,53 +3582,50 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
                 return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: init centre %u has %c = %lld um, beyond +-2^30", k / 2, "xy"[k & 1], (long long)init[k]);
     uint64_t q[2];
     VC_TRY(dist_metric(ctx, "vc_hull_clusters", q, 2));
-    const uint64_t S = ctx->survivors, n = ctx->n_voxels(), ncol64 = (uint64_t)ctx->nx * ctx->ny;
+    const uint64_t S = pass.S, n = pass.n, ncol64 = (uint64_t)ctx->nx * ctx->ny;
     if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: %llu voxels exceed the u32 index", (unsigned long long)n);
     const uint32_t ncol = (uint32_t)ncol64;
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->cl_valid = false;
-    if (!ctx->h_cl) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_cl), (kClAccTotal + kClHostBox) * sizeof(uint64_t), hipHostMallocDefault));
-    VC_TRY(ensure(ctx, ctx->d_cl_fmap, (size_t)ncol));
-    VC_TRY(ensure(ctx, ctx->d_cl_flab, (size_t)ncol));
-    VC_TRY(ensure(ctx, ctx->d_cl_lab, (size_t)S));
-    VC_TRY(ensure(ctx, ctx->d_cl_hist, (size_t)kClMaxK * kClBins));
-    VC_TRY(ensure(ctx, ctx->d_cl_box, (size_t)kClMaxK * 6));
-    VC_TRY(ensure(ctx, ctx->d_cl_seed, (size_t)kClMaxK));
-    VC_TRY(ensure(ctx, ctx->d_cl_acc, (size_t)kClAccTotal));
-    uint32_t *blo = ctx->d_cl_box.ptr, *bhi = blo + kClMaxK * 3;
-    uint64_t *h = ctx->h_cl;
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_fmap.ptr, 0, (size_t)ncol * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_flab.ptr, 0xff, (size_t)ncol, ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_hist.ptr, 0, (size_t)kClMaxK * kClBins * sizeof(uint32_t), ctx->stream));
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    ctx->clusters.stamp = kNever;
+    VC_HIP(ctx, ensure_pinned(ctx->clusters.h, kClAccTotal + kClHostBox));
+    VC_TRY(ensure(ctx, ctx->clusters.fmap, (size_t)ncol));
+    VC_TRY(ensure(ctx, ctx->clusters.flab, (size_t)ncol));
+    VC_TRY(ensure(ctx, ctx->clusters.lab, (size_t)S));
+    VC_TRY(ensure(ctx, ctx->clusters.hist, (size_t)kClMaxK * kClBins));
+    VC_TRY(ensure(ctx, ctx->clusters.box, (size_t)kClMaxK * 6));
+    VC_TRY(ensure(ctx, ctx->clusters.seed, (size_t)kClMaxK));
+    VC_TRY(ensure(ctx, ctx->clusters.acc, (size_t)kClAccTotal));
+    uint32_t *blo = ctx->clusters.box.ptr, *bhi = blo + kClMaxK * 3;
+    uint64_t *h = ctx->clusters.h;
+    VC_TRY(pass_start(ctx, pass, kWordsLater));     // (only the floor map made from the occupancy reads the words)
+    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.fmap.ptr, 0, (size_t)ncol * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.flab.ptr, 0xff, (size_t)ncol, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.hist.ptr, 0, (size_t)kClMaxK * kClBins * sizeof(uint32_t), ctx->stream));
     VC_HIP(ctx, hipMemsetAsync(blo, 0xff, (size_t)kClMaxK * 3 * sizeof(uint32_t), ctx->stream));
     VC_HIP(ctx, hipMemsetAsync(bhi, 0, (size_t)kClMaxK * 3 * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_seed.ptr, 0xff, (size_t)kClMaxK * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->d_cl_acc.ptr, 0, (size_t)kClAccTotal * sizeof(uint64_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.seed.ptr, 0xff, (size_t)kClMaxK * sizeof(uint32_t), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.acc.ptr, 0, (size_t)kClAccTotal * sizeof(uint64_t), ctx->stream));
     ClCols cols;
     memset(&cols, 0, sizeof cols);
-    cols.fmap = ctx->d_cl_fmap.ptr; cols.ncol = ncol; cols.ny = ctx->ny; cols.min_column = min_column;
+    cols.fmap = ctx->clusters.fmap.ptr; cols.ncol = ncol; cols.ny = ctx->ny; cols.min_column = min_column;
     cols.qx = (long long)q[0]; cols.qy = (long long)q[1];
     const dim3 block(kClBlock);
     const uint64_t cblocks = (ncol64 + kClBlock - 1) / kClBlock;
     const dim3 cgrid((uint32_t)(cblocks < kClMaxBlocks ? cblocks : kClMaxBlocks));
-    unsigned long long *acc = ctx->d_cl_acc.ptr;
+    unsigned long long *acc = ctx->clusters.acc.ptr;
     memset(h, 0, (kClAccTotal + kClHostBox) * sizeof(uint64_t));
     if (S) {
         // item 2: the floor map and its moments
-        if (ctx->cluster_floor_records) {
+        if (ctx->clusters.floor_records) {
             hipLaunchKernelGGL(k_cl_floor_records, dim3((uint32_t)((S + kClBlock - 1) / kClBlock)), block, 0, ctx->stream,
-                               (const uint64_t *)cur.records.ptr, S, ncol, ctx->d_cl_fmap.ptr);
+                               (const uint64_t *)cur.records.ptr, S, ncol, ctx->clusters.fmap.ptr);
         } else {
             VC_TRY(densify_words(ctx, cur));
             const uint32_t ngroups = (uint32_t)((ncol64 + 63) / 64), nchunks = (ctx->nz + kClLayers - 1) / kClLayers;
             const uint64_t waves = (uint64_t)ngroups * nchunks;
             hipLaunchKernelGGL(k_cl_floor, dim3((uint32_t)((waves + kClBlock / 64 - 1) / (kClBlock / 64))), block, 0, ctx->stream,
-                               (const uint64_t *)cur.words.ptr, (n + 63) / 64, ncol, ctx->nz, ngroups, nchunks, ctx->d_cl_fmap.ptr);
+                               (const uint64_t *)cur.words.ptr, pass.nwords, ncol, ctx->nz, ngroups, nchunks, ctx->clusters.fmap.ptr);
         }
         VC_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_cl_moments, cgrid, block, 0, ctx->stream, cols, acc);
@@ -3688,7 +3644,7 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
         // item 3: two launches per seed, the seeds' columns stay on the device until all are picked
         ClSeed sd;
         memset(&sd, 0, sizeof sd);
-        sd.seedcol = ctx->d_cl_seed.ptr; sd.pick = ctx->d_cl_seed.ptr; sd.best = acc + kClAccSeed;
+        sd.seedcol = ctx->clusters.seed.ptr; sd.pick = ctx->clusters.seed.ptr; sd.best = acc + kClAccSeed;
         sd.mx = (long long)((h[1] + Wtot / 2) / Wtot); sd.my = (long long)((h[2] + Wtot / 2) / Wtot);
         for (uint32_t j = 0; j < K; ++j) {
             sd.j = j;
@@ -3696,7 +3652,7 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
             hipLaunchKernelGGL(k_cl_seed_pick, cgrid, block, 0, ctx->stream, cols, sd);
             VC_HIP(ctx, hipGetLastError());
         }
-        VC_HIP(ctx, hipMemcpyAsync(h + 4, ctx->d_cl_seed.ptr, kClMaxK * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        VC_HIP(ctx, hipMemcpyAsync(h + 4, ctx->clusters.seed.ptr, kClMaxK * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const uint32_t *sc = reinterpret_cast<const uint32_t *>(h + 4);
         for (uint32_t k = 0; k < K; ++k) {
@@ -3712,7 +3668,7 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
     while (Wtot && r < max_iters) {
         ++r;
         VC_HIP(ctx, hipMemsetAsync(acc + kClAccRound, 0, kClMaxK * kClAcc * sizeof(uint64_t), ctx->stream));
-        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, K, c, ctx->d_cl_flab.ptr, acc + kClAccRound);
+        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, K, c, ctx->clusters.flab.ptr, acc + kClAccRound);
         VC_HIP(ctx, hipGetLastError());
         VC_HIP(ctx, hipMemcpyAsync(hr, acc + kClAccRound, kClMaxK * kClAcc * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3730,17 +3686,17 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
     if (S && !Wtot) {
         // no column reaches min_column: no rounds, every record takes label 0 (one cluster's launch; its weights are zero)
         VC_HIP(ctx, hipMemsetAsync(acc + kClAccRound, 0, kClMaxK * kClAcc * sizeof(uint64_t), ctx->stream));
-        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, 1u, c, ctx->d_cl_flab.ptr, acc + kClAccRound);
+        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, 1u, c, ctx->clusters.flab.ptr, acc + kClAccRound);
         VC_HIP(ctx, hipGetLastError());
         VC_HIP(ctx, hipMemcpyAsync(hr, acc + kClAccRound, kClMaxK * kClAcc * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     if (S) {
         // item 5: voxels and boxes from the columns, labels, histograms and iz ranges from the records
-        hipLaunchKernelGGL(k_cl_columns, cgrid, block, 0, ctx->stream, cols, K, (const uint8_t *)ctx->d_cl_flab.ptr, acc + kClAccVoxels, blo, bhi);
+        hipLaunchKernelGGL(k_cl_columns, cgrid, block, 0, ctx->stream, cols, K, (const uint8_t *)ctx->clusters.flab.ptr, acc + kClAccVoxels, blo, bhi);
         VC_HIP(ctx, hipGetLastError());
         ClRecords p;
         memset(&p, 0, sizeof p);
-        p.records = cur.records.ptr; p.flab = ctx->d_cl_flab.ptr; p.lab = ctx->d_cl_lab.ptr; p.hist = ctx->d_cl_hist.ptr;
+        p.records = cur.records.ptr; p.flab = ctx->clusters.flab.ptr; p.lab = ctx->clusters.lab.ptr; p.hist = ctx->clusters.hist.ptr;
         p.blo = blo; p.bhi = bhi;
         p.S = S; p.ncol = ncol; p.K = K; p.zlo = hist_iz_lo; p.zhi = hist_iz_hi;
         const uint64_t rblocks = (S + kClBlock - 1) / kClBlock, rgrid = rblocks < kClMaxBlocks ? rblocks : kClMaxBlocks;
@@ -3750,14 +3706,12 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
         VC_HIP(ctx, hipMemcpyAsync(h + kClAccVoxels, acc + kClAccVoxels, kClMaxK * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipMemcpyAsync(h + kClAccTotal, blo, kClMaxK * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    VC_HIP(ctx, hipEventElapsedTime(&stats->clusters_ms, ctx->ev[0], ctx->ev[1]));
+    VC_TRY(pass_end(ctx, pass, &stats->clusters_ms));
     const uint32_t *hb = reinterpret_cast<const uint32_t *>(h + kClAccTotal);     // lo [kClMaxK][3], hi [kClMaxK][3] (zeros when S = 0)
-    ctx->cl_out.assign(K, vc_cluster_t{});
+    ctx->clusters.out.assign(K, vc_cluster_t{});
     uint64_t labelled = 0;
     for (uint32_t k = 0; k < K; ++k) {
-        vc_cluster_t &o = ctx->cl_out[k];
+        vc_cluster_t &o = ctx->clusters.out[k];
         o.centre_um[0] = c.c[k][0]; o.centre_um[1] = c.c[k][1];
         o.voxels = S ? h[kClAccVoxels + k] : 0;
         o.weight = hr[kClAcc * k];
@@ -3777,15 +3731,15 @@ int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_c
     stats->iterations = r;
     stats->converged = converged ? 1u : 0u;
     stats->q[0] = q[0]; stats->q[1] = q[1];
-    ctx->cl_valid = true;
-    ctx->cl_n = S; ctx->cl_k = K; ctx->cl_ncol = ncol;
+    ctx->clusters.stamp = ctx->result_gen;
+    ctx->clusters.n = S; ctx->clusters.k = K; ctx->clusters.ncol = ncol;
     return VC_OK;
 }
 
 // The refusal the fetch calls and vc_paint_clusters share.
 static int clusters_current(vc_ctx *ctx)
 {
-    if (!ctx->carved || !ctx->cl_valid) return fail(ctx, VC_ERR_ARG, "no clusters: call vc_hull_clusters on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->clusters.stamp)) return fail(ctx, VC_ERR_ARG, "no clusters: call vc_hull_clusters on the current carve result");
     return VC_OK;
 }
 
@@ -3795,7 +3749,7 @@ int vc_fetch_cluster_labels(vc_ctx *ctx, uint8_t *labels)
     VC_TRY(clusters_current(ctx));
     if (!labels) return VC_OK;                   // only asked whether the clustering is valid
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->cl_n) VC_HIP(ctx, hipMemcpy(labels, ctx->d_cl_lab.ptr, (size_t)ctx->cl_n, hipMemcpyDeviceToHost));
+    if (ctx->clusters.n) VC_HIP(ctx, hipMemcpy(labels, ctx->clusters.lab.ptr, (size_t)ctx->clusters.n, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3803,7 +3757,7 @@ int vc_fetch_clusters(vc_ctx *ctx, vc_cluster_t *out)
 {
     if (!ctx || !out) return VC_ERR_ARG;
     VC_TRY(clusters_current(ctx));
-    memcpy(out, ctx->cl_out.data(), ctx->cl_out.size() * sizeof(vc_cluster_t));
+    memcpy(out, ctx->clusters.out.data(), ctx->clusters.out.size() * sizeof(vc_cluster_t));
     return VC_OK;
 }
 
@@ -3812,7 +3766,7 @@ int vc_fetch_cluster_histograms(vc_ctx *ctx, uint32_t *hist)
     if (!ctx || !hist) return VC_ERR_ARG;
     VC_TRY(clusters_current(ctx));
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(hist, ctx->d_cl_hist.ptr, (size_t)ctx->cl_k * kClBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VC_HIP(ctx, hipMemcpy(hist, ctx->clusters.hist.ptr, (size_t)ctx->clusters.k * kClBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3821,7 +3775,7 @@ int vc_fetch_floor_map(vc_ctx *ctx, uint32_t *n)
     if (!ctx || !n) return VC_ERR_ARG;
     VC_TRY(clusters_current(ctx));
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(n, ctx->d_cl_fmap.ptr, (size_t)ctx->cl_ncol * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    VC_HIP(ctx, hipMemcpy(n, ctx->clusters.fmap.ptr, (size_t)ctx->clusters.ncol * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3830,7 +3784,7 @@ int vc_fetch_floor_labels(vc_ctx *ctx, uint8_t *labels)
     if (!ctx || !labels) return VC_ERR_ARG;
     VC_TRY(clusters_current(ctx));
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(labels, ctx->d_cl_flab.ptr, (size_t)ctx->cl_ncol, hipMemcpyDeviceToHost));
+    VC_HIP(ctx, hipMemcpy(labels, ctx->clusters.flab.ptr, (size_t)ctx->clusters.ncol, hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3840,14 +3794,14 @@ int vc_paint_clusters(vc_ctx *ctx, const uint8_t *rgb)
     if (!rgb) return fail(ctx, VC_ERR_ARG, "vc_paint_clusters: no palette");
     VC_TRY(clusters_current(ctx));
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->cl_n) return VC_OK;
+    if (!ctx->clusters.n) return VC_OK;
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     ClPalette pal;
     memset(&pal, 0, sizeof pal);
-    for (uint32_t k = 0; k < ctx->cl_k; ++k) pal.rgb[k] = (uint32_t)rgb[3 * k] | ((uint32_t)rgb[3 * k + 1] << 8) | ((uint32_t)rgb[3 * k + 2] << 16);
-    hipLaunchKernelGGL(k_cl_paint, dim3((uint32_t)((ctx->cl_n + kClBlock - 1) / kClBlock)), dim3(kClBlock), 0, ctx->stream, cur.records.ptr,
-                       ctx->cl_n, (const uint8_t *)ctx->d_cl_lab.ptr, pal);
+    for (uint32_t k = 0; k < ctx->clusters.k; ++k) pal.rgb[k] = (uint32_t)rgb[3 * k] | ((uint32_t)rgb[3 * k + 1] << 8) | ((uint32_t)rgb[3 * k + 2] << 16);
+    hipLaunchKernelGGL(k_cl_paint, dim3((uint32_t)((ctx->clusters.n + kClBlock - 1) / kClBlock)), dim3(kClBlock), 0, ctx->stream, cur.records.ptr,
+                       ctx->clusters.n, (const uint8_t *)ctx->clusters.lab.ptr, pal);
     VC_HIP(ctx, hipGetLastError());
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VC_OK;
@@ -3875,10 +3829,10 @@ static uint64_t geo_edge_um(uint64_t s)
 // Relaxes from the keys as they are until nothing falls.  Tile route: list 0 holds n0 tiles.  Counts into stats.
 static int geo_relax(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint32_t n0, vc_geodesic_stats_t *stats)
 {
-    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->h_geo + 8);
+    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->geodesic.h + 8);
     const dim3 block(kGeoBlock);
     uint64_t rounds = 0;
-    if (ctx->geodesic_tiles) {
+    if (ctx->geodesic.tiles) {
         uint32_t par = 0, n = n0;
         while (n) {
             if (++rounds > p.S + 1) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_geodesic: the tiles have not settled after %llu rounds", (unsigned long long)(p.S + 1));
@@ -3898,7 +3852,7 @@ static int geo_relax(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uin
         // (both lists are empty and every flag is clear: the next relaxation starts at parity 0 again)
     } else {
         const dim3 sgrid((uint32_t)((p.S + kGeoBlock - 1) / kGeoBlock));
-        uint32_t *flag = ctx->d_geo_cnt.ptr + kGeoCntFlag;
+        uint32_t *flag = ctx->geodesic.cnt.ptr + kGeoCntFlag;
         for (;;) {
             if (++rounds > p.S + 1) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_geodesic: the sweeps have not settled after %llu rounds", (unsigned long long)(p.S + 1));
             VC_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(uint32_t), ctx->stream));
@@ -3922,13 +3876,13 @@ static int geo_relax(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uin
 // status = kGeoPath*.
 static int geo_walk(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint32_t voxel, std::vector<uint32_t> &out, uint32_t &status)
 {
-    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->h_geo + 8);
-    uint32_t *res = ctx->d_geo_cnt.ptr + kGeoCntPath;
+    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->geodesic.h + 8);
+    uint32_t *res = ctx->geodesic.cnt.ptr + kGeoCntPath;
     const uint64_t hops = (uint64_t)p.nx + p.ny + p.nz;
     uint64_t cap = hops < p.S ? hops : p.S;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        VC_TRY(ensure(ctx, ctx->d_geo_path, (size_t)(cap ? cap : 1)));
-        hipLaunchKernelGGL(k_geo_path, dim3(1), dim3(64), 0, ctx->stream, p, connectivity, voxel, ctx->d_geo_path.ptr, (uint32_t)cap, p.S, res);
+        VC_TRY(ensure(ctx, ctx->geodesic.path, (size_t)(cap ? cap : 1)));
+        hipLaunchKernelGGL(k_geo_path, dim3(1), dim3(64), 0, ctx->stream, p, connectivity, voxel, ctx->geodesic.path.ptr, (uint32_t)cap, p.S, res);
         VC_HIP(ctx, hipGetLastError());
         VC_HIP(ctx, hipMemcpyAsync(hc, res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3940,7 +3894,7 @@ static int geo_walk(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint
         cap = hc[0];
     }
     out.resize(hc[0]);
-    if (hc[0]) VC_HIP(ctx, hipMemcpy(out.data(), ctx->d_geo_path.ptr, (size_t)hc[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hc[0]) VC_HIP(ctx, hipMemcpy(out.data(), ctx->geodesic.path.ptr, (size_t)hc[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -3953,27 +3907,25 @@ int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, con
     if (flags & ~VC_GEO_PATHS) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: unknown flags %u (VC_GEO_PATHS)", flags);
     if (connectivity != 6 && connectivity != 18 && connectivity != 26)
         return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: connectivity %u, expected 6, 18 or 26", connectivity);
-    VC_TRY(result_refusals(ctx, "vc_hull_geodesic", "measure", "geodesic distances"));
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_geodesic", "measure", "geodesic distances", pass));
     if (K > VC_GEO_MAX_K) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: K = %u not in [0, %d]", K, VC_GEO_MAX_K);
     if (seed_mode > VC_GEO_SEEDS_IZ_MIN) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed mode %u, expected 0 (list), 1 (iz max) or 2 (iz min)", seed_mode);
     if (seed_mode == VC_GEO_SEEDS_LIST && n_seeds && !seeds) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu seeds and no list", (unsigned long long)n_seeds);
     if (seed_mode != VC_GEO_SEEDS_LIST && layers < 1) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: layers = 0, a layer mode seeds at least one");
     uint64_t q[3];
     VC_TRY(dist_metric(ctx, "vc_hull_geodesic", q));
-    const uint64_t S = ctx->survivors, n = ctx->n_voxels();
+    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
     if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu voxels exceed the u32 index", (unsigned long long)n);
     if (seed_mode != VC_GEO_SEEDS_LIST) n_seeds = 0;
     if (!S && n_seeds) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed 0 (voxel %u) is no survivor", seeds[0]);
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(finish_gather(ctx));                  // (a compact gather of a one-rank communicator may still read the words)
-    ctx->geo_valid = false;
-    ctx->dist_ev_kind.clear();
-    ctx->geo_ext.clear();
-    ctx->geo_paths.clear();
-    if (!ctx->h_res) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_res), 3 * sizeof(uint64_t), hipHostMallocDefault));
-    if (!ctx->h_geo) VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_geo), 12 * sizeof(uint64_t), hipHostMallocDefault));
-    uint64_t *h = ctx->h_geo;
+    StepBuf &cur = *pass.cur;
+    VC_TRY(pass_begin(ctx));
+    ctx->geodesic.stamp = kNever;
+    ctx->geodesic.ext.clear();
+    ctx->geodesic.paths.clear();
+    VC_HIP(ctx, ensure_pinned(ctx->geodesic.h, 12));
+    uint64_t *h = ctx->geodesic.h;
     uint32_t *hc = reinterpret_cast<uint32_t *>(h + 8);
     memset(h, 0, 12 * sizeof(uint64_t));
     stats->survivors = S;
@@ -3985,23 +3937,12 @@ int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, con
         stats->edge_um[m - 1] = geo_edge_um(s2);
         p.w8[m] = (unsigned long long)stats->edge_um[m - 1] << 8;
     }
-    // behind the step's record expansion (the second stream when overlap = 1; vc_carve_end has waited for it, this says so on the device)
-    if (S && cur.n) VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, cur.e2, 0));
-    VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    VC_TRY(pass_start(ctx, pass));
     if (S) {
-        const uint64_t nwords = (n + 63) / 64;
-        VC_TRY(densify_words(ctx, cur));
         // survivors before each word, as vc_hull_components counts them
-        const uint32_t wgroups = (uint32_t)((nwords + 63) / 64);
-        VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
-        VC_TRY(ensure(ctx, ctx->d_geo_woff, (size_t)nwords));
-        const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), cblock(kCcBlock);
-        hipLaunchKernelGGL(k_cc_wcount, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups, ctx->d_rscan.cnt.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, h + 10));          // (the total is not read; h_res holds the box next)
-        hipLaunchKernelGGL(k_cc_woff, wgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, wgroups,
-                           (const uint32_t *)ctx->d_rscan.off.ptr, (const uint64_t *)ctx->d_rscan.boff.ptr, ctx->d_geo_woff.ptr);
-        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
+        VC_TRY(ensure(ctx, ctx->geodesic.woff, (size_t)nwords));
+        VC_TRY(word_offsets(ctx, cur, nwords, ctx->geodesic.woff, h + 10));      // (the total is not read; h_res holds the box next)
         // the survivors' box: the tiles are laid from its low corner, the layer modes seed from its iz range
         uint32_t *hb = nullptr;
         VC_TRY(dist_survivor_box(ctx, cur, S, hb));
@@ -4016,31 +3957,31 @@ int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, con
         stats->tiles = tiles;
         if (tiles > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu tiles exceed the u32 index", (unsigned long long)tiles);
         p.tiles = (uint32_t)tiles;
-        VC_TRY(ensure(ctx, ctx->d_geo_key, (size_t)S));
-        VC_TRY(ensure(ctx, ctx->d_geo_acc, kGeoAccTotal));
-        VC_TRY(ensure(ctx, ctx->d_geo_cnt, kGeoCntTotal));
-        VC_TRY(ensure(ctx, ctx->d_geo_flag, (size_t)(2 * tiles)));
-        VC_TRY(ensure(ctx, ctx->d_geo_list, (size_t)(2 * tiles)));
-        if (n_seeds) VC_TRY(ensure(ctx, ctx->d_geo_seeds, (size_t)n_seeds));
-        p.records = cur.records.ptr; p.words = cur.words.ptr; p.woff = ctx->d_geo_woff.ptr; p.key = ctx->d_geo_key.ptr;
+        VC_TRY(ensure(ctx, ctx->geodesic.key, (size_t)S));
+        VC_TRY(ensure(ctx, ctx->geodesic.acc, kGeoAccTotal));
+        VC_TRY(ensure(ctx, ctx->geodesic.cnt, kGeoCntTotal));
+        VC_TRY(ensure(ctx, ctx->geodesic.flag, (size_t)(2 * tiles)));
+        VC_TRY(ensure(ctx, ctx->geodesic.list, (size_t)(2 * tiles)));
+        if (n_seeds) VC_TRY(ensure(ctx, ctx->geodesic.seeds, (size_t)n_seeds));
+        p.records = cur.records.ptr; p.words = cur.words.ptr; p.woff = ctx->geodesic.woff.ptr; p.key = ctx->geodesic.key.ptr;
         p.S = S; p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
-        p.flag[0] = ctx->d_geo_flag.ptr; p.flag[1] = ctx->d_geo_flag.ptr + tiles;
-        p.list[0] = ctx->d_geo_list.ptr; p.list[1] = ctx->d_geo_list.ptr + tiles;
-        p.count = ctx->d_geo_cnt.ptr;
-        unsigned long long *acc = ctx->d_geo_acc.ptr;
-        uint32_t *pick = ctx->d_geo_cnt.ptr + kGeoCntPick;
+        p.flag[0] = ctx->geodesic.flag.ptr; p.flag[1] = ctx->geodesic.flag.ptr + tiles;
+        p.list[0] = ctx->geodesic.list.ptr; p.list[1] = ctx->geodesic.list.ptr + tiles;
+        p.count = ctx->geodesic.cnt.ptr;
+        unsigned long long *acc = ctx->geodesic.acc.ptr;
+        uint32_t *pick = ctx->geodesic.cnt.ptr + kGeoCntPick;
         VC_HIP(ctx, hipMemsetAsync(p.key, 0xff, (size_t)S * sizeof(uint64_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_geo_flag.ptr, 0, (size_t)(2 * tiles) * sizeof(uint32_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_geo_cnt.ptr, 0, kGeoCntTotal * sizeof(uint32_t), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->geodesic.flag.ptr, 0, (size_t)(2 * tiles) * sizeof(uint32_t), ctx->stream));
+        VC_HIP(ctx, hipMemsetAsync(ctx->geodesic.cnt.ptr, 0, kGeoCntTotal * sizeof(uint32_t), ctx->stream));
         VC_HIP(ctx, hipMemsetAsync(acc, 0, kGeoAccTotal * sizeof(uint64_t), ctx->stream));
         VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBad, 0xff, sizeof(uint64_t), ctx->stream));
         const dim3 block(kGeoBlock);
         // item 2: the seed set
         if (seed_mode == VC_GEO_SEEDS_LIST) {
             if (n_seeds) {
-                VC_HIP(ctx, hipMemcpyAsync(ctx->d_geo_seeds.ptr, seeds, (size_t)n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+                VC_HIP(ctx, hipMemcpyAsync(ctx->geodesic.seeds.ptr, seeds, (size_t)n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
                 VC_DLAUNCH(VC_K_GEO_SEED, k_geo_seed_list, dim3((uint32_t)((n_seeds + kGeoBlock - 1) / kGeoBlock)), block, p,
-                           (const uint32_t *)ctx->d_geo_seeds.ptr, n_seeds, n, acc + kGeoAccSeeds);
+                           (const uint32_t *)ctx->geodesic.seeds.ptr, n_seeds, n, acc + kGeoAccSeeds);
             }
         } else {
             const uint32_t span = layers - 1 < zhi - zlo ? layers - 1 : zhi - zlo;
@@ -4094,8 +4035,8 @@ int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, con
             memset(&e, 0, sizeof e);
             e.d = d; e.voxel = voxel; e.record = rec; e.label = k;
             e.iy = voxel % ctx->ny; e.ix = (voxel / ctx->ny) % ctx->nx; e.iz = voxel / (ctx->ny * ctx->nx);
-            ctx->geo_ext.push_back(e);
-            if (flags & VC_GEO_PATHS) ctx->geo_paths.push_back(std::move(way));
+            ctx->geodesic.ext.push_back(e);
+            if (flags & VC_GEO_PATHS) ctx->geodesic.paths.push_back(std::move(way));
             VC_TRY(geo_relax(ctx, p, connectivity, hc[0], stats));
         }
         VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBest, 0, 2 * sizeof(uint64_t), ctx->stream));
@@ -4103,25 +4044,22 @@ int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, con
         VC_HIP(ctx, hipGetLastError());
         VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccBest, acc + kGeoAccBest, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    VC_HIP(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    dist_harvest(ctx);
-    VC_HIP(ctx, hipEventElapsedTime(&stats->geodesic_ms, ctx->ev[0], ctx->ev[1]));
+    VC_TRY(pass_end(ctx, pass, &stats->geodesic_ms));
     if (h[kGeoAccBest + 1] > S) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %llu reached of %llu survivors", (unsigned long long)h[kGeoAccBest + 1], (unsigned long long)S);
     stats->max_d = S ? h[kGeoAccBest] : 0;
     stats->reached = S ? h[kGeoAccBest + 1] : 0;
     stats->unreached = S - stats->reached;
-    stats->extremities = (uint32_t)ctx->geo_ext.size();
-    ctx->geo_p = p;
-    ctx->geo_valid = true;
-    ctx->geo_n = S; ctx->geo_max_d = stats->max_d; ctx->geo_conn = connectivity;
+    stats->extremities = (uint32_t)ctx->geodesic.ext.size();
+    ctx->geodesic.p = p;
+    ctx->geodesic.stamp = ctx->result_gen;
+    ctx->geodesic.n = S; ctx->geodesic.max_d = stats->max_d; ctx->geodesic.conn = connectivity;
     return VC_OK;
 }
 
 // The refusal the readers of the geodesic outputs share.
 static int geodesic_current(vc_ctx *ctx)
 {
-    if (!ctx->carved || !ctx->geo_valid) return fail(ctx, VC_ERR_ARG, "no geodesic distances: call vc_hull_geodesic on the current carve result");
+    if (!ctx->carved || !ctx->current(ctx->geodesic.stamp)) return fail(ctx, VC_ERR_ARG, "no geodesic distances: call vc_hull_geodesic on the current carve result");
     return VC_OK;
 }
 
@@ -4129,8 +4067,8 @@ static int geodesic_current(vc_ctx *ctx)
 static int geo_fetch_keys(vc_ctx *ctx, std::vector<uint64_t> &keys)
 {
     VC_HIP(ctx, hipSetDevice(ctx->device));
-    keys.resize((size_t)ctx->geo_n);
-    if (ctx->geo_n) VC_HIP(ctx, hipMemcpy(keys.data(), ctx->d_geo_key.ptr, (size_t)ctx->geo_n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    keys.resize((size_t)ctx->geodesic.n);
+    if (ctx->geodesic.n) VC_HIP(ctx, hipMemcpy(keys.data(), ctx->geodesic.key.ptr, (size_t)ctx->geodesic.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
 
@@ -4159,9 +4097,9 @@ int vc_fetch_extrema(vc_ctx *ctx, vc_extremum_t *out)
 {
     if (!ctx) return VC_ERR_ARG;
     VC_TRY(geodesic_current(ctx));
-    if (!ctx->geo_ext.empty()) {
+    if (!ctx->geodesic.ext.empty()) {
         if (!out) return VC_ERR_ARG;
-        memcpy(out, ctx->geo_ext.data(), ctx->geo_ext.size() * sizeof(vc_extremum_t));
+        memcpy(out, ctx->geodesic.ext.data(), ctx->geodesic.ext.size() * sizeof(vc_extremum_t));
     }
     return VC_OK;
 }
@@ -4184,11 +4122,11 @@ int vc_geodesic_path(vc_ctx *ctx, uint32_t voxel, uint32_t *out, uint32_t capaci
     *n = 0;
     VC_TRY(geodesic_current(ctx));
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if ((uint64_t)voxel >= ctx->n_voxels() || !ctx->geo_n) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
+    if ((uint64_t)voxel >= ctx->n_voxels() || !ctx->geodesic.n) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
     VC_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> way;
     uint32_t status = kGeoPathOk;
-    VC_TRY(geo_walk(ctx, ctx->geo_p, ctx->geo_conn, voxel, way, status));
+    VC_TRY(geo_walk(ctx, ctx->geodesic.p, ctx->geodesic.conn, voxel, way, status));
     if (status == kGeoPathNoSurvivor) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
     if (status == kGeoPathUnreached) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is unreached", voxel);
     if (status != kGeoPathOk) return fail(ctx, VC_ERR_HIP, "vc_geodesic_path: the walk from voxel %u found no next voxel", voxel);
@@ -4200,10 +4138,10 @@ int vc_fetch_extremum_path(vc_ctx *ctx, uint32_t k, uint32_t *out, uint32_t capa
     if (!ctx || !n) return VC_ERR_ARG;
     *n = 0;
     VC_TRY(geodesic_current(ctx));
-    if (ctx->geo_paths.size() != ctx->geo_ext.size() || (ctx->geo_ext.size() && ctx->geo_paths.empty()))
+    if (ctx->geodesic.paths.size() != ctx->geodesic.ext.size() || (ctx->geodesic.ext.size() && ctx->geodesic.paths.empty()))
         return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: vc_hull_geodesic ran without VC_GEO_PATHS");
-    if (k < 1 || k > ctx->geo_paths.size()) return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: k = %u not in [1, %zu]", k, ctx->geo_paths.size());
-    return geo_path_out(ctx, "vc_fetch_extremum_path", ctx->geo_paths[k - 1], out, capacity, n);
+    if (k < 1 || k > ctx->geodesic.paths.size()) return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: k = %u not in [1, %zu]", k, ctx->geodesic.paths.size());
+    return geo_path_out(ctx, "vc_fetch_extremum_path", ctx->geodesic.paths[k - 1], out, capacity, n);
 }
 
 int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette)
@@ -4213,7 +4151,7 @@ int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette)
     if (mode == VC_GEO_PAINT_LABELS && !palette) return fail(ctx, VC_ERR_ARG, "vc_paint_geodesic: no palette");
     VC_TRY(geodesic_current(ctx));
     if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->geo_n) return VC_OK;
+    if (!ctx->geodesic.n) return VC_OK;
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
     GeoPalette pal;
@@ -4221,8 +4159,8 @@ int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette)
     if (palette)
         for (uint32_t k = 0; k <= kGeoMaxK; ++k) pal.rgb[k] = (uint32_t)palette[3 * k] | ((uint32_t)palette[3 * k + 1] << 8) | ((uint32_t)palette[3 * k + 2] << 16);
     const uint32_t none = (uint32_t)VC_GEO_UNREACHED_R | ((uint32_t)VC_GEO_UNREACHED_G << 8) | ((uint32_t)VC_GEO_UNREACHED_B << 16);
-    hipLaunchKernelGGL(k_geo_paint, dim3((uint32_t)((ctx->geo_n + kGeoBlock - 1) / kGeoBlock)), dim3(kGeoBlock), 0, ctx->stream, cur.records.ptr,
-                       ctx->geo_n, (const unsigned long long *)ctx->d_geo_key.ptr, mode, (unsigned long long)ctx->geo_max_d, none, pal);
+    hipLaunchKernelGGL(k_geo_paint, dim3((uint32_t)((ctx->geodesic.n + kGeoBlock - 1) / kGeoBlock)), dim3(kGeoBlock), 0, ctx->stream, cur.records.ptr,
+                       ctx->geodesic.n, (const unsigned long long *)ctx->geodesic.key.ptr, mode, (unsigned long long)ctx->geodesic.max_d, none, pal);
     VC_HIP(ctx, hipGetLastError());
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VC_OK;
@@ -4307,7 +4245,7 @@ int vc_mog_destroy(vc_ctx *ctx, uint32_t model)
     if (model >= VC_MAX_MOG_MODELS || !ctx->mog[model].used) return fail(ctx, VC_ERR_ARG, "no background model %u", model);
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream_up));
-    release(ctx->mog[model].state);
+    ctx->mog[model].state.reset();
     ctx->mog[model].used = false;
     return VC_OK;
 }
@@ -4389,8 +4327,8 @@ int vc_mog2_destroy(vc_ctx *ctx, uint32_t model)
     if (!m) return fail(ctx, VC_ERR_ARG, "no MOG2 background model %u", model);
     VC_HIP(ctx, hipSetDevice(ctx->device));
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream_up));
-    release(m->state);
-    release(m->nmodes);
+    m->state.reset();
+    m->nmodes.reset();
     m->used = false;
     return VC_OK;
 }
@@ -4615,7 +4553,7 @@ int vc_foreground_to_slot(vc_ctx *ctx, uint32_t slot, const uint32_t *models, ui
     // scratch: HSV image | model mask | morphology buffer | the C pre-filtered masks
     VC_TRY(ensure(ctx, ctx->d_fg, HW * (5 + C) + 64));
     uint8_t *d_hsv = ctx->d_fg.ptr, *ma = d_hsv + HW * 3, *mb = ma + HW, *pre = mb + HW;
-    VC_TRY(stage_upload(ctx, *s, &s->h_bgr_all, &s->h_bgr_all_cap, s->bgr_all.ptr, bgr, HW * 3 * C, false));
+    VC_TRY(stage_upload(ctx, *s, s->h_bgr_all, s->bgr_all.ptr, bgr, HW * 3 * C, false));
     const dim3 g((uint32_t)((HW + 255) / 256)), blk(256);
     for (uint32_t c = 0; c < C; ++c) {
         const uint8_t *img = s->bgr_all.ptr + HW * 3 * c;
@@ -4692,12 +4630,12 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
         (k == "stream_priority" ? ctx->stream_priority : ctx->reserve_cus) = value;
         VC_HIP(ctx, make_streams(ctx));
     }
-    else if (k == "visible_check") ctx->visible_check = value != 0;
-    else if (k == "visible_big_rect" && value >= 1) ctx->visible_big_rect = value;
-    else if (k == "render_blocks") ctx->render_blocks = value != 0;
-    else if (k == "surface_order") ctx->surface_order = value != 0;
-    else if (k == "cluster_floor_records") ctx->cluster_floor_records = value != 0;
-    else if (k == "geodesic_tiles") ctx->geodesic_tiles = value != 0;
+    else if (k == "visible_check") ctx->visible.check = value != 0;
+    else if (k == "visible_big_rect" && value >= 1) ctx->visible.big_rect = value;
+    else if (k == "render_blocks") ctx->render.blocks = value != 0;
+    else if (k == "surface_order") ctx->surface.order = value != 0;
+    else if (k == "cluster_floor_records") ctx->clusters.floor_records = value != 0;
+    else if (k == "geodesic_tiles") ctx->geodesic.tiles = value != 0;
     else if (k == "cull") ctx->cull = value != 0;
     else if (k == "bricks") ctx->bricks = value != 0;
     else if (k == "dbg") ctx->dbg = value;
@@ -4767,8 +4705,8 @@ int vc_timing(vc_ctx *ctx, vc_timing_t *out)
         for (int w = 0; w < VC_WORK_KINDS; ++w)
             for (uint32_t k = 0; k < kShards; ++k) ctx->tm.work[w] += h[((size_t)w * kShards + k) * kStatStride];
     }
-    ctx->tm.work[VC_WORK_DIST_CELLS] += ctx->dist_work[0];       // (counted on the host: the boxes are known there)
-    ctx->tm.work[VC_WORK_DIST_LINES] += ctx->dist_work[1];
+    ctx->tm.work[VC_WORK_DIST_CELLS] += ctx->distance.work[0];       // (counted on the host: the boxes are known there)
+    ctx->tm.work[VC_WORK_DIST_LINES] += ctx->distance.work[1];
     *out = ctx->tm;
     return VC_OK;
 }
@@ -4790,7 +4728,7 @@ int vc_timing_reset(vc_ctx *ctx)
     ctx->tm.emit_launches = 0;
     memset(ctx->tm.kernel_ms_sum, 0, sizeof ctx->tm.kernel_ms_sum);
     memset(ctx->tm.kernel_launches, 0, sizeof ctx->tm.kernel_launches);
-    ctx->dist_work[0] = ctx->dist_work[1] = 0;
+    ctx->distance.work[0] = ctx->distance.work[1] = 0;
     if (ctx->d_stats.ptr && ctx->npending == 0) {
         VC_HIP(ctx, hipSetDevice(ctx->device));
         VC_HIP(ctx, hipMemset(ctx->d_stats.ptr, 0, ctx->d_stats.cap * sizeof(unsigned long long)));
@@ -4826,8 +4764,7 @@ int vc_comm_init(vc_ctx *ctx, int n_ranks, int rank, const uint8_t uid[VC_UNIQUE
     ctx->n_ranks = n_ranks;
     ctx->rank = rank;
     VC_TRY(ensure(ctx, ctx->d_counts, (size_t)n_ranks + 1));
-    if (ctx->h_counts) { (void)hipHostFree(ctx->h_counts); ctx->h_counts = nullptr; }
-    VC_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_counts), sizeof(uint64_t) * n_ranks, hipHostMallocDefault));
+    VC_HIP(ctx, ensure_pinned(ctx->h_counts, (size_t)n_ranks));
     return VC_OK;
 }
 
@@ -4902,7 +4839,7 @@ static int allgather_compact(vc_ctx *ctx, uint64_t *counts_out, uint64_t *total_
     const uint32_t half = ctx->gseq & 1u;
     VC_TRY(finish_one(ctx, half));                               // the gather before last owned this half; the last one may still run
     DevBuf<uint64_t> &ent_all = ctx->d_ent_all[half];
-    hipEvent_t *E = ctx->gx[ctx->gx_next];                       // this gather's own events: see vc_ctx::gx
+    Event *E = ctx->gx[ctx->gx_next];                       // this gather's own events: see vc_ctx::gx
     ctx->gx_idx[half] = ctx->gx_next;
     ctx->gx_next = (ctx->gx_next + 1) % kGatherRing;
     VC_HIP(ctx, hipEventRecord(E[0], sx));
