@@ -424,7 +424,8 @@ int vc_hull_morphology(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc
  *   4 other readers: vc_fetch_viewmask and vc_expand_entries stay the silhouette carve's.  Visibility, depth maps, photo rounds,
  *     component labels and a stored distance field fail until their pass runs again; a call that adds nothing (r2 = 0, a second
  *     closing, an empty hull) leaves the result and with it the first four valid, and drops only the stored distance field,
- *     whose buffer the transforms use.  The next carve restores the visual hull.
+ *     whose buffer the transforms use (on an empty hull no transform runs, and the stored field stays valid too).  The next
+ *     carve restores the visual hull.
  *     Everything that reads the step sees the grown hull exactly as it sees an opened one.  vc_surface_mesh keeps its own
  *     contract: edges at added voxels are not bracketed by the centre test and stay at the midpoint, as for VC_FOOT_ANY.
  *   5 VC_ERR_ARG (with a message, nothing launched) when there is no carve result, steps are in flight, the carve ran with
@@ -860,7 +861,9 @@ int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *
  *   timing          timing_detail (0)  1: vc_carve_begin steps record the events around preparation and carve kernels too
  *                                  (vc_carve always does; see vc_timing_t), every kernel carries begin / end events on its own
  *                                  launch (kernel_ms_sum) and counts its work (vc_timing_t::work)
- *                   kernel_events (0)  1: only the per-launch begin / end events (kernel_ms_sum), nothing else changes
+ *                   kernel_events (0)  1: only the per-launch begin / end events (kernel_ms_sum, kernel_launches) of the kernels of
+ *                                  carve steps, nothing else changes; the launches of the post-carve passes (VC_K_DIST_BOX and
+ *                                  above) carry theirs under timing_detail alone
  *   streams         stream_priority (1)  carve + preparation streams at the highest queue priority, the expansion stream at
  *                                  the lowest (the expansion fills every wave slot; the carve chain is a row of short launches
  *                                  that would queue behind it); launch_events (1)  the events the streams exchange ride on

@@ -1,0 +1,512 @@
+"""What a context holds behind a carve, as include/voxcarve.h describes it, in numpy and without a GPU: the current records, and for
+every product of a post-carve pass whether it is valid and its bytes.  Every operation goes through the restatements that the
+per-pass tests already hold the device to (oracle.carve_c / carve_np, footprint_np, closing_np, distance_np, components_np,
+visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, oracle.marching_np); nothing is restated here.
+What this module adds is how the passes COMBINE: which records a pass starts from, which frame set it reads, what it invalidates.
+
+  scene(grid)            one of GRIDS, the golden cameras, three frame sets (slots 0, 1, 2) with different hulls and colours
+  draw_chain(seed)       (scene, ops): CHAIN_LEN operations with all their parameters, drawn with numpy.random.default_rng(seed)
+                         alone; some draws (min_voxels) look at the model's state, so the chain is applied while it is drawn
+  Model(scene).apply(op) applies one operation; returns what the call returns and produces (stats, flags, labels, fields, images)
+  replay(seed, upto=k)   the model in front of step k of that chain
+  trace(seed)            one row per step (what ran, on how many records, whether the hull changed, ...) for the coverage conditions
+
+A record is uint64: the linear index in the low 32 bits, r, g, b in bytes 4 - 6, `seen` in byte 7.  The product names are those of
+test_gpu_result_generation.REFUSAL / BUILT."""
+import hashlib
+import os
+import sys
+
+import numpy as np
+
+import closing_np as cl
+import clusters_np as cn
+import components_np as ccn
+import distance_np as dn
+import fixtures_util as fx
+import footprint_np as fp
+import geodesic_np as gn
+import normals_np as nn
+import photo_np as pn
+import render_np as rn
+import surface_np as sn
+import visible_np as vn
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
+
+from oracle import carve_c, carve_np, marching_np                    # noqa: E402
+from test_gpu_result_generation import BUILT, REFUSAL, RENDER_HW, _views   # noqa: E402
+
+SEEDS = tuple(range(601, 625))              # the 24 chains of tests/test_chain_model.py and tests/test_gpu_chain.py
+CHAIN_LEN = 10
+GRIDS = ((40, 65, 36), (24, 130, 20), (30, 63, 30), (37, 53, 29))
+BOUNDS = carve_np.DEFAULT_BOUNDS
+ROLLS = (0, 9, -13)                         # columns the golden masks are rolled by in slots 0, 1, 2
+SLOT_IMAGES = ((0, 1, 2, 3), (0, 1, 2, 3), (1, 2))   # cameras with an image per slot: slot 2 cannot feed a colour pass
+FULL_SLOTS = tuple(s for s, cams in enumerate(SLOT_IMAGES) if len(cams) == 4)
+COLOUR_CAMERAS = (None, 1, 2)
+PRODUCTS = tuple(REFUSAL) + ("render", "surface")
+assert set(PRODUCTS) >= BUILT
+
+HULL_CHANGERS = ("close", "dilate", "erode", "open", "filter_components", "photo_carve")
+COMPACTIONS = ("erode", "open", "filter_components", "photo_carve")
+COLOUR_PASSES = ("color_visible", "photo_carve")
+QUIET = ("hull_distance", "hull_normals", "render", "surface_mesh")
+KINDS = ("carve",) + HULL_CHANGERS + ("color_visible", "clusters", "geodesic") + QUIET
+
+LOW = np.uint64(0xffffffff)
+NOT_RGB = np.uint64(0xff000000ffffffff)
+
+
+# ---- records ----------------------------------------------------------------------------------------------------------------------
+def pack(idx, rgb, seen):
+    rgb = np.asarray(rgb, dtype=np.uint64).reshape(-1, 3)
+    return np.asarray(idx, dtype=np.uint64) | (rgb[:, 0] << np.uint64(32)) | (rgb[:, 1] << np.uint64(40)) | \
+        (rgb[:, 2] << np.uint64(48)) | (np.asarray(seen, dtype=np.uint64) << np.uint64(56))
+
+
+def index_of(rec):
+    return (np.asarray(rec, dtype=np.uint64) & LOW).astype(np.int64)
+
+
+def rgb_of(rec):
+    rec = np.asarray(rec, dtype=np.uint64)
+    return np.stack([(rec >> np.uint64(s)) & np.uint64(255) for s in (32, 40, 48)], axis=1).astype(np.uint8).reshape(-1, 3)
+
+
+def seen_of(rec):
+    return ((np.asarray(rec, dtype=np.uint64) >> np.uint64(56)) & np.uint64(255)).astype(np.uint8)
+
+
+def with_rgb(rec, rgb):
+    return (np.asarray(rec, dtype=np.uint64) & NOT_RGB) | pack(np.zeros(len(rec), np.uint64), rgb, np.zeros(len(rec), np.uint64))
+
+
+# ---- the scene --------------------------------------------------------------------------------------------------------------------
+class Scene:
+    """One grid, the golden cameras and three frame sets.  masks[slot][c] uint8 [H, W]; frames[slot][c] uint8 [H, W, 3] BGR or None."""
+
+    def __init__(self, grid):
+        self.grid = tuple(int(v) for v in grid)
+        self.bounds = tuple(float(v) for v in BOUNDS)
+        self.cams = fx.golden_cameras()
+        self.oc = fx.oracle_cams(self.cams)
+        golden = fx.golden_masks()
+        self.H, self.W = golden[0].shape
+        self.C = len(self.cams)
+        self.masks = [[np.ascontiguousarray(np.roll(m, r, axis=1)) for m in golden] for r in ROLLS]
+        every = fx.synthetic_frames(self.C * len(ROLLS), self.H, self.W)         # (slot 0 holds the suite's `frames` fixture)
+        self.frames = [[every[self.C * s + c] if c in SLOT_IMAGES[s] else None for c in range(self.C)] for s in range(len(ROLLS))]
+        self.q = dn.steps_um(self.grid, self.bounds)
+        self.views = _views(self)
+        self._carves = {}
+
+    def mm(self, factor):
+        """A radius in mm: `factor` times the grid's largest step; "below" is half the smallest one."""
+        if factor == "below":
+            return 0.5 * min(self.q) / 1000.0
+        return float(factor) * max(self.q) / 1000.0
+
+    def carve_records(self, slot, min_views, color_cam, footprint="centre"):
+        """The records a carve of frame set `slot` leaves (the restatements' own, cached: many chains carve the same)."""
+        key = (slot, min_views, color_cam, footprint)
+        if key not in self._carves:
+            nx, ny, nz = self.grid
+            frames = self.frames[slot] if color_cam is not None else None
+            if footprint == "centre":
+                w = carve_c.carve(nx, ny, nz, self.oc, self.masks[slot], frames, bounds=self.bounds, min_views=min_views,
+                                  color_cam=0 if color_cam is None else color_cam, want_viewmask=True)
+                idx = w["idx"]
+                if color_cam is None:
+                    rec = pack(idx, np.zeros((idx.size, 3)), np.zeros(idx.size))
+                else:
+                    rec = pack(idx, w["bgr"][:, ::-1], (w["viewmask"][idx.astype(np.int64)] >> color_cam) & 1)
+            else:
+                w = fp.carve(self.grid, self.oc, self.masks[slot], footprint, frames=frames, min_views=min_views, color_cam=color_cam,
+                             bounds=self.bounds)
+                rec = pack(w["idx"], w["rgb"], w["seen"])
+            rec.setflags(write=False)
+            self._carves[key] = rec
+        return self._carves[key]
+
+
+_SCENES = {}
+
+
+def scene(grid):
+    grid = tuple(grid)
+    if grid not in _SCENES:
+        _SCENES[grid] = Scene(grid)
+    return _SCENES[grid]
+
+
+# ---- the model --------------------------------------------------------------------------------------------------------------------
+class Model:
+    """fault: None, or one deliberate mistake of the kind the chains exist to catch (tests/test_chain_model.py feeds it to the
+    comparison on the CPU): "grow_slot0" colours added voxels from slot 0 instead of the carve's slot, "drop_paint" gives the
+    records that a compaction keeps the colours of the carve again."""
+
+    def __init__(self, sc, fault=None, literal=False):
+        self.scene = sc
+        self.literal = literal               # the restatements' literal twins where a pass has one that is affordable here
+        self.grid, self.bounds = sc.grid, sc.bounds
+        self.fault = fault
+        self.records = None                  # uint64 [S]; None before the first carve
+        self.carve = None                    # slot, min_views, color_cam of the carve that made the result
+        self.carved = None                   # its records
+        self.products = {}                   # name -> bytes, for the valid ones
+        self.mesh_shape = (0, 0)             # (V, F) of the last surface mesh
+        self.painted = False                 # a colour pass or a paint has run since the carve
+
+    # what the result is
+    @property
+    def S(self):
+        return int(self.records.size)
+
+    @property
+    def idx(self):
+        return index_of(self.records)
+
+    @property
+    def rgb(self):
+        return rgb_of(self.records)
+
+    def occ(self):
+        return dn.volume(self.idx, self.grid)
+
+    def min_views(self):
+        return max(int(self.carve["min_views"]), 1)
+
+    def _changed(self, own=None):
+        self.products = dict(own or {})
+
+    def _compacted(self, keep):
+        rec = self.records[keep]
+        if self.fault == "drop_paint" and rec.size:
+            base, i = self.carved, index_of(rec)
+            pos = np.minimum(np.searchsorted(index_of(base), i), max(base.size - 1, 0))
+            hit = index_of(base)[pos] == i if base.size else np.zeros(i.size, bool)
+            rec = rec.copy()
+            rec[hit] = base[pos[hit]]
+        return rec
+
+    # the operations
+    def apply(self, op):
+        out = getattr(self, "_" + op["op"])(op)
+        out["survivors"] = self.S
+        return out
+
+    def _carve(self, op):
+        sc = self.scene
+        out = {}
+        if op.get("first") is not None:          # two steps in flight, both collected: the second one is current
+            f = op["first"]
+            out["first_records"] = sc.carve_records(f["slot"], f["min_views"], f["color_cam"])
+        rec = sc.carve_records(op["slot"], op["min_views"], op["color_cam"], op["footprint"])
+        self.records = rec.copy()
+        self.carved = rec
+        self.carve = {k: op[k] for k in ("slot", "min_views", "color_cam")}
+        self.painted = False
+        self._changed()
+        out["count"] = int(rec.size)
+        return out
+
+    def _grow(self, op):
+        sc = self.scene
+        r2 = dn.radius_r2(op["radius_mm"])
+        S0 = self.S
+        new_occ, dilated, cells = cl.grow(self.occ(), sc.q, r2, op["op"])
+        cc = self.carve["color_cam"]
+        slot = 0 if self.fault == "grow_slot0" else self.carve["slot"]
+        rec, added = cl.records_after(self.records, new_occ, self.grid, self.bounds, None if cc is None else sc.oc[cc],
+                                      None if cc is None else sc.frames[slot][cc], sc.H, sc.W)
+        n_added = int(added.sum())
+        if n_added:
+            self.records = rec
+            self._changed({"grown": added.tobytes()})
+        else:                                    # the result stays; the transforms took the distance field's buffer (no hull, no transform)
+            assert np.array_equal(rec, self.records)
+            if S0:
+                self.products.pop("distance", None)
+            self.products["grown"] = added.tobytes()
+        return {"stats": {"survivors_before": S0, "dilated": dilated, "survivors_after": int(rec.size), "added": n_added,
+                          "box_cells": cells, "q": sc.q}, "added": added, "changed": n_added > 0}
+
+    _close = _grow
+    _dilate = _grow
+
+    def _shrink(self, op):
+        sc = self.scene
+        r2 = dn.radius_r2(op["radius_mm"])
+        occ, idx, S0 = self.occ(), self.idx, self.S
+        opened, eroded = dn.open_(occ, sc.q, r2, op["border"])
+        keep = (opened if op["op"] == "open" else eroded).reshape(-1)[idx]
+        d_in = dn.inside_box(occ, sc.q, op["border"]).reshape(-1)[idx]
+        self.records = self._compacted(keep)
+        self._changed()
+        return {"stats": {"survivors_before": S0, "eroded": int(eroded.sum()), "survivors_after": self.S,
+                          "max_d2": int(d_in.max()) if S0 else 0, "q": sc.q}, "changed": self.S != S0}
+
+    _erode = _shrink
+    _open = _shrink
+
+    def _filter_components(self, op):
+        S0 = self.S
+        w = (ccn.components_literal if self.literal else ccn.components)(self.idx, self.grid, op["connectivity"], op["min_voxels"], op["keep_largest"])
+        self.records = self._compacted(w["keep"])
+        self._changed({"component_labels": w["labels"].tobytes()})
+        K = int(w["label"].size)
+        return {"stats": {"components": K, "components_kept": int(w["kept"].sum()), "survivors_before": S0, "survivors_after": self.S,
+                          "largest": int(w["size"].max()) if K else 0},
+                "components": {k: w[k] for k in ("label", "size", "lo", "hi", "kept")}, "labels": w["labels"], "changed": self.S != S0}
+
+    def _photo_carve(self, op):
+        sc = self.scene
+        S0, rec0 = self.S, self.records
+        w = (pn.photo_carve_literal if self.literal else pn.photo_carve)(self.idx, self.rgb, self.grid, self.bounds, sc.oc, sc.frames[op["slot"]], sc.H, sc.W, max_rounds=op["max_rounds"])
+        keep = w["rounds"] == 0
+        kept = self._compacted(keep)
+        if self.fault == "drop_paint":           # (the colouring of the kept records starts from what the compaction handed over)
+            w = dict(w, rgb=vn.color_visible(index_of(kept), rgb_of(kept), self.grid, self.bounds, sc.oc, sc.frames[op["slot"]], sc.H, sc.W)[2])
+        self.records = with_rgb(rec0[keep], w["rgb"])
+        self.painted = True
+        self._changed({"visibility": w["vis"].tobytes(), "photo_rounds": w["rounds"].tobytes()})
+        return {"stats": {"rounds": w["n_rounds"], "converged": bool(w["converged"]), "survivors_before": S0, "survivors_after": self.S},
+                "rounds": w["rounds"], "vis": w["vis"], "zmaps": w["zmaps"], "changed": self.S != S0}
+
+    def _color_visible(self, op):
+        sc = self.scene
+        zmaps, vis, rgb = (vn.color_visible_literal if self.literal else vn.color_visible)(self.idx, self.rgb, self.grid, self.bounds, sc.oc, sc.frames[op["slot"]], sc.H, sc.W)
+        self.records = with_rgb(self.records, rgb)
+        self.painted = True
+        self.products["visibility"] = vis.tobytes()
+        return {"vis": vis, "zmaps": zmaps}
+
+    def _clusters(self, op):
+        qxy = cn.steps_um_xy(self.grid, self.bounds)
+        w = (cn.clusters_literal if self.literal else cn.clusters)(self.occ(), qxy, op["k"], max_iters=op["max_iters"], min_column=op["min_column"])
+        d = cn.describe(self.records, self.grid, w)                          # (the histograms: the colours in front of the paint)
+        self.products["clusters"] = d["labels"].tobytes()
+        self.records = cn.paint(self.records, d["labels"], op["palette"])
+        self.painted = True
+        return {"stats": {k: w[k] for k in ("survivors", "columns", "weight", "iterations", "q")}, "converged": bool(w["converged"]),
+                "clusters": w, "describe": d}
+
+    def _geodesic(self, op):
+        sc = self.scene
+        idx = self.idx
+        srec = gn.seeds_by_layer(idx, self.grid, op["seeds"], op["layers"])
+        w = gn.geodesic(idx, self.grid, sc.q, op["connectivity"], srec, op["extrema"], method="dijkstra" if self.literal else "bellman")
+        self.products["geodesic"] = w["d"].tobytes()
+        self.records = with_rgb(self.records, gn.paint(self.rgb, w["keys"], op["paint"], op["palette"], w["max_d"]))
+        self.painted = True
+        rows = [(x["label"], x["voxel"], x["record"], x["d"], x["ix"], x["iy"], x["iz"]) for x in w["extrema"]]
+        return {"stats": {k: w[k] for k in ("survivors", "seeds", "reached", "unreached", "max_d", "extremities", "edge_um", "q")},
+                "d": w["d"], "labels": w["labels"], "extrema": rows}
+
+    def _hull_distance(self, op):
+        sc = self.scene
+        occ, idx = self.occ(), self.idx
+        field = dn.inside_box(occ, sc.q, op["border"])
+        wrec = field.reshape(-1)[idx]
+        self.products["distance"] = field.tobytes()
+        out = {"stats": {"survivors": self.S, "max_d2": int(wrec.max()) if self.S else 0, "q": sc.q}, "inside": field, "records": wrec}
+        if op["outside"]:
+            out["outside"] = dn.outside(occ, sc.q)
+        return out
+
+    def _hull_normals(self, op):
+        n4, st = (nn.normals_literal if self.literal else nn.normals)(self.occ(), self.scene.q, dn.radius_r2(op["radius_mm"]))
+        self.products["normals"] = n4.tobytes()
+        return {"stats": st, "n4": n4}
+
+    def _render(self, op):
+        sc = self.scene
+        H, W = RENDER_HW
+        w = rn.render(self.occ().reshape(-1), self.idx.astype(np.uint32), self.rgb, self.grid, self.bounds,
+                      [rn.view_params(v) for v in sc.views], H, W, block=8)
+        V = len(sc.views)
+        index, depth = w["index"].reshape(V, H, W), w["depth"].reshape(V, H, W)
+        self.products["render"] = index.tobytes() + depth.tobytes()
+        return {"index": index, "depth": depth, "face": w["face"].reshape(V, H, W), "rgb": w["rgb"].reshape(V, H, W, 3),
+                "stats": {"pixels": V * H * W, "hits": int((index != rn.MISS).sum())}}
+
+    def _surface_mesh(self, op):
+        sc = self.scene
+        masks = np.stack([m > 0 for m in sc.masks[self.carve["slot"]]])
+        w = sn.surface_mesh(self.occ().reshape(-1), self.idx, self.rgb, self.grid, self.bounds, sc.oc, masks, self.min_views(),
+                            op["refine_steps"])
+        self.mesh_shape = (int(w["verts"].shape[0]), int(w["faces"].shape[0]))
+        self.products["surface"] = np.ascontiguousarray(w["verts"]).tobytes() + np.ascontiguousarray(w["faces"]).tobytes()
+        return {"mesh": w, "stats": dict(w["stats"], n_faces=self.mesh_shape[1])}
+
+    # what the end of a chain compares on the final hull
+    def marching_cubes(self):
+        """marching_cubes(volume=None): the occupancy in the reference's reshape, (nx, ny, nz) over the voxel order."""
+        nx, ny, nz = self.grid
+        return marching_np.extract(self.occ().reshape(nx, ny, nz))
+
+
+# ---- chains -----------------------------------------------------------------------------------------------------------------------
+def _draw_step(rng, sc, centre_only=False):
+    step = {"slot": int(rng.integers(3)), "mode": ("fused", "lut")[int(rng.integers(2))],
+            "min_views": sc.C - int(rng.integers(2)), "color_cam": COLOUR_CAMERAS[int(rng.choice(3, p=(0.25, 0.4, 0.35)))]}
+    if not centre_only:
+        step["footprint"] = ("centre", "any")[int(rng.random() < 0.25)]
+    return step
+
+
+def _draw_carve(rng, sc):
+    op = dict(_draw_step(rng, sc), op="carve", first=None)
+    if op["footprint"] == "centre" and rng.random() < 0.45:      # two steps begun on two slots, both collected
+        first = _draw_step(rng, sc, centre_only=True)
+        first["slot"] = (op["slot"] + 1 + int(rng.integers(2))) % 3
+        op["first"] = first
+    return op
+
+
+def _palette(rng, rows):
+    return rng.integers(0, 256, (rows, 3), dtype=np.uint8)
+
+
+def _draw(rng, sc, model, kind):
+    pick = lambda seq, p=None: seq[int(rng.choice(len(seq), p=p))]
+    if kind == "carve":
+        return _draw_carve(rng, sc)
+    if kind in ("close", "dilate"):
+        return {"op": kind, "radius_mm": sc.mm(pick(("below", 1, 1.5, 2, 3), (0.12, 0.3, 0.25, 0.2, 0.13)))}
+    if kind == "erode":
+        return {"op": kind, "radius_mm": sc.mm(pick(("below", 0.25, 0.5, 1, 40), (0.12, 0.25, 0.25, 0.13, 0.25))), "border": pick(dn.BORDERS)}
+    if kind == "open":
+        return {"op": kind, "radius_mm": sc.mm(pick(("below", 0.25, 0.5, 1, 2), (0.12, 0.3, 0.3, 0.18, 0.1))), "border": pick(dn.BORDERS)}
+    if kind == "filter_components":
+        op = {"op": kind, "connectivity": pick(ccn.CONNECTIVITIES), "min_voxels": 0, "keep_largest": int(rng.integers(2))}
+        if not op["keep_largest"]:               # a floor from the hull's own component sizes: it sometimes drops something
+            sizes = np.sort(ccn.components(model.idx, model.grid, op["connectivity"])["size"])
+            if sizes.size:
+                op["min_voxels"] = int(sizes[int(rng.integers(sizes.size))]) + int(rng.integers(2))
+        return op
+    if kind == "photo_carve":
+        return {"op": kind, "slot": pick(FULL_SLOTS), "max_rounds": int(rng.integers(1, 4))}
+    if kind == "color_visible":
+        return {"op": kind, "slot": pick(FULL_SLOTS)}
+    if kind == "clusters":
+        k = int(rng.integers(1, 5))
+        return {"op": kind, "k": k, "max_iters": 32, "min_column": int(rng.integers(1, 3)), "palette": _palette(rng, k)}
+    if kind == "geodesic":
+        k = int(rng.integers(0, 4))
+        return {"op": kind, "seeds": pick(("floor", "top")), "layers": int(rng.integers(1, 3)), "extrema": k,
+                "connectivity": pick(ccn.CONNECTIVITIES), "paint": pick(("labels", "distance")), "palette": _palette(rng, k + 1)}
+    if kind == "hull_distance":
+        return {"op": kind, "border": pick(dn.BORDERS), "outside": bool(rng.integers(2))}
+    if kind == "hull_normals":
+        return {"op": kind, "radius_mm": normals_radius_mm(sc, pick((1, 1.5)))}
+    if kind == "render":
+        return {"op": kind}
+    if kind == "surface_mesh":
+        return {"op": kind, "refine_steps": pick((0, 3, 8))}
+    raise ValueError(kind)
+
+
+def normals_radius_mm(sc, factor=1.5):
+    """`factor` largest steps, or one where that ball reaches beyond normals_np.EXT_MAX cells on the finest axis."""
+    for f in (factor, 1):
+        mm = sc.mm(f)
+        try:
+            nn.ball(sc.q, dn.radius_r2(mm))
+            return mm
+        except ValueError:
+            continue
+    raise ValueError("no normals radius for grid %r" % (sc.grid,))
+
+
+_WEIGHTS = {"carve": 1.2, "close": 0.8, "dilate": 0.7, "erode": 0.8, "open": 0.8, "filter_components": 0.9, "photo_carve": 0.8,
+            "color_visible": 1.0, "clusters": 1.1, "geodesic": 1.0, "hull_distance": 1.1, "hull_normals": 1.1, "render": 1.1,
+            "surface_mesh": 1.0}
+
+
+_CHAINS = {}
+
+
+def draw_chain(seed):
+    """(scene, ops) of chain `seed`: a carve, then CHAIN_LEN - 1 drawn operations; now and then a burst of hull-changing passes."""
+    if seed not in _CHAINS:
+        _CHAINS[seed] = _draw_chain(seed)
+    return _CHAINS[seed]
+
+
+def _draw_chain(seed):
+    rng = np.random.default_rng(seed)
+    sc = scene(GRIDS[int(rng.integers(len(GRIDS)))])
+    model = Model(sc)
+    kinds = list(_WEIGHTS)
+    p = np.array([_WEIGHTS[k] for k in kinds])
+    p /= p.sum()
+    ops, burst = [], 0
+    while len(ops) < CHAIN_LEN:
+        if not ops:
+            kind = "carve"
+        elif model.S == 0 and rng.random() < 0.5:    # an empty hull: some passes run on it, then the chain goes on
+            kind, burst = "carve", 0
+        elif burst:
+            burst -= 1
+            kind = HULL_CHANGERS[int(rng.integers(len(HULL_CHANGERS)))]
+        else:
+            kind = kinds[int(rng.choice(len(kinds), p=p))]
+            if kind in HULL_CHANGERS and rng.random() < 0.5:
+                burst = int(rng.integers(2, 4))
+        op = _draw(rng, sc, model, kind)
+        model.apply(op)
+        ops.append(op)
+    return sc, ops
+
+
+def final_ops(sc):
+    """One run of every quiet pass, for the final hull of a chain."""
+    return [{"op": "hull_distance", "border": "open", "outside": True}, {"op": "hull_normals", "radius_mm": normals_radius_mm(sc)},
+            {"op": "render"}, {"op": "surface_mesh", "refine_steps": 8}]
+
+
+def run(seed, fault=None):
+    """Yields (step, op, out, model) of chain `seed`, the model as the operation left it."""
+    sc, ops = draw_chain(seed)
+    model = Model(sc, fault)
+    for step, op in enumerate(ops):
+        out = model.apply(op)
+        yield step, op, out, model
+
+
+def replay(seed, upto=None, fault=None, literal=False):
+    """The model of chain `seed` in front of step `upto` (None: behind the last one)."""
+    sc, ops = draw_chain(seed)
+    model = Model(sc, fault, literal)
+    for op in ops[:upto]:
+        model.apply(op)
+    return model
+
+
+def describe_op(op):
+    """The parameters of an operation as one short line (palettes as their shape), for the failure messages."""
+    return ", ".join("%s=%s" % (k, ("u8%r" % (v.shape,)) if isinstance(v, np.ndarray) else repr(v)) for k, v in op.items())
+
+
+def trace(seed):
+    """One dict per step: op, kind of carve, records before and after, whether the hull changed, and what the records carried
+    into the operation (seen == 0 bytes, painted colours)."""
+    rows = []
+    sc, ops = draw_chain(seed)
+    model = Model(sc)
+    for step, op in enumerate(ops):
+        before = None if model.records is None else model.records
+        carve_slot = None if model.carve is None else model.carve["slot"]
+        row = {"step": step, "op": op["op"], "before": 0 if before is None else int(before.size),
+               "seen0": bool(before is not None and before.size and (seen_of(before) == 0).any()),
+               "painted": bool(model.painted and before is not None and before.size), "carve_slot": carve_slot, "params": op}
+        out = model.apply(op)
+        row["after"] = model.S
+        row["digest"] = hashlib.sha1(model.records.tobytes()).hexdigest()
+        row["changed"] = bool(out.get("changed", False)) if op["op"] != "carve" else False
+        rows.append(row)
+    return rows

@@ -1,0 +1,243 @@
+"""Random chains of carves and post-carve passes on the device against tests/chain_model.py: how the passes COMBINE.
+
+Every pass is held to its restatement by its own test, always behind a synchronous carve of slot 0.  Here 24 chains of 10 drawn
+operations (chain_model.SEEDS; tests/test_chain_model.py asserts what they cover) run on three frame sets with different hulls and
+colours, through synchronous, footprint and pipelined carves, with up to nine passes behind one carve.  After EVERY operation the
+device is compared with the model: the call's stats, all 8 bytes of every record, the occupancy, the packed words' popcount, what
+the operation itself produces, and every product of every pass -- its fetch returns the model's bytes or refuses with its own
+message.  At the end of a chain the exchange form, the marching cubes of the occupancy and one run of every quiet pass are compared
+on the final hull.  The two geodesic routes and the two floor-map routes alternate by step parity.
+
+A failure names (seed, step, operation, parameters); chain_model.replay(seed, upto=step) rebuilds the model in front of it."""
+import contextlib
+
+import numpy as np
+import pytest
+
+import chain_model as cm
+from test_gpu_result_generation import REFUSAL, RENDER_HW, _fetches, _light, _render_images, _surface_mesh
+
+pytestmark = pytest.mark.gpu
+
+LOW = np.uint64(0xffffffff)
+
+
+@pytest.fixture(scope="module")
+def eng(built):
+    import voxcarve
+    e = voxcarve.CarveEngine(0)
+    yield e
+    e.close()
+
+
+def _setup(e, sc, cams, masks, frames):
+    """The scene's three frame sets; slot 0 is the suite's own fixtures."""
+    assert all(np.array_equal(a, b) for a, b in zip(masks, sc.masks[0])) and all(np.array_equal(a, b) for a, b in zip(frames, sc.frames[0]))
+    e.set_grid(*sc.grid, bounds=sc.bounds)
+    e.set_cameras(cams, sc.H, sc.W)
+    for slot in range(len(sc.masks)):
+        e.upload_masks(masks if slot == 0 else sc.masks[slot], slot=slot)
+        for c in cm.SLOT_IMAGES[slot]:
+            e.upload_frame(c, (frames if slot == 0 else sc.frames[slot])[c], slot=slot)
+    e.build_lut()
+
+
+@contextlib.contextmanager
+def _at(seed, step, op):
+    try:
+        yield
+    except AssertionError as err:
+        raise AssertionError("chain seed=%d, step=%s, %s: %s" % (seed, step, cm.describe_op(op), err)) from err
+
+
+def _same(got, want, keys):
+    for k in keys:
+        assert got[k] == want[k], (k, got[k], want[k])
+
+
+def _depth_maps(e, zmaps):
+    for c in range(e.n_cameras):
+        assert np.array_equal(e.fetch_depth(c).view(np.uint32).reshape(-1), zmaps[c]), ("depth map", c)
+
+
+def _carve(e, op, out):
+    if op["first"] is None:
+        n = e.carve(slot=op["slot"], min_views=op["min_views"], color_cam=op["color_cam"], mode=op["mode"], footprint=op["footprint"])
+    else:                                        # two steps in flight on two slots; the older one is collected and read first
+        f = op["first"]
+        e.carve_begin(slot=f["slot"], min_views=f["min_views"], color_cam=f["color_cam"], mode=f["mode"])
+        e.carve_begin(slot=op["slot"], min_views=op["min_views"], color_cam=op["color_cam"], mode=op["mode"])
+        assert e.carve_end() == out["first_records"].size, "the first step's count"
+        assert np.array_equal(e.fetch_records(), out["first_records"]), "the first step's records"
+        n = e.carve_end()
+    assert n == out["count"]
+
+
+def _grow(e, op, out):
+    st = (e.close_hull if op["op"] == "close" else e.dilate_hull)(op["radius_mm"])
+    _same(st, out["stats"], ("survivors_before", "dilated", "survivors_after", "added", "box_cells", "q"))
+
+
+def _shrink(e, op, out):
+    st = (e.open_hull if op["op"] == "open" else e.erode_hull)(op["radius_mm"], border=op["border"])
+    _same(st, out["stats"], ("survivors_before", "eroded", "survivors_after", "max_d2", "q"))
+
+
+def _filter_components(e, op, out):
+    st = e.filter_components(connectivity=op["connectivity"], min_voxels=op["min_voxels"], keep_largest=op["keep_largest"])
+    _same(st, out["stats"], ("components", "components_kept", "survivors_before", "survivors_after", "largest"))
+    got = e.fetch_components()
+    for k in ("label", "size", "lo", "hi", "kept"):
+        assert np.array_equal(got[k], out["components"][k]), k
+
+
+def _photo_carve(e, op, out):
+    st = e.photo_carve(slot=op["slot"], max_rounds=op["max_rounds"])
+    _same(st, out["stats"], ("rounds", "converged", "survivors_before", "survivors_after"))
+    _depth_maps(e, out["zmaps"])
+
+
+def _color_visible(e, op, out):
+    e.color_visible(slot=op["slot"])
+    _depth_maps(e, out["zmaps"])
+
+
+def _clusters(e, op, out, step):
+    e.set_option("cluster_floor_records", step & 1)
+    try:
+        st = e.cluster_hull(op["k"], max_iters=op["max_iters"], min_column=op["min_column"])
+    finally:
+        e.set_option("cluster_floor_records", 1)
+    w, d = out["clusters"], out["describe"]
+    _same(st, out["stats"], ("survivors", "columns", "weight", "iterations", "q"))
+    assert st["converged"] == out["converged"] and st["k"] == op["k"]
+    cl = e.fetch_clusters()
+    assert np.array_equal(cl["centre_um"], w["centres"])
+    assert np.array_equal(e.fetch_floor_map().reshape(-1), w["floor_map"]), "floor map"
+    assert np.array_equal(e.fetch_floor_labels().reshape(-1), w["floor_labels"]), "floor labels"
+    for k in ("voxels", "weight", "columns", "lo", "hi"):
+        assert np.array_equal(cl[k], d[k]), k
+    assert np.array_equal(e.fetch_cluster_histograms(), d["histograms"]), "histograms"
+    e.paint_clusters(op["palette"])
+
+
+def _geodesic(e, op, out, step):
+    e.set_option("geodesic_tiles", step & 1)
+    try:
+        st = e.hull_geodesic(seeds=op["seeds"], layers=op["layers"], extrema=op["extrema"], connectivity=op["connectivity"])
+    finally:
+        e.set_option("geodesic_tiles", 1)
+    _same(st, out["stats"], ("survivors", "seeds", "reached", "unreached", "max_d", "extremities", "edge_um", "q"))
+    assert np.array_equal(e.fetch_geodesic_labels(), out["labels"]), "labels"
+    ex = e.fetch_extrema()
+    rows = [(int(ex["label"][k]), int(ex["voxel"][k]), int(ex["record"][k]), int(ex["d"][k])) + tuple(int(v) for v in ex["index"][k])
+            for k in range(ex["label"].size)]
+    assert rows == out["extrema"], "extremities"
+    e.paint_geodesic(op["paint"], op["palette"])
+
+
+def _hull_distance(e, op, out):
+    st = e.hull_distance(border=op["border"], outside=op["outside"])
+    _same(st, out["stats"], ("survivors", "max_d2", "q"))
+    assert np.array_equal(e.fetch_record_distance(), out["records"]), "record distances"
+    if op["outside"]:
+        assert np.array_equal(e.fetch_distance_raw("outside"), out["outside"]), "outside field"
+
+
+def _hull_normals(e, op, out):
+    st = e.hull_normals(op["radius_mm"])
+    _same(st, out["stats"], ("survivors", "surface", "zero", "offsets", "ext", "q"))
+
+
+def _render(e, op, out, sc):
+    got = e.render(sc.views, *RENDER_HW)
+    assert np.array_equal(got["index"], out["index"]), "index"
+    assert np.array_equal(got["depth"].view(np.uint32), out["depth"].view(np.uint32)), "depth"
+    assert np.array_equal(got["face"], out["face"]) and np.array_equal(got["rgb"], out["rgb"]), "face, rgb"
+    _same(got["stats"], out["stats"], ("pixels", "hits"))
+
+
+def _surface_mesh_op(e, op, out):
+    got, want = e.surface_mesh(op["refine_steps"]), out["mesh"]
+    assert got["verts"].shape == want["verts"].shape and np.array_equal(got["verts"].view(np.uint64), want["verts"].view(np.uint64)), "vertices"
+    assert np.array_equal(got["faces"], want["faces"]), "faces"
+    assert np.array_equal(got["rgb"], want["rgb"].reshape(-1, 3)) and np.array_equal(got["refined"], want["refined"]), "colours, refined"
+    _same(got["stats"], out["stats"], ("n_verts", "n_faces", "refined", "unrefined"))
+
+
+def _run(e, sc, step, op, out):
+    kind = op["op"]
+    if kind == "carve":
+        _carve(e, op, out)
+    elif kind in ("close", "dilate"):
+        _grow(e, op, out)
+    elif kind in ("erode", "open"):
+        _shrink(e, op, out)
+    elif kind == "clusters":
+        _clusters(e, op, out, step)
+    elif kind == "geodesic":
+        _geodesic(e, op, out, step)
+    elif kind == "render":
+        _render(e, op, out, sc)
+    elif kind == "surface_mesh":
+        _surface_mesh_op(e, op, out)
+    else:
+        {"filter_components": _filter_components, "photo_carve": _photo_carve, "color_visible": _color_visible,
+         "hull_distance": _hull_distance, "hull_normals": _hull_normals}[kind](e, op, out)
+
+
+def _result_equals_model(e, m):
+    """Records, occupancy, packed words and every product: the model's bytes, or the product's own refusal."""
+    from voxcarve._lib import VoxcarveError
+    assert e.count == m.S, ("count", e.count, m.S)
+    got = e.fetch_records()
+    assert np.array_equal(got & LOW, m.records & LOW), "indices and order"
+    bad = np.flatnonzero(got != m.records)
+    assert bad.size == 0, "%d of %d records differ, first at %d: %#018x, want %#018x" % (bad.size, m.S, bad[0], int(got[bad[0]]), int(m.records[bad[0]]))
+    assert np.array_equal(e.fetch_occupancy(), m.occ().reshape(-1)), "occupancy"
+    assert int(np.bitwise_count(e.pack_entries()[:, 0]).sum()) == m.S, "popcount of the packed words"
+    for name, fetch in _fetches(e).items():
+        if name in m.products:
+            assert fetch().tobytes() == m.products[name], "product %s differs from the model" % name
+        else:
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + REFUSAL[name]):
+                fetch()
+    if "normals" in m.products:                  # (the calls that read the images and the mesh look at the normals first)
+        if "render" in m.products:
+            e.shade_render(_light(e))
+            assert _render_images(e) == m.products["render"], "product render differs from the model"
+        else:
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*no images of the current"):
+                e.shade_render(_light(e))
+        if "surface" in m.products:
+            e.surface_normals()
+            assert _surface_mesh(e, m.mesh_shape) == m.products["surface"], "product surface differs from the model"
+        else:
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*no mesh of the current"):
+                e.surface_normals()
+
+
+@pytest.mark.parametrize("seed", cm.SEEDS)
+def test_chain(eng, cams, masks, frames, seed):
+    e = eng
+    sc, ops = cm.draw_chain(seed)
+    _setup(e, sc, cams, masks, frames)
+    m = cm.Model(sc)
+    for step, op in enumerate(ops):
+        out = m.apply(op)
+        with _at(seed, step, op):
+            _run(e, sc, step, op, out)
+            _result_equals_model(e, m)
+    # the final hull: the exchange form, the marching cubes of the occupancy, one run of every quiet pass
+    with _at(seed, "end", {"op": "expand_entries(pack_entries())"}):
+        assert e.expand_entries(e.pack_entries()) == m.S
+        assert np.array_equal(e.fetch_gathered() & LOW, m.records & LOW)
+    with _at(seed, "end", {"op": "marching_cubes"}):
+        verts, faces = e.marching_cubes(volume=None)
+        want_v, want_f = m.marching_cubes()
+        assert np.array_equal(verts, want_v) and np.array_equal(faces, want_f)
+    for k, op in enumerate(cm.final_ops(sc)):
+        out = m.apply(op)
+        with _at(seed, "end + %d" % k, op):
+            _run(e, sc, k, op, out)
+            _result_equals_model(e, m)
