@@ -69,10 +69,12 @@ typedef enum {
     VC_K_DIST_RECORDS /* k_dist_records */,
     VC_K_GEO_SEED /* k_geo_seed_list, k_geo_seed_layers, k_geo_source */, VC_K_GEO_TILES /* k_geo_tiles */,
     VC_K_GEO_SWEEP /* k_geo_sweep */, VC_K_GEO_ARGMAX /* k_geo_best + k_geo_pick */,
+    VC_K_TEMPORAL_VOTE /* k_temporal_vote */, VC_K_TEMPORAL_RANK /* k_count_groups, k_cc_wcount, k_cc_woff, k_temporal_new<votes only> */,
+    VC_K_TEMPORAL_MERGE /* k_temporal_old + k_temporal_new */,
     VC_K_GROW_MARK /* k_grow_mark: the new set's bits and counts */, VC_K_GROW_RANK /* k_grow_apply, k_count_groups, k_cc_wcount, k_cc_woff */,
     VC_K_GROW_MERGE /* k_grow_old + k_grow_new */
 } vc_kernel_kind;
-#define VC_KERNEL_KINDS 25
+#define VC_KERNEL_KINDS 28
 enum {
     VC_WORK_WORD_BOXES = 0,   /* 8-byte word boxes k_brick_words read (listed bricks x 64 words x cameras asked)           */
     VC_WORK_TABLE_ENTRIES,    /* 4-byte table entries the per-voxel level read (VC_MODE_LUT)                                */
@@ -450,6 +452,54 @@ typedef struct {
 } vc_grow_stats_t;
 int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags /* must be 0 */, vc_grow_stats_t *stats);
 int vc_fetch_grown(vc_ctx *ctx, uint8_t *added);   /* u8 [S_after], record order: 1 = created by the last vc_hull_grow */
+
+/* ---- a vote of each voxel over the last frames' hulls (no reference counterpart) ------------------------------------------------
+ * Every other pass works on one frame.  Mask noise differs in every frame of a video, so voxels appear and vanish between carves
+ * while the figure stands still; vc_hull_temporal keeps the last `window` hulls on the device and replaces the current result by
+ * their vote.  It puts back what a momentary mask hole carved out and drops specks that live for one frame, with no radius and no
+ * size threshold.  The contract, bit for bit (tests/temporal_np.py restates it).  Integers only.
+ *   1 push: H_t is the current result's occupancy, as vc_fetch_occupancy sees it when the call starts.  It becomes the newest of a
+ *     ring of `window` snapshots on the device.  m = min(pushes since the last reset, window).
+ *   2 count: c(v) = the number of j in 0 .. m - 1 with v in H_{t-j}; c(v) <= 15.
+ *   3 thresholds: 1 <= keep_off <= keep_on <= window <= VC_TEMPORAL_MAX_WINDOW.  on = ceil(keep_on m / window), off =
+ *     ceil(keep_off m / window), in integers: they grow with the ring while it fills, and with m = 1 both are 1, so the first call
+ *     after a reset returns the hull as it is.
+ *   4 vote with hysteresis: P is the previous call's output, empty after a reset.  O_t = { v : c(v) >= on } + { v in P : c(v) >=
+ *     off }.  keep_off = keep_on is the plain k-of-window vote; keep_on = window with keep_off = 1 gives a hull that is slow to
+ *     take a voxel and slow to let it go.
+ *   5 result after the call: records, count and occupancy describe O_t in ascending linear index.  A record of H_t & O_t keeps its
+ *     8 bytes.  A voxel of O_t \ H_t gets a fresh record exactly as item 3 of vc_hull_grow colours one (the colour camera's pixel
+ *     under the centre, by the carve's float64 projection and in-image test, seen = 1; else zeros).  Records of H_t \ O_t are
+ *     dropped.  votes[r] = c of record r, added[r] = 1 for a fresh record.  Other readers follow item 4 of vc_hull_grow: when
+ *     O_t = H_t nothing is invalidated and the result generation does not advance, otherwise every product of a pass is stale.
+ *   6 stats: window; frames = m; on, off = the effective thresholds of this call; raw_changed = |H_t xor H_{t-1}| (0 when m = 1);
+ *     out_changed = |O_t xor P|; added = |O_t \ H_t|; removed = |H_t \ O_t|; survivors_after = survivors_before + added -
+ *     removed; temporal_ms = HIP events around the whole call.
+ *   7 state: the ring and P survive carves, passes and results.  They are reset by vc_temporal_reset, by a change of grid, slab or
+ *     cameras, and by a call whose `window` differs from the ring's.  keep_on and keep_off may change from call to call.
+ *   8 one push per result: the call is refused when the current result is already the last call's output.  Carve again first.
+ *   9 VC_ERR_ARG (with a message, nothing launched, no state touched) when there is no carve result, steps are in flight, the
+ *     carve ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached,
+ *     flags != 0, stats == NULL, window is 0 or above 15, keep_on or keep_off is out of range, the grid has more voxels than a u32
+ *     index, the slot has been prepared again since the carve (as vc_hull_grow), or item 8 applies.
+ *  10 an allocation failure returns VC_ERR_OOM and leaves result, ring and P as they were: the vote reads the result's words in
+ *     place and writes O_t to a staging buffer; the counts are read back and every buffer is sized before anything is committed.
+ *     Only then does the newest snapshot overwrite the ring's oldest slot (which the vote never reads), O_t go into the result's
+ *     words, and the staging buffer become P.
+ *  11 vc_fetch_temporal fails unless the current result is the last call's output; vc_fetch_temporal_history fails for age >= m.
+ * Memory: (window + 2) nwords 8 bytes (0.94 GB at 1024^3 with window 5), allocated by the first call.  What it does not do: it lags
+ * a moving figure by about window / 2 frames, there is no motion compensation, and multi-GPU is refused.
+ * Synchronous, one read-back in the middle (the five counts). */
+#define VC_TEMPORAL_MAX_WINDOW 15u
+typedef struct {
+    uint32_t window, frames /* m */, on, off /* the effective thresholds of this call */;
+    uint64_t survivors_before, survivors_after, added, removed, raw_changed, out_changed;
+    float temporal_ms;
+} vc_temporal_stats_t;
+int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t keep_off, uint32_t flags /* must be 0 */, vc_temporal_stats_t *stats);
+int vc_fetch_temporal(vc_ctx *ctx, uint8_t *votes, uint8_t *added);            /* u8 [S_after] each, record order; either may be NULL */
+int vc_fetch_temporal_history(vc_ctx *ctx, uint32_t age, uint8_t *bits);       /* the raw hull pushed `age` calls ago, laid out as vc_fetch_occupancy */
+int vc_temporal_reset(vc_ctx *ctx);
 
 /* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
  *      executable.py) -----------------------------------------------------------------------------------------------------------

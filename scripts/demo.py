@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -19,6 +19,10 @@ the device, assignment.configure(clusters=K) -- their floor positions in world m
 the device, assignment.configure(extremities=K) -- their world positions and distances are printed; --geodesic-paint
 labels|distance (with --extremities): every voxel in its region's colour or a grey ramp of its distance, in the PLY, the --render
 images and the --mesh;
+--temporal T [--frames F] [--noise P]: F frames (default 16) of the committed masks, each with a share P (default 0.02) of its
+pixels flipped by a generator seeded with 7000 + the frame number, are carved one after the other and every hull is replaced by
+the vote of the last T hulls on the device, assignment.configure(temporal_window=T) -- the voxels that change between consecutive
+raw hulls and between consecutive voted hulls are printed per frame, and the last voted hull is what is written;
 --help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
@@ -79,6 +83,18 @@ if "--close" in sys.argv:
     k = sys.argv.index("--close")
     close_mm = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
+temporal, n_frames, noise = 0, 16, 0.02
+for flag, conv in (("--temporal", int), ("--frames", int), ("--noise", float)):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        value = conv(sys.argv[k + 1])
+        del sys.argv[k:k + 2]
+        if flag == "--temporal":
+            temporal = value
+        elif flag == "--frames":
+            n_frames = value
+        else:
+            noise = value
 g = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 out = sys.argv[2] if len(sys.argv) > 2 else "hull.ply"
 color_mode = sys.argv[3] if len(sys.argv) > 3 else "camera"
@@ -86,11 +102,30 @@ hull = "photo" if color_mode == "photo" else "visual"
 color_mode = "visible" if color_mode == "photo" else color_mode
 masks = fx.golden_masks()
 frames = [np.dstack([m // 2 + 60, m // 3 + 40, 255 - m // 2]).astype(np.uint8) for m in masks]   # any BGR image
-assignment.configure(frame_source=assignment.StaticFrameSource([(frames, masks)]),
+sets = [(frames, masks)]
+if temporal:
+    sets = []
+    for t in range(n_frames):
+        rng = np.random.default_rng(7000 + t)
+        sets.append((frames, [np.where(rng.random(m.shape) < noise, 255 - m, m).astype(np.uint8) for m in masks]))
+assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal,
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
                      extremities=extremities, geodesic_paint=geodesic_paint if extremities else None)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
+if temporal:
+    raw_sum = out_sum = 0
+    for t in range(n_frames):
+        if t:
+            pos, col = assignment.set_voxel_positions(g, g // 2, g)
+        ts = assignment.temporal()
+        print("frame %2d: %d hulls, on %d off %d: raw hull %d voxels (%d changed), voted hull %d voxels (%d changed; %d restored, %d dropped), "
+              "%.3f ms" % (t, ts["frames"], ts["on"], ts["off"], ts["survivors_before"], ts["raw_changed"], ts["survivors_after"],
+                           ts["out_changed"], ts["added"], ts["removed"], ts["temporal_ms"]))
+        if t >= temporal:
+            raw_sum += ts["raw_changed"]
+            out_sum += ts["out_changed"]
+    print("flicker over frames %d..%d: %d voxels between raw hulls, %d between voted hulls" % (temporal, n_frames - 1, raw_sum, out_sum))
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
 if out != "-":
     with open(out, "w") as f:

@@ -22,6 +22,7 @@ VC_MORPH_ERODE = 0
 VC_MORPH_OPEN = 1
 VC_GROW_DILATE = 0
 VC_GROW_CLOSE = 1
+VC_TEMPORAL_MAX_WINDOW = 15
 VC_GEO_SEEDS_LIST, VC_GEO_SEEDS_IZ_MAX, VC_GEO_SEEDS_IZ_MIN = 0, 1, 2
 VC_GEO_PATHS = 1
 VC_GEO_MAX_K = 32
@@ -47,11 +48,11 @@ c_f64p = ctypes.POINTER(ctypes.c_double)
 c_ctx = ctypes.c_void_p
 
 
-VC_KERNEL_KINDS, VC_WORK_KINDS = 25, 10
+VC_KERNEL_KINDS, VC_WORK_KINDS = 28, 10
 KERNEL_KINDS = ("k_prep_pack", "k_prep_grid", "k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble", "k_scan_groups",
                 "k_finish_scan", "k_emit", "one_launch_carve", "k_cull", "k_count_groups", "foot_table", "k_carve_foot",
                 "k_dist_box", "k_dist_y", "k_dist_env", "k_dist_records", "geo_seed", "k_geo_tiles", "k_geo_sweep", "geo_argmax",
-                "k_grow_mark", "grow_rank", "grow_merge")
+                "k_temporal_vote", "temporal_rank", "temporal_merge", "k_grow_mark", "grow_rank", "grow_merge")
 WORK_KINDS = ("word_boxes", "table_entries", "projections", "emit_projections", "brick_boxes", "foot_projections", "foot_union_skips",
               "foot_words", "dist_cells", "dist_lines")
 
@@ -103,6 +104,13 @@ class VcMorphStats(ctypes.Structure):
 class VcGrowStats(ctypes.Structure):
     _fields_ = [("survivors_before", ctypes.c_uint64), ("dilated", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64),
                 ("added", ctypes.c_uint64), ("box_cells", ctypes.c_uint64), ("q", ctypes.c_uint64 * 3), ("grow_ms", ctypes.c_float)]
+
+
+class VcTemporalStats(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_uint32), ("frames", ctypes.c_uint32), ("on", ctypes.c_uint32), ("off", ctypes.c_uint32),
+                ("survivors_before", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64), ("added", ctypes.c_uint64),
+                ("removed", ctypes.c_uint64), ("raw_changed", ctypes.c_uint64), ("out_changed", ctypes.c_uint64),
+                ("temporal_ms", ctypes.c_float)]
 
 
 class VcNormalsStats(ctypes.Structure):
@@ -218,6 +226,11 @@ SIGNATURES = {
     "vc_hull_morphology": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcMorphStats)]),
     "vc_hull_grow": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcGrowStats)]),
     "vc_fetch_grown": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_hull_temporal": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                        ctypes.POINTER(VcTemporalStats)]),
+    "vc_fetch_temporal": (ctypes.c_int, [c_ctx, c_u8p, c_u8p]),
+    "vc_fetch_temporal_history": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
+    "vc_temporal_reset": (ctypes.c_int, [c_ctx]),
     "vc_hull_normals": (ctypes.c_int, [c_ctx, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcNormalsStats)]),
     "vc_fetch_record_normals": (ctypes.c_int, [c_ctx, c_i16p]),
     "vc_shade_render": (ctypes.c_int, [c_ctx, c_f64p, ctypes.c_uint32, ctypes.c_uint32]),

@@ -165,7 +165,9 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
              "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None,
              "clusters": 0, "cluster_min_column": 1, "cluster_paint": False,
-             "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None}
+             "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None,
+             "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None}
+_temporal_state = {"last": None}
 _cluster_state = {"centres_mm": None, "references": None, "last": None}
 _geodesic_state = {"last": None}
 GEODESIC_PAINTS = (None, "labels", "distance")
@@ -208,7 +210,12 @@ def configure(frame_source=None, **settings):
     distances through the hull from the seed set ("floor", the default, "top", or an array of voxel indices) and the K
     extremities by farthest-point selection (head, hands, feet).  extremities() returns the last frame's.  geodesic_paint =
     "labels" | "distance" paints every voxel by its region or its distance (CarveEngine.paint_geodesic) before the positions and
-    colours are returned; None (the default) leaves the colours.  0 (the default) runs nothing."""
+    colours are returned; None (the default) leaves the colours.  0 (the default) runs nothing.
+    temporal_window, temporal_keep, temporal_keep_off: when temporal_window = T > 0 (at most 15), every carve is followed --
+    before hull_close_mm and everything else -- by CarveEngine.temporal_filter(T, temporal_keep, temporal_keep_off): the hull
+    becomes the vote of the last T frames' hulls (keep defaults to the majority, keep_off to keep), which takes the frame-to-frame
+    flicker of mask noise out and lags a moving figure by about T / 2 frames.  temporal() returns the last frame's stats.
+    0 (the default) runs nothing."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -236,7 +243,13 @@ def configure(frame_source=None, **settings):
     g = settings.get("geodesic_seeds", _settings["geodesic_seeds"])
     if isinstance(g, str) and g not in ("floor", "top"):
         raise ValueError("geodesic_seeds %r, expected \"floor\", \"top\" or an array of voxel indices" % (g,))
+    t = settings.get("temporal_window", _settings["temporal_window"])
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0:
+        raise ValueError("temporal_window %r, expected an integer in 0..15" % (t,))
+    CarveEngine.temporal_thresholds(t if t > 0 else 1, settings.get("temporal_keep", _settings["temporal_keep"]) if t > 0 else None,
+                                    settings.get("temporal_keep_off", _settings["temporal_keep_off"]) if t > 0 else None)
     _settings.update(settings)
+    _temporal_state.update(last=None)
     _cluster_state.update(centres_mm=None, references=None, last=None)
     _geodesic_state.update(last=None)
     _source = frame_source
@@ -297,6 +310,9 @@ def set_voxel_positions(width, height, depth):
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"],
                   footprint=_settings["footprint"])
+    if _settings["temporal_window"] > 0:
+        _temporal_state["last"] = _engine.temporal_filter(_settings["temporal_window"], _settings["temporal_keep"],
+                                                          _settings["temporal_keep_off"])
     if _settings["hull_close_mm"] > 0:
         _engine.close_hull(_settings["hull_close_mm"])
     if _settings["hull_open_mm"] > 0:
@@ -341,6 +357,14 @@ def _geodesic_frame():
     _geodesic_state["last"] = out
     if _settings["geodesic_paint"] is not None:
         _engine.paint_geodesic(_settings["geodesic_paint"])
+
+
+def temporal():
+    """The stats of the last set_voxel_positions call's vote over the last frames' hulls (configure(temporal_window=T)): the dict
+    of CarveEngine.temporal_filter."""
+    if _engine is None or not initialized or _temporal_state["last"] is None:
+        raise RuntimeError("no temporal vote: configure(temporal_window=T) and set_voxel_positions have not run")
+    return _temporal_state["last"]
 
 
 def extremities():

@@ -44,6 +44,7 @@
 #include "vc_footprint.h"
 #include "vc_distance.h"
 #include "vc_grow.h"
+#include "vc_temporal.h"
 #include "vc_normals.h"
 #include "vc_clusters.h"
 #include "vc_geodesic.h"
@@ -382,6 +383,20 @@ struct vc_ctx {
         uint64_t stamp = kNever;         // added belongs to the vc_hull_grow that produced the current result
         uint64_t n = 0;                  // its survivors_after
     } grow;
+    // vc_hull_temporal: the ring of the last `window` hulls ([window][npad] words, slot `head` the newest), the previous output P,
+    // the staging buffer of O_t (swapped with P by a finished call), the five counters and their read-back, the records' vote and
+    // `added` bytes.  Ring, P, window, head and pushes OUTLIVE a result: a carve leaves them alone, geometry_changed starts them over.
+    struct Temporal {
+        DevBuf<uint64_t> ring, prev, stage;
+        DevBuf<unsigned long long> ctr;
+        Pinned<uint64_t> h;              // page-locked read-back of the counters
+        DevBuf<uint8_t> votes, added;
+        uint64_t stamp = kNever;         // votes and added belong to the vc_hull_temporal that produced the current result
+        uint64_t n = 0;                  // its survivors_after
+        uint32_t window = 0, head = 0;   // the ring's length, the slot of the newest snapshot
+        uint64_t pushes = 0;             // calls since the last reset (0: ring and P are empty)
+        uint64_t nwords = 0, npad = 0;   // occupancy words of a snapshot, and the even count its slot holds
+    } temporal;
     // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
     struct Render {
         DevBuf<uint32_t> idx, rgbf;
@@ -511,6 +526,7 @@ void geometry_changed(vc_ctx *ctx)
 {
     ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false;
     ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
+    ctx->temporal.pushes = 0;                    // the hulls of another grid or other cameras are no history of this one
     result_changed(ctx);
 }
 
@@ -3089,6 +3105,172 @@ int vc_fetch_grown(vc_ctx *ctx, uint8_t *added)
     if (!ctx->carved || !ctx->current(ctx->grow.stamp)) return fail(ctx, VC_ERR_ARG, "no added flags: call vc_hull_grow on the current carve result");
     VC_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->grow.n) VC_HIP(ctx, hipMemcpy(added, ctx->grow.added.ptr, (size_t)ctx->grow.n, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+// ---- the vote over the last frames' hulls (vc_temporal.h; contract in include/voxcarve.h) ----
+int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t keep_off, uint32_t flags, vc_temporal_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: flags must be 0 (got %u)", flags);
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_temporal", "vote on", "temporal voting", pass));
+    if (window < 1 || window > VC_TEMPORAL_MAX_WINDOW)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: window %u not in [1, %u]", window, VC_TEMPORAL_MAX_WINDOW);
+    if (keep_on < 1 || keep_on > window) return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: keep_on %u not in [1, window = %u]", keep_on, window);
+    if (keep_off < 1 || keep_off > keep_on)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: keep_off %u not in [1, keep_on = %u]", keep_off, keep_on);
+    StepBuf &cur = *pass.cur;
+    const uint64_t n = pass.n, nwords = pass.nwords, npad = (nwords + 1) & ~1ull;
+    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: %llu voxels exceed the u32 index", (unsigned long long)n);
+    if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: frame set %u has been prepared again since the carve: its images are not the ones "
+                    "the records' colours came from", cur.slot);
+    vc_ctx::Temporal &T = ctx->temporal;
+    if (ctx->current(T.stamp))
+        return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: the current result is already the last call's output (one push per result): carve again first");
+    if (!n || cur.words.cap < npad) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_temporal: the result's %llu occupancy words are not padded to %llu",
+                                                (unsigned long long)cur.words.cap, (unsigned long long)npad);
+    VC_TRY(pass_begin(ctx));
+    // a ring of another window or another grid starts over; its buffers are made beside the old ones, which stay until the call commits
+    const bool restart = T.pushes == 0 || T.window != window || T.nwords != nwords;
+    const bool alloc = T.ring.cap < (size_t)window * npad || T.prev.cap < npad || T.stage.cap < npad || !T.ring.ptr;
+    DevBuf<uint64_t> ring2, prev2, stage2;
+    if (alloc) {
+        if (!restart) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_temporal: the ring holds %zu words, %u x %llu are in use", T.ring.cap, window,
+                                  (unsigned long long)npad);
+        VC_TRY(ensure(ctx, ring2, (size_t)window * npad));
+        VC_TRY(ensure(ctx, prev2, (size_t)npad));
+        VC_TRY(ensure(ctx, stage2, (size_t)npad));
+    }
+    VC_TRY(ensure(ctx, T.ctr, 8));
+    VC_HIP(ctx, ensure_pinned(T.h, 8));
+    const uint64_t have = restart ? 0 : std::min<uint64_t>(T.pushes, window);     // snapshots in the ring
+    const uint32_t m = (uint32_t)std::min<uint64_t>(have + 1, window);
+    const uint32_t on = (keep_on * m + window - 1) / window, off = (keep_off * m + window - 1) / window;
+    const uint64_t S0 = pass.S;
+    VC_TRY(pass_start(ctx, pass, kWordsAlways));
+    TemporalParams tp;
+    memset(&tp, 0, sizeof tp);
+    tp.ring = alloc ? ring2.ptr : T.ring.ptr;
+    tp.cur = cur.words.ptr;
+    tp.prev = restart ? nullptr : T.prev.ptr;
+    tp.stage = alloc ? stage2.ptr : T.stage.ptr;
+    tp.ctr = T.ctr.ptr;
+    tp.nwords = nwords; tp.npad = npad; tp.n = n;
+    tp.window = window; tp.head = restart ? 0 : T.head;
+    tp.count = m - 1;                            // (the ring's oldest slot is read only when the ring is not yet full)
+    tp.on = on; tp.off = off;
+    const dim3 vblock(kTemporalBlock), vgrid((uint32_t)((npad / 2 + kTemporalBlock - 1) / kTemporalBlock));
+    VC_HIP(ctx, hipMemsetAsync(T.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    VC_DLAUNCH(VC_K_TEMPORAL_VOTE, k_temporal_vote, vgrid, vblock, tp);
+    VC_HIP(ctx, hipGetLastError());
+    // the read-back in the middle: |O_t| sizes the records
+    VC_HIP(ctx, hipMemcpyAsync(T.h.ptr, T.ctr.ptr, kTemporalCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t S1 = T.h[0], added = T.h[1], removed = T.h[2], raw_changed = T.h[3], out_changed = T.h[4];
+    if (S1 > n || removed > S0 || S0 + added - removed != S1)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_temporal: %llu voted in, %llu added to and %llu removed from %llu survivors, in a grid of %llu voxels",
+                    (unsigned long long)S1, (unsigned long long)added, (unsigned long long)removed, (unsigned long long)S0, (unsigned long long)n);
+    const bool changed = added || removed;
+    // every buffer of the hand-over before anything is committed: a failure leaves result, ring and P
+    const uint32_t wgroups = word_groups(nwords);
+    VC_TRY(ensure(ctx, T.votes, (size_t)S1));
+    VC_TRY(ensure(ctx, T.added, (size_t)S1));
+    VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
+    VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
+    if (changed) VC_TRY(ensure(ctx, ctx->d_rec_spare, std::max<size_t>(cur.records.cap, (size_t)S1)));
+    // committed from here on: the ring takes H_t, the result O_t, P the staging buffer
+    T.stamp = kNever;
+    if (alloc) { T.ring = std::move(ring2); T.prev = std::move(prev2); T.stage = std::move(stage2); }
+    if (restart) {
+        VC_HIP(ctx, hipMemsetAsync(T.ring.ptr, 0, (size_t)window * npad * sizeof(uint64_t), ctx->stream));   // (the slots' pads stay zero)
+        T.window = window; T.nwords = nwords; T.npad = npad;
+        T.head = window - 1;
+        T.pushes = 0;
+    }
+    T.head = (T.head + 1) % window;
+    T.pushes += 1;
+    VC_HIP(ctx, hipMemcpyAsync(T.ring.ptr + (size_t)T.head * npad, cur.words.ptr, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(T.added.ptr, 0, std::max<size_t>((size_t)S1, 1), ctx->stream));
+    GrowParams g;
+    memset(&g, 0, sizeof g);
+    g.xs = cur.emit.xs; g.ys = cur.emit.ys; g.zs = cur.emit.zs;
+    g.has_cam = cur.emit.has_cam && cur.emit.xs ? 1 : 0;
+    g.cam = cur.emit.cam;
+    g.frame = cur.emit.frame;
+    g.words = cur.words.ptr; g.woff = ctx->d_cc_woff.ptr;
+    g.out = ctx->d_rec_spare.ptr; g.added = T.added.ptr;
+    g.S1 = S1;
+    g.nx = ctx->nx; g.ny = ctx->ny; g.nz = ctx->nz; g.H = ctx->H; g.W = ctx->W;
+    tp.ring = T.ring.ptr; tp.head = T.head; tp.count = m; tp.cur = nullptr; tp.prev = nullptr;
+    const dim3 gblock(kGrowBlock), wgrid((uint32_t)((nwords + kGrowBlock - 1) / kGrowBlock));
+    if (changed) {
+        result_changed(ctx);
+        VC_HIP(ctx, hipMemcpyAsync(cur.words.ptr, tp.stage, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        // survivors per group of the step, counted again: the packing skips the groups whose count is zero
+        const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
+        VC_DLAUNCH(VC_K_TEMPORAL_RANK, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups,
+                   cur.groupcnt.ptr);
+    }
+    if (changed || S1) VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_cc_woff, ctx->h_res + 2, VC_K_TEMPORAL_RANK));
+    if (changed) {
+        // the merged list into the spare buffer: every old record of O_t to its new rank, a fresh record for every restored voxel
+        if (S0) VC_DLAUNCH(VC_K_TEMPORAL_MERGE, k_temporal_old, dim3((uint32_t)((S0 + kGrowBlock - 1) / kGrowBlock)), gblock, g,
+                           (const uint64_t *)cur.records.ptr, S0, nwords);
+        if (S1) VC_DLAUNCH(VC_K_TEMPORAL_MERGE, k_temporal_new<true>, wgrid, gblock, g, tp, T.votes.ptr);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(records_handed_over(ctx, cur, wgroups));
+    } else if (S1) {
+        // O_t = H_t: records, occupancy and every product of a pass stay; only the vote bytes are made
+        VC_DLAUNCH(VC_K_TEMPORAL_RANK, k_temporal_new<false>, wgrid, gblock, g, tp, T.votes.ptr);
+        VC_HIP(ctx, hipGetLastError());
+    }
+    std::swap(T.prev, T.stage);                  // (the launches above hold the pointers they were given)
+    VC_TRY(pass_end(ctx, pass, &stats->temporal_ms));
+    if (changed) ctx->survivors = cur.survivors = S1;
+    if ((changed || S1) && ctx->h_res[2] != S1)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_temporal: the new occupancy holds %llu voxels, %llu were voted in", (unsigned long long)ctx->h_res[2],
+                    (unsigned long long)S1);
+    stats->window = window; stats->frames = m; stats->on = on; stats->off = off;
+    stats->survivors_before = S0; stats->survivors_after = S1;
+    stats->added = added; stats->removed = removed;
+    stats->raw_changed = raw_changed; stats->out_changed = out_changed;
+    T.stamp = ctx->result_gen;
+    T.n = S1;
+    return VC_OK;
+}
+
+int vc_fetch_temporal(vc_ctx *ctx, uint8_t *votes, uint8_t *added)
+{
+    if (!ctx) return VC_ERR_ARG;
+    const vc_ctx::Temporal &T = ctx->temporal;
+    if (!ctx->carved || !ctx->current(T.stamp)) return fail(ctx, VC_ERR_ARG, "no votes: call vc_hull_temporal on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (votes && T.n) VC_HIP(ctx, hipMemcpy(votes, T.votes.ptr, (size_t)T.n, hipMemcpyDeviceToHost));
+    if (added && T.n) VC_HIP(ctx, hipMemcpy(added, T.added.ptr, (size_t)T.n, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_fetch_temporal_history(vc_ctx *ctx, uint32_t age, uint8_t *bits)
+{
+    if (!ctx || !bits) return VC_ERR_ARG;
+    const vc_ctx::Temporal &T = ctx->temporal;
+    const uint64_t m = std::min<uint64_t>(T.pushes, T.window);
+    if (age >= m) return fail(ctx, VC_ERR_ARG, "vc_fetch_temporal_history: age %u, the ring holds %llu hulls", age, (unsigned long long)m);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint32_t slot = (T.head + T.window - age) % T.window;
+    VC_HIP(ctx, hipMemcpy(bits, T.ring.ptr + (size_t)slot * T.npad, (size_t)T.nwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_temporal_reset(vc_ctx *ctx)
+{
+    if (!ctx) return VC_ERR_ARG;
+    ctx->temporal.pushes = 0;
+    ctx->temporal.stamp = kNever;
     return VC_OK;
 }
 

@@ -626,6 +626,55 @@ class CarveEngine:
         self._check(self._L.vc_fetch_grown(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_grown")
         return out
 
+    # -- the vote over the last frames' hulls (vc_hull_temporal): the one pass whose state outlives a result ------------------------
+    @staticmethod
+    def temporal_thresholds(window=5, keep=None, keep_off=None):
+        """(window, keep_on, keep_off) as temporal_filter takes them: keep defaults to window // 2 + 1 (the majority), keep_off to
+        keep (no hysteresis); ValueError unless they are integers with 1 <= keep_off <= keep <= window <= 15."""
+        keep = window // 2 + 1 if keep is None and isinstance(window, (int, np.integer)) else keep
+        keep_off = keep if keep_off is None else keep_off
+        for name, v in (("window", window), ("keep", keep), ("keep_off", keep_off)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("temporal %s %r, expected an integer" % (name, v))
+        if not 1 <= keep_off <= keep <= window <= _lib.VC_TEMPORAL_MAX_WINDOW:
+            raise ValueError("temporal window %d, keep %d, keep_off %d: expected 1 <= keep_off <= keep <= window <= %d"
+                             % (window, keep, keep_off, _lib.VC_TEMPORAL_MAX_WINDOW))
+        return int(window), int(keep), int(keep_off)
+
+    def temporal_filter(self, window=5, keep=None, keep_off=None):
+        """Pushes the current carve result onto a ring of the last `window` hulls on the device and replaces it by their vote: a
+        voxel enters when at least `keep` of the hulls hold it (default: the majority) and, once in, stays while at least keep_off
+        do (default: keep, a plain vote); the thresholds scale with the ring while it fills, so the first call returns the hull
+        as it is.  Restored voxels are coloured from the colour camera as close_hull colours (contract: include/voxcarve.h).  The
+        ring survives carves; temporal_reset, set_grid / set_cameras and another window start it over.  One call per carve.
+        Returns the stats as a dict: window, frames, on, off, survivors_before, survivors_after, added, removed, raw_changed,
+        out_changed, temporal_ms."""
+        window, keep, keep_off = self.temporal_thresholds(window, keep, keep_off)
+        st = _lib.VcTemporalStats()
+        self._check(self._L.vc_hull_temporal(self._ctx, window, keep, keep_off, 0, ctypes.byref(st)), "vc_hull_temporal")
+        self.count = int(st.survivors_after)
+        out = {name: int(getattr(st, name)) for name, _ in _lib.VcTemporalStats._fields_ if name != "temporal_ms"}
+        out["temporal_ms"] = float(st.temporal_ms)
+        return out
+
+    def fetch_temporal(self):
+        """(votes, added), u8 [S] each in record order: in how many of the ring's hulls the record's voxel is, and 1 where the last
+        temporal_filter created the record (fails once a carve or a pass that changes the survivors has run since)."""
+        votes, added = np.empty(self.count, dtype=np.uint8), np.empty(self.count, dtype=np.uint8)
+        self._check(self._L.vc_fetch_temporal(self._ctx, _ptr(votes, ctypes.c_uint8), _ptr(added, ctypes.c_uint8)), "vc_fetch_temporal")
+        return votes, added
+
+    def temporal_history(self, age):
+        """The raw hull that temporal_filter pushed `age` calls ago (0 = the last one) as occupancy words, uint64 [ceil(N / 64)]
+        laid out as vc_fetch_occupancy; fails for an age the ring does not hold."""
+        raw = np.empty((self.n_voxels + 63) // 64 if self.grid is not None else 0, dtype=np.uint64)
+        self._check(self._L.vc_fetch_temporal_history(self._ctx, int(age), raw.ctypes.data_as(_lib.c_u8p)), "vc_fetch_temporal_history")
+        return raw
+
+    def temporal_reset(self):
+        """Forgets the ring of hulls and the previous output: the next temporal_filter returns its hull as it is."""
+        self._check(self._L.vc_temporal_reset(self._ctx), "vc_temporal_reset")
+
     # -- ray-cast images of the current result (vc_render) --------------------------------------------------------------------------
     def render(self, views, H, W, shade=None, background=(0, 0, 0)):
         """Ray-casts the current carve result (after color_visible / photo_carve / filter_components, as fetch sees it) from each
