@@ -70,9 +70,9 @@ typedef enum {
     VC_K_GEO_SEED /* k_geo_seed_list, k_geo_seed_layers, k_geo_source */, VC_K_GEO_TILES /* k_geo_tiles */,
     VC_K_GEO_SWEEP /* k_geo_sweep */, VC_K_GEO_ARGMAX /* k_geo_best + k_geo_pick */,
     VC_K_TEMPORAL_VOTE /* k_temporal_vote */, VC_K_TEMPORAL_RANK /* k_count_groups, k_cc_wcount, k_cc_woff, k_temporal_new<votes only> */,
-    VC_K_TEMPORAL_MERGE /* k_temporal_old + k_temporal_new */,
+    VC_K_TEMPORAL_MERGE /* k_merge_old + k_temporal_new */,
     VC_K_GROW_MARK /* k_grow_mark: the new set's bits and counts */, VC_K_GROW_RANK /* k_grow_apply, k_count_groups, k_cc_wcount, k_cc_woff */,
-    VC_K_GROW_MERGE /* k_grow_old + k_grow_new */
+    VC_K_GROW_MERGE /* k_merge_old + k_grow_new */
 } vc_kernel_kind;
 #define VC_KERNEL_KINDS 28
 enum {

@@ -3,7 +3,8 @@ vc_temporal_reset; csrc/vc_temporal.h) against the restatement (tests/temporal_n
 indices, order, all 8 bytes of every record, the vote and `added` bytes, the occupancy words, every snapshot of the ring and every
 stat.  Random scenes whose hulls change from frame to frame on grids of 2, 11, 889 and 120 words, windows 1, 2, 5 and 15 with
 plain votes and hysteresis, thresholds changed mid-sequence, an empty hull and a solid grid inside a sequence, restored voxels
-inside and outside the colour camera's image, no colour camera; the real cameras at 64^3 with seeded mask noise in both carve
+inside and outside the colour camera's image, no colour camera; closings, dilations and erosions between the votes of one
+sequence (the record merge both adding passes share); the real cameras at 64^3 with seeded mask noise in both carve
 modes; the state rules; the readers of the voted hull; a call that changes nothing; every refusal; the launch counts;
 configure(temporal_window=...); 512^3 on invariants."""
 import ctypes
@@ -133,6 +134,45 @@ def test_random_sequences_equal_restatement(teng, grid, seed, mv, window, pairs)
             assert unseen > 0
     else:
         assert restored == dropped == 0                              # window 1 is the identity
+
+
+@pytest.mark.parametrize("grid,seed,mv,window,mm", [((9, 130, 12), 6, 1, 3, 250), ((37, 53, 29), 4, 2, 5, 100), ((12, 64, 10), 7, 2, 2, 250)])
+def test_votes_on_grown_hulls(teng, grid, seed, mv, window, mm):
+    """The two passes that add voxels in one sequence, through the record merge they share: a closing before the vote on odd frames
+    (the vote moves records a closing made, `added` colours included), a dilation straight after the vote on every third (a merge
+    after a merge) and an erosion after both (a compaction of merged records).  Lines that straddle occupancy words with a partial
+    last word; several 64-word groups with n % 64 != 0; lines of exactly one word in two groups."""
+    from test_gpu_closing import _check_grow
+    from test_gpu_distance import _check_morph
+    cams3, masks3, frames3 = fx.random_scene(seed, C=3, fg=0.7)
+    _start(teng, grid, cams3, masks3, frames3)
+    teng.temporal_reset()
+    f = Follower(teng, cams3, frames3)
+    closed = voted_in = voted_out = kept = dropped = first_of_word = 0
+    for t in range(2 * window + 2):
+        teng.upload_masks(_scene_masks(seed, t, 0.7))
+        teng.carve(min_views=mv)
+        grown = np.empty(0, np.uint64)
+        if t % 2 == 1:
+            st, want, added = _check_grow(teng, "close", cams3, frames3, mm=mm)
+            closed += st["added"]
+            grown = want[added == 1] & LOW
+        before = teng.fetch_records() & LOW
+        st, want, added = f.step(window, (window + 2) // 2, 1)
+        voted_in += st["added"]
+        voted_out += st["removed"]
+        stays = np.isin(grown, want & LOW)
+        kept += int(stays.sum())
+        dropped += int((~stays).sum())
+        first_of_word += int((~np.isin((want[added == 1] & LOW) >> np.uint64(6), before >> np.uint64(6))).sum())
+        if t % 3 == 2:
+            _check_grow(teng, "dilate", cams3, frames3, mm=mm)
+            _check_morph(teng, "erode", mm)
+    print("closings added %d, votes added %d and removed %d, grown voxels kept %d and dropped %d, restored as the first of a word %d"
+          % (closed, voted_in, voted_out, kept, dropped, first_of_word))
+    assert closed > 0 and voted_in > 0 and voted_out > 0 and kept > 0 and dropped > 0
+    if grid != (12, 64, 10):
+        assert first_of_word > 0
 
 
 def test_solid_grid_in_a_sequence(teng, cams, masks, frames):
@@ -396,7 +436,7 @@ def test_timing_reports_the_kernels(built, cams, masks, frames):
         st = e.temporal_filter(5)
         k = e.timing()["kernels"]
         assert st["added"] > 0 and st["removed"] > 0
-        # rank: k_count_groups, k_cc_wcount, k_cc_woff; merge: k_temporal_old, k_temporal_new
+        # rank: k_count_groups, k_cc_wcount, k_cc_woff; merge: k_merge_old, k_temporal_new
         assert k["k_temporal_vote"]["launches"] == 1 and k["temporal_rank"]["launches"] == 3 and k["temporal_merge"]["launches"] == 2
         assert all(k[name]["ms_sum"] > 0 for name in ("k_temporal_vote", "temporal_rank", "temporal_merge"))
         assert "k_grow_mark" not in k and "grow_merge" not in k

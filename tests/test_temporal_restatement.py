@@ -214,7 +214,7 @@ def test_public_names():
     assert _lib.KERNEL_KINDS[at:] == ("k_temporal_vote", "temporal_rank", "temporal_merge", "k_grow_mark", "grow_rank", "grow_merge")
     assert _lib.KERNEL_KINDS[at - 4:at] == ("geo_seed", "k_geo_tiles", "k_geo_sweep", "geo_argmax")
     makefile = open(os.path.join(os.path.dirname(_lib.__file__), "csrc", "Makefile")).read()
-    assert "vc_temporal.h" in makefile
+    assert "vc_temporal.h" in makefile and "vc_merge.h" in makefile
     for name in ("temporal_filter", "fetch_temporal", "temporal_history", "temporal_reset"):
         assert callable(getattr(CarveEngine, name))
     assert CarveEngine.temporal_thresholds() == (5, 3, 3) and CarveEngine.temporal_thresholds(8) == (8, 5, 5)

@@ -11,13 +11,11 @@
 //                      make one atomic per workgroup.  MODE = kGrowCount only counts the cells with f <= r2 (|Dl| of a closing)
 //   k_grow_apply       lane = word of the range: the added bits into the occupancy words
 //   k_cc_wcount, scan_counts, k_cc_woff   (vc_components.h) survivors before each word of the new occupancy
-//   k_grow_old         lane = old record: to its new rank, its 8 bytes unchanged
-//   k_grow_new         lane = word of the range: a fresh record for each added bit at its rank, coloured as the footprint carve
-//                      colours (one float64 projection of the centre, the in-image test, one load from the colour camera's
-//                      image in record layout; the mask is not consulted), and the record's `added` byte
+//   k_merge_old        (vc_merge.h) every old record to its new rank
+//   k_grow_new         lane = word of the range: a fresh record (merge_fresh, vc_merge.h) for each added bit at its rank
 // Every index formed from the box is checked against the grid before it is used.
 #pragma once
-#include "vc_components.h"       // cc_below (vc_kernels.h: decompose, wave_sum_u32, kSeenFlag; vc_device.h: project_point, pixel_offset)
+#include "vc_merge.h"            // MergeParams, merge_fresh (vc_components.h: cc_below; vc_kernels.h: wave_sum_u32)
 #include "vc_distance.h"         // DistBox, kDistBlock, kDistInf
 
 namespace vc {
@@ -26,20 +24,6 @@ constexpr uint32_t kGrowLines = 8;                           // y lines per wave
 constexpr uint32_t kGrowBlock = 256;
 
 enum { kGrowDilate = 0, kGrowClose = 1, kGrowCount = 2 };
-
-struct GrowParams {
-    const double *xs, *ys, *zs;
-    const uint32_t *frame;      // the colour camera's image, one dword per pixel in record layout (or null)
-    const uint64_t *words;      // the NEW occupancy
-    const uint32_t *woff;       // [nwords] survivors before each word of it
-    const unsigned long long *addw;   // [nrange] added bits of words w0 ..
-    uint64_t *out;              // [S1] the merged records
-    uint8_t *added;             // [S1] 1 = created by this call (zeroed beforehand)
-    uint64_t w0, nrange, S1;
-    uint32_t nx, ny, nz, H, W;
-    int has_cam;
-    CamDev cam;
-};
 
 template <int MODE>
 __global__ __launch_bounds__(kDistBlock) void k_grow_mark(const DistBox bx, const uint64_t *__restrict__ f, uint64_t r2,
@@ -106,41 +90,21 @@ __global__ __launch_bounds__(kGrowBlock) void k_grow_apply(uint64_t *__restrict_
     if (a) words[w0 + k] |= a;
 }
 
-__global__ __launch_bounds__(kGrowBlock) void k_grow_old(const GrowParams p, const uint64_t *__restrict__ records, uint64_t S0, uint64_t nwords)
-{
-    const uint64_t s = (uint64_t)blockIdx.x * kGrowBlock + threadIdx.x;
-    if (s >= S0) return;
-    const uint64_t rec = records[s];
-    const uint32_t i = (uint32_t)rec, w = i >> 6;
-    if (w >= nwords) return;
-    const uint64_t r = (uint64_t)p.woff[w] + (uint32_t)__popcll(p.words[w] & cc_below(i & 63u));
-    if (r < p.S1) p.out[r] = rec;
-}
-
-__global__ __launch_bounds__(kGrowBlock) void k_grow_new(const GrowParams p, uint64_t nwords)
+// addw: [nrange] added bits of words w0 ..
+__global__ __launch_bounds__(kGrowBlock) void k_grow_new(const MergeParams p, const unsigned long long *__restrict__ addw, uint64_t w0,
+                                                          uint64_t nrange, uint64_t nwords)
 {
     const uint64_t k = (uint64_t)blockIdx.x * kGrowBlock + threadIdx.x;
-    if (k >= p.nrange || p.w0 + k >= nwords) return;
-    uint64_t a = p.addw[k];
+    if (k >= nrange || w0 + k >= nwords) return;
+    uint64_t a = addw[k];
     if (!a) return;
-    const uint64_t w = p.w0 + k, nw = p.words[w];
+    const uint64_t w = w0 + k, nw = p.words[w];
     const uint64_t rank0 = p.woff[w];
     while (a) {
         const uint32_t b = (uint32_t)__ffsll((unsigned long long)a) - 1u;
         a &= a - 1;
-        const uint64_t i = (w << 6) + b, r = rank0 + (uint32_t)__popcll(nw & cc_below(b));
-        uint32_t ix, iy, iz;
-        decompose((uint32_t)i, p.nx, p.ny, ix, iy, iz);
-        if (iz >= p.nz || r >= p.S1) continue;
-        uint64_t rec = (uint32_t)i;
-        if (p.has_cam) {
-            double u, v;
-            project_point(p.cam, p.xs[ix], p.ys[iy], p.zs[iz], u, v);
-            const int32_t off = pixel_offset(u, v, p.H, p.W);
-            if (off >= 0) rec |= (p.frame ? (uint64_t)p.frame[off] : (uint64_t)kSeenFlag) << 32;   // R | G<<8 | B<<16 | seen<<24
-        }
-        p.out[r] = rec;
-        p.added[r] = 1;
+        const uint64_t r = rank0 + (uint32_t)__popcll(nw & cc_below(b));
+        if (r < p.S1) merge_fresh(p, (w << 6) + b, r);
     }
 }
 

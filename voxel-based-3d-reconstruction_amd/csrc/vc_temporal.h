@@ -10,13 +10,12 @@
 //                      buffer.  |O|, added, removed, raw_changed and out_changed are popcounts, summed over the wave and the
 //                      workgroup: one atomic per counter per workgroup.  The result's words are only read
 //   k_cc_wcount, scan_counts, k_cc_woff   (vc_components.h) survivors before each word of O
-//   k_temporal_old     lane = old record: to its new rank, its 8 bytes unchanged, when its bit is in O
+//   k_merge_old        (vc_merge.h) every old record whose bit is in O to its new rank
 //   k_temporal_new     lane = word of O: the planes again from the ring (which now holds the newest snapshot), the vote byte of each
-//                      set bit at its rank; RECORDS: a fresh record for each bit of O & ~H_t, coloured as k_grow_new colours, and
-//                      its `added` byte
+//                      set bit at its rank; RECORDS: a fresh record (merge_fresh, vc_merge.h) for each bit of O & ~H_t
 // Every word index is checked against nwords before it is used, every rank against S1.
 #pragma once
-#include "vc_grow.h"             // GrowParams, kGrowBlock (vc_components.h: cc_below; vc_kernels.h: decompose, wave_sum_u32)
+#include "vc_merge.h"            // MergeParams, merge_fresh, kMergeBlock (vc_components.h: cc_below; vc_kernels.h: wave_sum_u32)
 
 namespace vc {
 
@@ -151,24 +150,10 @@ __global__ __launch_bounds__(kTemporalBlock) void k_temporal_vote(const Temporal
     }
 }
 
-// g.words: O; g.woff: survivors before each word of it; g.out: the merged records; g.S1 = |O|
-__global__ __launch_bounds__(kGrowBlock) void k_temporal_old(const GrowParams g, const uint64_t *__restrict__ records, uint64_t S0, uint64_t nwords)
-{
-    const uint64_t s = (uint64_t)blockIdx.x * kGrowBlock + threadIdx.x;
-    if (s >= S0) return;
-    const uint64_t rec = records[s];
-    const uint32_t i = (uint32_t)rec, w = i >> 6, b = i & 63u;
-    if (w >= nwords) return;
-    const uint64_t o = g.words[w];
-    if (!((o >> b) & 1ull)) return;                              // voted out
-    const uint64_t r = (uint64_t)g.woff[w] + (uint32_t)__popcll(o & cc_below(b));
-    if (r < g.S1) g.out[r] = rec;
-}
-
 template <bool RECORDS>
-__global__ __launch_bounds__(kGrowBlock) void k_temporal_new(const GrowParams g, const TemporalParams p, uint8_t *__restrict__ votes)
+__global__ __launch_bounds__(kMergeBlock) void k_temporal_new(const MergeParams g, const TemporalParams p, uint8_t *__restrict__ votes)
 {
-    const uint64_t w = (uint64_t)blockIdx.x * kGrowBlock + threadIdx.x;
+    const uint64_t w = (uint64_t)blockIdx.x * kMergeBlock + threadIdx.x;
     if (w >= p.nwords) return;
     const uint64_t o = g.words[w] & tp_valid(w, p.n);
     if (!o) return;
@@ -183,21 +168,7 @@ __global__ __launch_bounds__(kGrowBlock) void k_temporal_new(const GrowParams g,
         const uint64_t r = rank0 + (uint32_t)__popcll(o & cc_below(b));
         if (r >= g.S1) continue;
         votes[r] = (uint8_t)(((pl.b0 >> b) & 1ull) | (((pl.b1 >> b) & 1ull) << 1) | (((pl.b2 >> b) & 1ull) << 2) | (((pl.b3 >> b) & 1ull) << 3));
-        if (RECORDS && ((fresh >> b) & 1ull)) {
-            const uint64_t i = (w << 6) + b;
-            uint32_t ix, iy, iz;
-            decompose((uint32_t)i, g.nx, g.ny, ix, iy, iz);
-            if (iz >= g.nz) continue;
-            uint64_t rec = (uint32_t)i;
-            if (g.has_cam) {
-                double u, v;
-                project_point(g.cam, g.xs[ix], g.ys[iy], g.zs[iz], u, v);
-                const int32_t off = pixel_offset(u, v, g.H, g.W);
-                if (off >= 0) rec |= (g.frame ? (uint64_t)g.frame[off] : (uint64_t)kSeenFlag) << 32;   // R | G<<8 | B<<16 | seen<<24
-            }
-            g.out[r] = rec;
-            g.added[r] = 1;
-        }
+        if (RECORDS && ((fresh >> b) & 1ull)) merge_fresh(g, (w << 6) + b, r);
     }
 }
 

@@ -331,10 +331,10 @@ struct vc_ctx {
     bool current(uint64_t stamp) const { return stamp == result_gen; }
     // Scratch the passes over the result share, one after the other on the context's stream.  h_res holds each pass's own read-backs
     // (photo: [0] removal count of the round, low 32 bits, [1] compaction total; components: [0] components, [1] kept records, [2] misc)
-    ScanBufs d_rscan;                // scans of the compactions (photo, components, morphology) and of word_offsets (components, grow, normals, geodesic)
-    DevBuf<uint64_t> d_rec_spare;    // the records' second buffer: a compaction's or the grow merge's target, then swapped with the step's
+    ScanBufs d_rscan;                // scans of the compactions (photo, components, morphology) and of word_offsets (components, grow, temporal, normals, geodesic)
+    DevBuf<uint32_t> d_woff;         // survivors before each occupancy word (word_offsets), good for the pass that made it only: components, grow, temporal, normals
+    DevBuf<uint64_t> d_rec_spare;    // the records' second buffer: a compaction's or a merge's target, then swapped with the step's
     Pinned<uint64_t> h_res;          // three pinned scalars (pass_begin makes them)
-    DevBuf<uint32_t> d_cc_woff;      // survivors before each word: the components', borrowed by vc_hull_grow for the ranks of the new occupancy
     std::vector<Event> dist_ev;      // timing_detail: begin / end events of the launches of distance, morphology, grow and geodesic (VC_DLAUNCH), made on first use
     std::vector<int> dist_ev_kind;   // the kernel kind of each pair the running call has used
     // What each pass over the result keeps: its buffers, its stamp (see result_gen), its counts, its options.
@@ -355,7 +355,7 @@ struct vc_ctx {
         uint64_t n = 0;                  // its input survivors
     } photo;
     // vc_hull_components: the union-find forest, labels, component numbers of the roots, the root list, sizes, boxes, keep flags,
-    // component entries, [kept components, largest], the select threshold (the survivors before each word: vc_ctx::d_cc_woff)
+    // component entries, [kept components, largest], the select threshold (the survivors before each word: vc_ctx::d_woff)
     struct Components {
         DevBuf<uint32_t> parent, label, cid, roots, size, box, comp, misc;
         DevBuf<uint8_t> kept;
@@ -421,10 +421,10 @@ struct vc_ctx {
         uint64_t stamp = kNever;         // the last surface mesh was made on the current result (valid outlives a carve)
         int order = 1;                   // vc_surface_mesh tries the cameras that rejected P_off first (same results)
     } surface;
-    // vc_hull_normals: survivors before each word, the ball's rows, the records' quadruples, [surface, zero]; the shaded images of
+    // vc_hull_normals: the ball's rows, the records' quadruples, [surface, zero]; the shaded images of
     // vc_shade_render ([V][H W] R | G << 8 | B << 16) and its lights; the quadruples of the last mesh's vertices
     struct Normals {
-        DevBuf<uint32_t> woff, rows, sh_rgb;
+        DevBuf<uint32_t> rows, sh_rgb;
         DevBuf<short4> out, verts;
         DevBuf<unsigned long long> ctr;
         DevBuf<double> sh_light;
@@ -1098,6 +1098,49 @@ int scan_counts(vc_ctx *ctx, hipStream_t st, ScanBufs &b, const uint32_t *cnt, u
     return VC_OK;
 }
 
+// timing_detail: the begin / end events a launch of the distance passes is to carry (null otherwise: an ordinary launch)
+static void dist_events(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
+{
+    start = stop = nullptr;
+    if (!ctx->timing_detail) return;
+    const size_t at = 2 * ctx->dist_ev_kind.size();
+    while (ctx->dist_ev.size() < at + 2) {
+        Event e;
+        if (make_event(e) != hipSuccess) return;
+        ctx->dist_ev.push_back(std::move(e));
+    }
+    start = ctx->dist_ev[at]; stop = ctx->dist_ev[at + 1];
+    ctx->dist_ev_kind.push_back(kind);
+}
+#define VC_DLAUNCH(kind, kernel, grid, block, ...)                                                      \
+    do {                                                                                                \
+        hipEvent_t ks_, ke_;                                                                            \
+        dist_events(ctx, kind, ks_, ke_);                                                               \
+        hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ks_, ke_, 0, __VA_ARGS__);           \
+    } while (0)
+
+// Survivors before each occupancy word of the step, as vc_components.h counts them, into woff[nwords]: popcounts per 64 words,
+// their scan in ctx->d_rscan, the wave scan inside each group.  The survivor total lands in *total_host once the stream has
+// drained.  kind >= 0: the launches carry that kind's events (VC_DLAUNCH).  Buffers sized by the caller (d_rscan: word_groups).
+static uint32_t word_groups(uint64_t nwords) { return (uint32_t)((nwords + 63) / 64); }   // 64 words per group: <= 2^20 groups
+
+static int word_offsets(vc_ctx *ctx, const StepBuf &cur, uint64_t nwords, DevBuf<uint32_t> &woff, uint64_t *total_host, int kind = -1)
+{
+    const uint32_t wgroups = word_groups(nwords);
+    const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), block(kCcBlock);
+    const uint64_t *words = cur.words.ptr;
+    if (kind >= 0) VC_DLAUNCH(kind, k_cc_wcount, wgrid, block, words, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+    else hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, words, nwords, wgroups, ctx->d_rscan.cnt.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, total_host));
+    const uint32_t *off = ctx->d_rscan.off.ptr;                  // (read-only to k_cc_woff, as the words are)
+    const uint64_t *boff = ctx->d_rscan.boff.ptr;
+    if (kind >= 0) VC_DLAUNCH(kind, k_cc_woff, wgrid, block, words, nwords, wgroups, off, boff, woff.ptr);
+    else hipLaunchKernelGGL(k_cc_woff, wgrid, block, 0, ctx->stream, words, nwords, wgroups, off, boff, woff.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
 // Stable compaction of records [0, S) by sel (vc_compact.h) on the context's stream, in the scan scratch of the passes over the
 // result (ctx->d_rscan); the count lands in *total_host once the stream has drained, and in d_rscan.boff[nscan].
 template <class Sel>
@@ -1140,6 +1183,62 @@ int compact_records(vc_ctx *ctx, StepBuf &cur, Sel sel, uint64_t S, uint64_t *to
     sel.out = ctx->d_rec_spare.ptr;
     VC_TRY(compact(ctx, sel, S, total_host));
     return records_handed_over(ctx, cur, (uint32_t)((S + kCompactGroup - 1) / kCompactGroup));
+}
+
+// ---- the other route to new records: the occupancy gained (and possibly lost) voxels (vc_merge.h) ----
+// A pass of this kind (vc_hull_grow, vc_hull_temporal) marks or votes and reads the new count S1 back; then merge_sized, its change
+// of the words, merge_ranked, its own kernel over the words for the fresh records, records_handed_over; after pass_end, merge_counted.
+int merge_refuse_slot(vc_ctx *ctx, const char *what, const StepBuf &cur)
+{
+    if (cur.slot < ctx->slots.size() && ctx->slots[cur.slot].gen == cur.slot_gen) return VC_OK;
+    return fail(ctx, VC_ERR_ARG, "%s: frame set %u has been prepared again since the carve: its images are not the ones "
+                "the records' colours came from", what, cur.slot);
+}
+
+int merge_refuse_index(vc_ctx *ctx, const char *what, uint64_t n)
+{
+    return n > 0xffffffffull ? fail(ctx, VC_ERR_ARG, "%s: %llu voxels exceed the u32 index", what, (unsigned long long)n) : VC_OK;
+}
+
+// Every buffer of the route, before result, ring or P is touched (a failed allocation leaves them all as they were), and the kernels'
+// parameters, which point into them.  records = false: only the ranks are wanted; added: the pass's own [S1] bytes, zeroed
+int merge_sized(vc_ctx *ctx, const StepBuf &cur, uint64_t nwords, uint64_t S1, bool records, uint8_t *added, MergeParams &p)
+{
+    VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
+    VC_TRY(ensure(ctx, ctx->d_woff, (size_t)nwords));
+    if (records) VC_TRY(ensure(ctx, ctx->d_rec_spare, std::max<size_t>(cur.records.cap, (size_t)S1)));
+    memset(&p, 0, sizeof p);
+    p.xs = cur.emit.xs; p.ys = cur.emit.ys; p.zs = cur.emit.zs;
+    p.has_cam = cur.emit.has_cam && cur.emit.xs ? 1 : 0;
+    p.cam = cur.emit.cam;
+    p.frame = cur.emit.frame;
+    p.words = cur.words.ptr; p.woff = ctx->d_woff.ptr;
+    p.out = ctx->d_rec_spare.ptr; p.added = added;
+    p.S1 = S1;
+    p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.H = ctx->H; p.W = ctx->W;
+    return VC_OK;
+}
+
+// Ranks of the occupancy into d_woff, their total into h_res[2].  changed: the words are new, so the survivors per group of the step
+// are counted again (the packing skips the groups whose count is zero) and every old record that stays goes to its new rank in the
+// spare buffer.  The launches run under the pass's two kinds.
+int merge_ranked(vc_ctx *ctx, StepBuf &cur, const MergeParams &p, uint64_t nwords, uint64_t S0, bool changed, int rank_kind, int merge_kind)
+{
+    if (changed) {
+        const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
+        VC_DLAUNCH(rank_kind, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups, cur.groupcnt.ptr);
+    }
+    VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_woff, ctx->h_res + 2, rank_kind));
+    const dim3 ogrid((uint32_t)((S0 + kMergeBlock - 1) / kMergeBlock));
+    if (changed && S0) VC_DLAUNCH(merge_kind, k_merge_old, ogrid, dim3(kMergeBlock), p, (const uint64_t *)cur.records.ptr, S0, nwords);
+    return VC_OK;
+}
+
+// after pass_end; `how` ends the pass's own message
+int merge_counted(vc_ctx *ctx, const char *what, uint64_t S1, const char *how)
+{
+    if (ctx->h_res[2] == S1) return VC_OK;
+    return fail(ctx, VC_ERR_HIP, "%s: the new occupancy holds %llu voxels, %llu %s", what, (unsigned long long)ctx->h_res[2], (unsigned long long)S1, how);
 }
 
 int ensure_exchange_scratch(vc_ctx *ctx, uint32_t ngroups)
@@ -2276,27 +2375,6 @@ int vc_fetch_occupancy(vc_ctx *ctx, uint8_t *bits)
     return VC_OK;
 }
 
-// timing_detail: the begin / end events a launch of the distance passes is to carry (null otherwise: an ordinary launch)
-static void dist_events(vc_ctx *ctx, int kind, hipEvent_t &start, hipEvent_t &stop)
-{
-    start = stop = nullptr;
-    if (!ctx->timing_detail) return;
-    const size_t at = 2 * ctx->dist_ev_kind.size();
-    while (ctx->dist_ev.size() < at + 2) {
-        Event e;
-        if (make_event(e) != hipSuccess) return;
-        ctx->dist_ev.push_back(std::move(e));
-    }
-    start = ctx->dist_ev[at]; stop = ctx->dist_ev[at + 1];
-    ctx->dist_ev_kind.push_back(kind);
-}
-#define VC_DLAUNCH(kind, kernel, grid, block, ...)                                                      \
-    do {                                                                                                \
-        hipEvent_t ks_, ke_;                                                                            \
-        dist_events(ctx, kind, ks_, ke_);                                                               \
-        hipExtLaunchKernelGGL(kernel, grid, block, 0, ctx->stream, ks_, ke_, 0, __VA_ARGS__);           \
-    } while (0)
-
 // after the call's stream has drained: the launches' times into vc_timing_t
 static void dist_harvest(vc_ctx *ctx)
 {
@@ -2374,28 +2452,6 @@ static int pass_end(vc_ctx *ctx, Pass &pass, float *ms)              // ms: wher
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     dist_harvest(ctx);
     if (ms) VC_HIP(ctx, hipEventElapsedTime(ms, ctx->ev[0], ctx->ev[1]));
-    return VC_OK;
-}
-
-// Survivors before each occupancy word of the step, as vc_components.h counts them, into woff[nwords]: popcounts per 64 words,
-// their scan in ctx->d_rscan, the wave scan inside each group.  The survivor total lands in *total_host once the stream has
-// drained.  kind >= 0: the launches carry that kind's events (VC_DLAUNCH).  Buffers sized by the caller (d_rscan: word_groups).
-static uint32_t word_groups(uint64_t nwords) { return (uint32_t)((nwords + 63) / 64); }   // 64 words per group: <= 2^20 groups
-
-static int word_offsets(vc_ctx *ctx, const StepBuf &cur, uint64_t nwords, DevBuf<uint32_t> &woff, uint64_t *total_host, int kind = -1)
-{
-    const uint32_t wgroups = word_groups(nwords);
-    const dim3 wgrid((wgroups + kCcBlock / 64 - 1) / (kCcBlock / 64)), block(kCcBlock);
-    const uint64_t *words = cur.words.ptr;
-    if (kind >= 0) VC_DLAUNCH(kind, k_cc_wcount, wgrid, block, words, nwords, wgroups, ctx->d_rscan.cnt.ptr);
-    else hipLaunchKernelGGL(k_cc_wcount, wgrid, block, 0, ctx->stream, words, nwords, wgroups, ctx->d_rscan.cnt.ptr);
-    VC_HIP(ctx, hipGetLastError());
-    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, wgroups, total_host));
-    const uint32_t *off = ctx->d_rscan.off.ptr;                  // (read-only to k_cc_woff, as the words are)
-    const uint64_t *boff = ctx->d_rscan.boff.ptr;
-    if (kind >= 0) VC_DLAUNCH(kind, k_cc_woff, wgrid, block, words, nwords, wgroups, off, boff, woff.ptr);
-    else hipLaunchKernelGGL(k_cc_woff, wgrid, block, 0, ctx->stream, words, nwords, wgroups, off, boff, woff.ptr);
-    VC_HIP(ctx, hipGetLastError());
     return VC_OK;
 }
 
@@ -2611,7 +2667,7 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
         const uint32_t wgroups = word_groups(nwords);
         const uint32_t rgroups = (uint32_t)((S0 + kCompactGroup - 1) / kCompactGroup);
         VC_TRY(ensure(ctx, ctx->d_rscan, wgroups > rgroups ? wgroups : rgroups));
-        VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
+        VC_TRY(ensure(ctx, ctx->d_woff, (size_t)nwords));
         VC_TRY(ensure(ctx, ctx->components.parent, (size_t)S0));
         VC_TRY(ensure(ctx, ctx->components.label, (size_t)S0));
         VC_TRY(ensure(ctx, ctx->components.cid, (size_t)S0));
@@ -2620,12 +2676,12 @@ int vc_hull_components(vc_ctx *ctx, uint32_t connectivity, uint64_t min_voxels, 
         VC_TRY(ensure(ctx, ctx->components.thr, 1));
         // 1 survivors before each word
         const dim3 block(kCcBlock);
-        VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_cc_woff, ctx->h_res + 1));
+        VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_woff, ctx->h_res + 1));
         CcParams p;
         memset(&p, 0, sizeof p);
         p.records = cur.records.ptr;
         p.words = cur.words.ptr;
-        p.woff = ctx->d_cc_woff.ptr;
+        p.woff = ctx->d_woff.ptr;
         p.parent = ctx->components.parent.ptr;
         p.label = ctx->components.label.ptr;
         p.cid = ctx->components.cid.ptr;
@@ -2978,11 +3034,9 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
     uint64_t q[3];
     VC_TRY(dist_metric(ctx, "vc_hull_grow", q));
     StepBuf &cur = *pass.cur;
-    if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_grow: frame set %u has been prepared again since the carve: its images are not the ones "
-                    "the records' colours came from", cur.slot);
+    VC_TRY(merge_refuse_slot(ctx, "vc_hull_grow", cur));
     const uint64_t n = pass.n, nwords = pass.nwords;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_grow: %llu voxels exceed the u32 index", (unsigned long long)n);
+    VC_TRY(merge_refuse_index(ctx, "vc_hull_grow", n));
     VC_TRY(pass_begin(ctx));
     const uint64_t S0 = pass.S;
     VC_TRY(pass_start(ctx, pass));
@@ -3040,42 +3094,21 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
             return fail(ctx, VC_ERR_HIP, "vc_hull_grow: %llu added to %llu survivors, %llu dilated, in a grid of %llu voxels", (unsigned long long)added,
                         (unsigned long long)S0, (unsigned long long)dilated, (unsigned long long)n);
         // every buffer of the hand-over before anything changes: a failure leaves the result
-        const uint32_t wgroups = word_groups(nwords);
         ctx->grow.stamp = kNever;                // (the added bytes of an earlier call go with their buffer)
         VC_TRY(ensure(ctx, ctx->grow.added, (size_t)S1));
+        VC_HIP(ctx, hipMemsetAsync(ctx->grow.added.ptr, 0, (size_t)S1, ctx->stream));   // (the pass's own bytes, stamp dropped above)
         if (added) {
-            VC_TRY(ensure(ctx, ctx->d_rec_spare, std::max<size_t>(cur.records.cap, (size_t)S1)));
-            VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
-            VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
-        }
-        VC_HIP(ctx, hipMemsetAsync(ctx->grow.added.ptr, 0, (size_t)S1, ctx->stream));
-        if (added) {
+            MergeParams p;
+            VC_TRY(merge_sized(ctx, cur, nwords, S1, true, ctx->grow.added.ptr, p));
             // the result changes from here on
             result_changed(ctx);
             const dim3 gblock(kGrowBlock), rgrid((uint32_t)((nrange + kGrowBlock - 1) / kGrowBlock));
-            VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, (const unsigned long long *)ctx->grow.addw.ptr, w0, nrange);
-            // survivors per group of the step, counted again: the packing skips the groups whose count is zero, and an added voxel
-            // may be the first of its group
-            const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
-            VC_DLAUNCH(VC_K_GROW_RANK, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups,
-                       cur.groupcnt.ptr);
-            // ranks of the new occupancy (in the components' offsets: their labels went stale with the result)
-            VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_cc_woff, ctx->h_res + 2, VC_K_GROW_RANK));
-            // the merged list into the spare buffer: every old record to its new rank, a fresh record for every added voxel
-            GrowParams p;
-            memset(&p, 0, sizeof p);
-            p.xs = cur.emit.xs; p.ys = cur.emit.ys; p.zs = cur.emit.zs;
-            p.has_cam = cur.emit.has_cam && cur.emit.xs ? 1 : 0;
-            p.cam = cur.emit.cam;
-            p.frame = cur.emit.frame;
-            p.words = cur.words.ptr; p.woff = ctx->d_cc_woff.ptr; p.addw = ctx->grow.addw.ptr;
-            p.out = ctx->d_rec_spare.ptr; p.added = ctx->grow.added.ptr;
-            p.w0 = w0; p.nrange = nrange; p.S1 = S1;
-            p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.H = ctx->H; p.W = ctx->W;
-            VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_old, dim3((uint32_t)((S0 + kGrowBlock - 1) / kGrowBlock)), gblock, p, (const uint64_t *)cur.records.ptr, S0, nwords);
-            VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_new, rgrid, gblock, p, nwords);
+            const unsigned long long *addw = ctx->grow.addw.ptr;
+            VC_DLAUNCH(VC_K_GROW_RANK, k_grow_apply, rgrid, gblock, cur.words.ptr, nwords, addw, w0, nrange);
+            VC_TRY(merge_ranked(ctx, cur, p, nwords, S0, true, VC_K_GROW_RANK, VC_K_GROW_MERGE));
+            VC_DLAUNCH(VC_K_GROW_MERGE, k_grow_new, rgrid, gblock, p, addw, w0, nrange, nwords);   // a fresh record for every added voxel
             VC_HIP(ctx, hipGetLastError());
-            VC_TRY(records_handed_over(ctx, cur, wgroups));
+            VC_TRY(records_handed_over(ctx, cur, word_groups(nwords)));
         }
     }
     // a call that adds nothing (r2 = 0, a second closing, the empty hull) leaves the result as it is, and with it the visibility,
@@ -3084,9 +3117,7 @@ int vc_hull_grow(vc_ctx *ctx, uint32_t op, uint64_t r2, uint32_t flags, vc_grow_
     VC_TRY(pass_end(ctx, pass, &stats->grow_ms));
     if (added) {
         ctx->survivors = cur.survivors = S1;
-        if (ctx->h_res[2] != S1)
-            return fail(ctx, VC_ERR_HIP, "vc_hull_grow: the new occupancy holds %llu voxels, %llu records were merged", (unsigned long long)ctx->h_res[2],
-                        (unsigned long long)S1);
+        VC_TRY(merge_counted(ctx, "vc_hull_grow", S1, "records were merged"));
     }
     stats->survivors_before = S0;
     stats->dilated = dilated;
@@ -3124,10 +3155,8 @@ int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t ke
         return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: keep_off %u not in [1, keep_on = %u]", keep_off, keep_on);
     StepBuf &cur = *pass.cur;
     const uint64_t n = pass.n, nwords = pass.nwords, npad = (nwords + 1) & ~1ull;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: %llu voxels exceed the u32 index", (unsigned long long)n);
-    if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: frame set %u has been prepared again since the carve: its images are not the ones "
-                    "the records' colours came from", cur.slot);
+    VC_TRY(merge_refuse_index(ctx, "vc_hull_temporal", n));
+    VC_TRY(merge_refuse_slot(ctx, "vc_hull_temporal", cur));
     vc_ctx::Temporal &T = ctx->temporal;
     if (ctx->current(T.stamp))
         return fail(ctx, VC_ERR_ARG, "vc_hull_temporal: the current result is already the last call's output (one push per result): carve again first");
@@ -3176,12 +3205,10 @@ int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t ke
                     (unsigned long long)S1, (unsigned long long)added, (unsigned long long)removed, (unsigned long long)S0, (unsigned long long)n);
     const bool changed = added || removed;
     // every buffer of the hand-over before anything is committed: a failure leaves result, ring and P
-    const uint32_t wgroups = word_groups(nwords);
     VC_TRY(ensure(ctx, T.votes, (size_t)S1));
     VC_TRY(ensure(ctx, T.added, (size_t)S1));
-    VC_TRY(ensure(ctx, ctx->d_rscan, wgroups));
-    VC_TRY(ensure(ctx, ctx->d_cc_woff, (size_t)nwords));
-    if (changed) VC_TRY(ensure(ctx, ctx->d_rec_spare, std::max<size_t>(cur.records.cap, (size_t)S1)));
+    MergeParams g;
+    VC_TRY(merge_sized(ctx, cur, nwords, S1, changed, T.added.ptr, g));
     // committed from here on: the ring takes H_t, the result O_t, P the staging buffer
     T.stamp = kNever;
     if (alloc) { T.ring = std::move(ring2); T.prev = std::move(prev2); T.stage = std::move(stage2); }
@@ -3195,45 +3222,23 @@ int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t ke
     T.pushes += 1;
     VC_HIP(ctx, hipMemcpyAsync(T.ring.ptr + (size_t)T.head * npad, cur.words.ptr, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
     VC_HIP(ctx, hipMemsetAsync(T.added.ptr, 0, std::max<size_t>((size_t)S1, 1), ctx->stream));
-    GrowParams g;
-    memset(&g, 0, sizeof g);
-    g.xs = cur.emit.xs; g.ys = cur.emit.ys; g.zs = cur.emit.zs;
-    g.has_cam = cur.emit.has_cam && cur.emit.xs ? 1 : 0;
-    g.cam = cur.emit.cam;
-    g.frame = cur.emit.frame;
-    g.words = cur.words.ptr; g.woff = ctx->d_cc_woff.ptr;
-    g.out = ctx->d_rec_spare.ptr; g.added = T.added.ptr;
-    g.S1 = S1;
-    g.nx = ctx->nx; g.ny = ctx->ny; g.nz = ctx->nz; g.H = ctx->H; g.W = ctx->W;
     tp.ring = T.ring.ptr; tp.head = T.head; tp.count = m; tp.cur = nullptr; tp.prev = nullptr;
-    const dim3 gblock(kGrowBlock), wgrid((uint32_t)((nwords + kGrowBlock - 1) / kGrowBlock));
+    const dim3 gblock(kMergeBlock), wgrid((uint32_t)((nwords + kMergeBlock - 1) / kMergeBlock));
     if (changed) {
         result_changed(ctx);
         VC_HIP(ctx, hipMemcpyAsync(cur.words.ptr, tp.stage, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-        // survivors per group of the step, counted again: the packing skips the groups whose count is zero
-        const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
-        VC_DLAUNCH(VC_K_TEMPORAL_RANK, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups,
-                   cur.groupcnt.ptr);
     }
-    if (changed || S1) VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_cc_woff, ctx->h_res + 2, VC_K_TEMPORAL_RANK));
-    if (changed) {
-        // the merged list into the spare buffer: every old record of O_t to its new rank, a fresh record for every restored voxel
-        if (S0) VC_DLAUNCH(VC_K_TEMPORAL_MERGE, k_temporal_old, dim3((uint32_t)((S0 + kGrowBlock - 1) / kGrowBlock)), gblock, g,
-                           (const uint64_t *)cur.records.ptr, S0, nwords);
-        if (S1) VC_DLAUNCH(VC_K_TEMPORAL_MERGE, k_temporal_new<true>, wgrid, gblock, g, tp, T.votes.ptr);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(records_handed_over(ctx, cur, wgroups));
-    } else if (S1) {
-        // O_t = H_t: records, occupancy and every product of a pass stay; only the vote bytes are made
-        VC_DLAUNCH(VC_K_TEMPORAL_RANK, k_temporal_new<false>, wgrid, gblock, g, tp, T.votes.ptr);
-        VC_HIP(ctx, hipGetLastError());
-    }
+    if (changed || S1) VC_TRY(merge_ranked(ctx, cur, g, nwords, S0, changed, VC_K_TEMPORAL_RANK, VC_K_TEMPORAL_MERGE));
+    // the vote byte of every record of O_t and a fresh record for every restored voxel; or O_t = H_t: records, occupancy and every
+    // product of a pass stay, only the vote bytes are made
+    if (changed && S1) VC_DLAUNCH(VC_K_TEMPORAL_MERGE, k_temporal_new<true>, wgrid, gblock, g, tp, T.votes.ptr);
+    else if (S1) VC_DLAUNCH(VC_K_TEMPORAL_RANK, k_temporal_new<false>, wgrid, gblock, g, tp, T.votes.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    if (changed) VC_TRY(records_handed_over(ctx, cur, word_groups(nwords)));
     std::swap(T.prev, T.stage);                  // (the launches above hold the pointers they were given)
     VC_TRY(pass_end(ctx, pass, &stats->temporal_ms));
     if (changed) ctx->survivors = cur.survivors = S1;
-    if ((changed || S1) && ctx->h_res[2] != S1)
-        return fail(ctx, VC_ERR_HIP, "vc_hull_temporal: the new occupancy holds %llu voxels, %llu were voted in", (unsigned long long)ctx->h_res[2],
-                    (unsigned long long)S1);
+    if (changed || S1) VC_TRY(merge_counted(ctx, "vc_hull_temporal", S1, "were voted in"));
     stats->window = window; stats->frames = m; stats->on = on; stats->off = off;
     stats->survivors_before = S0; stats->survivors_after = S1;
     stats->added = added; stats->removed = removed;
@@ -3613,7 +3618,7 @@ int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags, vc_normals_stats_t
     ctx->normals.stamp = kNever;
     if (S) {
         VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
-        VC_TRY(ensure(ctx, ctx->normals.woff, (size_t)nwords));
+        VC_TRY(ensure(ctx, ctx->d_woff, (size_t)nwords));
         VC_TRY(ensure(ctx, ctx->normals.rows, rows.size()));
         VC_TRY(ensure(ctx, ctx->normals.out, (size_t)S));
         VC_TRY(ensure(ctx, ctx->normals.ctr, 2));
@@ -3624,10 +3629,10 @@ int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags, vc_normals_stats_t
         VC_HIP(ctx, hipMemcpyAsync(ctx->normals.rows.ptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         VC_HIP(ctx, hipMemsetAsync(ctx->normals.out.ptr, 0, (size_t)S * sizeof(short4), ctx->stream));
         VC_HIP(ctx, hipMemsetAsync(ctx->normals.ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        VC_TRY(word_offsets(ctx, cur, nwords, ctx->normals.woff, ctx->h_res + 2));
+        VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_woff, ctx->h_res + 2));
         NrmParams p;
         memset(&p, 0, sizeof p);
-        p.words = cur.words.ptr; p.woff = ctx->normals.woff.ptr; p.rows = ctx->normals.rows.ptr;
+        p.words = cur.words.ptr; p.woff = ctx->d_woff.ptr; p.rows = ctx->normals.rows.ptr;
         p.out = ctx->normals.out.ptr; p.ctr = ctx->normals.ctr.ptr;
         p.nwords = nwords; p.n = n; p.S = S;
         for (int a = 0; a < 3; ++a) p.q[a] = (long long)q[a];
