@@ -739,6 +739,65 @@ int vc_geodesic_path(vc_ctx *ctx, uint32_t voxel, uint32_t *out, uint32_t capaci
 int vc_fetch_extremum_path(vc_ctx *ctx, uint32_t k /* 1 .. extremities */, uint32_t *out, uint32_t capacity, uint32_t *n);
 int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette /* [VC_GEO_MAX_K + 1][3] */);
 
+/* ---- the hull's figures measured: volume, area, centroid, axes, per group of records (no reference counterpart) -------------------
+ * vc_hull_measure reduces the records of the current carve result, as vc_fetch_occupancy and vc_fetch_records see it, to a few
+ * integers per group.  The result is left exactly as it is.  The contract, bit for bit (tests/measure_np.py restates it).  Integers
+ * only, and every value is a sum or an extremum over a set: neither evaluation order nor the arrival order of atomics shows.
+ *   1 inputs: the S records in ascending linear index i = (iz nx + ix) ny + iy, each {u32 i, u8 r, g, b, seen}; the occupancy;
+ *     a label per record from `source`:
+ *       VC_MEASURE_ALL       one group, G = 1 (`labels` and `groups` are ignored);
+ *       VC_MEASURE_CLUSTERS  the u8 labels of a vc_hull_clusters that is current, G = its K;
+ *       VC_MEASURE_GEODESIC  the u8 region labels of a vc_hull_geodesic that is current, G = its extremities + 1; label 255
+ *                            (unreached) belongs to no group;
+ *       VC_MEASURE_HOST      labels = const uint32_t [S] in record order and G = groups; 0xffffffff belongs to no group.
+ *     1 <= G <= VC_MEASURE_MAX_GROUPS.  Every axis of the grid has at most 65 536 cells: every sum then stays below 2^64.
+ *   2 per group g, over its records, a vc_measure_t of 21 u64 followed by 6 u32, 192 bytes:
+ *       voxels    its records                        surface   those with at least one exposed face
+ *       seen      those whose seen byte is 1         s1[3]     sum ix, sum iy, sum iz
+ *       s2[6]     sum ix^2, iy^2, iz^2, ix iy, ix iz, iy iz, in this order
+ *       faces[6]  exposed faces towards -x, +x, -y, +y, -z, +z
+ *       rgb[3]    sum r, sum g, sum b over the records with seen = 1, with the colours the records have at the call
+ *       lo[3], hi[3]  the inclusive box in (ix, iy, iz); lo = 0xffffffff > hi = 0 on every axis for a group without a record,
+ *                 as in vc_cluster_t.
+ *     A face is exposed when the neighbour in that direction lies outside the grid or is no survivor of the whole hull, in
+ *     whatever group it may be.  Nothing wraps around: i and i + 1 are no neighbours when (i + 1) mod ny = 0.
+ *   3 VC_MEASURE_PROFILE in flags: besides, per group and layer iz, {n, sum ix, sum iy} over the group's records of that layer,
+ *     u64 [G][nz][3] -- the cross-section and its centre line by height.  Refused when G nz > 2^20.
+ *   4 VC_ERR_ARG (with a message, nothing launched) when there is no carve result, steps are in flight, the carve ran with
+ *     VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached, source or a bit
+ *     of flags is unknown, stats == NULL, an axis has more than 65 536 cells, the cluster or geodesic pass the source names is
+ *     not current, labels == NULL with VC_MEASURE_HOST, G is out of range, or a host label is >= G and not 0xffffffff (the
+ *     message names the first such record).  S = 0 is no error: every group is empty.  Synchronous.
+ *   5 lifetime: vc_fetch_measure and vc_fetch_measure_profile fail ("no measurements") until the pass has run on the current
+ *     result and again after anything that changes which voxels survive, as vc_fetch_component_labels does; the profile also
+ *     when the last call ran without VC_MEASURE_PROFILE.  Colour passes leave them valid: the colour sums describe the records
+ *     as they were at the call.
+ * stats (required): survivors; groups = G; measured = the records in some group; unlabelled = survivors - measured;
+ * measure_ms = HIP events around the whole call.  voxcarve.measure derives world units (mm^3, mm^2, centroid, principal axes)
+ * from these integers and the grid on the host. */
+#define VC_MEASURE_ALL      0u
+#define VC_MEASURE_CLUSTERS 1u
+#define VC_MEASURE_GEODESIC 2u
+#define VC_MEASURE_HOST     3u
+#define VC_MEASURE_PROFILE  1u
+#define VC_MEASURE_MAX_GROUPS 4096u
+#define VC_MEASURE_MAX_AXIS 65536u
+#define VC_MEASURE_MAX_PROFILE (1u << 20)
+typedef struct {
+    uint64_t voxels, surface, seen;
+    uint64_t s1[3], s2[6], faces[6], rgb[3];
+    uint32_t lo[3], hi[3];
+} vc_measure_t;
+typedef struct {
+    uint64_t survivors, measured, unlabelled;
+    uint32_t groups;
+    float measure_ms;               /* HIP events around the whole call */
+} vc_measure_stats_t;
+int vc_hull_measure(vc_ctx *ctx, uint32_t source, const uint32_t *labels /* [S], VC_MEASURE_HOST only */, uint32_t groups, uint32_t flags,
+                    vc_measure_stats_t *stats);
+int vc_fetch_measure(vc_ctx *ctx, vc_measure_t *out);                      /* [G] */
+int vc_fetch_measure_profile(vc_ctx *ctx, uint64_t *out);                  /* [G][nz][3] */
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own

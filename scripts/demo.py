@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -19,6 +19,9 @@ the device, assignment.configure(clusters=K) -- their floor positions in world m
 the device, assignment.configure(extremities=K) -- their world positions and distances are printed; --geodesic-paint
 labels|distance (with --extremities): every voxel in its region's colour or a grey ramp of its distance, in the PLY, the --render
 images and the --mesh;
+--measure [SOURCE]: the hull's figures measured on the device, assignment.configure(measure=SOURCE) -- one line per group with its
+volume, boundary area, centroid, principal standard deviations, lean and height in world mm; SOURCE all (the default, the whole
+hull), clusters (with --clusters K), geodesic (with --extremities K: the regions) or components (with the component filter);
 --temporal T [--frames F] [--noise P]: F frames (default 16) of the committed masks, each with a share P (default 0.02) of its
 pixels flipped by a generator seeded with 7000 + the frame number, are carved one after the other and every hull is replaced by
 the vote of the last T hulls on the device, assignment.configure(temporal_window=T) -- the voxels that change between consecutive
@@ -58,6 +61,14 @@ if "--geodesic-paint" in sys.argv:
     k = sys.argv.index("--geodesic-paint")
     geodesic_paint = sys.argv[k + 1]
     del sys.argv[k:k + 2]
+measure = None
+if "--measure" in sys.argv:
+    k = sys.argv.index("--measure")
+    measure = "all"
+    if k + 1 < len(sys.argv) and sys.argv[k + 1] in ("all", "clusters", "geodesic", "components"):
+        measure = sys.argv[k + 1]
+        del sys.argv[k + 1]
+    del sys.argv[k]
 render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
@@ -111,7 +122,8 @@ if temporal:
 assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal,
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
-                     extremities=extremities, geodesic_paint=geodesic_paint if extremities else None)
+                     extremities=extremities, geodesic_paint=geodesic_paint if extremities else None,
+                     min_component_voxels=1 if measure == "components" else 0, measure=measure)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 if temporal:
     raw_sum = out_sum = 0
@@ -150,6 +162,15 @@ if extremities:
         w = ge["extrema"]["world_mm"][k]
         print("  extremity %d: voxel %d at x %.1f y %.1f z %.1f mm, %.1f mm along the hull, path of %d voxels" %
               (k + 1, ge["extrema"]["voxel"][k], w[0], w[1], w[2], ge["extrema"]["d_mm"][k], len(ge["paths"][k])))
+if measure:
+    ms = assignment.measurements()
+    w = ms["world"]
+    print("measure: %d groups by %s, %d of %d voxels in a group (%.3f ms on the device; areas are the voxel boundary's)" %
+          (ms["groups"], measure, ms["measured"], ms["survivors"], ms["measure_ms"]))
+    for k in range(ms["groups"]):
+        print("  group %d: %d voxels, volume %.4g mm3, area %.4g mm2, centroid x %.1f y %.1f z %.1f mm, std %.1f %.1f %.1f mm, lean %.1f deg, "
+              "height %.1f mm" % ((k, w["voxels"][k], w["volume_mm3"][k], w["area_mm2"][k]) + tuple(w["centroid_mm"][k]) +
+                                   tuple(w["std_mm"][k]) + (w["lean_deg"][k], w["height_mm"][k])))
 
 
 def write_image(path, img):

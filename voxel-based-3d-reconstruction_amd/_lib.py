@@ -29,6 +29,11 @@ VC_GEO_MAX_K = 32
 VC_GEO_TILE = (4, 64, 4)
 VC_GEO_PAINT_LABELS, VC_GEO_PAINT_DISTANCE = 0, 1
 VC_GEO_UNREACHED_RGB = (255, 0, 255)
+VC_MEASURE_ALL, VC_MEASURE_CLUSTERS, VC_MEASURE_GEODESIC, VC_MEASURE_HOST = 0, 1, 2, 3
+VC_MEASURE_PROFILE = 1
+VC_MEASURE_MAX_GROUPS = 4096
+VC_MEASURE_MAX_AXIS = 65536
+VC_MEASURE_MAX_PROFILE = 1 << 20
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
 VC_MAX_MOG_MODELS = 64
@@ -138,6 +143,17 @@ class VcGeodesicStats(ctypes.Structure):
                 ("max_d", ctypes.c_uint64), ("tile_visits", ctypes.c_uint64), ("tiles", ctypes.c_uint64), ("edge_um", ctypes.c_uint64 * 7),
                 ("q", ctypes.c_uint64 * 3), ("extremities", ctypes.c_uint32), ("rounds", ctypes.c_uint32), ("launches", ctypes.c_uint32),
                 ("geodesic_ms", ctypes.c_float)]
+
+
+class VcMeasure(ctypes.Structure):
+    _fields_ = [("voxels", ctypes.c_uint64), ("surface", ctypes.c_uint64), ("seen", ctypes.c_uint64), ("s1", ctypes.c_uint64 * 3),
+                ("s2", ctypes.c_uint64 * 6), ("faces", ctypes.c_uint64 * 6), ("rgb", ctypes.c_uint64 * 3), ("lo", ctypes.c_uint32 * 3),
+                ("hi", ctypes.c_uint32 * 3)]
+
+
+class VcMeasureStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("measured", ctypes.c_uint64), ("unlabelled", ctypes.c_uint64),
+                ("groups", ctypes.c_uint32), ("measure_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -252,6 +268,9 @@ SIGNATURES = {
     "vc_geodesic_path": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, c_u32p]),
     "vc_fetch_extremum_path": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, c_u32p]),
     "vc_paint_geodesic": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
+    "vc_hull_measure": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcMeasureStats)]),
+    "vc_fetch_measure": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcMeasure)]),
+    "vc_fetch_measure_profile": (ctypes.c_int, [c_ctx, c_u64p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

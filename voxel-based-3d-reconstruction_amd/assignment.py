@@ -166,7 +166,10 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None,
              "clusters": 0, "cluster_min_column": 1, "cluster_paint": False,
              "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None,
-             "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None}
+             "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None,
+             "measure": None, "measure_profile": False}
+_measure_state = {"last": None, "centroids_mm": None}
+MEASURES = (None, "all", "clusters", "geodesic", "components")
 _temporal_state = {"last": None}
 _cluster_state = {"centres_mm": None, "references": None, "last": None}
 _geodesic_state = {"last": None}
@@ -215,7 +218,13 @@ def configure(frame_source=None, **settings):
     before hull_close_mm and everything else -- by CarveEngine.temporal_filter(T, temporal_keep, temporal_keep_off): the hull
     becomes the vote of the last T frames' hulls (keep defaults to the majority, keep_off to keep), which takes the frame-to-frame
     flicker of mask noise out and lags a moving figure by about T / 2 frames.  temporal() returns the last frame's stats.
-    0 (the default) runs nothing."""
+    0 (the default) runs nothing.
+    measure, measure_profile: when measure = "all" | "clusters" | "geodesic" | "components", every frame ends -- after the
+    clusters and the extremities -- with CarveEngine.measure_hull(labels=measure, profile=measure_profile): the hull's figures
+    measured on the device, per group of that source (the whole hull; the figures of clusters=K; the regions of extremities=K;
+    the connected components, ranked by size, of the component filter -- which runs once more on its own output when it removed
+    something, so that its labels describe the hull).  measurements() returns the last frame's.  A source whose own pass is not
+    configured is refused.  None (the default) runs nothing."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -248,7 +257,20 @@ def configure(frame_source=None, **settings):
         raise ValueError("temporal_window %r, expected an integer in 0..15" % (t,))
     CarveEngine.temporal_thresholds(t if t > 0 else 1, settings.get("temporal_keep", _settings["temporal_keep"]) if t > 0 else None,
                                     settings.get("temporal_keep_off", _settings["temporal_keep_off"]) if t > 0 else None)
+    m = settings.get("measure", _settings["measure"])
+    if m not in MEASURES:
+        raise ValueError("measure %r, expected one of %s" % (m, MEASURES))
+    if not isinstance(settings.get("measure_profile", _settings["measure_profile"]), (bool, np.bool_)):
+        raise ValueError("measure_profile %r, expected True or False" % (settings["measure_profile"],))
+    merged = dict(_settings, **settings)
+    if m == "clusters" and not merged["clusters"] > 0:
+        raise ValueError('measure="clusters" needs clusters=K')
+    if m == "geodesic" and not merged["extremities"] > 0:
+        raise ValueError('measure="geodesic" needs extremities=K')
+    if m == "components" and not (merged["min_component_voxels"] or merged["keep_components"]):
+        raise ValueError('measure="components" needs the component filter: min_component_voxels or keep_components')
     _settings.update(settings)
+    _measure_state.update(last=None, centroids_mm=None)
     _temporal_state.update(last=None)
     _cluster_state.update(centres_mm=None, references=None, last=None)
     _geodesic_state.update(last=None)
@@ -328,6 +350,8 @@ def set_voxel_positions(width, height, depth):
         _cluster_frame()
     if _settings["extremities"] > 0:
         _geodesic_frame()
+    if _settings["measure"] is not None:
+        _measure_frame()
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)
@@ -357,6 +381,42 @@ def _geodesic_frame():
     _geodesic_state["last"] = out
     if _settings["geodesic_paint"] is not None:
         _engine.paint_geodesic(_settings["geodesic_paint"])
+
+
+def _measure_frame():
+    """The frame's measurements (see configure); with "clusters", label k is the same figure from frame to frame, so the
+    centroid's step since the previous frame is the figure's displacement."""
+    from . import measure
+    source = _settings["measure"]
+    if source == "components":
+        try:
+            _engine.component_ranks()
+        except ValueError:                                       # the filter removed something: label its output
+            _engine.filter_components(connectivity=_settings["component_connectivity"])
+    out = _engine.measure_hull(labels=source, profile=bool(_settings["measure_profile"]))
+    out["source"] = source
+    out["integers"] = _engine.fetch_measure()
+    out["world"] = measure.describe(out["integers"], _engine.grid, _engine.bounds)
+    if _settings["measure_profile"]:
+        out["profile"] = _engine.fetch_measure_profile()
+    if source == "clusters":
+        c = out["world"]["centroid_mm"]
+        prev = _measure_state["centroids_mm"]
+        out["velocity_mm"] = None if prev is None or prev.shape != c.shape else c - prev
+        _measure_state["centroids_mm"] = c.copy()
+    _measure_state["last"] = out
+
+
+def measurements():
+    """The measurements of the last set_voxel_positions call's hull (configure(measure=...)): the dict of
+    CarveEngine.measure_hull (survivors, groups, measured, unlabelled, measure_ms) with source; integers: the dict of
+    CarveEngine.fetch_measure; world: the dict of voxcarve.measure.describe (volume_mm3, area_mm2 -- the voxel boundary's, which
+    overstates a smooth surface --, centroid_mm, covariance_mm2, std_mm, axes, lean_deg, height_mm, top_mm, mean_rgb); profile:
+    u64 [G, nz, 3] with measure_profile=True; and, with measure="clusters", velocity_mm: float64 [K, 3], each figure's centroid
+    minus the previous frame's (None on the first frame; NaN rows for a figure that is empty in either)."""
+    if _engine is None or not initialized or _measure_state["last"] is None:
+        raise RuntimeError("no measurements: configure(measure=...) and set_voxel_positions have not run")
+    return _measure_state["last"]
 
 
 def temporal():

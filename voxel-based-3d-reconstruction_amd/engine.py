@@ -1063,6 +1063,94 @@ class CarveEngine:
         self._check(self._L.vc_paint_geodesic(self._ctx, _lib.VC_GEO_PAINT_LABELS if mode == "labels" else _lib.VC_GEO_PAINT_DISTANCE,
                                               _ptr(pal, ctypes.c_uint8)), "vc_paint_geodesic")
 
+    # -- the hull's figures measured per group of records (vc_hull_measure) --------------------------------------------------------
+    def component_ranks(self):
+        """(u32 [S], components): per record of the current hull the rank of its connected component, size descending then label
+        ascending -- the host labels of measure_hull(labels="components").  Needs a filter_components that is current and
+        removed nothing from its input (its labels are in its input's record order): otherwise ValueError."""
+        try:
+            lab = self.fetch_component_labels()
+            comp = self.fetch_components()
+        except _lib.VoxcarveError as exc:
+            raise ValueError('measure_hull(labels="components"): no components of the current hull (%s): run filter_components '
+                             "once more on its own output" % exc) from exc
+        if lab.size != self.count or not comp["kept"].all():
+            raise ValueError('measure_hull(labels="components"): the last filter_components removed voxels, its labels describe '
+                             "its input: run filter_components once more on its own output")
+        order = np.lexsort((comp["label"], -comp["size"].astype(np.int64)))
+        rank = np.empty(order.size, dtype=np.uint32)
+        rank[order] = np.arange(order.size, dtype=np.uint32)
+        return rank[np.searchsorted(comp["label"], lab)], int(order.size)
+
+    def measure_hull(self, labels="all", groups=None, profile=False):
+        """Reduces the records of the current carve result to a few integers per group (contract: include/voxcarve.h): voxels,
+        surface voxels, seen voxels, first and second moments of (ix, iy, iz), exposed faces per direction, colour sums, box --
+        and with profile=True {n, sum ix, sum iy} per group and layer.  labels: "all" (one group), "clusters" (the figures of a
+        current cluster_hull), "geodesic" (the regions of a current hull_geodesic; unreached voxels belong to no group),
+        "components" (the connected components of a current filter_components that removed nothing, ranked by size descending
+        then label ascending) or an integer array [S] in record order with `groups` = G (0xffffffff: no group).  Integers only
+        and exact; the result stays as it is.  voxcarve.measure.describe() turns the integers into mm.  Returns the stats as a
+        dict: survivors, groups, measured, unlabelled, measure_ms."""
+        src, lab, G = _lib.VC_MEASURE_ALL, None, 0
+        if isinstance(labels, str):
+            if labels == "clusters":
+                src = _lib.VC_MEASURE_CLUSTERS
+            elif labels == "geodesic":
+                src = _lib.VC_MEASURE_GEODESIC
+            elif labels == "components":
+                lab, G = self.component_ranks()
+                src = _lib.VC_MEASURE_HOST
+                if G == 0:                                       # (an empty hull has no component: one empty group)
+                    G = 1
+            elif labels != "all":
+                raise ValueError('measure_hull: labels %r, expected "all", "clusters", "geodesic", "components" or an integer array' % (labels,))
+        else:
+            v = np.asarray(labels).reshape(-1)
+            if v.size and (not np.issubdtype(v.dtype, np.integer) or int(v.min()) < 0 or int(v.max()) > 0xffffffff):
+                raise ValueError("measure_hull: labels must be integers in 0 .. 2^32 - 1")
+            if v.size != self.count:
+                raise ValueError("measure_hull: %d labels for %d records" % (v.size, self.count))
+            if groups is None:
+                raise ValueError("measure_hull: an array of labels needs groups=G")
+            if not 0 <= int(groups) <= 0xffffffff:
+                raise ValueError("measure_hull: groups %r" % (groups,))
+            src, lab, G = _lib.VC_MEASURE_HOST, v, int(groups)
+        if lab is not None:
+            lab = np.ascontiguousarray(lab, dtype=np.uint32)
+            if lab.size == 0:
+                lab = np.zeros(1, dtype=np.uint32)               # (a pointer the call can tell from NULL)
+        st = _lib.VcMeasureStats()
+        self._check(self._L.vc_hull_measure(self._ctx, src, None if lab is None else _ptr(lab, ctypes.c_uint32), G,
+                                            _lib.VC_MEASURE_PROFILE if profile else 0, ctypes.byref(st)), "vc_hull_measure")
+        self._ms_g = int(st.groups)
+        return {"survivors": int(st.survivors), "groups": int(st.groups), "measured": int(st.measured),
+                "unlabelled": int(st.unlabelled), "measure_ms": float(st.measure_ms)}
+
+    def measure_valid(self):
+        """True while the measurements of the last measure_hull() describe the current hull."""
+        return self._L.vc_fetch_measure(self._ctx, None) == _lib.VC_OK
+
+    def fetch_measure(self):
+        """The groups of the last measure_hull: dict of numpy arrays voxels, surface, seen u64 [G], s1 u64 [G, 3] (sum ix, iy,
+        iz), s2 u64 [G, 6] (sum ix^2, iy^2, iz^2, ix iy, ix iz, iy iz), faces u64 [G, 6] (-x, +x, -y, +y, -z, +z), rgb u64 [G, 3]
+        (over the seen records), lo / hi u32 [G, 3] (inclusive box in (ix, iy, iz); lo = 0xffffffff > hi = 0 for an empty group)."""
+        G = getattr(self, "_ms_g", 0)
+        raw = np.zeros((max(G, 1), 24), dtype=np.uint64)
+        self._check(self._L.vc_fetch_measure(self._ctx, raw.ctypes.data_as(ctypes.POINTER(_lib.VcMeasure))), "vc_fetch_measure")
+        raw = raw[:G]
+        box = np.ascontiguousarray(raw[:, 21:24]).view(np.uint32).reshape(G, 6)
+        return {"voxels": raw[:, 0].copy(), "surface": raw[:, 1].copy(), "seen": raw[:, 2].copy(), "s1": raw[:, 3:6].copy(),
+                "s2": raw[:, 6:12].copy(), "faces": raw[:, 12:18].copy(), "rgb": raw[:, 18:21].copy(), "lo": box[:, :3].copy(),
+                "hi": box[:, 3:].copy()}
+
+    def fetch_measure_profile(self):
+        """u64 [G, nz, 3]: per group and layer iz {n, sum ix, sum iy} of the last measure_hull(profile=True) -- the cross-section
+        and, divided by n, its centre line by height."""
+        G = getattr(self, "_ms_g", 0)
+        out = np.zeros((max(G, 1), self.grid[2], 3), dtype=np.uint64)
+        self._check(self._L.vc_fetch_measure_profile(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_fetch_measure_profile")
+        return out[:G]
+
     def set_option(self, name, value):
         """Launch-geometry tuning knobs (never change results); see vc_set_option."""
         self._check(self._L.vc_set_option(self._ctx, name.encode(), int(value)), "vc_set_option")
