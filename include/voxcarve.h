@@ -126,6 +126,10 @@ typedef struct {
      * valid when no step is in flight */
     uint64_t work[VC_WORK_KINDS];
     float visible_ms;   /* last vc_color_visible: its kernels, fill of the maps to the last colour (HIP events on the context's stream) */
+    float thin_ms;      /* last vc_hull_thin: HIP events around the whole call */
+    float thin_kernel_ms; /* ... and, with option timing_detail = 1, the sum of its mark, sub-step, list and row kernels' own
+                           begin .. end (0 otherwise): thin_ms minus this is the time the stream spent between them */
+    uint32_t thin_launches; /* the kernels of that sum */
 } vc_timing_t;
 
 /* ---- lifetime ------------------------------------------------------------------ */
@@ -798,6 +802,72 @@ int vc_hull_measure(vc_ctx *ctx, uint32_t source, const uint32_t *labels /* [S],
 int vc_fetch_measure(vc_ctx *ctx, vc_measure_t *out);                      /* [G] */
 int vc_fetch_measure_profile(vc_ctx *ctx, uint64_t *out);                  /* [G][nz][3] */
 
+/* ---- the hull thinned to a curve skeleton, topology kept (no reference counterpart) ---------------------------------------------------
+ * vc_hull_thin peels the current carve result, as vc_fetch_occupancy and vc_fetch_records see it, down to a centred, one-voxel-wide
+ * skeleton with the components, tunnels and cavities of the hull.  The result is left exactly as it is: the pass works on a copy
+ * of the occupancy.  The contract, bit for bit (tests/thin_np.py restates it).  Integers and bits only.
+ *   1 the object is the set H of survivors; everything outside the grid is background; connectivity is 26 for H and 6 for the
+ *     background.  N26*(p) = the 26 neighbours of p, N18*(p) = those that differ from p in at most two coordinates, the
+ *     6-neighbours = those that differ in one.
+ *   2 p is simple when H n N26*(p) has exactly one 26-connected component (adjacency inside N26*(p)) and (complement of H) n
+ *     N18*(p) has exactly one 6-connected component (adjacency inside N18*(p)) that contains a 6-neighbour of p.  A voxel with no
+ *     neighbour in H is not simple.  p is an end point when it has exactly one neighbour in H.
+ *   3 directions, as offsets in (ix, iy, iz): d0 .. d5 = (0,0,-1), (0,0,+1), (0,-1,0), (0,+1,0), (-1,0,0), (+1,0,0).  The
+ *     subfield of a voxel is s = (ix & 1) | (iy & 1) << 1 | (iz & 1) << 2.
+ *   4 a pass is six direction steps d0 .. d5.  At its start a direction step marks as candidates the voxels of H that are no
+ *     anchors and whose neighbour p + d is background; then eight sub-steps s = 0 .. 7 follow, and sub-step s removes from H, all
+ *     at once, every candidate of subfield s that is simple in the H of that moment -- and, with mode VC_THIN_CURVE, no end point
+ *     in that H.  VC_THIN_POINT has no end-point condition: a component shrinks to a topological kernel (a ball to a point, a
+ *     torus to a ring, a shell to a closed surface).  Passes repeat until one removes nothing or max_passes of them have run
+ *     (1 <= max_passes <= VC_THIN_MAX_PASSES; the last pass of a stable result is the one that removed nothing).  Two voxels of a
+ *     subfield are never 26-neighbours and the predicate reads N26* alone, so a sub-step equals the removal of its voxels one by
+ *     one in any order: every removal is of a simple voxel, and no order of evaluation shows.
+ *   5 anchors are never removed.  anchor_source VC_THIN_ANCHORS_NONE: none (`anchors`, `n_anchors` ignored).
+ *     VC_THIN_ANCHORS_LIST: n_anchors linear indices, duplicates allowed, every one a survivor.  VC_THIN_ANCHORS_EXTREMA: the
+ *     voxels at distance 0 of a vc_hull_geodesic that is current: its seed set and its extremities.
+ *   6 outputs.  Per record peel (u16): 0 for a kept voxel, else 1 + 6 (pass - 1) + d of the direction step that removed it (pass
+ *     from 1).  Per kept voxel, ascending by voxel index, a vc_skeleton_voxel_t {voxel, record, degree = the kept voxels in
+ *     N26*}.  Bit c of the table of vc_fetch_thin_table (byte c >> 3, bit c & 7) says whether a voxel whose neighbourhood has the
+ *     code c is simple; bit k of a code is the neighbour at offset (dx, dy, dz) with k27 = (dz + 1) 9 + (dx + 1) 3 + (dy + 1),
+ *     k = k27 below 13 and k27 - 1 above it.
+ *   7 VC_ERR_ARG (with a message; the outputs of an earlier call are gone once the arguments have passed) when there is no carve
+ *     result, steps are in flight, the carve ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of
+ *     more than one rank is attached, mode, anchor_source or flags (must be 0) is unknown, stats == NULL, max_passes is out of
+ *     range, the grid exceeds the u32 index, anchors == NULL with n_anchors > 0, an anchor is no survivor (the message names the
+ *     first such position and its voxel), or VC_THIN_ANCHORS_EXTREMA comes without a current vc_hull_geodesic.  S = 0 is no
+ *     error.  Synchronous.
+ *   8 lifetime: vc_fetch_thin and vc_fetch_skeleton fail ("no skeleton") until the pass has run on the current result and again
+ *     after anything that changes which voxels survive, as vc_fetch_component_labels does; colour passes leave them valid.
+ * Two routes evaluate the predicate, with equal bytes: in registers (option thin_table = 0, the default until the table has been
+ * measured faster) or by a look-up in the table of 2^26 bits, which a kernel builds with the same function at first use
+ * (thin_table = 1).  stats (required): survivors; anchors = the distinct anchor voxels; kept, removed; passes = passes run;
+ * steps = direction steps that had a candidate; launches = kernels the call launched (it depends on the route taken and is no
+ * part of the restated contract); stable = 0 when max_passes cut the thinning short; isolated / endpoints / junctions = kept
+ * voxels of degree 0 / 1 / >= 3; thin_ms = HIP events around the whole call. */
+#define VC_THIN_CURVE 0u
+#define VC_THIN_POINT 1u
+#define VC_THIN_ANCHORS_NONE    0u
+#define VC_THIN_ANCHORS_LIST    1u
+#define VC_THIN_ANCHORS_EXTREMA 2u
+#define VC_THIN_MAX_PASSES 10000u
+#define VC_THIN_DEFAULT_PASSES 4096u
+#define VC_THIN_TABLE_BYTES (1u << 23)
+typedef struct {
+    uint32_t voxel, record;
+    uint8_t degree, pad[3];         /* pad: zeros */
+} vc_skeleton_voxel_t;
+typedef struct {
+    uint64_t survivors, anchors, kept, removed;
+    uint64_t isolated, endpoints, junctions;
+    uint32_t passes, steps, launches, stable;
+    float thin_ms;                  /* HIP events around the whole call */
+} vc_thin_stats_t;
+int vc_hull_thin(vc_ctx *ctx, uint32_t mode, uint32_t anchor_source, const uint32_t *anchors /* [n_anchors], VC_THIN_ANCHORS_LIST only */,
+                 uint64_t n_anchors, uint32_t max_passes, uint32_t flags /* 0 */, vc_thin_stats_t *stats);
+int vc_fetch_thin(vc_ctx *ctx, uint16_t *peel);                            /* [S] */
+int vc_fetch_skeleton(vc_ctx *ctx, vc_skeleton_voxel_t *out);              /* [stats.kept] */
+int vc_fetch_thin_table(vc_ctx *ctx, uint8_t *bits);                       /* [VC_THIN_TABLE_BYTES]; builds the table if need be */
+
 /* ---- the step before the path ---------------------------------------------------------------------------------
  * extract_foreground_mask, background_subtraction.py:129-208, on the device: the front half (:153-168) by the calls below, the
  * contour stage (:171-193) by vc_fill_figures, the 2x2 post-filter and the final threshold (:195-206) by the carve path's own
@@ -961,6 +1031,8 @@ int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *
  *   geodesic        geodesic_tiles (1)  vc_hull_geodesic relaxes by tiles held in LDS, one workgroup per listed tile and launch;
  *                                  0: by sweeps of one lane per record over the whole hull (the same bytes;
  *                                  scripts/exp_geodesic.py times both)
+ *   thinning        thin_table (0)  vc_hull_thin evaluates the simple-point predicate in registers; 1: looks it up in the table
+ *                                  of 2^26 bits built on the device at first use (the same bytes; scripts/exp_thin.py times both)
  *   experiments     dbg (0)  bit 0: skip the per-voxel level (undecided words count as alive), bit 1: skip the word level
  *                                  too -- WRONG results on purpose, to time the levels apart (scripts/exp_bricks.py); bit 2:
  *                                  no word-level tests, every word of a listed brick goes to the per-voxel level (right results)

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -22,6 +22,9 @@ images and the --mesh;
 --measure [SOURCE]: the hull's figures measured on the device, assignment.configure(measure=SOURCE) -- one line per group with its
 volume, boundary area, centroid, principal standard deviations, lean and height in world mm; SOURCE all (the default, the whole
 hull), clusters (with --clusters K), geodesic (with --extremities K: the regions) or components (with the component filter);
+--skeleton curve|point [--skeleton-anchors extrema]: the hull thinned to a one-voxel-wide skeleton with its topology on the
+device, assignment.configure(skeleton=...) -- its voxels, end points, junctions and length in mm are printed; with
+--skeleton-anchors extrema (and --extremities K) the floor contact and the extremities are pinned;
 --temporal T [--frames F] [--noise P]: F frames (default 16) of the committed masks, each with a share P (default 0.02) of its
 pixels flipped by a generator seeded with 7000 + the frame number, are carved one after the other and every hull is replaced by
 the vote of the last T hulls on the device, assignment.configure(temporal_window=T) -- the voxels that change between consecutive
@@ -69,6 +72,15 @@ if "--measure" in sys.argv:
         measure = sys.argv[k + 1]
         del sys.argv[k + 1]
     del sys.argv[k]
+skeleton = skeleton_anchors = None
+if "--skeleton" in sys.argv:
+    k = sys.argv.index("--skeleton")
+    skeleton = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
+if "--skeleton-anchors" in sys.argv:
+    k = sys.argv.index("--skeleton-anchors")
+    skeleton_anchors = sys.argv[k + 1]
+    del sys.argv[k:k + 2]
 render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
@@ -123,7 +135,8 @@ assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_w
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
                      extremities=extremities, geodesic_paint=geodesic_paint if extremities else None,
-                     min_component_voxels=1 if measure == "components" else 0, measure=measure)
+                     min_component_voxels=1 if measure == "components" else 0, measure=measure,
+                     skeleton=skeleton, skeleton_anchors=skeleton_anchors if skeleton else None)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 if temporal:
     raw_sum = out_sum = 0
@@ -171,6 +184,11 @@ if measure:
         print("  group %d: %d voxels, volume %.4g mm3, area %.4g mm2, centroid x %.1f y %.1f z %.1f mm, std %.1f %.1f %.1f mm, lean %.1f deg, "
               "height %.1f mm" % ((k, w["voxels"][k], w["volume_mm3"][k], w["area_mm2"][k]) + tuple(w["centroid_mm"][k]) +
                                    tuple(w["std_mm"][k]) + (w["lean_deg"][k], w["height_mm"][k])))
+if skeleton:
+    sk = assignment.skeleton()
+    print("skeleton (%s): %d voxels of %d, %d end points, %d junctions, %.1f mm of edges; %d passes, %d anchors (%.3f ms on the device)" %
+          (skeleton, sk["stats"]["kept"], sk["stats"]["survivors"], sk["stats"]["endpoints"], sk["stats"]["junctions"],
+           sk["description"]["length_mm"], sk["stats"]["passes"], sk["stats"]["anchors"], sk["stats"]["thin_ms"]))
 
 
 def write_image(path, img):

@@ -34,6 +34,10 @@ VC_MEASURE_PROFILE = 1
 VC_MEASURE_MAX_GROUPS = 4096
 VC_MEASURE_MAX_AXIS = 65536
 VC_MEASURE_MAX_PROFILE = 1 << 20
+VC_THIN_CURVE, VC_THIN_POINT = 0, 1
+VC_THIN_ANCHORS_NONE, VC_THIN_ANCHORS_LIST, VC_THIN_ANCHORS_EXTREMA = 0, 1, 2
+VC_THIN_MAX_PASSES, VC_THIN_DEFAULT_PASSES = 10000, 4096
+VC_THIN_TABLE_BYTES = 1 << 23
 VC_MAX_CAMERAS = 16
 VC_UNIQUE_ID_BYTES = 128
 VC_MAX_MOG_MODELS = 64
@@ -74,7 +78,8 @@ class VcTiming(ctypes.Structure):
                 ("preps_timed", ctypes.c_uint32), ("emit_ms", ctypes.c_float), ("emit_ms_sum", ctypes.c_float),
                 ("emit_launches", ctypes.c_uint32),
                 ("kernel_ms_sum", ctypes.c_float * VC_KERNEL_KINDS), ("kernel_launches", ctypes.c_uint32 * VC_KERNEL_KINDS),
-                ("work", ctypes.c_uint64 * VC_WORK_KINDS), ("visible_ms", ctypes.c_float)]
+                ("work", ctypes.c_uint64 * VC_WORK_KINDS), ("visible_ms", ctypes.c_float), ("thin_ms", ctypes.c_float),
+                ("thin_kernel_ms", ctypes.c_float), ("thin_launches", ctypes.c_uint32)]
 
 
 class VcPhotoStats(ctypes.Structure):
@@ -154,6 +159,17 @@ class VcMeasure(ctypes.Structure):
 class VcMeasureStats(ctypes.Structure):
     _fields_ = [("survivors", ctypes.c_uint64), ("measured", ctypes.c_uint64), ("unlabelled", ctypes.c_uint64),
                 ("groups", ctypes.c_uint32), ("measure_ms", ctypes.c_float)]
+
+
+class VcSkeletonVoxel(ctypes.Structure):
+    _fields_ = [("voxel", ctypes.c_uint32), ("record", ctypes.c_uint32), ("degree", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
+
+
+class VcThinStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("anchors", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("removed", ctypes.c_uint64),
+                ("isolated", ctypes.c_uint64), ("endpoints", ctypes.c_uint64), ("junctions", ctypes.c_uint64),
+                ("passes", ctypes.c_uint32), ("steps", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("stable", ctypes.c_uint32),
+                ("thin_ms", ctypes.c_float)]
 
 
 class VcSurfaceStats(ctypes.Structure):
@@ -271,6 +287,11 @@ SIGNATURES = {
     "vc_hull_measure": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcMeasureStats)]),
     "vc_fetch_measure": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcMeasure)]),
     "vc_fetch_measure_profile": (ctypes.c_int, [c_ctx, c_u64p]),
+    "vc_hull_thin": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, c_u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.POINTER(VcThinStats)]),
+    "vc_fetch_thin": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_uint16)]),
+    "vc_fetch_skeleton": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcSkeletonVoxel)]),
+    "vc_fetch_thin_table": (ctypes.c_int, [c_ctx, c_u8p]),
     "vc_set_option": (ctypes.c_int, [c_ctx, ctypes.c_char_p, ctypes.c_int]),
     "vc_timing_struct_size": (ctypes.c_uint32, []),
     "vc_timing": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcTiming)]),

@@ -167,7 +167,10 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "clusters": 0, "cluster_min_column": 1, "cluster_paint": False,
              "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None,
              "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None,
-             "measure": None, "measure_profile": False}
+             "measure": None, "measure_profile": False,
+             "skeleton": None, "skeleton_anchors": None}
+_skeleton_state = {"last": None}
+SKELETONS = (None, "curve", "point")
 _measure_state = {"last": None, "centroids_mm": None}
 MEASURES = (None, "all", "clusters", "geodesic", "components")
 _temporal_state = {"last": None}
@@ -224,7 +227,12 @@ def configure(frame_source=None, **settings):
     measured on the device, per group of that source (the whole hull; the figures of clusters=K; the regions of extremities=K;
     the connected components, ranked by size, of the component filter -- which runs once more on its own output when it removed
     something, so that its labels describe the hull).  measurements() returns the last frame's.  A source whose own pass is not
-    configured is refused.  None (the default) runs nothing."""
+    configured is refused.  None (the default) runs nothing.
+    skeleton, skeleton_anchors: when skeleton = "curve" | "point", every frame ends -- after the frame's geodesic pass -- with
+    CarveEngine.thin_hull(skeleton, anchors=skeleton_anchors): the hull thinned to a centred, one-voxel-wide skeleton with its
+    topology, on the device; the hull itself stays.  skeleton_anchors = "extrema" pins the skeleton at the floor contact and the
+    extremities of extremities=K, which turns a noisy curve skeleton into a stick figure; it is refused without extremities=K.
+    skeleton() returns the last frame's.  None (the default) runs nothing."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -269,8 +277,15 @@ def configure(frame_source=None, **settings):
         raise ValueError('measure="geodesic" needs extremities=K')
     if m == "components" and not (merged["min_component_voxels"] or merged["keep_components"]):
         raise ValueError('measure="components" needs the component filter: min_component_voxels or keep_components')
+    if merged["skeleton"] not in SKELETONS:
+        raise ValueError("skeleton %r, expected one of %s" % (merged["skeleton"], SKELETONS))
+    if merged["skeleton_anchors"] not in (None, "extrema"):
+        raise ValueError('skeleton_anchors %r, expected None or "extrema"' % (merged["skeleton_anchors"],))
+    if merged["skeleton"] is not None and merged["skeleton_anchors"] == "extrema" and not merged["extremities"] > 0:
+        raise ValueError('skeleton_anchors="extrema" needs extremities=K')
     _settings.update(settings)
     _measure_state.update(last=None, centroids_mm=None)
+    _skeleton_state.update(last=None)
     _temporal_state.update(last=None)
     _cluster_state.update(centres_mm=None, references=None, last=None)
     _geodesic_state.update(last=None)
@@ -352,6 +367,8 @@ def set_voxel_positions(width, height, depth):
         _geodesic_frame()
     if _settings["measure"] is not None:
         _measure_frame()
+    if _settings["skeleton"] is not None:
+        _skeleton_frame()
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)
@@ -381,6 +398,23 @@ def _geodesic_frame():
     _geodesic_state["last"] = out
     if _settings["geodesic_paint"] is not None:
         _engine.paint_geodesic(_settings["geodesic_paint"])
+
+
+def _skeleton_frame():
+    """The frame's skeleton (see configure)."""
+    from . import skeleton as sk
+    stats = _engine.thin_hull(_settings["skeleton"], anchors=_settings["skeleton_anchors"])
+    rows = _engine.fetch_skeleton()
+    _skeleton_state["last"] = {"stats": stats, "skeleton": rows, "description": sk.describe(rows, _engine.grid, _engine.bounds)}
+
+
+def skeleton():
+    """The skeleton of the last set_voxel_positions call's hull (configure(skeleton=...)): stats, the dict of
+    CarveEngine.thin_hull; skeleton, the dict of CarveEngine.fetch_skeleton (voxel, record, degree, index); description, the
+    dict of voxcarve.skeleton.describe (positions_mm, edges, edge_mm, length_mm, endpoints, junctions)."""
+    if _engine is None or not initialized or _skeleton_state["last"] is None:
+        raise RuntimeError("no skeleton: configure(skeleton=...) and set_voxel_positions have not run")
+    return _skeleton_state["last"]
 
 
 def _measure_frame():

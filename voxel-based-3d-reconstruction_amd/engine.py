@@ -1151,6 +1151,68 @@ class CarveEngine:
         self._check(self._L.vc_fetch_measure_profile(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_fetch_measure_profile")
         return out[:G]
 
+    # -- the hull thinned to a curve skeleton (vc_hull_thin) -----------------------------------------------------------------------
+    def thin_hull(self, mode="curve", anchors=None, max_passes=_lib.VC_THIN_DEFAULT_PASSES):
+        """Thins the current carve result to a centred, one-voxel-wide skeleton with the hull's components, tunnels and cavities
+        (contract: include/voxcarve.h).  mode "curve" keeps end points, so limbs stay lines; "point" shrinks every component to
+        a topological kernel.  anchors: None, "extrema" (the voxels at distance 0 of a current hull_geodesic: its seeds and its
+        extremities) or linear indices of survivors, which are never removed.  The hull itself stays as it is.  Returns the
+        stats as a dict: survivors, anchors, kept, removed, passes, steps, launches, stable, isolated, endpoints, junctions,
+        thin_ms."""
+        if mode not in ("curve", "point"):
+            raise ValueError('thin_hull: mode %r, expected "curve" or "point"' % (mode,))
+        if not 1 <= int(max_passes) <= _lib.VC_THIN_MAX_PASSES:
+            raise ValueError("thin_hull: max_passes %r not in 1 .. %d" % (max_passes, _lib.VC_THIN_MAX_PASSES))
+        src, lst = _lib.VC_THIN_ANCHORS_NONE, None
+        if isinstance(anchors, str):
+            if anchors != "extrema":
+                raise ValueError('thin_hull: anchors %r, expected None, "extrema" or linear indices' % (anchors,))
+            src = _lib.VC_THIN_ANCHORS_EXTREMA
+        elif anchors is not None:
+            v = np.asarray(anchors).reshape(-1)
+            if v.size and (not np.issubdtype(v.dtype, np.integer) or int(v.min()) < 0 or int(v.max()) > 0xffffffff):
+                raise ValueError("thin_hull: anchors must be linear indices in 0 .. 2^32 - 1")
+            src, lst = _lib.VC_THIN_ANCHORS_LIST, np.ascontiguousarray(v, dtype=np.uint32)
+        st = _lib.VcThinStats()
+        self._check(self._L.vc_hull_thin(self._ctx, _lib.VC_THIN_CURVE if mode == "curve" else _lib.VC_THIN_POINT, src,
+                                         None if lst is None or lst.size == 0 else _ptr(lst, ctypes.c_uint32),
+                                         0 if lst is None else lst.size, int(max_passes), 0, ctypes.byref(st)), "vc_hull_thin")
+        self._thin = (int(st.survivors), int(st.kept))
+        out = {name: int(getattr(st, name)) for name, _ in _lib.VcThinStats._fields_ if name != "thin_ms"}
+        out["thin_ms"] = float(st.thin_ms)
+        return out
+
+    def thin_valid(self):
+        """True while the skeleton of the last thin_hull() describes the current hull."""
+        return self._L.vc_fetch_thin(self._ctx, None) == _lib.VC_OK
+
+    def fetch_thin(self):
+        """u16 [S]: per record 0 when the last thin_hull kept its voxel, else 1 + 6 (pass - 1) + d of the direction step that
+        removed it -- the order in which the hull was peeled."""
+        S = getattr(self, "_thin", (0, 0))[0]
+        out = np.zeros(max(S, 1), dtype=np.uint16)
+        self._check(self._L.vc_fetch_thin(self._ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))), "vc_fetch_thin")
+        return out[:S]
+
+    def fetch_skeleton(self):
+        """The kept voxels of the last thin_hull, ascending by voxel: dict of voxel u32 [K], record u32 [K], degree u8 [K] (the
+        kept voxels among the 26 neighbours) and index i64 [K, 3] = (ix, iy, iz)."""
+        K = getattr(self, "_thin", (0, 0))[1]
+        raw = np.zeros((max(K, 1), 3), dtype=np.uint32)
+        self._check(self._L.vc_fetch_skeleton(self._ctx, raw.ctypes.data_as(ctypes.POINTER(_lib.VcSkeletonVoxel))), "vc_fetch_skeleton")
+        raw = raw[:K]
+        nx, ny, _ = self.grid
+        i = raw[:, 0].astype(np.int64)
+        return {"voxel": raw[:, 0].copy(), "record": raw[:, 1].copy(), "degree": (raw[:, 2] & 0xff).astype(np.uint8),
+                "index": np.stack([(i // ny) % nx, i % ny, i // (nx * ny)], axis=1)}
+
+    def fetch_thin_table(self):
+        """u8 [2^23]: bit c (byte c >> 3, bit c & 7) says whether a voxel whose 26 neighbours have the code c is simple -- the
+        table thin_hull looks up with option thin_table = 1, built on the device at first use."""
+        out = np.zeros(_lib.VC_THIN_TABLE_BYTES, dtype=np.uint8)
+        self._check(self._L.vc_fetch_thin_table(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_thin_table")
+        return out
+
     def set_option(self, name, value):
         """Launch-geometry tuning knobs (never change results); see vc_set_option."""
         self._check(self._L.vc_set_option(self._ctx, name.encode(), int(value)), "vc_set_option")
