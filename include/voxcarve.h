@@ -205,7 +205,15 @@ int vc_carve(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int 
  * vc_allgather read.  The steps rotate through three sets of result buffers: a vc_carve_begin that is queued into the set
  * holding the collected result (the third one after it was issued) takes it away -- fetch before that call; afterwards the
  * vc_fetch_* functions fail with VC_ERR_ARG until the next vc_carve_end.
- * min_views > n_cameras is legal and yields the empty result (as the reference's threshold test would). */
+ * min_views > n_cameras is legal and yields the empty result (as the reference's threshold test would).
+ * KNOWN DEFECT, not yet fixed: steps in flight must share one colour camera.  With option fused_color_table = 1 (the default) a
+ * VC_MODE_FUSED step colours its survivors from ONE table over the whole grid, projected for one camera (vc_ctx::d_lut_color).  A
+ * vc_carve_begin with another color_cam projects its camera's table over it on the carve stream while the record expansion of
+ * the step before it may still be reading it on the second stream: nothing orders the two.  Seen on the device with two steps
+ * on two slots, color_cam 1 then 2, 30 x 63 x 30: 158 to 559 of the first step's 2797 records came back with colour and `seen`
+ * bytes of zero, another number in every run; the indices, the count and the second step were right.  vc_carve (begin + end)
+ * and VC_MODE_LUT (a table per camera) are not affected.  Until the projection waits for {step done} of the last expansion that
+ * was given the table, collect a step before beginning one with another colour camera, or set fused_color_table = 0. */
 int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int mode, uint32_t flags);
 int vc_carve_end(vc_ctx *ctx, uint64_t *n_out);
 /* Footprint carve: a camera passes a voxel by the foreground count of the pixel box its whole CELL projects to, not by the one
@@ -482,6 +490,9 @@ int vc_fetch_grown(vc_ctx *ctx, uint8_t *added);   /* u8 [S_after], record order
  *   7 state: the ring and P survive carves, passes and results.  They are reset by vc_temporal_reset, by a change of grid, slab or
  *     cameras, and by a call whose `window` differs from the ring's.  keep_on and keep_off may change from call to call.
  *   8 one push per result: the call is refused when the current result is already the last call's output.  Carve again first.
+ *     A pass that makes another result of it (erode, open, components, photo-consistency, a grow that adds voxels) lifts the
+ *     refusal as a carve does, and that result is pushed as it stands.  So does vc_temporal_reset: the votes of the last call go
+ *     with the ring (vc_fetch_temporal fails), and the current result may be pushed as the first hull of the new ring.
  *   9 VC_ERR_ARG (with a message, nothing launched, no state touched) when there is no carve result, steps are in flight, the
  *     carve ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached,
  *     flags != 0, stats == NULL, window is 0 or above 15, keep_on or keep_off is out of range, the grid has more voxels than a u32
@@ -775,7 +786,9 @@ int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette /* [VC_
  *   5 lifetime: vc_fetch_measure and vc_fetch_measure_profile fail ("no measurements") until the pass has run on the current
  *     result and again after anything that changes which voxels survive, as vc_fetch_component_labels does; the profile also
  *     when the last call ran without VC_MEASURE_PROFILE.  Colour passes leave them valid: the colour sums describe the records
- *     as they were at the call.
+ *     as they were at the call.  So does a later vc_hull_clusters or vc_hull_geodesic: the groups stay those of the labels that
+ *     were current at the call, whatever the label source holds by now.  A vc_hull_grow or vc_hull_temporal that adds and
+ *     removes nothing leaves them valid as well; one that changes the hull does not.
  * stats (required): survivors; groups = G; measured = the records in some group; unlabelled = survivors - measured;
  * measure_ms = HIP events around the whole call.  voxcarve.measure derives world units (mm^3, mm^2, centroid, principal axes)
  * from these integers and the grid on the host. */
@@ -837,7 +850,9 @@ int vc_fetch_measure_profile(vc_ctx *ctx, uint64_t *out);                  /* [G
  *     first such position and its voxel), or VC_THIN_ANCHORS_EXTREMA comes without a current vc_hull_geodesic.  S = 0 is no
  *     error.  Synchronous.
  *   8 lifetime: vc_fetch_thin and vc_fetch_skeleton fail ("no skeleton") until the pass has run on the current result and again
- *     after anything that changes which voxels survive, as vc_fetch_component_labels does; colour passes leave them valid.
+ *     after anything that changes which voxels survive, as vc_fetch_component_labels does; colour passes leave them valid, and
+ *     so does a later vc_hull_geodesic: a skeleton anchored at VC_THIN_ANCHORS_EXTREMA keeps the anchors of the geodesic pass that
+ *     was current at the call.
  * Two routes evaluate the predicate, with equal bytes: in registers (option thin_table = 0, the default until the table has been
  * measured faster) or by a look-up in the table of 2^26 bits, which a kernel builds with the same function at first use
  * (thin_table = 1).  stats (required): survivors; anchors = the distinct anchor voxels; kept, removed; passes = passes run;

@@ -1,18 +1,26 @@
 """What a context holds behind a carve, as include/voxcarve.h describes it, in numpy and without a GPU: the current records, and for
 every product of a post-carve pass whether it is valid and its bytes.  Every operation goes through the restatements that the
 per-pass tests already hold the device to (oracle.carve_c / carve_np, footprint_np, closing_np, distance_np, components_np,
-visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, oracle.marching_np); nothing is restated here.
-What this module adds is how the passes COMBINE: which records a pass starts from, which frame set it reads, what it invalidates.
+visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, temporal_np, measure_np, thin_np,
+oracle.marching_np); nothing is restated here.  What this module adds is how the passes COMBINE: which records a pass starts from,
+which frame set it reads, whose labels it takes, what it invalidates, and the one state that outlives a result (the vote's ring).
+
+Two families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
+and does not know them: tests/golden/chain_digests.json holds its records, so that it cannot move.  B (SEEDS_B, CHAIN_LEN_B,
+KINDS_B) draws from every kind, with carve -> temporal pairs on different slots in most chains.  tests/test_gpu_chain.py walks family
+A on the device; family B is held to its coverage conditions, its literal twins and its faults in tests/test_chain_model.py, and
+its walk on the device is not in the suite yet (REFUSAL_B names what its products' fetches are to refuse with there).
 
   scene(grid)            one of GRIDS, the golden cameras, three frame sets (slots 0, 1, 2) with different hulls and colours
-  draw_chain(seed)       (scene, ops): CHAIN_LEN operations with all their parameters, drawn with numpy.random.default_rng(seed)
-                         alone; some draws (min_voxels) look at the model's state, so the chain is applied while it is drawn
+  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B) operations with all their parameters, drawn with
+                         numpy.random.default_rng(seed) alone; some draws (min_voxels, the sources of a measurement, anchors) look
+                         at the model's state, so the chain is applied while it is drawn
   Model(scene).apply(op) applies one operation; returns what the call returns and produces (stats, flags, labels, fields, images)
   replay(seed, upto=k)   the model in front of step k of that chain
   trace(seed)            one row per step (what ran, on how many records, whether the hull changed, ...) for the coverage conditions
 
 A record is uint64: the linear index in the low 32 bits, r, g, b in bytes 4 - 6, `seen` in byte 7.  The product names are those of
-test_gpu_result_generation.REFUSAL / BUILT."""
+test_gpu_result_generation.REFUSAL / BUILT and, for the three passes that only family B knows, of REFUSAL_B."""
 import hashlib
 import os
 import sys
@@ -26,10 +34,13 @@ import distance_np as dn
 import fixtures_util as fx
 import footprint_np as fp
 import geodesic_np as gn
+import measure_np as mn
 import normals_np as nn
 import photo_np as pn
 import render_np as rn
 import surface_np as sn
+import temporal_np as tpn
+import thin_np as thn
 import visible_np as vn
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -39,22 +50,31 @@ if _ROOT not in sys.path:
 from oracle import carve_c, carve_np, marching_np                    # noqa: E402
 from test_gpu_result_generation import BUILT, REFUSAL, RENDER_HW, _views   # noqa: E402
 
-SEEDS = tuple(range(601, 625))              # the 24 chains of tests/test_chain_model.py and tests/test_gpu_chain.py
+SEEDS = tuple(range(601, 625))              # family A: the 24 chains drawn before the vote, the measurements and the skeleton existed
 CHAIN_LEN = 10
+SEEDS_B = tuple(range(701, 725))            # family B: every kind
+CHAIN_LEN_B = 14
 GRIDS = ((40, 65, 36), (24, 130, 20), (30, 63, 30), (37, 53, 29))
 BOUNDS = carve_np.DEFAULT_BOUNDS
 ROLLS = (0, 9, -13)                         # columns the golden masks are rolled by in slots 0, 1, 2
 SLOT_IMAGES = ((0, 1, 2, 3), (0, 1, 2, 3), (1, 2))   # cameras with an image per slot: slot 2 cannot feed a colour pass
 FULL_SLOTS = tuple(s for s, cams in enumerate(SLOT_IMAGES) if len(cams) == 4)
 COLOUR_CAMERAS = (None, 1, 2)
-PRODUCTS = tuple(REFUSAL) + ("render", "surface")
-assert set(PRODUCTS) >= BUILT
+# the products of the passes that only family B knows -> the refusal of their fetches (fetch_temporal; fetch_measure and, after
+# profile=True, fetch_measure_profile; fetch_thin + fetch_skeleton) once the result is another (include/voxcarve.h)
+REFUSAL_B = {"temporal": "no votes", "measure": "no measurements", "skeleton": "no skeleton"}
+PRODUCTS = tuple(REFUSAL) + ("render", "surface") + tuple(REFUSAL_B)
+assert set(PRODUCTS) >= BUILT and not set(REFUSAL_B) & (set(REFUSAL) | BUILT)
 
 HULL_CHANGERS = ("close", "dilate", "erode", "open", "filter_components", "photo_carve")
 COMPACTIONS = ("erode", "open", "filter_components", "photo_carve")
 COLOUR_PASSES = ("color_visible", "photo_carve")
 QUIET = ("hull_distance", "hull_normals", "render", "surface_mesh")
 KINDS = ("carve",) + HULL_CHANGERS + ("color_visible", "clusters", "geodesic") + QUIET
+NEW_KINDS = ("temporal", "measure", "thin")
+KINDS_B = KINDS + NEW_KINDS + ("temporal_reset",)
+RECOLOURING = ("color_visible", "clusters", "geodesic")      # change record colours and leave the hull alone
+MEASURE_SOURCES = ("all", "clusters", "geodesic", "components", "host")
 
 LOW = np.uint64(0xffffffff)
 NOT_RGB = np.uint64(0xff000000ffffffff)
@@ -145,8 +165,10 @@ def scene(grid):
 # ---- the model --------------------------------------------------------------------------------------------------------------------
 class Model:
     """fault: None, or one deliberate mistake of the kind the chains exist to catch (tests/test_chain_model.py feeds it to the
-    comparison on the CPU): "grow_slot0" colours added voxels from slot 0 instead of the carve's slot, "drop_paint" gives the
-    records that a compaction keeps the colours of the carve again."""
+    comparison on the CPU): "grow_slot0" colours added and restored voxels from slot 0 instead of the carve's slot, "drop_paint" gives the
+    records that a compaction keeps the colours of the carve again, "temporal_forgets_prev" empties the vote's previous output
+    at every carve (no hysteresis across frames), "measure_carve_colours" sums the colours the carve gave the records instead of
+    the ones they have at the call."""
 
     def __init__(self, sc, fault=None, literal=False):
         self.scene = sc
@@ -159,6 +181,10 @@ class Model:
         self.products = {}                   # name -> bytes, for the valid ones
         self.mesh_shape = (0, 0)             # (V, F) of the last surface mesh
         self.painted = False                 # a colour pass or a paint has run since the carve
+        self.vote = tpn.Vote()               # the ring and P of vc_hull_temporal: they outlive carves, passes and results
+        self.labels = {}                     # what a measurement or a skeleton may read while the product of that name is valid:
+        #                                      "clusters" (u8 labels, K), "geodesic" (u8 labels, extremities, distances),
+        #                                      "component_labels" (the dict of components_np)
 
     # what the result is
     @property
@@ -210,6 +236,8 @@ class Model:
         self.carve = {k: op[k] for k in ("slot", "min_views", "color_cam")}
         self.painted = False
         self._changed()
+        if self.fault == "temporal_forgets_prev":
+            self.vote.prev = None
         out["count"] = int(rec.size)
         return out
 
@@ -257,6 +285,7 @@ class Model:
         w = (ccn.components_literal if self.literal else ccn.components)(self.idx, self.grid, op["connectivity"], op["min_voxels"], op["keep_largest"])
         self.records = self._compacted(w["keep"])
         self._changed({"component_labels": w["labels"].tobytes()})
+        self.labels["component_labels"] = w
         K = int(w["label"].size)
         return {"stats": {"components": K, "components_kept": int(w["kept"].sum()), "survivors_before": S0, "survivors_after": self.S,
                           "largest": int(w["size"].max()) if K else 0},
@@ -289,6 +318,7 @@ class Model:
         w = (cn.clusters_literal if self.literal else cn.clusters)(self.occ(), qxy, op["k"], max_iters=op["max_iters"], min_column=op["min_column"])
         d = cn.describe(self.records, self.grid, w)                          # (the histograms: the colours in front of the paint)
         self.products["clusters"] = d["labels"].tobytes()
+        self.labels["clusters"] = (d["labels"], int(op["k"]))
         self.records = cn.paint(self.records, d["labels"], op["palette"])
         self.painted = True
         return {"stats": {k: w[k] for k in ("survivors", "columns", "weight", "iterations", "q")}, "converged": bool(w["converged"]),
@@ -300,6 +330,7 @@ class Model:
         srec = gn.seeds_by_layer(idx, self.grid, op["seeds"], op["layers"])
         w = gn.geodesic(idx, self.grid, sc.q, op["connectivity"], srec, op["extrema"], method="dijkstra" if self.literal else "bellman")
         self.products["geodesic"] = w["d"].tobytes()
+        self.labels["geodesic"] = (w["labels"], int(w["extremities"]), w["d"])
         self.records = with_rgb(self.records, gn.paint(self.rgb, w["keys"], op["paint"], op["palette"], w["max_d"]))
         self.painted = True
         rows = [(x["label"], x["voxel"], x["record"], x["d"], x["ix"], x["iy"], x["iz"]) for x in w["extrema"]]
@@ -341,6 +372,81 @@ class Model:
         self.mesh_shape = (int(w["verts"].shape[0]), int(w["faces"].shape[0]))
         self.products["surface"] = np.ascontiguousarray(w["verts"]).tobytes() + np.ascontiguousarray(w["faces"]).tobytes()
         return {"mesh": w, "stats": dict(w["stats"], n_faces=self.mesh_shape[1])}
+
+    # the vote over the last hulls: the ring and P are the model's, not the result's
+    def _temporal(self, op):
+        sc = self.scene
+        hull, S0 = self.occ(), self.S
+        ring_before, window_before = len(self.vote.ring), self.vote.window
+        out, counts, st = self.vote.push(hull, op["window"], op["keep"], op["keep_off"])
+        cc = self.carve["color_cam"]             # restored voxels: the carve's own frame set and colour camera
+        slot = 0 if self.fault == "grow_slot0" else self.carve["slot"]
+        rec, votes, added = tpn.records_after(self.records, hull, out, counts, self.grid, self.bounds, None if cc is None else sc.oc[cc],
+                                              None if cc is None else sc.frames[slot][cc], sc.H, sc.W)
+        own = {"temporal": votes.tobytes() + added.tobytes()}
+        changed = bool(st["added"] or st["removed"])
+        if changed:
+            self.records = rec
+            self._changed(own)
+        else:                                    # O_t == H_t: nothing is invalidated, the result generation stays
+            assert np.array_equal(rec, self.records) and not added.any()
+            self.products.update(own)
+        return {"stats": st, "votes": votes, "added": added, "changed": changed, "ring_before": ring_before,
+                "window_before": window_before, "by_hysteresis": int((out & ~(counts >= st["on"])).sum())}
+
+    def _temporal_reset(self, op):
+        self.vote.reset()
+        self.products.pop("temporal", None)
+        return {}
+
+    def components_current(self):
+        """The components of a filter_components that is current and removed nothing: its labels are in the result's order."""
+        return "component_labels" in self.products and bool(self.labels["component_labels"]["keep"].all())
+
+    def measure_labels(self, op):
+        """(u32 labels [S], G) of a measurement's source, from what the model holds as current."""
+        src = op["source"]
+        if src == "all":
+            return mn.labels_of("all", self.S)
+        if src == "host":
+            return mn.labels_of("host", self.S, op["labels"], op["groups"])
+        if src == "clusters":
+            assert "clusters" in self.products
+            return mn.labels_of("clusters", self.S, *self.labels["clusters"])
+        if src == "geodesic":
+            assert "geodesic" in self.products
+            return mn.labels_of("geodesic", self.S, *self.labels["geodesic"][:2])
+        assert src == "components" and self.components_current()
+        w = self.labels["component_labels"]
+        return mn.component_ranks(w["labels"], w["label"], w["size"]), max(int(w["label"].size), 1)
+
+    def _measure(self, op):
+        lab, G = self.measure_labels(op)
+        rec = self.records
+        if self.fault == "measure_carve_colours" and rec.size and self.carved.size:
+            base, i = self.carved, index_of(rec)
+            pos = np.minimum(np.searchsorted(index_of(base), i), base.size - 1)
+            hit = index_of(base)[pos] == i
+            rec = rec.copy()
+            rec[hit] = with_rgb(rec[hit], rgb_of(base[pos[hit]]))
+        w = (mn.measure_literal if self.literal else mn.measure)(rec, self.grid, lab, G, op["profile"])
+        self.products["measure"] = b"".join(np.ascontiguousarray(w[k]).tobytes() for k in mn.FIELDS) + \
+            (w["profile"].tobytes() if op["profile"] else b"")
+        return {"stats": mn.stats(rec, lab, G), "measure": w, "labels": lab, "groups": G}
+
+    def thin_anchors(self, op):
+        """The linear indices that a thinning pins: none, a list, or the voxels at distance 0 of the current geodesic pass."""
+        if isinstance(op["anchors"], str):
+            assert op["anchors"] == "extrema" and "geodesic" in self.products
+            return self.idx[self.labels["geodesic"][2] == 0]
+        return op["anchors"]
+
+    def _thin(self, op):
+        w = (thn.thin_literal if self.literal else thn.thin)(self.idx, self.grid, op["mode"], self.thin_anchors(op), op["max_passes"])
+        rows = np.zeros((w["voxel"].size, 3), dtype=np.uint32)   # vc_skeleton_voxel_t: {u32 voxel, u32 record, u8 degree, 3 zero bytes}
+        rows[:, 0], rows[:, 1], rows[:, 2] = w["voxel"], w["record"], w["degree"]
+        self.products["skeleton"] = w["peel"].tobytes() + rows.tobytes()
+        return {"stats": {k: w[k] for k in thn.STATS}, "thin": w}
 
     # what the end of a chain compares on the final hull
     def marching_cubes(self):
@@ -407,6 +513,34 @@ def _draw(rng, sc, model, kind):
         return {"op": kind}
     if kind == "surface_mesh":
         return {"op": kind, "refine_steps": pick((0, 3, 8))}
+    # family B
+    if kind == "temporal":                       # mostly the ring's own window: another one starts the ring over
+        window = model.vote.window if model.vote.window and rng.random() < 0.85 else pick((2, 3, 4))
+        r = rng.random()                         # slow to take a voxel and slow to let it go; a plain vote; or any thresholds
+        keep = window if r < 0.35 else int(rng.integers(1, window + 1))
+        return {"op": kind, "window": window, "keep": keep, "keep_off": 1 if r < 0.35 else keep if r < 0.6 else int(rng.integers(1, keep + 1))}
+    if kind == "temporal_reset":
+        return {"op": kind}
+    if kind == "measure":                        # among the sources that are current, the rarer ones more often
+        have = [("all", 1.0), ("host", 1.0)] + [(s, 6.0) for s in ("clusters", "geodesic") if s in model.products] + \
+            ([("components", 8.0)] if model.components_current() else [])
+        p = np.array([w for _, w in have])
+        op = {"op": kind, "source": pick([s for s, _ in have], p / p.sum()), "profile": bool(rng.integers(2))}
+        if op["source"] == "host":
+            G = int(rng.integers(1, 7))
+            lab = rng.integers(0, G, model.S).astype(np.uint32)
+            lab[rng.random(model.S) < 0.1] = mn.NONE
+            op.update(labels=lab, groups=G)
+        return op
+    if kind == "thin":
+        op = {"op": kind, "mode": pick(thn.MODES), "anchors": None, "max_passes": pick((thn.MAX_PASSES, 1, 2), (0.8, 0.1, 0.1))}
+        r = rng.random()
+        if "geodesic" in model.products and r < 0.85:
+            op["anchors"] = "extrema"
+        elif model.S and r > 0.55:               # a few survivors, one of them twice
+            a = model.idx[rng.integers(0, model.S, int(rng.integers(1, 7)))].astype(np.uint32)
+            op["anchors"] = np.concatenate([a, a[:1]])
+        return op
     raise ValueError(kind)
 
 
@@ -430,10 +564,15 @@ _WEIGHTS = {"carve": 1.2, "close": 0.8, "dilate": 0.7, "erode": 0.8, "open": 0.8
 _CHAINS = {}
 
 
+def family(seed):
+    return "B" if seed in SEEDS_B else "A"
+
+
 def draw_chain(seed):
-    """(scene, ops) of chain `seed`: a carve, then CHAIN_LEN - 1 drawn operations; now and then a burst of hull-changing passes."""
+    """(scene, ops) of chain `seed`.  Family A: a carve, then CHAIN_LEN - 1 drawn operations; now and then a burst of hull-changing
+    passes.  Family B: see _draw_chain_b."""
     if seed not in _CHAINS:
-        _CHAINS[seed] = _draw_chain(seed)
+        _CHAINS[seed] = (_draw_chain_b if family(seed) == "B" else _draw_chain)(seed)
     return _CHAINS[seed]
 
 
@@ -458,6 +597,57 @@ def _draw_chain(seed):
             if kind in HULL_CHANGERS and rng.random() < 0.5:
                 burst = int(rng.integers(2, 4))
         op = _draw(rng, sc, model, kind)
+        model.apply(op)
+        ops.append(op)
+    return sc, ops
+
+
+_WEIGHTS_B = {"carve": 1.5, "temporal": 2.0, "temporal_reset": 0.5, "measure": 1.5, "thin": 2.2, "close": 0.4, "dilate": 0.4,
+              "erode": 0.4, "open": 0.4, "filter_components": 0.7, "photo_carve": 0.4, "color_visible": 0.7, "clusters": 0.8,
+              "geodesic": 1.2, "hull_distance": 0.15, "hull_normals": 0.15, "render": 0.15, "surface_mesh": 0.15}
+assert set(_WEIGHTS_B) == set(KINDS_B)
+
+
+def _draw_chain_b(seed):
+    """A carve, then CHAIN_LEN_B - 1 operations drawn from every kind.  More often than not a vote follows a carve at once, so most
+    chains hold several carve -> temporal pairs on different slots; a vote drawn where the header refuses one (the current result is
+    already the last vote's output, item 8) becomes the carve that it asks for, with the vote behind it.  Half of the
+    filter_components runs drop nothing, and most of those are followed by a measurement, which may then take their labels; likewise
+    a measurement or a skeleton often follows the clusters or the geodesic distances that it can read.
+    The header refuses a vote in two more cases, which no chain can reach as the operations stand: with steps in flight (the
+    model's pipelined carve collects both of its steps before it returns) and on a slot prepared again since the carve (no
+    operation uploads or prepares anything behind a carve: the frame sets are fixed by the scene).  An operation that leaves a
+    step in flight or feeds a slot new input has to keep `temporal` out of the draw until the next carve, as item 9 of
+    vc_hull_temporal says."""
+    rng = np.random.default_rng(seed)
+    sc = scene(GRIDS[int(rng.integers(len(GRIDS)))])
+    model = Model(sc)
+    kinds = list(_WEIGHTS_B)
+    p = np.array([_WEIGHTS_B[k] for k in kinds])
+    p /= p.sum()
+    ops, queue = [], []
+    while len(ops) < CHAIN_LEN_B:
+        if not ops:
+            kind = "carve"
+        elif model.S == 0 and rng.random() < 0.5:
+            kind, queue = "carve", []
+        elif queue:
+            kind = queue.pop(0)
+        else:
+            kind = kinds[int(rng.choice(len(kinds), p=p))]
+        if kind == "temporal" and "temporal" in model.products:
+            kind, queue = "carve", ["temporal"]
+        op = _draw(rng, sc, model, kind)
+        if kind == "carve" and not queue and rng.random() < 0.6:
+            queue = ["temporal"]
+        if kind == "filter_components" and rng.random() < 0.5:
+            op.update(min_voxels=0, keep_largest=0)
+            if rng.random() < 0.8:
+                queue = ["measure"]
+        if kind in ("clusters", "geodesic") and not queue and rng.random() < 0.75:
+            queue = ["measure" if kind == "clusters" or rng.random() < 0.4 else "thin"]
+        if kind == "temporal_reset" and not queue and len(model.products) >= 2 and rng.random() < 0.8:
+            queue = ["temporal"]                 # the first vote after a reset changes nothing: every product must stay
         model.apply(op)
         ops.append(op)
     return sc, ops
@@ -488,25 +678,47 @@ def replay(seed, upto=None, fault=None, literal=False):
 
 
 def describe_op(op):
-    """The parameters of an operation as one short line (palettes as their shape), for the failure messages."""
-    return ", ".join("%s=%s" % (k, ("u8%r" % (v.shape,)) if isinstance(v, np.ndarray) else repr(v)) for k, v in op.items())
+    """The parameters of an operation as one short line (arrays as their type and shape), for the failure messages."""
+    return ", ".join("%s=%s" % (k, ("%s%r" % (v.dtype.name, v.shape)) if isinstance(v, np.ndarray) else repr(v)) for k, v in op.items())
 
 
-def trace(seed):
-    """One dict per step: op, kind of carve, records before and after, whether the hull changed, and what the records carried
-    into the operation (seen == 0 bytes, painted colours)."""
+def products_digest(model):
+    """sha1 over the valid products, sorted by name: each name and its bytes."""
+    h = hashlib.sha1()
+    for name in sorted(model.products):
+        h.update(name.encode())
+        h.update(model.products[name])
+    return h.hexdigest()
+
+
+def trace(seed, fault=None):
+    """One dict per step: op, kind of carve, records before and after, whether the hull changed, what the records carried into
+    the operation (seen == 0 bytes, painted colours), the valid products in front of and behind it and their digest, the carve that
+    made the result, what made its hull last (the carve or a pass that changed it), and the call's stats."""
     rows = []
     sc, ops = draw_chain(seed)
-    model = Model(sc)
+    model = Model(sc, fault)
+    carve_op = made_by = None
     for step, op in enumerate(ops):
         before = None if model.records is None else model.records
         carve_slot = None if model.carve is None else model.carve["slot"]
         row = {"step": step, "op": op["op"], "before": 0 if before is None else int(before.size),
                "seen0": bool(before is not None and before.size and (seen_of(before) == 0).any()),
-               "painted": bool(model.painted and before is not None and before.size), "carve_slot": carve_slot, "params": op}
+               "painted": bool(model.painted and before is not None and before.size), "carve_slot": carve_slot, "params": op,
+               "carve_op": carve_op, "made_by": made_by, "valid_before": dict(model.products)}
         out = model.apply(op)
         row["after"] = model.S
         row["digest"] = hashlib.sha1(model.records.tobytes()).hexdigest()
+        row["products_digest"] = products_digest(model)
+        row["valid"] = dict(model.products)
         row["changed"] = bool(out.get("changed", False)) if op["op"] != "carve" else False
+        row["stats"] = out.get("stats")
+        for k in ("ring_before", "window_before", "by_hysteresis"):
+            if k in out:
+                row[k] = out[k]
+        if op["op"] == "carve":
+            carve_op = made_by = op
+        elif row["changed"]:
+            made_by = op
         rows.append(row)
     return rows

@@ -1,14 +1,22 @@
 """tests/chain_model.py without a GPU: the chains that tests/test_gpu_chain.py walks are not hollow, and the model agrees with itself.
 
-The coverage conditions below are conditions on the INPUTS of the GPU test (chain_model.SEEDS, the draw weights), asserted here so that
-it cannot pass by doing nothing; where one fails, the seeds or the weights change, never the thresholds.  Then: the scene's three
-frame sets differ, the chains and replay() are deterministic, the literal twin of every restatement that has an affordable one gives
-the model's bytes at states the chains reach, and one deliberately wrong model -- a mistake of the kind the chains exist to catch --
-is told apart from the right one by the records alone.
+Two families of chains: A (chain_model.SEEDS: carves, morphology, components, photo-consistency, colour passes, clusters, geodesic
+distances, distance field, normals, images, mesh) and B (chain_model.SEEDS_B: all of these and the vote over the last hulls, the
+measurements and the skeleton).  Family A is held to the record digests it had before family B existed
+(tests/golden/chain_digests.json): what its seeds cover has not moved.  tests/test_gpu_chain.py walks family A on the device; family B
+is checked here alone so far, and every condition below is written so that its walk on the device can be added without another draw.
+
+The coverage conditions below are conditions on the INPUTS of the GPU test (the seeds, the draw weights, the lengths), asserted here
+so that it cannot pass by doing nothing; where one fails, the seeds, the weights or the length change, never the thresholds.  Then:
+the scene's three frame sets differ, the chains and replay() are deterministic, the literal twin of every restatement that has an
+affordable one gives the model's bytes at states the chains reach, and deliberately wrong models -- mistakes of the kind the chains
+exist to catch -- are told apart from the right one by the records or by the products' bytes.
 
 Not run here: footprint_np.carve_literal, whose loop over every pixel of every voxel's box takes minutes at the chains' grids
 (tests/test_footprint_restatement.py holds it to the vectorised form on its own grids)."""
 import collections
+import json
+import os
 
 import numpy as np
 import pytest
@@ -17,6 +25,7 @@ import chain_model as cm
 import closing_np as cl
 import distance_np as dn
 import surface_np as sn
+import temporal_np as tpn
 from oracle import carve_c, carve_np
 
 
@@ -25,9 +34,17 @@ def traces():
     return {seed: cm.trace(seed) for seed in cm.SEEDS}
 
 
+@pytest.fixture(scope="module")
+def traces_b():
+    return {seed: cm.trace(seed) for seed in cm.SEEDS_B}
+
+
 def test_seed_list():
     assert len(cm.SEEDS) == len(set(cm.SEEDS)) == 24 and cm.CHAIN_LEN == 10
-    assert set(cm.PRODUCTS) == set(cm.REFUSAL) | cm.BUILT          # (the product names of test_gpu_result_generation, imported)
+    assert 0 < len(cm.SEEDS_B) == len(set(cm.SEEDS_B)) <= 24 and cm.CHAIN_LEN_B <= 14 and not set(cm.SEEDS) & set(cm.SEEDS_B)
+    assert [cm.family(s) for s in (cm.SEEDS[0], cm.SEEDS_B[0])] == ["A", "B"]
+    assert set(cm.KINDS_B) > set(cm.KINDS) and set(cm.NEW_KINDS) <= set(cm.KINDS_B) - set(cm.KINDS)
+    assert set(cm.PRODUCTS) == set(cm.REFUSAL) | cm.BUILT | set(cm.REFUSAL_B)   # (the product names of test_gpu_result_generation, imported, and family B's)
 
 
 def test_the_three_frame_sets_differ():
@@ -106,7 +123,112 @@ def test_coverage_of_the_chains(traces):
     assert painted >= 6
 
 
-def test_chains_and_replay_are_deterministic(traces):
+def test_family_a_did_not_move(traces):
+    """The records behind every step of the 24 chains of family A are those the chains gave before the model knew the vote, the
+    measurements and the skeleton: the new kinds were not fed into the old draw."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "chain_digests.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(str(s) for s in cm.SEEDS)
+    for seed in cm.SEEDS:
+        assert [r["digest"] for r in traces[seed]] == want[str(seed)], seed
+        assert not any(r["op"] in cm.NEW_KINDS + ("temporal_reset",) for r in traces[seed])
+
+
+def test_coverage_of_family_b(traces_b):
+    """What the chains of family B exercise of the vote, the measurements and the skeleton."""
+    n = collections.Counter()
+    ran = collections.Counter()                  # kind -> runs on a non-empty hull
+    slots = collections.Counter()                # slot of the carve behind a vote
+    sources = collections.Counter()
+    modes = collections.Counter()
+    for seed, rows in traces_b.items():
+        assert len(rows) == cm.CHAIN_LEN_B and rows[0]["op"] == "carve"
+        thin_S = None                            # the S of the chain's previous skeleton
+        for r in rows:
+            op, p, st = r["op"], r["params"], r["stats"]
+            ran[op] += r["before"] > 0 if op != "carve" else r["after"] > 0
+            had, has = r["valid_before"], r["valid"]
+            if "measure" in had and op != "measure":
+                same = has.get("measure") == had["measure"]
+                n["measure carried across a colour pass"] += op in cm.RECOLOURING and same
+                n["measure dropped by a hull change"] += r["changed"] and "measure" not in has
+                assert same or "measure" not in has
+            if op == "temporal":
+                assert "temporal" not in had, "one push per result"
+                made = r["made_by"]
+                n["frames >= 2"] += st["frames"] >= 2
+                n["changed"] += r["changed"]
+                n["added > 0"] += st["added"] > 0
+                n["removed > 0"] += st["removed"] > 0
+                n["kept by hysteresis"] += p["keep_off"] < p["keep"] and r["by_hysteresis"] > 0
+                n["on a pass's hull"] += made["op"] in cm.HULL_CHANGERS
+                n["behind a pipelined carve"] += r["carve_op"]["first"] is not None
+                n["behind a footprint carve"] += r["carve_op"]["footprint"] != "centre"
+                n["colour camera None"] += r["carve_op"]["color_cam"] is None
+                n["window changed, ring non-empty"] += r["ring_before"] > 0 and r["window_before"] != p["window"]
+                n["changed nothing, two other products valid"] += not r["changed"] and len(had) >= 2
+                slots[r["carve_slot"]] += 1
+                if not r["changed"]:
+                    assert all(has[k] == had[k] for k in had) and set(has) == set(had) | {"temporal"}
+                else:
+                    assert set(has) == {"temporal"}
+            elif op == "temporal_reset":
+                n["reset with the ring non-empty"] += any(q["op"] == "temporal" for q in rows[:r["step"]])
+            elif op == "measure":
+                sources[p["source"]] += 1
+                n["profile"] += p["profile"]
+                n["measure of painted records"] += r["painted"]
+            elif op == "thin":
+                modes[p["mode"]] += 1
+                n["extrema anchors"] += isinstance(p["anchors"], str)
+                n["list anchors"] += isinstance(p["anchors"], np.ndarray)
+                n["cut short"] += st["stable"] == 0
+                if thin_S is not None:
+                    n["thin on another S"] += st["survivors"] != thin_S
+                    n["thin on a larger S"] += st["survivors"] > thin_S
+                thin_S = st["survivors"]
+    print("family B, operations on a non-empty hull:", {k: ran[k] for k in cm.KINDS_B})
+    print("family B, votes:", {k: n[k] for k in ("frames >= 2", "changed", "added > 0", "removed > 0", "kept by hysteresis", "on a pass's hull",
+                                                 "behind a pipelined carve", "behind a footprint carve", "colour camera None",
+                                                 "window changed, ring non-empty", "changed nothing, two other products valid",
+                                                 "reset with the ring non-empty")}, "carve slots behind votes:", dict(slots))
+    print("family B, measurements:", dict(sources), {k: n[k] for k in ("profile", "measure of painted records",
+                                                                       "measure carried across a colour pass", "measure dropped by a hull change")})
+    print("family B, skeletons:", dict(modes), {k: n[k] for k in ("extrema anchors", "list anchors", "cut short", "thin on another S",
+                                                                  "thin on a larger S")})
+    assert all(ran[k] >= 8 for k in cm.NEW_KINDS), dict(ran)
+    assert n["frames >= 2"] >= 12
+    assert n["changed"] >= 8 and n["added > 0"] >= 6 and n["removed > 0"] >= 6
+    assert n["kept by hysteresis"] >= 4
+    assert n["on a pass's hull"] >= 4
+    assert n["behind a pipelined carve"] >= 3 and n["behind a footprint carve"] >= 3 and n["colour camera None"] >= 3
+    assert n["window changed, ring non-empty"] >= 2
+    assert n["changed nothing, two other products valid"] >= 4
+    assert all(slots[s] >= 4 for s in range(3)), dict(slots)
+    assert all(sources[s] >= 3 for s in cm.MEASURE_SOURCES), dict(sources)
+    assert n["profile"] >= 6
+    assert n["measure of painted records"] >= 4
+    assert n["measure carried across a colour pass"] >= 4
+    assert n["measure dropped by a hull change"] >= 4
+    assert all(modes[m] >= 5 for m in ("curve", "point")), dict(modes)
+    assert n["extrema anchors"] >= 4 and n["list anchors"] >= 4 and n["cut short"] >= 3
+    assert n["thin on another S"] >= 6 and n["thin on a larger S"] >= 3
+
+
+def test_chains_and_replay_are_deterministic(traces, traces_b):
+    for seed in cm.SEEDS_B[:3]:
+        sc, ops = cm.draw_chain(seed)
+        sc2, ops2 = cm._draw_chain_b(seed)                       # (drawn again, past the cache)
+        assert sc2 is sc and [cm.describe_op(o) for o in ops2] == [cm.describe_op(o) for o in ops]
+        assert all(np.array_equal(a.get(k), b.get(k)) for a, b in zip(ops, ops2) for k in ("palette", "labels", "anchors"))
+        a, b = cm.replay(seed), cm.replay(seed)
+        assert np.array_equal(a.records, b.records) and a.products == b.products and a.carve == b.carve
+        assert all(np.array_equal(x, y) for x, y in zip(a.vote.ring, b.vote.ring)) and np.array_equal(a.vote.prev, b.vote.prev)
+        for upto in (1, 6, 11, cm.CHAIN_LEN_B):
+            m = cm.replay(seed, upto=upto)
+            row = traces_b[seed][upto - 1]
+            assert cm.hashlib.sha1(m.records.tobytes()).hexdigest() == row["digest"], (seed, upto)
+            assert cm.products_digest(m) == row["products_digest"] and m.products == row["valid"], (seed, upto)
     for seed in cm.SEEDS[:3]:
         sc, ops = cm.draw_chain(seed)
         sc2, ops2 = cm._draw_chain(seed)                         # (drawn again, past the cache)
@@ -119,17 +241,46 @@ def test_chains_and_replay_are_deterministic(traces):
             assert cm.hashlib.sha1(m.records.tobytes()).hexdigest() == traces[seed][upto - 1]["digest"], (seed, upto)
 
 
-def _smallest_state(traces, kind, at_least=200):
-    """(seed, step) of the run of `kind` on the fewest records (but at_least) among all chains."""
-    found = [(r["before"], seed, r["step"]) for seed, rows in traces.items() for r in rows if r["op"] == kind and r["before"] >= at_least]
+def _smallest_state(traces, kind, at_least=200, where=lambda r: True):
+    """(seed, step) of the run of `kind` on the fewest records (but at_least) among all chains, of the runs that `where` admits."""
+    found = [(r["before"], seed, r["step"]) for seed, rows in traces.items() for r in rows
+             if r["op"] == kind and r["before"] >= at_least and where(r)]
     assert found, kind
     return min(found)[1:]
 
 
-@pytest.mark.parametrize("kind", ["filter_components", "color_visible", "photo_carve", "clusters", "geodesic", "hull_normals"])
-def test_literal_twins_give_the_models_bytes(traces, kind):
-    """The pass applied to a state a chain reaches, by the vectorised form and by its literal twin: equal records and products."""
-    seed, step = _smallest_state(traces, kind)
+def _vote_twin(seed, step):
+    """temporal_np.Literal, fed the ring and the previous output that the chain has built up, against the model's temporal_np.Vote:
+    output, counts, stats, and with them the vote bytes and the records' indices."""
+    op = cm.draw_chain(seed)[1][step]
+    m = cm.replay(seed, upto=step)
+    lit = tpn.Literal(op["window"])
+    lit.hulls = [[bool(v) for v in h.reshape(-1)] for h in m.vote.ring]
+    lit.prev = None if m.vote.prev is None else [bool(v) for v in m.vote.prev.reshape(-1)]
+    out_l, counts_l, st_l = lit.push(m.occ(), op["keep"], op["keep_off"])
+    out = m.apply(op)
+    assert np.array_equal(out_l, m.vote.prev), (seed, step, cm.describe_op(op))
+    assert np.array_equal(np.flatnonzero(out_l.reshape(-1)), m.idx)
+    assert np.array_equal(counts_l.reshape(-1)[m.idx], out["votes"])
+    assert all(out["stats"][k] == v for k, v in st_l.items()), (out["stats"], st_l)
+    assert m.products["temporal"] == out["votes"].tobytes() + out["added"].tobytes()
+
+
+# the kinds that only family B knows, and which of their runs the twin is to take the smallest of
+_TWINS_B = {"temporal": lambda r: r["ring_before"] >= 1 and r["window_before"] == r["params"]["window"],
+            "measure": lambda r: True, "thin": lambda r: r["stats"]["stable"] == 1}
+
+
+@pytest.mark.parametrize("kind", ["filter_components", "color_visible", "photo_carve", "clusters", "geodesic", "hull_normals", "temporal",
+                                  "measure", "thin"])
+def test_literal_twins_give_the_models_bytes(traces, traces_b, kind):
+    """The pass applied to a state a chain reaches, by the vectorised form and by its literal twin: equal records and products.
+    The vote, the measurements and the skeleton (temporal_np.Literal, measure_np.measure_literal, thin_np.thin_literal) at the
+    smallest state of at least 200 records that family B reaches -- for the vote the smallest where the ring holds a hull and keeps
+    its window, for the skeleton the smallest whose thinning runs until it is stable, all passes of it."""
+    if kind == "temporal":
+        return _vote_twin(*_smallest_state(traces_b, kind, where=_TWINS_B[kind]))
+    seed, step = _smallest_state(traces_b, kind, where=_TWINS_B[kind]) if kind in _TWINS_B else _smallest_state(traces, kind)
     op = cm.draw_chain(seed)[1][step]
     if kind == "photo_carve":
         op = dict(op, max_rounds=1)                              # (the twin projects point by point: one round, then the colouring)
@@ -139,6 +290,8 @@ def test_literal_twins_give_the_models_bytes(traces, kind):
     assert np.array_equal(a.records, b.records), (seed, step, cm.describe_op(op))
     assert a.products == b.products
     assert out_a["survivors"] == out_b["survivors"] and out_a.get("stats") == out_b.get("stats")
+    if kind in _TWINS_B:
+        assert {"measure": "measure", "thin": "skeleton"}[kind] in a.products
 
 
 def test_literal_twins_of_the_morphology_on_a_window(traces):
@@ -174,18 +327,27 @@ def test_literal_twin_of_the_surface_refinement(traces):
     assert np.array_equal(verts.view(np.uint64), want["verts"][pick].view(np.uint64)) and np.array_equal(refined, want["refined"][pick])
 
 
-@pytest.mark.parametrize("fault", ["grow_slot0", "drop_paint"])
-def test_a_wrong_model_is_told_apart(traces, fault):
-    """The chains are not hollow: a model that colours added voxels from slot 0 instead of the carve's slot, or that loses the
-    painted colours at a compaction, gives other records than the right one in at least one chain -- the comparison of
-    tests/test_gpu_chain.py, fed on the CPU."""
+@pytest.mark.parametrize("fault, fam", [pytest.param("grow_slot0", "A", id="grow_slot0"), pytest.param("drop_paint", "A", id="drop_paint"),
+                                        pytest.param("grow_slot0", "B", id="grow_slot0-B"),
+                                        pytest.param("temporal_forgets_prev", "B", id="temporal_forgets_prev"),
+                                        pytest.param("measure_carve_colours", "B", id="measure_carve_colours")])
+def test_a_wrong_model_is_told_apart(traces, traces_b, fault, fam):
+    """The chains are not hollow: a model that colours added voxels from slot 0 instead of the carve's slot, that loses the
+    painted colours at a compaction, that forgets the vote's previous output at a carve, or that sums the carve's colours into a
+    measurement, gives other records (family B: or other products) than the right one in at least one chain -- the comparison
+    that the walk on the device makes (tests/test_gpu_chain.py), fed on the CPU.  In family B "grow_slot0" reaches the voxels that
+    a vote restores as well."""
     told = []
-    for seed in cm.SEEDS:
+    want = traces if fam == "A" else traces_b
+    for seed in want:
         for step, op, out, model in cm.run(seed, fault):
-            if cm.hashlib.sha1(model.records.tobytes()).hexdigest() != traces[seed][step]["digest"]:
+            row = want[seed][step]
+            # family A: by the records alone, as before family B existed; family B: by the records or by the products' bytes
+            if cm.hashlib.sha1(model.records.tobytes()).hexdigest() != row["digest"] or \
+                    (fam == "B" and cm.products_digest(model) != row["products_digest"]):
                 told.append((seed, step, op["op"]))
                 break
         if len(told) >= 3:
             break
-    print("%s told apart at (seed, step, op):" % fault, told)
-    assert told, "no chain tells the %s model from the right one" % fault
+    print("%s told apart in family %s at (seed, step, op):" % (fault, fam), told)
+    assert told, "no chain of family %s tells the %s model from the right one" % (fam, fault)
