@@ -1029,6 +1029,12 @@ int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *
  *                                  the per-voxel level takes one after the other
  *                   emit_lanes (1), emit_busy (1: grids >= 64 M voxels, 2: always, 0: never)  record expansion form
  *                   force_generic (0)  one thread per voxel everywhere (also env VOXCARVE_FORCE_GENERIC=1)
+ *                   emit_lut16 (1)  VC_MODE_LUT on a tile-ordered table (ny in {64, 128, 256, 512, 1024}): the expansion reads the
+ *                                  colour camera's entries as 16-bit differences to the smallest offset of their tile word, from a
+ *                                  compact copy (2 B per voxel of the slab + 4 B per 64) packed by the first step that names the
+ *                                  camera; a camera whose tile words span more than 65534 pixels of offset, or a device without
+ *                                  the memory, keeps the 4-byte entries.  0: 4-byte entries always.  Same records either way;
+ *                                  read by the next vc_carve_begin (vc_debug_counters out[6] tells which a step took)
  *   frame sets      grid_lds_kb (0 = 16; frame sets above 2 MB of mask bits: what their uncropped grids need at the finest block
  *                                  that fits 148 KB, brick pipeline, or 64 KB, other kernels; explicit values above 64 are
  *                                  clamped to 64 for those), grid_min_shift (1)  LDS budget / finest block of the cropped
@@ -1075,7 +1081,8 @@ int vc_timing(vc_ctx *ctx, vc_timing_t *out);
 uint32_t vc_timing_struct_size(void);
 /* Diagnostics of the last brick-pipeline carve (scripts/, DESIGN figures): out[0] bricks listed for a look at their words,
  * out[1] bricks that may hold survivors, out[2] bricks whose voxels all survive, out[3] bricks of the slab, out[4] brick
- * columns listed, out[5] tile words that took the per-voxel test; the rest 0. */
+ * columns listed, out[5] tile words that took the per-voxel test; out[6] 1 when the record expansion launched last read the colour
+ * camera's compact table (option emit_lut16), out[7] 1 while such a table exists. */
 int vc_debug_counters(vc_ctx *ctx, uint64_t out[8]);
 int vc_timing_reset(vc_ctx *ctx);
 

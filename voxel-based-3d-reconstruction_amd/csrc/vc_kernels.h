@@ -158,6 +158,8 @@ struct EmitParams {
                                 // B << 16 | seen << 24 (or null)
     const int32_t *lut;         // colour camera's packed table (FROM_LUT), else null
     uint32_t lut_tq;            // != 0: that table is in TILE order (tile words per row quad = ny / 16); 0: y-major
+    const uint16_t *lut16;      // L16 expansion: the tile-ordered table as 16-bit differences to cbase (k_pack_lut16), 0xFFFF = outside
+    const int32_t *cbase;       // ... and the smallest offset of each tile word; tile word 64 g + l belongs to group g (64 % lut_tq == 0)
     const uint64_t *words;
     const uint32_t *busylist;   // k_emit_busy: the groups with survivors; busycount[0] of them
     const uint32_t *busycount;
@@ -1161,6 +1163,25 @@ __global__ __launch_bounds__(kBlock) void k_adopt_lut(const CarveParams p, const
                 (u0 == 0xffffu) ? kEmptyBox
                                 : ((uint64_t)u0 | ((uint64_t)v0 << 16) | ((uint64_t)u1 << 32) | ((uint64_t)v1 << 48) |
                                    (inside ? kBoxAllInside : 0ull));
+    }
+}
+
+// The colour camera's tile-ordered table in compact form, for the record expansion: thread t is element t % 64 of tile word
+// T = t / 64 (a wave per tile word, as k_adopt_lut<true> is laid out).  cbase[T] = the word's smallest entry >= 0 (0: it has
+// none), lut16[t] = entry - cbase[T], 0xFFFF for "outside the image" (-1).  The 64 voxels of a tile word project to neighbouring
+// pixels, a few image rows apart; a word whose entries lie more than 65534 apart does not fit: its wave says so in *nofit (its
+// 16-bit values are then meaningless and the whole table goes unused).
+__global__ __launch_bounds__(kBlock) void k_pack_lut16(const int32_t *__restrict__ lut_tile, uint16_t *__restrict__ lut16,
+                                                       int32_t *__restrict__ cbase, uint32_t *nofit)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;      // grid covers n_pad exactly
+    const int32_t off = lut_tile[t];
+    const uint32_t lo = wave_min_u32(off >= 0 ? (uint32_t)off : 0xffffffffu), hi = wave_max_u32(off >= 0 ? (uint32_t)off : 0u);
+    const uint32_t base = lo == 0xffffffffu ? 0u : lo;
+    lut16[t] = off >= 0 ? (uint16_t)((uint32_t)off - base) : (uint16_t)0xffffu;
+    if ((t & 63u) == 0) {
+        cbase[t >> 6] = (int32_t)base;
+        if (hi > base && hi - base > 65534u) atomicAdd(nofit, 1u);
     }
 }
 
@@ -2582,12 +2603,14 @@ struct EmitBatch {
     uint32_t wl[EB];            // first record of the word inside the group (<= 4096) | word number inside the group << 16
     uint32_t jb[EB];            // INDIRECT only: voxel index of the word's bit 0 (else it follows from the word number)
     uint64_t wv[EB];
-    int32_t off[EB];
+    int32_t off[EB];            // L16: the 16-bit entry as read (0xFFFF where the lane has no survivor), decoded by emit_finish
+    uint32_t tw[EB];            // L16: the word's first tile word inside the group (its lanes read 4 in a row: tw + lane / 16)
     bool any;
 };
 
 // takes the next (up to) EB non-zero words of the group off `nz` and starts their table loads (or projects)
-template <bool FROM_LUT, int EB, bool INDIRECT>
+// L16: the colour table is the compact one (EmitParams::lut16, tile order only)
+template <bool FROM_LUT, int EB, bool INDIRECT, bool L16 = false>
 __device__ __forceinline__ void emit_prepare(const EmitParams &p, uint64_t &nz, uint64_t mine, uint32_t mybase, uint32_t &wstart,
                                              uint32_t tbase, uint64_t gw, uint32_t lane, EmitBatch<EB> &B,
                                              bool rowwords = false, uint32_t wix = 0, uint32_t wiy = 0, uint32_t wiz = 0)
@@ -2610,15 +2633,19 @@ __device__ __forceinline__ void emit_prepare(const EmitParams &p, uint64_t &nz, 
             wstart += (uint32_t)__popcll(B.wv[b]);
             tb[b] = (uint32_t)__builtin_amdgcn_readlane((int)tbase, (int)li);
         }
+        B.tw[b] = (tb[b] >> 6) & 63u;
     }
 #pragma unroll
     for (int b = 0; b < EB; ++b) {
-        B.off[b] = -1;
+        B.off[b] = L16 ? 0xffff : -1;
         // (the word's bits, wave-uniform, ARE the lane mask of "my voxel survives": handed to the compiler as such, the branch is
         // one s_and_saveexec instead of shift, and, compare per lane)
         if (p.has_cam && __builtin_amdgcn_inverse_ballot_w64(B.wv[b])) {
             const uint32_t j = (INDIRECT ? B.jb[b] : (uint32_t)((gw + (B.wl[b] >> 16)) << 6)) + lane;
-            if (FROM_LUT) {
+            if (FROM_LUT && L16) {
+                // (the same element of the same tile word, at half the byte offset)
+                B.off[b] = (int32_t)p.lut16[tb[b] + ((lane >> 4) << 6) + (lane & 15u)];
+            } else if (FROM_LUT) {
                 // (tile order: the word starts at a multiple of 64 and ny % 64 == 0, so its 64 voxels are 4 runs of 16 entries;
                 // everything but the lane terms is wave-uniform)
                 B.off[b] = p.lut[(!INDIRECT && p.lut_tq) ? tb[b] + ((lane >> 4) << 6) + (lane & 15u) : j];
@@ -2640,25 +2667,39 @@ __device__ __forceinline__ void emit_prepare(const EmitParams &p, uint64_t &nz, 
 
 // colour gathers and record stores of a prepared batch
 // ROOM: the group's records (at most 4 096) all fit the buffer -- no test per record
-template <bool ALLSEEN, int EB, bool INDIRECT, bool ROOM = false>
-__device__ __forceinline__ void emit_finish(const EmitParams &p, uint64_t out0, uint64_t gw, uint32_t lane, const EmitBatch<EB> &B)
+// L16: B.off holds 16-bit entries; cb = the lanes' tile-word bases of the group (EmitGroup::cb)
+template <bool ALLSEEN, int EB, bool INDIRECT, bool ROOM = false, bool L16 = false>
+__device__ __forceinline__ void emit_finish(const EmitParams &p, uint64_t out0, uint64_t gw, uint32_t lane, const EmitBatch<EB> &B, int32_t cb = 0)
 {
     const uint64_t below = (1ull << lane) - 1ull;
     uint64_t *__restrict__ grp = p.records + out0;                // (wave-uniform: the stores take a 32-bit offset from it)
+    int32_t off[EB];
+    if (L16) {
+        // lane l's voxel lies in tile word tw + l / 16 of the group, whose base lane tw + l / 16 holds: one cross-lane read per
+        // word, all of the batch issued together, outside any branch (and with every lane active)
+        int32_t base[EB];
+#pragma unroll
+        for (int b = 0; b < EB; ++b) base[b] = __builtin_amdgcn_ds_bpermute((int)((B.tw[b] + (lane >> 4)) << 2), cb);
+#pragma unroll
+        for (int b = 0; b < EB; ++b) off[b] = B.off[b] == 0xffff ? -1 : base[b] + B.off[b];
+    } else {
+#pragma unroll
+        for (int b = 0; b < EB; ++b) off[b] = B.off[b];
+    }
     // all gathers of the batch are issued before any of them is used (a load consumed inside its own branch is waited for
     // inside it: eight round trips in a row)
     uint32_t mw[EB], px[EB];
 #pragma unroll
     for (int b = 0; b < EB; ++b) {
         mw[b] = ~0u;
-        if (!ALLSEEN && p.maskbits && B.off[b] >= 0) mw[b] = p.maskbits[(uint32_t)B.off[b] >> 5];
+        if (!ALLSEEN && p.maskbits && off[b] >= 0) mw[b] = p.maskbits[(uint32_t)off[b] >> 5];
     }
     bool seen[EB];
 #pragma unroll
     for (int b = 0; b < EB; ++b) {
-        seen[b] = B.off[b] >= 0 && (ALLSEEN || (p.maskbits && ((mw[b] >> ((uint32_t)B.off[b] & 31u)) & 1u)));
+        seen[b] = off[b] >= 0 && (ALLSEEN || (p.maskbits && ((mw[b] >> ((uint32_t)off[b] & 31u)) & 1u)));
         px[b] = kSeenFlag;
-        if (seen[b] && p.frame) px[b] = p.frame[B.off[b]];                          // R | G<<8 | B<<16 | seen<<24: a record's upper half
+        if (seen[b] && p.frame) px[b] = p.frame[off[b]];                          // R | G<<8 | B<<16 | seen<<24: a record's upper half
     }
     uint64_t rec[EB];
 #pragma unroll
@@ -2681,8 +2722,9 @@ __device__ __forceinline__ void emit_finish(const EmitParams &p, uint64_t out0, 
 struct EmitGroup {
     uint64_t mine, out0;
     uint32_t mybase;
+    int32_t cb;                 // L16: base of tile word `lane` of the group
 };
-template <bool INDIRECT>
+template <bool INDIRECT, bool L16 = false>
 __device__ __forceinline__ EmitGroup emit_load_group(const EmitParams &p, uint32_t g, uint32_t lane)
 {
     EmitGroup h;
@@ -2691,18 +2733,22 @@ __device__ __forceinline__ EmitGroup emit_load_group(const EmitParams &p, uint32
     const uint64_t gw = (uint64_t)g * (INDIRECT ? p.entry_chunk : kGroupWords);
     h.mine = 0ull;
     h.mybase = 0;
+    h.cb = 0;
     if (gw + lane < nwords && (!INDIRECT || lane < p.entry_chunk)) {
         if (INDIRECT) {
             const ulonglong2 e = reinterpret_cast<const ulonglong2 *>(p.entries)[gw + lane];
             h.mine = e.x; h.mybase = (uint32_t)e.y;
         } else h.mine = p.words[gw + lane];
+        // (the group's 64 tile words are 64 g .. 64 g + 63, as many as it has y-major words: one coalesced 256-byte load, with
+        // the words and so a group ahead of its use)
+        if (L16 && !INDIRECT) h.cb = p.cbase[gw + lane];
     }
     return h;
 }
 
 // The dependent chain of a batch is table entry -> pixel -> store; the next batch's table loads are issued before the
 // current batch's pixels are waited for, so a group of B batches costs about B + 1 round trips instead of 2 B.
-template <bool FROM_LUT, bool ALLSEEN, int EB, bool INDIRECT, bool ROOM = false>
+template <bool FROM_LUT, bool ALLSEEN, int EB, bool INDIRECT, bool ROOM = false, bool L16 = false>
 __device__ __forceinline__ void emit_group_lanes(const EmitParams &p, const uint32_t g, const uint32_t lane, const EmitGroup &h)
 {
     const uint64_t gw = (uint64_t)g * kGroupWords;
@@ -2726,30 +2772,31 @@ __device__ __forceinline__ void emit_group_lanes(const EmitParams &p, const uint
         return;
     }
     EmitBatch<EB> B;
-    emit_prepare<FROM_LUT, EB, INDIRECT>(p, nz, h.mine, h.mybase, wstart, tbase, gw, lane, A);
+    emit_prepare<FROM_LUT, EB, INDIRECT, L16>(p, nz, h.mine, h.mybase, wstart, tbase, gw, lane, A);
     while (A.any) {                                                     // wave-uniform; A and B take turns (no copies)
-        emit_prepare<FROM_LUT, EB, INDIRECT>(p, nz, h.mine, h.mybase, wstart, tbase, gw, lane, B);
-        emit_finish<ALLSEEN, EB, INDIRECT, ROOM>(p, h.out0, gw, lane, A);
+        emit_prepare<FROM_LUT, EB, INDIRECT, L16>(p, nz, h.mine, h.mybase, wstart, tbase, gw, lane, B);
+        emit_finish<ALLSEEN, EB, INDIRECT, ROOM, L16>(p, h.out0, gw, lane, A, h.cb);
         if (!B.any) break;
-        emit_prepare<FROM_LUT, EB, INDIRECT>(p, nz, h.mine, h.mybase, wstart, tbase, gw, lane, A);
-        emit_finish<ALLSEEN, EB, INDIRECT, ROOM>(p, h.out0, gw, lane, B);
+        emit_prepare<FROM_LUT, EB, INDIRECT, L16>(p, nz, h.mine, h.mybase, wstart, tbase, gw, lane, A);
+        emit_finish<ALLSEEN, EB, INDIRECT, ROOM, L16>(p, h.out0, gw, lane, B, h.cb);
     }
 }
 
-template <bool FROM_LUT, bool ALLSEEN, int EB, bool INDIRECT = false>
+// L16 (FROM_LUT, not INDIRECT): the colour camera's table is read in its compact form, 2 B per entry (k_pack_lut16)
+template <bool FROM_LUT, bool ALLSEEN, int EB, bool INDIRECT = false, bool L16 = false>
 __global__ __launch_bounds__(kBlock) void k_emit_lanes(const EmitParams p)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t g = __builtin_amdgcn_readfirstlane((blockIdx.x * kBlock + threadIdx.x) >> 6);
     if (g >= p.ngroups) return;
     if (p.groupcnt[g] == 0) return;
-    emit_group_lanes<FROM_LUT, ALLSEEN, EB, INDIRECT>(p, g, lane, emit_load_group<INDIRECT>(p, g, lane));
+    emit_group_lanes<FROM_LUT, ALLSEEN, EB, INDIRECT, false, L16>(p, g, lane, emit_load_group<INDIRECT, L16>(p, g, lane));
 }
 
 // The same expansion driven by the list of busy groups (k_finish_scan): a fixed grid of waves strides over
 // it, so no wave is launched only to find its group empty (5 of 6 are).  A wave loads its next group's words and
 // offsets before it works on the current one (and that group's number one step earlier still).
-template <bool FROM_LUT, bool ALLSEEN, int EB>
+template <bool FROM_LUT, bool ALLSEEN, int EB, bool L16 = false>
 __global__ __launch_bounds__(kBlock) void k_emit_busy(const EmitParams p)
 {
     if (p.dbg & 16u) return;
@@ -2760,15 +2807,15 @@ __global__ __launch_bounds__(kBlock) void k_emit_busy(const EmitParams p)
     if (w >= nbusy) return;
     uint32_t g = p.busylist[w];
     uint32_t g1 = w + nwaves < nbusy ? p.busylist[w + nwaves] : 0u;
-    EmitGroup h = emit_load_group<false>(p, g, lane);
+    EmitGroup h = emit_load_group<false, L16>(p, g, lane);
     for (uint32_t t = w; t < nbusy; t += nwaves) {
         const bool more = t + nwaves < nbusy;                          // (wave-uniform)
         const uint32_t g2 = t + 2 * nwaves < nbusy ? p.busylist[t + 2 * nwaves] : 0u;
         EmitGroup hn = h;
-        if (more) hn = emit_load_group<false>(p, g1, lane);
+        if (more) hn = emit_load_group<false, L16>(p, g1, lane);
         // (a group holds at most 4 096 records: where that many fit behind its first one, nothing is tested per record)
-        if (FROM_LUT && h.out0 + 4096u <= p.capacity) emit_group_lanes<FROM_LUT, ALLSEEN, EB, false, true>(p, g, lane, h);
-        else emit_group_lanes<FROM_LUT, ALLSEEN, EB, false>(p, g, lane, h);
+        if (FROM_LUT && h.out0 + 4096u <= p.capacity) emit_group_lanes<FROM_LUT, ALLSEEN, EB, false, true, L16>(p, g, lane, h);
+        else emit_group_lanes<FROM_LUT, ALLSEEN, EB, false, false, L16>(p, g, lane, h);
         h = hn; g = g1; g1 = g2;
     }
 }

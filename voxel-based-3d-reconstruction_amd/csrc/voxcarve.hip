@@ -193,6 +193,7 @@ struct StepBuf {
     bool sparse_words = false;               // words of groups with groupcnt == 0 were left unwritten
     DevBuf<uint32_t> busyoff, busysum, busyblock, busylist;   // the groups with survivors, listed by the scan
     bool busy = false;
+    bool lut16 = false;                      // the expansion reads the colour camera's compact table (ensure_lut16)
     // compact exchange form of this step: non-zero words as {bits, global index of bit 0} pairs
     DevBuf<uint64_t> ent, mine, counts;      // pairs | {entries, survivors} of this rank | of all ranks
     Pinned<uint64_t> h_counts;               // 2 per rank
@@ -313,6 +314,16 @@ struct vc_ctx {
     int emit_lanes = 1;              // record expansion: lanes = voxels of a word (1) or lanes = survivors (0)
     int emit_busy = 1;               // ... driven by the list of busy groups (grids of >= kBusyListMinGroups groups)
     int emit_waves_per_cu = 256;     // waves of that launch per CU (a wave strides over the list when there are more busy groups)
+    // The colour camera's tile-ordered table in compact form (k_pack_lut16: 2 B per entry + 4 B per tile word), what the
+    // expansion of VC_MODE_LUT reads instead of d_lut_tile where it fits: one camera at a time, packed by the first step that
+    // names the camera (ensure_lut16), void with d_lut_tile (drop_lut16)
+    int emit_lut16 = 1;
+    DevBuf<uint16_t> d_lut16;
+    DevBuf<int32_t> d_cbase;
+    DevBuf<uint32_t> d_lut16_flag;
+    int lut16_cam = -1;              // the camera d_lut16 holds (-1: none)
+    uint32_t lut16_nofit = 0;        // cameras whose table does not fit 16 bits (or found no memory): 4-byte entries, not tried again
+    bool last_emit16 = false;        // the expansion launched last read the compact table (vc_debug_counters)
     int fused_hier = 1;              // VC_MODE_FUSED: interval-arithmetic word rejection (needs ny % 64 == 0)
     int lut_hier = 1;                // VC_MODE_LUT: hierarchical kernel (boxes + block grid) instead of stream + refine
     int timing_detail = 0;           // also time preparation and carve kernels of pipelined steps (three more events on the carve stream)
@@ -549,9 +560,18 @@ int fail(vc_ctx *ctx, int code, const char *fmt, ...);
 // The result is another from here on: every product of a post-carve pass is stale (their stamps no longer equal the generation).
 void result_changed(vc_ctx *ctx) { ++ctx->result_gen; }
 
+// The compact colour table is a copy of one camera of d_lut_tile: void, and its memory given back, whenever that table is
+// built again or replaced (no step is in flight then, so nothing reads it).
+void drop_lut16(vc_ctx *ctx)
+{
+    ctx->lut16_cam = -1; ctx->lut16_nofit = 0;
+    ctx->d_lut16.reset(); ctx->d_cbase.reset();
+}
+
 // Grid, slab or cameras are others from here on: tables and boxes are to be built again, and there is no carve result.
 void geometry_changed(vc_ctx *ctx)
 {
+    drop_lut16(ctx);
     ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false;
     ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
     ctx->temporal.pushes = 0;                    // the hulls of another grid or other cameras are no history of this one
@@ -1090,13 +1110,15 @@ int launch_emit(vc_ctx *ctx, StepBuf &sb, hipStream_t st, hipEvent_t start = nul
 #define VC_EMIT(kernel, grid) hipExtLaunchKernelGGL((kernel), grid, block, 0, st, start, stop, 0, e)
     if (sb.busy && ctx->emit_lanes) {
         const dim3 bg(256u * (uint32_t)ctx->emit_waves_per_cu / 4u);
-        if (e.lut && sb.allseen) VC_EMIT((k_emit_busy<true, true, 8>), bg);
+        if (e.lut16) VC_EMIT((k_emit_busy<true, true, 8, true>), bg);             // (ensure_lut16: steps that need every camera only)
+        else if (e.lut && sb.allseen) VC_EMIT((k_emit_busy<true, true, 8>), bg);
         else if (e.lut) VC_EMIT((k_emit_busy<true, false, 8>), bg);
         else if (sb.allseen) VC_EMIT((k_emit_busy<false, true, 4>), bg);
         else VC_EMIT((k_emit_busy<false, false, 4>), bg);
     }
     else if (ctx->emit_lanes) {
-        if (e.lut && sb.allseen) VC_EMIT((k_emit_lanes<true, true, 8>), eg);
+        if (e.lut16) VC_EMIT((k_emit_lanes<true, true, 8, false, true>), eg);
+        else if (e.lut && sb.allseen) VC_EMIT((k_emit_lanes<true, true, 8>), eg);
         else if (e.lut) VC_EMIT((k_emit_lanes<true, false, 8>), eg);
         else if (sb.allseen) VC_EMIT((k_emit_lanes<false, true, 4>), eg);
         else VC_EMIT((k_emit_lanes<false, false, 4>), eg);
@@ -1107,6 +1129,7 @@ int launch_emit(vc_ctx *ctx, StepBuf &sb, hipStream_t st, hipEvent_t start = nul
     else VC_EMIT((k_emit_words<false, false, kEmitBatch>), eg);
 #undef VC_EMIT
     VC_HIP(ctx, hipGetLastError());
+    ctx->last_emit16 = e.lut16 != nullptr && ctx->emit_lanes;
     return VC_OK;
 }
 
@@ -1365,6 +1388,45 @@ int ensure_color_table(vc_ctx *ctx, int cam)
                        (uint64_t *)nullptr);
     VC_HIP(ctx, hipGetLastError());
     ctx->lut_color_cam = cam;
+    return VC_OK;
+}
+
+// The colour camera's compact table for the expansion of VC_MODE_LUT (see vc_ctx::d_lut16), packed from d_lut_tile on the
+// carve stream by the first step that names the camera -- in front of the step's carve kernels, like the table above, so
+// that {scan done} orders the expansion stream behind it.  use = the step may read it: the camera's table fits 16 bits per
+// entry.  The verdict is read back once, here (first use: the streams drain); a camera that does not fit, or a device without
+// the memory, keeps the 4-byte entries and is not tried again until the table changes.
+int ensure_lut16(vc_ctx *ctx, int cam, uint64_t n_pad, bool &use)
+{
+    use = false;
+    if ((ctx->lut16_nofit >> cam) & 1u) return VC_OK;
+    if (ctx->lut16_cam == cam) { use = true; return VC_OK; }
+    // (an expansion in flight may still read the table of the camera before)
+    if (ctx->lut16_cam >= 0 && ctx->npending) VC_HIP(ctx, hipStreamSynchronize(ctx->stream2));
+    ctx->lut16_cam = -1;
+    VC_TRY(ensure(ctx, ctx->d_lut16_flag, 1));
+    auto room = [](auto &b, size_t elems) {
+        if (b.ptr && b.cap >= elems) return true;
+        b.reset();
+        if (hipMalloc(reinterpret_cast<void **>(&b.ptr), elems * sizeof(*b.ptr)) != hipSuccess) { (void)hipGetLastError(); b.ptr = nullptr; return false; }
+        b.cap = elems;
+        return true;
+    };
+    if (!room(ctx->d_lut16, (size_t)n_pad) || !room(ctx->d_cbase, (size_t)(n_pad / 64))) {
+        ctx->d_lut16.reset(); ctx->d_cbase.reset();
+        ctx->lut16_nofit |= 1u << cam;
+        return VC_OK;
+    }
+    VC_HIP(ctx, hipMemsetAsync(ctx->d_lut16_flag.ptr, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(k_pack_lut16, dim3(grid_for(n_pad)), dim3(kBlock), 0, ctx->stream, (const int32_t *)(ctx->d_lut_tile.ptr + (size_t)cam * n_pad),
+                       ctx->d_lut16.ptr, ctx->d_cbase.ptr, ctx->d_lut16_flag.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    uint32_t nofit = 0;
+    VC_HIP(ctx, hipMemcpyAsync(&nofit, ctx->d_lut16_flag.ptr, sizeof nofit, hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (nofit) { ctx->lut16_nofit |= 1u << cam; return VC_OK; }
+    ctx->lut16_cam = cam;
+    use = true;
     return VC_OK;
 }
 
@@ -1742,6 +1804,7 @@ int vc_build_lut(vc_ctx *ctx)
     VC_HIP(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     ctx->tile_valid = false;
     ctx->lut_foreign = false; ctx->ymajor_valid = false; ctx->upload_mask = 0;
+    drop_lut16(ctx);
     if (ctx->lut_tile && ctx->nx % 4 == 0 && ctx->ny % 64 == 0) {
         // ONE table, in tile order (words of 4 x-rows x 16 y), projected straight into that order; the colour look-up of
         // the record expansion reads it too (closed-form index).  No y-major copy unless something asks for one.
@@ -1779,6 +1842,7 @@ int vc_upload_lut(vc_ctx *ctx, uint32_t cam, const int32_t *lut)
     VC_HIP(ctx, hipSetDevice(ctx->device));
     const uint64_t n = ctx->n_voxels();
     const uint64_t n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
+    drop_lut16(ctx);
     if (ctx->upload_mask == 0) {                                 // first camera of a new table: whatever was there is void
         ctx->lut_valid = false; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false; ctx->tbox_valid = false; ctx->kbox_valid = false;
         VC_TRY(ensure(ctx, ctx->d_lut, (size_t)n_pad * ctx->C));
@@ -1971,6 +2035,13 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     // on the k_finish_scan launch, is behind it (queued where the expansion's parameters are set up it would follow that
     // launch, and the first expansion would read a table still being written)
     if (mode == VC_MODE_FUSED && ctx->fused_color_table && color_cam >= 0 && !sb.no_records) VC_TRY(ensure_color_table(ctx, color_cam));
+    // VC_MODE_LUT, where the tile-ordered table is what the expansion reads and a group's tile words are 64 in a row: the
+    // colour camera's compact table, packed here for the same reason.  (A step with a threshold below C takes the
+    // one-thread-per-voxel carve and, from then on, the y-major table it builds: sb.allseen holds wherever this applies.)
+    sb.lut16 = false;
+    if (mode == VC_MODE_LUT && ctx->emit_lut16 && ctx->emit_lanes && color_cam >= 0 && !sb.no_records && n && ctx->tile_valid &&
+        !ctx->ymajor_valid && p.tile_whole && sb.allseen)
+        VC_TRY(ensure_lut16(ctx, color_cam, p.n_pad, sb.lut16));
     if (sb.carve_timed) VC_HIP(ctx, hipEventRecord(sb.e0, ctx->stream));
     const dim3 block(kBlock);
     if (foot) {
@@ -2154,6 +2225,7 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
         if (mode == VC_MODE_LUT && ctx->tile_valid && !ctx->ymajor_valid) {
             e.lut = ctx->d_lut_tile.ptr + (size_t)color_cam * p.n_pad;      // the only table there is: tile order
             e.lut_tq = p.tq;
+            if (sb.lut16) { e.lut16 = ctx->d_lut16.ptr; e.cbase = ctx->d_cbase.ptr; }   // ... and its compact form
         }
         else if (mode == VC_MODE_LUT) e.lut = ctx->d_lut.ptr + (size_t)color_cam * p.n_pad;
         else if (ctx->fused_color_table && !sb.no_records) {
@@ -2227,6 +2299,8 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
             VC_TRY(ensure(ctx, sb.records, (size_t)(total + total / 8 + 1024)));
             sb.emit.records = sb.records.ptr;
             sb.emit.capacity = sb.records.cap;
+            // (a later step may have packed the compact table for another colour camera since: d_lut_tile still holds this one's)
+            if (sb.emit.lut16 && ctx->lut16_cam != sb.color_cam) { sb.emit.lut16 = nullptr; sb.emit.cbase = nullptr; }
             VC_TRY(launch_emit(ctx, sb, ctx->stream));
             sb.emit_ridden = false;
             VC_HIP(ctx, hipEventRecord(sb.e2, ctx->stream));
@@ -5225,6 +5299,7 @@ int vc_set_option(vc_ctx *ctx, const char *name, int value)
     else if (k == "voxel_pairs") ctx->voxel_pairs = value;
     else if (k == "voxel_batches" && value >= 0 && value <= 16) ctx->voxel_batches = value;
     else if (k == "emit_busy" && value >= 0 && value <= 2) ctx->emit_busy = value;          // 0 never, 1 large grids, 2 always
+    else if (k == "emit_lut16") ctx->emit_lut16 = value != 0;                               // read by the next vc_carve_begin
     else if (k == "emit_waves_per_cu" && value >= 4 && value <= 1024) ctx->emit_waves_per_cu = value;
     else if (k == "lut_tile") ctx->lut_tile = value != 0;
     else if (k == "grid_lds_kb" && value >= 0 && value <= 148) ctx->grid_lds_kb = value;
@@ -5269,6 +5344,8 @@ int vc_debug_counters(vc_ctx *ctx, uint64_t out[8])
         for (size_t i = 0; i < nw; ++i) { out[1] += (uint64_t)__builtin_popcountll(bits[i]); out[2] += (uint64_t)__builtin_popcountll(bits[nw + i]); }
         out[3] = (uint64_t)p.nbx * p.tq * p.nbz;
     }
+    out[6] = ctx->last_emit16 ? 1 : 0;
+    out[7] = ctx->lut16_cam >= 0 ? 1 : 0;
     return VC_OK;
 }
 

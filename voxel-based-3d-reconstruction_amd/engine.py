@@ -1221,7 +1221,9 @@ class CarveEngine:
         out = np.zeros(8, dtype=np.uint64)
         self._check(self._L.vc_debug_counters(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_debug_counters")
         return {"bricks_listed": int(out[0]), "bricks_live": int(out[1]), "bricks_full": int(out[2]), "bricks": int(out[3]),
-                "columns_listed": int(out[4]), "words_undecided": int(out[5])}
+                "columns_listed": int(out[4]), "words_undecided": int(out[5]),
+                # the expansion launched last read the colour camera's compact table (option emit_lut16) | such a table exists
+                "emit_lut16": int(out[6]), "lut16_table": int(out[7])}
 
     def synchronize(self):
         self._check(self._L.vc_synchronize(self._ctx), "vc_synchronize")
