@@ -815,6 +815,51 @@ int vc_hull_measure(vc_ctx *ctx, uint32_t source, const uint32_t *labels /* [S],
 int vc_fetch_measure(vc_ctx *ctx, vc_measure_t *out);                      /* [G] */
 int vc_fetch_measure_profile(vc_ctx *ctx, uint64_t *out);                  /* [G][nz][3] */
 
+/* ---- the hull's shell: what a viewer of opaque cubes can see, with faces and levels of detail (no reference counterpart) ----------
+ * vc_hull_shell lists the cells of the current carve result that have an exposed face, in cell order, with their exposed faces,
+ * at the voxels' resolution or on a grid 2^L times coarser with averaged colours; vc_fetch_shell_viewer turns the list into the
+ * float32 arrays the reference's viewer draws (assignment.py:127-133), on the device.  The result is left exactly as it is.  The
+ * contract, bit for bit (tests/shell_np.py restates it).
+ *   Grid: nx, ny, nz cells, linear index i = (iz nx + ix) ny + iy.  ON = a survivor of the current carve result as
+ *   vc_fetch_occupancy sees it (photo carve, components, morphology, grow, temporal vote and footprint rules included).
+ *   1 level: L in 0 .. VC_SHELL_MAX_LEVEL, f = 2^L.  The coarse grid has n'_a = ceil(n_a / f) cells per axis; coarse cell
+ *     (cx, cy, cz) covers the fine indices f c <= i_a < min(f c + f, n_a) per axis, is ON when any of its voxels is ON, and has
+ *     the index j = (cz nx' + cx) ny' + cy.  At L = 0 the coarse grid is the grid.
+ *   2 faces: one byte per ON cell; bits 0 .. 5 stand for -x, +x, -y, +y, -z, +z (the order of vc_measure_t::faces); a bit is set
+ *     when the neighbour across that face is OFF or outside the (coarse) grid.  Nothing wraps around.  The shell is the set of ON
+ *     cells with a non-zero face byte.
+ *   3 shell records: the shell cells in ascending j, 8 bytes each, {u32 j, u8 r, g, b, seen}.  At L = 0 bytes 4 .. 7 are the
+ *     survivor's record bytes unchanged.  At L > 0, with n = the level-0 shell voxels inside the cell whose seen byte has bit 0
+ *     set: n > 0 gives each channel as (sum c + n / 2) / n in unsigned integers (floor) and seen = 1; n = 0 gives 0, 0, 0, 0.
+ *     (Every coarse shell cell holds a level-0 shell voxel, so n = 0 only where the colour camera sees none of them.)
+ *   4 viewer arrays: `scaling` a double, the axes A = xs, ys, zs of vc_get_axes.  Per axis lo = f c, hi = min(f c + f, n_a) - 1,
+ *     v_a = (trunc(A[lo]) / scaling + trunc(A[hi]) / scaling) * 0.5 in float64; position = {(float)v_x, (float)(-v_z),
+ *     (float)v_y}, colour_k = (float)((double)c_k / 255.0).  At L = 0 these are the reference's arrays of the same voxels bit for
+ *     bit ((a + a) * 0.5 = a).  At L > 0 the caller draws cubes f times as large: stats.cube_scale = f.
+ *   5 a read-only pass: records, count and occupancy stay; the result generation does not advance, so the products of the other
+ *     passes stay valid.  vc_fetch_shell and vc_fetch_shell_viewer fail ("no shell") until the pass has run on the current result
+ *     and again after anything that changes which voxels survive.  Colour passes (vc_color_visible, vc_paint_clusters,
+ *     vc_paint_geodesic) leave the shell valid: it holds the colours the records had at the call, so run it after the colouring.
+ *     VC_ERR_ARG (with a message, nothing launched) when there is no carve result, steps are in flight, the carve ran with
+ *     VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached, L >
+ *     VC_SHELL_MAX_LEVEL, flags != 0, stats == NULL, or the grid exceeds the u32 index.  S = 0 is no error.  Synchronous, with
+ *     one read-back (the count) before the shell's buffers are sized; VC_ERR_OOM when they cannot be, the result as it was.
+ * stats (required): survivors = S; cells_on = the ON cells of the (coarse) grid (S at L = 0); shell = T, the cells listed;
+ * faces[k] = the shell cells with bit k set; level, cube_scale = 2^level, dims = the (coarse) grid; shell_ms = HIP events around
+ * the whole call.  vc_fetch_shell: either pointer may be NULL (both: only asks whether the shell is valid).
+ * vc_fetch_shell_viewer builds both arrays on the device and copies 24 bytes per shell record; either pointer may be NULL;
+ * VC_ERR_ARG when scaling is 0 or not finite. */
+#define VC_SHELL_MAX_LEVEL 6u
+typedef struct {
+    uint64_t survivors, cells_on, shell;
+    uint64_t faces[6];
+    uint32_t level, cube_scale, dims[3];
+    float shell_ms;                 /* HIP events around the whole call */
+} vc_shell_stats_t;
+int vc_hull_shell(vc_ctx *ctx, uint32_t level, uint32_t flags /* must be 0 */, vc_shell_stats_t *stats);
+int vc_fetch_shell(vc_ctx *ctx, uint64_t *records /* [shell] */, uint8_t *faces /* [shell] */);
+int vc_fetch_shell_viewer(vc_ctx *ctx, double scaling, float *positions /* [shell][3] */, float *colors /* [shell][3] */);
+
 /* ---- the hull thinned to a curve skeleton, topology kept (no reference counterpart) ---------------------------------------------------
  * vc_hull_thin peels the current carve result, as vc_fetch_occupancy and vc_fetch_records see it, down to a centred, one-voxel-wide
  * skeleton with the components, tunnels and cavities of the hull.  The result is left exactly as it is: the pass works on a copy

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -25,6 +25,9 @@ hull), clusters (with --clusters K), geodesic (with --extremities K: the regions
 --skeleton curve|point [--skeleton-anchors extrema]: the hull thinned to a one-voxel-wide skeleton with its topology on the
 device, assignment.configure(skeleton=...) -- its voxels, end points, junctions and length in mm are printed; with
 --skeleton-anchors extrema (and --extremities K) the floor contact and the extremities are pinned;
+--shell [LEVEL]: only what an opaque cube viewer can show -- the voxels with an exposed face, listed on the device with the
+viewer's arrays, assignment.configure(output="shell", output_level=LEVEL); survivors, shell, its share and the exposed faces are
+printed and the PLY holds the shell; LEVEL 1..6 (default 0) lists the cells of a grid 2^LEVEL times coarser with averaged colours;
 --temporal T [--frames F] [--noise P]: F frames (default 16) of the committed masks, each with a share P (default 0.02) of its
 pixels flipped by a generator seeded with 7000 + the frame number, are carved one after the other and every hull is replaced by
 the vote of the last T hulls on the device, assignment.configure(temporal_window=T) -- the voxels that change between consecutive
@@ -81,6 +84,14 @@ if "--skeleton-anchors" in sys.argv:
     k = sys.argv.index("--skeleton-anchors")
     skeleton_anchors = sys.argv[k + 1]
     del sys.argv[k:k + 2]
+shell_level = None
+if "--shell" in sys.argv:
+    k = sys.argv.index("--shell")
+    shell_level = 0
+    if k + 1 < len(sys.argv) and sys.argv[k + 1] in ("0", "1", "2", "3", "4", "5", "6"):
+        shell_level = int(sys.argv[k + 1])
+        del sys.argv[k + 1]
+    del sys.argv[k]
 render_dir = None
 if "--render" in sys.argv:
     k = sys.argv.index("--render")
@@ -136,7 +147,8 @@ assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_w
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
                      extremities=extremities, geodesic_paint=geodesic_paint if extremities else None,
                      min_component_voxels=1 if measure == "components" else 0, measure=measure,
-                     skeleton=skeleton, skeleton_anchors=skeleton_anchors if skeleton else None)
+                     skeleton=skeleton, skeleton_anchors=skeleton_anchors if skeleton else None,
+                     output="all" if shell_level is None else "shell", output_level=shell_level or 0)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 if temporal:
     raw_sum = out_sum = 0
@@ -159,7 +171,13 @@ if out != "-":
         for p, c in zip(pos, rgb):
             f.write("%g %g %g %d %d %d\n" % (p[0], p[1], p[2], c[0], c[1], c[2]))
 print("%d voxels of the %dx%dx%d grid survive all 4 views (footprint %s, %sopened by %g mm) -> %s; extent x %.2f..%.2f, y %.2f..%.2f, z %.2f..%.2f" %
-      (len(pos), g, g, g, footprint, "closed by %g mm, " % close_mm if close_mm > 0 else "", open_mm, out, pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max(), pos[:, 2].min(), pos[:, 2].max()))
+      (len(pos) if shell_level is None else assignment.shell()["survivors"], g, g, g, footprint, "closed by %g mm, " % close_mm if close_mm > 0 else "", open_mm, out, pos[:, 0].min(), pos[:, 0].max(), pos[:, 1].min(), pos[:, 1].max(), pos[:, 2].min(), pos[:, 2].max()))
+if shell_level is not None:
+    sh = assignment.shell()
+    print("shell (level %d, cubes x%d on a %dx%dx%d grid): %d survivors in %d cells, %d with an exposed face (%.1f %% of the survivors); "
+          "faces -x %d +x %d -y %d +y %d -z %d +z %d (%.3f ms on the device)" %
+          ((sh["level"], sh["cube_scale"]) + tuple(sh["dims"]) + (sh["survivors"], sh["cells_on"], sh["shell"],
+           100.0 * sh["shell"] / max(sh["survivors"], 1)) + tuple(sh["faces"]) + (sh["shell_ms"],)))
 if clusters:
     cl = assignment.clusters()
     print("clusters: %d figures in %d rounds (%s, %.3f ms on the device)" % (clusters, cl["iterations"],

@@ -34,6 +34,7 @@ VC_MEASURE_PROFILE = 1
 VC_MEASURE_MAX_GROUPS = 4096
 VC_MEASURE_MAX_AXIS = 65536
 VC_MEASURE_MAX_PROFILE = 1 << 20
+VC_SHELL_MAX_LEVEL = 6
 VC_THIN_CURVE, VC_THIN_POINT = 0, 1
 VC_THIN_ANCHORS_NONE, VC_THIN_ANCHORS_LIST, VC_THIN_ANCHORS_EXTREMA = 0, 1, 2
 VC_THIN_MAX_PASSES, VC_THIN_DEFAULT_PASSES = 10000, 4096
@@ -159,6 +160,11 @@ class VcMeasure(ctypes.Structure):
 class VcMeasureStats(ctypes.Structure):
     _fields_ = [("survivors", ctypes.c_uint64), ("measured", ctypes.c_uint64), ("unlabelled", ctypes.c_uint64),
                 ("groups", ctypes.c_uint32), ("measure_ms", ctypes.c_float)]
+
+
+class VcShellStats(ctypes.Structure):
+    _fields_ = [("survivors", ctypes.c_uint64), ("cells_on", ctypes.c_uint64), ("shell", ctypes.c_uint64), ("faces", ctypes.c_uint64 * 6),
+                ("level", ctypes.c_uint32), ("cube_scale", ctypes.c_uint32), ("dims", ctypes.c_uint32 * 3), ("shell_ms", ctypes.c_float)]
 
 
 class VcSkeletonVoxel(ctypes.Structure):
@@ -287,6 +293,9 @@ SIGNATURES = {
     "vc_hull_measure": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcMeasureStats)]),
     "vc_fetch_measure": (ctypes.c_int, [c_ctx, ctypes.POINTER(VcMeasure)]),
     "vc_fetch_measure_profile": (ctypes.c_int, [c_ctx, c_u64p]),
+    "vc_hull_shell": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcShellStats)]),
+    "vc_fetch_shell": (ctypes.c_int, [c_ctx, c_u64p, c_u8p]),
+    "vc_fetch_shell_viewer": (ctypes.c_int, [c_ctx, ctypes.c_double, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "vc_hull_thin": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, c_u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                     ctypes.POINTER(VcThinStats)]),
     "vc_fetch_thin": (ctypes.c_int, [c_ctx, ctypes.POINTER(ctypes.c_uint16)]),

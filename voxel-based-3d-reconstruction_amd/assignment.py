@@ -168,7 +168,10 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None,
              "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None,
              "measure": None, "measure_profile": False,
-             "skeleton": None, "skeleton_anchors": None}
+             "skeleton": None, "skeleton_anchors": None,
+             "output": "all", "output_level": 0}
+_shell_state = {"last": None}
+OUTPUTS = ("all", "shell")
 _skeleton_state = {"last": None}
 SKELETONS = (None, "curve", "point")
 _measure_state = {"last": None, "centroids_mm": None}
@@ -232,7 +235,13 @@ def configure(frame_source=None, **settings):
     CarveEngine.thin_hull(skeleton, anchors=skeleton_anchors): the hull thinned to a centred, one-voxel-wide skeleton with its
     topology, on the device; the hull itself stays.  skeleton_anchors = "extrema" pins the skeleton at the floor contact and the
     extremities of extremities=K, which turns a noisy curve skeleton into a stick figure; it is refused without extremities=K.
-    skeleton() returns the last frame's.  None (the default) runs nothing."""
+    skeleton() returns the last frame's.  None (the default) runs nothing.
+    output, output_level: "all" (the default) returns every survivor, as the reference does.  "shell" ends every frame -- after
+    every other pass and all painting -- with CarveEngine.hull_shell(output_level) and returns the arrays of
+    CarveEngine.fetch_shell_viewer(), made on the device: only the voxels with an exposed face, which is everything an opaque
+    cube viewer can show (at level 0 the same rows the full arrays hold for those voxels).  output_level = L in 1..6 lists the
+    cells of a grid 2^L times coarser instead, with averaged colours: the viewer must draw each cube shell()["cube_scale"] times
+    as large.  shell() returns the last frame's stats.  voxels_status() is unaffected.  output_level needs output="shell"."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
@@ -283,7 +292,15 @@ def configure(frame_source=None, **settings):
         raise ValueError('skeleton_anchors %r, expected None or "extrema"' % (merged["skeleton_anchors"],))
     if merged["skeleton"] is not None and merged["skeleton_anchors"] == "extrema" and not merged["extremities"] > 0:
         raise ValueError('skeleton_anchors="extrema" needs extremities=K')
+    if merged["output"] not in OUTPUTS:
+        raise ValueError("output %r, expected one of %s" % (merged["output"], OUTPUTS))
+    lv = merged["output_level"]
+    if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)) or not 0 <= lv <= 6:
+        raise ValueError("output_level %r, expected an integer in 0..6" % (lv,))
+    if lv != 0 and merged["output"] != "shell":
+        raise ValueError('output_level=%d needs output="shell"' % lv)
     _settings.update(settings)
+    _shell_state.update(last=None)
     _measure_state.update(last=None, centroids_mm=None)
     _skeleton_state.update(last=None)
     _temporal_state.update(last=None)
@@ -369,6 +386,9 @@ def set_voxel_positions(width, height, depth):
         _measure_frame()
     if _settings["skeleton"] is not None:
         _skeleton_frame()
+    if _settings["output"] == "shell":
+        _shell_state["last"] = _engine.hull_shell(int(_settings["output_level"]))
+        return _engine.fetch_shell_viewer()
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)
@@ -415,6 +435,14 @@ def skeleton():
     if _engine is None or not initialized or _skeleton_state["last"] is None:
         raise RuntimeError("no skeleton: configure(skeleton=...) and set_voxel_positions have not run")
     return _skeleton_state["last"]
+
+
+def shell():
+    """The stats of the last set_voxel_positions call's shell (configure(output="shell")): the dict of CarveEngine.hull_shell
+    (survivors, cells_on, shell, faces, level, cube_scale, dims, shell_ms)."""
+    if _engine is None or not initialized or _shell_state["last"] is None:
+        raise RuntimeError("no shell: configure(output=\"shell\") and set_voxel_positions have not run")
+    return _shell_state["last"]
 
 
 def _measure_frame():

@@ -1151,6 +1151,46 @@ class CarveEngine:
         self._check(self._L.vc_fetch_measure_profile(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_fetch_measure_profile")
         return out[:G]
 
+    # -- the hull's shell: what a viewer of opaque cubes can see (vc_hull_shell) ---------------------------------------------------
+    def hull_shell(self, level=0):
+        """Lists the cells of the current carve result that have an exposed face, in cell order, with their exposed faces
+        (contract: include/voxcarve.h): at level 0 the surface voxels with their records' colours, at level L in 1..6 the cells
+        of a grid 2^L times coarser with the rounded mean colour of the surface voxels inside them that the colour camera sees.
+        Everything a ray can hit is in the level-0 shell; the hull itself stays as it is.  Returns the stats as a dict:
+        survivors, cells_on, shell, faces [6] (-x, +x, -y, +y, -z, +z), level, cube_scale (2^level: the edge of the cube to draw
+        per cell, in voxels), dims (the coarse grid), shell_ms."""
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or level < 0:
+            raise ValueError("hull_shell: level %r, expected an integer in 0..%d" % (level, _lib.VC_SHELL_MAX_LEVEL))
+        st = _lib.VcShellStats()
+        self._check(self._L.vc_hull_shell(self._ctx, int(level), 0, ctypes.byref(st)), "vc_hull_shell")
+        self._shell_t = int(st.shell)
+        return {"survivors": int(st.survivors), "cells_on": int(st.cells_on), "shell": int(st.shell), "faces": [int(v) for v in st.faces],
+                "level": int(st.level), "cube_scale": int(st.cube_scale), "dims": [int(v) for v in st.dims], "shell_ms": float(st.shell_ms)}
+
+    def shell_valid(self):
+        """True while the list of the last hull_shell() describes the current hull."""
+        return self._L.vc_fetch_shell(self._ctx, None, None) == _lib.VC_OK
+
+    def fetch_shell(self):
+        """(records u64 [T], faces u8 [T]) of the last hull_shell: per shell cell {u32 cell index, r, g, b, seen} and the byte of
+        its exposed faces (bit k: -x, +x, -y, +y, -z, +z), ascending by cell."""
+        T = getattr(self, "_shell_t", 0)
+        rec = np.zeros(max(T, 1), dtype=np.uint64)
+        faces = np.zeros(max(T, 1), dtype=np.uint8)
+        self._check(self._L.vc_fetch_shell(self._ctx, _ptr(rec, ctypes.c_uint64), _ptr(faces, ctypes.c_uint8)), "vc_fetch_shell")
+        return rec[:T], faces[:T]
+
+    def fetch_shell_viewer(self, scaling_factor=SCALING_FACTOR):
+        """(positions float32 [T, 3], colors float32 [T, 3]) of the last hull_shell, made on the device: at level 0 exactly
+        viewer_positions(voxel_keys(...)) and viewer_colors(...) of the shell's voxels; above it the centre of each coarse cell
+        (draw its cube cube_scale times as large)."""
+        T = getattr(self, "_shell_t", 0)
+        pos = np.zeros((max(T, 1), 3), dtype=np.float32)
+        col = np.zeros((max(T, 1), 3), dtype=np.float32)
+        self._check(self._L.vc_fetch_shell_viewer(self._ctx, float(scaling_factor), _ptr(pos, ctypes.c_float), _ptr(col, ctypes.c_float)),
+                    "vc_fetch_shell_viewer")
+        return pos[:T], col[:T]
+
     # -- the hull thinned to a curve skeleton (vc_hull_thin) -----------------------------------------------------------------------
     def thin_hull(self, mode="curve", anchors=None, max_passes=_lib.VC_THIN_DEFAULT_PASSES):
         """Thins the current carve result to a centred, one-voxel-wide skeleton with the hull's components, tunnels and cavities
