@@ -206,14 +206,13 @@ int vc_carve(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int 
  * holding the collected result (the third one after it was issued) takes it away -- fetch before that call; afterwards the
  * vc_fetch_* functions fail with VC_ERR_ARG until the next vc_carve_end.
  * min_views > n_cameras is legal and yields the empty result (as the reference's threshold test would).
- * KNOWN DEFECT, not yet fixed: steps in flight must share one colour camera.  With option fused_color_table = 1 (the default) a
- * VC_MODE_FUSED step colours its survivors from ONE table over the whole grid, projected for one camera (vc_ctx::d_lut_color).  A
- * vc_carve_begin with another color_cam projects its camera's table over it on the carve stream while the record expansion of
- * the step before it may still be reading it on the second stream: nothing orders the two.  Seen on the device with two steps
- * on two slots, color_cam 1 then 2, 30 x 63 x 30: 158 to 559 of the first step's 2797 records came back with colour and `seen`
- * bytes of zero, another number in every run; the indices, the count and the second step were right.  vc_carve (begin + end)
- * and VC_MODE_LUT (a table per camera) are not affected.  Until the projection waits for {step done} of the last expansion that
- * was given the table, collect a step before beginning one with another colour camera, or set fused_color_table = 0. */
+ * Steps in flight may name different colour cameras.  With option fused_color_table = 1 (the default) a VC_MODE_FUSED step colours
+ * its survivors from ONE table over the whole grid, projected for one camera at a time: a vc_carve_begin with another color_cam
+ * projects its camera's table into the same buffer, on the device behind the last record expansion that was handed the old one
+ * (a stream wait on that step's {done} event; the host does not wait, and a step with the camera of the step before it queues
+ * nothing more than it did).  A step whose record buffer overflowed and whose table has been replaced since projects its survivors
+ * itself when vc_carve_end expands it again, as with fused_color_table = 0: the same bytes.  VC_MODE_LUT reads a table per
+ * camera. */
 int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int mode, uint32_t flags);
 int vc_carve_end(vc_ctx *ctx, uint64_t *n_out);
 /* Footprint carve: a camera passes a voxel by the foreground count of the pixel box its whole CELL projects to, not by the one

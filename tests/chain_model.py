@@ -1,7 +1,7 @@
 """What a context holds behind a carve, as include/voxcarve.h describes it, in numpy and without a GPU: the current records, and for
 every product of a post-carve pass whether it is valid and its bytes.  Every operation goes through the restatements that the
 per-pass tests already hold the device to (oracle.carve_c / carve_np, footprint_np, closing_np, distance_np, components_np,
-visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, temporal_np, measure_np, thin_np,
+visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, temporal_np, measure_np, thin_np, shell_np,
 oracle.marching_np); nothing is restated here.  What this module adds is how the passes COMBINE: which records a pass starts from,
 which frame set it reads, whose labels it takes, what it invalidates, and the one state that outlives a result (the vote's ring).
 
@@ -11,6 +11,10 @@ KINDS_B) draws from every kind, with carve -> temporal pairs on different slots 
 A on the device; family B is held to its coverage conditions, its literal twins and its faults in tests/test_chain_model.py, and
 its walk on the device is not in the suite yet (REFUSAL_B names what its products' fetches are to refuse with there).
 
+The hull's shell (vc_hull_shell) is no drawn kind: neither family's draws may move.  with_shell(ops, seed) puts `shell` operations
+at fixed places of a chain instead, without a random number; trace, run and replay take shell=True and walk the interleaved chain,
+whose original steps keep their records and their products (tests/test_chain_model.py asserts it).
+
   scene(grid)            one of GRIDS, the golden cameras, three frame sets (slots 0, 1, 2) with different hulls and colours
   draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B) operations with all their parameters, drawn with
                          numpy.random.default_rng(seed) alone; some draws (min_voxels, the sources of a measurement, anchors) look
@@ -18,9 +22,10 @@ its walk on the device is not in the suite yet (REFUSAL_B names what its product
   Model(scene).apply(op) applies one operation; returns what the call returns and produces (stats, flags, labels, fields, images)
   replay(seed, upto=k)   the model in front of step k of that chain
   trace(seed)            one row per step (what ran, on how many records, whether the hull changed, ...) for the coverage conditions
+  with_shell(ops, seed)  (ops with `shell` operations put in, for each the step of `ops` it stands for or None)
 
 A record is uint64: the linear index in the low 32 bits, r, g, b in bytes 4 - 6, `seen` in byte 7.  The product names are those of
-test_gpu_result_generation.REFUSAL / BUILT and, for the three passes that only family B knows, of REFUSAL_B."""
+test_gpu_result_generation.REFUSAL / BUILT and, for the three passes that only family B knows and for the shell, of REFUSAL_B."""
 import hashlib
 import os
 import sys
@@ -38,6 +43,7 @@ import measure_np as mn
 import normals_np as nn
 import photo_np as pn
 import render_np as rn
+import shell_np as shn
 import surface_np as sn
 import temporal_np as tpn
 import thin_np as thn
@@ -60,9 +66,10 @@ ROLLS = (0, 9, -13)                         # columns the golden masks are rolle
 SLOT_IMAGES = ((0, 1, 2, 3), (0, 1, 2, 3), (1, 2))   # cameras with an image per slot: slot 2 cannot feed a colour pass
 FULL_SLOTS = tuple(s for s, cams in enumerate(SLOT_IMAGES) if len(cams) == 4)
 COLOUR_CAMERAS = (None, 1, 2)
-# the products of the passes that only family B knows -> the refusal of their fetches (fetch_temporal; fetch_measure and, after
-# profile=True, fetch_measure_profile; fetch_thin + fetch_skeleton) once the result is another (include/voxcarve.h)
-REFUSAL_B = {"temporal": "no votes", "measure": "no measurements", "skeleton": "no skeleton"}
+# the products of the passes that only family B knows, and of the shell that with_shell puts into a chain -> the refusal of their
+# fetches (fetch_temporal; fetch_measure and, after profile=True, fetch_measure_profile; fetch_thin + fetch_skeleton; fetch_shell +
+# fetch_shell_viewer) once the result is another (include/voxcarve.h)
+REFUSAL_B = {"temporal": "no votes", "measure": "no measurements", "skeleton": "no skeleton", "shell": "no shell"}
 PRODUCTS = tuple(REFUSAL) + ("render", "surface") + tuple(REFUSAL_B)
 assert set(PRODUCTS) >= BUILT and not set(REFUSAL_B) & (set(REFUSAL) | BUILT)
 
@@ -168,7 +175,8 @@ class Model:
     comparison on the CPU): "grow_slot0" colours added and restored voxels from slot 0 instead of the carve's slot, "drop_paint" gives the
     records that a compaction keeps the colours of the carve again, "temporal_forgets_prev" empties the vote's previous output
     at every carve (no hysteresis across frames), "measure_carve_colours" sums the colours the carve gave the records instead of
-    the ones they have at the call."""
+    the ones they have at the call, "shell_repainted" lets a valid shell take the new colours when a pass repaints the records
+    (item 5 of vc_hull_shell: it holds the colours the records had at the call)."""
 
     def __init__(self, sc, fault=None, literal=False):
         self.scene = sc
@@ -185,6 +193,7 @@ class Model:
         self.labels = {}                     # what a measurement or a skeleton may read while the product of that name is valid:
         #                                      "clusters" (u8 labels, K), "geodesic" (u8 labels, extremities, distances),
         #                                      "component_labels" (the dict of components_np)
+        self.shell_level = 0                 # the level of the last shell
 
     # what the result is
     @property
@@ -221,6 +230,8 @@ class Model:
     # the operations
     def apply(self, op):
         out = getattr(self, "_" + op["op"])(op)
+        if self.fault == "shell_repainted" and op["op"] in RECOLOURING and "shell" in self.products:
+            self.products["shell"] = self._shell_product(shn.shell(self.records, self.grid, self.shell_level))
         out["survivors"] = self.S
         return out
 
@@ -448,6 +459,18 @@ class Model:
         self.products["skeleton"] = w["peel"].tobytes() + rows.tobytes()
         return {"stats": {k: w[k] for k in thn.STATS}, "thin": w}
 
+    # the shell: read-only, the generation stays; it keeps the colours of the call across colour passes and paints, and goes stale
+    # with everything else when the surviving voxels change (item 5 of vc_hull_shell)
+    @staticmethod
+    def _shell_product(w):
+        return w["records"].tobytes() + w["faces"].tobytes()
+
+    def _shell(self, op):
+        w = (shn.shell_literal if self.literal else shn.shell)(self.records, self.grid, op["level"])
+        self.shell_level = op["level"]
+        self.products["shell"] = self._shell_product(w)
+        return {"stats": w["stats"], "shell": w}
+
     # what the end of a chain compares on the final hull
     def marching_cubes(self):
         """marching_cubes(volume=None): the occupancy in the reference's reshape, (nx, ny, nz) over the voxel order."""
@@ -653,24 +676,63 @@ def _draw_chain_b(seed):
     return sc, ops
 
 
+SHELL_AFTER = (2, 6, 10)                     # a shell behind these steps of a chain ...
+SHELL_LEVELS = (0, 0, 1, 0, 2)               # ... at these levels in turn, starting at the seed's place in the list
+SHELL_STALERS = HULL_CHANGERS + ("carve", "temporal")
+
+
+def with_shell(ops, seed):
+    """(walk, origin): `ops` with a `shell` operation behind every step of SHELL_AFTER, directly in front of the first pass that
+    repaints the records (RECOLOURING) and directly in front of the first operation behind step 0 that may change the surviving
+    voxels (SHELL_STALERS); never two in a row.  The levels follow SHELL_LEVELS from the seed on.  origin[k] is the step of `ops`
+    that walk[k] is, None for a shell.  Nothing is drawn: the chain's own operations, and what they were drawn from, stay."""
+    first = lambda kinds: next((k for k, op in enumerate(ops) if k and op["op"] in kinds), None)
+    before = {first(RECOLOURING), first(SHELL_STALERS)} - {None}
+    walk, origin = [], []
+
+    def shell():
+        if walk[-1]["op"] != "shell":
+            walk.append({"op": "shell", "level": SHELL_LEVELS[(seed + origin.count(None)) % len(SHELL_LEVELS)]})
+            origin.append(None)
+
+    for k, op in enumerate(ops):
+        if k in before:
+            shell()
+        walk.append(op)
+        origin.append(k)
+        if k in SHELL_AFTER:
+            shell()
+    return walk, origin
+
+
+def walk_of(seed, shell=False):
+    """(scene, operations, origin) of chain `seed` as trace, run and replay walk it: as drawn, or with the shell put in."""
+    sc, ops = draw_chain(seed)
+    if not shell:
+        return sc, ops, list(range(len(ops)))
+    walk, origin = with_shell(ops, seed)
+    return sc, walk, origin
+
+
 def final_ops(sc):
     """One run of every quiet pass, for the final hull of a chain."""
     return [{"op": "hull_distance", "border": "open", "outside": True}, {"op": "hull_normals", "radius_mm": normals_radius_mm(sc)},
             {"op": "render"}, {"op": "surface_mesh", "refine_steps": 8}]
 
 
-def run(seed, fault=None):
-    """Yields (step, op, out, model) of chain `seed`, the model as the operation left it."""
-    sc, ops = draw_chain(seed)
+def run(seed, fault=None, shell=False):
+    """Yields (step, op, out, model) of chain `seed` (shell=True: of its walk with the shell put in), the model as the operation
+    left it."""
+    sc, ops, _ = walk_of(seed, shell)
     model = Model(sc, fault)
     for step, op in enumerate(ops):
         out = model.apply(op)
         yield step, op, out, model
 
 
-def replay(seed, upto=None, fault=None, literal=False):
-    """The model of chain `seed` in front of step `upto` (None: behind the last one)."""
-    sc, ops = draw_chain(seed)
+def replay(seed, upto=None, fault=None, literal=False, shell=False):
+    """The model of chain `seed` in front of step `upto` (None: behind the last one); shell=True: steps of the walk with the shell."""
+    sc, ops, _ = walk_of(seed, shell)
     model = Model(sc, fault, literal)
     for op in ops[:upto]:
         model.apply(op)
@@ -682,21 +744,22 @@ def describe_op(op):
     return ", ".join("%s=%s" % (k, ("%s%r" % (v.dtype.name, v.shape)) if isinstance(v, np.ndarray) else repr(v)) for k, v in op.items())
 
 
-def products_digest(model):
-    """sha1 over the valid products, sorted by name: each name and its bytes."""
+def products_digest(model, without=()):
+    """sha1 over the valid products but those named in `without`, sorted by name: each name and its bytes."""
     h = hashlib.sha1()
-    for name in sorted(model.products):
+    for name in sorted(set(model.products) - set(without)):
         h.update(name.encode())
         h.update(model.products[name])
     return h.hexdigest()
 
 
-def trace(seed, fault=None):
-    """One dict per step: op, kind of carve, records before and after, whether the hull changed, what the records carried into
+def trace(seed, fault=None, shell=False):
+    """One dict per step (shell=True: of the walk with the shell put in; "origin" is then the step of the chain as drawn, None for a
+    shell, and "products_digest_drawn" the digest without the shell's product): op, kind of carve, records before and after, whether the hull changed, what the records carried into
     the operation (seen == 0 bytes, painted colours), the valid products in front of and behind it and their digest, the carve that
     made the result, what made its hull last (the carve or a pass that changed it), and the call's stats."""
     rows = []
-    sc, ops = draw_chain(seed)
+    sc, ops, origin = walk_of(seed, shell)
     model = Model(sc, fault)
     carve_op = made_by = None
     for step, op in enumerate(ops):
@@ -710,6 +773,8 @@ def trace(seed, fault=None):
         row["after"] = model.S
         row["digest"] = hashlib.sha1(model.records.tobytes()).hexdigest()
         row["products_digest"] = products_digest(model)
+        row["products_digest_drawn"] = products_digest(model, without=("shell",))
+        row["origin"] = origin[step]
         row["valid"] = dict(model.products)
         row["changed"] = bool(out.get("changed", False)) if op["op"] != "carve" else False
         row["stats"] = out.get("stats")

@@ -5,6 +5,8 @@ distances, distance field, normals, images, mesh) and B (chain_model.SEEDS_B: al
 measurements and the skeleton).  Family A is held to the record digests it had before family B existed
 (tests/golden/chain_digests.json): what its seeds cover has not moved.  tests/test_gpu_chain.py walks family A on the device; family B
 is checked here alone so far, and every condition below is written so that its walk on the device can be added without another draw.
+The hull's shell is put into family B's chains at fixed places (chain_model.with_shell), not drawn: the original steps keep their
+records and products, and the shell has coverage conditions, a literal twin and a fault of its own.
 
 The coverage conditions below are conditions on the INPUTS of the GPU test (the seeds, the draw weights, the lengths), asserted here
 so that it cannot pass by doing nothing; where one fails, the seeds, the weights or the length change, never the thresholds.  Then:
@@ -37,6 +39,12 @@ def traces():
 @pytest.fixture(scope="module")
 def traces_b():
     return {seed: cm.trace(seed) for seed in cm.SEEDS_B}
+
+
+@pytest.fixture(scope="module")
+def traces_s():
+    """Family B with the shell put in."""
+    return {seed: cm.trace(seed, shell=True) for seed in cm.SEEDS_B}
 
 
 def test_seed_list():
@@ -215,6 +223,87 @@ def test_coverage_of_family_b(traces_b):
     assert n["thin on another S"] >= 6 and n["thin on a larger S"] >= 3
 
 
+def test_the_shell_leaves_the_drawn_steps_alone(traces_b, traces_s):
+    """The interleaving draws nothing and the pass is read-only: every step of a chain as drawn has the records and, but for the
+    shell's own, the products it has without the shell; the walk is the chain with shells put in, never two in a row."""
+    for seed in cm.SEEDS_B:
+        sc, ops = cm.draw_chain(seed)
+        walk, origin = cm.with_shell(ops, seed)
+        assert [k for k in origin if k is not None] == list(range(len(ops))) and all(walk[j] is ops[k] for j, k in enumerate(origin) if k is not None)
+        assert all(w["op"] == "shell" and w["level"] in cm.SHELL_LEVELS for w, k in zip(walk, origin) if k is None)
+        assert not any(a["op"] == b["op"] == "shell" for a, b in zip(walk, walk[1:])) and walk[0]["op"] == "carve"
+        assert cm.with_shell(ops, seed)[0] == walk                # (no state, no random number)
+        drawn = [r for r in traces_s[seed] if r["origin"] is not None]
+        assert [r["origin"] for r in drawn] == [r["step"] for r in traces_b[seed]]
+        for a, b in zip(drawn, traces_b[seed]):
+            assert a["op"] == b["op"] and a["digest"] == b["digest"], (seed, b["step"])
+            assert a["products_digest_drawn"] == b["products_digest"] == b["products_digest_drawn"], (seed, b["step"])
+            assert a["stats"] == b["stats"] and a["changed"] == b["changed"]
+        for r in traces_s[seed]:                                  # a shell changes nothing but its own product
+            if r["op"] == "shell":
+                assert not r["changed"] and r["after"] == r["before"]
+                assert {k: v for k, v in r["valid"].items() if k != "shell"} == {k: v for k, v in r["valid_before"].items() if k != "shell"}
+
+
+def test_coverage_of_the_shell(traces_s):
+    """What the interleaving gives the shell in family B's chains."""
+    n = collections.Counter()
+    levels = collections.Counter()
+    for seed, rows in traces_s.items():
+        for r in rows:
+            had, has = r["valid_before"], r["valid"]
+            if r["op"] == "shell":
+                levels[r["params"]["level"]] += 1
+                n["on a non-empty hull"] += r["before"] > 0
+                n["level > 0 on a non-empty hull"] += r["before"] > 0 and r["params"]["level"] > 0
+                n["coarse cells fewer than survivors"] += r["params"]["level"] > 0 and 0 < r["stats"]["shell"] < r["stats"]["survivors"]
+                n["of painted records"] += r["painted"]
+                n["with seen == 0 records"] += r["seen0"]
+                n["over a valid shell of another level"] += "shell" in had and had["shell"] != has["shell"]
+                n["on a pass's or a vote's hull"] += r["made_by"] is not None and r["made_by"]["op"] != "carve"
+                continue
+            if "shell" not in had:
+                continue
+            same = has.get("shell") == had["shell"]
+            assert same or "shell" not in has                     # valid with the bytes of the call, or gone
+            carried = same and r["before"] > 0
+            n["carried across a repaint"] += carried and r["op"] in cm.RECOLOURING
+            n["carried across a repaint that changed colours"] += carried and r["op"] in cm.RECOLOURING and r["digest"] != rows[r["step"] - 1]["digest"]
+            n["carried across a quiet pass, a measurement or a skeleton"] += carried and r["op"] in cm.QUIET + ("measure", "thin")
+            n["carried across a vote or a grow that changed nothing"] += carried and r["op"] in ("temporal", "close", "dilate")
+            n["dropped by a hull change"] += r["changed"] and "shell" not in has
+            n["dropped by a carve"] += r["op"] == "carve" and "shell" not in has
+            # another result: a carve, a compaction (even one that removes nothing: the generation advances), a grow or a vote
+            # that changed the hull; everything else leaves the shell as it was listed
+            if r["changed"] or r["op"] == "carve" or r["op"] in cm.COMPACTIONS:
+                assert "shell" not in has, (seed, r["step"], r["op"])
+            else:
+                assert same, (seed, r["step"], r["op"])
+    print("shell, runs per level:", dict(levels), dict(n))
+    assert n["on a non-empty hull"] >= 90
+    assert n["level > 0 on a non-empty hull"] >= 30 and min(levels[1], levels[2]) >= 12 and levels[0] > levels[1] + levels[2]
+    assert n["coarse cells fewer than survivors"] >= 30
+    assert n["of painted records"] >= 12 and n["with seen == 0 records"] >= 12
+    assert n["on a pass's or a vote's hull"] >= 8
+    assert n["carried across a repaint"] >= 24 and n["carried across a repaint that changed colours"] >= 24
+    assert n["carried across a quiet pass, a measurement or a skeleton"] >= 24
+    assert n["carried across a vote or a grow that changed nothing"] >= 3
+    assert n["dropped by a hull change"] >= 12 and n["dropped by a carve"] >= 12
+
+
+@pytest.mark.parametrize("coarse", [False, True], ids=["level 0", "level > 0"])
+def test_literal_twin_of_the_shell(traces_s, coarse):
+    """shell_np.shell_literal, the contract's loop over sets of cells, at the smallest state of at least 200 records on which the
+    walk lists a shell at level 0, and above it: the model's product, bytes and stats."""
+    seed, step = _smallest_state(traces_s, "shell", where=lambda r: (r["params"]["level"] > 0) == coarse)
+    op = cm.walk_of(seed, shell=True)[1][step]
+    a, b = cm.replay(seed, upto=step, shell=True), cm.replay(seed, upto=step, shell=True)
+    b.literal = True
+    out_a, out_b = a.apply(op), b.apply(op)
+    assert a.products["shell"] == b.products["shell"] and len(a.products["shell"]) == 9 * out_a["stats"]["shell"] > 0
+    assert out_a["stats"] == out_b["stats"] and np.array_equal(a.records, b.records) and a.products == b.products
+
+
 def test_chains_and_replay_are_deterministic(traces, traces_b):
     for seed in cm.SEEDS_B[:3]:
         sc, ops = cm.draw_chain(seed)
@@ -330,21 +419,23 @@ def test_literal_twin_of_the_surface_refinement(traces):
 @pytest.mark.parametrize("fault, fam", [pytest.param("grow_slot0", "A", id="grow_slot0"), pytest.param("drop_paint", "A", id="drop_paint"),
                                         pytest.param("grow_slot0", "B", id="grow_slot0-B"),
                                         pytest.param("temporal_forgets_prev", "B", id="temporal_forgets_prev"),
-                                        pytest.param("measure_carve_colours", "B", id="measure_carve_colours")])
-def test_a_wrong_model_is_told_apart(traces, traces_b, fault, fam):
+                                        pytest.param("measure_carve_colours", "B", id="measure_carve_colours"),
+                                        pytest.param("shell_repainted", "S", id="shell_repainted")])
+def test_a_wrong_model_is_told_apart(traces, traces_b, traces_s, fault, fam):
     """The chains are not hollow: a model that colours added voxels from slot 0 instead of the carve's slot, that loses the
     painted colours at a compaction, that forgets the vote's previous output at a carve, or that sums the carve's colours into a
-    measurement, gives other records (family B: or other products) than the right one in at least one chain -- the comparison
-    that the walk on the device makes (tests/test_gpu_chain.py), fed on the CPU.  In family B "grow_slot0" reaches the voxels that
-    a vote restores as well."""
+    measurement, or that lets a valid shell take the colours of a later repaint, gives other records (family B: or other
+    products) than the right one in at least one chain -- the comparison that the walk on the device makes
+    (tests/test_gpu_chain.py), fed on the CPU.  In family B "grow_slot0" reaches the voxels that a vote restores as well.  Family
+    "S" is family B with the shell put in (chain_model.with_shell)."""
     told = []
-    want = traces if fam == "A" else traces_b
+    want = {"A": traces, "B": traces_b, "S": traces_s}[fam]
     for seed in want:
-        for step, op, out, model in cm.run(seed, fault):
+        for step, op, out, model in cm.run(seed, fault, shell=fam == "S"):
             row = want[seed][step]
             # family A: by the records alone, as before family B existed; family B: by the records or by the products' bytes
             if cm.hashlib.sha1(model.records.tobytes()).hexdigest() != row["digest"] or \
-                    (fam == "B" and cm.products_digest(model) != row["products_digest"]):
+                    (fam != "A" and cm.products_digest(model) != row["products_digest"]):
                 told.append((seed, step, op["op"]))
                 break
         if len(told) >= 3:

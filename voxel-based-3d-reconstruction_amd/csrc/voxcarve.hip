@@ -539,6 +539,10 @@ struct vc_ctx {
     bool packed = false;
     DevBuf<int32_t> d_lut_color;             // colour camera's table over the WHOLE grid (expansion of remote words)
     int lut_color_cam = -1;
+    // One buffer, one camera at a time, yet steps in flight may name different colour cameras: {done} of the last expansion that
+    // was handed the table on another stream than the carve stream (borrowed from step_ev / gx; null: none since the last
+    // projection).  ensure_color_table makes the next camera's projection wait for it on the device.
+    hipEvent_t lut_color_reader = nullptr;
 
     DevBuf<uint8_t> d_fg;            // vc_bgr_to_hsv / vc_mask_morphology: input | output | scratch images
     DevBuf<uint32_t> d_cc;           // vc_fill_figures / vc_foreground_to_slot: lab | own | tot | par planes per camera (vc_contour.h)
@@ -678,6 +682,7 @@ hipError_t make_streams(vc_ctx *ctx)
 // host memory, written past the caches).
 hipError_t make_events(vc_ctx *ctx)
 {
+    ctx->lut_color_reader = nullptr;             // (borrowed from the ring made again below; everything has drained)
     for (uint32_t r = 0; r < kStepRing; ++r) {
         for (int i = 0; i < 3; ++i) {
             const bool dev = ctx->event_scope >= (i == 1 ? 2 : 1);
@@ -1392,6 +1397,12 @@ int enqueue_counts_exchange(vc_ctx *ctx, StepBuf &cur, hipStream_t st)
 int ensure_color_table(vc_ctx *ctx, int cam)
 {
     if (ctx->lut_color_cam == cam && ctx->d_lut_color.ptr) return VC_OK;
+    // another camera's table goes into the same buffer: the expansion of a step still in flight (or of a queued gather) may be
+    // reading the old one on its own stream.  The projection waits for it on the device; the host does not.
+    if (ctx->lut_color_reader) {
+        VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lut_color_reader, 0));
+        ctx->lut_color_reader = nullptr;
+    }
     const uint64_t n = (uint64_t)ctx->nx * ctx->ny * ctx->nz;
     const uint64_t n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
     VC_TRY(ensure(ctx, ctx->d_lut_color, (size_t)n_pad));
@@ -2275,6 +2286,8 @@ int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam
     }
     if (!ride || auto_exchange) VC_HIP(ctx, hipEventRecord(sb.e2, auto_exchange ? sx : sb.no_records ? s2 : s3));
     if (!sb.no_records && s3 != ctx->stream) { s.e_emit = sb.e2; s.emit_pending = true; }   // the expansion reads the slot's bits / images
+    // ... and, table-free with a colour camera, the one whole-grid colour table: a later step that names another camera waits
+    if (!sb.no_records && s3 != ctx->stream && mode == VC_MODE_FUSED && e.lut) ctx->lut_color_reader = sb.e2;
     // the slot's next preparation waits for the kernels of THIS step that read its bits / grids: always this step's own event
     // (a flag left set by an earlier step on the same slot must not keep that step's event in place: the preparation would
     // then overwrite bits and grids under this step's carve).  Without e_scan, e2 is behind the carve kernels too.
@@ -2316,6 +2329,9 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
             sb.emit.capacity = sb.records.cap;
             // (a later step may have packed the compact table for another colour camera since: d_lut_tile still holds this one's)
             if (sb.emit.lut16 && ctx->lut16_cam != sb.color_cam) { sb.emit.lut16 = nullptr; sb.emit.cbase = nullptr; }
+            // (... or projected the whole-grid colour table for another camera: a table-free step then projects its survivors
+            // itself, as with fused_color_table = 0 -- the same bytes, and the table stays the newer step's)
+            if (sb.mode == VC_MODE_FUSED && sb.emit.lut && ctx->lut_color_cam != sb.color_cam) sb.emit.lut = nullptr;
             VC_TRY(launch_emit(ctx, sb, ctx->stream));
             sb.emit_ridden = false;
             VC_HIP(ctx, hipEventRecord(sb.e2, ctx->stream));
@@ -5710,6 +5726,7 @@ static int allgather_compact(vc_ctx *ctx, uint64_t *counts_out, uint64_t *total_
     if (xs != sx) VC_HIP(ctx, hipStreamWaitEvent(xs, E[2], 0));
     if (S) VC_TRY(enqueue_expand(ctx, xs, ent_all.ptr, M, S, ctx->h_xtotal + 2 + half));
     VC_HIP(ctx, hipEventRecord(E[1], xs));
+    if (S && cur.color_cam >= 0 && xs != ctx->stream) ctx->lut_color_reader = E[1];   // (it may read the colour table there: ensure_color_table)
     if (S && cur.color_cam >= 0) {          // the expansion reads the slot's bits / images beside the carve stream
         Slot &sl = ctx->slots[cur.slot];
         sl.e_emit = E[1];
