@@ -86,7 +86,7 @@ enum {
                               /* the whole word, the camera fails its 64 voxels at once                                     */
     VC_WORK_FOOT_WORDS,       /* occupancy words k_carve_foot took                                                          */
     VC_WORK_DIST_CELLS,       /* cells of the boxes the distance transforms ran over (vc_hull_distance, vc_hull_morphology,    */
-                              /* vc_hull_grow),                                                                               */
+                              /* vc_hull_grow, vc_hull_compare with VC_COMPARE_DISTANCE),                                     */
                               /* one count per transform: each of its three passes reads and writes that many 8-byte values   */
     VC_WORK_DIST_LINES        /* lines k_dist_y and k_dist_env walked                                                        */
 };
@@ -514,6 +514,90 @@ int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t ke
 int vc_fetch_temporal(vc_ctx *ctx, uint8_t *votes, uint8_t *added);            /* u8 [S_after] each, record order; either may be NULL */
 int vc_fetch_temporal_history(vc_ctx *ctx, uint32_t age, uint8_t *bits);       /* the raw hull pushed `age` calls ago, laid out as vc_fetch_occupancy */
 int vc_temporal_reset(vc_ctx *ctx);
+
+/* ---- set algebra on hulls: keep, load, combine and compare (no reference counterpart) --------------------------------------------
+ * Every pass above works on the current carve result, which only a carve of the same context can make.  These calls give it a
+ * second operand: VC_HULL_REGISTERS kept hulls on the device, a pass that combines the current result with one of them by a set
+ * operation, and a pass that compares the two and changes nothing.  With them a saved reconstruction can be reloaded and measured,
+ * thinned, meshed or rendered; a static scene subtracted; every frame clipped to a region; two sessions united; what moved between
+ * two frames shown; and the difference of two hulls put in numbers.  Integers and bits only (tests/setops_np.py restates it).
+ *
+ * Kept hulls.  A register is empty or holds a hull of the current grid: its occupancy words (laid out as vc_fetch_occupancy, bits
+ * at or beyond n zero), its voxel count and, optionally, its records (u64: index in the low 32 bits, R | G << 8 | B << 16 |
+ * seen << 24 in the high 32, ascending index).  Registers survive carves, passes and results; a change of grid, slab or cameras
+ * empties all of them, as it empties the ring of vc_hull_temporal.
+ *   vc_hull_keep     the register becomes a copy of the current result, records included.  Refused as a pass is (no carve result,
+ *                    steps in flight, VC_FLAG_NO_RECORDS, a narrower slab, a communicator of more than one rank).
+ *   vc_hull_upload   exactly one of bits / records is non-NULL.  bits: laid out as vc_fetch_occupancy; the register then has no
+ *                    records (n_records must be 0).  records: strictly ascending in the low 32 bits, every index below n; n_records
+ *                    = 0 is the empty hull with records.  The device validates: a set bit at or beyond n, a record out of order, a
+ *                    duplicate or an index at or beyond n returns VC_ERR_ARG.  The hull is built beside the register and swapped in
+ *                    only when valid: a refused or failed upload leaves the register's previous content intact.  Needs a grid (the
+ *                    whole grid as slab, no steps in flight, at most 2^32 voxels), not a carve result.
+ *   vc_hull_release  empties the register and frees its memory; an empty register is no error.
+ *   vc_fetch_kept    count and has_records (either may be NULL), the words into bits and the records into records (either may be
+ *                    NULL: call with both NULL to size the buffers).  VC_ERR_ARG for an empty register, and for records of a
+ *                    register that has none.
+ *
+ * vc_hull_combine.  A is the current occupancy as vc_fetch_occupancy sees it, B the register's.  VC_SETOP_COPY gives R = B,
+ * VC_SETOP_AND A & B, VC_SETOP_OR A | B, VC_SETOP_ANDNOT A \ B, VC_SETOP_XOR the symmetric difference; R is restricted to the grid.
+ *   1 result: records, count and occupancy describe R in ascending linear index.
+ *   2 kept records: a record of A & R keeps its 8 bytes (but see 4).
+ *   3 added voxels: a voxel of R \ A can only arise under COPY, OR or XOR.  When the register has records it takes B's 8 bytes
+ *     verbatim; otherwise it gets a fresh record exactly as item 3 of vc_hull_grow colours one.  added[r] = 1 for these
+ *     (vc_fetch_combined: u8 [survivors_after], record order).
+ *   4 COPY from a register with records is a restore: every record of R is B's record verbatim, and added[r] = 1 only where the
+ *     voxel was not in A.
+ *   5 R = A: nothing is invalidated and the result generation does not advance, as a vote that equals its input.  Otherwise every
+ *     product of a pass is stale, and a refusal of vc_hull_temporal under its item 8 is lifted.  A restore (4) always counts as
+ *     another result, whether or not the sets differ: the records' bytes may.
+ *   6 readers: vc_fetch_viewmask and vc_expand_entries stay the silhouette carve's.  Everything else reads R as an ordinary result.
+ *   7 stats (required): survivors_before = |A|; other = |B|; common = |A & B|; survivors_after = |R|; added = |R \ A|; removed =
+ *     |A \ R|; setop_ms = HIP events around the whole call.
+ *   8 VC_ERR_ARG (with a message, nothing launched, no state touched) when there is no carve result, steps are in flight, the carve
+ *     ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more than one rank is attached, op is
+ *     unknown, flags != 0, stats == NULL, reg >= VC_HULL_REGISTERS, the register is empty, the grid has more voxels than a u32
+ *     index, or -- only when fresh records would be coloured: the register has no records and op is COPY, OR or XOR -- the slot has
+ *     been prepared again since the carve (as vc_hull_grow).
+ *   9 an allocation failure returns VC_ERR_OOM and leaves result and registers as they were: R goes to a staging buffer, the
+ *     counts are read back and every buffer is sized before anything is committed.
+ * Synchronous, one read-back in the middle (the four counts).
+ *
+ * vc_hull_compare changes nothing: not the records, not the generation, not a stored vc_hull_distance field (it keeps a field
+ * buffer of its own).  Always: a = |A|, b = |B|, common, only_a = |A \ B|, only_b = |B \ A|; the inclusive index box diff_lo,
+ * diff_hi (x, y, z) of the symmetric difference, UINT32_MAX and 0 for an empty one; compare_ms.  With VC_COMPARE_DISTANCE, by
+ * the metric of vc_hull_distance (its items 1 and 2, with the same refusals; q = the steps in um, else zeros): h2_ab = max over v
+ * in A \ B of min over w in B of d2(v, w) in um^2, the directed Hausdorff distance squared (the voxels of A & B contribute 0); 0
+ * when A \ B is empty, UINT64_MAX when A \ B is not and B is.  arg_ab = the smallest linear index that attains h2_ab, UINT32_MAX
+ * when A \ B is empty.  h2_ba and arg_ba: the same with the roles swapped.  Without the flag the four are 0 and UINT32_MAX.
+ * VC_ERR_ARG as items 8 of vc_hull_combine names them for a pass and a register, for unknown flags and stats == NULL.
+ * Synchronous, one read-back in the middle (counts and boxes). */
+#define VC_HULL_REGISTERS 4
+#define VC_SETOP_COPY   0u
+#define VC_SETOP_AND    1u
+#define VC_SETOP_OR     2u
+#define VC_SETOP_ANDNOT 3u
+#define VC_SETOP_XOR    4u
+#define VC_COMPARE_DISTANCE 1u
+typedef struct {
+    uint64_t survivors_before, other /* |B| */, common /* |A & B| */, survivors_after, added, removed;
+    float setop_ms;
+} vc_setop_stats_t;
+typedef struct {
+    uint64_t a, b, common, only_a, only_b;
+    uint32_t diff_lo[3], diff_hi[3];    /* x, y, z, inclusive */
+    uint64_t h2_ab, h2_ba;              /* um^2 */
+    uint32_t arg_ab, arg_ba;            /* linear index */
+    uint64_t q[3];
+    float compare_ms;
+} vc_compare_stats_t;
+int vc_hull_keep(vc_ctx *ctx, uint32_t reg);
+int vc_hull_upload(vc_ctx *ctx, uint32_t reg, const uint8_t *bits, const uint64_t *records, uint64_t n_records);
+int vc_hull_release(vc_ctx *ctx, uint32_t reg);
+int vc_fetch_kept(vc_ctx *ctx, uint32_t reg, uint8_t *bits /* NULL ok */, uint64_t *records /* NULL ok */, uint64_t *count, uint32_t *has_records);
+int vc_hull_combine(vc_ctx *ctx, uint32_t op, uint32_t reg, uint32_t flags /* must be 0 */, vc_setop_stats_t *stats);
+int vc_fetch_combined(vc_ctx *ctx, uint8_t *added);   /* u8 [S_after], record order: 1 = the voxel was not in A */
+int vc_hull_compare(vc_ctx *ctx, uint32_t reg, uint32_t flags, vc_compare_stats_t *stats);
 
 /* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
  *      executable.py) -----------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--save-hull PATH] [--subtract PATH] [--clip PATH] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -32,6 +32,9 @@ printed and the PLY holds the shell; LEVEL 1..6 (default 0) lists the cells of a
 pixels flipped by a generator seeded with 7000 + the frame number, are carved one after the other and every hull is replaced by
 the vote of the last T hulls on the device, assignment.configure(temporal_window=T) -- the voxels that change between consecutive
 raw hulls and between consecutive voted hulls are printed per frame, and the last voted hull is what is written;
+--save-hull PATH: the hull as it stands after every pass (grid, bounds, records) as an .npz, CarveEngine.save_hull;
+--subtract PATH / --clip PATH: a hull saved that way is subtracted from / intersected with every frame's hull on the device right
+after the carve, assignment.configure(hull_subtract=PATH, hull_clip=PATH) -- the voxels each takes away are printed;
 --help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
@@ -117,6 +120,18 @@ if "--close" in sys.argv:
     k = sys.argv.index("--close")
     close_mm = float(sys.argv[k + 1])
     del sys.argv[k:k + 2]
+save_hull = subtract = clip = None
+for flag in ("--save-hull", "--subtract", "--clip"):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        value = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
+        if flag == "--save-hull":
+            save_hull = value
+        elif flag == "--subtract":
+            subtract = value
+        else:
+            clip = value
 temporal, n_frames, noise = 0, 16, 0.02
 for flag, conv in (("--temporal", int), ("--frames", int), ("--noise", float)):
     if flag in sys.argv:
@@ -148,7 +163,8 @@ assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_w
                      extremities=extremities, geodesic_paint=geodesic_paint if extremities else None,
                      min_component_voxels=1 if measure == "components" else 0, measure=measure,
                      skeleton=skeleton, skeleton_anchors=skeleton_anchors if skeleton else None,
-                     output="all" if shell_level is None else "shell", output_level=shell_level or 0)
+                     output="all" if shell_level is None else "shell", output_level=shell_level or 0,
+                     hull_subtract=subtract, hull_clip=clip)
 pos, col = assignment.set_voxel_positions(g, g // 2, g)          # the reference's call: (width, height, depth)
 if temporal:
     raw_sum = out_sum = 0
@@ -163,6 +179,13 @@ if temporal:
             raw_sum += ts["raw_changed"]
             out_sum += ts["out_changed"]
     print("flicker over frames %d..%d: %d voxels between raw hulls, %d between voted hulls" % (temporal, n_frames - 1, raw_sum, out_sum))
+if subtract or clip:
+    for name, st in assignment.hull_ops().items():
+        print("%s: %d of %d voxels leave the hull, %d stay (%d in the operand; %.3f ms on the device)" %
+              (name, st["removed"], st["survivors_before"], st["survivors_after"], st["other"], st["setop_ms"]))
+if save_hull:
+    assignment._engine.save_hull(save_hull)
+    print("hull of %d voxels -> %s" % (assignment._engine.count, save_hull))
 rgb = (col * 255.0 + 0.5).astype(np.uint8)
 if out != "-":
     with open(out, "w") as f:

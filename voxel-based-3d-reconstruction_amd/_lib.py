@@ -23,6 +23,9 @@ VC_MORPH_OPEN = 1
 VC_GROW_DILATE = 0
 VC_GROW_CLOSE = 1
 VC_TEMPORAL_MAX_WINDOW = 15
+VC_HULL_REGISTERS = 4
+VC_SETOP_COPY, VC_SETOP_AND, VC_SETOP_OR, VC_SETOP_ANDNOT, VC_SETOP_XOR = 0, 1, 2, 3, 4
+VC_COMPARE_DISTANCE = 1
 VC_GEO_SEEDS_LIST, VC_GEO_SEEDS_IZ_MAX, VC_GEO_SEEDS_IZ_MIN = 0, 1, 2
 VC_GEO_PATHS = 1
 VC_GEO_MAX_K = 32
@@ -122,6 +125,18 @@ class VcTemporalStats(ctypes.Structure):
                 ("survivors_before", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64), ("added", ctypes.c_uint64),
                 ("removed", ctypes.c_uint64), ("raw_changed", ctypes.c_uint64), ("out_changed", ctypes.c_uint64),
                 ("temporal_ms", ctypes.c_float)]
+
+
+class VcSetopStats(ctypes.Structure):
+    _fields_ = [("survivors_before", ctypes.c_uint64), ("other", ctypes.c_uint64), ("common", ctypes.c_uint64),
+                ("survivors_after", ctypes.c_uint64), ("added", ctypes.c_uint64), ("removed", ctypes.c_uint64), ("setop_ms", ctypes.c_float)]
+
+
+class VcCompareStats(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_uint64), ("b", ctypes.c_uint64), ("common", ctypes.c_uint64), ("only_a", ctypes.c_uint64),
+                ("only_b", ctypes.c_uint64), ("diff_lo", ctypes.c_uint32 * 3), ("diff_hi", ctypes.c_uint32 * 3),
+                ("h2_ab", ctypes.c_uint64), ("h2_ba", ctypes.c_uint64), ("arg_ab", ctypes.c_uint32), ("arg_ba", ctypes.c_uint32),
+                ("q", ctypes.c_uint64 * 3), ("compare_ms", ctypes.c_float)]
 
 
 class VcNormalsStats(ctypes.Structure):
@@ -269,6 +284,13 @@ SIGNATURES = {
     "vc_fetch_temporal": (ctypes.c_int, [c_ctx, c_u8p, c_u8p]),
     "vc_fetch_temporal_history": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
     "vc_temporal_reset": (ctypes.c_int, [c_ctx]),
+    "vc_hull_keep": (ctypes.c_int, [c_ctx, ctypes.c_uint32]),
+    "vc_hull_upload": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, c_u64p, ctypes.c_uint64]),
+    "vc_hull_release": (ctypes.c_int, [c_ctx, ctypes.c_uint32]),
+    "vc_fetch_kept": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, c_u64p, c_u64p, c_u32p]),
+    "vc_hull_combine": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcSetopStats)]),
+    "vc_fetch_combined": (ctypes.c_int, [c_ctx, c_u8p]),
+    "vc_hull_compare": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcCompareStats)]),
     "vc_hull_normals": (ctypes.c_int, [c_ctx, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcNormalsStats)]),
     "vc_fetch_record_normals": (ctypes.c_int, [c_ctx, c_i16p]),
     "vc_shade_render": (ctypes.c_int, [c_ctx, c_f64p, ctypes.c_uint32, ctypes.c_uint32]),

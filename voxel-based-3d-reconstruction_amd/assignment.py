@@ -167,6 +167,7 @@ _settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused"
              "clusters": 0, "cluster_min_column": 1, "cluster_paint": False,
              "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None,
              "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None,
+             "hull_subtract": None, "hull_clip": None,
              "measure": None, "measure_profile": False,
              "skeleton": None, "skeleton_anchors": None,
              "output": "all", "output_level": 0}
@@ -177,6 +178,8 @@ SKELETONS = (None, "curve", "point")
 _measure_state = {"last": None, "centroids_mm": None}
 MEASURES = (None, "all", "clusters", "geodesic", "components")
 _temporal_state = {"last": None}
+_hull_ops_state = {"last": None}
+HULL_SUBTRACT_REG, HULL_CLIP_REG = 3, 2      # the registers of CarveEngine that hold the two operands
 _cluster_state = {"centres_mm": None, "references": None, "last": None}
 _geodesic_state = {"last": None}
 GEODESIC_PAINTS = (None, "labels", "distance")
@@ -225,6 +228,11 @@ def configure(frame_source=None, **settings):
     becomes the vote of the last T frames' hulls (keep defaults to the majority, keep_off to keep), which takes the frame-to-frame
     flicker of mask noise out and lags a moving figure by about T / 2 frames.  temporal() returns the last frame's stats.
     0 (the default) runs nothing.
+    hull_subtract, hull_clip: each a path to a file of CarveEngine.save_hull, a hull as an array (bool [n], ascending uint32
+    indices or uint64 records: voxcarve.hullio.as_operand), or None.  The operand is uploaded once, to registers 3 and 2 of the
+    engine, and every carve is followed -- before temporal_window and everything else -- by CarveEngine.combine_hull("andnot", 3)
+    (the static scene leaves the hull) and then CarveEngine.combine_hull("and", 2) (the hull is clipped to a region of
+    interest).  hull_ops() returns the last frame's stats.  None (the default) runs nothing.
     measure, measure_profile: when measure = "all" | "clusters" | "geodesic" | "components", every frame ends -- after the
     clusters and the extremities -- with CarveEngine.measure_hull(labels=measure, profile=measure_profile): the hull's figures
     measured on the device, per group of that source (the whole hull; the figures of clusters=K; the regions of extremities=K;
@@ -274,6 +282,10 @@ def configure(frame_source=None, **settings):
         raise ValueError("temporal_window %r, expected an integer in 0..15" % (t,))
     CarveEngine.temporal_thresholds(t if t > 0 else 1, settings.get("temporal_keep", _settings["temporal_keep"]) if t > 0 else None,
                                     settings.get("temporal_keep_off", _settings["temporal_keep_off"]) if t > 0 else None)
+    for name in ("hull_subtract", "hull_clip"):
+        h = settings.get(name, _settings[name])
+        if h is not None and not isinstance(h, (str, os.PathLike, np.ndarray)):
+            raise ValueError("%s %r, expected a path, an array or None" % (name, h))
     m = settings.get("measure", _settings["measure"])
     if m not in MEASURES:
         raise ValueError("measure %r, expected one of %s" % (m, MEASURES))
@@ -304,6 +316,7 @@ def configure(frame_source=None, **settings):
     _measure_state.update(last=None, centroids_mm=None)
     _skeleton_state.update(last=None)
     _temporal_state.update(last=None)
+    _hull_ops_state.update(last=None)
     _cluster_state.update(centres_mm=None, references=None, last=None)
     _geodesic_state.update(last=None)
     _source = frame_source
@@ -351,6 +364,9 @@ def set_voxel_positions(width, height, depth):
         if _settings["mode"] == "lut":
             _engine.build_lut()
         _engine._sized = (H, W)
+        _engine._operands = False                                               # (new cameras empty the registers)
+    if not getattr(_engine, "_operands", False):
+        _upload_operands()
     cc = _settings["color_camera"]
     photo = _settings["hull"] == "photo"
     visible = _settings["color_mode"] == "visible" or photo
@@ -364,6 +380,13 @@ def set_voxel_positions(width, height, depth):
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"],
                   footprint=_settings["footprint"])
+    if _settings["hull_subtract"] is not None or _settings["hull_clip"] is not None:
+        ops = {}
+        if _settings["hull_subtract"] is not None:
+            ops["subtract"] = _engine.combine_hull("andnot", HULL_SUBTRACT_REG)
+        if _settings["hull_clip"] is not None:
+            ops["clip"] = _engine.combine_hull("and", HULL_CLIP_REG)
+        _hull_ops_state["last"] = ops
     if _settings["temporal_window"] > 0:
         _temporal_state["last"] = _engine.temporal_filter(_settings["temporal_window"], _settings["temporal_keep"],
                                                           _settings["temporal_keep_off"])
@@ -392,6 +415,27 @@ def set_voxel_positions(width, height, depth):
     idx, rgb, _ = _engine.fetch()
     keys = voxel_keys(idx, _engine.grid, _engine.axes())
     return viewer_positions(keys), viewer_colors(rgb)
+
+
+def _upload_operands():
+    """The operands of hull_subtract and hull_clip into their registers (see configure): once per camera set."""
+    for name, reg in (("hull_subtract", HULL_SUBTRACT_REG), ("hull_clip", HULL_CLIP_REG)):
+        h = _settings[name]
+        if h is None:
+            continue
+        if isinstance(h, (str, os.PathLike)):
+            _engine.load_hull(h, reg)
+        else:
+            _engine.upload_hull(h, reg)
+    _engine._operands = True
+
+
+def hull_ops():
+    """The stats of the last set_voxel_positions call's set operations (configure(hull_subtract=..., hull_clip=...)): a dict
+    with "subtract" and / or "clip", each the dict of CarveEngine.combine_hull."""
+    if _engine is None or not initialized or _hull_ops_state["last"] is None:
+        raise RuntimeError("no hull operations: configure(hull_subtract=... or hull_clip=...) and set_voxel_positions have not run")
+    return _hull_ops_state["last"]
 
 
 def _cluster_frame():

@@ -45,6 +45,7 @@
 #include "vc_distance.h"
 #include "vc_grow.h"
 #include "vc_temporal.h"
+#include "vc_setops.h"
 #include "vc_normals.h"
 #include "vc_clusters.h"
 #include "vc_geodesic.h"
@@ -411,6 +412,25 @@ struct vc_ctx {
         uint64_t pushes = 0;             // calls since the last reset (0: ring and P are empty)
         uint64_t nwords = 0, npad = 0;   // occupancy words of a snapshot, and the even count its slot holds
     } temporal;
+    // vc_hull_keep / vc_hull_upload / vc_hull_combine / vc_hull_compare: the kept hulls (occupancy words [npad] with a zeroed pad, the
+    // voxel count, optionally the records), the staging buffer of R (after a commit that added voxels: A's words), the counters
+    // and their read-back, the records' `added` bytes; the comparison's own box field, index boxes and maxima.  The registers
+    // OUTLIVE a result: a carve leaves them alone, geometry_changed empties them.
+    struct Kept {
+        DevBuf<uint64_t> words, rec;
+        uint64_t count = 0;
+        bool used = false, has_rec = false;
+    };
+    struct Setops {
+        Kept reg[VC_HULL_REGISTERS];
+        DevBuf<uint64_t> stage, field;
+        DevBuf<unsigned long long> ctr, acc;
+        DevBuf<uint32_t> box;
+        Pinned<uint64_t> h;              // page-locked read-back of counters, boxes and maxima
+        DevBuf<uint8_t> added;
+        uint64_t stamp = kNever;         // added belongs to the vc_hull_combine that produced the current result
+        uint64_t n = 0;                  // its survivors_after
+    } setops;
     // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
     struct Render {
         DevBuf<uint32_t> idx, rgbf;
@@ -594,6 +614,7 @@ void geometry_changed(vc_ctx *ctx)
     ctx->lut_valid = false; ctx->upload_mask = 0; ctx->ymajor_valid = false; ctx->tile_valid = false; ctx->bbox_valid = false;
     ctx->tbox_valid = false; ctx->kbox_valid = false; ctx->carved = false; ctx->gathered = false; ctx->viewmask_valid = false;
     ctx->temporal.pushes = 0;                    // the hulls of another grid or other cameras are no history of this one
+    for (vc_ctx::Kept &k : ctx->setops.reg) { k.used = false; k.has_rec = false; k.count = 0; }   // ... and no operands for it
     result_changed(ctx);
 }
 
@@ -1294,16 +1315,21 @@ int merge_sized(vc_ctx *ctx, const StepBuf &cur, uint64_t nwords, uint64_t S1, b
 
 // Ranks of the occupancy into d_woff, their total into h_res[2].  changed: the words are new, so the survivors per group of the step
 // are counted again (the packing skips the groups whose count is zero) and every old record that stays goes to its new rank in the
-// spare buffer.  The launches run under the pass's two kinds.
+// spare buffer.  The launches run under the pass's two kinds (a kind of -1: they carry none, as word_offsets').
 int merge_ranked(vc_ctx *ctx, StepBuf &cur, const MergeParams &p, uint64_t nwords, uint64_t S0, bool changed, int rank_kind, int merge_kind)
 {
     if (changed) {
         const uint32_t sgroups = (uint32_t)((cur.n + kLutPad - 1) / kLutPad * kLutPad / (64 * kGroupWords));
-        VC_DLAUNCH(rank_kind, k_count_groups, dim3((sgroups + 3) / 4), dim3(kBlock), (const uint64_t *)cur.words.ptr, nwords, sgroups, cur.groupcnt.ptr);
+        const dim3 cgrid((sgroups + 3) / 4), cblock(kBlock);
+        if (rank_kind >= 0) VC_DLAUNCH(rank_kind, k_count_groups, cgrid, cblock, (const uint64_t *)cur.words.ptr, nwords, sgroups, cur.groupcnt.ptr);
+        else hipLaunchKernelGGL(k_count_groups, cgrid, cblock, 0, ctx->stream, (const uint64_t *)cur.words.ptr, nwords, sgroups, cur.groupcnt.ptr);
     }
     VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_woff, ctx->h_res + 2, rank_kind));
-    const dim3 ogrid((uint32_t)((S0 + kMergeBlock - 1) / kMergeBlock));
-    if (changed && S0) VC_DLAUNCH(merge_kind, k_merge_old, ogrid, dim3(kMergeBlock), p, (const uint64_t *)cur.records.ptr, S0, nwords);
+    const dim3 ogrid((uint32_t)((S0 + kMergeBlock - 1) / kMergeBlock)), oblock(kMergeBlock);
+    if (changed && S0) {
+        if (merge_kind >= 0) VC_DLAUNCH(merge_kind, k_merge_old, ogrid, oblock, p, (const uint64_t *)cur.records.ptr, S0, nwords);
+        else hipLaunchKernelGGL(k_merge_old, ogrid, oblock, 0, ctx->stream, p, (const uint64_t *)cur.records.ptr, S0, nwords);
+    }
     return VC_OK;
 }
 
@@ -3416,6 +3442,310 @@ int vc_temporal_reset(vc_ctx *ctx)
     if (!ctx) return VC_ERR_ARG;
     ctx->temporal.pushes = 0;
     ctx->temporal.stamp = kNever;
+    return VC_OK;
+}
+
+// ---- set algebra on hulls: kept hulls, combine, compare (vc_setops.h; contract in include/voxcarve.h) ----
+// The refusals of the calls that name a register; `filled`: the register must hold a hull.
+static int kept_refusals(vc_ctx *ctx, const char *what, uint32_t reg, bool filled)
+{
+    if (reg >= VC_HULL_REGISTERS) return fail(ctx, VC_ERR_ARG, "%s: register %u, there are %u", what, reg, (unsigned)VC_HULL_REGISTERS);
+    if (filled && !ctx->setops.reg[reg].used) return fail(ctx, VC_ERR_ARG, "%s: register %u is empty", what, reg);
+    return VC_OK;
+}
+
+static dim3 setop_pairs(uint64_t npad) { return dim3((uint32_t)((npad / 2 + kSetopBlock - 1) / kSetopBlock)); }
+
+// Queues count and check of staged occupancy words: ctr[0] = their voxels, ctr[1] += 1 per word with a bit at or beyond n.
+static int kept_count(vc_ctx *ctx, const uint64_t *words, uint64_t nwords, uint64_t n)
+{
+    hipLaunchKernelGGL(k_kept_bits, dim3((uint32_t)((nwords + kSetopBlock - 1) / kSetopBlock)), dim3(kSetopBlock), 0, ctx->stream, words, nwords, n,
+                       ctx->setops.ctr.ptr);
+    VC_HIP(ctx, hipGetLastError());
+    return VC_OK;
+}
+
+int vc_hull_keep(vc_ctx *ctx, uint32_t reg)
+{
+    if (!ctx) return VC_ERR_ARG;
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_keep", "keep", "hull registers", pass));
+    VC_TRY(kept_refusals(ctx, "vc_hull_keep", reg, false));
+    VC_TRY(merge_refuse_index(ctx, "vc_hull_keep", pass.n));
+    StepBuf &cur = *pass.cur;
+    const uint64_t n = pass.n, nwords = pass.nwords, npad = (nwords + 1) & ~1ull, S = pass.S;
+    if (!n || cur.words.cap < npad) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_keep: the result's %llu occupancy words are not padded to %llu",
+                                                (unsigned long long)cur.words.cap, (unsigned long long)npad);
+    vc_ctx::Setops &X = ctx->setops;
+    VC_TRY(pass_begin(ctx));
+    vc_ctx::Kept k;                              // built beside the register, which stays as it is until the copy is whole
+    VC_TRY(ensure(ctx, k.words, (size_t)npad));
+    VC_TRY(ensure(ctx, k.rec, (size_t)S));
+    VC_TRY(ensure(ctx, X.ctr, 8));
+    VC_HIP(ctx, ensure_pinned(X.h, 16));
+    VC_TRY(pass_start(ctx, pass, kWordsAlways));
+    // R = the result's valid bits, pad included, by the combine's own kernel (a = b = the result's words, COPY)
+    SetopParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.a = sp.b = cur.words.ptr; sp.stage = k.words.ptr; sp.ctr = X.ctr.ptr;
+    sp.nwords = nwords; sp.n = n; sp.op = kSetopCopy;
+    VC_HIP(ctx, hipMemsetAsync(X.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_setop_words, setop_pairs(npad), dim3(kSetopBlock), 0, ctx->stream, sp);
+    VC_HIP(ctx, hipGetLastError());
+    if (S) VC_HIP(ctx, hipMemcpyAsync(k.rec.ptr, cur.records.ptr, (size_t)S * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(X.h.ptr, X.ctr.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_TRY(pass_end(ctx, pass, nullptr));
+    if (X.h[0] != S) return fail(ctx, VC_ERR_HIP, "vc_hull_keep: the occupancy holds %llu voxels, the result %llu records", (unsigned long long)X.h[0],
+                                 (unsigned long long)S);
+    k.count = S; k.used = true; k.has_rec = true;
+    X.reg[reg] = std::move(k);
+    return VC_OK;
+}
+
+int vc_hull_upload(vc_ctx *ctx, uint32_t reg, const uint8_t *bits, const uint64_t *records, uint64_t n_records)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
+    if (!ctx->have_grid) return fail(ctx, VC_ERR_ARG, "vc_hull_upload: no grid");
+    if (ctx->z0 != 0 || ctx->z1 != ctx->nz)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_upload: the slab [%u,%u) is narrower than the grid's %u layers", ctx->z0, ctx->z1, ctx->nz);
+    VC_TRY(kept_refusals(ctx, "vc_hull_upload", reg, false));
+    if ((bits != nullptr) == (records != nullptr)) return fail(ctx, VC_ERR_ARG, "vc_hull_upload: exactly one of bits and records must be given");
+    if (bits && n_records) return fail(ctx, VC_ERR_ARG, "vc_hull_upload: n_records = %llu with bits", (unsigned long long)n_records);
+    const uint64_t n = ctx->n_voxels(), nwords = (n + 63) / 64, npad = (nwords + 1) & ~1ull;
+    if (!n) return fail(ctx, VC_ERR_ARG, "vc_hull_upload: the grid has no voxels");
+    VC_TRY(merge_refuse_index(ctx, "vc_hull_upload", n));
+    if (n_records > n) return fail(ctx, VC_ERR_ARG, "vc_hull_upload: %llu records in a grid of %llu voxels", (unsigned long long)n_records, (unsigned long long)n);
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    vc_ctx::Setops &X = ctx->setops;
+    vc_ctx::Kept k;                              // the hull is built here and swapped in only when it is valid
+    VC_TRY(ensure(ctx, k.words, (size_t)npad));
+    if (records) VC_TRY(ensure(ctx, k.rec, (size_t)n_records));
+    VC_TRY(ensure(ctx, X.ctr, 8));
+    VC_HIP(ctx, ensure_pinned(X.h, 16));
+    VC_HIP(ctx, hipMemsetAsync(X.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(k.words.ptr, 0, (size_t)npad * sizeof(uint64_t), ctx->stream));
+    if (bits) {
+        VC_HIP(ctx, hipMemcpyAsync(k.words.ptr, bits, (size_t)nwords * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    } else if (n_records) {
+        VC_HIP(ctx, hipMemcpyAsync(k.rec.ptr, records, (size_t)n_records * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_kept_records, dim3((uint32_t)((n_records + kSetopBlock - 1) / kSetopBlock)), dim3(kSetopBlock), 0, ctx->stream,
+                           (const uint64_t *)k.rec.ptr, n_records, nwords, n, reinterpret_cast<unsigned long long *>(k.words.ptr), X.ctr.ptr);
+        VC_HIP(ctx, hipGetLastError());
+    }
+    VC_TRY(kept_count(ctx, k.words.ptr, nwords, n));
+    VC_HIP(ctx, hipMemcpyAsync(X.h.ptr, X.ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (X.h[1] && bits)
+        return fail(ctx, VC_ERR_ARG, "vc_hull_upload: %llu words hold a bit at or beyond the grid's %llu voxels", (unsigned long long)X.h[1],
+                    (unsigned long long)n);
+    if (X.h[1])
+        return fail(ctx, VC_ERR_ARG, "vc_hull_upload: %llu records are out of order, duplicates or at or beyond the grid's %llu voxels",
+                    (unsigned long long)X.h[1], (unsigned long long)n);
+    if (records && X.h[0] != n_records)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_upload: %llu bits from %llu records", (unsigned long long)X.h[0], (unsigned long long)n_records);
+    k.count = X.h[0]; k.used = true; k.has_rec = records != nullptr;
+    X.reg[reg] = std::move(k);
+    return VC_OK;
+}
+
+int vc_hull_release(vc_ctx *ctx, uint32_t reg)
+{
+    if (!ctx) return VC_ERR_ARG;
+    VC_TRY(kept_refusals(ctx, "vc_hull_release", reg, false));
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->setops.reg[reg] = vc_ctx::Kept{};
+    return VC_OK;
+}
+
+int vc_fetch_kept(vc_ctx *ctx, uint32_t reg, uint8_t *bits, uint64_t *records, uint64_t *count, uint32_t *has_records)
+{
+    if (!ctx) return VC_ERR_ARG;
+    VC_TRY(kept_refusals(ctx, "vc_fetch_kept", reg, true));
+    const vc_ctx::Kept &k = ctx->setops.reg[reg];
+    if (records && !k.has_rec) return fail(ctx, VC_ERR_ARG, "vc_fetch_kept: register %u holds no records", reg);
+    if (count) *count = k.count;
+    if (has_records) *has_records = k.has_rec ? 1u : 0u;
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t nwords = (ctx->n_voxels() + 63) / 64;
+    if (bits && nwords) VC_HIP(ctx, hipMemcpy(bits, k.words.ptr, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (records && k.count) VC_HIP(ctx, hipMemcpy(records, k.rec.ptr, (size_t)k.count * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_hull_combine(vc_ctx *ctx, uint32_t op, uint32_t reg, uint32_t flags, vc_setop_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_combine: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_combine", "combine", "set operations", pass));
+    if (op > VC_SETOP_XOR) return fail(ctx, VC_ERR_ARG, "vc_hull_combine: unknown op %u (VC_SETOP_COPY .. VC_SETOP_XOR)", op);
+    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_combine: flags must be 0 (got %u)", flags);
+    VC_TRY(kept_refusals(ctx, "vc_hull_combine", reg, true));
+    StepBuf &cur = *pass.cur;
+    const uint64_t n = pass.n, nwords = pass.nwords, npad = (nwords + 1) & ~1ull;
+    VC_TRY(merge_refuse_index(ctx, "vc_hull_combine", n));
+    vc_ctx::Setops &X = ctx->setops;
+    const vc_ctx::Kept &B = X.reg[reg];
+    const bool colours = !B.has_rec && (op == VC_SETOP_COPY || op == VC_SETOP_OR || op == VC_SETOP_XOR);   // fresh records may be made
+    if (colours) VC_TRY(merge_refuse_slot(ctx, "vc_hull_combine", cur));
+    if (!n || cur.words.cap < npad || B.words.cap < npad)
+        return fail(ctx, VC_ERR_INTERNAL, "vc_hull_combine: %llu and %llu occupancy words are not padded to %llu", (unsigned long long)cur.words.cap,
+                    (unsigned long long)B.words.cap, (unsigned long long)npad);
+    VC_TRY(pass_begin(ctx));
+    VC_TRY(ensure(ctx, X.stage, (size_t)npad));
+    VC_TRY(ensure(ctx, X.ctr, 8));
+    VC_HIP(ctx, ensure_pinned(X.h, 16));
+    const uint64_t S0 = pass.S;
+    VC_TRY(pass_start(ctx, pass, kWordsAlways));
+    SetopParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.a = cur.words.ptr; sp.b = B.words.ptr; sp.stage = X.stage.ptr; sp.ctr = X.ctr.ptr;
+    sp.nwords = nwords; sp.n = n; sp.op = op;
+    VC_HIP(ctx, hipMemsetAsync(X.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_setop_words, setop_pairs(npad), dim3(kSetopBlock), 0, ctx->stream, sp);
+    VC_HIP(ctx, hipGetLastError());
+    // the read-back in the middle: |R| sizes the records
+    VC_HIP(ctx, hipMemcpyAsync(X.h.ptr, X.ctr.ptr, kSetopCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t S1 = X.h[0], common = X.h[1], added = X.h[2], removed = X.h[3];
+    if (S1 > n || removed > S0 || S0 + added - removed != S1 || common > S0 || common > B.count)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_combine: %llu in the result, %llu common, %llu added to and %llu removed from %llu survivors, in a grid of %llu voxels",
+                    (unsigned long long)S1, (unsigned long long)common, (unsigned long long)added, (unsigned long long)removed, (unsigned long long)S0,
+                    (unsigned long long)n);
+    const bool restore = op == VC_SETOP_COPY && B.has_rec;      // every record becomes B's: their bytes may differ where the sets do not
+    const bool changed = added || removed || restore;
+    // every buffer of the hand-over before anything is committed: a failure leaves result and registers
+    VC_TRY(ensure(ctx, X.added, (size_t)S1));
+    MergeParams g;
+    VC_TRY(merge_sized(ctx, cur, nwords, S1, changed, X.added.ptr, g));
+    // committed from here on
+    X.stamp = kNever;
+    VC_HIP(ctx, hipMemsetAsync(X.added.ptr, 0, std::max<size_t>((size_t)S1, 1), ctx->stream));
+    if (changed) {
+        result_changed(ctx);
+        // R into the result's words; where voxels were added the staging buffer takes A's words for the kernels that ask which are new
+        if (added) hipLaunchKernelGGL(k_setop_commit, setop_pairs(npad), dim3(kSetopBlock), 0, ctx->stream, cur.words.ptr, X.stage.ptr, nwords, n);
+        else VC_HIP(ctx, hipMemcpyAsync(cur.words.ptr, X.stage.ptr, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(merge_ranked(ctx, cur, g, nwords, restore ? 0 : S0, true, -1, -1));   // (a restore moves no record of A)
+        const uint64_t *olda = added ? X.stage.ptr : nullptr;
+        if (B.has_rec && B.count && (added || restore))
+            hipLaunchKernelGGL(k_merge_from, dim3((uint32_t)((B.count + kMergeBlock - 1) / kMergeBlock)), dim3(kMergeBlock), 0, ctx->stream, g,
+                               (const uint64_t *)B.rec.ptr, B.count, nwords, olda, restore ? 1 : 0);
+        else if (!B.has_rec && added)
+            hipLaunchKernelGGL(k_setop_fresh, dim3((uint32_t)((nwords + kMergeBlock - 1) / kMergeBlock)), dim3(kMergeBlock), 0, ctx->stream, g, olda,
+                               nwords, n);
+        VC_HIP(ctx, hipGetLastError());
+        VC_TRY(records_handed_over(ctx, cur, word_groups(nwords)));
+    }
+    VC_TRY(pass_end(ctx, pass, &stats->setop_ms));
+    if (changed) {
+        ctx->survivors = cur.survivors = S1;
+        VC_TRY(merge_counted(ctx, "vc_hull_combine", S1, "were combined"));
+    }
+    stats->survivors_before = S0; stats->other = B.count; stats->common = common;
+    stats->survivors_after = S1; stats->added = added; stats->removed = removed;
+    X.stamp = ctx->result_gen;
+    X.n = S1;
+    return VC_OK;
+}
+
+int vc_fetch_combined(vc_ctx *ctx, uint8_t *added)
+{
+    if (!ctx || !added) return VC_ERR_ARG;
+    if (!ctx->carved || !ctx->current(ctx->setops.stamp)) return fail(ctx, VC_ERR_ARG, "no added flags: call vc_hull_combine on the current carve result");
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->setops.n) VC_HIP(ctx, hipMemcpy(added, ctx->setops.added.ptr, (size_t)ctx->setops.n, hipMemcpyDeviceToHost));
+    return VC_OK;
+}
+
+int vc_hull_compare(vc_ctx *ctx, uint32_t reg, uint32_t flags, vc_compare_stats_t *stats)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_compare: stats must not be NULL");
+    memset(stats, 0, sizeof *stats);
+    Pass pass;
+    VC_TRY(pass_open(ctx, "vc_hull_compare", "compare", "comparison", pass));
+    if (flags & ~VC_COMPARE_DISTANCE) return fail(ctx, VC_ERR_ARG, "vc_hull_compare: unknown flags %u (VC_COMPARE_DISTANCE)", flags);
+    VC_TRY(kept_refusals(ctx, "vc_hull_compare", reg, true));
+    const bool distance = (flags & VC_COMPARE_DISTANCE) != 0;
+    uint64_t q[3] = {0, 0, 0};
+    if (distance) VC_TRY(dist_metric(ctx, "vc_hull_compare", q));
+    StepBuf &cur = *pass.cur;
+    const uint64_t n = pass.n, nwords = pass.nwords, npad = (nwords + 1) & ~1ull;
+    VC_TRY(merge_refuse_index(ctx, "vc_hull_compare", n));
+    vc_ctx::Setops &X = ctx->setops;
+    const vc_ctx::Kept &B = X.reg[reg];
+    if (!n || cur.words.cap < npad || B.words.cap < npad)
+        return fail(ctx, VC_ERR_INTERNAL, "vc_hull_compare: %llu and %llu occupancy words are not padded to %llu", (unsigned long long)cur.words.cap,
+                    (unsigned long long)B.words.cap, (unsigned long long)npad);
+    VC_TRY(pass_begin(ctx));
+    VC_TRY(ensure(ctx, X.ctr, 8));
+    VC_TRY(ensure(ctx, X.box, 12));
+    VC_TRY(ensure(ctx, X.acc, 4));
+    VC_HIP(ctx, ensure_pinned(X.h, 16));
+    VC_TRY(pass_start(ctx, pass, kWordsAlways));
+    uint32_t *hb = reinterpret_cast<uint32_t *>(X.h.ptr + 4);    // h[0..2]: the counts; h[4..9]: the boxes; h[10..13]: the maxima
+    for (int k = 0; k < 12; ++k) hb[k] = (k % 6) < 3 ? 0xffffffffu : 0u;
+    VC_HIP(ctx, hipMemcpyAsync(X.box.ptr, hb, 12 * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    VC_HIP(ctx, hipMemsetAsync(X.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    CompareParams cp;
+    memset(&cp, 0, sizeof cp);
+    cp.a = cur.words.ptr; cp.b = B.words.ptr; cp.ctr = X.ctr.ptr; cp.box = X.box.ptr;
+    cp.nwords = nwords; cp.n = n; cp.nx = ctx->nx; cp.ny = ctx->ny; cp.nz = ctx->nz;
+    hipLaunchKernelGGL(k_compare_words, setop_pairs(npad), dim3(kSetopBlock), 0, ctx->stream, cp);
+    VC_HIP(ctx, hipGetLastError());
+    VC_HIP(ctx, hipMemcpyAsync(X.h.ptr, X.ctr.ptr, kCompareCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipMemcpyAsync(hb, X.box.ptr, 12 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t common = X.h[0], only_a = X.h[1], only_b = X.h[2];
+    if (common + only_a != pass.S || common + only_b != B.count)
+        return fail(ctx, VC_ERR_HIP, "vc_hull_compare: %llu common, %llu and %llu one-sided voxels of hulls of %llu and %llu", (unsigned long long)common,
+                    (unsigned long long)only_a, (unsigned long long)only_b, (unsigned long long)pass.S, (unsigned long long)B.count);
+    const uint32_t dims[3] = {ctx->nx, ctx->ny, ctx->nz};
+    uint32_t diff[6], uni[6];
+    memcpy(diff, hb, sizeof diff);
+    memcpy(uni, hb + 6, sizeof uni);
+    if (only_a + only_b)
+        for (int a = 0; a < 3; ++a)
+            if (diff[a] > diff[3 + a] || diff[3 + a] >= dims[a] || uni[a] > diff[a] || uni[3 + a] < diff[3 + a] || uni[3 + a] >= dims[a])
+                return fail(ctx, VC_ERR_HIP, "vc_hull_compare: the difference's box [%u, %u] in the union's [%u, %u] on axis %c of %u cells", diff[a],
+                            diff[3 + a], uni[a], uni[3 + a], "xyz"[a], dims[a]);
+    uint64_t *hm = X.h.ptr + 10;
+    hm[0] = hm[2] = 0; hm[1] = hm[3] = 0xffffffffull;
+    if (distance && (only_a || only_b)) {
+        // two transforms over the union's index box, grown by a cell per side and clipped to the grid: every site of either hull lies
+        // inside it, so the minima are exact; sites = B for the voxels of A \ B, then sites = A for those of B \ A
+        DistBox bx;
+        memset(&bx, 0, sizeof bx);
+        bx.nx = ctx->nx; bx.ny = ctx->ny; bx.nz = ctx->nz;
+        for (int a = 0; a < 3; ++a) {
+            const int32_t lo = uni[a] ? (int32_t)uni[a] - 1 : 0, hi = std::min<int32_t>((int32_t)uni[3 + a] + 1, (int32_t)dims[a] - 1);
+            bx.o[a] = lo;
+            bx.b[a] = (uint32_t)(hi - lo + 1);
+        }
+        VC_TRY(dist_ensure(ctx, X.field, bx));
+        VC_HIP(ctx, hipMemcpyAsync(X.acc.ptr, hm, 4 * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        const dim3 wgrid((uint32_t)((nwords + kSetopBlock - 1) / kSetopBlock)), block(kSetopBlock);
+        for (int dir = 0; dir < 2; ++dir) {
+            if (!(dir ? only_b : only_a)) continue;
+            const uint64_t *x = dir ? B.words.ptr : cur.words.ptr, *y = dir ? cur.words.ptr : B.words.ptr;
+            VC_TRY(dist_transform(ctx, bx, kDistSiteOn, y, X.field.ptr, 0, q));
+            hipLaunchKernelGGL(k_compare_far<false>, wgrid, block, 0, ctx->stream, bx, (const uint64_t *)X.field.ptr, x, y, nwords, n, X.acc.ptr + 2 * dir);
+            hipLaunchKernelGGL(k_compare_far<true>, wgrid, block, 0, ctx->stream, bx, (const uint64_t *)X.field.ptr, x, y, nwords, n, X.acc.ptr + 2 * dir);
+            VC_HIP(ctx, hipGetLastError());
+        }
+        VC_TRY(pass_stop(ctx, pass));
+        VC_HIP(ctx, hipMemcpyAsync(hm, X.acc.ptr, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    VC_TRY(pass_end(ctx, pass, &stats->compare_ms));
+    stats->a = pass.S; stats->b = B.count; stats->common = common; stats->only_a = only_a; stats->only_b = only_b;
+    for (int a = 0; a < 3; ++a) { stats->diff_lo[a] = diff[a]; stats->diff_hi[a] = diff[3 + a]; stats->q[a] = q[a]; }
+    stats->h2_ab = hm[0]; stats->arg_ab = (uint32_t)hm[1];
+    stats->h2_ba = hm[2]; stats->arg_ba = (uint32_t)hm[3];
     return VC_OK;
 }
 

@@ -675,6 +675,113 @@ class CarveEngine:
         """Forgets the ring of hulls and the previous output: the next temporal_filter returns its hull as it is."""
         self._check(self._L.vc_temporal_reset(self._ctx), "vc_temporal_reset")
 
+    # -- set algebra on hulls (vc_hull_keep / upload / combine / compare): a second operand for the current result -----------------
+    SETOPS = {"copy": _lib.VC_SETOP_COPY, "and": _lib.VC_SETOP_AND, "or": _lib.VC_SETOP_OR, "andnot": _lib.VC_SETOP_ANDNOT,
+              "xor": _lib.VC_SETOP_XOR}
+
+    def keep_hull(self, reg=0):
+        """Register `reg` (0..3) on the device becomes a copy of the current carve result, records included.  Registers survive
+        carves and passes; set_grid / set_slab / set_cameras empty them."""
+        self._check(self._L.vc_hull_keep(self._ctx, int(reg)), "vc_hull_keep")
+
+    def upload_hull(self, hull, reg=0):
+        """Loads a hull of the current grid into register `reg`: a bool array [n], ascending uint32 indices, or uint64 records
+        (voxcarve.hullio.as_operand; only records bring colours).  The device validates it once more; a refused upload leaves
+        the register as it was.  Needs a grid, not a carve result."""
+        from . import hullio
+        if self.grid is None:
+            raise _lib.VoxcarveError("upload_hull: no grid")
+        kind, data = hullio.as_operand(hull, self.n_voxels)
+        if kind == "bits":
+            rc = self._L.vc_hull_upload(self._ctx, int(reg), _ptr(data, ctypes.c_uint8), None, 0)
+        else:
+            buf = data if data.size else np.zeros(1, dtype=np.uint64)        # (n_records = 0 still names a buffer)
+            rc = self._L.vc_hull_upload(self._ctx, int(reg), None, _ptr(buf, ctypes.c_uint64), int(data.size))
+        self._check(rc, "vc_hull_upload")
+
+    def release_hull(self, reg):
+        """Empties register `reg` and frees its memory."""
+        self._check(self._L.vc_hull_release(self._ctx, int(reg)), "vc_hull_release")
+
+    def fetch_kept(self, reg=0):
+        """Register `reg` as a dict: count, has_records, words (uint64 [ceil(n / 64)], laid out as fetch_occupancy's) and records
+        (uint64 [count], or None when the register has none); fails for an empty register."""
+        count, has = ctypes.c_uint64(0), ctypes.c_uint32(0)
+        self._check(self._L.vc_fetch_kept(self._ctx, int(reg), None, None, ctypes.byref(count), ctypes.byref(has)), "vc_fetch_kept")
+        words = np.empty((self.n_voxels + 63) // 64, dtype=np.uint64)
+        records = np.empty(count.value, dtype=np.uint64) if has.value else None
+        self._check(self._L.vc_fetch_kept(self._ctx, int(reg), words.ctypes.data_as(_lib.c_u8p),
+                                          _ptr(records, ctypes.c_uint64) if has.value and count.value else None, None, None), "vc_fetch_kept")
+        return {"count": int(count.value), "has_records": bool(has.value), "words": words, "records": records}
+
+    def combine_hull(self, op, reg=0):
+        """Replaces the current carve result A by a set operation with the hull B of register `reg`: op = "copy" (B), "and"
+        (A & B: clip), "or" (union), "andnot" (A \\ B: subtract), "xor" (what differs).  Records of A that stay keep their bytes;
+        a voxel that was not in A takes B's record when the register has records and is coloured from the colour camera as
+        close_hull colours otherwise; "copy" from a register with records restores B's records verbatim (contract:
+        include/voxcarve.h).  Returns the stats as a dict: survivors_before, other, common, survivors_after, added, removed,
+        setop_ms."""
+        if op not in self.SETOPS:
+            raise ValueError("op %r, expected one of %s" % (op, sorted(self.SETOPS)))
+        st = _lib.VcSetopStats()
+        self._check(self._L.vc_hull_combine(self._ctx, self.SETOPS[op], int(reg), 0, ctypes.byref(st)), "vc_hull_combine")
+        self.count = int(st.survivors_after)
+        out = {name: int(getattr(st, name)) for name, _ in _lib.VcSetopStats._fields_ if name != "setop_ms"}
+        out["setop_ms"] = float(st.setop_ms)
+        return out
+
+    def fetch_combined(self):
+        """u8 [S] in record order: 1 where the last combine_hull brought the voxel in (fails once a carve or a pass that changes
+        the survivors has run since)."""
+        out = np.empty(self.count, dtype=np.uint8)
+        self._check(self._L.vc_fetch_combined(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_combined")
+        return out
+
+    def compare_hull(self, reg=0, distance=False):
+        """Compares the current carve result A with the hull B of register `reg` and changes nothing.  Returns a dict: a, b,
+        common, only_a, only_b, diff_lo, diff_hi (the inclusive index box of the symmetric difference; UINT32_MAX and 0 when
+        there is none), compare_ms; with distance=True also h2_ab, h2_ba (directed Hausdorff distances squared, um^2), arg_ab,
+        arg_ba (the voxels that attain them) and q.  Derived on the host: iou = common / |A | B| and dice = 2 common / (a + b)
+        (None when both hulls are empty), hausdorff_mm = sqrt(max(h2_ab, h2_ba)) / 1000 (None without distance and when
+        either hull is empty)."""
+        st = _lib.VcCompareStats()
+        self._check(self._L.vc_hull_compare(self._ctx, int(reg), _lib.VC_COMPARE_DISTANCE if distance else 0, ctypes.byref(st)), "vc_hull_compare")
+        out = {name: int(getattr(st, name)) for name in ("a", "b", "common", "only_a", "only_b")}
+        out["diff_lo"] = tuple(int(v) for v in st.diff_lo)
+        out["diff_hi"] = tuple(int(v) for v in st.diff_hi)
+        out["compare_ms"] = float(st.compare_ms)
+        union = out["common"] + out["only_a"] + out["only_b"]
+        out["iou"] = out["common"] / union if union else None
+        out["dice"] = 2 * out["common"] / (out["a"] + out["b"]) if union else None
+        out["hausdorff_mm"] = None
+        if distance:
+            out.update(h2_ab=int(st.h2_ab), h2_ba=int(st.h2_ba), arg_ab=int(st.arg_ab), arg_ba=int(st.arg_ba), q=tuple(int(v) for v in st.q))
+            worst = max(out["h2_ab"], out["h2_ba"])
+            if union and worst != (1 << 64) - 1:
+                out["hausdorff_mm"] = float(np.sqrt(float(worst))) / 1000.0
+        return out
+
+    def save_hull(self, path):
+        """Writes the current carve result (grid, bounds, records) to `path` as an .npz (voxcarve.hullio.save)."""
+        from . import hullio
+        hullio.save(path, self.grid, self.bounds, self.fetch_records())
+
+    def load_hull(self, path, reg=0):
+        """Loads a file of save_hull into register `reg`; ValueError when its grid or bounds are not this engine's."""
+        from . import hullio
+        grid, bounds, records = hullio.load(path)
+        if self.grid is None or tuple(grid) != tuple(self.grid):
+            raise ValueError("%s holds a hull of grid %s, the engine's is %s" % (path, grid, self.grid))
+        if tuple(bounds) != tuple(self.bounds):
+            raise ValueError("%s holds a hull of bounds %s, the engine's are %s" % (path, bounds, self.bounds))
+        self.upload_hull(records, reg)
+
+    def set_hull(self, hull, reg=0):
+        """upload_hull(hull, reg), then combine_hull("copy", reg): the hull becomes the current result (needs a carve result to
+        replace; a carve of empty masks will do).  Returns combine_hull's stats."""
+        self.upload_hull(hull, reg)
+        return self.combine_hull("copy", reg)
+
     # -- ray-cast images of the current result (vc_render) --------------------------------------------------------------------------
     def render(self, views, H, W, shade=None, background=(0, 0, 0)):
         """Ray-casts the current carve result (after color_visible / photo_carve / filter_components, as fetch sees it) from each
