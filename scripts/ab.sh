@@ -1,7 +1,7 @@
 # Same-device A/B of two library builds (devices of the pool differ by +-5 %, more than most changes are worth):
 #   bash scripts/ab.sh build [rev]     builds ab_build/old (rev, default HEAD) and ab_build/new (working tree); here, no GPU
-#   bash scripts/ab.sh run <script + args>   on the GPU box: old, new, old, new, ... three times each
-set -e
+#   bash scripts/ab.sh run <script + args>   on the GPU box: old, new, old, new, ... three times each, ending at the first run that fails
+set -e -o pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=voxel-based-3d-reconstruction_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -I/opt/rocm/include"
@@ -20,7 +20,9 @@ else
   shift
   for i in 1 2 3; do
     for v in old new; do
-      echo -n "$v: "; VOXCARVE_LIB=$ROOT/ab_build/$v/libvoxcarve.so timeout -k 10 300 python "$@" | tail -1
+      # (each run under its own time limit; pipefail: the run's status, not tail's -- nothing more is started behind a failure)
+      echo -n "$v: "
+      VOXCARVE_LIB=$ROOT/ab_build/$v/libvoxcarve.so timeout -k 10 300 python "$@" | tail -1 || { rc=$?; echo "$v run $i: exit $rc"; exit $rc; }
     done
   done
 fi

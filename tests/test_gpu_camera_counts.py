@@ -43,7 +43,8 @@ def _constants():
     """The launch code's LDS constants, read from the sources (so that the rows follow them if they move)."""
     src = open(os.path.join(HIP, "voxcarve.hip")).read() + open(os.path.join(HIP, "vc_kernels.h")).read()
     val = {}
-    for name in ("kMaxCameras", "kHdrShift", "kGridHeader", "kWideBlock", "kMaxFirstLds", "kWideGridBytes", "kMaxWideLds"):
+    for name in ("kMaxCameras", "kHdrShift", "kGridHeader", "kWideBlock", "kMaxFirstLds", "kWideGridBytes", "kMaxWideLds",
+                 "kBusyListMinGroups"):
         expr = re.search(r"constexpr \w+ %s = ([^;]+);" % name, src).group(1)
         assert re.fullmatch(r"[\w\s*+]+", expr), (name, expr)
         val[name] = eval(expr, {"__builtins__": {}}, dict(val))
@@ -160,14 +161,39 @@ def brick_shape(grid):
     return ny in (256, 512, 1024, 2048, 4096) and nx % 4 == 0 and (ny >= 1024 or nx % (4096 // ny) == 0)
 
 
-def brick_path(grid, opts, mode):
-    """Whether vc_carve takes the brick pipeline for these options (voxcarve.hip: `bricks` of the carve step)."""
+# the kinds of a step's launches that route() predicts: the carve stage, the counting pass and the scans (the preparation kinds
+# depend on what the frame set has been through, k_emit on nothing)
+STEP_KINDS = frozenset(("k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble", "one_launch_carve", "k_cull", "k_count_groups",
+                        "k_scan_groups", "k_finish_scan"))
+
+
+def route(grid, C, H, W, mode, mv, viewmask, opts):
+    """The kinds of STEP_KINDS one vc_carve launches under these options (voxcarve.hip: plan_route / settle_route, the step's
+    route).  load() has built the table under the default lut_tile before a row sets its options, so on a grid of tile shape the
+    tile-ordered table, the tile boxes and the brick boxes exist whatever the row says."""
     o = {**DEFAULTS, **opts}
-    if not brick_shape(grid) or o["force_generic"] or not o["bricks"] or not o["cull"]:
-        return False
-    if mode == "lut":
-        return bool(o["lut_hier"] and o["lut_tile"])
-    return bool(o["fused_hier"] and o["fused_tile"] and o["fused_boxes"])
+    nx, ny, nz = grid
+    lut = mode == "lut"
+    tiles = nx % 4 == 0 and ny % 64 == 0
+    # one thread per voxel: thresholds below C, view masks, force_generic, masks larger than k_lut_first's LDS
+    fast = mv == C and not viewmask and not o["force_generic"] and \
+        not (lut and not o["lut_hier"] and (H * W + 31) // 32 * 4 > K["kMaxFirstLds"])
+    if lut:
+        tile_words = fast and tiles and o["lut_hier"] and o["lut_tile"]
+    else:
+        tile_words = fast and tiles and o["fused_hier"] and o["fused_tile"] and o["fused_boxes"]   # (the boxes' owner: cull and bricks)
+    bricks = bool(tile_words and brick_shape(grid) and o["bricks"] and o["cull"])
+    counted = fast and (lut or (ny % 64 == 0 and o["fused_hier"]))      # the kernel leaves its group counts
+    kinds = {"k_scan_groups"}
+    kinds |= {"k_cull_bricks", "k_brick_words", "k_voxel_words", "k_assemble"} if bricks else {"one_launch_carve"}
+    if tile_words and not bricks and o["cull"]:
+        kinds.add("k_cull")
+    if not counted:
+        kinds.add("k_count_groups")
+    groups = -(-nx * ny * nz // 8192) * 2
+    if o["emit_lanes"] and (o["emit_busy"] == 2 or (o["emit_busy"] == 1 and groups >= K["kBusyListMinGroups"])):
+        kinds.add("k_finish_scan")                                       # the busy list
+    return kinds
 
 
 class Options:
@@ -187,10 +213,10 @@ class Options:
         self.eng.touch_masks(0)
 
 
-def check(eng, want, grid, C, mv, cc, tag, opts={}, viewmask=False, touch=False, modes=("lut", "fused")):
-    """One carve per mode: the oracle's records, occupancy (and camera masks), on the path the row claims -- the brick pipeline
-    or a one-launch kernel, and among those the one-thread-per-voxel kernel exactly where vc_carve falls back to it (it alone,
-    with the chunked table-free kernel, needs k_count_groups).  Returns the kernels each mode launched."""
+def check(eng, want, grid, C, mv, cc, tag, opts={}, viewmask=False, touch=False, modes=("lut", "fused"), lists=True):
+    """One carve per mode: the oracle's records, occupancy (and camera masks), by exactly the step kinds route() names -- the
+    brick pipeline or a one-launch kernel, k_cull in front of it, k_count_groups behind the kernels that leave no group counts,
+    the busy list's k_finish_scan.  lists: also what the brick level's counters say.  Returns the kernels each mode launched."""
     seen_want = ((want["viewmask"][want["idx"]] >> cc) & 1).astype(bool)
     occ = np.zeros(grid[0] * grid[1] * grid[2], bool)
     occ[want["idx"]] = True
@@ -198,10 +224,7 @@ def check(eng, want, grid, C, mv, cc, tag, opts={}, viewmask=False, touch=False,
     H, W = eng.image_size
     launched = {}
     for mode in modes:
-        # voxcarve.hip, vc_carve: `fast` (else k_carve_generic) and `counted` (the kernel leaves its group counts)
-        fast = mv == C and not viewmask and not o["force_generic"] and \
-            not (mode == "lut" and not o["lut_hier"] and (H * W + 31) // 32 * 4 > K["kMaxFirstLds"])
-        counted = fast and (mode == "lut" or (grid[1] % 64 == 0 and o["fused_hier"]))
+        kinds = route(grid, C, H, W, mode, mv, viewmask, opts)
         if touch:
             eng.touch_masks(0)
         eng.timing(reset=True)
@@ -217,10 +240,8 @@ def check(eng, want, grid, C, mv, cc, tag, opts={}, viewmask=False, touch=False,
         if viewmask:
             assert np.array_equal(eng.fetch_viewmask(), want["viewmask"]), t
         launched[mode] = ks
-        assert ("k_count_groups" in ks) == (not counted), (t, fast, sorted(ks))
-        bricks = fast and brick_path(grid, opts, mode)
-        if bricks:
-            assert "k_brick_words" in ks and "one_launch_carve" not in ks, (t, sorted(ks))
+        assert set(ks) & STEP_KINDS == kinds, (t, sorted(ks), sorted(kinds))
+        if "k_brick_words" in kinds and lists:
             dc = eng.debug_counters()
             assert dc["words_undecided"] > 0, (t, dc)
             if o["dbg"] & 8192:
@@ -231,8 +252,6 @@ def check(eng, want, grid, C, mv, cc, tag, opts={}, viewmask=False, touch=False,
                 assert 0 < dc["bricks_listed"] <= dc["bricks"], (t, dc)
             # a step after one that listed nine bricks in ten lists them all without testing (launch_bricks)
             LISTS["most"] = dc["bricks_listed"] * 10 >= dc["bricks"] * 9
-        else:
-            assert "one_launch_carve" in ks and "k_brick_words" not in ks, (t, sorted(ks))
     return launched
 
 
@@ -271,6 +290,28 @@ def test_camera_count_sweep(eng, rig, C):
                 for opts in FAMILIES:
                     with Options(eng, opts):
                         check(eng, want, grid, C, mv, cc, (shape, C, opts), opts=opts)
+    assert total > 0
+
+
+ROUTE_GRIDS = ((16, 128, 12), (8, 192, 9), (5, 70, 11), (16, 256, 20))   # tile words | tile_whole == 0 (zeroed counts) | no tiles | bricks
+ROUTE_ROWS = tuple(r for k, r in enumerate(FAMILIES + ({"emit_busy": 2},)) if r not in FAMILIES[:k])
+
+
+def test_route_kinds_of_every_family(eng):
+    """Every option row on the smallest grid of every shape the step's route tells apart, both modes, at the threshold C with and
+    without view masks and at C - 1: the oracle's records, by exactly the kinds route() names."""
+    C = 4
+    cams, masks, frames = fx.random_scene(321, C=C, H=60, W=80, fg=0.55)
+    cc = 2
+    total = 0
+    for grid in ROUTE_GRIDS:
+        load(eng, grid, cams, masks, cc, frames[cc])
+        wants = {mv: oracle(grid, cams, masks, cc, frames[cc], mv) for mv in (C, C - 1)}
+        total += wants[C]["count"]
+        for opts in ROUTE_ROWS:
+            with Options(eng, opts):
+                for mv, vm in ((C, False), (C, True), (C - 1, False)):
+                    check(eng, wants[mv], grid, C, mv, cc, (grid, opts), opts=opts, viewmask=vm, lists=False)
     assert total > 0
 
 

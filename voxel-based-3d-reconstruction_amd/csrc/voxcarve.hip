@@ -167,9 +167,37 @@ void linspace(double lo, double hi, uint32_t n, std::vector<double> &out)
 
 }  // namespace
 
+// The route of one carve step: which kernels carve it, what they leave behind and what the stages behind them read.  Decided once per
+// step (plan_route, settle_route), queued by step_carve, kept with the step for everything that comes later; DESIGN.md, section 4, has
+// the table of families and conditions.  The families that stage a frame set's block grids in LDS come last (stages_grids).
+enum class Carve : uint8_t { Foot, Generic, FusedChunked, LutStream, FusedHier, LutHier, Bricks };
+enum class Table : uint8_t { None, YMajor, Tile, Color };    // Color: the colour camera's table over the whole grid (ensure_color_table)
+struct StepRoute {
+    Carve family = Carve::Generic;
+    bool lut = false, viewmask = false;   // VC_MODE_LUT (Generic and Bricks come in both modes) | VC_FLAG_VIEWMASK (Foot, Generic)
+    bool allseen = false;        // every survivor is seen by the colour camera: the threshold is C, or the footprint rule colours by the centre's pixel
+    bool tile = false;           // FusedHier, LutHier, Bricks: words of 4 x-rows x 16 y (else y-lines)
+    int boxes = 0;               // FusedHier: word boxes from float64 intervals (0), float32 intervals (1), read from ensure_boxes' (2)
+    bool pair = false, b16 = false;   // LutHier on y-lines: two cameras per round trip; else (and LutStream) 16 alive words per batch, not 8
+    bool boxed_tiles = false;    // tile words whose boxes are read: the routes the brick boxes serve (Bricks where brick_shape holds, else k_cull)
+    bool cull = false;           // k_cull runs in front of the one-launch kernel
+    bool zero_counts = false;    // waves and groups do not coincide (!tile_whole): counts by atomics into zeroed memory, every word stored
+    bool counted = false, sparse_words = false;   // the kernels leave the group counts (else k_count_groups) | and dead groups' words unwritten
+    bool grids = false, wide_grids = false;       // the frame set's block grids are wanted | sized for the brick pipeline's LDS (148 KB, else 64)
+    Table carve_table = Table::None, emit_table = Table::None;   // what the carve kernels | the record expansion look pixels up in
+    bool try_lut16 = false, lut16 = false;        // the colour camera's compact table may be tried | is what the expansion reads (ensure_lut16)
+    bool count_nz = false;       // k_assemble counts the groups' non-zero words for the packing (StepBuf::nz_valid starts from this)
+    bool busy = false;           // the scan lists the groups with survivors (k_finish_scan); expansion and packing stride over the list
+    size_t lds = 0;              // dynamic LDS of the carve kernels (stages_grids: known once the frame set is prepared)
+    // the step's events: a rank packs and exchanges its counts behind the scan | on another stream than the carve's; {scan done} is
+    // wanted | rides on k_finish_scan; {expansion begun, step done} ride on the expansion
+    bool exchange = false, xstream = false, scan_ev = false, scan_ridden = false, ride = false;
+};
+
 // One carve step's device state.  Two of them exist so that step i+1 can be enqueued before the
 // host has collected step i (vc_carve_begin / vc_carve_end): the device never idles between steps.
 struct StepBuf {
+    StepRoute route;
     DevBuf<uint64_t> words;
     DevBuf<uint32_t> groupcnt, groupoff;
     DevBuf<uint32_t> groupnz;                // non-zero words per group (brick pipeline, compact exchange: k_assemble counts them in passing)
@@ -190,17 +218,14 @@ struct StepBuf {
     bool emit_timed = false;                 // e_scan / e2 bracket the record expansion
     bool pending = false, used = false;
     EmitParams emit;                         // kept for a re-run after a records regrow
-    bool allseen = false, want_vm = false, has_first = false;
     bool no_records = false;                 // VC_FLAG_NO_RECORDS: occupancy words + count only
     bool sparse_words = false;               // words of groups with groupcnt == 0 were left unwritten
-    DevBuf<uint32_t> busyoff, busysum, busyblock, busylist;   // the groups with survivors, listed by the scan
-    bool busy = false;
-    bool lut16 = false;                      // the expansion reads the colour camera's compact table (ensure_lut16)
+    DevBuf<uint32_t> busyoff, busysum, busyblock, busylist;   // the groups with survivors, listed by the scan (route.busy)
     // compact exchange form of this step: non-zero words as {bits, global index of bit 0} pairs
     DevBuf<uint64_t> ent, mine, counts;      // pairs | {entries, survivors} of this rank | of all ranks
     Pinned<uint64_t> h_counts;               // 2 per rank
     bool counts_exchanged = false;           // vc_carve_begin already packed and all-gathered the counts
-    int mode = 0, color_cam = -1;            // what the step was run with (vc_expand_entries colours the same way)
+    int color_cam = -1;                      // what the step was run with (vc_expand_entries colours the same way; the mode: route.lut)
     uint32_t slot = 0, slot_gen = 0;         // frame set the step read, and which preparation of it
     uint32_t min_views = 1;                  // the threshold it ran with, after the clamp to >= 1 (vc_surface_mesh's point test)
     uint64_t n = 0, survivors = 0;
@@ -330,10 +355,8 @@ struct vc_ctx {
     int lut_hier = 1;                // VC_MODE_LUT: hierarchical kernel (boxes + block grid) instead of stream + refine
     int timing_detail = 0;           // also time preparation and carve kernels of pipelined steps (three more events on the carve stream)
     int kernel_events = 0;           // every launch of a step carries begin / end events of its own (no packet of their own: vc_timing_t::kernel_ms_sum)
-    uint32_t foot_rule = 0, foot_q = 0;   // inside vc_carve_footprint: the step's carve kernel is k_carve_foot with this rule (0: the centre rule)
     DevBuf<double> d_foot_axes;      // the cell lattices lx | ly | lz (nx + 1, ny + 1, nz + 1 values), made by the first footprint carve on a grid
     bool foot_axes_valid = false;
-    bool sync_call = false;          // inside vc_carve: the step is collected at once, events between its kernels cost nothing that matters
     DevBuf<uint16_t> d_viewmask;
     DevBuf<double> d_scratch;
     Pinned<uint64_t> h_total;        // one scalar (all-gather count)
@@ -828,7 +851,7 @@ int build_brick_boxes(vc_ctx *ctx)
 }
 
 // Grid shapes the brick pipeline takes: a group of 4096 consecutive voxels must lie inside one brick column (see k_assemble).
-bool brick_shape(const vc_ctx *ctx, const CarveParams &p)
+bool brick_shape(const vc_ctx *ctx)
 {
     if (!ctx->bricks || !ctx->cull || !ctx->kbox_valid) return false;
     if (ctx->ny != 256 && ctx->ny != 512 && ctx->ny != 1024 && ctx->ny != 2048 && ctx->ny != 4096) return false;
@@ -1143,30 +1166,45 @@ int ensure_footprint(vc_ctx *ctx, Slot &s)
 
 constexpr int kEmitBatch = 4;              // survivors per lane in flight together in k_emit_words
 
+// The colour source of a step, one half of the expansion's parameters (everything else zero): axes and image size, and with a colour
+// camera its model, its mask bits and its frame in the step's frame set.  For the step's own expansion and for vc_expand_entries'.
+void emit_color_source(const vc_ctx *ctx, uint32_t slot, int color_cam, EmitParams &e)
+{
+    memset(&e, 0, sizeof e);
+    e.xs = ctx->d_axes.ptr; e.ys = e.xs + ctx->nx; e.zs = e.ys + ctx->ny;
+    e.nx = ctx->nx; e.ny = ctx->ny; e.H = ctx->H; e.W = ctx->W;
+    if (color_cam < 0) return;
+    const Slot &s = ctx->slots[slot];
+    e.has_cam = 1;
+    e.cam = ctx->cams[color_cam];
+    e.maskbits = s.bits.ptr + (size_t)color_cam * ctx->mwords;
+    if (s.frames.ptr && s.have_frame[color_cam]) e.frame = s.frames.ptr + (size_t)color_cam * ctx->H * ctx->W;
+}
+
 // start / stop: events that are to carry the launch's own begin and end (its packet's signals, hipExtLaunchKernelGGL), or null
 int launch_emit(vc_ctx *ctx, StepBuf &sb, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr)
 {
     const EmitParams &e = sb.emit;
     const dim3 eg((e.ngroups + 3) / 4), block(kBlock);
 #define VC_EMIT(kernel, grid) hipExtLaunchKernelGGL((kernel), grid, block, 0, st, start, stop, 0, e)
-    if (sb.busy && ctx->emit_lanes) {
+    if (sb.route.busy && ctx->emit_lanes) {
         const dim3 bg(256u * (uint32_t)ctx->emit_waves_per_cu / 4u);
         if (e.lut16) VC_EMIT((k_emit_busy<true, true, 8, true>), bg);             // (ensure_lut16: steps that need every camera only)
-        else if (e.lut && sb.allseen) VC_EMIT((k_emit_busy<true, true, 8>), bg);
+        else if (e.lut && sb.route.allseen) VC_EMIT((k_emit_busy<true, true, 8>), bg);
         else if (e.lut) VC_EMIT((k_emit_busy<true, false, 8>), bg);
-        else if (sb.allseen) VC_EMIT((k_emit_busy<false, true, 4>), bg);
+        else if (sb.route.allseen) VC_EMIT((k_emit_busy<false, true, 4>), bg);
         else VC_EMIT((k_emit_busy<false, false, 4>), bg);
     }
     else if (ctx->emit_lanes) {
         if (e.lut16) VC_EMIT((k_emit_lanes<true, true, 8, false, true>), eg);
-        else if (e.lut && sb.allseen) VC_EMIT((k_emit_lanes<true, true, 8>), eg);
+        else if (e.lut && sb.route.allseen) VC_EMIT((k_emit_lanes<true, true, 8>), eg);
         else if (e.lut) VC_EMIT((k_emit_lanes<true, false, 8>), eg);
-        else if (sb.allseen) VC_EMIT((k_emit_lanes<false, true, 4>), eg);
+        else if (sb.route.allseen) VC_EMIT((k_emit_lanes<false, true, 4>), eg);
         else VC_EMIT((k_emit_lanes<false, false, 4>), eg);
     }
-    else if (e.lut && sb.allseen) VC_EMIT((k_emit_words<true, true, kEmitBatch>), eg);
+    else if (e.lut && sb.route.allseen) VC_EMIT((k_emit_words<true, true, kEmitBatch>), eg);
     else if (e.lut) VC_EMIT((k_emit_words<true, false, kEmitBatch>), eg);
-    else if (sb.allseen) VC_EMIT((k_emit_words<false, true, kEmitBatch>), eg);
+    else if (sb.route.allseen) VC_EMIT((k_emit_words<false, true, kEmitBatch>), eg);
     else VC_EMIT((k_emit_words<false, false, kEmitBatch>), eg);
 #undef VC_EMIT
     VC_HIP(ctx, hipGetLastError());
@@ -1387,7 +1425,7 @@ int enqueue_pack(vc_ctx *ctx, StepBuf &cur, hipStream_t st)
     VC_TRY(ensure_exchange_scratch(ctx, ngroups));
     VC_TRY(ensure(ctx, cur.ent, (size_t)(2 * nwords)));          // worst case: every word non-zero (n / 4 bytes)
     const dim3 grid((ngroups + 3) / 4), block(kBlock);
-    if (cur.nz_valid && cur.busy) {
+    if (cur.nz_valid && cur.route.busy) {
         // the carve left the counts of non-zero words and the list of groups with survivors: no counting pass, and the packing
         // strides over the list (5 of 6 groups are empty; a launch over all of them is dispatch bound)
         VC_TRY(scan_counts(ctx, st, ctx->d_xscan, cur.groupnz.ptr, ngroups, ctx->h_xtotal));
@@ -1523,7 +1561,7 @@ int enqueue_expand(vc_ctx *ctx, hipStream_t st, const uint64_t *d_entries, uint6
     VC_TRY(ensure(ctx, ctx->d_yscan, ngroups));
     // (the table-free mode colours from the colour camera's table too, unless fused_color_table is off: the whole-grid table the
     // expansion of other ranks' words needs is the very one)
-    const bool from_lut = (cur.mode == VC_MODE_LUT || ctx->fused_color_table) && cur.color_cam >= 0;
+    const bool from_lut = (cur.route.lut || ctx->fused_color_table) && cur.color_cam >= 0;
     if (from_lut && !(ctx->lut_color_cam == cur.color_cam && ctx->d_lut_color.ptr)) {
         VC_TRY(ensure_color_table(ctx, cur.color_cam));           // built on the first stream, once per camera
         if (st != ctx->stream) VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1538,25 +1576,16 @@ int enqueue_expand(vc_ctx *ctx, hipStream_t st, const uint64_t *d_entries, uint6
     }
     if (S_hint > ctx->d_gathered.cap)            // survivor counts drift from frame to frame: grow with slack
         VC_TRY(ensure(ctx, ctx->d_gathered, (size_t)(S_hint + S_hint / 8 + 1024)));
-    EmitParams e;                                // axes, camera, mask bits and frame of the step
-    memset(&e, 0, sizeof e);
-    e.xs = ctx->d_axes.ptr; e.ys = e.xs + ctx->nx; e.zs = e.ys + ctx->ny;
-    e.nx = ctx->nx; e.ny = ctx->ny; e.H = ctx->H; e.W = ctx->W;
-    if (cur.color_cam >= 0) {
-        const Slot &s = ctx->slots[cur.slot];
-        e.has_cam = 1;
-        e.cam = ctx->cams[cur.color_cam];
-        e.maskbits = s.bits.ptr + (size_t)cur.color_cam * ctx->mwords;
-        if (s.frames.ptr && s.have_frame[cur.color_cam]) e.frame = s.frames.ptr + (size_t)cur.color_cam * ctx->H * ctx->W;
-    }
+    EmitParams e;
+    emit_color_source(ctx, cur.slot, cur.color_cam, e);          // axes, camera, mask bits and frame of the step
     e.entries = d_entries;
     e.groupcnt = ctx->d_yscan.cnt.ptr; e.groupoff = ctx->d_yscan.off.ptr; e.blockoff = ctx->d_yscan.boff.ptr;
     e.n = M * 64; e.i0 = 0; e.z0 = 0; e.ngroups = ngroups; e.entry_chunk = chunk;
     e.records = ctx->d_gathered.ptr; e.capacity = ctx->d_gathered.cap;
     e.lut = from_lut ? ctx->d_lut_color.ptr : nullptr;
-    if (from_lut && cur.allseen) hipLaunchKernelGGL((k_emit_lanes<true, true, 8, true>), grid, block, 0, st, e);
+    if (from_lut && cur.route.allseen) hipLaunchKernelGGL((k_emit_lanes<true, true, 8, true>), grid, block, 0, st, e);
     else if (from_lut) hipLaunchKernelGGL((k_emit_lanes<true, false, 8, true>), grid, block, 0, st, e);
-    else if (cur.allseen) hipLaunchKernelGGL((k_emit_lanes<false, true, 4, true>), grid, block, 0, st, e);
+    else if (cur.route.allseen) hipLaunchKernelGGL((k_emit_lanes<false, true, 4, true>), grid, block, 0, st, e);
     else hipLaunchKernelGGL((k_emit_lanes<false, false, 4, true>), grid, block, 0, st, e);
     VC_HIP(ctx, hipGetLastError());
     return VC_OK;
@@ -1967,364 +1996,399 @@ int vc_project(vc_ctx *ctx, uint32_t cam, const double *xyz, uint64_t n, double 
     return VC_OK;
 }
 
-int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int mode, uint32_t flags)
+// ---------------------------------------------------------------------------------------------------------------- the carve step
+// What the three entry points ask of step_begin.  sync: the step is collected at once (vc_carve, vc_carve_footprint), events between
+// its kernels cost nothing that matters.  foot_rule != 0: the carve kernel is k_carve_foot with this rule and q.
+struct StepRequest { uint32_t slot, min_views; int color_cam, mode; uint32_t flags; bool sync; uint32_t foot_rule, foot_q; };
+struct StepSize { uint64_t n, nwords; uint32_t ngroups, nscan; };
+
+static bool stages_grids(Carve f) { return f >= Carve::FusedHier; }
+// scan and record expansion run beside the next step's carve | packing and collectives of a rank do
+static hipStream_t emit_stream(const vc_ctx *ctx) { return (ctx->overlap && !ctx->comm) ? ctx->stream2 : ctx->stream; }
+static hipStream_t exchange_stream(const vc_ctx *ctx) { return ctx->overlap ? ctx->stream_x : ctx->stream; }
+
+// The route, first half: what follows from the request and the context as the step finds it -- grid shape, C, mwords, the options,
+// tile_valid / ymajor_valid, tile_whole.  Where the carve reads the y-major table (carve_table), ensure_ymajor runs in front of
+// it and leaves ymajor_valid set: the expansion's table and the compact table's test are decided HERE as they stand BEHIND that call.
+// Left open: Bricks or k_cull, which wait for ensure_boxes (settle_route), and the LDS of the grid-staging families (step_prepare).
+static StepRoute plan_route(const vc_ctx *ctx, const StepRequest &rq, bool tile_whole)
 {
-    if (!ctx) return VC_ERR_ARG;
-    if (ctx->npending >= kDepth) return fail(ctx, VC_ERR_ARG, "%d carve steps are already in flight: call vc_carve_end", kDepth);
-    if (!ctx->have_grid || !ctx->have_cams) return fail(ctx, VC_ERR_ARG, "grid and cameras must be set before vc_carve");
-    if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks)
-        return fail(ctx, VC_ERR_ARG, "no masks uploaded in slot %u", slot);
-    if (mode != VC_MODE_FUSED && mode != VC_MODE_LUT) return fail(ctx, VC_ERR_ARG, "unknown mode %d", mode);
-    if (mode == VC_MODE_LUT && !ctx->lut_valid) return fail(ctx, VC_ERR_ARG, "VC_MODE_LUT needs vc_build_lut first");
-    if (color_cam >= (int)ctx->C) return fail(ctx, VC_ERR_ARG, "colour camera %d not in [0,%u)", color_cam, ctx->C);
-    if (min_views < 1) min_views = 1;            // a voxel no camera sees never enters voxels_visible
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    Slot &s = ctx->slots[slot];
-    const uint64_t n = ctx->n_voxels();
-    const bool want_vm = (flags & VC_FLAG_VIEWMASK) != 0;
+    StepRoute r;
+    const bool foot = rq.foot_rule != 0, no_records = (rq.flags & VC_FLAG_NO_RECORDS) != 0;
+    r.lut = rq.mode == VC_MODE_LUT; r.viewmask = (rq.flags & VC_FLAG_VIEWMASK) != 0;
+    r.allseen = foot || rq.min_views == ctx->C;
+    // The chunked kernels cover the reference's case (seen by ALL cameras); the one-thread-per-voxel kernels cover thresholds below C, the
+    // camera bitmask, and thresholds above C (no voxel can be seen by more cameras than there are: the reference's
+    // sum(views.values()) >= views_threshold is never true, the result is empty) -- and masks too large for k_lut_first's LDS (one camera's)
+    bool fast = !foot && !ctx->force_generic && !r.viewmask && rq.min_views == ctx->C;
+    if (r.lut && !ctx->lut_hier && (size_t)ctx->mwords * sizeof(uint32_t) > kMaxFirstLds) fast = false;
+    r.grids = fast;
+    if (foot) r.family = Carve::Foot;
+    else if (!fast) r.family = Carve::Generic;
+    else if (r.lut && ctx->lut_hier) {
+        r.family = Carve::LutHier;
+        r.tile = ctx->lut_tile && ctx->tile_valid;
+        r.pair = ctx->refine_pair != 0; r.b16 = !r.pair && ctx->refine_b != 8;
+    }
+    else if (r.lut) { r.family = Carve::LutStream; r.b16 = ctx->refine_b != 8; r.lds = (size_t)ctx->mwords * sizeof(uint32_t); }
+    else if (ctx->ny % 64 == 0 && ctx->fused_hier) {
+        r.family = Carve::FusedHier;
+        r.tile = ctx->fused_tile && ctx->nx % 4 == 0;                 // ny % 64 == 0 here
+        r.boxes = ctx->fused_boxes ? 2 : ctx->fused_f32box ? 1 : 0;
+    }
+    else r.family = Carve::FusedChunked;
+    const bool hier = stages_grids(r.family);
+    r.boxed_tiles = hier && r.tile && (r.lut || r.boxes == 2);
+    r.zero_counts = hier && r.tile && !tile_whole;
+    r.sparse_words = hier && !r.zero_counts;
+    r.counted = hier || r.family == Carve::LutStream;                 // (chunked, one thread per voxel, footprint: their totals get counted)
+    // which table the carve reads: the tile-ordered one (hierarchical kernel on tile words), else the y-major one
+    r.carve_table = !r.lut ? Table::None : r.family == Carve::LutHier && r.tile ? Table::Tile : Table::YMajor;
+    const bool ymajor = ctx->ymajor_valid || r.carve_table == Table::YMajor;
+    if (rq.color_cam >= 0) {
+        if (r.lut) r.emit_table = ctx->tile_valid && !ymajor ? Table::Tile : Table::YMajor;   // Tile: the only table there is
+        else if (ctx->fused_color_table && !no_records) r.emit_table = Table::Color;
+    }
+    // the compact table: where the tile-ordered table is what the expansion reads and a group's tile words are 64 in a row.  (A step with a
+    // threshold below C takes the one-thread-per-voxel carve and, from then on, the y-major table it builds: allseen holds wherever this applies.)
+    r.try_lut16 = r.emit_table == Table::Tile && ctx->emit_lut16 && ctx->emit_lanes && !no_records && tile_whole && r.allseen;
+    return r;
+}
+
+// The route, second half, behind ensure_boxes(tile) -- which sets kbox_valid for the table-free tile route: the brick pipeline
+// where the shape allows, else k_cull in front of the one-launch kernel; and what hangs on that: the busy list and the events.
+static void settle_route(const vc_ctx *ctx, const StepRequest &rq, bool carve_timed, bool tile_whole, uint32_t ngroups, StepRoute &r)
+{
+    const bool no_records = (rq.flags & VC_FLAG_NO_RECORDS) != 0;
+    if (r.boxed_tiles && brick_shape(ctx)) {
+        r.family = Carve::Bricks;
+        r.wide_grids = r.sparse_words = true;                         // (k_cull_bricks zeroes every group's count itself)
+    }
+    else if (r.boxed_tiles) r.cull = ctx->cull && ctx->kbox_valid;
+    // a rank of a communicator packs and exchanges the counts right behind the carve: vc_allgather finds them on the host
+    r.exchange = no_records && ctx->comm && ctx->gather_compact;
+    r.count_nz = r.exchange && r.family == Carve::Bricks && tile_whole;
+    // the expansion of a large grid iterates over the scan's list of groups that have survivors (a rank's packing strides over it too)
+    r.busy = ctx->emit_lanes && (!no_records || (r.exchange && r.count_nz)) &&
+             (ctx->emit_busy == 2 || (ctx->emit_busy == 1 && ngroups >= kBusyListMinGroups));
+    // the events a pipelined step hands from stream to stream ride on the launches in front: {scan done} on k_finish_scan, {step done} on the expansion
+    r.xstream = r.exchange && exchange_stream(ctx) != ctx->stream;   // the packing waits for the scan across streams
+    r.scan_ev = (!no_records && (emit_stream(ctx) != ctx->stream || carve_timed)) || r.xstream;
+    r.ride = ctx->launch_events && !no_records;
+    r.scan_ridden = r.busy && ctx->launch_events && r.scan_ev;
+}
+
+// vc_ctx::kev_sb names the step whose kernels are being queued for as long as step_begin runs, whichever way it leaves
+struct KevScope { vc_ctx *ctx; ~KevScope() { ctx->kev_sb = nullptr; } };
+
+// Stage 1 (behind the refusals): the step's set of buffers, its events from the ring, the result it replaces invalidated ...
+static StepBuf &step_open(vc_ctx *ctx, const StepRequest &rq)
+{
     ctx->gathered = false;
     result_changed(ctx);   // the next carve invalidates what the post-carve passes left
-    ctx->tm.voxels = n;
+    ctx->tm.voxels = ctx->n_voxels();
     if (ctx->head == ctx->cur) {
         // this step is queued into the buffers that hold the result the vc_fetch_* functions read: it is gone from here on
         ctx->carved = false; ctx->viewmask_valid = false; ctx->packed = false;
     }
     StepBuf &sb = ctx->sb[ctx->head];
-    sb.e_scan = ctx->step_ev[ctx->step_next][0];
-    sb.e2 = ctx->step_ev[ctx->step_next][1];
-    sb.e_emit0 = ctx->step_ev[ctx->step_next][2];
+    Event *ev = ctx->step_ev[ctx->step_next];
+    sb.e_scan = ev[0]; sb.e2 = ev[1]; sb.e_emit0 = ev[2];
     ctx->step_next = (ctx->step_next + 1) % kStepRing;
-    sb.n = n; sb.survivors = 0; sb.want_vm = want_vm; sb.has_first = false;
-    const bool foot = ctx->foot_rule != 0;                       // vc_carve_footprint: colour and seen by the centre's pixel alone
-    sb.allseen = foot || min_views == ctx->C;
-    sb.min_views = min_views;
-    sb.no_records = (flags & VC_FLAG_NO_RECORDS) != 0;
-    sb.sparse_words = false;
-    sb.mode = mode; sb.color_cam = color_cam; sb.slot = slot;
-    // a rank of a communicator packs and exchanges the counts right behind the carve, so that
-    // vc_allgather finds them on the host and only has the payload and the expansion left
-    sb.counts_exchanged = false;
-    const bool auto_exchange = sb.no_records && ctx->comm && ctx->gather_compact;
-    // packing + collectives of a step run on the exchange stream, beside the next step's carve
-    hipStream_t sx = ctx->overlap ? ctx->stream_x : ctx->stream;
-    if (n == 0) {
-        if (auto_exchange) {                     // an empty slab still takes part in the collective
-            VC_TRY(enqueue_pack(ctx, sb, sx));
-            VC_TRY(enqueue_counts_exchange(ctx, sb, sx));
-            VC_HIP(ctx, hipEventRecord(sb.e2, sx));
-            sb.counts_exchanged = true;
-        }
-        sb.pending = true; sb.used = false; ctx->head = (ctx->head + 1) % kDepth; ctx->npending++;
-        return VC_OK;
-    }
-
-    const uint64_t nwords = (n + 63) / 64;
-    const uint64_t n_pad = (n + kLutPad - 1) / kLutPad * kLutPad;
-    const uint32_t ngroups = (uint32_t)(n_pad / (64 * kGroupWords));
-    const uint32_t nscan = (ngroups + kScanBlock - 1) / kScanBlock;
-    VC_TRY(ensure(ctx, sb.words, n_pad / 64));
-    VC_TRY(ensure(ctx, sb.groupcnt, ngroups));
-    VC_TRY(ensure(ctx, sb.groupoff, ngroups));
-    VC_TRY(ensure(ctx, sb.blocksum, kMaxScanBlocks));
-    VC_TRY(ensure(ctx, sb.blockoff, kMaxScanBlocks + 1));
-    if (want_vm) VC_TRY(ensure(ctx, ctx->d_viewmask, n));
-    if (!sb.records.ptr && !sb.no_records) VC_TRY(ensure(ctx, sb.records, (size_t)(n / 16 + 1024)));
-
-    CarveParams p;
-    fill_params(ctx, p);
-    sb.kmask = 0;
-    ctx->kev_sb = nullptr;
+    sb.n = ctx->n_voxels(); sb.survivors = 0; sb.kmask = 0;
+    sb.min_views = rq.min_views; sb.color_cam = rq.color_cam; sb.slot = rq.slot;
+    sb.no_records = (rq.flags & VC_FLAG_NO_RECORDS) != 0;
+    sb.sparse_words = sb.counts_exchanged = false;
+    sb.carve_timed = ctx->timing_detail || rq.sync;
     if (ctx->timing_detail || ctx->kernel_events) ctx->kev_sb = &sb;   // every launch of this step carries begin / end events
-    if (ctx->timing_detail) {                                     // ... and the kernels count their work
+    return sb;
+}
+
+// ... and the empty slab, which still takes part in the collective
+static int step_empty(vc_ctx *ctx, StepBuf &sb)
+{
+    if (sb.no_records && ctx->comm && ctx->gather_compact) {
+        hipStream_t sx = exchange_stream(ctx);
+        VC_TRY(enqueue_pack(ctx, sb, sx));
+        VC_TRY(enqueue_counts_exchange(ctx, sb, sx));
+        VC_HIP(ctx, hipEventRecord(sb.e2, sx));
+        sb.counts_exchanged = true;
+    }
+    sb.pending = true; sb.used = false; ctx->head = (ctx->head + 1) % kDepth; ctx->npending++;
+    return VC_OK;
+}
+
+// Stage 2: the step's buffers (timing_detail: and the kernels' work counters), and the carve's pointers into them
+static int step_size(vc_ctx *ctx, const StepRequest &rq, StepBuf &sb, const StepSize &z, CarveParams &p)
+{
+    VC_TRY(ensure(ctx, sb.words, p.n_pad / 64));
+    VC_TRY(ensure(ctx, sb.groupcnt, z.ngroups)); VC_TRY(ensure(ctx, sb.groupoff, z.ngroups));
+    VC_TRY(ensure(ctx, sb.blocksum, kMaxScanBlocks)); VC_TRY(ensure(ctx, sb.blockoff, kMaxScanBlocks + 1));
+    if (rq.flags & VC_FLAG_VIEWMASK) VC_TRY(ensure(ctx, ctx->d_viewmask, z.n));
+    if (!sb.records.ptr && !sb.no_records) VC_TRY(ensure(ctx, sb.records, (size_t)(z.n / 16 + 1024)));
+    if (ctx->timing_detail) {
         if (!ctx->d_stats.ptr) {
             VC_TRY(ensure(ctx, ctx->d_stats, (size_t)VC_WORK_KINDS * kShards * kStatStride));
             VC_HIP(ctx, hipMemset(ctx->d_stats.ptr, 0, ctx->d_stats.cap * sizeof(unsigned long long)));
         }
         p.stats = ctx->d_stats.ptr;
     }
-    p.words = sb.words.ptr;
-    p.groupcnt = sb.groupcnt.ptr;
-    p.viewmask = ctx->d_viewmask.ptr;
-    p.min_views = min_views;
+    p.words = sb.words.ptr; p.groupcnt = sb.groupcnt.ptr; p.viewmask = ctx->d_viewmask.ptr; p.min_views = rq.min_views;
+    return VC_OK;
+}
 
-    // The chunked kernels cover the reference's case (seen by ALL cameras); the one-thread-per-voxel kernels cover
-    // thresholds below C, the camera bitmask, and thresholds above C (no voxel can be seen by more cameras than
-    // there are: the reference's sum(views.values()) >= views_threshold is never true, the result is empty).
-    bool fast = !foot && !ctx->force_generic && !want_vm && min_views == ctx->C;
-    // k_lut_first keeps one camera's mask bits in LDS; larger masks take the generic kernel.
-    if (mode == VC_MODE_LUT && !ctx->lut_hier && (size_t)ctx->mwords * sizeof(uint32_t) > kMaxFirstLds) fast = false;
-    // per-frame preparation, on the device, in front of the carve (nothing to do when the slot has been used before)
-    sb.prepped = !s.bits_valid || (fast && !s.grids_valid);
-    sb.carve_timed = ctx->timing_detail || ctx->sync_call;
+// Stage 4: everything that is made in front of the carve, in this order.  The tables sit HERE, on the carve stream in front of the carve
+// kernels, so that {scan done} -- which the expansion waits for on its own stream and which rides on the k_finish_scan launch -- is behind
+// them: queued where the expansion's parameters are set up, they would follow that launch and the first expansion read a table being written.
+static int step_prepare(vc_ctx *ctx, const StepRequest &rq, StepBuf &sb, Slot &s, const StepSize &z, CarveParams &p)
+{
+    StepRoute &r = sb.route;
+    if (r.boxed_tiles && !r.lut) VC_TRY(ensure_boxes(ctx, true));         // tile boxes without a table (and the brick boxes behind them)
+    settle_route(ctx, rq, sb.carve_timed, p.tile_whole != 0, z.ngroups, r);
+    sb.sparse_words = r.sparse_words;
+    // per-frame preparation (nothing to do when the slot has been used before); it sizes the grids for the LDS of the kernels that stage them
+    sb.prepped = !s.bits_valid || (r.grids && !s.grids_valid);
     sb.prep_timed = sb.prepped && sb.carve_timed;
-    // (the brick pipeline's grid-staging kernels take up to 148 KB of LDS, the others 64: the preparation sizes the grids for it)
-    const bool fused_tiles = mode == VC_MODE_FUSED && fast && ctx->ny % 64 == 0 && ctx->fused_hier && ctx->fused_tile && ctx->nx % 4 == 0 && ctx->fused_boxes;
-    if (fused_tiles) VC_TRY(ensure_boxes(ctx, true));
-    const bool bricks = fast && brick_shape(ctx, p) && (fused_tiles || (mode == VC_MODE_LUT && ctx->lut_hier && ctx->lut_tile && ctx->tile_valid));
-    VC_TRY(ensure_prepared(ctx, s, fast, &p, sb.prep_timed, bricks));
-    sb.nz_valid = false;
-    if (auto_exchange && bricks && p.tile_whole) {               // k_assemble counts the groups' non-zero words for the packing
-        VC_TRY(ensure(ctx, sb.groupnz, ngroups));
+    VC_TRY(ensure_prepared(ctx, s, r.grids, &p, sb.prep_timed, r.wide_grids));
+    if (stages_grids(r.family)) r.lds = ((size_t)s.budget_words + 8) * sizeof(uint32_t);
+    sb.nz_valid = r.count_nz;
+    if (r.count_nz) {
+        VC_TRY(ensure(ctx, sb.groupnz, z.ngroups));
         p.groupnz = sb.groupnz.ptr;
-        sb.nz_valid = true;
     }
     sb.slot_gen = s.gen;
     if (s.prep_pending) { VC_HIP(ctx, hipStreamWaitEvent(ctx->stream, s.e_prep, 0)); s.prep_pending = false; }
-    if (foot) VC_TRY(ensure_footprint(ctx, s));                  // lattices + the slot's tables, on the carve stream behind the preparation
-    p.maskbits = s.bits.ptr;
-    p.blockgrid = s.grid.ptr;
-    p.coarsegrid = s.has_coarse ? s.coarse.ptr : nullptr;
+    if (r.family == Carve::Foot) VC_TRY(ensure_footprint(ctx, s));         // lattices + the slot's tables, behind the preparation
+    p.maskbits = s.bits.ptr; p.blockgrid = s.grid.ptr; p.coarsegrid = s.has_coarse ? s.coarse.ptr : nullptr;
     p.counts = s.boxes.ptr + kCountBase;
-    // which table the step reads: the tile-ordered one (hierarchical kernels on tile words), else the y-major one
-    const bool lut_tiled = mode == VC_MODE_LUT && fast && ctx->lut_hier && ctx->lut_tile && ctx->tile_valid;
-    if (mode == VC_MODE_LUT && !lut_tiled) VC_TRY(ensure_ymajor(ctx));
-    p.lut = ctx->d_lut.ptr;
-    p.bbox = ctx->d_bbox.ptr;
-    const size_t grid_lds = ((size_t)s.budget_words + 8) * sizeof(uint32_t);
+    if (r.carve_table == Table::YMajor) VC_TRY(ensure_ymajor(ctx));
+    p.lut = ctx->d_lut.ptr; p.bbox = ctx->d_bbox.ptr;
+    // the colour camera's table over the whole grid (VC_MODE_FUSED), its compact tile-ordered table (VC_MODE_LUT): made by the first step that names it
+    if (r.emit_table == Table::Color) VC_TRY(ensure_color_table(ctx, rq.color_cam));
+    if (r.try_lut16) VC_TRY(ensure_lut16(ctx, rq.color_cam, p.n_pad, r.lut16));
+    return VC_OK;
+}
 
-    // VC_MODE_FUSED colours the survivors from the colour camera's table over the whole grid: projected once, HERE -- in front of
-    // the carve kernels on their stream, so that {scan done}, which the expansion waits for on its own stream and which rides
-    // on the k_finish_scan launch, is behind it (queued where the expansion's parameters are set up it would follow that
-    // launch, and the first expansion would read a table still being written)
-    if (mode == VC_MODE_FUSED && ctx->fused_color_table && color_cam >= 0 && !sb.no_records) VC_TRY(ensure_color_table(ctx, color_cam));
-    // VC_MODE_LUT, where the tile-ordered table is what the expansion reads and a group's tile words are 64 in a row: the
-    // colour camera's compact table, packed here for the same reason.  (A step with a threshold below C takes the
-    // one-thread-per-voxel carve and, from then on, the y-major table it builds: sb.allseen holds wherever this applies.)
-    sb.lut16 = false;
-    if (mode == VC_MODE_LUT && ctx->emit_lut16 && ctx->emit_lanes && color_cam >= 0 && !sb.no_records && n && ctx->tile_valid &&
-        !ctx->ymajor_valid && p.tile_whole && sb.allseen)
-        VC_TRY(ensure_lut16(ctx, color_cam, p.n_pad, sb.lut16));
-    if (sb.carve_timed) VC_HIP(ctx, hipEventRecord(sb.e0, ctx->stream));
+// Stage 5: the carve kernels of the route, between the step's timing events
+static int step_carve(vc_ctx *ctx, const StepRequest &rq, StepBuf &sb, Slot &s, const StepSize &z, CarveParams &p)
+{
+    const StepRoute &r = sb.route;
     const dim3 block(kBlock);
-    if (foot) {
+    // grids of the kernels whose workgroups stride: four waves' items per workgroup, so many workgroups per CU at the most
+    auto strided = [](uint64_t items, int per_cu) {
+        const uint64_t want = (items + 3) / 4, most = 256ull * (uint64_t)per_cu;
+        return dim3((uint32_t)(want < most ? want : most));
+    };
+    const uint64_t groups = p.n_pad / 4096;
+#define VC_CARVE(kernel, grid, blk, lds) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, kernel, grid, blk, lds, ctx->stream, p)
+    if (sb.carve_timed) VC_HIP(ctx, hipEventRecord(sb.e0, ctx->stream));
+    if (r.zero_counts) VC_HIP(ctx, hipMemsetAsync(sb.groupcnt.ptr, 0, sizeof(uint32_t) * z.ngroups, ctx->stream));
+    if (r.boxed_tiles && !r.lut) { p.tbox = ctx->d_tbox.ptr; p.kbox = ctx->d_kbox.ptr; }     // (ensure_boxes may have made them)
+    if (r.cull) {
+        p.live = ctx->d_live.ptr;
+        const uint32_t cw = p.nbrick_pad / 256;
+        VC_KLAUNCH(VC_K_CULL, k_cull, dim3(cw < 1 ? 1 : (cw > 1024 ? 1024 : cw)), block, r.lds, ctx->stream, p);
+    }
+    switch (r.family) {
+    case Carve::Foot: {
         FootParams f;
         f.lx = ctx->d_foot_axes.ptr; f.ly = f.lx + ctx->nx + 1; f.lz = f.ly + ctx->ny + 1;
-        f.sat = s.sat.ptr; f.rule = ctx->foot_rule; f.q = ctx->foot_q;
-        const dim3 grid((uint32_t)((nwords + 3) / 4));
-        if (want_vm) VC_KLAUNCH(VC_K_FOOT_CARVE, (k_carve_foot<true>), grid, block, 0, ctx->stream, p, f);
+        f.sat = s.sat.ptr; f.rule = rq.foot_rule; f.q = rq.foot_q;
+        const dim3 grid((uint32_t)((z.nwords + 3) / 4));
+        if (r.viewmask) VC_KLAUNCH(VC_K_FOOT_CARVE, (k_carve_foot<true>), grid, block, 0, ctx->stream, p, f);
         else VC_KLAUNCH(VC_K_FOOT_CARVE, (k_carve_foot<false>), grid, block, 0, ctx->stream, p, f);
-    } else if (fast) {
-        const uint64_t nchunks = (n + 64 * kSub - 1) / (64 * kSub);
-        const uint64_t want = (nchunks + 3) / 4;
-        const uint64_t gmax = 256ull * (uint64_t)ctx->fused_blocks_per_cu;
-        const dim3 grid((uint32_t)(want < gmax ? want : gmax));
-        if (mode == VC_MODE_LUT && ctx->lut_hier) {
-            // one launch: word-level rejection by pixel box x foreground-block grid, exact test for the rest
-            const size_t lds = grid_lds;
-            const uint64_t groups = p.n_pad / 4096;
-            const uint64_t rwant = (groups + 3) / 4;
-            const uint64_t rmax = 256ull * (uint64_t)ctx->hier_blocks_per_cu;
-            const dim3 rgrid((uint32_t)(rwant < rmax ? rwant : rmax));
-            sb.sparse_words = true;
-            if (ctx->lut_tile && ctx->tile_valid) {
-                if (!p.tile_whole) {             // waves and groups do not coincide: counts by atomics, every word stored
-                    VC_HIP(ctx, hipMemsetAsync(sb.groupcnt.ptr, 0, sizeof(uint32_t) * ngroups, ctx->stream));
-                    sb.sparse_words = false;
-                }
-                if (brick_shape(ctx, p)) {
-                    sb.sparse_words = true;              // (k_cull_bricks zeroes every group's count itself)
-                    VC_TRY(launch_bricks<true>(ctx, p, lds, ngroups));
-                } else {
-                    if (ctx->cull && ctx->kbox_valid) {
-                        p.live = ctx->d_live.ptr;
-                        const uint32_t cw = p.nbrick_pad / 256;
-                        VC_KLAUNCH(VC_K_CULL, k_cull, dim3(cw < 1 ? 1 : (cw > 1024 ? 1024 : cw)), block, lds, ctx->stream, p);
-                    }
-                    VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_refine<8, true, true, true>), rgrid, block, lds, ctx->stream, p);
-                }
-            }
-            else if (ctx->refine_pair) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_refine<8, true, true>), rgrid, block, lds, ctx->stream, p);
-            else if (ctx->refine_b == 8) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_refine<8, true, false>), rgrid, block, lds, ctx->stream, p);
-            else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_refine<16, true, false>), rgrid, block, lds, ctx->stream, p);
-        } else if (mode == VC_MODE_LUT) {
-            const size_t lds = (size_t)ctx->mwords * sizeof(uint32_t);
-            const int kv = ctx->first_kv;
-            const uint64_t chunks = p.n_pad / (256 * kv);
-            const uint64_t fwant = (chunks + 7) / 8;
-            uint32_t per_cu = (uint32_t)(kLdsBytes / (lds ? lds : 1));
-            if (per_cu > (uint32_t)ctx->first_blocks_per_cu) per_cu = (uint32_t)ctx->first_blocks_per_cu;
-            if (per_cu < 1) per_cu = 1;
-            const uint32_t fmax = 256u * per_cu;
-            const dim3 fgrid((uint32_t)(fwant < fmax ? fwant : fmax)), fblock(kFirstBlock);
-            if (kv == 1) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_first<1>), fgrid, fblock, lds, ctx->stream, p);
-            else if (kv == 4) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_first<4>), fgrid, fblock, lds, ctx->stream, p);
-            else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_first<2>), fgrid, fblock, lds, ctx->stream, p);
-            VC_HIP(ctx, hipGetLastError());
-            if (sb.carve_timed) { VC_HIP(ctx, hipEventRecord(sb.e_first, ctx->stream)); sb.has_first = true; }
-            const uint64_t groups = p.n_pad / 4096;
-            const uint64_t rwant = (groups + 3) / 4;
-            const uint64_t rmax = 256ull * (uint64_t)ctx->refine_blocks_per_cu;
-            const dim3 rgrid((uint32_t)(rwant < rmax ? rwant : rmax));
-            if (ctx->refine_b == 8) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_refine<8, false, false>), rgrid, block, 0, ctx->stream, p);
-            else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_lut_refine<16, false, false>), rgrid, block, 0, ctx->stream, p);
-        }
-        else if (ctx->ny % 64 == 0 && ctx->fused_hier) {
-            const size_t lds = grid_lds;
-            const uint64_t groups = p.n_pad / 4096;
-            const uint64_t rwant = (groups + 3) / 4;
-            const uint64_t rmax = 256ull * (uint64_t)ctx->hier_blocks_per_cu;
-            const dim3 rgrid((uint32_t)(rwant < rmax ? rwant : rmax));
-            sb.sparse_words = true;
-            if (ctx->fused_tile && ctx->nx % 4 == 0) {            // ny % 64 == 0 here: words of 4 x-rows x 16 y
-                if (!p.tile_whole) {
-                    VC_HIP(ctx, hipMemsetAsync(sb.groupcnt.ptr, 0, sizeof(uint32_t) * ngroups, ctx->stream));
-                    sb.sparse_words = false;
-                }
-                if (ctx->fused_boxes) {
-                    VC_TRY(ensure_boxes(ctx, true));
-                    p.tbox = ctx->d_tbox.ptr;
-                    p.kbox = ctx->d_kbox.ptr;
-                    if (brick_shape(ctx, p)) {
-                        sb.sparse_words = true;
-                        VC_TRY(launch_bricks<false>(ctx, p, lds, ngroups));
-                    } else {
-                        if (ctx->cull && ctx->kbox_valid) {
-                            p.live = ctx->d_live.ptr;
-                            const uint32_t cw = p.nbrick_pad / 256;
-                            VC_KLAUNCH(VC_K_CULL, k_cull, dim3(cw < 1 ? 1 : (cw > 1024 ? 1024 : cw)), block, lds, ctx->stream, p);
-                        }
-                        VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused_hier<true, 2>), rgrid, block, lds, ctx->stream, p);
-                    }
-                }
-                else if (ctx->fused_f32box) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused_hier<true, 1>), rgrid, block, lds, ctx->stream, p);
-                else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused_hier<true, 0>), rgrid, block, lds, ctx->stream, p);
-            }
-            else if (ctx->fused_boxes) {
-                VC_TRY(ensure_boxes(ctx, false));
-                p.bbox = ctx->d_bbox.ptr;
-                VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused_hier<false, 2>), rgrid, block, lds, ctx->stream, p);
-            }
-            else if (ctx->fused_f32box) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused_hier<false, 1>), rgrid, block, lds, ctx->stream, p);
-            else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused_hier<false, 0>), rgrid, block, lds, ctx->stream, p);
-        }
-        else if (ctx->ny % 64 == 0) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused<kSub, true>), grid, block, 0, ctx->stream, p);
-        else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_fused<kSub, false>), grid, block, 0, ctx->stream, p);
-    } else {
-        const dim3 grid(grid_for(n));
-        if (mode == VC_MODE_LUT) {
-            if (want_vm) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_generic<true, true>), grid, block, 0, ctx->stream, p);
-            else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_generic<true, false>), grid, block, 0, ctx->stream, p);
-        } else {
-            if (want_vm) VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_generic<false, true>), grid, block, 0, ctx->stream, p);
-            else VC_KLAUNCH(VC_K_CARVE_ONE_LAUNCH, (k_carve_generic<false, false>), grid, block, 0, ctx->stream, p);
-        }
+        break;
     }
+    case Carve::Generic: {
+        const dim3 grid(grid_for(z.n));
+        if (r.lut && r.viewmask) VC_CARVE((k_carve_generic<true, true>), grid, block, 0);
+        else if (r.lut) VC_CARVE((k_carve_generic<true, false>), grid, block, 0);
+        else if (r.viewmask) VC_CARVE((k_carve_generic<false, true>), grid, block, 0);
+        else VC_CARVE((k_carve_generic<false, false>), grid, block, 0);
+        break;
+    }
+    case Carve::FusedChunked: {
+        const dim3 grid = strided((z.n + 64 * kSub - 1) / (64 * kSub), ctx->fused_blocks_per_cu);
+        if (ctx->ny % 64 == 0) VC_CARVE((k_carve_fused<kSub, true>), grid, block, 0);
+        else VC_CARVE((k_carve_fused<kSub, false>), grid, block, 0);
+        break;
+    }
+    case Carve::LutStream: {
+        const int kv = ctx->first_kv;
+        const uint64_t fwant = (p.n_pad / (256 * kv) + 7) / 8;
+        uint32_t per_cu = (uint32_t)(kLdsBytes / (r.lds ? r.lds : 1));
+        if (per_cu > (uint32_t)ctx->first_blocks_per_cu) per_cu = (uint32_t)ctx->first_blocks_per_cu;
+        const uint32_t fmax = 256u * (per_cu < 1 ? 1u : per_cu);
+        const dim3 fgrid((uint32_t)(fwant < fmax ? fwant : fmax)), fblock(kFirstBlock);
+        if (kv == 1) VC_CARVE((k_lut_first<1>), fgrid, fblock, r.lds);
+        else if (kv == 4) VC_CARVE((k_lut_first<4>), fgrid, fblock, r.lds);
+        else VC_CARVE((k_lut_first<2>), fgrid, fblock, r.lds);
+        VC_HIP(ctx, hipGetLastError());
+        if (sb.carve_timed) VC_HIP(ctx, hipEventRecord(sb.e_first, ctx->stream));
+        const dim3 rgrid = strided(groups, ctx->refine_blocks_per_cu);
+        if (!r.b16) VC_CARVE((k_lut_refine<8, false, false>), rgrid, block, 0);
+        else VC_CARVE((k_lut_refine<16, false, false>), rgrid, block, 0);
+        break;
+    }
+    case Carve::FusedHier: {                     // word-level rejection by interval arithmetic, or by the boxes read
+        const dim3 rgrid = strided(groups, ctx->hier_blocks_per_cu);
+        if (!r.tile && r.boxes == 2) {           // (the y-line boxes: built by the first such step, behind its first timing event)
+            VC_TRY(ensure_boxes(ctx, false));
+            p.bbox = ctx->d_bbox.ptr;
+        }
+        if (r.tile && r.boxes == 2) VC_CARVE((k_carve_fused_hier<true, 2>), rgrid, block, r.lds);
+        else if (r.tile && r.boxes == 1) VC_CARVE((k_carve_fused_hier<true, 1>), rgrid, block, r.lds);
+        else if (r.tile) VC_CARVE((k_carve_fused_hier<true, 0>), rgrid, block, r.lds);
+        else if (r.boxes == 2) VC_CARVE((k_carve_fused_hier<false, 2>), rgrid, block, r.lds);
+        else if (r.boxes == 1) VC_CARVE((k_carve_fused_hier<false, 1>), rgrid, block, r.lds);
+        else VC_CARVE((k_carve_fused_hier<false, 0>), rgrid, block, r.lds);
+        break;
+    }
+    case Carve::LutHier: {                       // one launch: word-level rejection by pixel box x foreground-block grid, exact test for the rest
+        const dim3 rgrid = strided(groups, ctx->hier_blocks_per_cu);
+        if (r.tile) VC_CARVE((k_lut_refine<8, true, true, true>), rgrid, block, r.lds);
+        else if (r.pair) VC_CARVE((k_lut_refine<8, true, true>), rgrid, block, r.lds);
+        else if (!r.b16) VC_CARVE((k_lut_refine<8, true, false>), rgrid, block, r.lds);
+        else VC_CARVE((k_lut_refine<16, true, false>), rgrid, block, r.lds);
+        break;
+    }
+    case Carve::Bricks:
+        if (r.lut) VC_TRY(launch_bricks<true>(ctx, p, r.lds, z.ngroups));
+        else VC_TRY(launch_bricks<false>(ctx, p, r.lds, z.ngroups));
+        break;
+    }
+#undef VC_CARVE
     VC_HIP(ctx, hipGetLastError());
     if (sb.carve_timed) VC_HIP(ctx, hipEventRecord(sb.e1, ctx->stream));
+    return VC_OK;
+}
 
-    // ---- compaction: group counts -> two-level scan -> record expansion
-    // the carve kernels are VALU-issue bound, the expansion is memory bound: on its own stream the expansion of this
-    // step runs beside the carve of the next one (two steps in flight) instead of after it
-    // (the small scan kernels stay on the first stream, right behind the carve: on the second they would queue for
-    // compute units against the next carve's thousands of workgroups and delay the expansion they feed)
-    hipStream_t s3 = (ctx->overlap && !ctx->comm) ? ctx->stream2 : ctx->stream;
-    hipStream_t s2 = ctx->stream;
-    // kernels that do not know their group totals (fused, generic) get them counted
-    const bool counted = fast && (mode == VC_MODE_LUT || (ctx->ny % 64 == 0 && ctx->fused_hier));
-    if (!counted) {
-        VC_KLAUNCH(VC_K_COUNT_GROUPS, k_count_groups, dim3((ngroups + 3) / 4), block, 0, s2, sb.words.ptr, nwords, ngroups,
+// Stage 6: group counts -> two-level scan (and the list of busy groups), on the carve stream right behind the carve: on the expansion's
+// stream the small scan kernels would queue for compute units against the next carve's thousands of workgroups and delay the expansion
+static int step_scan(vc_ctx *ctx, StepBuf &sb, const StepSize &z)
+{
+    const StepRoute &r = sb.route;
+    hipStream_t st = ctx->stream;
+    const dim3 block(kBlock);
+    if (!r.counted) {
+        VC_KLAUNCH(VC_K_COUNT_GROUPS, k_count_groups, dim3((z.ngroups + 3) / 4), block, 0, st, sb.words.ptr, z.nwords, z.ngroups,
                            sb.groupcnt.ptr);
         VC_HIP(ctx, hipGetLastError());
     }
-    // the expansion of a large grid iterates over the list of groups that have survivors, made by the same scan
-    // (a rank of a communicator has no expansion of its own, but its packing strides over the same list)
-    sb.busy = ctx->emit_lanes && (!sb.no_records || (auto_exchange && sb.nz_valid)) &&
-              (ctx->emit_busy == 2 || (ctx->emit_busy == 1 && ngroups >= kBusyListMinGroups));
-    if (sb.busy) {
-        VC_TRY(ensure(ctx, sb.busyoff, ngroups));
-        VC_TRY(ensure(ctx, sb.busylist, ngroups));
-        VC_TRY(ensure(ctx, sb.busysum, kMaxScanBlocks));
-        VC_TRY(ensure(ctx, sb.busyblock, 1));                    // the count of busy groups
+    if (r.busy) {
+        VC_TRY(ensure(ctx, sb.busyoff, z.ngroups)); VC_TRY(ensure(ctx, sb.busylist, z.ngroups));
+        VC_TRY(ensure(ctx, sb.busysum, kMaxScanBlocks)); VC_TRY(ensure(ctx, sb.busyblock, 1));   // (busyblock: the count of busy groups)
     }
-    VC_KLAUNCH(VC_K_SCAN_GROUPS, k_scan_groups, dim3(nscan), dim3(kScanThreads), 0, s2, (const uint32_t *)sb.groupcnt.ptr, ngroups, sb.groupoff.ptr,
-               sb.blocksum.ptr, sb.blockoff.ptr, sb.h_total.ptr, sb.busy ? sb.busyoff.ptr : (uint32_t *)nullptr, sb.busysum.ptr,
+    VC_KLAUNCH(VC_K_SCAN_GROUPS, k_scan_groups, dim3(z.nscan), dim3(kScanThreads), 0, st, (const uint32_t *)sb.groupcnt.ptr, z.ngroups, sb.groupoff.ptr,
+               sb.blocksum.ptr, sb.blockoff.ptr, sb.h_total.ptr, r.busy ? sb.busyoff.ptr : (uint32_t *)nullptr, sb.busysum.ptr,
                sb.busyblock.ptr, (uint32_t)ctx->dbg);
     VC_HIP(ctx, hipGetLastError());
-    // the two events a pipelined step hands from stream to stream ride on the launches in front of them where those are the
-    // list-driven ones (large grids): {scan done} on k_finish_scan, {step done} on the expansion
-    const bool xstream = auto_exchange && sx != ctx->stream;     // the packing waits for the scan across streams
-    const bool want_scan_ev = (!sb.no_records && (s3 != ctx->stream || sb.carve_timed)) || xstream;
-    const bool ride = ctx->launch_events && !sb.no_records;
-    sb.emit_ridden = ride;
-    bool scan_ridden = false;
-    if (sb.busy) {
+    if (r.busy) {
         // level 2 of both scans + the list in one launch (k_scan_groups has left the count in busyblock[0] when nscan == 1)
-        scan_ridden = ctx->launch_events && want_scan_ev;
         hipEvent_t fs0 = nullptr, fs1 = nullptr;
         kev_pick(ctx, VC_K_FINISH_SCAN, fs0, fs1);
-        if (scan_ridden) { fs1 = sb.e_scan; if (fs0) sb.kused[VC_K_FINISH_SCAN][1] = fs1; }
-        hipExtLaunchKernelGGL(k_finish_scan, dim3(grid_for(ngroups)), block, 0, s2, fs0, fs1, 0,
-                              (const uint64_t *)sb.blocksum.ptr, nscan, sb.blockoff.ptr, sb.h_total.ptr, (const uint32_t *)sb.busysum.ptr, sb.busyblock.ptr,
-                              (const uint32_t *)sb.groupcnt.ptr, ngroups, (const uint32_t *)sb.busyoff.ptr, sb.busylist.ptr, (uint32_t)ctx->dbg);
+        if (r.scan_ridden) { fs1 = sb.e_scan; if (fs0) sb.kused[VC_K_FINISH_SCAN][1] = fs1; }
+        hipExtLaunchKernelGGL(k_finish_scan, dim3(grid_for(z.ngroups)), block, 0, st, fs0, fs1, 0,
+                              (const uint64_t *)sb.blocksum.ptr, z.nscan, sb.blockoff.ptr, sb.h_total.ptr, (const uint32_t *)sb.busysum.ptr, sb.busyblock.ptr,
+                              (const uint32_t *)sb.groupcnt.ptr, z.ngroups, (const uint32_t *)sb.busyoff.ptr, sb.busylist.ptr, (uint32_t)ctx->dbg);
         VC_HIP(ctx, hipGetLastError());
-    } else if (nscan > 1) {
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanThreads), 0, s2, sb.blocksum.ptr, nscan, sb.blockoff.ptr, sb.h_total.ptr);
+    } else if (z.nscan > 1) {
+        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(kScanThreads), 0, st, sb.blocksum.ptr, z.nscan, sb.blockoff.ptr, sb.h_total.ptr);
         VC_HIP(ctx, hipGetLastError());
     }
+    return VC_OK;
+}
 
+// Stage 7: the expansion's parameters (kept with the step for a re-run after a records regrow)
+static void step_emit_params(const vc_ctx *ctx, StepBuf &sb, const StepSize &z, const CarveParams &p)
+{
+    const StepRoute &r = sb.route;
     EmitParams &e = sb.emit;
-    memset(&e, 0, sizeof e);
-    e.xs = p.xs; e.ys = p.ys; e.zs = p.zs;
+    emit_color_source(ctx, sb.slot, sb.color_cam, e);
     e.words = sb.words.ptr; e.groupcnt = sb.groupcnt.ptr; e.groupoff = sb.groupoff.ptr; e.blockoff = sb.blockoff.ptr;
-    e.n = n; e.i0 = ctx->i0(); e.ngroups = ngroups;
-    e.nx = ctx->nx; e.ny = ctx->ny; e.z0 = ctx->z0; e.H = ctx->H; e.W = ctx->W;
-    if (color_cam >= 0) {
-        e.has_cam = 1;
-        e.cam = ctx->cams[color_cam];
-        e.maskbits = s.bits.ptr + (size_t)color_cam * ctx->mwords;
-        if (s.frames.ptr && s.have_frame[color_cam])
-            e.frame = s.frames.ptr + (size_t)color_cam * ctx->H * ctx->W;
-        if (mode == VC_MODE_LUT && ctx->tile_valid && !ctx->ymajor_valid) {
-            e.lut = ctx->d_lut_tile.ptr + (size_t)color_cam * p.n_pad;      // the only table there is: tile order
-            e.lut_tq = p.tq;
-            if (sb.lut16) { e.lut16 = ctx->d_lut16.ptr; e.cbase = ctx->d_cbase.ptr; }   // ... and its compact form
-        }
-        else if (mode == VC_MODE_LUT) e.lut = ctx->d_lut.ptr + (size_t)color_cam * p.n_pad;
-        else if (ctx->fused_color_table && !sb.no_records) {
-            // table-free carve, but the colour look-up of the survivors reads the colour camera's table (4 B per
-            // voxel of the whole grid, one camera: made in front of this step's carve kernels, see above) instead of
-            // projecting every survivor again
-            e.lut = ctx->d_lut_color.ptr + ctx->i0();
-        }
+    e.n = z.n; e.i0 = ctx->i0(); e.ngroups = z.ngroups; e.z0 = ctx->z0;
+    if (r.emit_table == Table::Tile) {
+        e.lut = ctx->d_lut_tile.ptr + (size_t)sb.color_cam * p.n_pad;
+        e.lut_tq = p.tq;
+        if (r.lut16) { e.lut16 = ctx->d_lut16.ptr; e.cbase = ctx->d_cbase.ptr; }   // ... and its compact form
     }
-    e.records = sb.records.ptr;
-    e.capacity = sb.records.cap;
+    else if (r.emit_table == Table::YMajor) e.lut = ctx->d_lut.ptr + (size_t)sb.color_cam * p.n_pad;
+    // (table-free carve, but the survivors' colour look-up reads the colour camera's table instead of projecting each of them again)
+    else if (r.emit_table == Table::Color) e.lut = ctx->d_lut_color.ptr + ctx->i0();
+    e.records = sb.records.ptr; e.capacity = sb.records.cap;
     e.busylist = sb.busylist.ptr; e.busycount = sb.busyblock.ptr;
-    e.dbg = (uint32_t)ctx->dbg;
-    e.stats = p.stats;
+    e.dbg = (uint32_t)ctx->dbg; e.stats = p.stats;
+}
+
+// Stage 8: the record expansion on its stream (memory bound where the carve kernels are VALU-issue bound: it runs beside the carve of
+// the next step, two steps in flight), a rank's packing and exchange on theirs, and the step's events handed to the slot
+static int step_finish(vc_ctx *ctx, StepBuf &sb, Slot &s)
+{
+    const StepRoute &r = sb.route;
+    hipStream_t s3 = emit_stream(ctx), sx = exchange_stream(ctx);
+    sb.emit_ridden = r.ride;
     sb.emit_timed = false;
-    bool scan_recorded = false;                                  // e_scan recorded by THIS step (Slot::carve_pending may still be set by an earlier one)
-    if (want_scan_ev) {
-        if (!scan_ridden) VC_HIP(ctx, hipEventRecord(sb.e_scan, ctx->stream));     // cross-stream dependency
+    if (r.scan_ev) {
+        if (!r.scan_ridden) VC_HIP(ctx, hipEventRecord(sb.e_scan, ctx->stream));     // cross-stream dependency
         if (!sb.no_records && s3 != ctx->stream) VC_HIP(ctx, hipStreamWaitEvent(s3, sb.e_scan, 0));
-        if (xstream) VC_HIP(ctx, hipStreamWaitEvent(sx, sb.e_scan, 0));
+        if (r.xstream) VC_HIP(ctx, hipStreamWaitEvent(sx, sb.e_scan, 0));
         sb.emit_timed = !sb.no_records;
-        scan_recorded = true;
     }
     if (!sb.no_records) {
-        VC_TRY(launch_emit(ctx, sb, s3, ride ? sb.e_emit0 : nullptr, ride ? sb.e2 : nullptr));
-        if (ride) sb.emit_timed = true;
+        VC_TRY(launch_emit(ctx, sb, s3, r.ride ? sb.e_emit0 : nullptr, r.ride ? sb.e2 : nullptr));
+        if (r.ride) sb.emit_timed = true;
     }
-    if (auto_exchange) {
+    if (r.exchange) {
         VC_TRY(enqueue_pack(ctx, sb, sx));
         VC_TRY(enqueue_counts_exchange(ctx, sb, sx));
         sb.counts_exchanged = true;
     }
-    if (!ride || auto_exchange) VC_HIP(ctx, hipEventRecord(sb.e2, auto_exchange ? sx : sb.no_records ? s2 : s3));
+    if (!r.ride || r.exchange) VC_HIP(ctx, hipEventRecord(sb.e2, r.exchange ? sx : sb.no_records ? ctx->stream : s3));
     if (!sb.no_records && s3 != ctx->stream) { s.e_emit = sb.e2; s.emit_pending = true; }   // the expansion reads the slot's bits / images
     // ... and, table-free with a colour camera, the one whole-grid colour table: a later step that names another camera waits
-    if (!sb.no_records && s3 != ctx->stream && mode == VC_MODE_FUSED && e.lut) ctx->lut_color_reader = sb.e2;
-    // the slot's next preparation waits for the kernels of THIS step that read its bits / grids: always this step's own event
-    // (a flag left set by an earlier step on the same slot must not keep that step's event in place: the preparation would
-    // then overwrite bits and grids under this step's carve).  Without e_scan, e2 is behind the carve kernels too.
-    s.e_carve = scan_recorded ? sb.e_scan : sb.e2;
+    if (!sb.no_records && s3 != ctx->stream && r.emit_table == Table::Color) ctx->lut_color_reader = sb.e2;
+    // the slot's next preparation waits for the kernels of THIS step that read its bits / grids: always this step's own event (a flag left set by
+    // an earlier step on the slot must not keep that step's event in place: the preparation would then overwrite bits and grids under this
+    // step's carve).  Without e_scan, e2 is behind the carve kernels too.
+    s.e_carve = r.scan_ev ? sb.e_scan : sb.e2;
     s.carve_pending = true;
-    ctx->kev_sb = nullptr;
-    sb.pending = true;
-    sb.used = true;
-    ctx->head = (ctx->head + 1) % kDepth;
-    ctx->npending++;
+    sb.pending = sb.used = true; ctx->head = (ctx->head + 1) % kDepth; ctx->npending++;
     return VC_OK;
+}
+
+// A step, stage by stage
+static int step_begin(vc_ctx *ctx, StepRequest rq)
+{
+    if (!ctx) return VC_ERR_ARG;
+    if (ctx->npending >= kDepth) return fail(ctx, VC_ERR_ARG, "%d carve steps are already in flight: call vc_carve_end", kDepth);
+    if (!ctx->have_grid || !ctx->have_cams) return fail(ctx, VC_ERR_ARG, "grid and cameras must be set before vc_carve");
+    if (rq.slot >= ctx->slots.size() || !ctx->slots[rq.slot].have_masks)
+        return fail(ctx, VC_ERR_ARG, "no masks uploaded in slot %u", rq.slot);
+    if (rq.mode != VC_MODE_FUSED && rq.mode != VC_MODE_LUT) return fail(ctx, VC_ERR_ARG, "unknown mode %d", rq.mode);
+    if (rq.mode == VC_MODE_LUT && !ctx->lut_valid) return fail(ctx, VC_ERR_ARG, "VC_MODE_LUT needs vc_build_lut first");
+    if (rq.color_cam >= (int)ctx->C) return fail(ctx, VC_ERR_ARG, "colour camera %d not in [0,%u)", rq.color_cam, ctx->C);
+    if (rq.min_views < 1) rq.min_views = 1;      // a voxel no camera sees never enters voxels_visible
+    VC_HIP(ctx, hipSetDevice(ctx->device));
+    KevScope scope{ctx};
+    StepBuf &sb = step_open(ctx, rq);                                      // 1
+    CarveParams p;
+    fill_params(ctx, p);
+    sb.route = plan_route(ctx, rq, p.tile_whole != 0);                     // 3, first half (an empty slab keeps it too: mode, allseen, view masks)
+    if (sb.n == 0) return step_empty(ctx, sb);
+    Slot &s = ctx->slots[rq.slot];
+    const uint32_t ngroups = (uint32_t)(p.n_pad / (64 * kGroupWords));
+    const StepSize z{sb.n, (sb.n + 63) / 64, ngroups, (ngroups + kScanBlock - 1) / kScanBlock};
+    VC_TRY(step_size(ctx, rq, sb, z, p));                                  // 2
+    VC_TRY(step_prepare(ctx, rq, sb, s, z, p));                            // 4, with the route's second half behind the boxes
+    VC_TRY(step_carve(ctx, rq, sb, s, z, p));                              // 5
+    VC_TRY(step_scan(ctx, sb, z));                                         // 6
+    step_emit_params(ctx, sb, z, p);                                       // 7
+    return step_finish(ctx, sb, s);                                        // 8
+}
+
+int vc_carve_begin(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int mode, uint32_t flags)
+{
+    return step_begin(ctx, StepRequest{slot, min_views, color_cam, mode, flags, false, 0, 0});
 }
 
 // Completes the oldest step in flight: its survivor count, and its records become what the
@@ -2354,10 +2418,10 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
             sb.emit.records = sb.records.ptr;
             sb.emit.capacity = sb.records.cap;
             // (a later step may have packed the compact table for another colour camera since: d_lut_tile still holds this one's)
-            if (sb.emit.lut16 && ctx->lut16_cam != sb.color_cam) { sb.emit.lut16 = nullptr; sb.emit.cbase = nullptr; }
+            if (sb.route.lut16 && ctx->lut16_cam != sb.color_cam) { sb.emit.lut16 = nullptr; sb.emit.cbase = nullptr; }
             // (... or projected the whole-grid colour table for another camera: a table-free step then projects its survivors
             // itself, as with fused_color_table = 0 -- the same bytes, and the table stays the newer step's)
-            if (sb.mode == VC_MODE_FUSED && sb.emit.lut && ctx->lut_color_cam != sb.color_cam) sb.emit.lut = nullptr;
+            if (sb.route.emit_table == Table::Color && ctx->lut_color_cam != sb.color_cam) sb.emit.lut = nullptr;
             VC_TRY(launch_emit(ctx, sb, ctx->stream));
             sb.emit_ridden = false;
             VC_HIP(ctx, hipEventRecord(sb.e2, ctx->stream));
@@ -2369,7 +2433,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
             VC_HIP(ctx, hipEventElapsedTime(&ms, sb.e0, sb.e1));
             ctx->tm.carve_ms = ms;
             ctx->tm.first_ms = ms;                               // one kernel sequence does the whole carve ...
-            if (sb.has_first) VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.first_ms, sb.e0, sb.e_first));   // ... unless a streaming first pass was timed
+            if (sb.route.family == Carve::LutStream) VC_HIP(ctx, hipEventElapsedTime(&ctx->tm.first_ms, sb.e0, sb.e_first));   // ... unless a streaming first pass was timed
             ctx->tm.first_ms_sum += ctx->tm.first_ms;
             ctx->tm.carve_ms_sum += ms;
             ctx->tm.carve_launches += 1;
@@ -2411,7 +2475,7 @@ int vc_carve_end(vc_ctx *ctx, uint64_t *n_out)
     ctx->survivors = sb.survivors;
     ctx->tm.survivors = sb.survivors;
     ctx->carved = true;
-    ctx->viewmask_valid = sb.want_vm;
+    ctx->viewmask_valid = sb.route.viewmask;
     *n_out = sb.survivors;
     return VC_OK;
 }
@@ -2422,10 +2486,7 @@ int vc_carve(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color_cam, int 
     if (!ctx || !n_out) return VC_ERR_ARG;
     *n_out = 0;
     if (ctx->npending != 0) return fail(ctx, VC_ERR_ARG, "vc_carve with steps in flight: drain them with vc_carve_end");
-    ctx->sync_call = true;
-    const int rc = vc_carve_begin(ctx, slot, min_views, color_cam, mode, flags);
-    ctx->sync_call = false;
-    if (rc != VC_OK) return rc;
+    VC_TRY(step_begin(ctx, StepRequest{slot, min_views, color_cam, mode, flags, true, 0, 0}));
     return vc_carve_end(ctx, n_out);
 }
 
@@ -2440,12 +2501,7 @@ int vc_carve_footprint(vc_ctx *ctx, uint32_t slot, uint32_t min_views, int color
     if (rule != VC_FOOT_ANY && rule != VC_FOOT_COVER) return fail(ctx, VC_ERR_ARG, "unknown footprint rule %u (VC_FOOT_ANY, VC_FOOT_COVER)", rule);
     if (rule == VC_FOOT_COVER && (q < 1 || q > 256)) return fail(ctx, VC_ERR_ARG, "footprint cover q = %u not in 1..256", q);
     if (flags & ~(uint32_t)(VC_FLAG_VIEWMASK | VC_FLAG_NO_RECORDS)) return fail(ctx, VC_ERR_ARG, "unknown flags 0x%x", flags);
-    ctx->sync_call = true;
-    ctx->foot_rule = rule; ctx->foot_q = rule == VC_FOOT_COVER ? q : 1u;
-    const int rc = vc_carve_begin(ctx, slot, min_views, color_cam, VC_MODE_FUSED, flags);
-    ctx->sync_call = false;
-    ctx->foot_rule = 0;
-    if (rc != VC_OK) return rc;
+    VC_TRY(step_begin(ctx, StepRequest{slot, min_views, color_cam, VC_MODE_FUSED, flags, true, rule, rule == VC_FOOT_COVER ? q : 1u}));
     return vc_carve_end(ctx, n_out);
 }
 
