@@ -701,6 +701,57 @@ int vc_shade_render(vc_ctx *ctx, const double *light /* [n_views][3] */, uint32_
 int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb);     /* [H W 3] */
 int vc_surface_normals(vc_ctx *ctx, int16_t *n4);                  /* [V][4], vertex order of vc_fetch_surface_mesh */
 
+/* ---- free-viewpoint images: sub-voxel ray hits textured from the camera frames (no reference counterpart) -------------------------
+ * vc_texture_render is a pass over the images of the last vc_render, like vc_shade_render: every hit is refined along its own ray
+ * against the silhouettes, and the pixel is coloured from the cameras that see the refined point, weighted by how close they look
+ * to the viewing direction.  It reads the render's images, the current carve result's cameras, masks and threshold, the depth maps
+ * of a current vc_color_visible and the images of frame set `slot` (every camera needs one); it changes none of them, and
+ * vc_fetch_render, vc_fetch_shaded and the records stay as they are.  The contract, bit for bit (tests/texture_np.py restates it);
+ * float64 with no contraction, in the order written, unless stated otherwise.  Per pixel of each view of the last render; a miss
+ * keeps the render's pixel:
+ *   1 ray: o, d = item 2 of vc_render for the stored view; t0 = (double)depth of the render; P(t)_j = o_j + t * d_j (one multiply,
+ *     one add).
+ *   2 inside(P) = item 2 of vc_surface_mesh: the carve's cameras, the post-filtered masks the carve read, T(P) >= m.
+ *   3 refinement, steps in 0..24, reach_mm = L >= 0.  With steps > 0: in0 = inside(P(t0)); (lo, hi) = in0 ? (max(t0 - L, 0), t0) :
+ *     (t0, t0 + L); the pixel is REFINED iff !inside(P(lo)) && inside(P(hi)); then `steps` times mid = (lo + hi) * 0.5,
+ *     inside(P(mid)) ? hi = mid : lo = mid, and t = (lo + hi) * 0.5.  Otherwise (steps = 0, L = 0, the view inside the hull, or
+ *     an occupancy that disagrees with the point test: a photo carve, a foreign lookup table) t = t0.  Output depth = (float)t.
+ *   4 candidates, P = P(t): camera c of the carve with d_c = camera z of P (item 3 of vc_color_visible) and (u, v) = the carve's
+ *     projection of P is a candidate iff d_c > 0, 0 <= v < H_c and 0 <= u < W_c on the floats, and (float)d_c <=
+ *     zmap_c[int(v) W_c + int(u)] + tol (the add in float32), zmap_c = the current vc_color_visible map of c, tol = depth_tolerance.
+ *   5 weight of a candidate: C_c,j = -((R[0][j]*t0 + R[1][j]*t1) + R[2][j]*t2) from camera c's R and t (as item 2 of vc_render
+ *     makes o); a = C_c - P, b = o - P; dot = (a0*b0 + a1*b1) + a2*b2, aa and bb alike; c = (dot > 0 and aa * bb is a finite
+ *     normal number) ? min(dot / sqrt(aa * bb), 1.0) : 0.0; then `sharpen` times (0..6) c = c * c; w_c = (uint32_t)floor(c * 65535.0
+ *     + 0.5).  A camera that is no candidate has w_c = 0.  Only the `best` (1..16) largest weights stay, ties to the lower camera
+ *     index; the others count as 0.
+ *   6 sample of camera c's image of `slot`, read as RGB.  filter = 0: pixel int(v) W_c + int(u).  filter = 1, bilinear in integers:
+ *     fu = u - 0.5, x0 = floor(fu), ax = (int)floor((fu - x0) * 256.0); fv, y0, ay alike; columns x0, x0 + 1 and rows y0, y0 + 1
+ *     clamped into the image; per channel ch = ((p00 (256 - ax) + p10 ax)(256 - ay) + (p01 (256 - ax) + p11 ax) ay + 32768) >> 16,
+ *     p10 = the pixel at column x0 + 1 of row y0, p01 = column x0 of row y0 + 1.
+ *   7 blend: Ws = sum of the w_c that stayed.  Ws == 0: the pixel keeps the render's rgb, count = 0, best_cam = 255.  Otherwise per
+ *     channel ch = (sum w_c ch_c + Ws / 2) / Ws in 64-bit integers, count = the cameras with w_c > 0 that stayed, best_cam = the
+ *     heaviest of them.  A miss has count = 0, best_cam = 255, refined = 0 and depth +inf.
+ * stats (required): pixels = n_views H W, hits, refined, textured = hits with Ws > 0, fallback = hits with Ws == 0 (all contract);
+ * point_tests = camera tests of item 2 the device evaluated (a diagnostic: it stops a point's test once it is decided);
+ * texture_ms = HIP events around the whole call.  VC_ERR_ARG (with a message, nothing launched, the textured images of an
+ * earlier call left as they were) when there is no carve result, steps are in flight, the carve ran with VC_FLAG_NO_RECORDS, the
+ * slab is narrower than the grid, a communicator of more than one rank is attached, the last render is missing or did not run on
+ * the current result, vc_color_visible has not run on the current result, a camera of `slot` has no image, steps > 24, best
+ * outside 1..16, sharpen > 6, filter > 1, reach_mm or depth_tolerance negative or not finite, flags != 0, stats == NULL, or --
+ * with steps > 0 -- the carve's frame set has been prepared again since the carve or has new masks or images waiting for it
+ * (vc_surface_mesh's rule).  An empty hull is no error.  Synchronous.
+ * The images stay valid until the next vc_texture_render, the next vc_render or vc_destroy.  vc_fetch_textured copies one view
+ * out (rgb [H W 3], the others [H W]; any pointer may be NULL); it fails before the first vc_texture_render on the last render
+ * and for view >= n_views. */
+typedef struct {
+    uint64_t pixels, hits, refined, textured, fallback;   /* contract: textured + fallback = hits */
+    uint64_t point_tests;                                 /* diagnostic, implementation-defined */
+    float texture_ms;                                     /* HIP events around the whole call */
+} vc_texture_stats_t;
+int vc_texture_render(vc_ctx *ctx, uint32_t slot, uint32_t steps, double reach_mm, float depth_tolerance, uint32_t best,
+                      uint32_t sharpen, uint32_t filter, uint32_t flags /* must be 0 */, vc_texture_stats_t *stats);
+int vc_fetch_textured(vc_ctx *ctx, uint32_t view, uint8_t *rgb, float *depth, uint8_t *count, uint8_t *best_cam, uint8_t *refined);
+
 /* ---- the hull split into K figures on the floor plane (no reference counterpart) --------------------------------------------------
  * vc_hull_clusters runs K-means over the columns of the current carve result, as vc_fetch_occupancy and vc_fetch_records see it
  * (photo carve, components, morphology, grow and footprint rules included): world "up" is -z, so a floor position is a column

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--save-hull PATH] [--subtract PATH] [--clip PATH] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--textured] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--save-hull PATH] [--subtract PATH] [--clip PATH] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -11,7 +11,9 @@ voxel when any pixel its whole cell projects to is foreground (the outer hull), 
 what is thinner than the ball leaves the hull; --close MM: the hull closed by a ball of MM millimetres on the device after the
 carve and before any opening, assignment.configure(hull_close_mm=MM) -- tunnels and dents narrower than the ball are filled, which
 is what a hole in one camera's mask carves; --smooth (with --render): every hit shaded by the hull's surface normal under a
-headlight, assignment.render_views(smooth=True), instead of the six face brightnesses; --normals (with --mesh): the PLY carries
+headlight, assignment.render_views(smooth=True), instead of the six face brightnesses; --textured (with --render; colour mode `visible`, the default with it): every hit refined
+along its ray against the silhouettes and coloured from the camera images that see it, assignment.render_views(textured=True);
+--normals (with --mesh): the PLY carries
 nx, ny, nz per vertex, assignment.surface_mesh(normals=True); --clusters K: the hull split into K figures on the floor plane on
 the device, assignment.configure(clusters=K) -- their floor positions in world mm and their sizes are printed; --cluster-paint
 (with --clusters): every voxel in its figure's colour, in the PLY, the --render images and the --mesh;
@@ -49,6 +51,9 @@ from voxcarve import assignment
 smooth = "--smooth" in sys.argv
 if smooth:
     sys.argv.remove("--smooth")
+textured = "--textured" in sys.argv
+if textured:
+    sys.argv.remove("--textured")
 with_normals = "--normals" in sys.argv
 if with_normals:
     sys.argv.remove("--normals")
@@ -146,7 +151,9 @@ for flag, conv in (("--temporal", int), ("--frames", int), ("--noise", float)):
             noise = value
 g = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 out = sys.argv[2] if len(sys.argv) > 2 else "hull.ply"
-color_mode = sys.argv[3] if len(sys.argv) > 3 else "camera"
+color_mode = sys.argv[3] if len(sys.argv) > 3 else ("visible" if textured else "camera")
+if textured and color_mode != "visible":
+    sys.exit("--textured needs the colour mode `visible`: its depth maps say which cameras see a point")
 hull = "photo" if color_mode == "photo" else "visual"
 color_mode = "visible" if color_mode == "photo" else color_mode
 masks = fx.golden_masks()
@@ -249,7 +256,13 @@ if render_dir:
     os.makedirs(render_dir, exist_ok=True)
     shade = (200, 200, 225, 225, 255, 150, 255)        # x sides, y sides, top (rays along +z: up is -z), bottom, inside
     orbit = camera.orbit(8, 4500.0, 25.0, 1500.0, 1080, 1920)
-    if smooth:
+    if textured:
+        r = assignment.render_views(orbit, 1920, 1080, textured=True)
+        c = assignment.render_views(textured=True)
+        ts = r["texture_stats"]
+        print("textured: %d of %d hits refined along their rays, %d coloured from the camera images, %d kept the voxel colour "
+              "(%.2f ms for 8 views on the device)" % (ts["refined"], ts["hits"], ts["textured"], ts["fallback"], ts["texture_ms"]))
+    elif smooth:
         r = assignment.render_views(orbit, 1920, 1080, smooth=True)
         c = assignment.render_views(smooth=True)
     else:

@@ -198,6 +198,11 @@ class VcSurfaceStats(ctypes.Structure):
                 ("unrefined", ctypes.c_uint64), ("point_tests", ctypes.c_uint64), ("surface_ms", ctypes.c_float)]
 
 
+class VcTextureStats(ctypes.Structure):
+    _fields_ = [("pixels", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("refined", ctypes.c_uint64), ("textured", ctypes.c_uint64),
+                ("fallback", ctypes.c_uint64), ("point_tests", ctypes.c_uint64), ("texture_ms", ctypes.c_float)]
+
+
 class VcComponent(ctypes.Structure):
     _fields_ = [("label", ctypes.c_uint32), ("size", ctypes.c_uint32), ("lo", ctypes.c_uint32 * 3), ("hi", ctypes.c_uint32 * 3),
                 ("kept", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
@@ -296,6 +301,9 @@ SIGNATURES = {
     "vc_shade_render": (ctypes.c_int, [c_ctx, c_f64p, ctypes.c_uint32, ctypes.c_uint32]),
     "vc_fetch_shaded": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p]),
     "vc_surface_normals": (ctypes.c_int, [c_ctx, c_i16p]),
+    "vc_texture_render": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_float, ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcTextureStats)]),
+    "vc_fetch_textured": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, ctypes.POINTER(ctypes.c_float), c_u8p, c_u8p, c_u8p]),
     "vc_hull_clusters": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                         c_i64p, ctypes.c_uint32, ctypes.POINTER(VcClusterStats)]),
     "vc_fetch_cluster_labels": (ctypes.c_int, [c_ctx, c_u8p]),

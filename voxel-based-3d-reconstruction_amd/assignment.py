@@ -571,18 +571,27 @@ def _ensure_normals():
         _engine.hull_normals(_settings["normal_radius_mm"])
 
 
-def render_views(views=None, width=None, height=None, shade=None, smooth=False, ambient=64):
+def render_views(views=None, width=None, height=None, shade=None, smooth=False, ambient=64, textured=False, texture_steps=8):
     """Images of the hull of the last set_voxel_positions call, after whatever configure(...) asked for (component filter,
     photo carve, colouring), ray-cast on the device (CarveEngine.render): views = a list of camera.Camera (default: the
     calibrated cameras), width x height pixels (default: the mask size).  Returns the dict of CarveEngine.render: rgb
     [V, H, W, 3], depth, index, face and stats.  smooth=True shades every hit by the hull's surface normal under a headlight
     per view instead of the six face brightnesses of `shade` (CarveEngine.render_shaded: rgb is the shaded image, rgb_flat the
-    unshaded one; ambient 0..255 is the brightness of a surface that faces away)."""
+    unshaded one; ambient 0..255 is the brightness of a surface that faces away).  textured=True colours every hit from the
+    frame's camera images instead of its voxel, after texture_steps bisection steps along the ray against the silhouettes
+    (CarveEngine.render_textured: rgb is the textured image, rgb_voxels the render's own, depth the refined one); it needs
+    configure(color_mode="visible"), whose depth maps say which cameras see a point, and excludes smooth and shade."""
     if _engine is None or not initialized or _engine._sized is None:
         raise RuntimeError("set_voxel_positions has not run")
     H, W = _engine.image_size
     views = _engine._cameras if views is None else views
     H, W = H if height is None else height, W if width is None else width
+    if textured:
+        if smooth or shade is not None:
+            raise ValueError("render_views: textured=True takes its colours from the camera images; smooth and shade are the voxel render's")
+        if _settings["color_mode"] != "visible":
+            raise ValueError("render_views: textured=True needs configure(color_mode=\"visible\")")
+        return _engine.render_textured(views, H, W, slot=0, steps=texture_steps)
     if smooth:
         if shade is not None:
             raise ValueError("render_views: shade is the flat render's; smooth=True shades by the normals")

@@ -957,6 +957,64 @@ class CarveEngine:
         out["rgb"] = self.shade_render(light, ambient)
         return out
 
+    # -- free-viewpoint images: refined ray hits textured from the camera frames (vc_texture_render) ----------------------------------
+    def visibility_valid(self):
+        """True while the depth maps of the last color_visible() belong to the current hull."""
+        if self.image_size is None:
+            return False
+        out = np.empty(self.image_size, dtype=np.float32)
+        return self._L.vc_fetch_depth(self._ctx, 0, _ptr(out, ctypes.c_float)) == _lib.VC_OK
+
+    def texture_render(self, slot=0, steps=8, reach_mm=None, depth_tolerance=None, best=2, sharpen=2, filter="bilinear"):
+        """Textures the images of the last render() from the camera frames of `slot` (needs a current color_visible() and a
+        render of the current result; contract: include/voxcarve.h).  Every hit is moved along its ray by `steps` bisection
+        steps of the carve's own point test within reach_mm of the voxel face (None: the voxel diagonal), then coloured from the
+        `best` cameras that see the point past color_visible's depth maps (depth_tolerance None: default_depth_tolerance()),
+        weighted by the cosine between their direction and the viewing direction, squared `sharpen` times; filter "nearest" or
+        "bilinear".  Nothing else changes.  Returns a dict: rgb u8 [V, H, W, 3] (the render's own where no camera sees the
+        point), depth f32 [V, H, W], count u8 [V, H, W] (cameras blended), best_cam u8 [V, H, W] (255: none), refined bool
+        [V, H, W] and stats (pixels, hits, refined, textured, fallback, point_tests, texture_ms)."""
+        filters = {"nearest": 0, "bilinear": 1, 0: 0, 1: 1}
+        if filter not in filters:
+            raise ValueError("texture_render: filter %r is neither 'nearest' nor 'bilinear'" % (filter,))
+        if self.grid is not None:
+            diag = self.default_depth_tolerance()
+        else:
+            diag = 0.0                                   # (no grid: the call reports it)
+        reach = diag if reach_mm is None else float(reach_mm)
+        tol = diag if depth_tolerance is None else float(depth_tolerance)
+        st = _lib.VcTextureStats()
+        self._check(self._L.vc_texture_render(self._ctx, int(slot), int(steps), reach, tol, int(best), int(sharpen), filters[filter], 0,
+                                              ctypes.byref(st)), "vc_texture_render")
+        V, (H, W) = self._render_shape
+        out = {"rgb": np.empty((V, H, W, 3), dtype=np.uint8), "depth": np.empty((V, H, W), dtype=np.float32),
+               "count": np.empty((V, H, W), dtype=np.uint8), "best_cam": np.empty((V, H, W), dtype=np.uint8)}
+        refined = np.empty((V, H, W), dtype=np.uint8)
+        for k in range(V):
+            self._check(self._L.vc_fetch_textured(self._ctx, k, _ptr(out["rgb"][k], ctypes.c_uint8), _ptr(out["depth"][k], ctypes.c_float),
+                                                  _ptr(out["count"][k], ctypes.c_uint8), _ptr(out["best_cam"][k], ctypes.c_uint8),
+                                                  _ptr(refined[k], ctypes.c_uint8)), "vc_fetch_textured")
+        out["refined"] = refined != 0
+        out["stats"] = {"pixels": int(st.pixels), "hits": int(st.hits), "refined": int(st.refined), "textured": int(st.textured),
+                        "fallback": int(st.fallback), "point_tests": int(st.point_tests), "texture_ms": float(st.texture_ms)}
+        return out
+
+    def render_textured(self, views, H, W, slot=0, steps=8, reach_mm=None, depth_tolerance=None, best=2, sharpen=2, filter="bilinear",
+                        background=(0, 0, 0)):
+        """render() + texture_render(): free-viewpoint images of the hull coloured from the camera frames.  Raises unless
+        color_visible() is current (it is not run here: it would recolour the records).  Returns render()'s dict with rgb
+        textured and rgb_voxels the render's own, depth refined and depth_voxels the render's own, count, best_cam, refined,
+        stats (the render's) and texture_stats."""
+        if not self.visibility_valid():
+            raise _lib.VoxcarveError("render_textured: no depth maps of the current hull: call color_visible() first")
+        out = self.render(views, H, W, background=background)
+        tex = self.texture_render(slot, steps, reach_mm, depth_tolerance, best, sharpen, filter)
+        out["rgb_voxels"], out["depth_voxels"] = out["rgb"], out["depth"]
+        for k in ("rgb", "depth", "count", "best_cam", "refined"):
+            out[k] = tex[k]
+        out["texture_stats"] = tex["stats"]
+        return out
+
     def surface_normals(self):
         """int16 [V, 4]: per vertex of the last surface_mesh() the stored normal of the voxel its colour comes from (the ON end
         of its grid edge).  Needs hull_normals() and a mesh of the current result."""
