@@ -502,14 +502,14 @@ def test_assignment_and_demo_end_to_end(built, cams, masks, frames, tmp_path):
             e = assignment._engine
             got = assignment.render_views(smooth=True, ambient=32)
             st = e.hull_normals(radius)
-            want = e.render_shaded(e._cameras, H, W, ambient=32)
+            want = e.render_shaded(e.cameras, H, W, ambient=32)
             assert np.array_equal(got["rgb"], want["rgb"]) and np.array_equal(got["rgb_flat"], want["rgb_flat"])
             assert (got["rgb"] != got["rgb_flat"]).any() and st["surface"] == 2703
             rec, idx, occ, q = _hull(e)
             n4, _ = nn.normals(occ, q, nn.default_r2(q) if radius is None else dn.radius_r2(radius))
             assert np.array_equal(e.fetch_record_normals(), n4)
             flat = assignment.render_views()
-            assert "rgb_flat" not in flat and np.array_equal(flat["rgb"], e.render(e._cameras, H, W)["rgb"])
+            assert "rgb_flat" not in flat and np.array_equal(flat["rgb"], e.render(e.cameras, H, W)["rgb"])
             with pytest.raises(ValueError):
                 assignment.render_views(smooth=True, shade=(255,) * 7)
             mesh = assignment.surface_mesh(4, normals=True)

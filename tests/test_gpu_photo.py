@@ -214,7 +214,7 @@ def test_set_voxel_positions_photo_hull_both_sources(built):
             dev.append(assignment.set_voxel_positions(64, 32, 64))
             status.append(assignment.voxels_status().copy())
             sets.append((fs, [assignment._engine.fetch_mask(c) for c in range(4)]))     # the masks the device carved
-        cams = assignment._engine._cameras
+        cams = assignment._engine.cameras
         assignment.configure(frame_source=assignment.StaticFrameSource(sets), data_path=data, hull="photo", photo_var_threshold=900)
         static = [assignment.set_voxel_positions(64, 32, 64) for _ in sets]
         assert assignment.set_voxel_positions(64, 32, 64) == ([], [])

@@ -250,11 +250,11 @@ def test_render_views_after_configure(built, cams, masks, frames):
         assignment.set_voxel_positions(64, 32, 64)
         e = assignment._engine
         got = assignment.render_views()
-        want = e.render(e._cameras, H, W)
+        want = e.render(e.cameras, H, W)
         for k in ("index", "depth", "face", "rgb"):
             assert np.array_equal(got[k], want[k])
         occ, idx, rgb = _state(e)
-        ref = rn.render(occ, idx, rgb, e.grid, e.bounds, [rn.view_params(v) for v in e._cameras], H, W, block=8)
+        ref = rn.render(occ, idx, rgb, e.grid, e.bounds, [rn.view_params(v) for v in e.cameras], H, W, block=8)
         assert np.array_equal(got["index"].reshape(4, -1), ref["index"])
         orb = _orbit(2)
         assert np.array_equal(assignment.render_views(orb, 320, 240)["rgb"], e.render(orb, 240, 320)["rgb"])

@@ -183,7 +183,7 @@ def test_set_voxel_positions_visible_mode_both_sources(built):
         for fs in frame_sets:
             dev.append(assignment.set_voxel_positions(64, 32, 64))
             sets.append((fs, [assignment._engine.fetch_mask(c) for c in range(4)]))     # the masks the device carved
-        cams = assignment._engine._cameras
+        cams = assignment._engine.cameras
         assignment.configure(frame_source=assignment.StaticFrameSource(sets), data_path=data, color_mode="visible")
         static = [assignment.set_voxel_positions(64, 32, 64) for _ in sets]
         assert assignment.set_voxel_positions(64, 32, 64) == ([], [])

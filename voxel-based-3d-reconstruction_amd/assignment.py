@@ -10,6 +10,7 @@ The default source reuses the reference's own ``background_subtraction`` module 
 when this file is dropped into a reference checkout; tests and benchmarks install a
 ``StaticFrameSource``.
 """
+import collections
 import os
 
 import numpy as np
@@ -159,166 +160,268 @@ initialized = False
 frame_count = 0
 _engine = None
 _source = None
-_settings = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused",
-             "views_threshold": 4, "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS,
-             "color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200,
-             "min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26, "footprint": "centre",
-             "hull_open_mm": 0.0, "hull_border": "open", "hull_close_mm": 0.0, "normal_radius_mm": None,
-             "clusters": 0, "cluster_min_column": 1, "cluster_paint": False,
-             "extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None,
-             "temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None,
-             "hull_subtract": None, "hull_clip": None,
-             "measure": None, "measure_profile": False,
-             "skeleton": None, "skeleton_anchors": None,
-             "output": "all", "output_level": 0}
-_shell_state = {"last": None}
-OUTPUTS = ("all", "shell")
-_skeleton_state = {"last": None}
-SKELETONS = (None, "curve", "point")
-_measure_state = {"last": None, "centroids_mm": None}
-MEASURES = (None, "all", "clusters", "geodesic", "components")
-_temporal_state = {"last": None}
-_hull_ops_state = {"last": None}
+_cameras, _sized = None, None        # the calibrated cameras of data_path; the (H, W) the engine was last given them for
+_operands = False        # hull_subtract / hull_clip are in their registers (new cameras empty them)
+_last = {}               # the last frame's results, by stage: what the accessors below hand out
+_carry = {}              # what a frame leaves for the next: the clusters' centres_mm and references, the measure's centroids_mm
 HULL_SUBTRACT_REG, HULL_CLIP_REG = 3, 2      # the registers of CarveEngine that hold the two operands
-_cluster_state = {"centres_mm": None, "references": None, "last": None}
-_geodesic_state = {"last": None}
-GEODESIC_PAINTS = (None, "labels", "distance")
-COLOR_MODES = ("camera", "visible")
-HULLS = ("visual", "photo")
+BASE_SETTINGS = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused", "views_threshold": 4,
+                 "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS, "footprint": "centre", "normal_radius_mm": None}
+
+
+# -- the checks of configure(): a check takes the merged settings and raises ValueError; these make one for the setting `name` ----
+def _one_of(name, allowed):
+    def check(s):
+        if s[name] not in allowed:
+            raise ValueError("%s %r, expected one of %s" % (name, s[name], allowed))
+    return check
+
+
+def _integer(name, hi, bools=True):
+    def check(s):
+        if (isinstance(s[name], bool) and not bools) or not isinstance(s[name], (int, np.integer)) or not 0 <= s[name] <= hi:
+            raise ValueError("%s %r, expected an integer in 0..%d" % (name, s[name], hi))
+    return check
+
+
+def _operand(name):
+    def check(s):
+        if s[name] is not None and not isinstance(s[name], (str, os.PathLike, np.ndarray)):
+            raise ValueError("%s %r, expected a path, an array or None" % (name, s[name]))
+    return check
+
+
+def _check_temporal(s):
+    t = s["temporal_window"]
+    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0:
+        raise ValueError("temporal_window %r, expected an integer in 0..15" % (t,))
+    CarveEngine.temporal_thresholds(t if t > 0 else 1, s["temporal_keep"] if t > 0 else None, s["temporal_keep_off"] if t > 0 else None)
+
+
+def _check_min_column(s):
+    if int(s["cluster_min_column"]) < 0:
+        raise ValueError("cluster_min_column %r is negative" % (s["cluster_min_column"],))
+
+
+def _check_seeds(s):
+    if isinstance(s["geodesic_seeds"], str) and s["geodesic_seeds"] not in ("floor", "top"):
+        raise ValueError("geodesic_seeds %r, expected \"floor\", \"top\" or an array of voxel indices" % (s["geodesic_seeds"],))
+
+
+def _check_profile(s):
+    if not isinstance(s["measure_profile"], (bool, np.bool_)):
+        raise ValueError("measure_profile %r, expected True or False" % (s["measure_profile"],))
+
+
+def _check_anchors(s):
+    if s["skeleton_anchors"] not in (None, "extrema"):
+        raise ValueError('skeleton_anchors %r, expected None or "extrema"' % (s["skeleton_anchors"],))
+
+
+def _check_across(s):                                            # (what one stage's settings ask of another's)
+    if s["measure"] == "clusters" and not s["clusters"] > 0:
+        raise ValueError('measure="clusters" needs clusters=K')
+    if s["measure"] == "geodesic" and not s["extremities"] > 0:
+        raise ValueError('measure="geodesic" needs extremities=K')
+    if s["measure"] == "components" and not _components_on(s):
+        raise ValueError('measure="components" needs the component filter: min_component_voxels or keep_components')
+    if s["skeleton"] is not None and s["skeleton_anchors"] == "extrema" and not s["extremities"] > 0:
+        raise ValueError('skeleton_anchors="extrema" needs extremities=K')
+    if s["output_level"] != 0 and s["output"] != "shell":
+        raise ValueError('output_level=%d needs output="shell"' % s["output_level"])
+
+
+def _components_on(s):
+    return bool(s["min_component_voxels"] or s["keep_components"])
+
+
+def _recolours(s):                                               # (from every camera's image: the frame uploads them all)
+    return s["hull"] == "photo" or s["color_mode"] == "visible"
+
+
+# -- what the stages run: each takes the settings, works on _engine and keeps what its accessor hands out in _last ---------------
+def _run_clip(s):
+    ops = _last["hull_ops"] if s["hull_subtract"] is not None else {}                        # (this frame's, made a moment ago)
+    _last["hull_ops"] = dict(ops, clip=_engine.combine_hull("and", HULL_CLIP_REG))
+
+
+def _run_clusters(s):
+    """The frame's split into figures, warm-started from the previous frame's centres (see configure)."""
+    from .clusters import MATCH_MAX_K, match
+    K = int(s["clusters"])
+    out = _engine.cluster_hull(K, min_column=int(s["cluster_min_column"]), init_mm=_carry.get("centres_mm"))
+    out["figures"] = _engine.fetch_clusters()
+    out["histograms"] = _engine.fetch_cluster_histograms()
+    if _carry.get("references") is None:
+        _carry["references"] = out["histograms"].copy()
+    out["identity"] = match(_carry["references"], out["histograms"]) if K <= MATCH_MAX_K else None
+    _carry["centres_mm"] = out["centres_mm"]
+    _last["clusters"] = out
+    if s["cluster_paint"]:
+        _engine.paint_clusters()
+
+
+def _run_extremities(s):
+    """The frame's geodesic distances and extremities (see configure)."""
+    out = _engine.hull_geodesic(seeds=s["geodesic_seeds"], extrema=int(s["extremities"]), paths=True)
+    out["extrema"] = _engine.fetch_extrema()
+    out["paths"] = _engine.stick_figure()
+    _last["extremities"] = out
+    if s["geodesic_paint"] is not None:
+        _engine.paint_geodesic(s["geodesic_paint"])
+
+
+def _run_measure(s):
+    """The frame's measurements (see configure); with "clusters", label k is the same figure from frame to frame, so the
+    centroid's step since the previous frame is the figure's displacement."""
+    from . import measure
+    source = s["measure"]
+    if source == "components":
+        try:
+            _engine.component_ranks()
+        except ValueError:                                       # the filter removed something: label its output
+            _engine.filter_components(connectivity=s["component_connectivity"])
+    out = _engine.measure_hull(labels=source, profile=bool(s["measure_profile"]))
+    out["source"] = source
+    out["integers"] = _engine.fetch_measure()
+    out["world"] = measure.describe(out["integers"], _engine.grid, _engine.bounds)
+    if s["measure_profile"]:
+        out["profile"] = _engine.fetch_measure_profile()
+    if source == "clusters":
+        c = out["world"]["centroid_mm"]
+        prev = _carry.get("centroids_mm")
+        out["velocity_mm"] = None if prev is None or prev.shape != c.shape else c - prev
+        _carry["centroids_mm"] = c.copy()
+    _last["measure"] = out
+
+
+def _run_skeleton(s):
+    """The frame's skeleton (see configure)."""
+    from . import skeleton as sk
+    stats = _engine.thin_hull(s["skeleton"], anchors=s["skeleton_anchors"])
+    rows = _engine.fetch_skeleton()
+    _last["skeleton"] = {"stats": stats, "skeleton": rows, "description": sk.describe(rows, _engine.grid, _engine.bounds)}
+
+
+def _run_output(s):                                              # (returns what set_voxel_positions returns)
+    if s["output"] == "shell":
+        _last["shell"] = _engine.hull_shell(int(s["output_level"]))
+        return _engine.fetch_shell_viewer()
+    idx, rgb, _ = _engine.fetch()
+    keys = voxel_keys(idx, _engine.grid, _engine.axes())
+    return viewer_positions(keys), viewer_colors(rgb)
+
+
+# The frame chain: what follows every carve, IN THIS ORDER.  This list is the one place that says it; configure()'s docstring
+# numbers its paragraphs by it.  A stage names the settings it owns with their defaults, the checks of them (configure), whether
+# the settings turn it on, and what it runs on _engine.  The last stage is always on and returns what set_voxel_positions does.
+Stage = collections.namedtuple("Stage", "name defaults checks on run")
+STAGES = [
+    Stage("hull_subtract", {"hull_subtract": None}, [_operand("hull_subtract")], lambda s: s["hull_subtract"] is not None,
+          lambda s: _last.update(hull_ops={"subtract": _engine.combine_hull("andnot", HULL_SUBTRACT_REG)})),
+    Stage("hull_clip", {"hull_clip": None}, [_operand("hull_clip")], lambda s: s["hull_clip"] is not None, _run_clip),
+    Stage("temporal", {"temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None}, [_check_temporal],
+          lambda s: s["temporal_window"] > 0,
+          lambda s: _last.update(temporal=_engine.temporal_filter(s["temporal_window"], s["temporal_keep"], s["temporal_keep_off"]))),
+    Stage("close", {"hull_close_mm": 0.0}, [lambda s: CarveEngine.radius_r2(s["hull_close_mm"])], lambda s: s["hull_close_mm"] > 0,
+          lambda s: _engine.close_hull(s["hull_close_mm"])),
+    Stage("open", {"hull_open_mm": 0.0, "hull_border": "open"},
+          [lambda s: CarveEngine.radius_r2(s["hull_open_mm"]), lambda s: CarveEngine._dist_flags(s["hull_border"])],
+          lambda s: s["hull_open_mm"] > 0, lambda s: _engine.open_hull(s["hull_open_mm"], border=s["hull_border"])),
+    Stage("components", {"min_component_voxels": 0, "keep_components": 0, "component_connectivity": 26}, [], _components_on,
+          lambda s: _engine.filter_components(connectivity=s["component_connectivity"], min_voxels=s["min_component_voxels"],
+                                              keep_largest=s["keep_components"])),
+    Stage("colour", {"color_mode": "camera", "hull": "visual", "photo_var_threshold": 1200},
+          [_one_of("color_mode", ("camera", "visible")), _one_of("hull", ("visual", "photo"))], _recolours,
+          lambda s: (_engine.photo_carve(slot=0, var_threshold=s["photo_var_threshold"]) if s["hull"] == "photo"
+                     else _engine.color_visible(slot=0))),
+    Stage("clusters", {"clusters": 0, "cluster_min_column": 1, "cluster_paint": False}, [_integer("clusters", 16), _check_min_column],
+          lambda s: s["clusters"] > 0, _run_clusters),
+    Stage("extremities", {"extremities": 0, "geodesic_seeds": "floor", "geodesic_paint": None},
+          [_integer("extremities", 32), _one_of("geodesic_paint", (None, "labels", "distance")), _check_seeds],
+          lambda s: s["extremities"] > 0, _run_extremities),
+    Stage("measure", {"measure": None, "measure_profile": False},
+          [_one_of("measure", (None, "all", "clusters", "geodesic", "components")), _check_profile],
+          lambda s: s["measure"] is not None, _run_measure),
+    Stage("skeleton", {"skeleton": None, "skeleton_anchors": None}, [_one_of("skeleton", (None, "curve", "point")), _check_anchors],
+          lambda s: s["skeleton"] is not None, _run_skeleton),
+    Stage("output", {"output": "all", "output_level": 0}, [_one_of("output", ("all", "shell")), _integer("output_level", 6, bools=False)],
+          lambda s: True, _run_output),
+]
+_settings = dict(BASE_SETTINGS, **{name: default for stage in STAGES for name, default in stage.defaults.items()})
 
 
 def configure(frame_source=None, **settings):
-    """Install a frame source / override data_path, num_cameras, device, mode, ...; resets state.
-    color_mode: "camera" (default) colours every survivor from the colour camera, as the reference does (assignment.py:133);
-    "visible" recolours the surface voxels from every camera that sees them (CarveEngine.color_visible).
-    hull: "visual" (default) is the carve's visual hull; "photo" refines it by photo-consistency after every carve
-    (CarveEngine.photo_carve with var_threshold=photo_var_threshold), which needs every camera's image and colours the result as
-    "visible" does; voxels_status() then describes the photo hull.
-    min_component_voxels, keep_components: when either is non-zero, every carve is followed by CarveEngine.filter_components
-    (connectivity=component_connectivity), before any colouring or photo carve: components smaller than min_component_voxels,
-    or beyond the keep_components largest, leave the hull (floating specks of mask noise); voxels_status() describes what is
-    kept.  0 and 0 (the default) keep every survivor.
+    """Install a frame source / override data_path, num_cameras, device, mode, ...; resets state.  A call that raises changes
+    nothing.  Every carve is followed by the stages that the settings turn on, in the order of STAGES above -- the order of the
+    numbered paragraphs here; by default none runs but the last, which returns every survivor.
     footprint: "centre" (default) asks, as the reference does, whether the pixel under a voxel's centre is foreground; "any",
     "all" and ("cover", q) test the pixel box the voxel's whole cell projects to (CarveEngine.carve(footprint=...)): "any" keeps
     what is thinner than a voxel (the outer hull), "all" gives the inner hull.
-    hull_open_mm, hull_border: when hull_open_mm > 0, every carve is followed by CarveEngine.open_hull(hull_open_mm,
-    border=hull_border), before the component filter, any photo carve and any colouring: what is thinner than a ball of that
-    radius in world millimetres leaves the hull (spurs, fins and specks of mask noise, attached to the figure or not);
-    voxels_status() describes what is kept.  0 (the default) keeps every survivor.
-    hull_close_mm: when > 0, every carve is followed by CarveEngine.close_hull(hull_close_mm), before hull_open_mm, the component
-    filter, any photo carve and any colouring (close, then open, is the usual clean-up order): tunnels and dents narrower than a
-    ball of that radius in world millimetres are filled -- what a hole in one camera's mask carves through the figure; the added
-    voxels are coloured from the colour camera.  voxels_status() describes the closed hull.  0 (the default) adds nothing.
     normal_radius_mm: the radius of the ball that render_views(smooth=True) and surface_mesh(normals=True) estimate the hull's
     surface normals from (CarveEngine.hull_normals); None (the default) is 3 x the largest grid step.
-    clusters, cluster_min_column, cluster_paint: when clusters = K > 0 (at most 16), every frame ends -- after all hull passes
-    and the colouring -- with CarveEngine.cluster_hull(K, min_column=cluster_min_column): the hull split into K figures on the
-    floor plane.  The first frame seeds itself and keeps its colour signatures as the references; every later frame starts from
-    the previous frame's centres, so label k stays the same figure while the figures keep apart.  clusters() returns the last
-    frame's split.  cluster_paint=True paints every voxel in its figure's colour (voxcarve.clusters.PALETTE) before the
-    positions and colours are returned.  0 (the default) runs nothing.
-    extremities, geodesic_seeds, geodesic_paint: when extremities = K > 0 (at most 32), every frame ends -- after all hull passes,
-    the colouring and the clusters -- with CarveEngine.hull_geodesic(seeds=geodesic_seeds, extrema=K, paths=True): geodesic
-    distances through the hull from the seed set ("floor", the default, "top", or an array of voxel indices) and the K
-    extremities by farthest-point selection (head, hands, feet).  extremities() returns the last frame's.  geodesic_paint =
-    "labels" | "distance" paints every voxel by its region or its distance (CarveEngine.paint_geodesic) before the positions and
-    colours are returned; None (the default) leaves the colours.  0 (the default) runs nothing.
-    temporal_window, temporal_keep, temporal_keep_off: when temporal_window = T > 0 (at most 15), every carve is followed --
-    before hull_close_mm and everything else -- by CarveEngine.temporal_filter(T, temporal_keep, temporal_keep_off): the hull
-    becomes the vote of the last T frames' hulls (keep defaults to the majority, keep_off to keep), which takes the frame-to-frame
-    flicker of mask noise out and lags a moving figure by about T / 2 frames.  temporal() returns the last frame's stats.
-    0 (the default) runs nothing.
-    hull_subtract, hull_clip: each a path to a file of CarveEngine.save_hull, a hull as an array (bool [n], ascending uint32
-    indices or uint64 records: voxcarve.hullio.as_operand), or None.  The operand is uploaded once, to registers 3 and 2 of the
-    engine, and every carve is followed -- before temporal_window and everything else -- by CarveEngine.combine_hull("andnot", 3)
-    (the static scene leaves the hull) and then CarveEngine.combine_hull("and", 2) (the hull is clipped to a region of
-    interest).  hull_ops() returns the last frame's stats.  None (the default) runs nothing.
-    measure, measure_profile: when measure = "all" | "clusters" | "geodesic" | "components", every frame ends -- after the
-    clusters and the extremities -- with CarveEngine.measure_hull(labels=measure, profile=measure_profile): the hull's figures
-    measured on the device, per group of that source (the whole hull; the figures of clusters=K; the regions of extremities=K;
-    the connected components, ranked by size, of the component filter -- which runs once more on its own output when it removed
-    something, so that its labels describe the hull).  measurements() returns the last frame's.  A source whose own pass is not
-    configured is refused.  None (the default) runs nothing.
-    skeleton, skeleton_anchors: when skeleton = "curve" | "point", every frame ends -- after the frame's geodesic pass -- with
+    1, 2. hull_subtract, hull_clip: each a path to a file of CarveEngine.save_hull, a hull as an array (bool [n], ascending uint32
+    indices or uint64 records: voxcarve.hullio.as_operand), or None (the default: nothing runs).  The operand is uploaded once,
+    to registers 3 and 2 of the engine; the stages are CarveEngine.combine_hull("andnot", 3) (the static scene leaves the hull)
+    and CarveEngine.combine_hull("and", 2) (the hull is clipped to a region of interest).  hull_ops() returns their stats.
+    3. temporal_window, temporal_keep, temporal_keep_off: when temporal_window = T > 0 (at most 15),
+    CarveEngine.temporal_filter(T, temporal_keep, temporal_keep_off): the hull becomes the vote of the last T frames' hulls (keep
+    defaults to the majority, keep_off to keep), which takes the frame-to-frame flicker of mask noise out and lags a moving
+    figure by about T / 2 frames.  temporal() returns the last frame's stats.  0 (the default) runs nothing.
+    4. hull_close_mm: when > 0, CarveEngine.close_hull(hull_close_mm) (close, then open, is the usual clean-up order): tunnels and
+    dents narrower than a ball of that radius in world millimetres are filled -- what a hole in one camera's mask carves through
+    the figure; the added voxels are coloured from the colour camera.  voxels_status() describes the closed hull.
+    5. hull_open_mm, hull_border: when hull_open_mm > 0, CarveEngine.open_hull(hull_open_mm, border=hull_border): what is thinner
+    than a ball of that radius in world millimetres leaves the hull (spurs, fins and specks of mask noise, attached to the figure
+    or not); voxels_status() describes what is kept.  0 (the default) keeps every survivor.
+    6. min_component_voxels, keep_components: when either is non-zero, CarveEngine.filter_components(connectivity=
+    component_connectivity): components smaller than min_component_voxels, or beyond the keep_components largest, leave the
+    hull (floating specks of mask noise); voxels_status() describes what is kept.  0 and 0 (the default) keep every survivor.
+    7. hull, color_mode: hull="photo" refines the visual hull by photo-consistency (CarveEngine.photo_carve with var_threshold=
+    photo_var_threshold), which needs every camera's image and colours the result as "visible" does; voxels_status() then
+    describes the photo hull.  Otherwise color_mode="visible" recolours the surface voxels from every camera that sees them
+    (CarveEngine.color_visible).  "visual" and "camera" (the defaults): every survivor of the carve's visual hull, coloured from
+    the colour camera as the reference does (assignment.py:133).
+    8. clusters, cluster_min_column, cluster_paint: when clusters = K > 0 (at most 16), CarveEngine.cluster_hull(K,
+    min_column=cluster_min_column): the hull split into K figures on the floor plane.  The first frame seeds itself and keeps its
+    colour signatures as the references; every later frame starts from the previous frame's centres, so label k stays the same
+    figure while the figures keep apart.  clusters() returns the last frame's split.  cluster_paint=True then paints every voxel
+    in its figure's colour (voxcarve.clusters.PALETTE).  0 (the default) runs nothing.
+    9. extremities, geodesic_seeds, geodesic_paint: when extremities = K > 0 (at most 32),
+    CarveEngine.hull_geodesic(seeds=geodesic_seeds, extrema=K, paths=True): geodesic distances through the hull from the seed set
+    ("floor", the default, "top", or an array of voxel indices) and the K extremities by farthest-point selection (head, hands,
+    feet).  extremities() returns the last frame's.  geodesic_paint = "labels" | "distance" then paints every voxel by its region
+    or its distance (CarveEngine.paint_geodesic); None (the default) leaves the colours.  0 (the default) runs nothing.
+    10. measure, measure_profile: when measure = "all" | "clusters" | "geodesic" | "components" (None, the default, runs nothing),
+    CarveEngine.measure_hull(labels=measure, profile=measure_profile): the hull's figures measured on the device, per group of
+    that source (the whole hull; the figures of clusters=K; the regions of extremities=K; the connected components, ranked by
+    size, of the component filter -- which runs once more on its own output when it removed something, so that its labels
+    describe the hull).  measurements() returns the last frame's.  A source whose own pass is not configured is refused.
+    11. skeleton, skeleton_anchors: when skeleton = "curve" | "point" (None, the default, runs nothing),
     CarveEngine.thin_hull(skeleton, anchors=skeleton_anchors): the hull thinned to a centred, one-voxel-wide skeleton with its
     topology, on the device; the hull itself stays.  skeleton_anchors = "extrema" pins the skeleton at the floor contact and the
     extremities of extremities=K, which turns a noisy curve skeleton into a stick figure; it is refused without extremities=K.
-    skeleton() returns the last frame's.  None (the default) runs nothing.
-    output, output_level: "all" (the default) returns every survivor, as the reference does.  "shell" ends every frame -- after
-    every other pass and all painting -- with CarveEngine.hull_shell(output_level) and returns the arrays of
-    CarveEngine.fetch_shell_viewer(), made on the device: only the voxels with an exposed face, which is everything an opaque
-    cube viewer can show (at level 0 the same rows the full arrays hold for those voxels).  output_level = L in 1..6 lists the
-    cells of a grid 2^L times coarser instead, with averaged colours: the viewer must draw each cube shell()["cube_scale"] times
-    as large.  shell() returns the last frame's stats.  voxels_status() is unaffected.  output_level needs output="shell"."""
+    skeleton() returns the last frame's.
+    12. output, output_level: "all" (the default) returns every survivor, as the reference does.  "shell" runs
+    CarveEngine.hull_shell(output_level) and returns the arrays of CarveEngine.fetch_shell_viewer(), made on the device: only the
+    voxels with an exposed face, which is everything an opaque cube viewer can show (at level 0 the same rows the full arrays
+    hold for those voxels).  output_level = L in 1..6 lists the cells of a grid 2^L times coarser instead, with averaged colours:
+    the viewer must draw each cube shell()["cube_scale"] times as large.  shell() returns the last frame's stats.
+    voxels_status() is unaffected.  output_level needs output="shell"."""
     global _source, _engine, initialized, frame_count
     unknown = set(settings) - set(_settings)
     if unknown:
         raise TypeError("unknown settings: %s" % sorted(unknown))
-    if settings.get("color_mode", _settings["color_mode"]) not in COLOR_MODES:
-        raise ValueError("color_mode %r, expected one of %s" % (settings["color_mode"], COLOR_MODES))
-    if settings.get("hull", _settings["hull"]) not in HULLS:
-        raise ValueError("hull %r, expected one of %s" % (settings["hull"], HULLS))
-    footprint_rule(settings.get("footprint", _settings["footprint"]))          # raises ValueError on anything else
-    CarveEngine.radius_r2(settings.get("hull_open_mm", _settings["hull_open_mm"]))   # ... on a negative or non-finite radius
-    CarveEngine._dist_flags(settings.get("hull_border", _settings["hull_border"]))
-    CarveEngine.radius_r2(settings.get("hull_close_mm", _settings["hull_close_mm"]))
-    if settings.get("normal_radius_mm", _settings["normal_radius_mm"]) is not None:
-        CarveEngine.radius_r2(settings.get("normal_radius_mm", _settings["normal_radius_mm"]))
-    k = settings.get("clusters", _settings["clusters"])
-    if not isinstance(k, (int, np.integer)) or not 0 <= k <= 16:
-        raise ValueError("clusters %r, expected an integer in 0..16" % (k,))
-    if int(settings.get("cluster_min_column", _settings["cluster_min_column"])) < 0:
-        raise ValueError("cluster_min_column %r is negative" % (settings["cluster_min_column"],))
-    k = settings.get("extremities", _settings["extremities"])
-    if not isinstance(k, (int, np.integer)) or not 0 <= k <= 32:
-        raise ValueError("extremities %r, expected an integer in 0..32" % (k,))
-    if settings.get("geodesic_paint", _settings["geodesic_paint"]) not in GEODESIC_PAINTS:
-        raise ValueError("geodesic_paint %r, expected one of %s" % (settings["geodesic_paint"], GEODESIC_PAINTS))
-    g = settings.get("geodesic_seeds", _settings["geodesic_seeds"])
-    if isinstance(g, str) and g not in ("floor", "top"):
-        raise ValueError("geodesic_seeds %r, expected \"floor\", \"top\" or an array of voxel indices" % (g,))
-    t = settings.get("temporal_window", _settings["temporal_window"])
-    if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0:
-        raise ValueError("temporal_window %r, expected an integer in 0..15" % (t,))
-    CarveEngine.temporal_thresholds(t if t > 0 else 1, settings.get("temporal_keep", _settings["temporal_keep"]) if t > 0 else None,
-                                    settings.get("temporal_keep_off", _settings["temporal_keep_off"]) if t > 0 else None)
-    for name in ("hull_subtract", "hull_clip"):
-        h = settings.get(name, _settings[name])
-        if h is not None and not isinstance(h, (str, os.PathLike, np.ndarray)):
-            raise ValueError("%s %r, expected a path, an array or None" % (name, h))
-    m = settings.get("measure", _settings["measure"])
-    if m not in MEASURES:
-        raise ValueError("measure %r, expected one of %s" % (m, MEASURES))
-    if not isinstance(settings.get("measure_profile", _settings["measure_profile"]), (bool, np.bool_)):
-        raise ValueError("measure_profile %r, expected True or False" % (settings["measure_profile"],))
     merged = dict(_settings, **settings)
-    if m == "clusters" and not merged["clusters"] > 0:
-        raise ValueError('measure="clusters" needs clusters=K')
-    if m == "geodesic" and not merged["extremities"] > 0:
-        raise ValueError('measure="geodesic" needs extremities=K')
-    if m == "components" and not (merged["min_component_voxels"] or merged["keep_components"]):
-        raise ValueError('measure="components" needs the component filter: min_component_voxels or keep_components')
-    if merged["skeleton"] not in SKELETONS:
-        raise ValueError("skeleton %r, expected one of %s" % (merged["skeleton"], SKELETONS))
-    if merged["skeleton_anchors"] not in (None, "extrema"):
-        raise ValueError('skeleton_anchors %r, expected None or "extrema"' % (merged["skeleton_anchors"],))
-    if merged["skeleton"] is not None and merged["skeleton_anchors"] == "extrema" and not merged["extremities"] > 0:
-        raise ValueError('skeleton_anchors="extrema" needs extremities=K')
-    if merged["output"] not in OUTPUTS:
-        raise ValueError("output %r, expected one of %s" % (merged["output"], OUTPUTS))
-    lv = merged["output_level"]
-    if isinstance(lv, bool) or not isinstance(lv, (int, np.integer)) or not 0 <= lv <= 6:
-        raise ValueError("output_level %r, expected an integer in 0..6" % (lv,))
-    if lv != 0 and merged["output"] != "shell":
-        raise ValueError('output_level=%d needs output="shell"' % lv)
+    footprint_rule(merged["footprint"])                          # raises ValueError on anything else
+    if merged["normal_radius_mm"] is not None:
+        CarveEngine.radius_r2(merged["normal_radius_mm"])        # ... on a negative or non-finite radius
+    for stage in STAGES:
+        for check in stage.checks:
+            check(merged)
+    _check_across(merged)
     _settings.update(settings)
-    _shell_state.update(last=None)
-    _measure_state.update(last=None, centroids_mm=None)
-    _skeleton_state.update(last=None)
-    _temporal_state.update(last=None)
-    _hull_ops_state.update(last=None)
-    _cluster_state.update(centres_mm=None, references=None, last=None)
-    _geodesic_state.update(last=None)
+    _last.clear(), _carry.clear()
     _source = frame_source
     if _engine is not None:
         _engine.close()
@@ -335,14 +438,14 @@ def set_voxel_positions(width, height, depth):
     :param depth: voxel volume depth
     :return: (positions float32 [S,3], colors float32 [S,3]); ([], []) at the end of the video
     """
-    global initialized, frame_count, _engine, _source
+    global initialized, frame_count, _engine, _source, _cameras, _sized, _operands
     if not initialized:
         if _source is None:
             _source = ReferenceVideoSource(_settings["data_path"], _settings["num_cameras"])
         _engine = CarveEngine(_settings["device"])
         _engine.set_grid(width, height * 2, depth, _settings["bounds"])        # assignment.py:85
-        _engine._cameras = load_cameras(_settings["data_path"], _settings["num_cameras"])   # :88
-        _engine._sized = None
+        _cameras = load_cameras(_settings["data_path"], _settings["num_cameras"])   # :88
+        _sized = None
         initialized = True
 
     device_source = hasattr(_source, "fill_slot")
@@ -355,162 +458,66 @@ def set_voxel_positions(width, height, depth):
         frames, masks = item
         frame_count += 1
         H, W = np.asarray(masks[0]).shape[:2]
-    if _engine._sized != (H, W):
-        _engine.set_cameras(_engine._cameras, H, W)
-        if getattr(_source, "post_on_device", False):
+    if _sized != (H, W):
+        _engine.set_cameras(_cameras, H, W)
+        if hasattr(_source, "post_on_device") and _source.post_on_device:
             n = _settings["num_cameras"]
             _engine.set_mask_postfilter([cam_bg_model_params[c][4] for c in range(n)],
                                         [cam_bg_model_params[c][5] for c in range(n)])
         if _settings["mode"] == "lut":
             _engine.build_lut()
-        _engine._sized = (H, W)
-        _engine._operands = False                                               # (new cameras empty the registers)
-    if not getattr(_engine, "_operands", False):
+        _sized = (H, W)
+        _operands = False                                                       # (new cameras empty the registers)
+    if not _operands:
         _upload_operands()
+        _operands = True
     cc = _settings["color_camera"]
-    photo = _settings["hull"] == "photo"
-    visible = _settings["color_mode"] == "visible" or photo
     if device_source:
         if not _source.fill_slot(_engine, 0):                                   # masks and images made on the device
             return [], []
         frame_count += 1
     else:
         _engine.upload_masks(masks, slot=0)
-        for c in (range(len(frames)) if visible else (cc,)):                   # "visible": every camera's image
+        for c in (range(len(frames)) if _recolours(_settings) else (cc,)):     # recolouring: every camera's image
             _engine.upload_frame(c, frames[c], slot=0)
     _engine.carve(slot=0, min_views=_settings["views_threshold"], color_cam=cc, mode=_settings["mode"],
                   footprint=_settings["footprint"])
-    if _settings["hull_subtract"] is not None or _settings["hull_clip"] is not None:
-        ops = {}
-        if _settings["hull_subtract"] is not None:
-            ops["subtract"] = _engine.combine_hull("andnot", HULL_SUBTRACT_REG)
-        if _settings["hull_clip"] is not None:
-            ops["clip"] = _engine.combine_hull("and", HULL_CLIP_REG)
-        _hull_ops_state["last"] = ops
-    if _settings["temporal_window"] > 0:
-        _temporal_state["last"] = _engine.temporal_filter(_settings["temporal_window"], _settings["temporal_keep"],
-                                                          _settings["temporal_keep_off"])
-    if _settings["hull_close_mm"] > 0:
-        _engine.close_hull(_settings["hull_close_mm"])
-    if _settings["hull_open_mm"] > 0:
-        _engine.open_hull(_settings["hull_open_mm"], border=_settings["hull_border"])
-    if _settings["min_component_voxels"] or _settings["keep_components"]:
-        _engine.filter_components(connectivity=_settings["component_connectivity"], min_voxels=_settings["min_component_voxels"],
-                                  keep_largest=_settings["keep_components"])
-    if photo:
-        _engine.photo_carve(slot=0, var_threshold=_settings["photo_var_threshold"])
-    elif visible:
-        _engine.color_visible(slot=0)
-    if _settings["clusters"] > 0:
-        _cluster_frame()
-    if _settings["extremities"] > 0:
-        _geodesic_frame()
-    if _settings["measure"] is not None:
-        _measure_frame()
-    if _settings["skeleton"] is not None:
-        _skeleton_frame()
-    if _settings["output"] == "shell":
-        _shell_state["last"] = _engine.hull_shell(int(_settings["output_level"]))
-        return _engine.fetch_shell_viewer()
-    idx, rgb, _ = _engine.fetch()
-    keys = voxel_keys(idx, _engine.grid, _engine.axes())
-    return viewer_positions(keys), viewer_colors(rgb)
+    return [stage.run(_settings) for stage in STAGES if stage.on(_settings)][-1]       # (the last stage's: the output is always on)
 
 
 def _upload_operands():
     """The operands of hull_subtract and hull_clip into their registers (see configure): once per camera set."""
     for name, reg in (("hull_subtract", HULL_SUBTRACT_REG), ("hull_clip", HULL_CLIP_REG)):
         h = _settings[name]
-        if h is None:
-            continue
         if isinstance(h, (str, os.PathLike)):
             _engine.load_hull(h, reg)
-        else:
+        elif h is not None:
             _engine.upload_hull(h, reg)
-    _engine._operands = True
+
+
+def _last_result(stage, what, how):                              # (for the accessors below)
+    if _engine is None or not initialized or _last.get(stage) is None:
+        raise RuntimeError("no %s: configure(%s) and set_voxel_positions have not run" % (what, how))
+    return _last[stage]
 
 
 def hull_ops():
     """The stats of the last set_voxel_positions call's set operations (configure(hull_subtract=..., hull_clip=...)): a dict
     with "subtract" and / or "clip", each the dict of CarveEngine.combine_hull."""
-    if _engine is None or not initialized or _hull_ops_state["last"] is None:
-        raise RuntimeError("no hull operations: configure(hull_subtract=... or hull_clip=...) and set_voxel_positions have not run")
-    return _hull_ops_state["last"]
-
-
-def _cluster_frame():
-    """The frame's split into figures, warm-started from the previous frame's centres (see configure)."""
-    from .clusters import MATCH_MAX_K, match
-    K = int(_settings["clusters"])
-    out = _engine.cluster_hull(K, min_column=int(_settings["cluster_min_column"]), init_mm=_cluster_state["centres_mm"])
-    out["figures"] = _engine.fetch_clusters()
-    out["histograms"] = _engine.fetch_cluster_histograms()
-    if _cluster_state["references"] is None:
-        _cluster_state["references"] = out["histograms"].copy()
-    out["identity"] = match(_cluster_state["references"], out["histograms"]) if K <= MATCH_MAX_K else None
-    _cluster_state["centres_mm"] = out["centres_mm"]
-    _cluster_state["last"] = out
-    if _settings["cluster_paint"]:
-        _engine.paint_clusters()
-
-
-def _geodesic_frame():
-    """The frame's geodesic distances and extremities (see configure)."""
-    out = _engine.hull_geodesic(seeds=_settings["geodesic_seeds"], extrema=int(_settings["extremities"]), paths=True)
-    out["extrema"] = _engine.fetch_extrema()
-    out["paths"] = _engine.stick_figure()
-    _geodesic_state["last"] = out
-    if _settings["geodesic_paint"] is not None:
-        _engine.paint_geodesic(_settings["geodesic_paint"])
-
-
-def _skeleton_frame():
-    """The frame's skeleton (see configure)."""
-    from . import skeleton as sk
-    stats = _engine.thin_hull(_settings["skeleton"], anchors=_settings["skeleton_anchors"])
-    rows = _engine.fetch_skeleton()
-    _skeleton_state["last"] = {"stats": stats, "skeleton": rows, "description": sk.describe(rows, _engine.grid, _engine.bounds)}
+    return _last_result("hull_ops", "hull operations", "hull_subtract=... or hull_clip=...")
 
 
 def skeleton():
     """The skeleton of the last set_voxel_positions call's hull (configure(skeleton=...)): stats, the dict of
     CarveEngine.thin_hull; skeleton, the dict of CarveEngine.fetch_skeleton (voxel, record, degree, index); description, the
     dict of voxcarve.skeleton.describe (positions_mm, edges, edge_mm, length_mm, endpoints, junctions)."""
-    if _engine is None or not initialized or _skeleton_state["last"] is None:
-        raise RuntimeError("no skeleton: configure(skeleton=...) and set_voxel_positions have not run")
-    return _skeleton_state["last"]
+    return _last_result("skeleton", "skeleton", "skeleton=...")
 
 
 def shell():
     """The stats of the last set_voxel_positions call's shell (configure(output="shell")): the dict of CarveEngine.hull_shell
     (survivors, cells_on, shell, faces, level, cube_scale, dims, shell_ms)."""
-    if _engine is None or not initialized or _shell_state["last"] is None:
-        raise RuntimeError("no shell: configure(output=\"shell\") and set_voxel_positions have not run")
-    return _shell_state["last"]
-
-
-def _measure_frame():
-    """The frame's measurements (see configure); with "clusters", label k is the same figure from frame to frame, so the
-    centroid's step since the previous frame is the figure's displacement."""
-    from . import measure
-    source = _settings["measure"]
-    if source == "components":
-        try:
-            _engine.component_ranks()
-        except ValueError:                                       # the filter removed something: label its output
-            _engine.filter_components(connectivity=_settings["component_connectivity"])
-    out = _engine.measure_hull(labels=source, profile=bool(_settings["measure_profile"]))
-    out["source"] = source
-    out["integers"] = _engine.fetch_measure()
-    out["world"] = measure.describe(out["integers"], _engine.grid, _engine.bounds)
-    if _settings["measure_profile"]:
-        out["profile"] = _engine.fetch_measure_profile()
-    if source == "clusters":
-        c = out["world"]["centroid_mm"]
-        prev = _measure_state["centroids_mm"]
-        out["velocity_mm"] = None if prev is None or prev.shape != c.shape else c - prev
-        _measure_state["centroids_mm"] = c.copy()
-    _measure_state["last"] = out
+    return _last_result("shell", "shell", "output=\"shell\"")
 
 
 def measurements():
@@ -520,17 +527,13 @@ def measurements():
     overstates a smooth surface --, centroid_mm, covariance_mm2, std_mm, axes, lean_deg, height_mm, top_mm, mean_rgb); profile:
     u64 [G, nz, 3] with measure_profile=True; and, with measure="clusters", velocity_mm: float64 [K, 3], each figure's centroid
     minus the previous frame's (None on the first frame; NaN rows for a figure that is empty in either)."""
-    if _engine is None or not initialized or _measure_state["last"] is None:
-        raise RuntimeError("no measurements: configure(measure=...) and set_voxel_positions have not run")
-    return _measure_state["last"]
+    return _last_result("measure", "measurements", "measure=...")
 
 
 def temporal():
     """The stats of the last set_voxel_positions call's vote over the last frames' hulls (configure(temporal_window=T)): the dict
     of CarveEngine.temporal_filter."""
-    if _engine is None or not initialized or _temporal_state["last"] is None:
-        raise RuntimeError("no temporal vote: configure(temporal_window=T) and set_voxel_positions have not run")
-    return _temporal_state["last"]
+    return _last_result("temporal", "temporal vote", "temporal_window=T")
 
 
 def extremities():
@@ -538,9 +541,7 @@ def extremities():
     CarveEngine.hull_geodesic (survivors, seeds, reached, unreached, max_d, extremities, ...) with extrema: the dict of
     CarveEngine.fetch_extrema (label, voxel, record, d, d_mm, index, world_mm, in the order they were picked) and paths: the list
     of CarveEngine.stick_figure (world mm, one per extremity)."""
-    if _engine is None or not initialized or _geodesic_state["last"] is None:
-        raise RuntimeError("no extremities: configure(extremities=K) and set_voxel_positions have not run")
-    return _geodesic_state["last"]
+    return _last_result("extremities", "extremities", "extremities=K")
 
 
 def clusters():
@@ -549,9 +550,7 @@ def clusters():
     dict of CarveEngine.fetch_clusters (per figure centre_um, centre_mm, voxels, weight, columns, lo, hi), histograms u32
     [K, 512] and identity: the permutation voxcarve.clusters.match finds between the first frame's colour signatures and this
     frame's (identity[k] = the label that looks like the first frame's figure k; None above 8 figures)."""
-    if _engine is None or not initialized or _cluster_state["last"] is None:
-        raise RuntimeError("no clusters: configure(clusters=K) and set_voxel_positions have not run")
-    return _cluster_state["last"]
+    return _last_result("clusters", "clusters", "clusters=K")
 
 
 def voxels_status():
@@ -563,7 +562,6 @@ def voxels_status():
         raise RuntimeError("set_voxel_positions has not run")
     nx, ny, nz = _engine.grid
     return _engine.fetch_occupancy().reshape(nx, ny, nz)
-
 
 
 def _ensure_normals():
@@ -581,10 +579,10 @@ def render_views(views=None, width=None, height=None, shade=None, smooth=False, 
     frame's camera images instead of its voxel, after texture_steps bisection steps along the ray against the silhouettes
     (CarveEngine.render_textured: rgb is the textured image, rgb_voxels the render's own, depth the refined one); it needs
     configure(color_mode="visible"), whose depth maps say which cameras see a point, and excludes smooth and shade."""
-    if _engine is None or not initialized or _engine._sized is None:
+    if _engine is None or not initialized or _sized is None:
         raise RuntimeError("set_voxel_positions has not run")
     H, W = _engine.image_size
-    views = _engine._cameras if views is None else views
+    views = _cameras if views is None else views
     H, W = H if height is None else height, W if width is None else width
     if textured:
         if smooth or shade is not None:
@@ -606,7 +604,7 @@ def surface_mesh(refine_steps=8, normals=False):
     outward faces, the voxels' colours.  Returns the dict of CarveEngine.surface_mesh: verts [V, 3] float64, faces [F, 3], rgb
     [V, 3], refined [V] and stats; voxel_reconstruction.write_ply writes it out.  normals=True adds "normals": float64 [V, 3]
     unit vectors, the surface normal of the voxel each vertex takes its colour from (zero where that voxel has none)."""
-    if _engine is None or not initialized or _engine._sized is None:
+    if _engine is None or not initialized or _sized is None:
         raise RuntimeError("set_voxel_positions has not run")
     mesh = _engine.surface_mesh(refine_steps)
     if normals:

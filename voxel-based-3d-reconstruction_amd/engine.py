@@ -40,6 +40,17 @@ def _ptr(a, ctype):
     return a.ctypes.data_as(ctypes.POINTER(ctype))
 
 
+def _stats(st, **overrides):
+    """A filled Vc*Stats struct as a dict, field by field of its _fields_: integers as int, the *_ms floats as float, arrays as
+    a tuple of int.  `overrides` replace or add keys: what a pass reports differently from its struct, said at the call."""
+    out = {}
+    for name, ctype in st._fields_:
+        v = getattr(st, name)
+        out[name] = tuple(int(x) for x in v) if isinstance(v, ctypes.Array) else float(v) if ctype is ctypes.c_float else int(v)
+    out.update(overrides)
+    return out
+
+
 class CarveEngine:
     def __init__(self, device=0):
         self._L = _lib.load()
@@ -51,8 +62,19 @@ class CarveEngine:
         self.n_cameras = 0
         self.image_size = None
         self.count = 0
+        self.n_ranks, self.rank = 1, 0
+        self._cams = []                      # what set_cameras() was given
+        self._pin_bytes = 0                  # the page-locked buffer of fetch_records(pinned=True)
+        # the sizes of the last pass's outputs, which its fetch_* calls allocate by: empty until the pass has run
         self._render_shape = (0, (0, 0))     # views and size of the last render()
         self._mesh_verts = 0                 # vertices of the last surface_mesh()
+        self._photo_n = 0                    # records the last photo_carve() started from
+        self._cc_n, self._cc_k = 0, 0        # records the last filter_components() started from, and its components
+        self._cl_k = 0                       # figures of the last cluster_hull()
+        self._geo_k = 0                      # extremities of the last hull_geodesic()
+        self._ms_g = 0                       # groups of the last measure_hull()
+        self._shell_t = 0                    # cells of the last hull_shell()
+        self._thin = (0, 0)                  # records the last thin_hull() started from, and the voxels it kept
 
     # -- lifetime -----------------------------------------------------------------
     def close(self):
@@ -118,6 +140,11 @@ class CarveEngine:
         self.n_cameras = len(cams)
         self._cams = cams
         self.image_size = (int(H), int(W))
+
+    @property
+    def cameras(self):
+        """The camera.Camera list of the last set_cameras (the calibrated cameras): read-only."""
+        return self._cams
 
     # -- per-frame inputs -----------------------------------------------------------
     def upload_masks(self, masks, slot=0):
@@ -224,7 +251,7 @@ class CarveEngine:
         per camera [figure_threshold, figure_inner_threshold, opening_pre, closing_pre, ...] (the rows of
         assignment.cam_bg_model_params).  The 2x2 post-filter is set_mask_postfilter's.
         Asynchronous: the next carve on the slot waits for it on the device."""
-        ids = np.array([int(getattr(m, "_model", m)) for m in models], dtype=np.uint32)
+        ids = np.array([int(m if isinstance(m, (int, np.integer)) else m._model) for m in models], dtype=np.uint32)
         f = np.ascontiguousarray(np.stack([np.asarray(x) for x in frames]), dtype=np.uint8)
         if f.ndim != 4 or f.shape[3] != 3:
             raise ValueError("frames shape %s, expected [C, H, W, 3]" % (f.shape,))
@@ -407,7 +434,7 @@ class CarveEngine:
             self._check(self._L.vc_fetch_records(self._ctx, _ptr(rec, ctypes.c_uint64)), "vc_fetch_records")
             return rec
         need = max(self.count, 1) * 8
-        if getattr(self, "_pin_bytes", 0) < need:
+        if self._pin_bytes < need:
             self._release_pinned()
             ptr = ctypes.c_void_p()
             grow = (need + need // 4 + 7) // 8 * 8
@@ -419,7 +446,7 @@ class CarveEngine:
         return out
 
     def _release_pinned(self):
-        if getattr(self, "_pin_bytes", 0):
+        if self._pin_bytes:
             self._pin_arr = None
             self._L.vc_host_free(self._ctx, self._pin_ptr)
             self._pin_bytes = 0
@@ -478,12 +505,11 @@ class CarveEngine:
                                            int(max_rounds), 0, ctypes.byref(st)), "vc_photo_carve")
         self.count = int(st.survivors_after)
         self._photo_n = int(st.survivors_before)
-        return {"rounds": int(st.rounds), "converged": bool(st.converged), "survivors_before": int(st.survivors_before),
-                "survivors_after": int(st.survivors_after), "photo_ms": float(st.photo_ms)}
+        return _stats(st, converged=bool(st.converged))
 
     def fetch_photo_rounds(self):
         """u8 [survivors_before]: per record of the last photo_carve's input, in its order, the round that removed it (0 = kept)."""
-        out = np.empty(getattr(self, "_photo_n", 0), dtype=np.uint8)
+        out = np.empty(self._photo_n, dtype=np.uint8)
         self._check(self._L.vc_fetch_photo_rounds(self._ctx, _ptr(out, ctypes.c_uint8)), "vc_fetch_photo_rounds")
         return out
 
@@ -499,21 +525,19 @@ class CarveEngine:
                                                ctypes.byref(st)), "vc_hull_components")
         self.count = int(st.survivors_after)
         self._cc_n, self._cc_k = int(st.survivors_before), int(st.components)
-        return {"components": int(st.components), "components_kept": int(st.components_kept),
-                "survivors_before": int(st.survivors_before), "survivors_after": int(st.survivors_after),
-                "largest": int(st.largest), "components_ms": float(st.components_ms)}
+        return _stats(st)
 
     def fetch_component_labels(self):
         """u32 [survivors_before]: per record of the last filter_components' input, in its order, the label of its component
         (the smallest linear index in it)."""
-        out = np.empty(getattr(self, "_cc_n", 0), dtype=np.uint32)
+        out = np.empty(self._cc_n, dtype=np.uint32)
         self._check(self._L.vc_fetch_component_labels(self._ctx, _ptr(out, ctypes.c_uint32)), "vc_fetch_component_labels")
         return out
 
     def fetch_components(self):
         """The components of the last filter_components in ascending label: dict of numpy arrays label u32 [K], size u32 [K],
         lo / hi u32 [K, 3] (inclusive box in (ix, iy, iz)), kept bool [K]."""
-        raw = np.empty((getattr(self, "_cc_k", 0), 10), dtype=np.uint32)
+        raw = np.empty((self._cc_k, 10), dtype=np.uint32)
         self._check(self._L.vc_fetch_components(self._ctx, raw.ctypes.data_as(ctypes.c_void_p)), "vc_fetch_components")
         return {"label": raw[:, 0].copy(), "size": raw[:, 1].copy(), "lo": raw[:, 2:5].copy(), "hi": raw[:, 5:8].copy(),
                 "kept": raw[:, 8] != 0}
@@ -533,8 +557,7 @@ class CarveEngine:
         sites_inside_box, max_d2, q (x, y, z in um), distance_ms.  The fetch_* calls below read the fields."""
         st = _lib.VcDistanceStats()
         self._check(self._L.vc_hull_distance(self._ctx, self._dist_flags(border, outside), ctypes.byref(st)), "vc_hull_distance")
-        return {"survivors": int(st.survivors), "sites_inside_box": int(st.sites_inside_box), "max_d2": int(st.max_d2),
-                "q": tuple(int(v) for v in st.q), "distance_ms": float(st.distance_ms)}
+        return _stats(st)
 
     def fetch_record_distance(self):
         """u64 [S] in record order: the squared inside distance of each survivor in um^2 (after hull_distance, which leaves
@@ -578,8 +601,7 @@ class CarveEngine:
         st = _lib.VcMorphStats()
         self._check(self._L.vc_hull_morphology(self._ctx, op, int(r2), self._dist_flags(border), ctypes.byref(st)), "vc_hull_morphology")
         self.count = int(st.survivors_after)
-        return {"survivors_before": int(st.survivors_before), "eroded": int(st.eroded), "survivors_after": int(st.survivors_after),
-                "max_d2": int(st.max_d2), "q": tuple(int(v) for v in st.q), "morph_ms": float(st.morph_ms)}
+        return _stats(st)
 
     def erode_hull(self, radius_mm, border="open"):
         """Erodes the current carve result by a ball of radius_mm millimetres (a Euclidean ball in world units, whatever the grid's
@@ -601,8 +623,7 @@ class CarveEngine:
         st = _lib.VcGrowStats()
         self._check(self._L.vc_hull_grow(self._ctx, op, int(r2), 0, ctypes.byref(st)), "vc_hull_grow")
         self.count = int(st.survivors_after)
-        return {"survivors_before": int(st.survivors_before), "dilated": int(st.dilated), "survivors_after": int(st.survivors_after),
-                "added": int(st.added), "box_cells": int(st.box_cells), "q": tuple(int(v) for v in st.q), "grow_ms": float(st.grow_ms)}
+        return _stats(st)
 
     def dilate_hull(self, radius_mm):
         """Dilates the current carve result by a ball of radius_mm millimetres (a Euclidean ball in world units, clipped to the
@@ -653,9 +674,7 @@ class CarveEngine:
         st = _lib.VcTemporalStats()
         self._check(self._L.vc_hull_temporal(self._ctx, window, keep, keep_off, 0, ctypes.byref(st)), "vc_hull_temporal")
         self.count = int(st.survivors_after)
-        out = {name: int(getattr(st, name)) for name, _ in _lib.VcTemporalStats._fields_ if name != "temporal_ms"}
-        out["temporal_ms"] = float(st.temporal_ms)
-        return out
+        return _stats(st)
 
     def fetch_temporal(self):
         """(votes, added), u8 [S] each in record order: in how many of the ring's hulls the record's voxel is, and 1 where the last
@@ -726,9 +745,7 @@ class CarveEngine:
         st = _lib.VcSetopStats()
         self._check(self._L.vc_hull_combine(self._ctx, self.SETOPS[op], int(reg), 0, ctypes.byref(st)), "vc_hull_combine")
         self.count = int(st.survivors_after)
-        out = {name: int(getattr(st, name)) for name, _ in _lib.VcSetopStats._fields_ if name != "setop_ms"}
-        out["setop_ms"] = float(st.setop_ms)
-        return out
+        return _stats(st)
 
     def fetch_combined(self):
         """u8 [S] in record order: 1 where the last combine_hull brought the voxel in (fails once a carve or a pass that changes
@@ -746,16 +763,15 @@ class CarveEngine:
         either hull is empty)."""
         st = _lib.VcCompareStats()
         self._check(self._L.vc_hull_compare(self._ctx, int(reg), _lib.VC_COMPARE_DISTANCE if distance else 0, ctypes.byref(st)), "vc_hull_compare")
-        out = {name: int(getattr(st, name)) for name in ("a", "b", "common", "only_a", "only_b")}
-        out["diff_lo"] = tuple(int(v) for v in st.diff_lo)
-        out["diff_hi"] = tuple(int(v) for v in st.diff_hi)
-        out["compare_ms"] = float(st.compare_ms)
+        out = _stats(st)
+        if not distance:                                         # (the call left the distance fields alone)
+            for name in ("h2_ab", "h2_ba", "arg_ab", "arg_ba", "q"):
+                del out[name]
         union = out["common"] + out["only_a"] + out["only_b"]
         out["iou"] = out["common"] / union if union else None
         out["dice"] = 2 * out["common"] / (out["a"] + out["b"]) if union else None
         out["hausdorff_mm"] = None
         if distance:
-            out.update(h2_ab=int(st.h2_ab), h2_ba=int(st.h2_ba), arg_ab=int(st.arg_ab), arg_ba=int(st.arg_ba), q=tuple(int(v) for v in st.q))
             worst = max(out["h2_ab"], out["h2_ba"])
             if union and worst != (1 << 64) - 1:
                 out["hausdorff_mm"] = float(np.sqrt(float(worst))) / 1000.0
@@ -816,8 +832,7 @@ class CarveEngine:
             self._check(self._L.vc_fetch_render(self._ctx, k, _ptr(out["index"][k], ctypes.c_uint32), _ptr(out["depth"][k], ctypes.c_float),
                                                 _ptr(out["rgb"][k], ctypes.c_uint8), _ptr(out["face"][k], ctypes.c_uint8)),
                         "vc_fetch_render")
-        out["stats"] = {"pixels": int(st.pixels), "hits": int(st.hits), "cells_visited": int(st.cells_visited),
-                        "blocks_skipped": int(st.blocks_skipped), "render_ms": float(st.render_ms)}
+        out["stats"] = _stats(st)
         return out
 
     def silhouette_agreement(self, slot=0):
@@ -879,9 +894,7 @@ class CarveEngine:
         refined = np.empty(V, dtype=np.uint8)
         self._check(self._L.vc_fetch_surface_mesh(self._ctx, _ptr(verts, ctypes.c_double), _ptr(faces, ctypes.c_uint32),
                                                   _ptr(rgb, ctypes.c_uint8), _ptr(refined, ctypes.c_uint8)), "vc_fetch_surface_mesh")
-        return {"verts": verts, "faces": faces, "rgb": rgb, "refined": refined != 0,
-                "stats": {"n_verts": V, "n_faces": F, "refined": int(st.refined), "unrefined": int(st.unrefined),
-                          "point_tests": int(st.point_tests), "surface_ms": float(st.surface_ms)}}
+        return {"verts": verts, "faces": faces, "rgb": rgb, "refined": refined != 0, "stats": _stats(st)}
 
     # -- surface normals of the hull, smooth-shaded renders, mesh normals (vc_hull_normals, vc_shade_render, vc_surface_normals) ----
     def grid_steps_um(self):
@@ -907,8 +920,7 @@ class CarveEngine:
             raise ValueError("radius^2 = %d um^2 does not fit 64 bits" % r2)
         st = _lib.VcNormalsStats()
         self._check(self._L.vc_hull_normals(self._ctx, int(r2), 0, ctypes.byref(st)), "vc_hull_normals")
-        return {"survivors": int(st.survivors), "surface": int(st.surface), "zero": int(st.zero), "offsets": int(st.offsets),
-                "q": tuple(int(v) for v in st.q), "ext": tuple(int(v) for v in st.ext), "normals_ms": float(st.normals_ms)}
+        return _stats(st)
 
     def fetch_record_normals(self):
         """int16 [S, 4] in record order: (n_x, n_y, n_z, w), the normal scaled so that its largest component is +-32767; w = 1 on
@@ -977,10 +989,7 @@ class CarveEngine:
         filters = {"nearest": 0, "bilinear": 1, 0: 0, 1: 1}
         if filter not in filters:
             raise ValueError("texture_render: filter %r is neither 'nearest' nor 'bilinear'" % (filter,))
-        if self.grid is not None:
-            diag = self.default_depth_tolerance()
-        else:
-            diag = 0.0                                   # (no grid: the call reports it)
+        diag = self.default_depth_tolerance() if self.grid is not None else 0.0   # (no grid: the call reports it)
         reach = diag if reach_mm is None else float(reach_mm)
         tol = diag if depth_tolerance is None else float(depth_tolerance)
         st = _lib.VcTextureStats()
@@ -995,8 +1004,7 @@ class CarveEngine:
                                                   _ptr(out["count"][k], ctypes.c_uint8), _ptr(out["best_cam"][k], ctypes.c_uint8),
                                                   _ptr(refined[k], ctypes.c_uint8)), "vc_fetch_textured")
         out["refined"] = refined != 0
-        out["stats"] = {"pixels": int(st.pixels), "hits": int(st.hits), "refined": int(st.refined), "textured": int(st.textured),
-                        "fallback": int(st.fallback), "point_tests": int(st.point_tests), "texture_ms": float(st.texture_ms)}
+        out["stats"] = _stats(st)
         return out
 
     def render_textured(self, views, H, W, slot=0, steps=8, reach_mm=None, depth_tolerance=None, best=2, sharpen=2, filter="bilinear",
@@ -1045,9 +1053,7 @@ class CarveEngine:
                                              None if init is None else _ptr(init, ctypes.c_int64), 0, ctypes.byref(st)),
                     "vc_hull_clusters")
         self._cl_k = int(k)
-        return {"survivors": int(st.survivors), "columns": int(st.columns), "weight": int(st.weight),
-                "iterations": int(st.iterations), "converged": bool(st.converged), "q": tuple(int(v) for v in st.q),
-                "clusters_ms": float(st.clusters_ms), "k": int(k), "centres_mm": self.fetch_clusters()["centre_mm"]}
+        return _stats(st, converged=bool(st.converged), k=int(k), centres_mm=self.fetch_clusters()["centre_mm"])
 
     def clusters_valid(self):
         """True while the clustering of the last cluster_hull() describes the current hull."""
@@ -1063,7 +1069,7 @@ class CarveEngine:
         """The figures of the last cluster_hull: dict of numpy arrays centre_um int64 [K, 2] (from the grid's (x_min, y_min)
         corner), centre_mm float64 [K, 2] (world), voxels u64 [K], weight u64 [K], columns u32 [K], lo / hi u32 [K, 3] (inclusive
         box in (ix, iy, iz); lo = 0xffffffff > hi = 0 for a figure without a voxel)."""
-        K = getattr(self, "_cl_k", 0)
+        K = self._cl_k
         raw = (_lib.VcCluster * max(K, 1))()
         self._check(self._L.vc_fetch_clusters(self._ctx, raw), "vc_fetch_clusters")
         um = np.array([[int(v) for v in raw[k].centre_um] for k in range(K)], dtype=np.int64).reshape(K, 2)
@@ -1077,7 +1083,7 @@ class CarveEngine:
     def fetch_cluster_histograms(self):
         """u32 [K, 512]: per figure the histogram of its seen records' colours in the band of cluster_hull's hist_iz, bin
         (r >> 5) << 6 | (g >> 5) << 3 | (b >> 5), with the colours the records had at that call."""
-        out = np.empty((getattr(self, "_cl_k", 0), 512), dtype=np.uint32)
+        out = np.empty((self._cl_k, 512), dtype=np.uint32)
         self._check(self._L.vc_fetch_cluster_histograms(self._ctx, _ptr(out, ctypes.c_uint32)), "vc_fetch_cluster_histograms")
         return out
 
@@ -1100,7 +1106,7 @@ class CarveEngine:
         first K of voxcarve.clusters.PALETTE).  fetch() / fetch_records(), render and mesh then show the split; the next carve
         gives the camera colours again."""
         from .clusters import PALETTE
-        K = getattr(self, "_cl_k", 0)
+        K = self._cl_k
         pal = np.ascontiguousarray(PALETTE[:K] if palette is None else palette, dtype=np.uint8)
         if pal.shape != (K, 3):
             raise ValueError("paint_clusters: palette of shape %r, expected %r" % (pal.shape, (K, 3)))
@@ -1134,10 +1140,7 @@ class CarveEngine:
         self._check(self._L.vc_hull_geodesic(self._ctx, int(connectivity), mode, _ptr(lst, ctypes.c_uint32) if n else None, n, int(layers),
                                              int(extrema), _lib.VC_GEO_PATHS if paths else 0, ctypes.byref(st)), "vc_hull_geodesic")
         self._geo_k = int(st.extremities)
-        return {"survivors": int(st.survivors), "seeds": int(st.seeds), "reached": int(st.reached), "unreached": int(st.unreached),
-                "max_d": int(st.max_d), "tile_visits": int(st.tile_visits), "tiles": int(st.tiles),
-                "edge_um": tuple(int(v) for v in st.edge_um), "q": tuple(int(v) for v in st.q), "extremities": int(st.extremities),
-                "rounds": int(st.rounds), "launches": int(st.launches), "geodesic_ms": float(st.geodesic_ms)}
+        return _stats(st)
 
     def geodesic_valid(self):
         """True while the outputs of the last hull_geodesic() describe the current hull."""
@@ -1163,7 +1166,7 @@ class CarveEngine:
     def fetch_extrema(self):
         """The extremities of the last hull_geodesic, in the order they were picked: dict of numpy arrays label u32 [E] (1 .. E),
         voxel u32, record u32, d u64 (um, when picked), d_mm float64, index u32 [E, 3] (ix, iy, iz), world_mm float64 [E, 3]."""
-        E = getattr(self, "_geo_k", 0)
+        E = self._geo_k
         raw = (_lib.VcExtremum * max(E, 1))()
         self._check(self._L.vc_fetch_extrema(self._ctx, raw), "vc_fetch_extrema")
         index = np.array([[raw[k].ix, raw[k].iy, raw[k].iz] for k in range(E)], dtype=np.uint32).reshape(E, 3)
@@ -1201,7 +1204,7 @@ class CarveEngine:
         it was picked (the seed set or an earlier extremity): a list of float64 [n, 3] arrays in world mm, extremity first."""
         nx, ny, _ = self.grid
         out = []
-        for k in range(1, getattr(self, "_geo_k", 0) + 1):
+        for k in range(1, self._geo_k + 1):
             i = self._path(self._L.vc_fetch_extremum_path, "vc_fetch_extremum_path", k).astype(np.int64)
             out.append(self.voxel_world_mm((i // ny) % nx, i % ny, i // (nx * ny)))
         if not out:
@@ -1222,8 +1225,8 @@ class CarveEngine:
             raise ValueError("paint_geodesic: mode %r, expected \"labels\" or \"distance\"" % (mode,))
         pal = np.zeros((MAX_K + 1, 3), dtype=np.uint8)
         src = np.asarray(PALETTE if palette is None else palette, dtype=np.uint8)
-        if src.ndim != 2 or src.shape[1] != 3 or src.shape[0] > MAX_K + 1 or (mode == "labels" and src.shape[0] < getattr(self, "_geo_k", 0) + 1):
-            raise ValueError("paint_geodesic: palette of shape %r, expected [%d .. %d, 3]" % (src.shape, getattr(self, "_geo_k", 0) + 1, MAX_K + 1))
+        if src.ndim != 2 or src.shape[1] != 3 or src.shape[0] > MAX_K + 1 or (mode == "labels" and src.shape[0] < self._geo_k + 1):
+            raise ValueError("paint_geodesic: palette of shape %r, expected [%d .. %d, 3]" % (src.shape, self._geo_k + 1, MAX_K + 1))
         pal[:src.shape[0]] = src
         self._check(self._L.vc_paint_geodesic(self._ctx, _lib.VC_GEO_PAINT_LABELS if mode == "labels" else _lib.VC_GEO_PAINT_DISTANCE,
                                               _ptr(pal, ctypes.c_uint8)), "vc_paint_geodesic")
@@ -1288,8 +1291,7 @@ class CarveEngine:
         self._check(self._L.vc_hull_measure(self._ctx, src, None if lab is None else _ptr(lab, ctypes.c_uint32), G,
                                             _lib.VC_MEASURE_PROFILE if profile else 0, ctypes.byref(st)), "vc_hull_measure")
         self._ms_g = int(st.groups)
-        return {"survivors": int(st.survivors), "groups": int(st.groups), "measured": int(st.measured),
-                "unlabelled": int(st.unlabelled), "measure_ms": float(st.measure_ms)}
+        return _stats(st)
 
     def measure_valid(self):
         """True while the measurements of the last measure_hull() describe the current hull."""
@@ -1299,7 +1301,7 @@ class CarveEngine:
         """The groups of the last measure_hull: dict of numpy arrays voxels, surface, seen u64 [G], s1 u64 [G, 3] (sum ix, iy,
         iz), s2 u64 [G, 6] (sum ix^2, iy^2, iz^2, ix iy, ix iz, iy iz), faces u64 [G, 6] (-x, +x, -y, +y, -z, +z), rgb u64 [G, 3]
         (over the seen records), lo / hi u32 [G, 3] (inclusive box in (ix, iy, iz); lo = 0xffffffff > hi = 0 for an empty group)."""
-        G = getattr(self, "_ms_g", 0)
+        G = self._ms_g
         raw = np.zeros((max(G, 1), 24), dtype=np.uint64)
         self._check(self._L.vc_fetch_measure(self._ctx, raw.ctypes.data_as(ctypes.POINTER(_lib.VcMeasure))), "vc_fetch_measure")
         raw = raw[:G]
@@ -1311,7 +1313,7 @@ class CarveEngine:
     def fetch_measure_profile(self):
         """u64 [G, nz, 3]: per group and layer iz {n, sum ix, sum iy} of the last measure_hull(profile=True) -- the cross-section
         and, divided by n, its centre line by height."""
-        G = getattr(self, "_ms_g", 0)
+        G = self._ms_g
         out = np.zeros((max(G, 1), self.grid[2], 3), dtype=np.uint64)
         self._check(self._L.vc_fetch_measure_profile(self._ctx, _ptr(out, ctypes.c_uint64)), "vc_fetch_measure_profile")
         return out[:G]
@@ -1329,8 +1331,7 @@ class CarveEngine:
         st = _lib.VcShellStats()
         self._check(self._L.vc_hull_shell(self._ctx, int(level), 0, ctypes.byref(st)), "vc_hull_shell")
         self._shell_t = int(st.shell)
-        return {"survivors": int(st.survivors), "cells_on": int(st.cells_on), "shell": int(st.shell), "faces": [int(v) for v in st.faces],
-                "level": int(st.level), "cube_scale": int(st.cube_scale), "dims": [int(v) for v in st.dims], "shell_ms": float(st.shell_ms)}
+        return _stats(st, faces=[int(v) for v in st.faces], dims=[int(v) for v in st.dims])     # (these two have been lists)
 
     def shell_valid(self):
         """True while the list of the last hull_shell() describes the current hull."""
@@ -1339,7 +1340,7 @@ class CarveEngine:
     def fetch_shell(self):
         """(records u64 [T], faces u8 [T]) of the last hull_shell: per shell cell {u32 cell index, r, g, b, seen} and the byte of
         its exposed faces (bit k: -x, +x, -y, +y, -z, +z), ascending by cell."""
-        T = getattr(self, "_shell_t", 0)
+        T = self._shell_t
         rec = np.zeros(max(T, 1), dtype=np.uint64)
         faces = np.zeros(max(T, 1), dtype=np.uint8)
         self._check(self._L.vc_fetch_shell(self._ctx, _ptr(rec, ctypes.c_uint64), _ptr(faces, ctypes.c_uint8)), "vc_fetch_shell")
@@ -1349,7 +1350,7 @@ class CarveEngine:
         """(positions float32 [T, 3], colors float32 [T, 3]) of the last hull_shell, made on the device: at level 0 exactly
         viewer_positions(voxel_keys(...)) and viewer_colors(...) of the shell's voxels; above it the centre of each coarse cell
         (draw its cube cube_scale times as large)."""
-        T = getattr(self, "_shell_t", 0)
+        T = self._shell_t
         pos = np.zeros((max(T, 1), 3), dtype=np.float32)
         col = np.zeros((max(T, 1), 3), dtype=np.float32)
         self._check(self._L.vc_fetch_shell_viewer(self._ctx, float(scaling_factor), _ptr(pos, ctypes.c_float), _ptr(col, ctypes.c_float)),
@@ -1383,9 +1384,7 @@ class CarveEngine:
                                          None if lst is None or lst.size == 0 else _ptr(lst, ctypes.c_uint32),
                                          0 if lst is None else lst.size, int(max_passes), 0, ctypes.byref(st)), "vc_hull_thin")
         self._thin = (int(st.survivors), int(st.kept))
-        out = {name: int(getattr(st, name)) for name, _ in _lib.VcThinStats._fields_ if name != "thin_ms"}
-        out["thin_ms"] = float(st.thin_ms)
-        return out
+        return _stats(st)
 
     def thin_valid(self):
         """True while the skeleton of the last thin_hull() describes the current hull."""
@@ -1394,7 +1393,7 @@ class CarveEngine:
     def fetch_thin(self):
         """u16 [S]: per record 0 when the last thin_hull kept its voxel, else 1 + 6 (pass - 1) + d of the direction step that
         removed it -- the order in which the hull was peeled."""
-        S = getattr(self, "_thin", (0, 0))[0]
+        S = self._thin[0]
         out = np.zeros(max(S, 1), dtype=np.uint16)
         self._check(self._L.vc_fetch_thin(self._ctx, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))), "vc_fetch_thin")
         return out[:S]
@@ -1402,7 +1401,7 @@ class CarveEngine:
     def fetch_skeleton(self):
         """The kept voxels of the last thin_hull, ascending by voxel: dict of voxel u32 [K], record u32 [K], degree u8 [K] (the
         kept voxels among the 26 neighbours) and index i64 [K, 3] = (ix, iy, iz)."""
-        K = getattr(self, "_thin", (0, 0))[1]
+        K = self._thin[1]
         raw = np.zeros((max(K, 1), 3), dtype=np.uint32)
         self._check(self._L.vc_fetch_skeleton(self._ctx, raw.ctypes.data_as(ctypes.POINTER(_lib.VcSkeletonVoxel))), "vc_fetch_skeleton")
         raw = raw[:K]
@@ -1471,7 +1470,7 @@ class CarveEngine:
 
     def allgather(self):
         """RCCL all-gather of all ranks' survivor records; returns (counts per rank, total)."""
-        counts = np.zeros(getattr(self, "n_ranks", 1), dtype=np.uint64)
+        counts = np.zeros(self.n_ranks, dtype=np.uint64)
         total = ctypes.c_uint64(0)
         self._check(self._L.vc_allgather(self._ctx, _ptr(counts, ctypes.c_uint64), ctypes.byref(total)),
                     "vc_allgather")
