@@ -752,6 +752,75 @@ int vc_texture_render(vc_ctx *ctx, uint32_t slot, uint32_t steps, double reach_m
                       uint32_t sharpen, uint32_t filter, uint32_t flags /* must be 0 */, vc_texture_stats_t *stats);
 int vc_fetch_textured(vc_ctx *ctx, uint32_t view, uint8_t *rgb, float *depth, uint8_t *count, uint8_t *best_cam, uint8_t *refined);
 
+/* ---- lit renders: cast shadows, ambient occlusion and a floor (the reference's viewer has a positioned light, a shadow map and a
+ * floor grid; this is their headless counterpart, not a port) ------------------------------------------------------------------------
+ * vc_light_render is a pass over the images of the last vc_render, like vc_shade_render and vc_texture_render: every hit pixel,
+ * and every pixel that sees the floor, casts one ray to the light and sixteen rays into the hemisphere above its face through the
+ * current carve result.  It reads the render's images, the occupancy, the records and -- with smooth = 1 -- the normals of a
+ * current vc_hull_normals; it changes none of them, and vc_fetch_render, vc_fetch_shaded and vc_fetch_textured stay as they are.
+ * The contract, bit for bit (tests/light_np.py restates it); float64 with no contraction, in the order written.  Symbols are
+ * those of items 1-5 of vc_render.  Per pixel of each view of the last render:
+ *   1 primary ray and point: o, d = item 2 of vc_render for the stored view.  A HULL pixel is a hit of the render that is no
+ *     floor pixel; t' = (double)depth of the render, Q_a = o_a + t' * d_a.
+ *   2 start cell: c = the hit cell (from idx), face = 2a + k.  c0 = c moved one cell along axis a, by -1 when k = 0 and by +1 when
+ *     k = 1: the cell the primary ray came from, empty or outside the grid.  The outward sign is sigma = -1 for k = 0, +1 for
+ *     k = 1.  Face 6 (the camera inside a survivor): the pixel keeps the render's rgb, shadow = 0, ao = 16, and casts no ray.
+ *     c0 outside the grid: every secondary ray of the pixel is open (it leaves a convex grid).
+ *   3 secondary walk: item 4 of vc_render from cell c0 with t = 0, origin Q and a direction e -- the same tn, the same tie rule,
+ *     the same step bound; it starts from the given cell, not from item 3's entry, so that rounding of Q cannot put the ray back
+ *     into the voxel it left.  It gives hit or miss and the hit's t.
+ *   4 shadow ray: e = pos[0..2] - Q for a point light (pos[3] = 1, world mm), pos[0..2] for a directional one (pos[3] = 0, from
+ *     the surface towards the light).  sigma * e_a <= 0: the face is turned away, shadow = 2, no walk.  Otherwise the ray is
+ *     occluded iff the walk hits and, for a point light, t < 1; shadow = 1 when occluded, else 0.
+ *   5 occlusion rays: sixteen vectors (iu, iv, in) in the face's frame, u = (a + 1) % 3, v = (a + 2) % 3, the normal axis a with
+ *     sign sigma.  Four rings of four: (+-1, 0, 2) and (0, +-1, 2); (+-1, +-1, 2); (+-1, 0, 1) and (0, +-1, 1); (+-1, +-1, 1); in a
+ *     ring the order is +u, -u, +v, -v, or (+, +), (+, -), (-, +), (-, -).  e_u = (double)iu * s_u, e_v = (double)iv * s_v,
+ *     e_a = (double)(sigma in) * s_a.  Ray k is occluded iff its walk hits with t < ao_reach / sqrt((double)(iu^2 + iv^2 + in^2)).
+ *     ao = the open rays, 0..16; ao_reach = 0: no rays, ao = 16.
+ *   6 floor (floor = 1): a FLOOR pixel has d_z != 0, tf = (floor_z - o_z) / d_z > 0, is a miss of the render or has
+ *     tf < (double)depth, and Q = o + tf * d has floor_rect[0] <= Q_x <= floor_rect[1], floor_rect[2] <= Q_y <= floor_rect[3].
+ *     Its base colour is floor_rgb[(kx + ky) & 1], kx = (int64)floor(Q_x / floor_cell_mm), ky alike.  Its frame is a = 2,
+ *     sigma = -1 if o_z < floor_z, else +1.  Its secondary rays are items 3 AND 4 of vc_render in full (entry, then walk) from
+ *     origin Q -- the floor may lie outside the grid --, judged by 4 and 5 above; a ray that misses the grid is open.
+ *   7 shade: the normal is the record's of vc_hull_normals when smooth = 1, its w = 1 (w is 0 or 1: any w != 0 counts) and n16 != 0,
+ *     else the face normal (sigma on
+ *     axis a, 0 elsewhere); always the face normal on the floor.  c as in vc_shade_render with L = e of the shadow ray.
+ *     a_term = (ambient * ao * 2 + 16) / 32 in integers; s = a_term + (shadow ? 0 : (uint32_t)floor((double)(255 - ambient) * c +
+ *     0.5)); rgb_k = (base_k * s + 127) / 255, base = the record's RGB as it is at this call, or the floor's colour.
+ *   8 outputs: rgb; depth = the render's, (float)tf on the floor; kind = 0 background, 1 hull, 2 floor; shadow; ao.  A background
+ *     pixel keeps the render's rgb and depth, shadow = 0, ao = 16.
+ * stats (required): pixels = n_views H W, hull_pixels, floor_pixels, shadowed (shadow = 1), facing_away (shadow = 2), rays_walked =
+ * the shadow rays of item 4 that are not turned away plus, when ao_reach > 0, 16 per hull or floor pixel -- face-6 pixels cast and
+ * count none, an open ray of a start cell outside the grid counts (all contract); cells_visited, blocks_skipped = diagnostics of
+ * the walk the device took (option render_blocks, same images); light_ms = HIP events around the whole call.
+ * VC_ERR_ARG (with a message, nothing launched, the lit images of an earlier call left as they were) when there is no carve
+ * result, steps are in flight, the carve ran with VC_FLAG_NO_RECORDS, the slab is narrower than the grid, a communicator of more
+ * than one rank is attached, the last render is missing or did not run on the current result, smooth = 1 without normals of the
+ * current result, flags != 0, stats or light == NULL, a parameter that is not finite, pos[3] neither 0 nor 1, a direction whose
+ * squared length is no normal number, ambient > 255, smooth or floor > 1, ao_reach < 0, and with floor = 1 an empty rectangle, or
+ * floor_cell_mm not > 0 or so small that a bound of the rectangle is 2^52 cells or more from 0.  An empty hull is no error.
+ * Synchronous.  The images stay valid until the next vc_light_render, the next vc_render or vc_destroy.  vc_fetch_lit copies one
+ * view out (rgb [H W 3], the others [H W]; any pointer may be NULL); it fails before the first vc_light_render on the last render
+ * and for view >= n_views. */
+typedef struct {
+    double pos[4];               /* x, y, z, w: w = 1 a point in world mm, w = 0 a direction from the surface towards the light */
+    uint32_t ambient;            /* 0..255 */
+    uint32_t smooth;             /* 1: shade by the normals of vc_hull_normals */
+    double ao_reach;             /* >= 0, in grid steps (the comparison of item 5); 0: no occlusion rays */
+    uint32_t floor;              /* 0 | 1 */
+    double floor_z;
+    double floor_rect[4];        /* x0, x1, y0, y1 */
+    double floor_cell_mm;        /* > 0 */
+    uint8_t floor_rgb[2][3];
+} vc_light_t;
+typedef struct {
+    uint64_t pixels, hull_pixels, floor_pixels, shadowed, facing_away, rays_walked;   /* contract */
+    uint64_t cells_visited, blocks_skipped;                                            /* diagnostics, implementation-defined */
+    float light_ms;                                                                    /* HIP events around the whole call */
+} vc_light_stats_t;
+int vc_light_render(vc_ctx *ctx, const vc_light_t *light, uint32_t flags /* must be 0 */, vc_light_stats_t *stats);
+int vc_fetch_lit(vc_ctx *ctx, uint32_t view, uint8_t *rgb, float *depth, uint8_t *kind, uint8_t *shadow, uint8_t *ao);
+
 /* ---- the hull split into K figures on the floor plane (no reference counterpart) --------------------------------------------------
  * vc_hull_clusters runs K-means over the columns of the current carve result, as vc_fetch_occupancy and vc_fetch_records see it
  * (photo carve, components, morphology, grow and footprint rules included): world "up" is -z, so a floor position is a column

@@ -12,7 +12,8 @@ what is thinner than the ball leaves the hull; --close MM: the hull closed by a 
 carve and before any opening, assignment.configure(hull_close_mm=MM) -- tunnels and dents narrower than the ball are filled, which
 is what a hole in one camera's mask carves; --smooth (with --render): every hit shaded by the hull's surface normal under a
 headlight, assignment.render_views(smooth=True), instead of the six face brightnesses; --textured (with --render; colour mode `visible`, the default with it): every hit refined
-along its ray against the silhouettes and coloured from the camera images that see it, assignment.render_views(textured=True);
+along its ray against the silhouettes and coloured from the camera images that see it, assignment.render_views(textured=True); --lit (with --render, also with --smooth): cast shadows, ambient occlusion and a
+chequered floor under a point light above the first camera, assignment.render_views(lit=True);
 --normals (with --mesh): the PLY carries
 nx, ny, nz per vertex, assignment.surface_mesh(normals=True); --clusters K: the hull split into K figures on the floor plane on
 the device, assignment.configure(clusters=K) -- their floor positions in world mm and their sizes are printed; --cluster-paint
@@ -54,6 +55,11 @@ if smooth:
 textured = "--textured" in sys.argv
 if textured:
     sys.argv.remove("--textured")
+lit = "--lit" in sys.argv
+if lit:
+    sys.argv.remove("--lit")
+if lit and textured:
+    sys.exit("--lit lights the voxel render; --textured takes its colours from the camera images")
 with_normals = "--normals" in sys.argv
 if with_normals:
     sys.argv.remove("--normals")
@@ -262,6 +268,13 @@ if render_dir:
         ts = r["texture_stats"]
         print("textured: %d of %d hits refined along their rays, %d coloured from the camera images, %d kept the voxel colour "
               "(%.2f ms for 8 views on the device)" % (ts["refined"], ts["hits"], ts["textured"], ts["fallback"], ts["texture_ms"]))
+    elif lit:
+        r = assignment.render_views(orbit, 1920, 1080, lit=True, smooth=smooth)
+        c = assignment.render_views(lit=True, smooth=smooth)
+        ls = r["light_stats"]
+        print("lit: %d hull and %d floor pixels, %d in shadow, %d turned from the light, %d secondary rays "
+              "(%.2f ms for 8 views on the device)" % (ls["hull_pixels"], ls["floor_pixels"], ls["shadowed"], ls["facing_away"],
+                                                        ls["rays_walked"], ls["light_ms"]))
     elif smooth:
         r = assignment.render_views(orbit, 1920, 1080, smooth=True)
         c = assignment.render_views(smooth=True)

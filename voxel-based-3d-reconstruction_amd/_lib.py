@@ -6,6 +6,8 @@ device, loading / context creation raises -- nothing here falls back to the CPU.
 import ctypes
 import os
 
+from . import lighting           # the lit pass's structs (vc_light_t, vc_light_stats_t) and its defaults
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvoxcarve.so")
 
@@ -304,6 +306,8 @@ SIGNATURES = {
     "vc_texture_render": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_float, ctypes.c_uint32,
                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(VcTextureStats)]),
     "vc_fetch_textured": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, ctypes.POINTER(ctypes.c_float), c_u8p, c_u8p, c_u8p]),
+    "vc_light_render": (ctypes.c_int, [c_ctx, ctypes.POINTER(lighting.Light), ctypes.c_uint32, ctypes.POINTER(lighting.LightStats)]),
+    "vc_fetch_lit": (ctypes.c_int, [c_ctx, ctypes.c_uint32, c_u8p, ctypes.POINTER(ctypes.c_float), c_u8p, c_u8p, c_u8p]),
     "vc_hull_clusters": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                         c_i64p, ctypes.c_uint32, ctypes.POINTER(VcClusterStats)]),
     "vc_fetch_cluster_labels": (ctypes.c_int, [c_ctx, c_u8p]),

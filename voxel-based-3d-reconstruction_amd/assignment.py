@@ -569,7 +569,8 @@ def _ensure_normals():
         _engine.hull_normals(_settings["normal_radius_mm"])
 
 
-def render_views(views=None, width=None, height=None, shade=None, smooth=False, ambient=64, textured=False, texture_steps=8):
+def render_views(views=None, width=None, height=None, shade=None, smooth=False, ambient=64, textured=False, texture_steps=8,
+                 lit=False, light=None, floor="auto"):
     """Images of the hull of the last set_voxel_positions call, after whatever configure(...) asked for (component filter,
     photo carve, colouring), ray-cast on the device (CarveEngine.render): views = a list of camera.Camera (default: the
     calibrated cameras), width x height pixels (default: the mask size).  Returns the dict of CarveEngine.render: rgb
@@ -578,12 +579,24 @@ def render_views(views=None, width=None, height=None, shade=None, smooth=False, 
     unshaded one; ambient 0..255 is the brightness of a surface that faces away).  textured=True colours every hit from the
     frame's camera images instead of its voxel, after texture_steps bisection steps along the ray against the silhouettes
     (CarveEngine.render_textured: rgb is the textured image, rgb_voxels the render's own, depth the refined one); it needs
-    configure(color_mode="visible"), whose depth maps say which cameras see a point, and excludes smooth and shade."""
+    configure(color_mode="visible"), whose depth maps say which cameras see a point, and excludes smooth and shade.
+    lit=True adds cast shadows, ambient occlusion and a floor (CarveEngine.render_lit: rgb is the lit image, rgb_flat the
+    render's own, with kind, shadow and ao per pixel): light = (x, y, z, w), None = a point light above the first view's
+    camera; floor = None, "auto" or a dict (CarveEngine.light_render); smooth=True lights by the normals.  It excludes textured
+    and shade."""
     if _engine is None or not initialized or _sized is None:
         raise RuntimeError("set_voxel_positions has not run")
     H, W = _engine.image_size
     views = _cameras if views is None else views
     H, W = H if height is None else height, W if width is None else width
+    if lit:
+        if textured:
+            raise ValueError("render_views: lit=True lights the voxel render; textured=True takes its colours from the camera images")
+        if shade is not None:
+            raise ValueError("render_views: shade is the flat render's; lit=True shades by the light")
+        if smooth:
+            _ensure_normals()
+        return _engine.render_lit(views, H, W, light=light, ambient=ambient, smooth=smooth, floor=floor)
     if textured:
         if smooth or shade is not None:
             raise ValueError("render_views: textured=True takes its colours from the camera images; smooth and shade are the voxel render's")

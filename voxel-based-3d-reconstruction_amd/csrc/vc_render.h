@@ -11,6 +11,8 @@
 //                  (each axis's events are non-decreasing in t, so the voxel walk takes all events in (t, axis) order, and
 //                  inside an empty block it can only end at the block's exit).  A hit's colour comes from a binary search of
 //                  the records (ascending index).  Hits, cells looked at and blocks skipped: wave sums, one atomic per wave.
+// The ray, the entry and the walk are functions of their own (rpixel, rentry, rwalk): vc_texture.h takes the ray, vc_light.h all
+// three for its secondary rays.
 #pragma once
 #include "vc_kernels.h"          // wave_sum_u32
 
@@ -127,6 +129,134 @@ __device__ __forceinline__ void radvance(RAxis &a, int ax, double xt, int xa)
 
 __device__ __forceinline__ bool rinside(const RAxis &a) { return a.c >= 0 && a.c < a.n; }
 
+// Item 2: origin and direction of the ray of pixel (u, v) of a view.
+__device__ __forceinline__ void rpixel(const RenderView &vw, uint32_t u, uint32_t v, double &o0, double &o1, double &o2,
+                                       double &d0, double &d1, double &d2)
+{
+    const double fx = vw.K[0], fy = vw.K[1], cx = vw.K[2], cy = vw.K[3];
+    const double k1 = vw.dist[0], k2 = vw.dist[1], p1 = vw.dist[2], p2 = vw.dist[3], k3 = vw.dist[4];
+    const double xd = (((double)u + 0.5) - cx) / fx, yd = (((double)v + 0.5) - cy) / fy;
+    double x = xd, y = yd;
+    for (int it = 0; it < 8; ++it) {
+        const double r2 = x * x + y * y;
+        const double cd = ((1.0 + k1 * r2) + (k2 * r2) * r2) + ((k3 * r2) * r2) * r2;
+        const double dx = ((2.0 * p1) * x) * y + p2 * (r2 + (2.0 * x) * x);
+        const double dy = p1 * (r2 + (2.0 * y) * y) + ((2.0 * p2) * x) * y;
+        x = (xd - dx) / cd;
+        y = (yd - dy) / cd;
+    }
+    const double *R = vw.R, *t = vw.t;
+    d0 = (x * R[0] + y * R[3]) + R[6];
+    d1 = (x * R[1] + y * R[4]) + R[7];
+    d2 = (x * R[2] + y * R[5]) + R[8];
+    o0 = -((R[0] * t[0] + R[3] * t[1]) + R[6] * t[2]);
+    o1 = -((R[1] * t[0] + R[4] * t[1]) + R[7] * t[2]);
+    o2 = -((R[2] * t[0] + R[5] * t[1]) + R[8] * t[2]);
+}
+
+// The rest of an axis once o and d are set: the grid's boundaries (item 1) and the direction's inverse and sign.
+__device__ __forceinline__ void raxis(RAxis &a, double e, double s, uint32_t n)
+{
+    a.e = e; a.s = s; a.n = (int32_t)n;
+    a.inv = a.d != 0.0 ? 1.0 / a.d : 0.0;
+    a.up = a.d > 0.0;
+}
+
+// Item 3: the slab entry of a ray whose axes hold o, d, inv, e, s, n, up.  True: the ray misses the grid.  Otherwise t_in, the
+// axis of entry (-1: the ray starts inside), and every axis's cell and next boundary parameter.
+__device__ __forceinline__ bool rentry(RAxis &A0, RAxis &A1, RAxis &A2, double &t_in, int &ax)
+{
+    bool miss = false;
+    double n0, f0, n1, f1, n2, f2;
+    rslab(A0, n0, f0, miss);
+    rslab(A1, n1, f1, miss);
+    rslab(A2, n2, f2, miss);
+    double t_out = __builtin_inf();
+    t_in = 0.0;
+    if (n0 > t_in) t_in = n0;
+    if (n1 > t_in) t_in = n1;
+    if (n2 > t_in) t_in = n2;
+    if (f0 < t_out) t_out = f0;
+    if (f1 < t_out) t_out = f1;
+    if (f2 < t_out) t_out = f2;
+    if (t_in >= t_out) miss = true;
+    ax = -1;
+    if (miss) return true;
+    if (t_in > 0.0) ax = n0 == t_in ? 0 : (n1 == t_in ? 1 : (n2 == t_in ? 2 : -1));
+    A0.c = ax == 0 ? (A0.up ? 0 : A0.n - 1) : rcell(A0, t_in);
+    A1.c = ax == 1 ? (A1.up ? 0 : A1.n - 1) : rcell(A1, t_in);
+    A2.c = ax == 2 ? (A2.up ? 0 : A2.n - 1) : rcell(A2, t_in);
+    A0.tn = rnext(A0); A1.tn = rnext(A1); A2.tn = rnext(A2);
+    return false;
+}
+
+// Item 4: the walk from the cells the axes hold (inside the grid, tn set).  True on a hit: oidx its linear index, tt the
+// parameter and ax the axis of the step that entered it (both left as given when the first cell is the hit).  skip: empty
+// blocks of 8^3 voxels are left in one step (bmap; the same results).  cells, skips: cells looked at, blocks skipped (added).
+// t_stop: the walk gives up (no hit) once a step has taken its parameter to t_stop or beyond.  From the first step on tt never
+// decreases (each axis's events are non-decreasing and every step takes the least), so a caller that only asks for hits with
+// t < t_stop loses none; the starting cell is looked at whatever tt it is given.  +inf walks to the end -- unless a step takes
+// tt itself to +inf, which needs all three tn at +inf: no direction of a validated view or light gets there.
+__device__ __forceinline__ bool rwalk(const uint64_t *__restrict__ words, const uint64_t *__restrict__ bmap, uint32_t skip,
+                                      const uint32_t (&n)[3], const uint32_t (&nb)[3], RAxis &A0, RAxis &A1, RAxis &A2,
+                                      double &tt, int &ax, uint32_t &oidx, uint32_t &cells, uint32_t &skips, double t_stop)
+{
+    const uint64_t nx = n[0], ny = n[1], nbx = nb[0], nby = nb[1];
+    uint64_t cw = ~0ull, cword = 0, cbw = ~0ull, cbword = 0;   // the occupancy / map word in hand
+    bool hit = false;
+    // every iteration moves an axis one way for good: at most nx + ny + nz of them
+    const uint32_t limit = n[0] + n[1] + n[2] + 1;
+    for (uint32_t guard = 0; guard < limit; ++guard) {
+        bool full = true;
+        if (skip) {
+            const uint64_t lb = ((uint64_t)(A2.c >> kRenderShift) * nbx + (uint64_t)(A0.c >> kRenderShift)) * nby +
+                                (uint64_t)(A1.c >> kRenderShift);
+            if ((lb >> 6) != cbw) { cbw = lb >> 6; cbword = bmap[cbw]; }
+            full = (cbword >> (lb & 63)) & 1ull;
+        }
+        if (full) {
+            ++cells;
+            const uint64_t lin = ((uint64_t)A2.c * nx + (uint64_t)A0.c) * ny + (uint64_t)A1.c;
+            if ((lin >> 6) != cw) { cw = lin >> 6; cword = words[cw]; }
+            if ((cword >> (lin & 63)) & 1ull) {
+                hit = true;
+                oidx = (uint32_t)lin;
+                break;
+            }
+            int best = 0;
+            double bt = A0.tn;
+            if (A1.tn < bt) { best = 1; bt = A1.tn; }
+            if (A2.tn < bt) { best = 2; bt = A2.tn; }
+            tt = bt;
+            ax = best;
+            if (best == 0) { A0.c += A0.up ? 1 : -1; A0.tn = rnext(A0); }
+            else if (best == 1) { A1.c += A1.up ? 1 : -1; A1.tn = rnext(A1); }
+            else { A2.c += A2.up ? 1 : -1; A2.tn = rnext(A2); }
+        } else {
+            ++skips;
+            int32_t k0, k1b, k2b;
+            double b0, b1, b2;
+            rexit(A0, k0, b0);
+            rexit(A1, k1b, b1);
+            rexit(A2, k2b, b2);
+            int xa = 0;
+            double xt = b0;
+            if (b1 < xt) { xa = 1; xt = b1; }
+            if (b2 < xt) { xa = 2; xt = b2; }
+            radvance(A0, 0, xt, xa);
+            radvance(A1, 1, xt, xa);
+            radvance(A2, 2, xt, xa);
+            if (xa == 0) { A0.c = A0.up ? k0 : k0 - 1; A0.tn = rnext(A0); }
+            else if (xa == 1) { A1.c = A1.up ? k1b : k1b - 1; A1.tn = rnext(A1); }
+            else { A2.c = A2.up ? k2b : k2b - 1; A2.tn = rnext(A2); }
+            tt = xt;
+            ax = xa;
+        }
+        if (!rinside(A0) || !rinside(A1) || !rinside(A2) || tt >= t_stop) break;
+    }
+    return hit;
+}
+
 __global__ __launch_bounds__(kRenderBlock) void k_render(const RenderParams p)
 {
     const uint32_t lane = threadIdx.x & 63;
@@ -136,112 +266,19 @@ __global__ __launch_bounds__(kRenderBlock) void k_render(const RenderParams p)
         const uint32_t view = tile / p.tiles_per_view, tr = tile % p.tiles_per_view;
         const uint32_t u = (tr % p.tiles_x) * 8 + (lane & 7), v = (tr / p.tiles_x) * 8 + (lane >> 3);
         if (u < p.W && v < p.H) {
-            const RenderView &vw = p.views[view];
-            const double fx = vw.K[0], fy = vw.K[1], cx = vw.K[2], cy = vw.K[3];
-            const double k1 = vw.dist[0], k2 = vw.dist[1], p1 = vw.dist[2], p2 = vw.dist[3], k3 = vw.dist[4];
             // 2 the pixel ray
-            const double xd = (((double)u + 0.5) - cx) / fx, yd = (((double)v + 0.5) - cy) / fy;
-            double x = xd, y = yd;
-            for (int it = 0; it < 8; ++it) {
-                const double r2 = x * x + y * y;
-                const double cd = ((1.0 + k1 * r2) + (k2 * r2) * r2) + ((k3 * r2) * r2) * r2;
-                const double dx = ((2.0 * p1) * x) * y + p2 * (r2 + (2.0 * x) * x);
-                const double dy = p1 * (r2 + (2.0 * y) * y) + ((2.0 * p2) * x) * y;
-                x = (xd - dx) / cd;
-                y = (yd - dy) / cd;
-            }
-            const double *R = vw.R, *t = vw.t;
             RAxis A0, A1, A2;
-            A0.d = (x * R[0] + y * R[3]) + R[6];
-            A1.d = (x * R[1] + y * R[4]) + R[7];
-            A2.d = (x * R[2] + y * R[5]) + R[8];
-            A0.o = -((R[0] * t[0] + R[3] * t[1]) + R[6] * t[2]);
-            A1.o = -((R[1] * t[0] + R[4] * t[1]) + R[7] * t[2]);
-            A2.o = -((R[2] * t[0] + R[5] * t[1]) + R[8] * t[2]);
-            A0.e = p.e[0]; A1.e = p.e[1]; A2.e = p.e[2];
-            A0.s = p.s[0]; A1.s = p.s[1]; A2.s = p.s[2];
-            A0.n = (int32_t)p.n[0]; A1.n = (int32_t)p.n[1]; A2.n = (int32_t)p.n[2];
-            A0.inv = A0.d != 0.0 ? 1.0 / A0.d : 0.0;
-            A1.inv = A1.d != 0.0 ? 1.0 / A1.d : 0.0;
-            A2.inv = A2.d != 0.0 ? 1.0 / A2.d : 0.0;
-            A0.up = A0.d > 0.0; A1.up = A1.d > 0.0; A2.up = A2.d > 0.0;
-            // 3 entry
-            bool miss = false;
-            double n0, f0, n1, f1, n2, f2;
-            rslab(A0, n0, f0, miss);
-            rslab(A1, n1, f1, miss);
-            rslab(A2, n2, f2, miss);
-            double t_in = 0.0, t_out = __builtin_inf();
-            if (n0 > t_in) t_in = n0;
-            if (n1 > t_in) t_in = n1;
-            if (n2 > t_in) t_in = n2;
-            if (f0 < t_out) t_out = f0;
-            if (f1 < t_out) t_out = f1;
-            if (f2 < t_out) t_out = f2;
-            if (t_in >= t_out) miss = true;
+            rpixel(p.views[view], u, v, A0.o, A1.o, A2.o, A0.d, A1.d, A2.d);
+            raxis(A0, p.e[0], p.s[0], p.n[0]);
+            raxis(A1, p.e[1], p.s[1], p.n[1]);
+            raxis(A2, p.e[2], p.s[2], p.n[2]);
+            // 3 entry, 4 the walk
             uint32_t oidx = kRenderMiss, orgbf = p.bg | (255u << 24);
             float odepth = __builtin_inff();
-            if (!miss) {
-                int ax = -1;                                             // axis of entry / of the last step; -1: started inside
-                if (t_in > 0.0) ax = n0 == t_in ? 0 : (n1 == t_in ? 1 : (n2 == t_in ? 2 : -1));
-                A0.c = ax == 0 ? (A0.up ? 0 : A0.n - 1) : rcell(A0, t_in);
-                A1.c = ax == 1 ? (A1.up ? 0 : A1.n - 1) : rcell(A1, t_in);
-                A2.c = ax == 2 ? (A2.up ? 0 : A2.n - 1) : rcell(A2, t_in);
-                A0.tn = rnext(A0); A1.tn = rnext(A1); A2.tn = rnext(A2);
-                const uint64_t nx = p.n[0], ny = p.n[1], nbx = p.nb[0], nby = p.nb[1];
-                uint64_t cw = ~0ull, cword = 0, cbw = ~0ull, cbword = 0;   // the occupancy / map word in hand
-                double tt = t_in;
-                bool hit = false;
-                // 4 the walk; every iteration moves an axis one way for good: at most nx + ny + nz of them
-                const uint32_t limit = p.n[0] + p.n[1] + p.n[2] + 1;
-                for (uint32_t guard = 0; guard < limit; ++guard) {
-                    bool full = true;
-                    if (p.skip) {
-                        const uint64_t lb = ((uint64_t)(A2.c >> kRenderShift) * nbx + (uint64_t)(A0.c >> kRenderShift)) * nby +
-                                            (uint64_t)(A1.c >> kRenderShift);
-                        if ((lb >> 6) != cbw) { cbw = lb >> 6; cbword = p.bmap[cbw]; }
-                        full = (cbword >> (lb & 63)) & 1ull;
-                    }
-                    if (full) {
-                        ++cells;
-                        const uint64_t lin = ((uint64_t)A2.c * nx + (uint64_t)A0.c) * ny + (uint64_t)A1.c;
-                        if ((lin >> 6) != cw) { cw = lin >> 6; cword = p.words[cw]; }
-                        if ((cword >> (lin & 63)) & 1ull) {
-                            hit = true;
-                            oidx = (uint32_t)lin;
-                            break;
-                        }
-                        int best = 0;
-                        double bt = A0.tn;
-                        if (A1.tn < bt) { best = 1; bt = A1.tn; }
-                        if (A2.tn < bt) { best = 2; bt = A2.tn; }
-                        tt = bt;
-                        ax = best;
-                        if (best == 0) { A0.c += A0.up ? 1 : -1; A0.tn = rnext(A0); }
-                        else if (best == 1) { A1.c += A1.up ? 1 : -1; A1.tn = rnext(A1); }
-                        else { A2.c += A2.up ? 1 : -1; A2.tn = rnext(A2); }
-                    } else {
-                        ++skips;
-                        int32_t k0, k1b, k2b;
-                        double b0, b1, b2;
-                        rexit(A0, k0, b0);
-                        rexit(A1, k1b, b1);
-                        rexit(A2, k2b, b2);
-                        int xa = 0;
-                        double xt = b0;
-                        if (b1 < xt) { xa = 1; xt = b1; }
-                        if (b2 < xt) { xa = 2; xt = b2; }
-                        radvance(A0, 0, xt, xa);
-                        radvance(A1, 1, xt, xa);
-                        radvance(A2, 2, xt, xa);
-                        if (xa == 0) { A0.c = A0.up ? k0 : k0 - 1; A0.tn = rnext(A0); }
-                        else if (xa == 1) { A1.c = A1.up ? k1b : k1b - 1; A1.tn = rnext(A1); }
-                        else { A2.c = A2.up ? k2b : k2b - 1; A2.tn = rnext(A2); }
-                        tt = xt;
-                        ax = xa;
-                    }
-                    if (!rinside(A0) || !rinside(A1) || !rinside(A2)) break;
-                }
+            double tt = 0.0;
+            int ax = -1;                                                 // axis of entry / of the last step; -1: started inside
+            if (!rentry(A0, A1, A2, tt, ax)) {
+                const bool hit = rwalk(p.words, p.bmap, p.skip, p.n, p.nb, A0, A1, A2, tt, ax, oidx, cells, skips, __builtin_inf());
                 if (hit) {
                     hits = 1;
                     const bool pos = ax == 0 ? A0.up : (ax == 1 ? A1.up : A2.up);

@@ -20,7 +20,7 @@
 #pragma once
 #include "vc_device.h"
 #include "vc_kernels.h"          // kMaxCameras, wave_sum_u32
-#include "vc_render.h"           // RenderView, kRenderMiss
+#include "vc_render.h"           // RenderView, rpixel, kRenderMiss
 
 #pragma clang fp contract(off)
 
@@ -133,26 +133,8 @@ __global__ __launch_bounds__(kTexBlock) void k_texture(const TexParams p)
             if (p.idx[o] != kRenderMiss) {
                 hits = 1;
                 // 1 the pixel ray, as k_render makes it
-                const RenderView &vw = p.views[view];
-                const double fx = vw.K[0], fy = vw.K[1], cx = vw.K[2], cy = vw.K[3];
-                const double k1 = vw.dist[0], k2 = vw.dist[1], p1 = vw.dist[2], p2 = vw.dist[3], k3 = vw.dist[4];
-                const double xd = (((double)pu + 0.5) - cx) / fx, yd = (((double)pv + 0.5) - cy) / fy;
-                double x = xd, y = yd;
-                for (int it = 0; it < 8; ++it) {
-                    const double r2 = x * x + y * y;
-                    const double cd = ((1.0 + k1 * r2) + (k2 * r2) * r2) + ((k3 * r2) * r2) * r2;
-                    const double dx = ((2.0 * p1) * x) * y + p2 * (r2 + (2.0 * x) * x);
-                    const double dy = p1 * (r2 + (2.0 * y) * y) + ((2.0 * p2) * x) * y;
-                    x = (xd - dx) / cd;
-                    y = (yd - dy) / cd;
-                }
-                const double *R = vw.R, *t = vw.t;
-                const double d0 = (x * R[0] + y * R[3]) + R[6];
-                const double d1 = (x * R[1] + y * R[4]) + R[7];
-                const double d2 = (x * R[2] + y * R[5]) + R[8];
-                const double o0 = -((R[0] * t[0] + R[3] * t[1]) + R[6] * t[2]);
-                const double o1 = -((R[1] * t[0] + R[4] * t[1]) + R[7] * t[2]);
-                const double o2 = -((R[2] * t[0] + R[5] * t[1]) + R[8] * t[2]);
+                double o0, o1, o2, d0, d1, d2;
+                rpixel(p.views[view], pu, pv, o0, o1, o2, d0, d1, d2);
                 const double t0 = (double)p.depth[o];
                 // 3 the bracket and the bisection
                 double tt = t0;

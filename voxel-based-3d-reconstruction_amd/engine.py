@@ -5,10 +5,11 @@ voxel_reconstruction.py:35-124 + assignment.py:116-133.  All compute happens in 
 library; this class only marshals numpy buffers across the C ABI.
 """
 import ctypes
+import sys
 
 import numpy as np
 
-from . import _lib
+from . import _lib, lighting
 from .camera import Camera
 
 # reference voxel_reconstruction.py:35-36 (x_min, x_max, y_min, y_max, z_min, z_max)
@@ -84,6 +85,11 @@ class CarveEngine:
             self._ctx = _lib.c_ctx()
 
     def __del__(self):
+        # an engine that is still alive when the interpreter shuts down (a module's global, such as
+        # background_subtraction._engine) is left to the process's exit: its context's teardown would run inside a finalising
+        # interpreter, beside the exit handlers of whatever else holds a HIP runtime in the process (torch brings its own copy)
+        if sys.is_finalizing():
+            return
         try:
             self.close()
         except Exception:
@@ -1021,6 +1027,53 @@ class CarveEngine:
         for k in ("rgb", "depth", "count", "best_cam", "refined"):
             out[k] = tex[k]
         out["texture_stats"] = tex["stats"]
+        return out
+
+    # -- lit renders: cast shadows, ambient occlusion and a floor (vc_light_render) ---------------------------------------------------
+    def light_render(self, light, ambient=64, smooth=False, ao_reach=4.0, floor=None):
+        """Lights the images of the last render() (needs a render of the current result; contract: include/voxcarve.h): every hit
+        and every pixel that sees the floor casts a shadow ray to the light and sixteen occlusion rays through the hull.
+        light: (x, y, z, w), w = 1 a point in world mm, w = 0 a direction from the surface towards the light ((x, y, z): a
+        point); ambient 0..255: the brightness the occlusion rays share out, all a shadowed or averted surface gets; smooth:
+        shade by the normals of hull_normals() (which must be current) instead of the cube faces; ao_reach: how far, in grid
+        steps, an occlusion ray looks (0: none); floor: None, "auto" (lighting.auto_floor: the grid's largest z boundary, the
+        x / y bounds grown by half their span, 250 mm cells in two greys) or a dict {z, rect: (x0, x1, y0, y1), cell_mm,
+        rgb: two RGB triples}.  Nothing else changes.  Returns a dict: rgb u8 [V, H, W, 3], depth f32 [V, H, W] (the floor's
+        where it shows), kind u8 [V, H, W] (0 background, 1 hull, 2 floor), shadow u8 [V, H, W] (1 in shadow, 2 turned away),
+        ao u8 [V, H, W] (open rays, 0..16) and stats (pixels, hull_pixels, floor_pixels, shadowed, facing_away, rays_walked,
+        cells_visited, blocks_skipped, light_ms)."""
+        L = lighting.light_struct(light, ambient, smooth, ao_reach, floor, self.grid, getattr(self, "bounds", None))
+        st = lighting.LightStats()
+        self._check(self._L.vc_light_render(self._ctx, ctypes.byref(L), 0, ctypes.byref(st)), "vc_light_render")
+        V, (H, W) = self._render_shape
+        out = {"rgb": np.empty((V, H, W, 3), dtype=np.uint8), "depth": np.empty((V, H, W), dtype=np.float32),
+               "kind": np.empty((V, H, W), dtype=np.uint8), "shadow": np.empty((V, H, W), dtype=np.uint8),
+               "ao": np.empty((V, H, W), dtype=np.uint8)}
+        for k in range(V):
+            self._check(self._L.vc_fetch_lit(self._ctx, k, _ptr(out["rgb"][k], ctypes.c_uint8), _ptr(out["depth"][k], ctypes.c_float),
+                                             _ptr(out["kind"][k], ctypes.c_uint8), _ptr(out["shadow"][k], ctypes.c_uint8),
+                                             _ptr(out["ao"][k], ctypes.c_uint8)), "vc_fetch_lit")
+        out["stats"] = _stats(st)
+        return out
+
+    def render_lit(self, views, H, W, light=None, ambient=64, smooth=False, ao_reach=4.0, floor="auto", background=(0, 0, 0)):
+        """render() + light_render(): images of the hull with cast shadows, ambient occlusion and a floor.  light=None is a point
+        light 1000 mm above (towards -z of) the first view's camera centre, lighting.light_above(views[0]); smooth=True runs
+        hull_normals() when the normals are stale.  Returns render()'s dict with rgb lit and rgb_flat the render's own, depth
+        with the floor's and depth_hull the render's own, kind, shadow, ao, stats (the render's) and light_stats."""
+        views = list(views)
+        if not views:
+            raise ValueError("render_lit: no views")
+        if light is None:
+            light = lighting.light_above(views[0])
+        if smooth and not self.normals_valid():
+            self.hull_normals()
+        out = self.render(views, H, W, background=background)
+        lit = self.light_render(light, ambient, smooth, ao_reach, floor)
+        out["rgb_flat"], out["depth_hull"] = out["rgb"], out["depth"]
+        for k in ("rgb", "depth", "kind", "shadow", "ao"):
+            out[k] = lit[k]
+        out["light_stats"] = lit["stats"]
         return out
 
     def surface_normals(self):
