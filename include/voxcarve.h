@@ -599,6 +599,68 @@ int vc_hull_combine(vc_ctx *ctx, uint32_t op, uint32_t reg, uint32_t flags /* mu
 int vc_fetch_combined(vc_ctx *ctx, uint8_t *added);   /* u8 [S_after], record order: 1 = the voxel was not in A */
 int vc_hull_compare(vc_ctx *ctx, uint32_t reg, uint32_t flags, vc_compare_stats_t *stats);
 
+/* ---- block motion between consecutive hulls, and a hull warp (no reference counterpart) -------------------------------------------
+ * The passes above work on one frame.  vc_hull_motion estimates where each part of the hull went between the hull of a register
+ * (the previous frame, kept by vc_hull_keep) and the current result: one integer vector per block of b^3 voxels, by exhaustive
+ * block matching on the two bit volumes.  Integers and bits only (tests/motion_np.py restates it).
+ *
+ * A is the current occupancy as vc_fetch_occupancy sees it, B the hull of register `reg`, bits only; both are empty outside the
+ * grid.  Parameters: block edge b in {4, 8, 16}, apron a in 0..16, search range s in 1..8, with b + 2a + 2s <= 64 (one y row of a
+ * block's search region is then at most one 64-bit word; 64 itself is allowed).
+ *   1 blocks: the grid is cut into cubes of b^3 voxels, NB = ceil(n / b) per axis (grids need not be multiples of b); block index
+ *     k = (bz NBx + bx) NBy + by, the voxels' own order.  A block is listed when its b^3 cells hold a voxel of A or of B.  Listed
+ *     blocks come out in ascending k.
+ *   2 cost: the window W(k) is the block grown by a cells per side, not clipped.  For d = (dx, dy, dz) in [-s, s]^3:
+ *     cost(k, d) = |{ v in W(k) : A(v) != B(v - d) }|.  d is the displacement of the content from the old hull to the new one.
+ *   3 the choice: the smallest cost wins; among equal costs the smallest dx^2 + dy^2 + dz^2; then the smallest (dz, dx, dy) in
+ *     lexicographic order.  No order of evaluation shows.
+ *   4 row per listed block (vc_motion_t): block; d (x, y, z); flags bit 0: some |component| of d equals s, so the motion may
+ *     exceed the range; cost; cost0 = the cost at d = 0; count_a, count_b = the voxels of A and of B in the block proper; ties =
+ *     how many displacements attain the smallest cost.  1 means the vector is determined; a window whose search region of B is
+ *     solid or empty throughout gives d = 0 with ties = (2s + 1)^3: the aperture problem, reported and not hidden.
+ *   5 stats (required): blocks, listed, moved (d != 0), unique (ties = 1), clipped (flag bit 0), cost0_sum and cost_sum (the
+ *     change before and after compensation, over the listed blocks), a = |A|, b = |B|, motion_ms = HIP events around the call.
+ *   6 vc_hull_motion changes nothing: not the records, not the result generation, not the register.
+ *   7 VC_ERR_ARG (with a message, nothing launched) as item 8 of vc_hull_combine names them for a pass and a filled register, for
+ *     flags != 0, stats == NULL, b, a or s outside their ranges, b + 2a + 2s > 64, and for more than 2^26 blocks.
+ *   8 lifetime: the field is stale once the result generation advances (a carve or any pass that changes the survivors), once
+ *     register `reg` is rewritten (vc_hull_keep, vc_hull_upload) or released, or once grid, slab or cameras change.
+ *     vc_fetch_motion, vc_hull_warp and vc_paint_motion then return VC_ERR_ARG by name.  Colour passes (vc_color_visible,
+ *     vc_paint_clusters, vc_paint_geodesic, vc_paint_motion) leave it valid.
+ * vc_fetch_motion: the listed blocks into *count, their rows into rows (either may be NULL: call with rows NULL to size it).
+ *
+ * vc_hull_warp needs a current field made against register `src`, and dst != src.  It writes to register `dst` the prediction
+ * P(v) = B(v - d_k) for v in listed block k: a gather, so it leaves no holes.  Unlisted blocks are empty (what d = 0 gives there).
+ * P is clipped to the grid; the register holds bits only, no records, and is an ordinary operand of vc_hull_compare and
+ * vc_hull_combine afterwards.  Stats (required): warped = |P|, common = |P & A|, a = |A|, warp_ms.  Refused as vc_hull_motion is,
+ * for dst >= VC_HULL_REGISTERS, src == dst and a field made against another register.  A refused or failed call leaves dst as
+ * it was.
+ *
+ * vc_paint_motion recolours every record by its block's vector, as vc_paint_clusters recolours: channel = 128 + (127 d_axis) / s
+ * with C integer division, x -> R, y -> G, z -> B; index and seen byte stay.  A colour pass: it invalidates what colour passes
+ * invalidate and nothing else.
+ * vc_hull_motion is synchronous with one read-back in the middle (the number of listed blocks). */
+typedef struct {
+    uint32_t block;                     /* k */
+    int8_t d[3];                        /* x, y, z */
+    uint8_t flags;                      /* bit 0: clipped by the search range */
+    uint32_t cost, cost0;
+    uint16_t count_a, count_b, ties, reserved;
+} vc_motion_t;
+typedef struct {
+    uint64_t blocks, listed, moved, unique, clipped, cost0_sum, cost_sum, a, b;
+    float motion_ms;
+} vc_motion_stats_t;
+typedef struct {
+    uint64_t warped, common, a;
+    float warp_ms;
+} vc_warp_stats_t;
+int vc_hull_motion(vc_ctx *ctx, uint32_t reg, uint32_t block, uint32_t apron, uint32_t search, uint32_t flags /* must be 0 */,
+                   vc_motion_stats_t *stats);
+int vc_fetch_motion(vc_ctx *ctx, vc_motion_t *rows /* NULL ok */, uint64_t *count /* NULL ok */);
+int vc_hull_warp(vc_ctx *ctx, uint32_t src, uint32_t dst, uint32_t flags /* must be 0 */, vc_warp_stats_t *stats);
+int vc_paint_motion(vc_ctx *ctx);
+
 /* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
  *      executable.py) -----------------------------------------------------------------------------------------------------------
  * vc_render casts one ray per pixel of each view through the current carve result and keeps, per pixel, the first survivor the

@@ -1,7 +1,7 @@
 """Carves the reference's own scene (4 calibrated cameras + frame-0 MOG masks, committed fixtures) on the
 GPU and writes the visual hull as a coloured point cloud (PLY) -- what the reference hands to its OpenGL
 viewer after `G` is pressed.   python scripts/demo.py [grid=128] [out=hull.ply] [camera|visible|photo] [--render DIR]
-[--smooth] [--textured] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--save-hull PATH] [--subtract PATH] [--clip PATH] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
+[--smooth] [--textured] [--mesh PATH] [--normals] [--footprint centre|any|all] [--temporal T] [--frames F] [--noise P] [--close MM] [--open MM] [--clusters K] [--cluster-paint] [--extremities K] [--geodesic-paint labels|distance] [--measure [all|clusters|geodesic|components]] [--skeleton curve|point] [--skeleton-anchors extrema] [--shell [LEVEL]] [--save-hull PATH] [--subtract PATH] [--clip PATH] [--motion [BLOCK]] [--motion-paint] [--help] (`visible`: every surface voxel coloured by the cameras that see it, assignment.configure(color_mode="visible");
 `photo`: the visual hull refined by photo-consistency carving and coloured that way, assignment.configure(hull="photo");
 out `-`: no PLY; --render DIR: ray-cast images of the hull on the device, 8 orbit views at 1920x1080 and the 4 calibrated
 cameras at mask size, as PNG when Pillow is importable, else binary PPM; --mesh PATH: the hull's surface mesh in world mm,
@@ -38,6 +38,11 @@ raw hulls and between consecutive voted hulls are printed per frame, and the las
 --save-hull PATH: the hull as it stands after every pass (grid, bounds, records) as an .npz, CarveEngine.save_hull;
 --subtract PATH / --clip PATH: a hull saved that way is subtracted from / intersected with every frame's hull on the device right
 after the carve, assignment.configure(hull_subtract=PATH, hull_clip=PATH) -- the voxels each takes away are printed;
+--motion [BLOCK] [--motion-paint] [--frames F]: F frames (default 4) of the committed masks, frame t rolled by 2 t columns, are
+carved one after the other and from the second on the block motion against the previous frame's hull is estimated on the device,
+assignment.configure(motion_block=BLOCK) with BLOCK 4, 8 (the default) or 16 -- per frame the listed, unique and moved blocks, the
+change before and after compensation and the median vector in mm are printed; --motion-paint: every voxel coloured by its block's
+vector (grey = at rest), in the PLY, the --render images and the --mesh;
 --help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
@@ -143,7 +148,20 @@ for flag in ("--save-hull", "--subtract", "--clip"):
             subtract = value
         else:
             clip = value
-temporal, n_frames, noise = 0, 16, 0.02
+motion_block = 0
+if "--motion" in sys.argv:
+    k = sys.argv.index("--motion")
+    motion_block = 8
+    if k + 1 < len(sys.argv) and sys.argv[k + 1] in ("4", "8", "16"):
+        motion_block = int(sys.argv[k + 1])
+        del sys.argv[k + 1]
+    del sys.argv[k]
+motion_paint = "--motion-paint" in sys.argv
+if motion_paint:
+    sys.argv.remove("--motion-paint")
+if motion_block and "--temporal" in sys.argv:
+    sys.exit("--motion rolls the masks from frame to frame, --temporal flips their pixels: one of the two")
+temporal, n_frames, noise = 0, 4 if motion_block else 16, 0.02
 for flag, conv in (("--temporal", int), ("--frames", int), ("--noise", float)):
     if flag in sys.argv:
         k = sys.argv.index(flag)
@@ -170,7 +188,10 @@ if temporal:
     for t in range(n_frames):
         rng = np.random.default_rng(7000 + t)
         sets.append((frames, [np.where(rng.random(m.shape) < noise, 255 - m, m).astype(np.uint8) for m in masks]))
-assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal,
+if motion_block:
+    sets = [(frames, [np.roll(m, 2 * t, axis=1) for m in masks]) for t in range(n_frames)]
+assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal, motion_block=motion_block,
+                     motion_paint=motion_paint,
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
                      extremities=extremities, geodesic_paint=geodesic_paint if extremities else None,
@@ -192,6 +213,14 @@ if temporal:
             raw_sum += ts["raw_changed"]
             out_sum += ts["out_changed"]
     print("flicker over frames %d..%d: %d voxels between raw hulls, %d between voted hulls" % (temporal, n_frames - 1, raw_sum, out_sum))
+if motion_block:
+    for t in range(1, n_frames):
+        pos, col = assignment.set_voxel_positions(g, g // 2, g)
+        mo = assignment.motion()
+        ms, med = mo["stats"], mo["description"]["median_mm"]
+        print("frame %2d: %d of %d blocks listed, %d unique, %d moved, %d at the range; change %d -> %d voxels; median vector "
+              "x %.1f y %.1f z %.1f mm (%.3f ms on the device)" % (t, ms["listed"], ms["blocks"], ms["unique"], ms["moved"], ms["clipped"],
+                                                                   ms["cost0_sum"], ms["cost_sum"], med[0], med[1], med[2], ms["motion_ms"]))
 if subtract or clip:
     for name, st in assignment.hull_ops().items():
         print("%s: %d of %d voxels leave the hull, %d stay (%d in the operand; %.3f ms on the device)" %

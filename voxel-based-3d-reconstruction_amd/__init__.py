@@ -9,7 +9,7 @@ C ABI (include/voxcarve.h) onto hand-written gfx950 HIP kernels.  No PyTorch, no
   voxcarve.assignment              set_voxel_positions(width, height, depth)
   voxcarve.slabs                   z-slab split + survivor all-gather (RCCL over xGMI)
 """
-from . import _lib, camera, clusters, engine, geodesic, hullio, measure, skeleton  # noqa: F401
+from . import _lib, camera, clusters, engine, geodesic, hullio, measure, motion, skeleton  # noqa: F401
 from .camera import Camera, load_cameras, rodrigues  # noqa: F401
 from .engine import CarveEngine, DEFAULT_BOUNDS  # noqa: F401
 

@@ -165,6 +165,7 @@ _operands = False        # hull_subtract / hull_clip are in their registers (new
 _last = {}               # the last frame's results, by stage: what the accessors below hand out
 _carry = {}              # what a frame leaves for the next: the clusters' centres_mm and references, the measure's centroids_mm
 HULL_SUBTRACT_REG, HULL_CLIP_REG = 3, 2      # the registers of CarveEngine that hold the two operands
+MOTION_REG = 1                               # ... and the one that holds the previous frame's hull for the motion stage
 BASE_SETTINGS = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused", "views_threshold": 4,
                  "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS, "footprint": "centre", "normal_radius_mm": None}
 
@@ -216,6 +217,18 @@ def _check_profile(s):
 def _check_anchors(s):
     if s["skeleton_anchors"] not in (None, "extrema"):
         raise ValueError('skeleton_anchors %r, expected None or "extrema"' % (s["skeleton_anchors"],))
+
+
+def _check_motion(s):
+    from . import motion
+    b = s["motion_block"]
+    if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or (b != 0 and b not in motion.BLOCKS):
+        raise ValueError("motion_block %r, expected 0 or one of %s" % (b, motion.BLOCKS))
+    if not isinstance(s["motion_paint"], (bool, np.bool_)):
+        raise ValueError("motion_paint %r, expected True or False" % (s["motion_paint"],))
+    motion.check_params(b if b else motion.BLOCKS[0], s["motion_apron"], s["motion_search"])
+    if s["motion_paint"] and (s["cluster_paint"] or s["geodesic_paint"] is not None):
+        raise ValueError("motion_paint excludes cluster_paint and geodesic_paint: one pass colours the records")
 
 
 def _check_across(s):                                            # (what one stage's settings ask of another's)
@@ -303,6 +316,19 @@ def _run_skeleton(s):
     _last["skeleton"] = {"stats": stats, "skeleton": rows, "description": sk.describe(rows, _engine.grid, _engine.bounds)}
 
 
+def _run_motion(s):
+    """The frame's motion field against the previous frame's hull (see configure); then this frame's hull is kept for the next."""
+    from . import motion
+    if _carry.get("motion_kept"):
+        stats = _engine.hull_motion(MOTION_REG, int(s["motion_block"]), s["motion_apron"], int(s["motion_search"]))
+        rows = _engine.fetch_motion()
+        _last["motion"] = {"stats": stats, "rows": rows, "description": motion.describe(rows, _engine.grid, _engine.bounds)}
+        if s["motion_paint"]:
+            _engine.paint_motion()
+    _engine.keep_hull(MOTION_REG)
+    _carry["motion_kept"] = True
+
+
 def _run_output(s):                                              # (returns what set_voxel_positions returns)
     if s["output"] == "shell":
         _last["shell"] = _engine.hull_shell(int(s["output_level"]))
@@ -345,6 +371,8 @@ STAGES = [
           lambda s: s["measure"] is not None, _run_measure),
     Stage("skeleton", {"skeleton": None, "skeleton_anchors": None}, [_one_of("skeleton", (None, "curve", "point")), _check_anchors],
           lambda s: s["skeleton"] is not None, _run_skeleton),
+    Stage("motion", {"motion_block": 0, "motion_apron": None, "motion_search": 4, "motion_paint": False}, [_check_motion],
+          lambda s: s["motion_block"] > 0, _run_motion),
     Stage("output", {"output": "all", "output_level": 0}, [_one_of("output", ("all", "shell")), _integer("output_level", 6, bools=False)],
           lambda s: True, _run_output),
 ]
@@ -402,7 +430,13 @@ def configure(frame_source=None, **settings):
     topology, on the device; the hull itself stays.  skeleton_anchors = "extrema" pins the skeleton at the floor contact and the
     extremities of extremities=K, which turns a noisy curve skeleton into a stick figure; it is refused without extremities=K.
     skeleton() returns the last frame's.
-    12. output, output_level: "all" (the default) returns every survivor, as the reference does.  "shell" runs
+    12. motion_block, motion_apron, motion_search, motion_paint: when motion_block = b in {4, 8, 16} (0, the default, runs
+    nothing), every frame's hull is kept in register 1 of the engine (CarveEngine.keep_hull), and from the second frame of a
+    session on CarveEngine.hull_motion(1, b, motion_apron, motion_search) estimates, before that, where each block of b^3 voxels
+    went since the previous frame (motion_apron = None is b // 2; b + 2 motion_apron + 2 motion_search <= 64).  motion() returns
+    the last frame's field.  motion_paint=True then paints every voxel by its block's vector (CarveEngine.paint_motion); it
+    excludes cluster_paint and geodesic_paint.  The hull that is matched and kept is the one the stages above leave.
+    13. output, output_level: "all" (the default) returns every survivor, as the reference does.  "shell" runs
     CarveEngine.hull_shell(output_level) and returns the arrays of CarveEngine.fetch_shell_viewer(), made on the device: only the
     voxels with an exposed face, which is everything an opaque cube viewer can show (at level 0 the same rows the full arrays
     hold for those voxels).  output_level = L in 1..6 lists the cells of a grid 2^L times coarser instead, with averaged colours:
@@ -468,6 +502,7 @@ def set_voxel_positions(width, height, depth):
             _engine.build_lut()
         _sized = (H, W)
         _operands = False                                                       # (new cameras empty the registers)
+        _carry.pop("motion_kept", None)                                         # ... the previous frame's hull among them
     if not _operands:
         _upload_operands()
         _operands = True
@@ -505,6 +540,14 @@ def hull_ops():
     """The stats of the last set_voxel_positions call's set operations (configure(hull_subtract=..., hull_clip=...)): a dict
     with "subtract" and / or "clip", each the dict of CarveEngine.combine_hull."""
     return _last_result("hull_ops", "hull operations", "hull_subtract=... or hull_clip=...")
+
+
+def motion():
+    """The motion field of the last set_voxel_positions call's hull against the previous frame's (configure(motion_block=b)):
+    stats, the dict of CarveEngine.hull_motion; rows, the dict of CarveEngine.fetch_motion (block, ijk, d, cost, cost0, count_a,
+    count_b, ties, flags); description, the dict of voxcarve.motion.describe (centre_mm, velocity_mm, speed_mm, median_mm).  The
+    first frame of a session has no previous hull and so no field."""
+    return _last_result("motion", "motion field", "motion_block=b")
 
 
 def skeleton():

@@ -76,6 +76,7 @@ class CarveEngine:
         self._ms_g = 0                       # groups of the last measure_hull()
         self._shell_t = 0                    # cells of the last hull_shell()
         self._thin = (0, 0)                  # records the last thin_hull() started from, and the voxels it kept
+        self._motion = (8, 4, 4)             # block, apron and search of the last hull_motion()
 
     # -- lifetime -----------------------------------------------------------------
     def close(self):
@@ -803,6 +804,50 @@ class CarveEngine:
         replace; a carve of empty masks will do).  Returns combine_hull's stats."""
         self.upload_hull(hull, reg)
         return self.combine_hull("copy", reg)
+
+    # -- block motion between a kept hull and the current result (vc_hull_motion, vc_hull_warp, vc_paint_motion) --------------------
+    def hull_motion(self, reg=0, block=8, apron=None, search=4):
+        """Estimates where each block of `block`^3 voxels went between the hull of register `reg` (the previous frame:
+        keep_hull) and the current carve result: exhaustive matching of a window of the block grown by `apron` cells per side
+        (None: block // 2) over the displacements of [-search, search]^3 (contract: include/voxcarve.h).  block in {4, 8, 16},
+        apron in 0..16, search in 1..8, block + 2 apron + 2 search <= 64.  Changes nothing.  Returns the stats as a dict:
+        blocks, listed, moved, unique, clipped, cost0_sum, cost_sum, a, b, motion_ms."""
+        from . import motion
+        block, apron, search = motion.check_params(block, apron, search)
+        st = motion.MotionStats()
+        self._check(self._L.vc_hull_motion(self._ctx, int(reg), block, apron, search, 0, ctypes.byref(st)), "vc_hull_motion")
+        self._motion = (block, apron, search)
+        return _stats(st)
+
+    def fetch_motion(self):
+        """The field of the last hull_motion as a dict of arrays over the listed blocks, ascending block index: block u32 [L],
+        ijk int64 [L, 3] (the block's position in blocks), d i8 [L, 3] (voxels, x y z), cost, cost0 u32, count_a, count_b,
+        ties u16, flags u8 (bit 0: clipped by the search range); and the scalars grid, edge, apron, search.  Fails once a carve
+        or a pass has changed the hull, or the register has been written."""
+        from . import motion
+        n = ctypes.c_uint64(0)
+        self._check(self._L.vc_fetch_motion(self._ctx, None, ctypes.byref(n)), "vc_fetch_motion")
+        raw = np.zeros(int(n.value), dtype=motion.ROW_DTYPE)
+        if n.value:
+            self._check(self._L.vc_fetch_motion(self._ctx, raw.ctypes.data_as(ctypes.c_void_p), None), "vc_fetch_motion")
+        return motion.rows_dict(raw, self.grid, *getattr(self, "_motion", (8, 4, 4)))
+
+    def warp_hull(self, src=0, dst=1):
+        """Writes to register `dst` the prediction of the current result from the hull of register `src` and the field of the
+        last hull_motion(src): every listed block gathers the old hull's bits by its vector.  Returns a dict: warped, common, a,
+        warp_ms and predicted_iou = common / |P | A| (None when both are empty)."""
+        from . import motion
+        st = motion.WarpStats()
+        self._check(self._L.vc_hull_warp(self._ctx, int(src), int(dst), 0, ctypes.byref(st)), "vc_hull_warp")
+        out = _stats(st)
+        union = out["warped"] + out["a"] - out["common"]
+        out["predicted_iou"] = out["common"] / union if union else None
+        return out
+
+    def paint_motion(self):
+        """Recolours the current result in place by the field of the last hull_motion: channel = 128 + 127 d / search, x -> r,
+        y -> g, z -> b (grey = at rest).  The next carve gives the camera colours again."""
+        self._check(self._L.vc_paint_motion(self._ctx), "vc_paint_motion")
 
     # -- ray-cast images of the current result (vc_render) --------------------------------------------------------------------------
     def render(self, views, H, W, shade=None, background=(0, 0, 0)):
