@@ -3,29 +3,40 @@ every product of a post-carve pass whether it is valid and its bytes.  Every ope
 per-pass tests already hold the device to (oracle.carve_c / carve_np, footprint_np, closing_np, distance_np, components_np,
 visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, temporal_np, measure_np, thin_np, shell_np,
 oracle.marching_np); nothing is restated here.  What this module adds is how the passes COMBINE: which records a pass starts from,
-which frame set it reads, whose labels it takes, what it invalidates, and the one state that outlives a result (the vote's ring).
+which frame set it reads, whose labels it takes, what it invalidates, and the state that outlives a result (the vote's ring, the
+four hull registers).
 
-Two families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
+Three families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
 and does not know them: tests/golden/chain_digests.json holds its records, so that it cannot move.  B (SEEDS_B, CHAIN_LEN_B,
 KINDS_B) draws from every kind, with carve -> temporal pairs on different slots in most chains.  tests/test_gpu_chain.py walks family
 A on the device; family B is held to its coverage conditions, its literal twins and its faults in tests/test_chain_model.py, and
 its walk on the device is not in the suite yet (REFUSAL_B names what its products' fetches are to refuse with there).
+
+Family C (SEEDS_C, CHAIN_LEN_C, KINDS_C) is family A's kinds and the hull registers: keep, upload, release, combine, compare
+(tests/setops_np.py), motion, warp, paint_motion (tests/motion_np.py).  The model holds the four registers -- each None or
+{occ, records or None} -- which outlive carves, passes and results, and the motion field, which is a product of the current result
+AND tied to the register it was made against (item 8 of vc_hull_motion): a write to that register makes it stale and leaves every
+other product.  REFUSAL_C names the two new products, `combined` (the added bytes of vc_hull_combine) and `motion`, and what their
+fetches refuse with; tests/golden/chain_digests_c.json holds the family's record digests; tests/test_gpu_chain.py walks it on
+the device and compares the registers (vc_fetch_kept) after every step as well.
 
 The hull's shell (vc_hull_shell) is no drawn kind: neither family's draws may move.  with_shell(ops, seed) puts `shell` operations
 at fixed places of a chain instead, without a random number; trace, run and replay take shell=True and walk the interleaved chain,
 whose original steps keep their records and their products (tests/test_chain_model.py asserts it).
 
   scene(grid)            one of GRIDS, the golden cameras, three frame sets (slots 0, 1, 2) with different hulls and colours
-  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B) operations with all their parameters, drawn with
-                         numpy.random.default_rng(seed) alone; some draws (min_voxels, the sources of a measurement, anchors) look
-                         at the model's state, so the chain is applied while it is drawn
+  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B, C: CHAIN_LEN_C) operations with all their parameters, drawn
+                         with numpy.random.default_rng(seed) alone; some draws (min_voxels, the sources of a measurement, anchors,
+                         which registers are filled, the hull of an upload) look at the model's state, so the chain is applied while
+                         it is drawn
   Model(scene).apply(op) applies one operation; returns what the call returns and produces (stats, flags, labels, fields, images)
   replay(seed, upto=k)   the model in front of step k of that chain
   trace(seed)            one row per step (what ran, on how many records, whether the hull changed, ...) for the coverage conditions
   with_shell(ops, seed)  (ops with `shell` operations put in, for each the step of `ops` it stands for or None)
 
 A record is uint64: the linear index in the low 32 bits, r, g, b in bytes 4 - 6, `seen` in byte 7.  The product names are those of
-test_gpu_result_generation.REFUSAL / BUILT and, for the three passes that only family B knows and for the shell, of REFUSAL_B."""
+test_gpu_result_generation.REFUSAL / BUILT and, for the three passes that only family B knows and for the shell, of REFUSAL_B; for
+the combine's added bytes and the motion field, of REFUSAL_C."""
 import hashlib
 import os
 import sys
@@ -40,9 +51,11 @@ import fixtures_util as fx
 import footprint_np as fp
 import geodesic_np as gn
 import measure_np as mn
+import motion_np as mo
 import normals_np as nn
 import photo_np as pn
 import render_np as rn
+import setops_np as so
 import shell_np as shn
 import surface_np as sn
 import temporal_np as tpn
@@ -60,6 +73,8 @@ SEEDS = tuple(range(601, 625))              # family A: the 24 chains drawn befo
 CHAIN_LEN = 10
 SEEDS_B = tuple(range(701, 725))            # family B: every kind
 CHAIN_LEN_B = 14
+SEEDS_C = tuple(range(801, 817))            # family C: family A's kinds and the hull registers
+CHAIN_LEN_C = 12
 GRIDS = ((40, 65, 36), (24, 130, 20), (30, 63, 30), (37, 53, 29))
 BOUNDS = carve_np.DEFAULT_BOUNDS
 ROLLS = (0, 9, -13)                         # columns the golden masks are rolled by in slots 0, 1, 2
@@ -70,8 +85,11 @@ COLOUR_CAMERAS = (None, 1, 2)
 # fetches (fetch_temporal; fetch_measure and, after profile=True, fetch_measure_profile; fetch_thin + fetch_skeleton; fetch_shell +
 # fetch_shell_viewer) once the result is another (include/voxcarve.h)
 REFUSAL_B = {"temporal": "no votes", "measure": "no measurements", "skeleton": "no skeleton", "shell": "no shell"}
-PRODUCTS = tuple(REFUSAL) + ("render", "surface") + tuple(REFUSAL_B)
-assert set(PRODUCTS) >= BUILT and not set(REFUSAL_B) & (set(REFUSAL) | BUILT)
+# the products that only family C knows -> the refusal of vc_fetch_combined (its first three words are also vc_fetch_grown's) and of
+# vc_fetch_motion, vc_hull_warp and vc_paint_motion
+REFUSAL_C = {"combined": "no added flags: call vc_hull_combine", "motion": "no motion field"}
+PRODUCTS = tuple(REFUSAL) + ("render", "surface") + tuple(REFUSAL_B) + tuple(REFUSAL_C)
+assert set(PRODUCTS) >= BUILT and not set(REFUSAL_B) & (set(REFUSAL) | BUILT) and not set(REFUSAL_C) & (set(REFUSAL) | BUILT | set(REFUSAL_B))
 
 HULL_CHANGERS = ("close", "dilate", "erode", "open", "filter_components", "photo_carve")
 COMPACTIONS = ("erode", "open", "filter_components", "photo_carve")
@@ -80,7 +98,15 @@ QUIET = ("hull_distance", "hull_normals", "render", "surface_mesh")
 KINDS = ("carve",) + HULL_CHANGERS + ("color_visible", "clusters", "geodesic") + QUIET
 NEW_KINDS = ("temporal", "measure", "thin")
 KINDS_B = KINDS + NEW_KINDS + ("temporal_reset",)
-RECOLOURING = ("color_visible", "clusters", "geodesic")      # change record colours and leave the hull alone
+RECOLOURING = ("color_visible", "clusters", "geodesic", "paint_motion")   # change record colours and leave the hull alone
+REGISTER_KINDS = ("keep", "upload", "release", "combine", "compare", "motion", "warp", "paint_motion")
+KINDS_C = KINDS + REGISTER_KINDS
+REGISTERS = 4                               # VC_HULL_REGISTERS
+REGISTER_WRITERS = ("keep", "upload", "release", "warp")
+MOTION_PARAMS = ((4, 0, 1), (4, 2, 2), (8, 4, 4), (16, 8, 4), (8, 4, 8))     # block edge, apron, search range
+MOTION_ROW_KEYS = ("block", "ijk", "d", "cost", "cost0", "count_a", "count_b", "ties", "flags")
+UPLOAD_SOURCES = ("carve", "eroded", "shifted", "empty", "full")
+FAULTS_C = ("combine_slot0", "copy_keeps_a", "motion_survives_keep", "register_dies_with_carve", "noop_combine_invalidates")
 MEASURE_SOURCES = ("all", "clusters", "geodesic", "components", "host")
 
 LOW = np.uint64(0xffffffff)
@@ -129,6 +155,7 @@ class Scene:
         self.q = dn.steps_um(self.grid, self.bounds)
         self.views = _views(self)
         self._carves = {}
+        self._matches = {}
 
     def mm(self, factor):
         """A radius in mm: `factor` times the grid's largest step; "below" is half the smallest one."""
@@ -158,6 +185,17 @@ class Scene:
             self._carves[key] = rec
         return self._carves[key]
 
+    def match(self, a, b_occ, b, ap, s, literal=False):
+        """motion_np.match of two hulls of this grid (cached: the block matching is the dearest restatement of family C, and a chain
+        is applied once while it is drawn and once more by whoever walks it)."""
+        key = (hashlib.sha1(np.packbits(a)).digest(), hashlib.sha1(np.packbits(b_occ)).digest(), b, ap, s, bool(literal))
+        if key not in self._matches:
+            rows = (mo.match_literal if literal else mo.match)(a, b_occ, self.grid, b, ap, s)
+            for v in rows.values():
+                v.setflags(write=False)
+            self._matches[key] = rows
+        return self._matches[key]
+
 
 _SCENES = {}
 
@@ -176,7 +214,11 @@ class Model:
     records that a compaction keeps the colours of the carve again, "temporal_forgets_prev" empties the vote's previous output
     at every carve (no hysteresis across frames), "measure_carve_colours" sums the colours the carve gave the records instead of
     the ones they have at the call, "shell_repainted" lets a valid shell take the new colours when a pass repaints the records
-    (item 5 of vc_hull_shell: it holds the colours the records had at the call)."""
+    (item 5 of vc_hull_shell: it holds the colours the records had at the call).  Family C's (FAULTS_C): "combine_slot0" colours
+    the fresh records of a combine from slot 0, "copy_keeps_a" lets a restore keep A's bytes on the voxels both hulls hold (item 4
+    of vc_hull_combine: every record is B's), "motion_survives_keep" leaves the motion field valid when its register is written
+    (item 8 of vc_hull_motion), "register_dies_with_carve" empties the registers at every carve (they survive carves, passes
+    and results), "noop_combine_invalidates" drops every product at a combine with R = A (item 5 of vc_hull_combine)."""
 
     def __init__(self, sc, fault=None, literal=False):
         self.scene = sc
@@ -194,6 +236,10 @@ class Model:
         #                                      "clusters" (u8 labels, K), "geodesic" (u8 labels, extremities, distances),
         #                                      "component_labels" (the dict of components_np)
         self.shell_level = 0                 # the level of the last shell
+        self.registers = [None] * REGISTERS  # each None or {"occ": bool [nz, nx, ny], "records": uint64 [count] or None, "origin":
+        #                                      what wrote it, for the traces}: they outlive carves, passes and results
+        self.field = None                    # the last motion field: rows, b, a, s and the register it was made against; it is
+        #                                      current while "motion" is among the products
 
     # what the result is
     @property
@@ -249,6 +295,8 @@ class Model:
         self._changed()
         if self.fault == "temporal_forgets_prev":
             self.vote.prev = None
+        if self.fault == "register_dies_with_carve":
+            self.registers = [None] * REGISTERS
         out["count"] = int(rec.size)
         return out
 
@@ -471,6 +519,115 @@ class Model:
         self.products["shell"] = self._shell_product(w)
         return {"stats": w["stats"], "shell": w}
 
+    # the hull registers: they are the model's, not the result's.  The motion field is a product of the result that is tied to one
+    # of them as well (item 8 of vc_hull_motion).
+    def _written(self, reg, hull):
+        self.registers[reg] = hull
+        if self.field is not None and self.field["reg"] == reg and self.fault != "motion_survives_keep":
+            self.products.pop("motion", None)
+
+    def filled(self, records=None):
+        """The registers that hold a hull (records=True / False: with / without records)."""
+        return [r for r, k in enumerate(self.registers) if k is not None and (records is None or (k["records"] is not None) == records)]
+
+    def motion_valid(self, reg=None):
+        return "motion" in self.products and (reg is None or self.field["reg"] == reg)
+
+    def _keep(self, op):
+        self._written(op["reg"], {"occ": self.occ(), "records": self.records.copy(),
+                                  "origin": {"how": "keep", "slot": self.carve["slot"], "painted": self.painted}})
+        return {}
+
+    def upload_hull(self, op):
+        """(occ, records) of an upload's hull, from what the model holds: the carve of another frame set, the current hull eroded by
+        one step (with the colours its records have now) or moved by a small vector, the empty hull or the full grid.  Where no
+        carve gives the colours they are made from the index, so that no two records of a register look alike."""
+        sc, src = self.scene, op["source"]
+        if src == "carve":
+            rec = sc.carve_records(op["slot"], op["min_views"], op["color_cam"])
+            return dn.volume(index_of(rec), self.grid), rec.copy()
+        if src == "eroded":
+            occ = dn.erode(self.occ(), sc.q, dn.radius_r2(sc.mm(1)))
+            return occ, self.records[occ.reshape(-1)[self.idx]]
+        if src == "shifted":
+            occ = mo.shifted(self.occ(), op["shift"])
+        else:
+            occ = (np.zeros if src == "empty" else np.ones)(self.occ().shape, dtype=bool)
+        i = dn.indices(occ).astype(np.uint64)
+        return occ, pack(i, np.stack([i & np.uint64(255), (i >> np.uint64(8)) & np.uint64(255), (i * np.uint64(7)) & np.uint64(255)], axis=1),
+                         np.ones(i.size))
+
+    def _upload(self, op):
+        occ, rec = self.upload_hull(op)
+        self._written(op["reg"], {"occ": occ, "records": rec if op["form"] == "records" else None,
+                                  "origin": {"how": "upload", "slot": op.get("slot"), "painted": False}})
+        return {"occ": occ, "records": rec}
+
+    def _release(self, op):
+        self._written(op["reg"], None)
+        return {}
+
+    def _combine(self, op):
+        sc = self.scene
+        B = self.registers[op["reg"]]
+        cc = self.carve["color_cam"]             # fresh records: the carve's own frame set and colour camera (items 3 of
+        slot = 0 if self.fault == "combine_slot0" else self.carve["slot"]    # vc_hull_combine and of vc_hull_grow)
+        a, rec_a = self.occ(), self.records
+        rec, added, r, st = so.combine(rec_a, a, B["occ"], B["records"], op["setop"], self.grid, self.bounds, None if cc is None else sc.oc[cc],
+                                       None if cc is None else sc.frames[slot][cc], sc.H, sc.W)
+        restore = op["setop"] == "copy" and B["records"] is not None
+        if self.fault == "copy_keeps_a" and restore:
+            rec[added == 0] = rec_a[r.reshape(-1)[self.idx]]
+        changed = bool(st["added"] or st["removed"] or restore)   # a restore always counts as another result (item 5)
+        if changed or self.fault == "noop_combine_invalidates":
+            self.records = rec
+            self._changed({"combined": added.tobytes()})
+        else:                                    # R = A: nothing is invalidated, the result generation stays
+            assert np.array_equal(rec, self.records) and not added.any()
+            self.products["combined"] = added.tobytes()
+        return {"stats": st, "added": added, "changed": changed, "restore": restore, "fresh": int(st["added"]) if B["records"] is None else 0,
+                "bytes_changed": bool(rec.size == rec_a.size and not np.array_equal(rec, rec_a))}
+
+    def _compare(self, op):
+        B = self.registers[op["reg"]]
+        st = so.compare(self.occ(), B["occ"], self.scene.q if op["distance"] else None)
+        return {"stats": st, "derived": so.derived(st)}
+
+    @staticmethod
+    def motion_bytes(rows, b, a, s):
+        return b"".join(np.ascontiguousarray(rows[k]).tobytes() for k in MOTION_ROW_KEYS) + np.array([b, a, s], dtype=np.uint32).tobytes()
+
+    def _motion(self, op):
+        B = self.registers[op["reg"]]
+        b, ap, s = op["block"], op["apron"], op["search"]
+        a = self.occ()
+        rows = self.scene.match(a, B["occ"], b, ap, s, self.literal)
+        self.field = {"rows": rows, "b": b, "a": ap, "s": s, "reg": op["reg"]}
+        self.products["motion"] = self.motion_bytes(rows, b, ap, s)
+        return {"stats": mo.stats(rows, a, B["occ"], self.grid, b), "rows": rows}
+
+    def _warp(self, op):
+        f = self.field
+        assert self.motion_valid(op["src"]) and op["dst"] != op["src"]
+        a = self.occ()
+        P, st = mo.warp(f["rows"], a, self.registers[op["src"]]["occ"], self.grid, f["b"])
+        self._written(op["dst"], {"occ": P, "records": None, "origin": {"how": "warp", "slot": None, "painted": False}})
+        return {"stats": st, "predicted_iou": mo.iou(a, P), "P": P}
+
+    def _paint_motion(self, op):
+        f = self.field
+        assert self.motion_valid()
+        self.records = mo.paint(self.records, f["rows"], self.grid, f["b"], f["s"])
+        self.painted = True
+        return {}
+
+    def registers_digest(self):
+        """sha1 over the four registers: empty, or the hull's words and its records."""
+        h = hashlib.sha1()
+        for k in self.registers:
+            h.update(b"-" if k is None else b"+" + mo.words(k["occ"]).tobytes() + (b"-" if k["records"] is None else b"+" + k["records"].tobytes()))
+        return h.hexdigest()
+
     # what the end of a chain compares on the final hull
     def marching_cubes(self):
         """marching_cubes(volume=None): the occupancy in the reference's reshape, (nx, ny, nz) over the voxel order."""
@@ -500,10 +657,18 @@ def _palette(rng, rows):
     return rng.integers(0, 256, (rows, 3), dtype=np.uint8)
 
 
-def _draw(rng, sc, model, kind):
+def _draw(rng, sc, model, kind, hint=None):
+    """hint (family C alone): parameters that the chain's shape fixes -- a register, a set operation, a slot to stay away from."""
     pick = lambda seq, p=None: seq[int(rng.choice(len(seq), p=p))]
+    hint = hint or {}
     if kind == "carve":
-        return _draw_carve(rng, sc)
+        op = _draw_carve(rng, sc)
+        if hint.get("not_slot") == op["slot"]:   # (family C's "previous frame" pattern: the next carve is of another frame set)
+            by = 1 + int(rng.integers(2))
+            op["slot"] = (op["slot"] + by) % 3
+            if op["first"] is not None:
+                op["first"]["slot"] = (op["first"]["slot"] + by) % 3
+        return op
     if kind in ("close", "dilate"):
         return {"op": kind, "radius_mm": sc.mm(pick(("below", 1, 1.5, 2, 3), (0.12, 0.3, 0.25, 0.2, 0.13)))}
     if kind == "erode":
@@ -564,6 +729,39 @@ def _draw(rng, sc, model, kind):
             a = model.idx[rng.integers(0, model.S, int(rng.integers(1, 7)))].astype(np.uint32)
             op["anchors"] = np.concatenate([a, a[:1]])
         return op
+    # family C
+    if kind in ("keep", "upload"):               # mostly into an empty register; now and then over a filled one
+        free = [r for r in range(REGISTERS) if model.registers[r] is None]
+        reg = hint["reg"] if "reg" in hint else pick(free) if free and rng.random() < 0.7 else int(rng.integers(REGISTERS))
+        if kind == "keep":
+            return {"op": kind, "reg": reg}
+        op = {"op": kind, "reg": reg, "form": pick(("bits", "records"), (0.6, 0.4)), "source": pick(UPLOAD_SOURCES, (0.35, 0.15, 0.25, 0.1, 0.15))}
+        if op["source"] == "carve":              # the hull of another frame set than the current result's
+            op.update(slot=(model.carve["slot"] + 1 + int(rng.integers(2))) % 3, min_views=sc.C - int(rng.integers(2)),
+                      color_cam=COLOUR_CAMERAS[int(rng.integers(3))])
+        if op["source"] == "shifted":
+            op["shift"] = tuple(int(v) for v in rng.integers(-3, 4, 3))
+        return op
+    if kind == "release":
+        filled = model.filled()
+        return {"op": kind, "reg": hint["reg"] if "reg" in hint else pick(filled) if filled and rng.random() < 0.8 else int(rng.integers(REGISTERS))}
+    if kind in ("combine", "compare", "motion"):     # only on a filled register: the header refuses an empty one
+        reg = hint.get("reg")
+        if reg is None or model.registers[reg] is None:
+            reg = pick(model.filled())
+        op = {"op": kind, "reg": reg}
+        if kind == "combine":
+            op["setop"] = hint["setop"] if "setop" in hint else pick(so.OPS)
+        elif kind == "compare":
+            op["distance"] = hint["distance"] if "distance" in hint else bool(rng.integers(2))
+        else:
+            op["block"], op["apron"], op["search"] = pick(MOTION_PARAMS, (0.25, 0.25, 0.25, 0.12, 0.13))
+        return op
+    if kind == "warp":
+        src = model.field["reg"]
+        return {"op": kind, "src": src, "dst": pick([r for r in range(REGISTERS) if r != src])}
+    if kind == "paint_motion":
+        return {"op": kind}
     raise ValueError(kind)
 
 
@@ -588,14 +786,14 @@ _CHAINS = {}
 
 
 def family(seed):
-    return "B" if seed in SEEDS_B else "A"
+    return "B" if seed in SEEDS_B else "C" if seed in SEEDS_C else "A"
 
 
 def draw_chain(seed):
     """(scene, ops) of chain `seed`.  Family A: a carve, then CHAIN_LEN - 1 drawn operations; now and then a burst of hull-changing
-    passes.  Family B: see _draw_chain_b."""
+    passes.  Family B: see _draw_chain_b.  Family C: see _draw_chain_c."""
     if seed not in _CHAINS:
-        _CHAINS[seed] = (_draw_chain_b if family(seed) == "B" else _draw_chain)(seed)
+        _CHAINS[seed] = {"A": _draw_chain, "B": _draw_chain_b, "C": _draw_chain_c}[family(seed)](seed)
     return _CHAINS[seed]
 
 
@@ -671,6 +869,89 @@ def _draw_chain_b(seed):
             queue = ["measure" if kind == "clusters" or rng.random() < 0.4 else "thin"]
         if kind == "temporal_reset" and not queue and len(model.products) >= 2 and rng.random() < 0.8:
             queue = ["temporal"]                 # the first vote after a reset changes nothing: every product must stay
+        model.apply(op)
+        ops.append(op)
+    return sc, ops
+
+
+_WEIGHTS_C = {"carve": 0.9, "close": 0.4, "dilate": 0.4, "erode": 0.4, "open": 0.4, "filter_components": 0.5, "photo_carve": 0.4,
+              "color_visible": 0.6, "clusters": 0.5, "geodesic": 0.4, "hull_distance": 1.0, "hull_normals": 0.3, "render": 0.2,
+              "surface_mesh": 0.2, "keep": 0.8, "upload": 2.4, "release": 0.4, "combine": 3.2, "compare": 1.0, "motion": 1.6,
+              "warp": 0.7, "paint_motion": 0.3}
+assert set(_WEIGHTS_C) == set(KINDS_C) and not set(KINDS_C) & set(NEW_KINDS + ("temporal_reset", "shell"))
+
+
+def _draw_chain_c(seed):
+    """A carve, then CHAIN_LEN_C - 1 operations drawn from family A's kinds and the eight of the hull registers.  A combine, a
+    comparison or a motion estimate drawn while every register is empty becomes the keep that it needs, with itself behind it; a
+    warp or a paint drawn without a current field becomes the motion estimate (item 8 of vc_hull_combine, the refusals of
+    vc_hull_warp).  Behind the draw, the pairs that matter are queued more often than chance would give them:
+      carve -> keep -> carve of another slot [-> motion | hull changer -> combine or compare], the "previous frame" pattern;
+      keep -> two quiet passes -> "and" / "or" with the kept hull (R = A with products to lose), or keep -> a colour pass -> "copy"
+      (a restore whose sets are equal and whose bytes are not);
+      motion -> warp | paint_motion | a colour pass | a hull changer | a write to its register (behind a quiet pass, so that
+      another product is there to stay) | a write to another register;
+      warp -> compare or combine with its target;  upload -> combine with it (bits: an operation that makes fresh records);
+      hull_distance -> compare with distances."""
+    rng = np.random.default_rng(seed)
+    sc = scene(GRIDS[int(rng.integers(len(GRIDS)))])
+    model = Model(sc)
+    kinds = list(_WEIGHTS_C)
+    p = np.array([_WEIGHTS_C[k] for k in kinds])
+    p /= p.sum()
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]
+    ops, queue = [], []
+    while len(ops) < CHAIN_LEN_C:
+        hint = None
+        if not ops:
+            kind = "carve"
+        elif model.S == 0 and rng.random() < 0.5:
+            kind, queue = "carve", []
+        elif queue:
+            kind, hint = queue.pop(0)
+        else:
+            kind = kinds[int(rng.choice(len(kinds), p=p))]
+        if kind in ("combine", "compare", "motion") and not model.filled():
+            queue.insert(0, (kind, None))
+            kind, hint = "keep", None
+        if kind in ("warp", "paint_motion") and not model.motion_valid():
+            queue.insert(0, (kind, None))
+            kind, hint = ("motion" if model.filled() else "keep"), None
+        op = _draw(rng, sc, model, kind, hint)
+        if not queue:
+            r = rng.random()
+            if kind == "carve" and hint is None and r < 0.45:
+                reg = {"reg": int(rng.integers(REGISTERS))}
+                other = ("carve", {"not_slot": op["slot"]})
+                r = rng.random()
+                if r < 0.3:
+                    queue = [("keep", reg), other, ("motion", reg)]
+                elif r < 0.5:
+                    queue = [("keep", reg), other] + [(pick(HULL_CHANGERS), None)] * (1 + int(rng.integers(2))) + [(pick(("combine", "compare")), reg)]
+                elif r < 0.65:
+                    queue = [("keep", reg), (pick(QUIET), None), (pick(QUIET), None), ("combine", dict(reg, setop=pick(("and", "or"))))]
+                elif r < 0.9:
+                    queue = [("keep", reg), (pick(("color_visible", "clusters", "geodesic")), None), ("combine", dict(reg, setop="copy"))]
+                else:
+                    queue = [("keep", reg), other]
+            elif kind == "keep" and r < 0.55:
+                reg = {"reg": op["reg"]}
+                if r < 0.3:
+                    queue = [(pick(QUIET), None), (pick(QUIET), None), ("combine", dict(reg, setop=pick(("and", "or"))))]
+                else:
+                    queue = [(pick(("color_visible", "clusters", "geodesic")), None), ("combine", dict(reg, setop="copy"))]
+            elif kind == "motion" and r < 0.85:
+                own, others = {"reg": op["reg"]}, [q for q in range(REGISTERS) if q != op["reg"]]
+                writer = pick(("keep", "upload", "release"))
+                queue = [[("warp", None)], [(pick(QUIET), None), (writer, own)], [("paint_motion", None)], [("color_visible", None)],
+                         [(pick(HULL_CHANGERS), None)], [(pick(QUIET), None), (writer, own)], [(writer, own)],
+                         [(writer, {"reg": pick(others)}), ("paint_motion", None)]][int(rng.integers(8))]
+            elif kind == "warp" and r < 0.9:             # (its target has no records: "or" and "xor" make fresh ones)
+                queue = [("compare", {"reg": op["dst"]}) if r < 0.25 else ("combine", {"reg": op["dst"], "setop": pick(("or", "xor", "and"))})]
+            elif kind == "upload" and r < 0.85:
+                queue = [("combine", {"reg": op["reg"], "setop": pick(("or", "xor", "copy"))} if op["form"] == "bits" else {"reg": op["reg"]})]
+            elif kind == "hull_distance" and model.filled() and r < 0.7:
+                queue = [("compare", {"reg": pick(model.filled()), "distance": True})]
         model.apply(op)
         ops.append(op)
     return sc, ops
@@ -762,14 +1043,30 @@ def trace(seed, fault=None, shell=False):
     sc, ops, origin = walk_of(seed, shell)
     model = Model(sc, fault)
     carve_op = made_by = None
+    since = [None] * REGISTERS                   # per register, since it was written: the slot then, carves of other slots, hull changes
     for step, op in enumerate(ops):
         before = None if model.records is None else model.records
         carve_slot = None if model.carve is None else model.carve["slot"]
         row = {"step": step, "op": op["op"], "before": 0 if before is None else int(before.size),
                "seen0": bool(before is not None and before.size and (seen_of(before) == 0).any()),
                "painted": bool(model.painted and before is not None and before.size), "carve_slot": carve_slot, "params": op,
-               "carve_op": carve_op, "made_by": made_by, "valid_before": dict(model.products)}
+               "carve_op": carve_op, "made_by": made_by, "valid_before": dict(model.products),
+               "registers_before": [None if k is None else {"count": int(k["occ"].sum()), "has_records": k["records"] is not None,
+                                                            "origin": k["origin"], "since": dict(since[r])}
+                                    for r, k in enumerate(model.registers)],
+               "motion_reg_before": model.field["reg"] if model.motion_valid() else None}
         out = model.apply(op)
+        row["registers_digest"] = model.registers_digest()
+        row["motion_reg"] = model.field["reg"] if model.motion_valid() else None
+        for k in ("restore", "fresh", "bytes_changed"):
+            if k in out:
+                row[k] = out[k]
+        if op["op"] in REGISTER_WRITERS:
+            since[op["dst" if op["op"] == "warp" else "reg"]] = {"slot": carve_slot, "other_carves": 0, "hull_changes": 0}
+        for s in since:
+            if s is not None:
+                s["other_carves"] += op["op"] == "carve" and op["slot"] != s["slot"]
+                s["hull_changes"] += op["op"] != "carve" and bool(out.get("changed", False))
         row["after"] = model.S
         row["digest"] = hashlib.sha1(model.records.tobytes()).hexdigest()
         row["products_digest"] = products_digest(model)

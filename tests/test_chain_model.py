@@ -7,6 +7,9 @@ measurements and the skeleton).  Family A is held to the record digests it had b
 is checked here alone so far, and every condition below is written so that its walk on the device can be added without another draw.
 The hull's shell is put into family B's chains at fixed places (chain_model.with_shell), not drawn: the original steps keep their
 records and products, and the shell has coverage conditions, a literal twin and a fault of its own.
+Family C (chain_model.SEEDS_C) is family A's kinds and the hull registers: keep, upload, release, combine, compare, motion, warp and
+paint_motion.  tests/test_gpu_chain.py walks it on the device; here it has its coverage conditions, its five faults, the literal
+twins of the set algebra and of the block matching, and its own golden digests (tests/golden/chain_digests_c.json).
 
 The coverage conditions below are conditions on the INPUTS of the GPU test (the seeds, the draw weights, the lengths), asserted here
 so that it cannot pass by doing nothing; where one fails, the seeds, the weights or the length change, never the thresholds.  Then:
@@ -47,12 +50,22 @@ def traces_s():
     return {seed: cm.trace(seed, shell=True) for seed in cm.SEEDS_B}
 
 
+@pytest.fixture(scope="module")
+def traces_c():
+    return {seed: cm.trace(seed) for seed in cm.SEEDS_C}
+
+
 def test_seed_list():
     assert len(cm.SEEDS) == len(set(cm.SEEDS)) == 24 and cm.CHAIN_LEN == 10
     assert 0 < len(cm.SEEDS_B) == len(set(cm.SEEDS_B)) <= 24 and cm.CHAIN_LEN_B <= 14 and not set(cm.SEEDS) & set(cm.SEEDS_B)
-    assert [cm.family(s) for s in (cm.SEEDS[0], cm.SEEDS_B[0])] == ["A", "B"]
+    assert cm.SEEDS_C == tuple(range(801, 817)) and cm.CHAIN_LEN_C == 12 and not set(cm.SEEDS_C) & (set(cm.SEEDS) | set(cm.SEEDS_B))
+    assert [cm.family(s) for s in (cm.SEEDS[0], cm.SEEDS_B[0], cm.SEEDS_C[0])] == ["A", "B", "C"]
     assert set(cm.KINDS_B) > set(cm.KINDS) and set(cm.NEW_KINDS) <= set(cm.KINDS_B) - set(cm.KINDS)
-    assert set(cm.PRODUCTS) == set(cm.REFUSAL) | cm.BUILT | set(cm.REFUSAL_B)   # (the product names of test_gpu_result_generation, imported, and family B's)
+    assert set(cm.KINDS_C) - set(cm.KINDS) == set(cm.REGISTER_KINDS) and len(cm.REGISTER_KINDS) == 8
+    assert not set(cm.KINDS_C) & set(cm.NEW_KINDS + ("temporal_reset", "shell"))
+    # (the product names of test_gpu_result_generation, imported, family B's and family C's)
+    assert set(cm.PRODUCTS) == set(cm.REFUSAL) | cm.BUILT | set(cm.REFUSAL_B) | set(cm.REFUSAL_C)
+    assert not cm.REFUSAL["grown"].startswith(cm.REFUSAL_C["combined"]) and cm.REFUSAL_C["combined"].startswith(cm.REFUSAL["grown"])
 
 
 def test_the_three_frame_sets_differ():
@@ -442,3 +455,205 @@ def test_a_wrong_model_is_told_apart(traces, traces_b, traces_s, fault, fam):
             break
     print("%s told apart in family %s at (seed, step, op):" % (fault, fam), told)
     assert told, "no chain of family %s tells the %s model from the right one" % (fam, fault)
+
+
+# ---- family C: the hull registers and the motion field ------------------------------------------------------------------------------
+READERS = ("combine", "compare", "motion")
+
+
+def _target(r):
+    """The register that a row's operation writes, or None."""
+    if r["op"] not in cm.REGISTER_WRITERS:
+        return None
+    return r["params"]["dst" if r["op"] == "warp" else "reg"]
+
+
+def test_coverage_of_family_c(traces_c):
+    """What the 16 chains of family C exercise of the registers, the set algebra and the motion field; and, on every row, what the
+    model's own rules say must hold whatever was drawn."""
+    n = collections.Counter()
+    ran = collections.Counter()
+    setops = collections.Counter()
+    params = collections.Counter()
+    for seed, rows in traces_c.items():
+        assert len(rows) == cm.CHAIN_LEN_C and rows[0]["op"] == "carve"
+        assert all(r["op"] in cm.KINDS_C for r in rows)
+        for k, r in enumerate(rows):
+            op, p, st, regs = r["op"], r["params"], r["stats"], r["registers_before"]
+            had, has = r["valid_before"], r["valid"]
+            ran[op] += 1
+            field, field_after = r["motion_reg_before"], r["motion_reg"]
+            n["through the empty hull"] += op != "carve" and r["before"] > 0 and r["after"] == 0 and k + 1 < len(rows)
+            if op in READERS or op == "warp":
+                reg = p["src" if op == "warp" else "reg"]
+                assert regs[reg] is not None, (seed, k, "a read of an empty register")
+                n["read a register with records"] += regs[reg]["has_records"]
+                n["read a register without records"] += not regs[reg]["has_records"]
+                n["read after a carve of another slot and a hull change"] += regs[reg]["since"]["other_carves"] >= 1 and regs[reg]["since"]["hull_changes"] >= 1
+            if op in ("compare", "motion", "keep", "upload", "release", "warp"):        # they change nothing of the result
+                assert r["digest"] == rows[k - 1]["digest"] and not r["changed"]
+                assert {x: v for x, v in has.items() if x != "motion"} == {x: v for x, v in had.items() if x != "motion"}
+            if op == "combine":
+                setops[p["setop"]] += 1
+                others = {x: v for x, v in had.items() if x != "combined"}
+                if not r["changed"]:
+                    assert st["added"] == st["removed"] == 0 and r["digest"] == rows[k - 1]["digest"]
+                    assert {x: v for x, v in has.items() if x != "combined"} == others and has["combined"] == bytes(r["after"])
+                    n["R = A with two other products valid"] += len(others) >= 2
+                    n["R = A, the distance field stays"] += "distance" in others   # (unlike a grow that adds nothing: item 5 of vc_hull_combine)
+                else:
+                    assert set(has) == {"combined"}
+                n["restore, equal sets, other bytes"] += r["restore"] and st["added"] == st["removed"] == 0 and r["bytes_changed"]
+                n["fresh records, slot 1 or 2, a colour camera"] += r["fresh"] > 0 and r["carve_slot"] in (1, 2) and r["carve_op"]["color_cam"] is not None
+                n["fresh records, no colour camera"] += r["fresh"] > 0 and r["carve_op"]["color_cam"] is None
+                n["combine behind a footprint carve"] += r["carve_op"]["footprint"] != "centre"
+                n["combine behind a pipelined carve"] += r["carve_op"]["first"] is not None
+                n["combine three hull changes deep"] += sum(q["changed"] for q in rows[max(k - 3, 0):k]) >= 2 and r["changed"]
+            elif op == "compare":
+                n["compare with distances, distance valid"] += p["distance"] and "distance" in had
+                assert has == had
+            elif op == "motion":
+                params[(p["block"], p["apron"], p["search"])] += 1
+                origin = regs[p["reg"]]["origin"]
+                n["motion between two slots, moved > 0"] += origin["how"] == "keep" and origin["slot"] != r["carve_slot"] and st["moved"] > 0
+                assert field_after == p["reg"]
+            elif op == "upload":
+                n["upload " + p["form"]] += 1
+            elif op == "release":
+                n["release of a filled register"] += regs[p["reg"]] is not None
+                n["release of an empty register"] += regs[p["reg"]] is None
+            elif op == "warp":
+                nxt = rows[k + 1] if k + 1 < len(rows) else None
+                n["warp, then compare or combine with dst"] += nxt is not None and nxt["op"] in ("compare", "combine") and nxt["params"]["reg"] == p["dst"]
+                assert field_after == field == p["src"]
+            target = _target(r)
+            if target is not None:
+                n["an overwritten register"] += op != "release" and regs[target] is not None
+            if field is not None and op != "motion":
+                if r["changed"] or op == "carve" or op in cm.COMPACTIONS:     # (a compaction that removes nothing is another result too)
+                    assert field_after is None, (seed, k, "a field that outlives its result")
+                    n["field stale after a hull changer"] += r["changed"]
+                elif target == field:
+                    assert field_after is None and "motion" not in has, (seed, k, "a field that outlives its register")
+                    n["field stale after a write to its register, another product stays"] += len(has) >= 1
+                else:
+                    assert field_after == field and has["motion"] == had["motion"], (seed, k, "a field lost to " + op)
+                    n["field valid after a colour pass"] += op in cm.RECOLOURING
+                    n["field valid after a write to another register"] += target is not None
+    print("family C, operations:", {k: ran[k] for k in cm.KINDS_C})
+    print("family C, set operations:", dict(setops), "motion parameters:", dict(params))
+    print("family C:", dict(n))
+    assert all(ran[k] >= 1 for k in cm.REGISTER_KINDS), dict(ran)
+    assert all(setops[k] >= 1 for k in cm.so.OPS), dict(setops)
+    for name in ("read a register with records", "read a register without records", "R = A with two other products valid",
+                 "R = A, the distance field stays",
+                 "restore, equal sets, other bytes", "fresh records, slot 1 or 2, a colour camera", "fresh records, no colour camera",
+                 "combine behind a footprint carve", "combine behind a pipelined carve", "combine three hull changes deep",
+                 "read after a carve of another slot and a hull change", "release of a filled register", "upload bits", "upload records",
+                 "an overwritten register", "motion between two slots, moved > 0", "field valid after a colour pass",
+                 "field stale after a hull changer", "field stale after a write to its register, another product stays",
+                 "field valid after a write to another register", "warp, then compare or combine with dst",
+                 "compare with distances, distance valid", "through the empty hull"):
+        assert n[name] >= 1, name
+
+
+def test_family_c_is_held_to_its_digests(traces_c):
+    """The records behind every step of family C, and a second draw of it: the same operations, the same digests."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "chain_digests_c.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(str(s) for s in cm.SEEDS_C)
+    for seed in cm.SEEDS_C:
+        assert [r["digest"] for r in traces_c[seed]] == want[str(seed)], seed
+    for seed in cm.SEEDS_C[:3]:
+        sc, ops = cm.draw_chain(seed)
+        sc2, ops2 = cm._draw_chain_c(seed)                       # (drawn again, past the cache)
+        assert sc2 is sc and [cm.describe_op(o) for o in ops2] == [cm.describe_op(o) for o in ops]
+        assert all(np.array_equal(a.get("palette"), b.get("palette")) for a, b in zip(ops, ops2))
+        again = cm.trace(seed)
+        for a, b in zip(again, traces_c[seed]):
+            assert (a["digest"], a["products_digest"], a["registers_digest"]) == (b["digest"], b["products_digest"], b["registers_digest"])
+        for upto in (1, 5, 9, cm.CHAIN_LEN_C):
+            m = cm.replay(seed, upto=upto)
+            row = traces_c[seed][upto - 1]
+            assert cm.hashlib.sha1(m.records.tobytes()).hexdigest() == row["digest"] and m.registers_digest() == row["registers_digest"]
+            assert cm.products_digest(m) == row["products_digest"] and m.products == row["valid"], (seed, upto)
+
+
+@pytest.mark.parametrize("fault", cm.FAULTS_C)
+def test_a_wrong_model_of_the_registers_is_told_apart(traces_c, fault):
+    """Each of family C's deliberate mistakes changes a byte that the walk on the device compares -- the records, a product or its
+    validity, a register -- in at least one chain."""
+    told = []
+    for seed in traces_c:
+        for step, op, out, model in cm.run(seed, fault):
+            row = traces_c[seed][step]
+            if cm.hashlib.sha1(model.records.tobytes()).hexdigest() != row["digest"] or cm.products_digest(model) != row["products_digest"] or \
+                    model.registers_digest() != row["registers_digest"]:
+                told.append((seed, step, op["op"]))
+                break
+        if len(told) >= 3:
+            break
+    print("%s told apart in family C at (seed, step, op):" % fault, told)
+    assert told, "no chain of family C tells the %s model from the right one" % fault
+
+
+def _states_c(traces_c, kind, count, where=lambda r: True):
+    """(seed, step) of the `count` runs of `kind` on the fewest records among family C's chains, one per seed."""
+    found = sorted((r["before"], seed, r["step"]) for seed, rows in traces_c.items() for r in rows if r["op"] == kind and where(r))
+    out, seen = [], set()
+    for _, seed, step in found:
+        if seed not in seen:
+            seen.add(seed)
+            out.append((seed, step))
+    assert len(out) >= count, (kind, out)
+    return out[:count]
+
+
+def _window(m, reg, half):
+    """The current hull and the register's, cut to a box of 2 half cells around the centre of mass of their union."""
+    a, b = m.occ(), m.registers[reg]["occ"]
+    c = [int(round(v)) for v in np.argwhere(a | b).mean(axis=0)]
+    sl = tuple(slice(max(c[k] - half[k], 0), c[k] + half[k]) for k in range(3))
+    return np.ascontiguousarray(a[sl]), np.ascontiguousarray(b[sl])
+
+
+def test_literal_twins_of_the_set_algebra(traces_c):
+    """setops_np.combine_literal on three seeds, whole grids: records, added bytes and R of the model's combine at the state the
+    chain reaches; setops_np.compare_literal, which holds every voxel of a difference against every voxel of the other hull, on a
+    window of three such states."""
+    for seed, step in _states_c(traces_c, "combine", 3, where=lambda r: r["before"] > 0):
+        m = cm.replay(seed, upto=step)
+        op = cm.draw_chain(seed)[1][step]
+        B, sc, cc = m.registers[op["reg"]], m.scene, m.carve["color_cam"]
+        cam, frame = (None, None) if cc is None else (sc.oc[cc], sc.frames[m.carve["slot"]][cc])
+        rec, added, r = cm.so.combine_literal(m.records, m.occ(), B["occ"], B["records"], op["setop"], m.grid, m.bounds, cam, frame, sc.H, sc.W)
+        a = m.occ()
+        out = m.apply(op)
+        assert np.array_equal(rec, m.records) and np.array_equal(added, out["added"]), (seed, step, cm.describe_op(op))
+        assert np.array_equal(r, m.occ()) and np.array_equal(r, cm.so.combine_sets_literal(a, B["occ"], op["setop"]))
+    for seed, step in _states_c(traces_c, "compare", 3, where=lambda r: r["before"] > 0):
+        m = cm.replay(seed, upto=step)
+        a, b = _window(m, cm.draw_chain(seed)[1][step]["reg"], (4, 5, 6))
+        assert a.any() or b.any()
+        assert cm.so.compare_literal(a, b, m.scene.q) == cm.so.compare(a, b, m.scene.q), (seed, step)
+
+
+def test_literal_twin_of_the_block_matching(traces_c):
+    """motion_np.match_literal, block by block and displacement by displacement, against motion_np.match on three seeds: on the
+    chain's own grid where the search range is 1 or 2, on a window of the two hulls otherwise."""
+    for seed, step in _states_c(traces_c, "motion", 3, where=lambda r: r["stats"]["listed"] > 0):
+        m = cm.replay(seed, upto=step)
+        op = cm.draw_chain(seed)[1][step]
+        b, ap, s = op["block"], op["apron"], op["search"]
+        if s <= 2:
+            a, bo, grid = m.occ(), m.registers[op["reg"]]["occ"], m.grid
+        else:
+            a, bo = _window(m, op["reg"], (b, b, b))
+            grid = (a.shape[1], a.shape[2], a.shape[0])
+        want, got = cm.mo.match(a, bo, grid, b, ap, s), cm.mo.match_literal(a, bo, grid, b, ap, s)
+        assert len(want["block"]) > 0
+        for key in cm.MOTION_ROW_KEYS:
+            assert np.array_equal(want[key], got[key]) and want[key].dtype == got[key].dtype, (seed, step, key)
+        if s <= 2:
+            m.apply(op)
+            assert cm.Model.motion_bytes(got, b, ap, s) == m.products["motion"]

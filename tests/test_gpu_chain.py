@@ -8,6 +8,11 @@ the operation itself produces, and every product of every pass -- its fetch retu
 message.  At the end of a chain the exchange form, the marching cubes of the occupancy and one run of every quiet pass are compared
 on the final hull.  The two geodesic routes and the two floor-map routes alternate by step parity.
 
+test_chain_c walks family C the same way (chain_model.SEEDS_C: 16 chains of 12 operations, family A's kinds and keep, upload, release,
+combine, compare, motion, warp, paint_motion): behind pipelined and footprint carves, on every slot, with and without a colour
+camera.  After every operation it compares, besides all of the above, the combine's added bytes and the motion field (the model's
+bytes or the refusal by name) and all four hull registers (count, has_records, words, records, or "register r is empty").
+
 A failure names (seed, step, operation, parameters); chain_model.replay(seed, upto=step) rebuilds the model in front of it."""
 import contextlib
 
@@ -15,6 +20,8 @@ import numpy as np
 import pytest
 
 import chain_model as cm
+import motion_np
+from test_gpu_motion import STAT_KEYS
 from test_gpu_result_generation import REFUSAL, RENDER_HW, _fetches, _light, _render_images, _surface_mesh
 
 pytestmark = pytest.mark.gpu
@@ -176,9 +183,61 @@ def _surface_mesh_op(e, op, out):
     _same(got["stats"], out["stats"], ("n_verts", "n_faces", "refined", "unrefined"))
 
 
+def _keep(e, op, out):
+    e.keep_hull(op["reg"])
+
+
+def _upload(e, op, out):
+    e.upload_hull(out["occ"].reshape(-1) if op["form"] == "bits" else out["records"], op["reg"])
+
+
+def _release(e, op, out):
+    e.release_hull(op["reg"])
+
+
+def _timed(st, key):
+    """The call's stats without its time, which is positive."""
+    assert st.pop(key) > 0, key
+    return st
+
+
+def _combine(e, op, out):
+    st = _timed(e.combine_hull(op["setop"], op["reg"]), "setop_ms")
+    assert sorted(st) == sorted(out["stats"])                    # (every field of VcSetopStats but the time)
+    _same(st, out["stats"], sorted(st))
+
+
+def _compare(e, op, out):
+    st = _timed(e.compare_hull(op["reg"], distance=op["distance"]), "compare_ms")
+    derived = {k: st.pop(k) for k in ("iou", "dice", "hausdorff_mm")}
+    assert sorted(st) == sorted(out["stats"])
+    _same(st, out["stats"], sorted(st))
+    _same(derived, out["derived"], sorted(derived))
+
+
+def _motion(e, op, out):
+    st = _timed(e.hull_motion(op["reg"], op["block"], op["apron"], op["search"]), "motion_ms")
+    assert sorted(st) == sorted(STAT_KEYS)
+    _same(st, out["stats"], STAT_KEYS)
+
+
+def _warp(e, op, out):
+    st = _timed(e.warp_hull(op["src"], op["dst"]), "warp_ms")
+    assert st.pop("predicted_iou") == out["predicted_iou"], "predicted_iou"
+    assert sorted(st) == sorted(out["stats"])
+    _same(st, out["stats"], sorted(st))
+
+
+def _paint_motion(e, op, out):
+    e.paint_motion()
+
+
 def _run(e, sc, step, op, out):
     kind = op["op"]
-    if kind == "carve":
+    if kind in cm.REGISTER_KINDS:
+        {"keep": _keep, "upload": _upload, "release": _release, "combine": _combine, "compare": _compare, "motion": _motion,
+         "warp": _warp, "paint_motion": _paint_motion}[kind](e, op, out)
+    elif kind == "carve":
         _carve(e, op, out)
     elif kind in ("close", "dilate"):
         _grow(e, op, out)
@@ -228,6 +287,57 @@ def _result_equals_model(e, m):
                 e.surface_normals()
 
 
+def _registers_equal_model(e, m):
+    """What outlives a result: the combine's added bytes and the motion field -- the model's bytes, or the refusal by name -- and
+    the four hull registers."""
+    from voxcarve._lib import VoxcarveError
+    if "combined" in m.products:
+        assert e.fetch_combined().tobytes() == m.products["combined"], "product combined differs from the model"
+    else:
+        with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + cm.REFUSAL_C["combined"]):
+            e.fetch_combined()
+    if "motion" in m.products:
+        got, f = e.fetch_motion(), m.field
+        for key in cm.MOTION_ROW_KEYS:
+            assert np.array_equal(np.asarray(got[key]).astype(np.int64), np.asarray(f["rows"][key]).astype(np.int64)), ("motion field", key)
+        assert sorted(got) == sorted(cm.MOTION_ROW_KEYS + ("grid", "edge", "apron", "search"))
+        assert (got["grid"], got["edge"], got["apron"], got["search"]) == (m.grid, f["b"], f["a"], f["s"]), "the field's scalars"
+    else:
+        for call in (e.fetch_motion, e.paint_motion):
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + cm.REFUSAL_C["motion"]):
+                call()
+    for reg, want in enumerate(m.registers):
+        if want is None:
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*register %d is empty" % reg):
+                e.fetch_kept(reg)
+            continue
+        got = e.fetch_kept(reg)
+        assert got["count"] == int(want["occ"].sum()), ("register", reg, "count", got["count"])
+        assert got["has_records"] == (want["records"] is not None), ("register", reg, "has_records")
+        assert np.array_equal(got["words"], motion_np.words(want["occ"])), ("register", reg, "words")
+        if want["records"] is None:
+            assert got["records"] is None, ("register", reg, "records")
+        else:
+            assert np.array_equal(got["records"], want["records"]), ("register", reg, "records")
+
+
+def _end_of_chain(e, sc, m, seed, after=lambda: None):
+    """The final hull: the exchange form, the marching cubes of the occupancy, one run of every quiet pass."""
+    with _at(seed, "end", {"op": "expand_entries(pack_entries())"}):
+        assert e.expand_entries(e.pack_entries()) == m.S
+        assert np.array_equal(e.fetch_gathered() & LOW, m.records & LOW)
+    with _at(seed, "end", {"op": "marching_cubes"}):
+        verts, faces = e.marching_cubes(volume=None)
+        want_v, want_f = m.marching_cubes()
+        assert np.array_equal(verts, want_v) and np.array_equal(faces, want_f)
+    for k, op in enumerate(cm.final_ops(sc)):
+        out = m.apply(op)
+        with _at(seed, "end + %d" % k, op):
+            _run(e, sc, k, op, out)
+            _result_equals_model(e, m)
+            after()
+
+
 @pytest.mark.parametrize("seed", cm.SEEDS)
 def test_chain(eng, cams, masks, frames, seed):
     e = eng
@@ -252,3 +362,24 @@ def test_chain(eng, cams, masks, frames, seed):
         with _at(seed, "end + %d" % k, op):
             _run(e, sc, k, op, out)
             _result_equals_model(e, m)
+
+
+@pytest.mark.parametrize("seed", cm.SEEDS_C)
+def test_chain_c(eng, cams, masks, frames, seed):
+    """Family C: the hull registers and the motion field behind every kind of carve.  The engine is the one the chains before
+    have used: set_cameras empties the registers."""
+    from voxcarve._lib import VoxcarveError
+    e = eng
+    sc, ops = cm.draw_chain(seed)
+    _setup(e, sc, cams, masks, frames)
+    for reg in range(cm.REGISTERS):
+        with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*register %d is empty" % reg):
+            e.fetch_kept(reg)
+    m = cm.Model(sc)
+    for step, op in enumerate(ops):
+        out = m.apply(op)
+        with _at(seed, step, op):
+            _run(e, sc, step, op, out)
+            _result_equals_model(e, m)
+            _registers_equal_model(e, m)
+    _end_of_chain(e, sc, m, seed, after=lambda: _registers_equal_model(e, m))
