@@ -11,7 +11,7 @@ if [ "$1" = build ]; then
   # the old revision's sources go to a scratch directory and are deleted again: only the two libraries stay in the tree
   TMP=$(mktemp -d); mkdir -p $TMP/pkg/csrc $TMP/include
   git -C $ROOT show $REV:include/voxcarve.h > $TMP/include/voxcarve.h                    # (voxcarve.hip includes ../../include/voxcarve.h)
-  for f in $(git -C $ROOT ls-tree --name-only $REV $SRC/); do git -C $ROOT show $REV:$f > $TMP/pkg/csrc/$(basename $f); done
+  for f in $(git -C $ROOT ls-tree -r --name-only $REV $SRC/); do mkdir -p $TMP/pkg/$(dirname ${f#*/}); git -C $ROOT show $REV:$f > $TMP/pkg/${f#*/}; done   # (csrc/ and csrc/host/)
   /opt/rocm/bin/hipcc $FLAGS -o $ROOT/ab_build/old/libvoxcarve.so $TMP/pkg/csrc/voxcarve.hip -ldl
   rm -rf $TMP
   /opt/rocm/bin/hipcc $FLAGS -o $ROOT/ab_build/new/libvoxcarve.so $ROOT/$SRC/voxcarve.hip -ldl

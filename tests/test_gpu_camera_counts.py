@@ -39,9 +39,15 @@ FAMILIES = ({"lut_hier": 1}, {"bricks": 0}, {"cull": 0}, {"lut_tile": 0}, {"fuse
             {"voxel_pairs": 1}, {"dbg": 8192}, {"grid_lds_kb": 148, "dbg": 8192}, {"grid_lds_kb": 148, "dbg": 16384}, {"force_generic": 1})
 
 
+def _host_source():
+    """The host side as the compiler reads it: voxcarve.hip and every host/*.h it includes, in its order."""
+    top = open(os.path.join(HIP, "voxcarve.hip")).read()
+    return top + "".join(open(os.path.join(HIP, f)).read() for f in re.findall(r'^#include "(host/\w+\.h)"', top, re.M))
+
+
 def _constants():
     """The launch code's LDS constants, read from the sources (so that the rows follow them if they move)."""
-    src = open(os.path.join(HIP, "voxcarve.hip")).read() + open(os.path.join(HIP, "vc_kernels.h")).read()
+    src = _host_source() + open(os.path.join(HIP, "vc_kernels.h")).read()
     val = {}
     for name in ("kMaxCameras", "kHdrShift", "kGridHeader", "kWideBlock", "kMaxFirstLds", "kWideGridBytes", "kMaxWideLds",
                  "kBusyListMinGroups"):
@@ -54,7 +60,7 @@ def _constants():
 def _defaults():
     """The initial value of every option in OPTION_NAMES: the initialiser of the vc_ctx field vc_set_option writes (the C ABI
     has no getter), read from the source so that the rows restore whatever the library starts with."""
-    src = open(os.path.join(HIP, "voxcarve.hip")).read()
+    src = _host_source()
     ctx = re.search(r"^struct vc_ctx \{(.*?)^\};", src, re.S | re.M).group(1)
     out = {}
     for name in OPTION_NAMES:

@@ -810,7 +810,7 @@ template <typename T>
 int ensure(vc_ctx *ctx, DevBuf<T> &b, size_t elems)
 {
     if (elems <= b.cap && b.ptr) return VC_OK;
-    if (b.ptr) { VC_HIP(ctx, hipFree(b.ptr)); b.ptr = nullptr; b.cap = 0; }
+    b.reset();                                   // (the owner frees, vc_owned.h: as everywhere it does, an error of hipFree is dropped)
     if (elems == 0) elems = 1;
     VC_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&b.ptr), elems * sizeof(T)));
     b.cap = elems;
@@ -1631,8 +1631,7 @@ int enqueue_expand(vc_ctx *ctx, hipStream_t st, const uint64_t *d_entries, uint6
 }  // namespace
 
 // ================================================================ C ABI
-extern "C" {
-
+// (every entry point is declared extern "C" by include/voxcarve.h: its definition takes that linkage; helpers are static)
 int vc_device_count(int *n_out)
 {
     if (!n_out) return VC_ERR_ARG;
@@ -4736,1137 +4735,13 @@ int vc_fetch_lit(vc_ctx *ctx, uint32_t view, uint8_t *rgb, float *depth, uint8_t
     return VC_OK;
 }
 
-// ---- the hull split into K figures on the floor plane (vc_clusters.h; contract in include/voxcarve.h) ----
-// d_cl_acc: [0, 4) Wtot, sum w Px, sum w Py, columns; [4, 20) the seeds' largest keys; [20, 36) voxels per cluster; [36, 100) the
-// round's {W_k, sum w Px, sum w Py, columns}.  d_cl_box: lo [K][3], then hi [K][3].
-constexpr uint32_t kClAccSeed = 4, kClAccVoxels = 20, kClAccRound = 36, kClAccTotal = kClAccRound + kClMaxK * kClAcc;
-constexpr uint32_t kClHostBox = kClMaxK * 6 / 2;               // the boxes read back behind the accumulators, as u64
-
-int vc_hull_clusters(vc_ctx *ctx, uint32_t K, uint32_t max_iters, uint32_t min_column, uint32_t hist_iz_lo, uint32_t hist_iz_hi,
-                     const int64_t *init, uint32_t flags, vc_cluster_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: flags must be 0 (got %u)", flags);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_clusters", "label", "clustering", pass));
-    if (K < 1 || K > kClMaxK) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: K = %u not in [1, %u]", K, kClMaxK);
-    if (max_iters < 1 || max_iters > 255) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: max_iters %u not in [1, 255]", max_iters);
-    if (hist_iz_lo > hist_iz_hi || hist_iz_hi >= ctx->nz)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: the band [%u, %u] of the colour signature is not inside the grid's %u layers",
-                    hist_iz_lo, hist_iz_hi, ctx->nz);
-    if (init)
-        for (uint32_t k = 0; k < 2 * K; ++k)
-            if (init[k] > (1ll << 30) || init[k] < -(1ll << 30))
-                return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: init centre %u has %c = %lld um, beyond +-2^30", k / 2, "xy"[k & 1], (long long)init[k]);
-    uint64_t q[2];
-    VC_TRY(dist_metric(ctx, "vc_hull_clusters", q, 2));
-    const uint64_t S = pass.S, n = pass.n, ncol64 = (uint64_t)ctx->nx * ctx->ny;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_clusters: %llu voxels exceed the u32 index", (unsigned long long)n);
-    const uint32_t ncol = (uint32_t)ncol64;
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    ctx->clusters.stamp = kNever;
-    VC_HIP(ctx, ensure_pinned(ctx->clusters.h, kClAccTotal + kClHostBox));
-    VC_TRY(ensure(ctx, ctx->clusters.fmap, (size_t)ncol));
-    VC_TRY(ensure(ctx, ctx->clusters.flab, (size_t)ncol));
-    VC_TRY(ensure(ctx, ctx->clusters.lab, (size_t)S));
-    VC_TRY(ensure(ctx, ctx->clusters.hist, (size_t)kClMaxK * kClBins));
-    VC_TRY(ensure(ctx, ctx->clusters.box, (size_t)kClMaxK * 6));
-    VC_TRY(ensure(ctx, ctx->clusters.seed, (size_t)kClMaxK));
-    VC_TRY(ensure(ctx, ctx->clusters.acc, (size_t)kClAccTotal));
-    uint32_t *blo = ctx->clusters.box.ptr, *bhi = blo + kClMaxK * 3;
-    uint64_t *h = ctx->clusters.h;
-    VC_TRY(pass_start(ctx, pass, kWordsLater));     // (only the floor map made from the occupancy reads the words)
-    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.fmap.ptr, 0, (size_t)ncol * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.flab.ptr, 0xff, (size_t)ncol, ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.hist.ptr, 0, (size_t)kClMaxK * kClBins * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(blo, 0xff, (size_t)kClMaxK * 3 * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(bhi, 0, (size_t)kClMaxK * 3 * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.seed.ptr, 0xff, (size_t)kClMaxK * sizeof(uint32_t), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->clusters.acc.ptr, 0, (size_t)kClAccTotal * sizeof(uint64_t), ctx->stream));
-    ClCols cols;
-    memset(&cols, 0, sizeof cols);
-    cols.fmap = ctx->clusters.fmap.ptr; cols.ncol = ncol; cols.ny = ctx->ny; cols.min_column = min_column;
-    cols.qx = (long long)q[0]; cols.qy = (long long)q[1];
-    const dim3 block(kClBlock);
-    const uint64_t cblocks = (ncol64 + kClBlock - 1) / kClBlock;
-    const dim3 cgrid((uint32_t)(cblocks < kClMaxBlocks ? cblocks : kClMaxBlocks));
-    unsigned long long *acc = ctx->clusters.acc.ptr;
-    memset(h, 0, (kClAccTotal + kClHostBox) * sizeof(uint64_t));
-    if (S) {
-        // item 2: the floor map and its moments
-        if (ctx->clusters.floor_records) {
-            hipLaunchKernelGGL(k_cl_floor_records, dim3((uint32_t)((S + kClBlock - 1) / kClBlock)), block, 0, ctx->stream,
-                               (const uint64_t *)cur.records.ptr, S, ncol, ctx->clusters.fmap.ptr);
-        } else {
-            VC_TRY(densify_words(ctx, cur));
-            const uint32_t ngroups = (uint32_t)((ncol64 + 63) / 64), nchunks = (ctx->nz + kClLayers - 1) / kClLayers;
-            const uint64_t waves = (uint64_t)ngroups * nchunks;
-            hipLaunchKernelGGL(k_cl_floor, dim3((uint32_t)((waves + kClBlock / 64 - 1) / (kClBlock / 64))), block, 0, ctx->stream,
-                               (const uint64_t *)cur.words.ptr, pass.nwords, ncol, ctx->nz, ngroups, nchunks, ctx->clusters.fmap.ptr);
-        }
-        VC_HIP(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_cl_moments, cgrid, block, 0, ctx->stream, cols, acc);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(h, acc, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    const uint64_t Wtot = h[0], columns = h[3];
-    if (Wtot > S || columns > S || h[1] >= (1ull << 62) || h[2] >= (1ull << 62))
-        return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: the floor map weighs %llu in %llu columns, the result has %llu records",
-                    (unsigned long long)Wtot, (unsigned long long)columns, (unsigned long long)S);
-    ClCentres c;
-    memset(&c, 0, sizeof c);
-    if (init) for (uint32_t k = 0; k < K; ++k) { c.c[k][0] = init[2 * k]; c.c[k][1] = init[2 * k + 1]; }
-    if (Wtot && !init) {
-        // item 3: two launches per seed, the seeds' columns stay on the device until all are picked
-        ClSeed sd;
-        memset(&sd, 0, sizeof sd);
-        sd.seedcol = ctx->clusters.seed.ptr; sd.pick = ctx->clusters.seed.ptr; sd.best = acc + kClAccSeed;
-        sd.mx = (long long)((h[1] + Wtot / 2) / Wtot); sd.my = (long long)((h[2] + Wtot / 2) / Wtot);
-        for (uint32_t j = 0; j < K; ++j) {
-            sd.j = j;
-            hipLaunchKernelGGL(k_cl_seed_best, cgrid, block, 0, ctx->stream, cols, sd);
-            hipLaunchKernelGGL(k_cl_seed_pick, cgrid, block, 0, ctx->stream, cols, sd);
-            VC_HIP(ctx, hipGetLastError());
-        }
-        VC_HIP(ctx, hipMemcpyAsync(h + 4, ctx->clusters.seed.ptr, kClMaxK * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t *sc = reinterpret_cast<const uint32_t *>(h + 4);
-        for (uint32_t k = 0; k < K; ++k) {
-            if (sc[k] >= ncol) return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: seed %u fell on column %u of %u", k, sc[k], ncol);
-            c.c[k][0] = (long long)q[0] * (sc[k] / ctx->ny); c.c[k][1] = (long long)q[1] * (sc[k] % ctx->ny);
-        }
-    }
-    // item 4: one launch and 8 K words back per round
-    uint32_t r = 0;
-    bool converged = Wtot == 0;
-    uint64_t *hr = h + kClAccRound;
-    memset(hr, 0, kClMaxK * kClAcc * sizeof(uint64_t));
-    while (Wtot && r < max_iters) {
-        ++r;
-        VC_HIP(ctx, hipMemsetAsync(acc + kClAccRound, 0, kClMaxK * kClAcc * sizeof(uint64_t), ctx->stream));
-        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, K, c, ctx->clusters.flab.ptr, acc + kClAccRound);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(hr, acc + kClAccRound, kClMaxK * kClAcc * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        bool changed = false;
-        for (uint32_t k = 0; k < K; ++k) {
-            const uint64_t W = hr[kClAcc * k];
-            if (!W) continue;
-            if (W > Wtot) return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: cluster %u weighs %llu of %llu", k, (unsigned long long)W, (unsigned long long)Wtot);
-            const long long x = (long long)((hr[kClAcc * k + 1] + W / 2) / W), y = (long long)((hr[kClAcc * k + 2] + W / 2) / W);
-            changed |= x != c.c[k][0] || y != c.c[k][1];
-            c.c[k][0] = x; c.c[k][1] = y;
-        }
-        if (!changed) { converged = true; break; }
-    }
-    if (S && !Wtot) {
-        // no column reaches min_column: no rounds, every record takes label 0 (one cluster's launch; its weights are zero)
-        VC_HIP(ctx, hipMemsetAsync(acc + kClAccRound, 0, kClMaxK * kClAcc * sizeof(uint64_t), ctx->stream));
-        hipLaunchKernelGGL(k_cl_round, cgrid, block, 0, ctx->stream, cols, 1u, c, ctx->clusters.flab.ptr, acc + kClAccRound);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(hr, acc + kClAccRound, kClMaxK * kClAcc * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (S) {
-        // item 5: voxels and boxes from the columns, labels, histograms and iz ranges from the records
-        hipLaunchKernelGGL(k_cl_columns, cgrid, block, 0, ctx->stream, cols, K, (const uint8_t *)ctx->clusters.flab.ptr, acc + kClAccVoxels, blo, bhi);
-        VC_HIP(ctx, hipGetLastError());
-        ClRecords p;
-        memset(&p, 0, sizeof p);
-        p.records = cur.records.ptr; p.flab = ctx->clusters.flab.ptr; p.lab = ctx->clusters.lab.ptr; p.hist = ctx->clusters.hist.ptr;
-        p.blo = blo; p.bhi = bhi;
-        p.S = S; p.ncol = ncol; p.K = K; p.zlo = hist_iz_lo; p.zhi = hist_iz_hi;
-        const uint64_t rblocks = (S + kClBlock - 1) / kClBlock, rgrid = rblocks < kClMaxBlocks ? rblocks : kClMaxBlocks;
-        p.per = ((S + rgrid - 1) / rgrid + kClBlock - 1) / kClBlock * kClBlock;
-        hipLaunchKernelGGL(k_cl_records, dim3((uint32_t)rgrid), block, 0, ctx->stream, p);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(h + kClAccVoxels, acc + kClAccVoxels, kClMaxK * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipMemcpyAsync(h + kClAccTotal, blo, kClMaxK * 6 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VC_TRY(pass_end(ctx, pass, &stats->clusters_ms));
-    const uint32_t *hb = reinterpret_cast<const uint32_t *>(h + kClAccTotal);     // lo [kClMaxK][3], hi [kClMaxK][3] (zeros when S = 0)
-    ctx->clusters.out.assign(K, vc_cluster_t{});
-    uint64_t labelled = 0;
-    for (uint32_t k = 0; k < K; ++k) {
-        vc_cluster_t &o = ctx->clusters.out[k];
-        o.centre_um[0] = c.c[k][0]; o.centre_um[1] = c.c[k][1];
-        o.voxels = S ? h[kClAccVoxels + k] : 0;
-        o.weight = hr[kClAcc * k];
-        o.columns = (uint32_t)hr[kClAcc * k + 3];
-        for (int a = 0; a < 3; ++a) {
-            o.lo[a] = o.voxels ? hb[3 * k + a] : 0xffffffffu;
-            o.hi[a] = o.voxels ? hb[kClMaxK * 3 + 3 * k + a] : 0u;
-        }
-        labelled += o.voxels;
-    }
-    if (labelled != S)
-        return fail(ctx, VC_ERR_HIP, "vc_hull_clusters: the occupancy holds %llu voxels, the result %llu records", (unsigned long long)labelled,
-                    (unsigned long long)S);
-    stats->survivors = S;
-    stats->columns = columns;
-    stats->weight = Wtot;
-    stats->iterations = r;
-    stats->converged = converged ? 1u : 0u;
-    stats->q[0] = q[0]; stats->q[1] = q[1];
-    ctx->clusters.stamp = ctx->result_gen;
-    ctx->clusters.n = S; ctx->clusters.k = K; ctx->clusters.ncol = ncol;
-    return VC_OK;
-}
-
-// The refusal the fetch calls and vc_paint_clusters share.
-static int clusters_current(vc_ctx *ctx)
-{
-    if (!ctx->carved || !ctx->current(ctx->clusters.stamp)) return fail(ctx, VC_ERR_ARG, "no clusters: call vc_hull_clusters on the current carve result");
-    return VC_OK;
-}
-
-int vc_fetch_cluster_labels(vc_ctx *ctx, uint8_t *labels)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(clusters_current(ctx));
-    if (!labels) return VC_OK;                   // only asked whether the clustering is valid
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->clusters.n) VC_HIP(ctx, hipMemcpy(labels, ctx->clusters.lab.ptr, (size_t)ctx->clusters.n, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_clusters(vc_ctx *ctx, vc_cluster_t *out)
-{
-    if (!ctx || !out) return VC_ERR_ARG;
-    VC_TRY(clusters_current(ctx));
-    memcpy(out, ctx->clusters.out.data(), ctx->clusters.out.size() * sizeof(vc_cluster_t));
-    return VC_OK;
-}
-
-int vc_fetch_cluster_histograms(vc_ctx *ctx, uint32_t *hist)
-{
-    if (!ctx || !hist) return VC_ERR_ARG;
-    VC_TRY(clusters_current(ctx));
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(hist, ctx->clusters.hist.ptr, (size_t)ctx->clusters.k * kClBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_floor_map(vc_ctx *ctx, uint32_t *n)
-{
-    if (!ctx || !n) return VC_ERR_ARG;
-    VC_TRY(clusters_current(ctx));
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(n, ctx->clusters.fmap.ptr, (size_t)ctx->clusters.ncol * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_floor_labels(vc_ctx *ctx, uint8_t *labels)
-{
-    if (!ctx || !labels) return VC_ERR_ARG;
-    VC_TRY(clusters_current(ctx));
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(labels, ctx->clusters.flab.ptr, (size_t)ctx->clusters.ncol, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_paint_clusters(vc_ctx *ctx, const uint8_t *rgb)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!rgb) return fail(ctx, VC_ERR_ARG, "vc_paint_clusters: no palette");
-    VC_TRY(clusters_current(ctx));
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->clusters.n) return VC_OK;
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    ClPalette pal;
-    memset(&pal, 0, sizeof pal);
-    for (uint32_t k = 0; k < ctx->clusters.k; ++k) pal.rgb[k] = (uint32_t)rgb[3 * k] | ((uint32_t)rgb[3 * k + 1] << 8) | ((uint32_t)rgb[3 * k + 2] << 16);
-    hipLaunchKernelGGL(k_cl_paint, dim3((uint32_t)((ctx->clusters.n + kClBlock - 1) / kClBlock)), dim3(kClBlock), 0, ctx->stream, cur.records.ptr,
-                       ctx->clusters.n, (const uint8_t *)ctx->clusters.lab.ptr, pal);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VC_OK;
-}
-
-// ---- geodesic distances through the hull, its extremities and paths (vc_geodesic.h; contract in include/voxcarve.h) ----
-// d_geo_acc: [0] the largest d, [1] the reached records, [2] the distinct seeds, [3] the first seed that is no survivor,
-// [4, 6) k_geo_source's answer.  d_geo_cnt: [0, 2) the entries of the two tile lists, [2] the picked record, [3] the sweeps' change
-// flag, [4, 6) k_geo_path's answer.  h_geo: [0, 8) accumulators, [8] two counters (u32), [10] the word scan's total.
-constexpr uint32_t kGeoAccBest = 0, kGeoAccSeeds = 2, kGeoAccBad = 3, kGeoAccOut = 4, kGeoAccTotal = 6;
-constexpr uint32_t kGeoCntPick = 2, kGeoCntFlag = 3, kGeoCntPath = 4, kGeoCntTotal = 6;
-constexpr uint32_t kGeoSweepsPerRound = 8;
-constexpr uint32_t kGeoMaxBlocks = 4096;
-
-// (isqrt(4 s) + 1) div 2: sqrt(s) rounded to the nearest integer (s < 2^42)
-static uint64_t geo_edge_um(uint64_t s)
-{
-    const uint64_t t = 4 * s;
-    uint64_t r = (uint64_t)sqrtl((long double)t);
-    while (r * r > t) --r;
-    while ((r + 1) * (r + 1) <= t) ++r;
-    return (r + 1) / 2;
-}
-
-// Relaxes from the keys as they are until nothing falls.  Tile route: list 0 holds n0 tiles.  Counts into stats.
-static int geo_relax(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint32_t n0, vc_geodesic_stats_t *stats)
-{
-    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->geodesic.h + 8);
-    const dim3 block(kGeoBlock);
-    uint64_t rounds = 0;
-    if (ctx->geodesic.tiles) {
-        uint32_t par = 0, n = n0;
-        while (n) {
-            if (++rounds > p.S + 1) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_geodesic: the tiles have not settled after %llu rounds", (unsigned long long)(p.S + 1));
-            if (connectivity == 6) VC_DLAUNCH(VC_K_GEO_TILES, k_geo_tiles<6>, dim3(n), block, p, par);
-            else if (connectivity == 18) VC_DLAUNCH(VC_K_GEO_TILES, k_geo_tiles<18>, dim3(n), block, p, par);
-            else VC_DLAUNCH(VC_K_GEO_TILES, k_geo_tiles<26>, dim3(n), block, p, par);
-            VC_HIP(ctx, hipGetLastError());
-            VC_HIP(ctx, hipMemcpyAsync(hc, p.count + (par ^ 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VC_HIP(ctx, hipMemsetAsync(p.count + par, 0, sizeof(uint32_t), ctx->stream));
-            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            stats->tile_visits += n;
-            stats->launches += 1;
-            n = hc[0];
-            if ((uint64_t)n > stats->tiles) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %u tiles listed of %llu", n, (unsigned long long)stats->tiles);
-            par ^= 1u;
-        }
-        // (both lists are empty and every flag is clear: the next relaxation starts at parity 0 again)
-    } else {
-        const dim3 sgrid((uint32_t)((p.S + kGeoBlock - 1) / kGeoBlock));
-        uint32_t *flag = ctx->geodesic.cnt.ptr + kGeoCntFlag;
-        for (;;) {
-            if (++rounds > p.S + 1) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_geodesic: the sweeps have not settled after %llu rounds", (unsigned long long)(p.S + 1));
-            VC_HIP(ctx, hipMemsetAsync(flag, 0, sizeof(uint32_t), ctx->stream));
-            for (uint32_t k = 0; k < kGeoSweepsPerRound; ++k) {
-                if (connectivity == 6) VC_DLAUNCH(VC_K_GEO_SWEEP, k_geo_sweep<6>, sgrid, block, p, flag);
-                else if (connectivity == 18) VC_DLAUNCH(VC_K_GEO_SWEEP, k_geo_sweep<18>, sgrid, block, p, flag);
-                else VC_DLAUNCH(VC_K_GEO_SWEEP, k_geo_sweep<26>, sgrid, block, p, flag);
-            }
-            VC_HIP(ctx, hipGetLastError());
-            VC_HIP(ctx, hipMemcpyAsync(hc, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            stats->launches += kGeoSweepsPerRound;
-            if (!hc[0]) break;
-        }
-    }
-    stats->rounds += (uint32_t)rounds;
-    return VC_OK;
-}
-
-// Walks the path from `voxel` into `out` (host), growing d_geo_path when the path is longer than nx + ny + nz voxels.
-// status = kGeoPath*.
-static int geo_walk(vc_ctx *ctx, const GeoParams &p, uint32_t connectivity, uint32_t voxel, std::vector<uint32_t> &out, uint32_t &status)
-{
-    uint32_t *hc = reinterpret_cast<uint32_t *>(ctx->geodesic.h + 8);
-    uint32_t *res = ctx->geodesic.cnt.ptr + kGeoCntPath;
-    const uint64_t hops = (uint64_t)p.nx + p.ny + p.nz;
-    uint64_t cap = hops < p.S ? hops : p.S;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        VC_TRY(ensure(ctx, ctx->geodesic.path, (size_t)(cap ? cap : 1)));
-        hipLaunchKernelGGL(k_geo_path, dim3(1), dim3(64), 0, ctx->stream, p, connectivity, voxel, ctx->geodesic.path.ptr, (uint32_t)cap, p.S, res);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(hc, res, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        status = hc[1];
-        out.clear();
-        if (status != kGeoPathOk) return VC_OK;
-        if ((uint64_t)hc[0] <= cap) break;
-        if (attempt == 1 || (uint64_t)hc[0] > p.S) return fail(ctx, VC_ERR_HIP, "a path of %u voxels through %llu survivors", hc[0], (unsigned long long)p.S);
-        cap = hc[0];
-    }
-    out.resize(hc[0]);
-    if (hc[0]) VC_HIP(ctx, hipMemcpy(out.data(), ctx->geodesic.path.ptr, (size_t)hc[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_hull_geodesic(vc_ctx *ctx, uint32_t connectivity, uint32_t seed_mode, const uint32_t *seeds, uint64_t n_seeds, uint32_t layers,
-                     uint32_t K, uint32_t flags, vc_geodesic_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags & ~VC_GEO_PATHS) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: unknown flags %u (VC_GEO_PATHS)", flags);
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: connectivity %u, expected 6, 18 or 26", connectivity);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_geodesic", "measure", "geodesic distances", pass));
-    if (K > VC_GEO_MAX_K) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: K = %u not in [0, %d]", K, VC_GEO_MAX_K);
-    if (seed_mode > VC_GEO_SEEDS_IZ_MIN) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed mode %u, expected 0 (list), 1 (iz max) or 2 (iz min)", seed_mode);
-    if (seed_mode == VC_GEO_SEEDS_LIST && n_seeds && !seeds) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu seeds and no list", (unsigned long long)n_seeds);
-    if (seed_mode != VC_GEO_SEEDS_LIST && layers < 1) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: layers = 0, a layer mode seeds at least one");
-    uint64_t q[3];
-    VC_TRY(dist_metric(ctx, "vc_hull_geodesic", q));
-    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu voxels exceed the u32 index", (unsigned long long)n);
-    if (seed_mode != VC_GEO_SEEDS_LIST) n_seeds = 0;
-    if (!S && n_seeds) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed 0 (voxel %u) is no survivor", seeds[0]);
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    ctx->geodesic.stamp = kNever;
-    ctx->geodesic.ext.clear();
-    ctx->geodesic.paths.clear();
-    VC_HIP(ctx, ensure_pinned(ctx->geodesic.h, 12));
-    uint64_t *h = ctx->geodesic.h;
-    uint32_t *hc = reinterpret_cast<uint32_t *>(h + 8);
-    memset(h, 0, 12 * sizeof(uint64_t));
-    stats->survivors = S;
-    for (int a = 0; a < 3; ++a) stats->q[a] = q[a];
-    GeoParams p;
-    memset(&p, 0, sizeof p);
-    for (uint32_t m = 1; m < 8; ++m) {
-        const uint64_t s2 = (m & 1 ? q[0] * q[0] : 0) + (m & 2 ? q[1] * q[1] : 0) + (m & 4 ? q[2] * q[2] : 0);
-        stats->edge_um[m - 1] = geo_edge_um(s2);
-        p.w8[m] = (unsigned long long)stats->edge_um[m - 1] << 8;
-    }
-    VC_TRY(pass_start(ctx, pass));
-    if (S) {
-        // survivors before each word, as vc_hull_components counts them
-        VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
-        VC_TRY(ensure(ctx, ctx->geodesic.woff, (size_t)nwords));
-        VC_TRY(word_offsets(ctx, cur, nwords, ctx->geodesic.woff, h + 10));      // (the total is not read; h_res holds the box next)
-        // the survivors' box: the tiles are laid from its low corner, the layer modes seed from its iz range
-        uint32_t *hb = nullptr;
-        VC_TRY(dist_survivor_box(ctx, cur, S, hb));
-        uint64_t tiles = 1;
-        const uint32_t tdim[3] = {kGeoTX, kGeoTY, kGeoTZ};
-        for (int a = 0; a < 3; ++a) {
-            p.lo[a] = hb[a];
-            p.nt[a] = (hb[3 + a] - hb[a]) / tdim[a] + 1;
-            tiles *= p.nt[a];
-        }
-        const uint32_t zlo = hb[2], zhi = hb[5];
-        stats->tiles = tiles;
-        if (tiles > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: %llu tiles exceed the u32 index", (unsigned long long)tiles);
-        p.tiles = (uint32_t)tiles;
-        VC_TRY(ensure(ctx, ctx->geodesic.key, (size_t)S));
-        VC_TRY(ensure(ctx, ctx->geodesic.acc, kGeoAccTotal));
-        VC_TRY(ensure(ctx, ctx->geodesic.cnt, kGeoCntTotal));
-        VC_TRY(ensure(ctx, ctx->geodesic.flag, (size_t)(2 * tiles)));
-        VC_TRY(ensure(ctx, ctx->geodesic.list, (size_t)(2 * tiles)));
-        if (n_seeds) VC_TRY(ensure(ctx, ctx->geodesic.seeds, (size_t)n_seeds));
-        p.records = cur.records.ptr; p.words = cur.words.ptr; p.woff = ctx->geodesic.woff.ptr; p.key = ctx->geodesic.key.ptr;
-        p.S = S; p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
-        p.flag[0] = ctx->geodesic.flag.ptr; p.flag[1] = ctx->geodesic.flag.ptr + tiles;
-        p.list[0] = ctx->geodesic.list.ptr; p.list[1] = ctx->geodesic.list.ptr + tiles;
-        p.count = ctx->geodesic.cnt.ptr;
-        unsigned long long *acc = ctx->geodesic.acc.ptr;
-        uint32_t *pick = ctx->geodesic.cnt.ptr + kGeoCntPick;
-        VC_HIP(ctx, hipMemsetAsync(p.key, 0xff, (size_t)S * sizeof(uint64_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->geodesic.flag.ptr, 0, (size_t)(2 * tiles) * sizeof(uint32_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->geodesic.cnt.ptr, 0, kGeoCntTotal * sizeof(uint32_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(acc, 0, kGeoAccTotal * sizeof(uint64_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBad, 0xff, sizeof(uint64_t), ctx->stream));
-        const dim3 block(kGeoBlock);
-        // item 2: the seed set
-        if (seed_mode == VC_GEO_SEEDS_LIST) {
-            if (n_seeds) {
-                VC_HIP(ctx, hipMemcpyAsync(ctx->geodesic.seeds.ptr, seeds, (size_t)n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-                VC_DLAUNCH(VC_K_GEO_SEED, k_geo_seed_list, dim3((uint32_t)((n_seeds + kGeoBlock - 1) / kGeoBlock)), block, p,
-                           (const uint32_t *)ctx->geodesic.seeds.ptr, n_seeds, n, acc + kGeoAccSeeds);
-            }
-        } else {
-            const uint32_t span = layers - 1 < zhi - zlo ? layers - 1 : zhi - zlo;
-            const uint32_t z0 = seed_mode == VC_GEO_SEEDS_IZ_MAX ? zhi - span : zlo, z1 = seed_mode == VC_GEO_SEEDS_IZ_MAX ? zhi : zlo + span;
-            VC_DLAUNCH(VC_K_GEO_SEED, k_geo_seed_layers, dim3((uint32_t)((S + kGeoBlock - 1) / kGeoBlock)), block, p, z0, z1, acc + kGeoAccSeeds);
-        }
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccSeeds, acc + kGeoAccSeeds, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipMemcpyAsync(hc, p.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (h[kGeoAccBad] != ~0ull) {
-            dist_harvest(ctx);
-            const uint64_t bad = h[kGeoAccBad];
-            return fail(ctx, VC_ERR_ARG, "vc_hull_geodesic: seed %llu (voxel %u) is no survivor", (unsigned long long)bad, bad < n_seeds ? seeds[bad] : 0u);
-        }
-        stats->seeds = h[kGeoAccSeeds];
-        if (stats->seeds > S || (uint64_t)hc[0] > tiles)
-            return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %llu seeds in %u tiles of %llu survivors", (unsigned long long)stats->seeds, hc[0], (unsigned long long)S);
-        VC_TRY(geo_relax(ctx, p, connectivity, hc[0], stats));
-        // item 3: farthest point, two passes; the path back before the point becomes a source
-        const uint64_t gblocks = (S + kGeoBlock - 1) / kGeoBlock;
-        const dim3 ggrid((uint32_t)(gblocks < kGeoMaxBlocks ? gblocks : kGeoMaxBlocks));
-        for (uint32_t k = 1; k <= K && stats->seeds; ++k) {
-            VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBest, 0, 2 * sizeof(uint64_t), ctx->stream));
-            VC_HIP(ctx, hipMemsetAsync(pick, 0xff, sizeof(uint32_t), ctx->stream));
-            VC_DLAUNCH(VC_K_GEO_ARGMAX, k_geo_best, ggrid, block, (const unsigned long long *)p.key, S, acc + kGeoAccBest);
-            VC_DLAUNCH(VC_K_GEO_ARGMAX, k_geo_pick, ggrid, block, (const unsigned long long *)p.key, S, (const unsigned long long *)(acc + kGeoAccBest), pick);
-            VC_HIP(ctx, hipGetLastError());
-            std::vector<uint32_t> way;
-            if (flags & VC_GEO_PATHS) {
-                VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccBest, acc + kGeoAccBest, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-                VC_HIP(ctx, hipMemcpyAsync(hc, pick, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-                VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (h[kGeoAccBest] == 0 || (uint64_t)hc[0] >= S) break;
-                uint64_t rec = 0;
-                VC_HIP(ctx, hipMemcpy(&rec, cur.records.ptr + hc[0], sizeof rec, hipMemcpyDeviceToHost));
-                uint32_t status = kGeoPathOk;
-                VC_TRY(geo_walk(ctx, p, connectivity, (uint32_t)rec, way, status));
-                if (status != kGeoPathOk) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: the path of extremity %u ended with status %u", k, status);
-            }
-            VC_DLAUNCH(VC_K_GEO_SEED, k_geo_source, dim3(1), dim3(64), p, (const unsigned long long *)(acc + kGeoAccBest), (const uint32_t *)pick, k,
-                       acc + kGeoAccOut);
-            VC_HIP(ctx, hipGetLastError());
-            VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccOut, acc + kGeoAccOut, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-            VC_HIP(ctx, hipMemcpyAsync(hc, p.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const uint64_t d = h[kGeoAccOut];
-            const uint32_t rec = (uint32_t)h[kGeoAccOut + 1], voxel = (uint32_t)(h[kGeoAccOut + 1] >> 32);
-            if (d == 0 || rec == 0xffffffffu) break;
-            vc_extremum_t e;
-            memset(&e, 0, sizeof e);
-            e.d = d; e.voxel = voxel; e.record = rec; e.label = k;
-            e.iy = voxel % ctx->ny; e.ix = (voxel / ctx->ny) % ctx->nx; e.iz = voxel / (ctx->ny * ctx->nx);
-            ctx->geodesic.ext.push_back(e);
-            if (flags & VC_GEO_PATHS) ctx->geodesic.paths.push_back(std::move(way));
-            VC_TRY(geo_relax(ctx, p, connectivity, hc[0], stats));
-        }
-        VC_HIP(ctx, hipMemsetAsync(acc + kGeoAccBest, 0, 2 * sizeof(uint64_t), ctx->stream));
-        VC_DLAUNCH(VC_K_GEO_ARGMAX, k_geo_best, ggrid, block, (const unsigned long long *)p.key, S, acc + kGeoAccBest);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(h + kGeoAccBest, acc + kGeoAccBest, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VC_TRY(pass_end(ctx, pass, &stats->geodesic_ms));
-    if (h[kGeoAccBest + 1] > S) return fail(ctx, VC_ERR_HIP, "vc_hull_geodesic: %llu reached of %llu survivors", (unsigned long long)h[kGeoAccBest + 1], (unsigned long long)S);
-    stats->max_d = S ? h[kGeoAccBest] : 0;
-    stats->reached = S ? h[kGeoAccBest + 1] : 0;
-    stats->unreached = S - stats->reached;
-    stats->extremities = (uint32_t)ctx->geodesic.ext.size();
-    ctx->geodesic.p = p;
-    ctx->geodesic.stamp = ctx->result_gen;
-    ctx->geodesic.n = S; ctx->geodesic.max_d = stats->max_d; ctx->geodesic.conn = connectivity;
-    return VC_OK;
-}
-
-// The refusal the readers of the geodesic outputs share.
-static int geodesic_current(vc_ctx *ctx)
-{
-    if (!ctx->carved || !ctx->current(ctx->geodesic.stamp)) return fail(ctx, VC_ERR_ARG, "no geodesic distances: call vc_hull_geodesic on the current carve result");
-    return VC_OK;
-}
-
-// The keys of the last call, on the host.
-static int geo_fetch_keys(vc_ctx *ctx, std::vector<uint64_t> &keys)
-{
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    keys.resize((size_t)ctx->geodesic.n);
-    if (ctx->geodesic.n) VC_HIP(ctx, hipMemcpy(keys.data(), ctx->geodesic.key.ptr, (size_t)ctx->geodesic.n * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_geodesic(vc_ctx *ctx, uint64_t *d)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(geodesic_current(ctx));
-    if (!d) return VC_OK;                        // only asked whether the distances are valid
-    std::vector<uint64_t> keys;
-    VC_TRY(geo_fetch_keys(ctx, keys));
-    for (size_t s = 0; s < keys.size(); ++s) d[s] = keys[s] == kGeoNone ? kGeoNone : keys[s] >> 8;
-    return VC_OK;
-}
-
-int vc_fetch_geodesic_labels(vc_ctx *ctx, uint8_t *labels)
-{
-    if (!ctx || !labels) return VC_ERR_ARG;
-    VC_TRY(geodesic_current(ctx));
-    std::vector<uint64_t> keys;
-    VC_TRY(geo_fetch_keys(ctx, keys));
-    for (size_t s = 0; s < keys.size(); ++s) labels[s] = (uint8_t)(keys[s] & 255u);     // (2^64 - 1 gives 255)
-    return VC_OK;
-}
-
-int vc_fetch_extrema(vc_ctx *ctx, vc_extremum_t *out)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(geodesic_current(ctx));
-    if (!ctx->geodesic.ext.empty()) {
-        if (!out) return VC_ERR_ARG;
-        memcpy(out, ctx->geodesic.ext.data(), ctx->geodesic.ext.size() * sizeof(vc_extremum_t));
-    }
-    return VC_OK;
-}
-
-// *n = the path's length; out takes it when capacity holds it.
-static int geo_path_out(vc_ctx *ctx, const char *what, const std::vector<uint32_t> &way, uint32_t *out, uint32_t capacity, uint32_t *n)
-{
-    *n = (uint32_t)way.size();
-    if (way.size() > capacity) return fail(ctx, VC_ERR_ARG, "%s: the path has %zu voxels, the capacity is %u", what, way.size(), capacity);
-    if (!way.empty()) {
-        if (!out) return VC_ERR_ARG;
-        memcpy(out, way.data(), way.size() * sizeof(uint32_t));
-    }
-    return VC_OK;
-}
-
-int vc_geodesic_path(vc_ctx *ctx, uint32_t voxel, uint32_t *out, uint32_t capacity, uint32_t *n)
-{
-    if (!ctx || !n) return VC_ERR_ARG;
-    *n = 0;
-    VC_TRY(geodesic_current(ctx));
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if ((uint64_t)voxel >= ctx->n_voxels() || !ctx->geodesic.n) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<uint32_t> way;
-    uint32_t status = kGeoPathOk;
-    VC_TRY(geo_walk(ctx, ctx->geodesic.p, ctx->geodesic.conn, voxel, way, status));
-    if (status == kGeoPathNoSurvivor) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is no survivor", voxel);
-    if (status == kGeoPathUnreached) return fail(ctx, VC_ERR_ARG, "vc_geodesic_path: voxel %u is unreached", voxel);
-    if (status != kGeoPathOk) return fail(ctx, VC_ERR_HIP, "vc_geodesic_path: the walk from voxel %u found no next voxel", voxel);
-    return geo_path_out(ctx, "vc_geodesic_path", way, out, capacity, n);
-}
-
-int vc_fetch_extremum_path(vc_ctx *ctx, uint32_t k, uint32_t *out, uint32_t capacity, uint32_t *n)
-{
-    if (!ctx || !n) return VC_ERR_ARG;
-    *n = 0;
-    VC_TRY(geodesic_current(ctx));
-    if (ctx->geodesic.paths.size() != ctx->geodesic.ext.size() || (ctx->geodesic.ext.size() && ctx->geodesic.paths.empty()))
-        return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: vc_hull_geodesic ran without VC_GEO_PATHS");
-    if (k < 1 || k > ctx->geodesic.paths.size()) return fail(ctx, VC_ERR_ARG, "vc_fetch_extremum_path: k = %u not in [1, %zu]", k, ctx->geodesic.paths.size());
-    return geo_path_out(ctx, "vc_fetch_extremum_path", ctx->geodesic.paths[k - 1], out, capacity, n);
-}
-
-int vc_paint_geodesic(vc_ctx *ctx, uint32_t mode, const uint8_t *palette)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (mode > VC_GEO_PAINT_DISTANCE) return fail(ctx, VC_ERR_ARG, "vc_paint_geodesic: mode %u, expected 0 (labels) or 1 (distance)", mode);
-    if (mode == VC_GEO_PAINT_LABELS && !palette) return fail(ctx, VC_ERR_ARG, "vc_paint_geodesic: no palette");
-    VC_TRY(geodesic_current(ctx));
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->geodesic.n) return VC_OK;
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    GeoPalette pal;
-    memset(&pal, 0, sizeof pal);
-    if (palette)
-        for (uint32_t k = 0; k <= kGeoMaxK; ++k) pal.rgb[k] = (uint32_t)palette[3 * k] | ((uint32_t)palette[3 * k + 1] << 8) | ((uint32_t)palette[3 * k + 2] << 16);
-    const uint32_t none = (uint32_t)VC_GEO_UNREACHED_R | ((uint32_t)VC_GEO_UNREACHED_G << 8) | ((uint32_t)VC_GEO_UNREACHED_B << 16);
-    hipLaunchKernelGGL(k_geo_paint, dim3((uint32_t)((ctx->geodesic.n + kGeoBlock - 1) / kGeoBlock)), dim3(kGeoBlock), 0, ctx->stream, cur.records.ptr,
-                       ctx->geodesic.n, (const unsigned long long *)ctx->geodesic.key.ptr, mode, (unsigned long long)ctx->geodesic.max_d, none, pal);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VC_OK;
-}
-
-// ---- the hull's figures measured per group of records (vc_measure.h; contract in include/voxcarve.h) ----
-static_assert(sizeof(vc_measure_t) == kMsStride * sizeof(uint64_t) && offsetof(vc_measure_t, lo) == kMsSums * sizeof(uint64_t),
-              "the kernels lay an entry out as vc_measure_t");
-
-static MsDiv ms_divisor(uint32_t d)
-{
-    MsDiv q;
-    q.m = (unsigned long long)(0xffffffffffffffffull / d + 1ull);    // (d = 1 wraps to 0: ms_div takes that for "by one")
-    q.d = d;
-    return q;
-}
-
-#define VC_MS_FOLD()                                                                                                                    \
-    hipLaunchKernelGGL(k_ms_fold, dim3((p.tab * kMsStride * kMsFoldSlices + kMsBlock - 1) / kMsBlock), dim3(kMsBlock), 0, ctx->stream,  \
-                       (const unsigned long long *)p.part, grid.x, p.tab * kMsStride, p.out)
-// The launches of one label form (kMsLabels*): the sums per group, then the profile if asked for.
-#define VC_MS_LAUNCH(KIND)                                                                                                              \
-    do {                                                                                                                                \
-        hipLaunchKernelGGL(k_ms_groups<KIND>, grid, dim3(kMsBlock), (size_t)p.tab * kMsStride * sizeof(uint64_t), ctx->stream, p);      \
-        VC_MS_FOLD();                                                                                                                   \
-        if (profile) hipLaunchKernelGGL(k_ms_profile<KIND>, grid, dim3(kMsBlock), 0, ctx->stream, p);                                   \
-    } while (0)
-
-int vc_hull_measure(vc_ctx *ctx, uint32_t source, const uint32_t *labels, uint32_t groups, uint32_t flags, vc_measure_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_measure: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags & ~VC_MEASURE_PROFILE) return fail(ctx, VC_ERR_ARG, "vc_hull_measure: unknown flags %u (VC_MEASURE_PROFILE)", flags);
-    if (source > VC_MEASURE_HOST)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_measure: source %u, expected 0 (all), 1 (clusters), 2 (geodesic) or 3 (host labels)", source);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_measure", "measure", "measuring", pass));
-    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
-    if (ctx->nx > VC_MEASURE_MAX_AXIS || ctx->ny > VC_MEASURE_MAX_AXIS || ctx->nz > VC_MEASURE_MAX_AXIS)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_measure: the grid %u x %u x %u has an axis of more than %u cells", ctx->nx, ctx->ny, ctx->nz,
-                    VC_MEASURE_MAX_AXIS);
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_measure: %llu voxels exceed the u32 index", (unsigned long long)n);
-    uint32_t G = 1;
-    const void *dev_labels = nullptr;
-    if (source == VC_MEASURE_CLUSTERS) {
-        if (!ctx->current(ctx->clusters.stamp))
-            return fail(ctx, VC_ERR_ARG, "vc_hull_measure: no clusters of the current carve result to take the labels from: call vc_hull_clusters first");
-        G = ctx->clusters.k;
-        dev_labels = ctx->clusters.lab.ptr;
-    } else if (source == VC_MEASURE_GEODESIC) {
-        if (!ctx->current(ctx->geodesic.stamp))
-            return fail(ctx, VC_ERR_ARG, "vc_hull_measure: no geodesic regions of the current carve result to take the labels from: call vc_hull_geodesic first");
-        G = (uint32_t)ctx->geodesic.ext.size() + 1u;
-        dev_labels = ctx->geodesic.key.ptr;
-    } else if (source == VC_MEASURE_HOST) {
-        if (!labels) return fail(ctx, VC_ERR_ARG, "vc_hull_measure: VC_MEASURE_HOST and no labels");
-        G = groups;
-    }
-    if (G < 1 || G > VC_MEASURE_MAX_GROUPS) return fail(ctx, VC_ERR_ARG, "vc_hull_measure: G = %u not in [1, %u]", G, VC_MEASURE_MAX_GROUPS);
-    const bool profile = (flags & VC_MEASURE_PROFILE) != 0;
-    if (profile && (uint64_t)G * ctx->nz > VC_MEASURE_MAX_PROFILE)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_measure: a profile of %u groups x %u layers exceeds %u entries", G, ctx->nz, VC_MEASURE_MAX_PROFILE);
-    if (source == VC_MEASURE_HOST)
-        for (uint64_t s = 0; s < S; ++s)
-            if (labels[s] >= G && labels[s] != 0xffffffffu)
-                return fail(ctx, VC_ERR_ARG, "vc_hull_measure: record %llu has label %u, not below G = %u and not 0xffffffff", (unsigned long long)s,
-                            labels[s], G);
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    ctx->measure.stamp = kNever;
-    const size_t cells = (size_t)G * kMsStride, pcells = profile ? (size_t)G * ctx->nz * 3 : 0;
-    VC_HIP(ctx, ensure_pinned(ctx->measure.h, cells));
-    VC_TRY(ensure(ctx, ctx->measure.out, cells));
-    if (profile) VC_TRY(ensure(ctx, ctx->measure.prof, pcells));
-    if (source == VC_MEASURE_HOST && S) VC_TRY(ensure(ctx, ctx->measure.lab, (size_t)S));
-    // as many workgroups as their tables fit kMsPartBytes, between a workgroup per compute unit and kMsMaxBlocks
-    const uint32_t tab = source == VC_MEASURE_ALL ? 1u : G < kMsTable ? G : kMsTable;
-    uint64_t most = kMsPartBytes / ((uint64_t)tab * kMsStride * sizeof(uint64_t));
-    most = most > kMsMaxBlocks ? kMsMaxBlocks : most < 256 ? 256 : most;
-    uint64_t blocks = (S + kMsBlock - 1) / kMsBlock;
-    if (blocks > most) blocks = most;
-    const uint64_t per = S ? ((S + blocks - 1) / blocks + kMsBlock - 1) / kMsBlock * kMsBlock : kMsBlock;
-    const dim3 grid((uint32_t)((S + per - 1) / per));
-    if (S) VC_TRY(ensure(ctx, ctx->measure.part, (size_t)grid.x * tab * kMsStride));
-    VC_TRY(pass_start(ctx, pass));
-    hipLaunchKernelGGL(k_ms_init, dim3((uint32_t)((cells + kMsBlock - 1) / kMsBlock)), dim3(kMsBlock), 0, ctx->stream, ctx->measure.out.ptr, G);
-    VC_HIP(ctx, hipGetLastError());
-    if (profile) VC_HIP(ctx, hipMemsetAsync(ctx->measure.prof.ptr, 0, pcells * sizeof(uint64_t), ctx->stream));
-    if (S) {
-        if (source == VC_MEASURE_HOST) {
-            VC_HIP(ctx, hipMemcpyAsync(ctx->measure.lab.ptr, labels, (size_t)S * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            dev_labels = ctx->measure.lab.ptr;
-        }
-        MsParams p;
-        memset(&p, 0, sizeof p);
-        p.records = cur.records.ptr; p.words32 = reinterpret_cast<const uint32_t *>(cur.words.ptr); p.labels = dev_labels;
-        p.out = ctx->measure.out.ptr; p.prof = profile ? ctx->measure.prof.ptr : nullptr;
-        p.S = S; p.nw32 = 2 * nwords;
-        p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.ncol = ctx->nx * ctx->ny; p.G = G; p.tab = tab; p.per = per;
-        p.by_ncol = ms_divisor(p.ncol); p.by_ny = ms_divisor(p.ny);
-        p.part = ctx->measure.part.ptr;
-        if (source == VC_MEASURE_ALL) {
-            hipLaunchKernelGGL(k_ms_all, grid, dim3(kMsBlock), 0, ctx->stream, p);
-            VC_MS_FOLD();
-            if (profile) hipLaunchKernelGGL(k_ms_profile<kMsLabelsNone>, grid, dim3(kMsBlock), 0, ctx->stream, p);
-        } else if (source == VC_MEASURE_CLUSTERS) VC_MS_LAUNCH(kMsLabelsU8);
-        else if (source == VC_MEASURE_GEODESIC) VC_MS_LAUNCH(kMsLabelsKey);
-        else VC_MS_LAUNCH(kMsLabelsU32);
-        VC_HIP(ctx, hipGetLastError());
-    }
-    VC_HIP(ctx, hipMemcpyAsync(ctx->measure.h, ctx->measure.out.ptr, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->measure_ms));
-    uint64_t measured = 0;
-    for (uint32_t g = 0; g < G; ++g) measured += ctx->measure.h[(size_t)g * kMsStride + kMsVoxels];
-    if (measured > S) return fail(ctx, VC_ERR_HIP, "vc_hull_measure: %llu records measured of %llu", (unsigned long long)measured, (unsigned long long)S);
-    stats->survivors = S; stats->groups = G; stats->measured = measured; stats->unlabelled = S - measured;
-    ctx->measure.g = G; ctx->measure.nz = ctx->nz; ctx->measure.profile = profile;
-    ctx->measure.stamp = ctx->result_gen;
-    return VC_OK;
-}
-
-// The refusal the two fetch calls share.
-static int measure_current(vc_ctx *ctx)
-{
-    if (!ctx->carved || !ctx->current(ctx->measure.stamp)) return fail(ctx, VC_ERR_ARG, "no measurements: call vc_hull_measure on the current carve result");
-    return VC_OK;
-}
-
-int vc_fetch_measure(vc_ctx *ctx, vc_measure_t *out)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(measure_current(ctx));
-    if (!out) return VC_OK;                      // only asked whether the measurements are valid
-    memcpy(out, ctx->measure.h, (size_t)ctx->measure.g * sizeof(vc_measure_t));
-    return VC_OK;
-}
-
-int vc_fetch_measure_profile(vc_ctx *ctx, uint64_t *out)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(measure_current(ctx));
-    if (!ctx->measure.profile) return fail(ctx, VC_ERR_ARG, "no measurements by layer: the last vc_hull_measure ran without VC_MEASURE_PROFILE");
-    if (!out) return VC_OK;
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(out, ctx->measure.prof.ptr, (size_t)ctx->measure.g * ctx->measure.nz * 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-// ---- the hull's shell: the cells with an exposed face, their faces, levels of detail (vc_shell.h; contract in include/voxcarve.h) ----
-static ShGrid shell_grid(const uint32_t *words32, uint64_t nw32, uint32_t nx, uint32_t ny, uint32_t nz)
-{
-    ShGrid g;
-    memset(&g, 0, sizeof g);
-    g.words32 = words32; g.nw32 = nw32;
-    g.nx = nx; g.ny = ny; g.nz = nz; g.ncol = nx * ny;
-    g.by_ncol = ms_divisor(g.ncol); g.by_ny = ms_divisor(ny);
-    return g;
-}
-
-int vc_hull_shell(vc_ctx *ctx, uint32_t level, uint32_t flags, vc_shell_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_shell: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_shell: flags must be 0 (got %u)", flags);
-    if (level > VC_SHELL_MAX_LEVEL) return fail(ctx, VC_ERR_ARG, "vc_hull_shell: level %u not in 0..%u", level, VC_SHELL_MAX_LEVEL);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_shell", "list the shell of", "shell listing", pass));
-    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_shell: %llu voxels exceed the u32 index", (unsigned long long)n);
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    vc_ctx::Shell &sh = ctx->shell;
-    sh.stamp = kNever;
-    const uint32_t L = level, f = 1u << L;
-    const uint32_t cnx = (ctx->nx + f - 1) / f, cny = (ctx->ny + f - 1) / f, cnz = (ctx->nz + f - 1) / f;
-    const uint64_t cn = (uint64_t)cnx * cny * cnz, nwc = (cn + 63) / 64;
-    const uint32_t rgroups = (uint32_t)((S + kCompactGroup - 1) / kCompactGroup), cgroups = word_groups(nwc);
-    VC_HIP(ctx, ensure_pinned(sh.h, kShCounters));
-    VC_TRY(ensure(ctx, sh.cnt, kShCounters));
-    if (S) {
-        VC_TRY(ensure(ctx, ctx->d_rscan, rgroups > cgroups ? rgroups : cgroups));
-        VC_TRY(ensure(ctx, sh.fb, (size_t)S));
-        if (L) {
-            VC_TRY(ensure(ctx, sh.cwords, (size_t)nwc));
-            VC_TRY(ensure(ctx, sh.shw, (size_t)nwc));
-            VC_TRY(ensure(ctx, sh.woff, (size_t)nwc));
-        }
-    }
-    VC_TRY(pass_start(ctx, pass));
-    VC_HIP(ctx, hipMemsetAsync(sh.cnt.ptr, 0, kShCounters * sizeof(uint64_t), ctx->stream));
-    uint64_t T = 0;
-    if (S) {
-        const dim3 block(kShBlock), sgrid((uint32_t)((S + kShBlock - 1) / kShBlock)), wgrid((uint32_t)((nwc + kShBlock - 1) / kShBlock));
-        const dim3 cgrid((cgroups + kCcBlock / 64 - 1) / (kCcBlock / 64));
-        const ShGrid fine = shell_grid(reinterpret_cast<const uint32_t *>(cur.words.ptr), 2 * nwords, ctx->nx, ctx->ny, ctx->nz);
-        const ShGrid coarse = shell_grid(reinterpret_cast<const uint32_t *>(sh.cwords.ptr), 2 * nwc, cnx, cny, cnz);
-        const ShLevel lev = {L, cnx, cny};
-        // the level-0 face bytes: at level 0 with the counts of the compaction, above it with the coarse cells' bits
-        if (!L) {
-            const ShSel0<true> first = {fine, cur.records.ptr, sh.fb.ptr, nullptr, nullptr, 0};
-            hipLaunchKernelGGL(k_compact_count<ShSel0<true>>, dim3(rgroups), dim3(kCompactBlock), 0, ctx->stream, S, ctx->d_rscan.cnt.ptr, first);
-            VC_HIP(ctx, hipGetLastError());
-        } else {
-            VC_HIP(ctx, hipMemsetAsync(sh.cwords.ptr, 0, (size_t)nwc * sizeof(uint64_t), ctx->stream));
-            hipLaunchKernelGGL(k_sh_mark, sgrid, block, 0, ctx->stream, (const uint64_t *)cur.records.ptr, S, fine, lev, sh.fb.ptr,
-                               reinterpret_cast<uint32_t *>(sh.cwords.ptr), 2 * nwc);
-            hipLaunchKernelGGL(k_sh_cshell, wgrid, block, 0, ctx->stream, coarse, (const uint64_t *)sh.cwords.ptr, nwc, sh.shw.ptr,
-                               sh.cnt.ptr + 6);
-            hipLaunchKernelGGL(k_cc_wcount, cgrid, dim3(kCcBlock), 0, ctx->stream, (const uint64_t *)sh.shw.ptr, nwc, cgroups, ctx->d_rscan.cnt.ptr);
-            VC_HIP(ctx, hipGetLastError());
-        }
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, L ? cgroups : rgroups, ctx->h_res + 0));
-        // the one read-back before the end: the number of shell cells sizes their buffers
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        T = ctx->h_res[0];
-        if (T > S || T > cn) return fail(ctx, VC_ERR_HIP, "vc_hull_shell: %llu shell cells of %llu survivors", (unsigned long long)T, (unsigned long long)S);
-        if (T) {
-            VC_TRY(ensure(ctx, sh.rec, (size_t)T));
-            VC_TRY(ensure(ctx, sh.faces, (size_t)T));
-            if (L) VC_TRY(ensure(ctx, sh.acc, (size_t)T * 4));
-        }
-        const uint32_t *off = ctx->d_rscan.off.ptr;
-        const uint64_t *boff = ctx->d_rscan.boff.ptr;
-        if (T && !L) {
-            const ShSel0<false> second = {fine, cur.records.ptr, sh.fb.ptr, sh.rec.ptr, sh.faces.ptr, T};
-            hipLaunchKernelGGL(k_compact_scatter<ShSel0<false>>, dim3(rgroups), dim3(kCompactBlock), 0, ctx->stream, S, off, boff, second);
-        } else if (T) {
-            const dim3 tgrid((uint32_t)((T + kShBlock - 1) / kShBlock));
-            hipLaunchKernelGGL(k_cc_woff, cgrid, dim3(kCcBlock), 0, ctx->stream, (const uint64_t *)sh.shw.ptr, nwc, cgroups, off, boff, sh.woff.ptr);
-            VC_HIP(ctx, hipMemsetAsync(sh.acc.ptr, 0, (size_t)T * 4 * sizeof(uint32_t), ctx->stream));
-            hipLaunchKernelGGL(k_sh_emit, wgrid, block, 0, ctx->stream, coarse, (const uint64_t *)sh.shw.ptr, nwc, (const uint32_t *)sh.woff.ptr,
-                               sh.rec.ptr, sh.faces.ptr, T);
-            hipLaunchKernelGGL(k_sh_accum, sgrid, block, 0, ctx->stream, (const uint64_t *)cur.records.ptr, (const uint8_t *)sh.fb.ptr, S, fine, lev,
-                               (const uint64_t *)sh.shw.ptr, nwc, (const uint32_t *)sh.woff.ptr, sh.acc.ptr, T);
-            hipLaunchKernelGGL(k_sh_final, tgrid, block, 0, ctx->stream, (const uint32_t *)sh.acc.ptr, sh.rec.ptr, T);
-        }
-        if (T) {
-            const uint64_t blocks = (T + kShBlock - 1) / kShBlock;
-            hipLaunchKernelGGL(k_sh_fcount, dim3((uint32_t)(blocks < kShCountBlocks ? blocks : kShCountBlocks)), block, 0, ctx->stream,
-                               (const uint8_t *)sh.faces.ptr, T, sh.cnt.ptr);
-        }
-        VC_HIP(ctx, hipGetLastError());
-    }
-    VC_HIP(ctx, hipMemcpyAsync(sh.h, sh.cnt.ptr, kShCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->shell_ms));
-    stats->survivors = S; stats->cells_on = L ? sh.h[6] : S; stats->shell = T;
-    for (int k = 0; k < 6; ++k) stats->faces[k] = sh.h[k];
-    stats->level = L; stats->cube_scale = f;
-    stats->dims[0] = cnx; stats->dims[1] = cny; stats->dims[2] = cnz;
-    sh.T = T; sh.level = L;
-    sh.dims[0] = cnx; sh.dims[1] = cny; sh.dims[2] = cnz;
-    sh.stamp = ctx->result_gen;
-    return VC_OK;
-}
-
-// The refusal the two fetch calls share.
-static int shell_current(vc_ctx *ctx)
-{
-    if (!ctx->carved || !ctx->current(ctx->shell.stamp)) return fail(ctx, VC_ERR_ARG, "no shell: call vc_hull_shell on the current carve result");
-    return VC_OK;
-}
-
-int vc_fetch_shell(vc_ctx *ctx, uint64_t *records, uint8_t *faces)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(shell_current(ctx));
-    const vc_ctx::Shell &sh = ctx->shell;
-    if (!sh.T || (!records && !faces)) return VC_OK;            // (both NULL: only asked whether the shell is valid)
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (records) VC_HIP(ctx, hipMemcpy(records, sh.rec.ptr, (size_t)sh.T * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (faces) VC_HIP(ctx, hipMemcpy(faces, sh.faces.ptr, (size_t)sh.T, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_shell_viewer(vc_ctx *ctx, double scaling, float *positions, float *colors)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(shell_current(ctx));
-    if (!std::isfinite(scaling) || scaling == 0.0) return fail(ctx, VC_ERR_ARG, "vc_fetch_shell_viewer: scaling %g is zero or not finite", scaling);
-    vc_ctx::Shell &sh = ctx->shell;
-    if (!sh.T || (!positions && !colors)) return VC_OK;
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    // item 4 of the contract in float64 on the host: per axis and (coarse) cell the midpoint of its first and last voxel's
-    // truncated, scaled coordinate (z negated: the viewer's y points up), per colour byte c / 255
-    const uint32_t f = 1u << sh.level, fine[3] = {ctx->nx, ctx->ny, ctx->nz};
-    const std::vector<double> *axes[3] = {&ctx->xs, &ctx->ys, &ctx->zs};
-    std::vector<float> tab;
-    tab.reserve((size_t)sh.dims[0] + sh.dims[1] + sh.dims[2] + 256);
-    for (int a = 0; a < 3; ++a)
-        for (uint32_t c = 0; c < sh.dims[a]; ++c) {
-            const uint64_t lo = (uint64_t)f * c, end = lo + f < fine[a] ? lo + f : fine[a], hi = end - 1;
-            const double v = (std::trunc((*axes[a])[lo]) / scaling + std::trunc((*axes[a])[hi]) / scaling) * 0.5;
-            tab.push_back(a == 2 ? (float)(-v) : (float)v);
-        }
-    for (uint32_t c = 0; c < 256; ++c) tab.push_back((float)((double)c / 255.0));
-    VC_TRY(ensure(ctx, sh.tab, tab.size()));
-    VC_TRY(ensure(ctx, sh.view, (size_t)sh.T * 6));
-    VC_HIP(ctx, hipMemcpy(sh.tab.ptr, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    const ShGrid cg = shell_grid(nullptr, 0, sh.dims[0], sh.dims[1], sh.dims[2]);
-    float *pos = sh.view.ptr, *col = pos + (size_t)sh.T * 3;
-    hipLaunchKernelGGL(k_sh_viewer, dim3((uint32_t)((sh.T + kShBlock - 1) / kShBlock)), dim3(kShBlock), 0, ctx->stream,
-                       (const uint64_t *)sh.rec.ptr, sh.T, cg, (const float *)sh.tab.ptr, pos, col);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (positions) VC_HIP(ctx, hipMemcpy(positions, pos, (size_t)sh.T * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (colors) VC_HIP(ctx, hipMemcpy(colors, col, (size_t)sh.T * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-// ---- the hull thinned to a curve skeleton (vc_thin.h; contract in include/voxcarve.h) ----
-static_assert(sizeof(vc_skeleton_voxel_t) == sizeof(ThRow) && offsetof(vc_skeleton_voxel_t, degree) == 8, "k_thin_rows lays a row out as vc_skeleton_voxel_t");
-
-// The predicate's table on the device, built once per context (on the context's stream: a launch behind it may read it).
-static int thin_table(vc_ctx *ctx, uint32_t *launches)
-{
-    if (ctx->thin.table_built) return VC_OK;
-    VC_TRY(ensure(ctx, ctx->thin.table, (size_t)kThTableWords));
-    VC_DLAUNCH(kThinKind, k_thin_table, dim3(kThTableWords / kThBlock), dim3(kThBlock), ctx->thin.table.ptr);
-    VC_HIP(ctx, hipGetLastError());
-    if (launches) *launches += 1;
-    ctx->thin.table_built = true;
-    return VC_OK;
-}
-
-int vc_hull_thin(vc_ctx *ctx, uint32_t mode, uint32_t anchor_source, const uint32_t *anchors, uint64_t n_anchors, uint32_t max_passes,
-                 uint32_t flags, vc_thin_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: unknown flags %u (none is defined)", flags);
-    if (mode > VC_THIN_POINT) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: mode %u, expected 0 (curve) or 1 (point)", mode);
-    if (anchor_source > VC_THIN_ANCHORS_EXTREMA)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_thin: anchor source %u, expected 0 (none), 1 (list) or 2 (extrema)", anchor_source);
-    if (max_passes < 1 || max_passes > VC_THIN_MAX_PASSES)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_thin: max_passes = %u not in [1, %u]", max_passes, VC_THIN_MAX_PASSES);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_thin", "thin", "thinning", pass));
-    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: %llu voxels exceed the u32 index", (unsigned long long)n);
-    if (anchor_source != VC_THIN_ANCHORS_LIST) n_anchors = 0;
-    if (n_anchors && !anchors) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: %llu anchors and no list", (unsigned long long)n_anchors);
-    if (n_anchors > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: %llu anchors exceed the u32 index", (unsigned long long)n_anchors);
-    if (anchor_source == VC_THIN_ANCHORS_EXTREMA && !ctx->current(ctx->geodesic.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_hull_thin: no geodesic pass of the current carve result to take the anchors from: call vc_hull_geodesic first");
-    if (!S && n_anchors) return fail(ctx, VC_ERR_ARG, "vc_hull_thin: anchor 0 (voxel %u) is no survivor", anchors[0]);
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    vc_ctx::Thin &T = ctx->thin;
-    T.stamp = kNever;
-    VC_HIP(ctx, ensure_pinned(T.h, kThCnt));
-    memset(T.h, 0, kThCnt * sizeof(uint32_t));
-    if (S) {
-        VC_TRY(ensure(ctx, T.work, (size_t)nwords));
-        VC_TRY(ensure(ctx, T.anchor, (size_t)nwords));
-        VC_TRY(ensure(ctx, T.listed, (size_t)nwords));
-        VC_TRY(ensure(ctx, T.woff, (size_t)nwords));
-        VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
-        VC_TRY(ensure(ctx, T.live[0], (size_t)S));
-        VC_TRY(ensure(ctx, T.live[1], (size_t)S));
-        VC_TRY(ensure(ctx, T.cand, (size_t)S));
-        VC_TRY(ensure(ctx, T.peel, (size_t)S));
-        VC_TRY(ensure(ctx, T.rows, (size_t)S));
-        VC_TRY(ensure(ctx, T.cnt, (size_t)kThCnt));
-        if (n_anchors) VC_TRY(ensure(ctx, T.list, (size_t)n_anchors));
-    }
-    VC_TRY(pass_start(ctx, pass));
-    uint32_t launches = 0, passes = 0, stable = 0;
-    uint64_t removed_all = 0;
-    // the launches of one stable compaction of n entries (compact) and of the words' record offsets (word_offsets)
-    auto compact_launches = [](uint64_t n) { return 3u + ((n + kCompactGroup - 1) / kCompactGroup > kScanBlock ? 1u : 0u); };
-    if (!S) { passes = 1; stable = 1; }                          // (one pass over nothing removes nothing)
-    else {
-        const dim3 block(kThBlock);
-        const dim3 sgrid((uint32_t)((S + kThBlock - 1) / kThBlock));
-        VC_HIP(ctx, hipMemcpyAsync(T.work.ptr, cur.words.ptr, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(T.anchor.ptr, 0, (size_t)nwords * sizeof(uint64_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(T.listed.ptr, 0, (size_t)nwords * sizeof(uint64_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(T.cnt.ptr, 0, kThCnt * sizeof(uint32_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(T.cnt.ptr + kThCntBad, 0xff, sizeof(uint32_t), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(T.peel.ptr, 0, (size_t)S * sizeof(uint16_t), ctx->stream));
-        // item 5: the anchors' bits
-        if (anchor_source != VC_THIN_ANCHORS_NONE) {
-            if (n_anchors) {
-                VC_HIP(ctx, hipMemcpyAsync(T.list.ptr, anchors, (size_t)n_anchors * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-                VC_DLAUNCH(kThinKind, k_thin_anchor, dim3((uint32_t)((n_anchors + kThBlock - 1) / kThBlock)), block, (const uint32_t *)T.list.ptr,
-                           (uint32_t)n_anchors, n, (const unsigned long long *)cur.words.ptr, T.anchor.ptr, T.cnt.ptr);
-                launches += 1;
-            } else if (anchor_source == VC_THIN_ANCHORS_EXTREMA && ctx->geodesic.n == S) {
-                VC_DLAUNCH(kThinKind, k_thin_pinned, sgrid, block, (const uint64_t *)cur.records.ptr, (const unsigned long long *)ctx->geodesic.key.ptr, S,
-                           T.anchor.ptr);
-                launches += 1;
-            }
-            VC_DLAUNCH(kThinKind, k_thin_count, dim3((uint32_t)((nwords + kThBlock - 1) / kThBlock)), block, (const unsigned long long *)T.anchor.ptr,
-                       nwords, T.cnt.ptr);
-            launches += 1;
-            VC_HIP(ctx, hipGetLastError());
-            VC_HIP(ctx, hipMemcpyAsync(T.h, T.cnt.ptr, kThCnt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (T.h[kThCntBad] != 0xffffffffu) {
-                dist_harvest(ctx);
-                const uint32_t bad = T.h[kThCntBad];
-                return fail(ctx, VC_ERR_ARG, "vc_hull_thin: anchor %u (voxel %u) is no survivor", bad, bad < n_anchors ? anchors[bad] : 0u);
-            }
-            stats->anchors = T.h[kThCntAnchors];
-        }
-        if (T.use_table) VC_TRY(thin_table(ctx, &launches));
-        ThParams p;
-        memset(&p, 0, sizeof p);
-        p.work = T.work.ptr; p.anchor = T.anchor.ptr; p.table = T.table.ptr; p.cnt = T.cnt.ptr; p.cand = T.cand.ptr; p.peel = T.peel.ptr;
-        p.nwords = nwords; p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz; p.ncol = ctx->nx * ctx->ny;
-        p.by_ncol = ms_divisor(p.ncol); p.by_ny = ms_divisor(p.ny);
-        // the border list before the first pass; a voxel that joins it later takes its record from the words' record offsets
-        VC_TRY(word_offsets(ctx, cur, nwords, T.woff, ctx->h_res + 1, kThinKind));
-        launches += 3 + (word_groups(nwords) > kScanBlock ? 1 : 0);
-        int at = 0;                                              // which of the two buffers holds the border list
-        p.border = T.live[at].ptr; p.listed = T.listed.ptr; p.orig = reinterpret_cast<const unsigned long long *>(cur.words.ptr); p.woff = T.woff.ptr;
-        VC_DLAUNCH(kThinKind, k_thin_border, sgrid, block, p, (const uint64_t *)cur.records.ptr, S);
-        launches += 1;
-        uint64_t blocks = (S + kThBlock - 1) / kThBlock;         // (the lists' counts stay on the device: the launches stride over them)
-        if (blocks > kThMaxBlocks) blocks = kThMaxBlocks;
-        const dim3 grid((uint32_t)blocks);
-        while (passes < max_passes) {
-            passes += 1;
-            // item 4: six direction steps of a mark and eight sub-steps each
-            VC_HIP(ctx, hipMemsetAsync(T.cnt.ptr, 0, (kThCntRemoved + 1) * sizeof(uint32_t), ctx->stream));
-            for (uint32_t d = 0; d < 6; ++d) {
-                const uint32_t code = 1u + 6u * (passes - 1u) + d;
-                VC_DLAUNCH(kThinKind, k_thin_mark, grid, block, p, d);
-                for (uint32_t s = 0; s < 8; ++s) {
-                    if (T.use_table) VC_DLAUNCH(kThinKind, k_thin_sub<true>, grid, block, p, d, s, mode == VC_THIN_CURVE ? 1u : 0u, code);
-                    else VC_DLAUNCH(kThinKind, k_thin_sub<false>, grid, block, p, d, s, mode == VC_THIN_CURVE ? 1u : 0u, code);
-                }
-                launches += 9;
-            }
-            VC_HIP(ctx, hipGetLastError());
-            // the one read-back of the pass: how many it removed, and how long the border list has grown
-            VC_HIP(ctx, hipMemcpyAsync(T.h + kThCntRemoved, T.cnt.ptr + kThCntRemoved, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-            VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const uint64_t removed = T.h[kThCntRemoved], listed = T.h[kThCntBorder];
-            if (removed == 0) { stable = 1; break; }
-            if (removed_all + removed >= S || removed > listed || listed > S) {
-                dist_harvest(ctx);
-                return fail(ctx, VC_ERR_INTERNAL, "vc_hull_thin: pass %u removed %llu of %llu listed voxels (%llu survivors, %llu removed before)", passes,
-                            (unsigned long long)removed, (unsigned long long)listed, (unsigned long long)S, (unsigned long long)removed_all);
-            }
-            removed_all += removed;
-            // the border list without them (vc_compact.h); its count goes back to the device
-            ThSelLive sel;
-            sel.live = T.live[at].ptr; sel.work = T.work.ptr; sel.out = T.live[at ^ 1].ptr;
-            VC_TRY(compact(ctx, sel, listed, ctx->h_res));
-            launches += compact_launches(listed);
-            VC_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(T.cnt.ptr + kThCntBorder), (int)(uint32_t)(listed - removed), 1, ctx->stream));
-            at ^= 1;
-            p.border = T.live[at].ptr;
-        }
-        // item 6: the kept voxels in record order, their rows and the degree counts
-        const uint64_t kept = S - removed_all;
-        ThSelKept sel;
-        sel.records = cur.records.ptr; sel.work = T.work.ptr; sel.out = T.live[at ^ 1].ptr;
-        VC_TRY(compact(ctx, sel, S, ctx->h_res));
-        launches += compact_launches(S);
-        VC_DLAUNCH(kThinKind, k_thin_rows, dim3((uint32_t)((kept + kThBlock - 1) / kThBlock)), block, p, (const unsigned long long *)T.live[at ^ 1].ptr,
-                   (uint32_t)kept, T.rows.ptr);
-        launches += 1;
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(T.h, T.cnt.ptr, kThCnt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    ctx->tm.thin_kernel_ms = 0;
-    ctx->tm.thin_launches = 0;
-    VC_TRY(pass_end(ctx, pass, &stats->thin_ms));
-    ctx->tm.thin_ms = stats->thin_ms;
-    const uint64_t live = S - removed_all;
-    if (S && ctx->h_res[0] != live)
-        return fail(ctx, VC_ERR_INTERNAL, "vc_hull_thin: %llu voxels kept of %llu, %llu removed", (unsigned long long)ctx->h_res[0], (unsigned long long)S,
-                    (unsigned long long)removed_all);
-    stats->survivors = S; stats->kept = live; stats->removed = removed_all;
-    stats->passes = passes; stats->steps = T.h[kThCntSteps]; stats->launches = launches; stats->stable = stable;
-    stats->isolated = T.h[kThCntIsolated]; stats->endpoints = T.h[kThCntEnds]; stats->junctions = T.h[kThCntJunctions];
-    T.n = S; T.kept = live;
-    T.stamp = ctx->result_gen;
-    return VC_OK;
-}
-
-// The refusal the two fetch calls share.
-static int thin_current(vc_ctx *ctx)
-{
-    if (!ctx->carved || !ctx->current(ctx->thin.stamp)) return fail(ctx, VC_ERR_ARG, "no skeleton: call vc_hull_thin on the current carve result");
-    return VC_OK;
-}
-
-int vc_fetch_thin(vc_ctx *ctx, uint16_t *peel)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(thin_current(ctx));
-    if (!peel || !ctx->thin.n) return VC_OK;     // (NULL: only asked whether the skeleton is valid)
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(peel, ctx->thin.peel.ptr, (size_t)ctx->thin.n * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_skeleton(vc_ctx *ctx, vc_skeleton_voxel_t *out)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(thin_current(ctx));
-    if (!out || !ctx->thin.kept) return VC_OK;
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_HIP(ctx, hipMemcpy(out, ctx->thin.rows.ptr, (size_t)ctx->thin.kept * sizeof(vc_skeleton_voxel_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_thin_table(vc_ctx *ctx, uint8_t *bits)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!bits) return fail(ctx, VC_ERR_ARG, "vc_fetch_thin_table: bits must not be NULL");
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->dist_ev_kind.clear();
-    VC_TRY(thin_table(ctx, nullptr));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->dist_ev_kind.clear();                   // (the table's launch belongs to no call's time)
-    VC_HIP(ctx, hipMemcpy(bits, ctx->thin.table.ptr, VC_THIN_TABLE_BYTES, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
+// From here on the host side of a family lives beside its kernels in a file of its own under host/, included once, in dependency
+// order (still this one translation unit: a file may use what stands above it).
+#include "host/clusters.h"   // vc_hull_clusters (dist_metric of the distance passes above)
+#include "host/geodesic.h"   // vc_hull_geodesic, extremities, paths (dist_metric and the survivors' box of the distance passes above)
+#include "host/measure.h"    // vc_hull_measure (the labels of clusters.h and geodesic.h); ms_divisor
+#include "host/shell.h"      // vc_hull_shell (ms_divisor of measure.h, as vc_shell.h takes ms_div from vc_measure.h)
+#include "host/thin.h"       // vc_hull_thin (ms_divisor of measure.h, as vc_thin.h takes ms_div from vc_measure.h)
 
 // ---- the step before the path, its data-parallel part (reference background_subtraction.py:153-168) ----
 static int hsv_tables(vc_ctx *ctx);
@@ -6678,5 +5553,3 @@ int vc_fetch_gathered(vc_ctx *ctx, uint64_t *records)
         VC_HIP(ctx, hipMemcpy(records, ctx->d_gathered.ptr, ctx->gathered_total * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VC_OK;
 }
-
-}  // extern "C"
