@@ -2,11 +2,11 @@
 every product of a post-carve pass whether it is valid and its bytes.  Every operation goes through the restatements that the
 per-pass tests already hold the device to (oracle.carve_c / carve_np, footprint_np, closing_np, distance_np, components_np,
 visible_np, photo_np, clusters_np, geodesic_np, normals_np, render_np, surface_np, temporal_np, measure_np, thin_np, shell_np,
-oracle.marching_np); nothing is restated here.  What this module adds is how the passes COMBINE: which records a pass starts from,
+setops_np, motion_np, texture_np, light_np, oracle.marching_np); nothing is restated here.  What this module adds is how the passes COMBINE: which records a pass starts from,
 which frame set it reads, whose labels it takes, what it invalidates, and the state that outlives a result (the vote's ring, the
-four hull registers).
+four hull registers, the images of the last render and of the passes over them).
 
-Three families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
+Four families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
 and does not know them: tests/golden/chain_digests.json holds its records, so that it cannot move.  B (SEEDS_B, CHAIN_LEN_B,
 KINDS_B) draws from every kind, with carve -> temporal pairs on different slots in most chains.  tests/test_gpu_chain.py walks family
 A on the device; family B is held to its coverage conditions, its literal twins and its faults in tests/test_chain_model.py, and
@@ -20,12 +20,29 @@ other product.  REFUSAL_C names the two new products, `combined` (the added byte
 fetches refuse with; tests/golden/chain_digests_c.json holds the family's record digests; tests/test_gpu_chain.py walks it on
 the device and compares the registers (vc_fetch_kept) after every step as well.
 
+Family D (SEEDS_D, CHAIN_LEN_D, KINDS_D) is family A's kinds and the passes over a render's images: shade (normals_np.shade),
+texture (texture_np), light (light_np), surface_normals, and `feed`, which uploads or touches the masks of the carve's frame set
+without carving.  The images of the last render and the three passes' images -- the products `shaded` (rgb of every view),
+`textured` (rgb, depth, count, best_cam, refined) and `lit` (rgb, depth, kind, shadow, ao), Model.pictures -- are kept apart from
+the products of the result: a carve or a hull changer leaves them to be fetched, the next render drops them, and the three passes
+ask for a render OF THE CURRENT RESULT ("render" among the products).  A pass that only recolours (color_visible, the paints of
+clusters and geodesic) leaves the generation alone: the render stays current, its rgb stays that of the old colours and is what a
+pixel without a normal, without a camera or inside a survivor keeps, while the base colours of shade and light are the records' at
+the call.  The model also holds which colour pass the depth maps belong to ("visibility" among the products), which frame sets
+have input waiting and whether the carve's has been prepared again since the carve (texture with steps > 0, vc_surface_mesh's
+rule), and whether the normals are current.  An operation whose prerequisites are missing is not kept out of the draw: the model
+returns the refusal (OP_REFUSAL_D: a substring of the library's message) and leaves every byte as it was; a carve may carry a
+`probe`, an image pass tried while its step is in flight or behind the same carve without records.  REFUSAL_D names what the
+fetches of the three products refuse with while there are no images; tests/golden/chain_digests_d.json holds, per chain and step,
+the digests of the records and of the three products; tests/test_gpu_chain.py walks the family on the device and compares every
+pixel after every step.
+
 The hull's shell (vc_hull_shell) is no drawn kind: neither family's draws may move.  with_shell(ops, seed) puts `shell` operations
 at fixed places of a chain instead, without a random number; trace, run and replay take shell=True and walk the interleaved chain,
 whose original steps keep their records and their products (tests/test_chain_model.py asserts it).
 
   scene(grid)            one of GRIDS, the golden cameras, three frame sets (slots 0, 1, 2) with different hulls and colours
-  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B, C: CHAIN_LEN_C) operations with all their parameters, drawn
+  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B, C: CHAIN_LEN_C, D: CHAIN_LEN_D) operations with all their parameters, drawn
                          with numpy.random.default_rng(seed) alone; some draws (min_voxels, the sources of a measurement, anchors,
                          which registers are filled, the hull of an upload) look at the model's state, so the chain is applied while
                          it is drawn
@@ -36,7 +53,7 @@ whose original steps keep their records and their products (tests/test_chain_mod
 
 A record is uint64: the linear index in the low 32 bits, r, g, b in bytes 4 - 6, `seen` in byte 7.  The product names are those of
 test_gpu_result_generation.REFUSAL / BUILT and, for the three passes that only family B knows and for the shell, of REFUSAL_B; for
-the combine's added bytes and the motion field, of REFUSAL_C."""
+the combine's added bytes and the motion field, of REFUSAL_C; for the shaded, textured and lit images, of REFUSAL_D."""
 import hashlib
 import os
 import sys
@@ -50,6 +67,7 @@ import distance_np as dn
 import fixtures_util as fx
 import footprint_np as fp
 import geodesic_np as gn
+import light_np as ln
 import measure_np as mn
 import motion_np as mo
 import normals_np as nn
@@ -59,6 +77,7 @@ import setops_np as so
 import shell_np as shn
 import surface_np as sn
 import temporal_np as tpn
+import texture_np as tn
 import thin_np as thn
 import visible_np as vn
 
@@ -108,6 +127,36 @@ MOTION_ROW_KEYS = ("block", "ijk", "d", "cost", "cost0", "count_a", "count_b", "
 UPLOAD_SOURCES = ("carve", "eroded", "shifted", "empty", "full")
 FAULTS_C = ("combine_slot0", "copy_keeps_a", "motion_survives_keep", "register_dies_with_carve", "noop_combine_invalidates")
 MEASURE_SOURCES = ("all", "clusters", "geodesic", "components", "host")
+SEEDS_D = tuple(range(901, 917))            # family D: family A's kinds and the passes over a render's images
+CHAIN_LEN_D = 12
+HW_D = (24, 32)                             # the size of family D's views: light_np at RENDER_HW made the CPU checks too slow.  3 x 4
+#                                             tiles of 8 x 8 pixels per view; every pixel is compared on the device
+VIEW_EYES = ((2500.0, 1500.0, -2000.0), (-1800.0, 2600.0, -900.0))   # test_gpu_result_generation._views': from the grid's centre, mm
+IMAGE_PASSES = ("shade", "texture", "light")                 # they read the images of the last vc_render and make images of their own
+IMAGE_KINDS = IMAGE_PASSES + ("surface_normals", "feed")
+KINDS_D = KINDS + IMAGE_KINDS
+# the images of the three passes -> the refusal of vc_fetch_shaded, vc_fetch_textured, vc_fetch_lit while there are none: before the
+# pass has run on the LAST render (a carve does not touch them, the next vc_render drops them)
+REFUSAL_D = {"shaded": "no shaded images: call vc_shade_render", "textured": "no textured images: call vc_texture_render",
+             "lit": "no lit images: call vc_light_render"}
+PICTURE_KEYS = {"shaded": ("rgb",), "textured": ("rgb", "depth", "count", "best_cam", "refined"), "lit": ("rgb", "depth", "kind", "shadow", "ao")}
+# why a call of family D is refused -> a substring of the library's message (include/voxcarve.h lists the cases; the words are the
+# library's).  The first seven are the ones the chains draw on purpose.
+OP_REFUSAL_D = {"no_render": "no images of the current carve result: call vc_render",
+                "no_depth_maps": "no depth maps of the current carve result: call vc_color_visible",
+                "no_image_in_slot": "has no frame in slot 2",
+                "fed": "has been prepared again since the carve, or has masks or images that wait for it",
+                "stale_normals": "smooth = 1 and no normals: call vc_hull_normals",
+                "no_records": "the last carve ran with VC_FLAG_NO_RECORDS",
+                "in_flight": "carve steps are in flight: collect them with vc_carve_end",
+                "no_normals": "no normals: call vc_hull_normals on the current carve result",
+                "no_mesh": "no mesh of the current carve result: call vc_surface_mesh"}
+DRAWN_REFUSALS = ("no_render", "no_depth_maps", "no_image_in_slot", "fed", "stale_normals", "no_records", "in_flight")
+FAULTS_D = ("textured_survives_render", "lit_dies_with_carve", "stale_depth_maps_accepted", "texture_carve_slot", "recolour_stales_render",
+            "render_follows_records", "smooth_accepts_stale_normals", "steps_ignore_feed")
+LIGHT_POINTS = ((900.0, -1400.0, -2600.0), (-2000.0, 800.0, -1500.0), (0.0, 0.0, -3000.0))    # from the grid's centre, mm (up is -z)
+LIGHT_SUNS = ((0.35, -0.5, -1.0), (-0.6, 0.2, -0.7), (0.0, 0.0, -1.0))                         # from the surface towards the light
+FLOOR_CELL_MM, FLOOR_RGB = 170.0, ((70, 80, 90), (210, 200, 190))                               # test_gpu_light._floor's
 
 LOW = np.uint64(0xffffffff)
 NOT_RGB = np.uint64(0xff000000ffffffff)
@@ -154,8 +203,19 @@ class Scene:
         self.frames = [[every[self.C * s + c] if c in SLOT_IMAGES[s] else None for c in range(self.C)] for s in range(len(ROLLS))]
         self.q = dn.steps_um(self.grid, self.bounds)
         self.views = _views(self)
+        self._views_at = {RENDER_HW: self.views}
         self._carves = {}
         self._matches = {}
+        self._memo = {}
+
+    def views_at(self, hw):
+        """The two views of test_gpu_result_generation._views at another image size."""
+        if hw not in self._views_at:
+            from voxcarve import camera
+            b = self.bounds
+            ctr = np.array([(b[0] + b[1]) / 2, (b[2] + b[3]) / 2, (b[4] + b[5]) / 2])
+            self._views_at[hw] = [camera.look_at(ctr + np.array(eye), ctr, 60.0, hw[0], hw[1]) for eye in VIEW_EYES]
+        return self._views_at[hw]
 
     def mm(self, factor):
         """A radius in mm: `factor` times the grid's largest step; "below" is half the smallest one."""
@@ -184,6 +244,18 @@ class Scene:
             rec.setflags(write=False)
             self._carves[key] = rec
         return self._carves[key]
+
+    def memo(self, what, parts, make):
+        """make() under the key (what, the parts' bytes): the lit and the textured images are the dearest restatements of family D,
+        and a chain is applied once while it is drawn and again by whoever walks it."""
+        h = hashlib.sha1(what.encode())
+        for x in parts:
+            h.update(np.ascontiguousarray(x).tobytes() if isinstance(x, np.ndarray) else repr(x).encode())
+            h.update(b"|")
+        key = h.digest()
+        if key not in self._memo:
+            self._memo[key] = make()
+        return self._memo[key]
 
     def match(self, a, b_occ, b, ap, s, literal=False):
         """motion_np.match of two hulls of this grid (cached: the block matching is the dearest restatement of family C, and a chain
@@ -218,10 +290,18 @@ class Model:
     the fresh records of a combine from slot 0, "copy_keeps_a" lets a restore keep A's bytes on the voxels both hulls hold (item 4
     of vc_hull_combine: every record is B's), "motion_survives_keep" leaves the motion field valid when its register is written
     (item 8 of vc_hull_motion), "register_dies_with_carve" empties the registers at every carve (they survive carves, passes
-    and results), "noop_combine_invalidates" drops every product at a combine with R = A (item 5 of vc_hull_combine)."""
+    and results), "noop_combine_invalidates" drops every product at a combine with R = A (item 5 of vc_hull_combine).  Family D's
+    (FAULTS_D), each a plausible misreading of the header: "textured_survives_render" keeps the textured images over a new render,
+    "lit_dies_with_carve" drops the lit ones at a carve, "stale_depth_maps_accepted" lets texture read the depth maps of a colour
+    pass made before the hull changed, "texture_carve_slot" samples the carve's frame set instead of the call's,
+    "recolour_stales_render" makes the render stale at a pass that only recolours, "render_follows_records" gives the pixels that
+    keep the render's rgb the colours the records have now, "smooth_accepts_stale_normals" lets a smooth light read normals of a
+    hull that is gone, "steps_ignore_feed" lets texture refine against a frame set that has been fed since the carve."""
 
-    def __init__(self, sc, fault=None, literal=False):
+    def __init__(self, sc, fault=None, literal=False, hw=RENDER_HW):
         self.scene = sc
+        self.hw = tuple(hw)                  # the size of the rendered views (family D: HW_D) ...
+        self.views = sc.views_at(self.hw)    # ... and the views
         self.literal = literal               # the restatements' literal twins where a pass has one that is affordable here
         self.grid, self.bounds = sc.grid, sc.bounds
         self.fault = fault
@@ -240,6 +320,16 @@ class Model:
         #                                      what wrote it, for the traces}: they outlive carves, passes and results
         self.field = None                    # the last motion field: rows, b, a, s and the register it was made against; it is
         #                                      current while "motion" is among the products
+        # family D: the images of the last render and of the passes over them.  They are kept apart from the products: a carve or a
+        # hull changer leaves them to be fetched, and only the next render drops them.  "render" among the products says that the
+        # images are OF THE CURRENT RESULT, which is what the three passes ask for.
+        self.images = None                   # index, depth, face, rgb [V, H, W(, 3)] of the last render
+        self.pictures = {}                   # "shaded" | "textured" | "lit" -> {key: array [V, H, W(, 3)]} (PICTURE_KEYS)
+        self.n4 = None                       # the stored normals; current while "normals" is among the products
+        self.zmaps = None                    # the depth maps of the last colour pass; current while "visibility" is among the products
+        self.dirty = set()                   # frame sets with masks or images that wait to be prepared (a feed)
+        self.prepared_again = False          # the carve's frame set has been prepared since the carve: its masks are others
+        self.recoloured = False              # a pass has recoloured the records since the render: its rgb is of the old colours
 
     # what the result is
     @property
@@ -278,8 +368,20 @@ class Model:
         out = getattr(self, "_" + op["op"])(op)
         if self.fault == "shell_repainted" and op["op"] in RECOLOURING and "shell" in self.products:
             self.products["shell"] = self._shell_product(shn.shell(self.records, self.grid, self.shell_level))
+        if op["op"] in RECOLOURING and "render" in self.products:    # the generation stays: the render is still of the current
+            self.recoloured = True                                   # result, and its rgb of the colours it saw
+            if self.fault == "recolour_stales_render":
+                del self.products["render"]
         out["survivors"] = self.S
         return out
+
+    def _prepares(self, slot):
+        """A pass that reads the images of frame set `slot` brings waiting input into the device's layout first: the set is
+        prepared again, and if it is the carve's, its masks are no longer the ones the occupancy came from."""
+        if slot in self.dirty:
+            self.dirty.discard(slot)
+            if slot == self.carve["slot"]:
+                self.prepared_again = True
 
     def _carve(self, op):
         sc = self.scene
@@ -287,6 +389,14 @@ class Model:
         if op.get("first") is not None:          # two steps in flight, both collected: the second one is current
             f = op["first"]
             out["first_records"] = sc.carve_records(f["slot"], f["min_views"], f["color_cam"])
+            self.dirty.discard(f["slot"])
+        if op.get("probe") is not None:          # family D: an image pass tried while this carve's step is in flight, or behind the
+            why = op["probe"]["how"]             # same carve without records; the pass_open of every pass refuses it
+            out.update(refused=why, refusal=OP_REFUSAL_D[why])
+        self.dirty.discard(op["slot"])           # the carve prepares what waits for its frame set
+        self.prepared_again = False
+        if self.fault == "lit_dies_with_carve":
+            self.pictures.pop("lit", None)
         rec = sc.carve_records(op["slot"], op["min_views"], op["color_cam"], op["footprint"])
         self.records = rec.copy()
         self.carved = rec
@@ -361,6 +471,8 @@ class Model:
         self.records = with_rgb(rec0[keep], w["rgb"])
         self.painted = True
         self._changed({"visibility": w["vis"].tobytes(), "photo_rounds": w["rounds"].tobytes()})
+        self._prepares(op["slot"])
+        self.zmaps = w["zmaps"]
         return {"stats": {"rounds": w["n_rounds"], "converged": bool(w["converged"]), "survivors_before": S0, "survivors_after": self.S},
                 "rounds": w["rounds"], "vis": w["vis"], "zmaps": w["zmaps"], "changed": self.S != S0}
 
@@ -370,6 +482,8 @@ class Model:
         self.records = with_rgb(self.records, rgb)
         self.painted = True
         self.products["visibility"] = vis.tobytes()
+        self._prepares(op["slot"])
+        self.zmaps = zmaps
         return {"vis": vis, "zmaps": zmaps}
 
     def _clusters(self, op):
@@ -410,18 +524,159 @@ class Model:
     def _hull_normals(self, op):
         n4, st = (nn.normals_literal if self.literal else nn.normals)(self.occ(), self.scene.q, dn.radius_r2(op["radius_mm"]))
         self.products["normals"] = n4.tobytes()
+        self.n4 = n4
         return {"stats": st, "n4": n4}
 
     def _render(self, op):
         sc = self.scene
-        H, W = RENDER_HW
+        H, W = self.hw
         w = rn.render(self.occ().reshape(-1), self.idx.astype(np.uint32), self.rgb, self.grid, self.bounds,
-                      [rn.view_params(v) for v in sc.views], H, W, block=8)
-        V = len(sc.views)
+                      [rn.view_params(v) for v in self.views], H, W, block=8)
+        V = len(self.views)
         index, depth = w["index"].reshape(V, H, W), w["depth"].reshape(V, H, W)
         self.products["render"] = index.tobytes() + depth.tobytes()
-        return {"index": index, "depth": depth, "face": w["face"].reshape(V, H, W), "rgb": w["rgb"].reshape(V, H, W, 3),
-                "stats": {"pixels": V * H * W, "hits": int((index != rn.MISS).sum())}}
+        self.images = {"index": index, "depth": depth, "face": w["face"].reshape(V, H, W), "rgb": w["rgb"].reshape(V, H, W, 3)}
+        dropped = tuple(sorted(self.pictures))   # the images of the passes over the render before: they do not outlive it
+        self.pictures = {k: v for k, v in self.pictures.items() if self.fault == "textured_survives_render" and k == "textured"}
+        self.recoloured = False
+        return dict(self.images, dropped=dropped, stats={"pixels": V * H * W, "hits": int((index != rn.MISS).sum())})
+
+    # the passes over the render's images.  A call whose prerequisites are missing returns {"refused": the case, "refusal": a
+    # substring of the library's message} and changes nothing; the cases are tried in the order the library tries them.
+    @staticmethod
+    def _refused(why):
+        return {"refused": why, "refusal": OP_REFUSAL_D[why]}
+
+    def render_rgb(self):
+        """The render's own rgb, which a pixel without a normal, without a camera or inside a survivor keeps: of the colours the
+        records had at the render."""
+        if self.fault != "render_follows_records" or "render" not in self.products:
+            return self.images["rgb"]
+        rgb = self.images["rgb"].copy()          # (the wrong model: the colours the records have now)
+        hit = self.images["index"] != rn.MISS
+        if hit.any():
+            rgb[hit] = self.rgb[np.searchsorted(self.idx, self.images["index"][hit].astype(np.int64))]
+        return rgb
+
+    def flat_images(self):
+        V, (H, W) = len(self.views), self.hw
+        ren = {k: self.images[k].reshape(V, H * W) for k in ("index", "depth", "face")}
+        ren["rgb"] = self.render_rgb().reshape(V, H * W, 3)
+        return ren
+
+    def _pictured(self, name, w):
+        V, (H, W) = len(self.views), self.hw
+        self.pictures[name] = {k: np.ascontiguousarray(np.asarray(w[k]).reshape((V, H, W) + ((3,) if k == "rgb" else ())).astype(
+            np.float32 if k == "depth" else np.uint8)) for k in PICTURE_KEYS[name]}
+
+    def _shade(self, op):
+        if "normals" not in self.products:
+            return self._refused("no_normals")
+        if "render" not in self.products:
+            return self._refused("no_render")
+        ren = self.flat_images()
+        idx32, rgb = self.idx.astype(np.uint32), self.rgb
+        self._pictured("shaded", {"rgb": np.stack([nn.shade(ren["index"][v], ren["rgb"][v], idx32, rgb, self.n4, op["light"][v], op["ambient"])
+                                                   for v in range(len(self.views))])})
+        return {}
+
+    def texture_refusal(self, op):
+        if "render" not in self.products:
+            return "no_render"
+        if "visibility" not in self.products and not (self.fault == "stale_depth_maps_accepted" and self.zmaps is not None):
+            return "no_depth_maps"
+        if len(SLOT_IMAGES[op["slot"]]) < self.scene.C:
+            return "no_image_in_slot"
+        fed = self.prepared_again or (op["slot"] == self.carve["slot"] and op["slot"] in self.dirty)
+        if op["steps"] > 0 and fed and self.fault != "steps_ignore_feed":
+            return "fed"
+        return None
+
+    def _texture(self, op):
+        sc = self.scene
+        why = self.texture_refusal(op)
+        if why:
+            return self._refused(why)
+        self._prepares(op["slot"])
+        H, W = self.hw
+        ren = self.flat_images()
+        slot = self.carve["slot"] if self.fault == "texture_carve_slot" and self.carve["slot"] in FULL_SLOTS else op["slot"]
+        masks = np.stack([m > 0 for m in sc.masks[self.carve["slot"]]])
+        views = [rn.view_params(v) for v in self.views]
+        kw = dict(steps=op["steps"], reach=op["reach_mm"], tol=op["depth_tolerance"], best=op["best"], sharpen=op["sharpen"], filt=op["filter"])
+        hit = ren["index"] != rn.MISS
+        w = dict(sc.memo("texture", [ren["index"], ren["depth"], ren["rgb"], self.zmaps, self.carve["slot"], self.min_views(), slot, sorted(kw.items())],
+                         lambda: tn.texture(views, H, W, hit, ren["depth"], ren["rgb"], sc.oc, masks, self.min_views(), self.zmaps, sc.frames[slot], **kw)))
+        if self.literal:                         # the literal twin, one pixel at a time, on every pixel of view `literal_view`
+            v = op.get("literal_view", 0)
+            one = tn.texture_literal(views[v], H, W, hit[v], ren["depth"][v], ren["rgb"][v], sc.oc, masks, self.min_views(), self.zmaps,
+                                     sc.frames[slot], **kw)
+            for k in PICTURE_KEYS["textured"]:
+                w[k] = np.array(w[k], copy=True)
+                w[k][v] = one[k]
+        self._pictured("textured", w)
+        return {"stats": w["stats"]}
+
+    def light_params(self, op):
+        """The `lt` of light_np: the operation's light, with the floor (None or test_gpu_light._floor's) spelled out."""
+        return {"pos": op["pos"], "ambient": op["ambient"], "smooth": int(op["smooth"]), "ao_reach": op["ao_reach"], "floor": op["floor"]}
+
+    def _light(self, op):
+        if "render" not in self.products:
+            return self._refused("no_render")
+        if op["smooth"] and "normals" not in self.products and not (self.fault == "smooth_accepts_stale_normals" and self.n4 is not None):
+            return self._refused("stale_normals")
+        sc = self.scene
+        H, W = self.hw
+        views = [rn.view_params(v) for v in self.views]
+        args = (self.occ().reshape(-1), self.idx.astype(np.uint32), self.rgb, self._n4_for_light() if op["smooth"] else None, self.grid, self.bounds, views, H, W,
+                self.flat_images(), self.light_params(op))
+        w = dict(sc.memo("light", [self.records] + [args[9][k] for k in ("index", "depth", "face", "rgb")] + [args[3], sorted(args[10].items())],
+                         lambda: ln.light(*args, block=8)))
+        if self.literal:                         # the literal twin, one ray at a time, on the pixels of `literal_pixels`
+            px = np.asarray(op.get("literal_pixels", np.arange(H * W)), dtype=np.int64)
+            ren = {k: v[:, px] for k, v in args[9].items()}
+            one = ln.light_literal(*args[:9], ren, args[10], pixels=px)
+            for k in PICTURE_KEYS["lit"]:
+                w[k] = np.array(w[k], copy=True)
+                w[k][:, px] = one[k]
+        self._pictured("lit", w)
+        return {"stats": w["stats"]}
+
+    def _n4_for_light(self):
+        if "normals" in self.products:
+            return self.n4
+        return np.resize(self.n4, (self.S, 4)) if self.n4.size else np.zeros((self.S, 4), np.int16)   # (the wrong model's stale ones)
+
+    def _surface_normals(self, op):
+        if "normals" not in self.products:
+            return self._refused("no_normals")
+        if "surface" not in self.products:
+            return self._refused("no_mesh")
+        el, axis, on_low = sn.mesh_edges(self.occ().reshape(-1), self.grid)
+        nx, ny, _ = self.grid
+        on = np.where(on_low, el, el + np.array([nx * ny, ny, 1], dtype=np.int64)[axis])
+        return {"n4": self.n4[np.searchsorted(self.idx, on)]}
+
+    def _feed(self, op):
+        """Masks of the carve's frame set uploaded again, or touched: the same bytes, which wait to be prepared."""
+        self.dirty.add(op["slot"])
+        return {}
+
+    def picture_digest(self, name):
+        """sha1 of one pass's images (PICTURE_KEYS' order), None while there are none."""
+        if name not in self.pictures:
+            return None
+        return hashlib.sha1(b"".join(self.pictures[name][k].tobytes() for k in PICTURE_KEYS[name])).hexdigest()
+
+    def pictures_digest(self):
+        """sha1 over the images of the three passes that exist, sorted by name: each name and its bytes (PICTURE_KEYS' order)."""
+        h = hashlib.sha1()
+        for name in sorted(self.pictures):
+            h.update(name.encode())
+            for k in PICTURE_KEYS[name]:
+                h.update(self.pictures[name][k].tobytes())
+        return h.hexdigest()
 
     def _surface_mesh(self, op):
         sc = self.scene
@@ -658,7 +913,8 @@ def _palette(rng, rows):
 
 
 def _draw(rng, sc, model, kind, hint=None):
-    """hint (family C alone): parameters that the chain's shape fixes -- a register, a set operation, a slot to stay away from."""
+    """hint (families C and D): parameters that the chain's shape fixes -- a register, a set operation, a slot to stay away from or
+    to take, the steps of a texture, whether a light is smooth."""
     pick = lambda seq, p=None: seq[int(rng.choice(len(seq), p=p))]
     hint = hint or {}
     if kind == "carve":
@@ -762,6 +1018,32 @@ def _draw(rng, sc, model, kind, hint=None):
         return {"op": kind, "src": src, "dst": pick([r for r in range(REGISTERS) if r != src])}
     if kind == "paint_motion":
         return {"op": kind}
+    # family D
+    V = len(sc.views)
+    if kind == "shade":
+        return {"op": kind, "light": np.array([pick(LIGHT_SUNS) for _ in range(V)], dtype=np.float64), "ambient": pick((0, 64, 200))}
+    if kind == "texture":
+        diag = vn.default_tolerance(sc.grid, sc.bounds)
+        slot = hint["slot"] if "slot" in hint else pick((0, 1, 2), (0.42, 0.42, 0.16))
+        steps = hint["steps"] if "steps" in hint else pick((0, 3, 8), (0.3, 0.3, 0.4))
+        return {"op": kind, "slot": slot, "steps": steps, "reach_mm": diag * pick((1.0, 2.0, 0.5)),
+                "depth_tolerance": float(np.float32(diag * pick((1.0, 0.25)))), "best": pick((1, 2, 4)), "sharpen": pick((0, 2, 6)),
+                "filter": int(rng.integers(2))}
+    if kind == "light":
+        b = sc.bounds
+        sun = bool(rng.integers(2))
+        at = pick(LIGHT_SUNS if sun else LIGHT_POINTS)
+        pos = at + (0.0,) if sun else tuple(0.5 * (b[2 * a] + b[2 * a + 1]) + at[a] for a in range(3)) + (1.0,)
+        floor = None
+        if rng.random() < 0.6:                   # (as test_gpu_light._floor makes it)
+            from voxcarve import lighting
+            floor = dict(lighting.auto_floor(sc.grid, sc.bounds), cell_mm=FLOOR_CELL_MM, rgb=FLOOR_RGB)
+        return {"op": kind, "pos": pos, "ambient": pick((0, 64, 120)), "smooth": hint["smooth"] if "smooth" in hint else bool(rng.random() < (0.8 if "normals" in model.products else 0.4)),
+                "ao_reach": pick((0.0, 2.0, 4.0), (0.2, 0.3, 0.5)), "floor": floor}
+    if kind == "surface_normals":
+        return {"op": kind}
+    if kind == "feed":
+        return {"op": kind, "slot": model.carve["slot"], "how": pick(("touch", "upload"))}
     raise ValueError(kind)
 
 
@@ -785,15 +1067,20 @@ _WEIGHTS = {"carve": 1.2, "close": 0.8, "dilate": 0.7, "erode": 0.8, "open": 0.8
 _CHAINS = {}
 
 
+def model_of(seed, fault=None, literal=False):
+    """A fresh model of chain `seed`'s scene, with its family's view size."""
+    return Model(draw_chain(seed)[0], fault, literal, hw=HW_D if family(seed) == "D" else RENDER_HW)
+
+
 def family(seed):
-    return "B" if seed in SEEDS_B else "C" if seed in SEEDS_C else "A"
+    return "B" if seed in SEEDS_B else "C" if seed in SEEDS_C else "D" if seed in SEEDS_D else "A"
 
 
 def draw_chain(seed):
     """(scene, ops) of chain `seed`.  Family A: a carve, then CHAIN_LEN - 1 drawn operations; now and then a burst of hull-changing
-    passes.  Family B: see _draw_chain_b.  Family C: see _draw_chain_c."""
+    passes.  Family B: see _draw_chain_b.  Family C: see _draw_chain_c.  Family D: see _draw_chain_d."""
     if seed not in _CHAINS:
-        _CHAINS[seed] = {"A": _draw_chain, "B": _draw_chain_b, "C": _draw_chain_c}[family(seed)](seed)
+        _CHAINS[seed] = {"A": _draw_chain, "B": _draw_chain_b, "C": _draw_chain_c, "D": _draw_chain_d}[family(seed)](seed)
     return _CHAINS[seed]
 
 
@@ -957,6 +1244,92 @@ def _draw_chain_c(seed):
     return sc, ops
 
 
+_WEIGHTS_D = {"carve": 1.0, "close": 0.3, "dilate": 0.3, "erode": 0.3, "open": 0.3, "filter_components": 0.4, "photo_carve": 0.4,
+              "color_visible": 0.9, "clusters": 0.5, "geodesic": 0.4, "hull_distance": 0.2, "hull_normals": 0.8, "render": 1.2,
+              "surface_mesh": 0.7, "shade": 0.9, "texture": 1.6, "light": 1.6, "surface_normals": 0.9, "feed": 0.4}
+assert set(_WEIGHTS_D) == set(KINDS_D) and not set(KINDS_D) & set(NEW_KINDS + ("temporal_reset", "shell"))
+
+_SEQUENCES_D = np.array([1.0, 1.0, 1.0, 1.0, 1.0, 1.5, 1.0, 1.9, 1.0, 0.8, 1.8, 1.9])              # how often each queued sequence is taken
+_SEQUENCES_D /= _SEQUENCES_D.sum()
+
+
+def _draw_chain_d(seed):
+    """A carve, then CHAIN_LEN_D - 1 operations drawn from family A's kinds, the three passes over a render's images, the mesh's
+    normals and the feed.  Nothing keeps an image pass away from a state that refuses it: the model says what the refusal is.
+    Behind a carve (nine times in ten), and behind every second other operation once the queue is empty, one of twelve sequences
+    is queued (_SEQUENCES_D weighs them); CV is color_visible and N hull_normals, each left out where its product is current:
+      CV N render, texture (steps > 0), shade, light;
+      N render, texture (no depth maps), light (smooth), shade, surface_mesh, surface_normals, carve;
+      CV render, texture, light, carve, any of four, render, light: images that outlive a carve and are dropped by the next render;
+      CV N render, a recolouring pass, texture, light (smooth): the render's rgb is of the old colours, the records' of the new;
+      a hull changer, CV, texture (the render is stale), N render, texture, light (smooth);
+      CV N render, feed, texture (steps > 0, the carve's slot: refused), texture (steps = 0: accepted, and it prepares the set
+      again), texture (steps > 0, any slot: refused), light;
+      an erosion to nothing, CV N render, texture, light, carve;
+      N surface_mesh, surface_normals, render, shade, light;
+      CV render, texture of slot 2 (which has two images), light (smooth, no normals), carve, light (no render);
+      CV N render, texture (steps = 0), carve, render, light;
+      CV N, a hull changer, render, texture (the depth maps are stale), light (smooth: so are the normals), light;
+      N surface_mesh, CV (the mesh stays), surface_normals, render, shade, texture.
+    A surface_mesh drawn by chance is followed by the surface_normals that read it.
+    A carve that is neither the first nor pipelined carries, more often than not, a `probe`: an image pass that is tried while the
+    carve's step is in flight (not a footprint carve's: it has no begin), or behind the same carve without records, in turn, and
+    refused.  Once the carve's frame set has been prepared again, vc_surface_mesh and vc_hull_grow refuse as well (their own tests hold them to that): a surface_mesh, a
+    close or a dilate drawn then becomes the carve that ends the state."""
+    rng = np.random.default_rng(seed)
+    sc = scene(GRIDS[int(rng.integers(len(GRIDS)))])
+    model = Model(sc, hw=HW_D)
+    kinds = list(_WEIGHTS_D)
+    p = np.array([_WEIGHTS_D[k] for k in kinds])
+    p /= p.sum()
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]
+    ops, queue = [], []
+    while len(ops) < CHAIN_LEN_D:
+        hint = None
+        if not ops:
+            kind = "carve"
+        elif model.S == 0 and not queue and rng.random() < 0.5:
+            kind = "carve"
+        elif queue:
+            kind, hint = queue.pop(0)
+            while queue and hint and hint.get("unless") in model.products:   # (depth maps or normals that are current already)
+                kind, hint = queue.pop(0)
+        else:
+            kind = kinds[int(rng.choice(len(kinds), p=p))]
+        if kind in ("close", "dilate", "surface_mesh") and model.prepared_again:
+            kind, hint = "carve", None
+        op = _draw(rng, sc, model, kind, hint)
+        if hint and hint.get("empty"):
+            op["radius_mm"] = sc.mm(40)
+        if kind == "carve" and ops and op["first"] is None and rng.random() < 0.85:
+            probes = sum(o.get("probe") is not None for o in ops)             # (the two kinds in turn; a footprint carve has no begin)
+            op["probe"] = {"how": ("in_flight", "no_records")[probes % 2] if op["footprint"] == "centre" else "no_records",
+                           "op": _draw(rng, sc, model, pick(("texture", "light")))}
+        if kind == "surface_mesh" and not queue:     # a mesh drawn by chance: its normals are read once they can be
+            queue = [("hull_normals", {"unless": "normals"}), ("surface_normals", None)]
+        if not queue and rng.random() < (0.9 if kind == "carve" else 0.5):
+            own = {"slot": op["slot"] if kind == "carve" else model.carve["slot"]}
+            tex = lambda **kw: ("texture", dict({"slot": pick(FULL_SLOTS)}, **kw))
+            N, CV, R, any_light = ("hull_normals", {"unless": "normals"}), ("color_visible", {"unless": "visibility"}), ("render", None), ("light", None)
+            smooth, flat = ("light", {"smooth": True}), ("light", {"smooth": False})
+            queue = [[CV, N, R, tex(steps=pick((3, 8))), ("shade", None), any_light],
+                     [N, R, tex(), smooth, ("shade", None), ("surface_mesh", None), ("surface_normals", None), ("carve", None)],
+                     [CV, R, tex(), flat, ("carve", None), (pick(("color_visible", "hull_normals", "light", "texture")), None), R, any_light],
+                     [CV, N, R, (pick(("clusters", "geodesic", "color_visible")), None), tex(), smooth],
+                     [(pick(HULL_CHANGERS), None), CV, tex(), N, R, tex(), smooth],
+                     [CV, N, R, ("feed", None), ("texture", dict(own, steps=8)), ("texture", dict(own, steps=0)), tex(steps=3), any_light],
+                     [("erode", {"empty": True}), CV, N, R, tex(), any_light, ("carve", None)],
+                     [N, ("surface_mesh", None), ("surface_normals", None), R, ("shade", None), any_light],
+                     [CV, R, ("texture", {"slot": 2}), smooth, ("carve", None), any_light],
+                     [CV, N, R, tex(steps=0), ("carve", None), R, any_light],
+                     [CV, N, (pick(HULL_CHANGERS), None), R, tex(), smooth, flat],
+                     [N, ("surface_mesh", None), CV, ("surface_normals", None), R, ("shade", None), tex()],
+                     ][int(rng.choice(12, p=_SEQUENCES_D))]
+        model.apply(op)
+        ops.append(op)
+    return sc, ops
+
+
 SHELL_AFTER = (2, 6, 10)                     # a shell behind these steps of a chain ...
 SHELL_LEVELS = (0, 0, 1, 0, 2)               # ... at these levels in turn, starting at the seed's place in the list
 SHELL_STALERS = HULL_CHANGERS + ("carve", "temporal")
@@ -1005,7 +1378,7 @@ def run(seed, fault=None, shell=False):
     """Yields (step, op, out, model) of chain `seed` (shell=True: of its walk with the shell put in), the model as the operation
     left it."""
     sc, ops, _ = walk_of(seed, shell)
-    model = Model(sc, fault)
+    model = model_of(seed, fault)
     for step, op in enumerate(ops):
         out = model.apply(op)
         yield step, op, out, model
@@ -1014,7 +1387,7 @@ def run(seed, fault=None, shell=False):
 def replay(seed, upto=None, fault=None, literal=False, shell=False):
     """The model of chain `seed` in front of step `upto` (None: behind the last one); shell=True: steps of the walk with the shell."""
     sc, ops, _ = walk_of(seed, shell)
-    model = Model(sc, fault, literal)
+    model = model_of(seed, fault, literal)
     for op in ops[:upto]:
         model.apply(op)
     return model
@@ -1041,7 +1414,7 @@ def trace(seed, fault=None, shell=False):
     made the result, what made its hull last (the carve or a pass that changed it), and the call's stats."""
     rows = []
     sc, ops, origin = walk_of(seed, shell)
-    model = Model(sc, fault)
+    model = model_of(seed, fault)
     carve_op = made_by = None
     since = [None] * REGISTERS                   # per register, since it was written: the slot then, carves of other slots, hull changes
     for step, op in enumerate(ops):
@@ -1054,8 +1427,16 @@ def trace(seed, fault=None, shell=False):
                "registers_before": [None if k is None else {"count": int(k["occ"].sum()), "has_records": k["records"] is not None,
                                                             "origin": k["origin"], "since": dict(since[r])}
                                     for r, k in enumerate(model.registers)],
-               "motion_reg_before": model.field["reg"] if model.motion_valid() else None}
+               "motion_reg_before": model.field["reg"] if model.motion_valid() else None,
+               "pictures_before": tuple(sorted(model.pictures)), "render_current_before": "render" in model.products,
+               "recoloured_before": model.recoloured,
+               "fed_before": bool(model.carve is not None and (model.prepared_again or model.carve["slot"] in model.dirty))}
         out = model.apply(op)
+        row["refused"] = out.get("refused")
+        row["dropped"] = out.get("dropped", ())
+        row["pictures"] = tuple(sorted(model.pictures))
+        row["pictures_digest"] = model.pictures_digest()
+        row["picture_digests"] = {name: model.picture_digest(name) for name in REFUSAL_D}
         row["registers_digest"] = model.registers_digest()
         row["motion_reg"] = model.field["reg"] if model.motion_valid() else None
         for k in ("restore", "fresh", "bytes_changed"):

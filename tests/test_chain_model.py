@@ -10,6 +10,10 @@ records and products, and the shell has coverage conditions, a literal twin and 
 Family C (chain_model.SEEDS_C) is family A's kinds and the hull registers: keep, upload, release, combine, compare, motion, warp and
 paint_motion.  tests/test_gpu_chain.py walks it on the device; here it has its coverage conditions, its five faults, the literal
 twins of the set algebra and of the block matching, and its own golden digests (tests/golden/chain_digests_c.json).
+Family D (chain_model.SEEDS_D) is family A's kinds and the passes over a render's images: shade, texture, light, surface_normals
+and the feed of the carve's frame set, with the refusals that the model expects drawn on purpose.  tests/test_gpu_chain.py walks
+it on the device; here it has its coverage conditions, its eight faults, the literal twins of texture and light inside the model,
+and golden digests of the records and of the three passes' images (tests/golden/chain_digests_d.json).
 
 The coverage conditions below are conditions on the INPUTS of the GPU test (the seeds, the draw weights, the lengths), asserted here
 so that it cannot pass by doing nothing; where one fails, the seeds, the weights or the length change, never the thresholds.  Then:
@@ -657,3 +661,164 @@ def test_literal_twin_of_the_block_matching(traces_c):
         if s <= 2:
             m.apply(op)
             assert cm.Model.motion_bytes(got, b, ap, s) == m.products["motion"]
+
+
+# ---- family D: the passes over a render's images ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def traces_d():
+    return {seed: cm.trace(seed) for seed in cm.SEEDS_D}
+
+
+def _golden_d():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "chain_digests_d.json")) as f:
+        return json.load(f)
+
+
+def _digests_d(row):
+    """What tests/golden/chain_digests_d.json holds of a step: the records and the images of the three passes (None: there are none)."""
+    return dict(row["picture_digests"], records=row["digest"])
+
+
+def test_family_d_constants():
+    assert cm.SEEDS_D == tuple(range(901, 917)) and cm.CHAIN_LEN_D == 12
+    assert not set(cm.SEEDS_D) & (set(cm.SEEDS) | set(cm.SEEDS_B) | set(cm.SEEDS_C)) and cm.family(cm.SEEDS_D[0]) == "D"
+    assert set(cm.KINDS_D) - set(cm.KINDS) == set(cm.IMAGE_KINDS) and len(cm.IMAGE_KINDS) == 5
+    assert not set(cm.KINDS_D) & set(cm.NEW_KINDS + ("temporal_reset", "shell"))
+    assert set(cm.REFUSAL_D) == set(cm.PICTURE_KEYS) == {"shaded", "textured", "lit"} and not set(cm.REFUSAL_D) & set(cm.PRODUCTS)
+    assert set(cm.DRAWN_REFUSALS) <= set(cm.OP_REFUSAL_D) and len(cm.FAULTS_D) >= 6
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "voxcarve.h")).read()
+    assert "VC_FLAG_NO_RECORDS" in header and cm.HW_D[0] >= 24 and cm.HW_D[1] >= 32
+
+
+def test_coverage_of_family_d(traces_d):
+    """What the 16 chains of family D exercise of the image passes (the issue's table: conditions on the draw, met by the draw
+    alone); and, on every row, what the model's own rules say must hold whatever was drawn."""
+    n = collections.Counter()
+    filters = set()
+    for seed, rows in traces_d.items():
+        assert len(rows) == cm.CHAIN_LEN_D and rows[0]["op"] == "carve"
+        assert all(r["op"] in cm.KINDS_D for r in rows), "a kind that family D must not draw"
+        after_carve = False                      # lit or textured images exist, and a carve has run since they were made
+        for k, r in enumerate(rows):
+            op, p = r["op"], r["params"]
+            old = set(r["pictures_before"]) & {"lit", "textured"}
+            if op == "render":
+                assert r["pictures"] == () and set(r["dropped"]) == set(r["pictures_before"]), (seed, k, "a render keeps no image of a pass")
+                n["a render that drops lit or textured images"] += bool(old)
+                after_carve = False
+            elif op not in cm.IMAGE_PASSES or r["refused"]:
+                assert r["picture_digests"] == rows[k - 1]["picture_digests"] if k else not r["pictures"], (seed, k, "images moved by " + op)
+            if op == "carve":
+                after_carve = after_carve or bool(old)
+                if p.get("probe"):
+                    assert r["refused"] == p["probe"]["how"] and p["first"] is None and (p["footprint"] == "centre" or r["refused"] == "no_records")
+            n["lit or textured images fetched after a later carve"] += after_carve and bool(set(r["pictures"]) & {"lit", "textured"})
+            if r["refused"]:
+                n["refused: " + r["refused"]] += 1
+                if op != "carve":                # nothing moved: records, products, images
+                    prev = rows[k - 1]
+                    assert (r["digest"], r["products_digest"], r["pictures_digest"]) == (prev["digest"], prev["products_digest"], prev["pictures_digest"])
+                continue
+            if op == "feed":
+                n["feed"] += 1
+                assert r["digest"] == rows[k - 1]["digest"] and r["valid"] == rows[k - 1]["valid"]
+            if op in cm.IMAGE_PASSES + ("surface_normals",):
+                assert r["digest"] == rows[k - 1]["digest"] and r["valid"] == rows[k - 1]["valid"], (seed, k, "an image pass moved the result")
+                n["accepted " + op] += 1
+            if op in cm.IMAGE_PASSES:
+                assert r["render_current_before"] and {"shade": "shaded", "texture": "textured", "light": "lit"}[op] in r["pictures"]
+                n["behind a hull changer"] += r["made_by"]["op"] in cm.HULL_CHANGERS
+                n["behind a footprint carve"] += r["carve_op"]["footprint"] != "centre"
+                n["behind a pipelined pair"] += r["carve_op"]["first"] is not None
+                n["behind a recolouring pass"] += r["recoloured_before"]
+                n["on an empty hull"] += r["before"] == 0
+            if op == "texture":
+                n["texture, steps > 0"] += p["steps"] > 0
+                n["texture, steps = 0"] += p["steps"] == 0
+                n["texture, steps > 0, another slot than the fed one"] += p["steps"] > 0 and r["fed_before"]
+                n["texture with fallback pixels behind a recolouring pass"] += r["recoloured_before"] and r["stats"]["fallback"] > 0
+                filters.add(p["filter"])
+                assert r["stats"]["textured"] + r["stats"]["fallback"] == r["stats"]["hits"]
+            if op == "light":
+                n["light, smooth"] += bool(p["smooth"])
+                n["light, floor"] += p["floor"] is not None
+                n["light, point"] += p["pos"][3] == 1.0
+                n["light, sun"] += p["pos"][3] == 0.0
+    print("family D:", dict(n), "filters:", sorted(filters))
+    floors = {"accepted texture": 10, "texture, steps > 0": 6, "texture, steps = 0": 2, "accepted light": 10, "light, smooth": 4,
+              "light, floor": 4, "light, point": 3, "light, sun": 3, "accepted shade": 6, "accepted surface_normals": 4,
+              "lit or textured images fetched after a later carve": 4, "a render that drops lit or textured images": 4,
+              "behind a hull changer": 2, "behind a footprint carve": 2, "behind a pipelined pair": 2, "behind a recolouring pass": 2,
+              "on an empty hull": 1, "feed": 2}
+    floors.update({"refused: " + why: 2 for why in cm.DRAWN_REFUSALS})
+    for name, least in floors.items():
+        assert n[name] >= least, (name, n[name], least)
+    assert filters == {0, 1}
+
+
+def test_family_d_is_held_to_its_digests(traces_d):
+    """The records and the three passes' images behind every step of family D, and a second draw and two replays of it."""
+    want = _golden_d()
+    assert sorted(want) == sorted(str(s) for s in cm.SEEDS_D)
+    for seed in cm.SEEDS_D:
+        assert [_digests_d(r) for r in traces_d[seed]] == want[str(seed)], seed
+    for seed in cm.SEEDS_D[:3]:
+        sc, ops = cm.draw_chain(seed)
+        sc2, ops2 = cm._draw_chain_d(seed)                       # (drawn again, past the cache)
+        assert sc2 is sc and [cm.describe_op(o) for o in ops2] == [cm.describe_op(o) for o in ops]
+        assert all(np.array_equal(a.get("palette"), b.get("palette")) and np.array_equal(a.get("light"), b.get("light")) for a, b in zip(ops, ops2))
+        for upto in (4, 8, cm.CHAIN_LEN_D):
+            row = traces_d[seed][upto - 1]
+            for m in (cm.replay(seed, upto=upto), cm.replay(seed, upto=upto)):
+                assert cm.hashlib.sha1(m.records.tobytes()).hexdigest() == row["digest"] and m.pictures_digest() == row["pictures_digest"]
+                assert cm.products_digest(m) == row["products_digest"] and m.products == row["valid"], (seed, upto)
+
+
+def test_families_a_b_c_draw_as_before_family_d(traces, traces_c):
+    """Family D's state and operations are the model's, so families A and C pass through them: none of it may show."""
+    for rows in list(traces.values()) + list(traces_c.values()):
+        assert all(r["refused"] is None and r["pictures"] == () and not r["fed_before"] for r in rows)
+
+
+@pytest.mark.parametrize("fault", cm.FAULTS_D)
+def test_a_wrong_model_of_the_image_passes_is_told_apart(traces_d, fault):
+    """Each of family D's deliberate mistakes changes something the walk on the device compares -- the images of a pass, whether
+    they exist, a product's validity or a refusal -- in at least one chain."""
+    told = []
+    # (the chains that run the kinds the mistake is about come first: the first chain that tells it apart ends the search)
+    about = {"textured_survives_render": "texture", "lit_dies_with_carve": "light", "stale_depth_maps_accepted": "texture",
+             "texture_carve_slot": "texture", "recolour_stales_render": "render", "render_follows_records": "texture",
+             "smooth_accepts_stale_normals": "light", "steps_ignore_feed": "feed"}[fault]
+    for seed in sorted(traces_d, key=lambda s: -sum(r["op"] == about for r in traces_d[s])):
+        for step, op, out, model in cm.run(seed, fault):
+            row = traces_d[seed][step]
+            if (cm.hashlib.sha1(model.records.tobytes()).hexdigest(), cm.products_digest(model), model.pictures_digest(), out.get("refused")) != \
+                    (row["digest"], row["products_digest"], row["pictures_digest"], row["refused"]):
+                told.append((seed, step, op["op"]))
+                break
+        if told:
+            break
+    print("%s told apart in family D at (seed, step, op):" % fault, told)
+    assert told, "no chain of family D tells the %s model from the right one" % fault
+
+
+def test_literal_twins_of_the_image_passes(traces_d):
+    """texture_np.texture_literal and light_np.light_literal inside the model (literal=True) on the three chains with the most
+    accepted texture and light passes: the same digests at every step.  The twins are Python loops over pixels and rays, so the
+    literal model takes every pixel of view 0 from texture_literal and the pixels of every second row and column of both views from
+    light_literal, through their pixels= argument; the other pixels are the vectorised form's, which the walk on the device
+    compares one by one."""
+    busy = sorted(traces_d, key=lambda s: -sum(r["op"] in ("texture", "light") and not r["refused"] for r in traces_d[s]))[:3]
+    H, W = cm.HW_D
+    px = (np.arange(0, H, 2)[:, None] * W + np.arange(0, W, 4)[None, :]).reshape(-1)
+    for seed in busy:
+        sc, ops = cm.draw_chain(seed)
+        m = cm.model_of(seed, literal=True)
+        ran = collections.Counter()
+        for step, op in enumerate(ops):
+            out = m.apply(dict(op, literal_view=0, literal_pixels=px) if op["op"] in ("texture", "light") else op)
+            row = traces_d[seed][step]
+            ran[op["op"]] += op["op"] in ("texture", "light") and not out.get("refused")
+            assert (cm.hashlib.sha1(m.records.tobytes()).hexdigest(), m.pictures_digest(), out.get("refused")) == \
+                (row["digest"], row["pictures_digest"], row["refused"]), (seed, step, cm.describe_op(op))
+        assert ran["texture"] + ran["light"] >= 2, (seed, dict(ran))

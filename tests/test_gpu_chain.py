@@ -13,14 +13,23 @@ combine, compare, motion, warp, paint_motion): behind pipelined and footprint ca
 camera.  After every operation it compares, besides all of the above, the combine's added bytes and the motion field (the model's
 bytes or the refusal by name) and all four hull registers (count, has_records, words, records, or "register r is empty").
 
+test_chain_d walks family D (chain_model.SEEDS_D: 16 chains of 12 operations, family A's kinds and shade, texture, light,
+surface_normals and the feed of the carve's frame set).  After every operation it compares, besides what test_chain checks, every
+pixel of every view (chain_model.HW_D, 24 x 32: 3 x 4 tiles of the kernels) of the shaded, the textured and the lit images (the model's bytes, depths as their bits, or the refusal by
+name; a view index of n_views is refused too) and of the last render, which like them outlives the result it was made of.  A call
+that the model refuses must raise with the model's words, and the whole comparison then holds as before: nothing moved.
+
 A failure names (seed, step, operation, parameters); chain_model.replay(seed, upto=step) rebuilds the model in front of it."""
 import contextlib
+import ctypes
+import re
 
 import numpy as np
 import pytest
 
 import chain_model as cm
 import motion_np
+from test_gpu_light import COUNTS as LIGHT_COUNTS
 from test_gpu_motion import STAT_KEYS
 from test_gpu_result_generation import REFUSAL, RENDER_HW, _fetches, _light, _render_images, _surface_mesh
 
@@ -167,8 +176,8 @@ def _hull_normals(e, op, out):
     _same(st, out["stats"], ("survivors", "surface", "zero", "offsets", "ext", "q"))
 
 
-def _render(e, op, out, sc):
-    got = e.render(sc.views, *RENDER_HW)
+def _render(e, op, out, sc, views=None, hw=RENDER_HW):
+    got = e.render(sc.views if views is None else views, *hw)
     assert np.array_equal(got["index"], out["index"]), "index"
     assert np.array_equal(got["depth"].view(np.uint32), out["depth"].view(np.uint32)), "depth"
     assert np.array_equal(got["face"], out["face"]) and np.array_equal(got["rgb"], out["rgb"]), "face, rgb"
@@ -321,7 +330,7 @@ def _registers_equal_model(e, m):
             assert np.array_equal(got["records"], want["records"]), ("register", reg, "records")
 
 
-def _end_of_chain(e, sc, m, seed, after=lambda: None):
+def _end_of_chain(e, sc, m, seed, after=lambda: None, run=None):
     """The final hull: the exchange form, the marching cubes of the occupancy, one run of every quiet pass."""
     with _at(seed, "end", {"op": "expand_entries(pack_entries())"}):
         assert e.expand_entries(e.pack_entries()) == m.S
@@ -333,7 +342,7 @@ def _end_of_chain(e, sc, m, seed, after=lambda: None):
     for k, op in enumerate(cm.final_ops(sc)):
         out = m.apply(op)
         with _at(seed, "end + %d" % k, op):
-            _run(e, sc, k, op, out)
+            (run or _run)(e, sc, k, op, out)
             _result_equals_model(e, m)
             after()
 
@@ -383,3 +392,144 @@ def test_chain_c(eng, cams, masks, frames, seed):
             _result_equals_model(e, m)
             _registers_equal_model(e, m)
     _end_of_chain(e, sc, m, seed, after=lambda: _registers_equal_model(e, m))
+
+
+# ---- family D: the passes over a render's images -------------------------------------------------------------------------------------
+TEXTURE_COUNTS = ("pixels", "hits", "refined", "textured", "fallback")
+
+
+def _image_call(e, op):
+    """One of the three passes over the render's images, as the operation says; returns the call's stats (None: it has none)."""
+    if op["op"] == "shade":
+        e.shade_render(op["light"], op["ambient"])
+        return None
+    if op["op"] == "texture":
+        return e.texture_render(op["slot"], op["steps"], op["reach_mm"], op["depth_tolerance"], op["best"], op["sharpen"], op["filter"])["stats"]
+    return e.light_render(op["pos"], ambient=op["ambient"], smooth=op["smooth"], ao_reach=op["ao_reach"], floor=op["floor"])["stats"]
+
+
+def _refuses(out):
+    from voxcarve._lib import VoxcarveError
+    return pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + re.escape(out["refusal"]))
+
+
+def _carve_probed(e, op, out):
+    """A carve with an image pass tried where every pass must refuse: while the carve's step is in flight, or behind the same
+    carve without records.  Whatever happens, no step is left in flight."""
+    probe = op["probe"]
+    assert out["refused"] == probe["how"]
+    kw = dict(slot=op["slot"], min_views=op["min_views"], color_cam=op["color_cam"], mode=op["mode"])
+    if probe["how"] == "in_flight":
+        e.carve_begin(**kw)
+        try:
+            with _refuses(out):
+                _image_call(e, probe["op"])
+        finally:
+            n = e.carve_end()
+        assert n == out["count"]
+    else:
+        assert e.carve(records=False, footprint=op["footprint"], **kw) == out["count"]
+        with _refuses(out):
+            _image_call(e, probe["op"])
+        _carve(e, op, out)
+
+
+def _run_d(e, sc, step, op, out):
+    kind = op["op"]
+    if kind == "carve" and op.get("probe") is not None:
+        _carve_probed(e, op, out)
+    elif kind == "render":                       # (family D's views are smaller than the other families')
+        _render(e, op, out, sc, sc.views_at(cm.HW_D), cm.HW_D)
+    elif kind == "feed":
+        if op["how"] == "touch":
+            e.touch_masks(op["slot"])
+        else:
+            e.upload_masks(sc.masks[op["slot"]], slot=op["slot"])
+    elif kind not in cm.IMAGE_KINDS:
+        _run(e, sc, step, op, out)
+    elif out.get("refused"):
+        with _refuses(out):
+            e.surface_normals() if kind == "surface_normals" else _image_call(e, op)
+    elif kind == "surface_normals":
+        assert np.array_equal(e.surface_normals(), out["n4"]), "the mesh's normals"
+    else:
+        st = _image_call(e, op)
+        if kind == "texture":
+            _same(st, out["stats"], TEXTURE_COUNTS)
+        elif kind == "light":
+            _same(st, out["stats"], LIGHT_COUNTS)
+
+
+def _fetch_picture(e, name, view):
+    """One view of a pass's images through the library's fetch, every plane of it."""
+    from voxcarve.engine import _ptr
+    H, W = cm.HW_D
+    got = {k: np.empty((H, W, 3) if k == "rgb" else (H, W), dtype=np.float32 if k == "depth" else np.uint8) for k in cm.PICTURE_KEYS[name]}
+    ptrs = [_ptr(got[k], ctypes.c_float if k == "depth" else ctypes.c_uint8) for k in cm.PICTURE_KEYS[name]]
+    call = {"shaded": e._L.vc_fetch_shaded, "textured": e._L.vc_fetch_textured, "lit": e._L.vc_fetch_lit}[name]
+    e._check(call(e._ctx, view, *ptrs), "vc_fetch_" + name)
+    return got
+
+
+def _pictures_equal_model(e, m):
+    """The images that outlive a result: the last render's, and the shaded, textured and lit ones -- every pixel of every view is
+    the model's (depths as their bits), or the fetch refuses by name; a view index of n_views is refused as well."""
+    from voxcarve._lib import VoxcarveError
+    from voxcarve.engine import _ptr
+    V, (H, W) = len(m.views), m.hw
+    if m.images is not None:
+        for v in range(V):
+            got = {"index": np.empty((H, W), np.uint32), "depth": np.empty((H, W), np.float32), "rgb": np.empty((H, W, 3), np.uint8),
+                   "face": np.empty((H, W), np.uint8)}
+            e._check(e._L.vc_fetch_render(e._ctx, v, _ptr(got["index"], ctypes.c_uint32), _ptr(got["depth"], ctypes.c_float),
+                                          _ptr(got["rgb"], ctypes.c_uint8), _ptr(got["face"], ctypes.c_uint8)), "vc_fetch_render")
+            for k, a in got.items():
+                assert a.tobytes() == m.images[k][v].tobytes(), ("the last render", k, "view", v)
+    for name in cm.REFUSAL_D:
+        if name not in m.pictures:
+            for v in (0, V):
+                with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + cm.REFUSAL_D[name]):
+                    _fetch_picture(e, name, v)
+            continue
+        for v in range(V):
+            got = _fetch_picture(e, name, v)
+            for k in cm.PICTURE_KEYS[name]:
+                want = m.pictures[name][k][v]
+                a = (got[k] != 0).astype(np.uint8) if k == "refined" else got[k]
+                bad = np.flatnonzero((a.view(np.uint32) if k == "depth" else a).reshape(-1) != (want.view(np.uint32) if k == "depth" else want).reshape(-1))
+                assert bad.size == 0, "%s, %s of view %d: %d values differ from the model, first at %d" % (name, k, v, bad.size, bad[0])
+        with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*view %d not in" % V):
+            _fetch_picture(e, name, V)
+
+
+def _told_of_the_probe(e, m):
+    """_result_equals_model asks vc_shade_render whether the render is of the current result, and where it is, that call has made
+    shaded images of its own light: the model is told."""
+    if "normals" in m.products and "render" in m.products:
+        assert not m.apply({"op": "shade", "light": _light(e), "ambient": 64}).get("refused")
+
+
+@pytest.mark.parametrize("seed", cm.SEEDS_D)
+def test_chain_d(eng, cams, masks, frames, seed):
+    """Family D: the passes over a render's images behind every kind of carve, with the refusals the model expects.  The engine is
+    the one the chains before have used, and images outlive set_grid and set_cameras: a carve and a render in front of the chain
+    drop whatever an earlier chain left, so that the chain starts without shaded, textured or lit images, as the model does."""
+    e = eng
+    sc, ops = cm.draw_chain(seed)
+    _setup(e, sc, cams, masks, frames)
+    e.carve()
+    e.render(sc.views_at(cm.HW_D), *cm.HW_D)
+    m = cm.model_of(seed)
+    assert m.hw == cm.HW_D
+    for step, op in enumerate(ops):
+        out = m.apply(op)
+        with _at(seed, step, op):
+            _run_d(e, sc, step, op, out)
+            _pictures_equal_model(e, m)              # (in front of the probe below, which shades)
+            _result_equals_model(e, m)
+            _told_of_the_probe(e, m)
+
+    def after():
+        _told_of_the_probe(e, m)
+        _pictures_equal_model(e, m)
+    _end_of_chain(e, sc, m, seed, after=after, run=_run_d)

@@ -3,7 +3,10 @@
 Every product is built once on the 64^3 hull of the four golden cameras.  After each call that changes the result every product's
 fetch refuses with its own message, except what that call itself produces; a pass that leaves the hull alone leaves every other
 product valid and byte-identical.  The per-pass test_stale_* tests know the passes that existed when they were written; this one
-knows all of them."""
+knows the passes that existed before the vote.  It does not know vc_hull_temporal, vc_hull_measure, vc_hull_thin, vc_hull_shell, the
+hull registers (vc_hull_keep, vc_hull_combine, vc_hull_compare), vc_hull_motion and vc_hull_warp, nor what vc_texture_render and
+vc_light_render make: tests/test_gpu_chain.py covers the registers and the motion field (family C of tests/chain_model.py) and the
+passes over a render's images (family D) in random chains, after every step."""
 import ctypes
 
 import numpy as np
