@@ -17,6 +17,10 @@
 //   records   u64 [S]                           {u32 idx, r, g, b, seen}, ascending idx
 //
 // There is no CPU path in this library: without a GPU vc_create fails (VC_ERR_NODEV).
+//
+// Layout: the kernels' headers, then the host side in dependency order.  The core (vc_ctx, the launch helpers, set-up, the carve step,
+// the pass frame) and the passes up to the set algebra stand in this file; every later family lives in a file of its own under host/,
+// included once where its code stood; behind them the foreground front end, the options and the multi-GPU calls, in this file again.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <dlfcn.h>
@@ -3850,893 +3854,15 @@ int vc_hull_compare(vc_ctx *ctx, uint32_t reg, uint32_t flags, vc_compare_stats_
     return VC_OK;
 }
 
-// ---- block motion between a kept hull and the current result, its warp and its colours (vc_motion.h; contract in include/voxcarve.h) ----
-constexpr uint64_t kMotionMaxBlocks = (uint64_t)kMaxScanBlocks * kScanBlock * 64u;   // a scan group is a wave of 64 blocks
-
-int vc_hull_motion(vc_ctx *ctx, uint32_t reg, uint32_t block, uint32_t apron, uint32_t search, uint32_t flags, vc_motion_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_motion: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_motion", "match", "motion", pass));
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_motion: flags must be 0 (got %u)", flags);
-    VC_TRY(kept_refusals(ctx, "vc_hull_motion", reg, true));
-    if (block != 4 && block != 8 && block != 16) return fail(ctx, VC_ERR_ARG, "vc_hull_motion: block edge %u, expected 4, 8 or 16", block);
-    if (apron > 16) return fail(ctx, VC_ERR_ARG, "vc_hull_motion: apron %u not in 0..16", apron);
-    if (search < 1 || search > 8) return fail(ctx, VC_ERR_ARG, "vc_hull_motion: search range %u not in 1..8", search);
-    if (block + 2 * apron + 2 * search > 64)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_motion: block + 2 apron + 2 search = %u exceeds the 64 bits of a row", block + 2 * apron + 2 * search);
-    StepBuf &cur = *pass.cur;
-    const uint64_t n = pass.n, nwords = pass.nwords;
-    VC_TRY(merge_refuse_index(ctx, "vc_hull_motion", n));
-    vc_ctx::Motion &M = ctx->motion;
-    const vc_ctx::Kept &B = ctx->setops.reg[reg];
-    MotionGrid g;
-    memset(&g, 0, sizeof g);
-    g.nx = ctx->nx; g.ny = ctx->ny; g.nz = ctx->nz;
-    g.nbx = (g.nx + block - 1) / block; g.nby = (g.ny + block - 1) / block; g.nbz = (g.nz + block - 1) / block;
-    const uint64_t nblocks = (uint64_t)g.nbx * g.nby * g.nbz;
-    if (!n || !nblocks || nblocks > kMotionMaxBlocks)
-        return fail(ctx, VC_ERR_ARG, "vc_hull_motion: %llu blocks of edge %u, at most %llu", (unsigned long long)nblocks, block,
-                    (unsigned long long)kMotionMaxBlocks);
-    if (B.words.cap < nwords) return fail(ctx, VC_ERR_INTERNAL, "vc_hull_motion: register %u holds %llu of %llu occupancy words", reg,
-                                          (unsigned long long)B.words.cap, (unsigned long long)nwords);
-    g.nblocks = (uint32_t)nblocks; g.b = block; g.a = apron; g.s = search; g.nwords = nwords; g.n = n;
-    const uint32_t ngroups = (uint32_t)((nblocks + 63) / 64);
-    VC_TRY(pass_begin(ctx));
-    M.stamp = kNever;
-    VC_TRY(ensure(ctx, M.counts, (size_t)nblocks));
-    VC_TRY(ensure(ctx, M.vec, (size_t)nblocks));
-    VC_TRY(ensure(ctx, M.mask, ngroups));
-    VC_TRY(ensure(ctx, M.ctr, 8));
-    VC_TRY(ensure(ctx, ctx->d_rscan, ngroups));
-    VC_HIP(ctx, ensure_pinned(M.h, 8));
-    VC_TRY(pass_start(ctx, pass, kWordsAlways));
-    VC_HIP(ctx, hipMemsetAsync(M.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(M.vec.ptr, 0, (size_t)nblocks * sizeof(uint32_t), ctx->stream));
-    MotionListParams lp;
-    memset(&lp, 0, sizeof lp);
-    lp.a = cur.words.ptr; lp.b = B.words.ptr; lp.g = g; lp.ngroups = ngroups;
-    lp.counts = M.counts.ptr; lp.mask = M.mask.ptr; lp.cnt = ctx->d_rscan.cnt.ptr;
-    hipLaunchKernelGGL(k_motion_list, dim3((ngroups + kMotionBlock / 64 - 1) / (kMotionBlock / 64)), dim3(kMotionBlock), 0, ctx->stream, lp);
-    VC_HIP(ctx, hipGetLastError());
-    // the read-back in the middle: the listed blocks size the rows and the matching launch
-    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_rscan, ctx->d_rscan.cnt.ptr, ngroups, ctx->h_res + 0));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t listed = ctx->h_res[0];
-    if (listed > nblocks) return fail(ctx, VC_ERR_HIP, "vc_hull_motion: %llu of %llu blocks listed", (unsigned long long)listed, (unsigned long long)nblocks);
-    VC_TRY(ensure(ctx, M.rows, (size_t)listed));
-    if (listed) {
-        hipLaunchKernelGGL(k_motion_rank, dim3((uint32_t)((nblocks + kMotionBlock - 1) / kMotionBlock)), dim3(kMotionBlock), 0, ctx->stream, g, ngroups,
-                           (const uint32_t *)M.counts.ptr, (const uint64_t *)M.mask.ptr, (const uint32_t *)ctx->d_rscan.off.ptr,
-                           (const uint64_t *)ctx->d_rscan.boff.ptr, M.rows.ptr, listed);
-        VC_HIP(ctx, hipGetLastError());
-        MotionMatchParams mp;
-        memset(&mp, 0, sizeof mp);
-        mp.a = cur.words.ptr; mp.b = B.words.ptr; mp.g = g; mp.rows = M.rows.ptr; mp.listed = listed; mp.vec = M.vec.ptr; mp.ctr = M.ctr.ptr;
-        const uint32_t W = block + 2 * apron, R = W + 2 * search;
-        const size_t lds = ((size_t)R * R + (size_t)W * W) * sizeof(uint64_t);       // at most 51 200 bytes (16 / 16 / 8: R = 64, W = 48)
-        hipLaunchKernelGGL(k_motion_match, dim3((uint32_t)listed), dim3(kMotionBlock), lds, ctx->stream, mp);
-        VC_HIP(ctx, hipGetLastError());
-    }
-    VC_TRY(pass_stop(ctx, pass));
-    VC_HIP(ctx, hipMemcpyAsync(M.h.ptr, M.ctr.ptr, kMotionCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->motion_ms));
-    if (M.h[0] > listed || M.h[1] > listed || M.h[2] > listed || M.h[4] > M.h[3])
-        return fail(ctx, VC_ERR_HIP, "vc_hull_motion: %llu moved, %llu unique, %llu clipped of %llu listed blocks, cost %llu -> %llu", (unsigned long long)M.h[0],
-                    (unsigned long long)M.h[1], (unsigned long long)M.h[2], (unsigned long long)listed, (unsigned long long)M.h[3], (unsigned long long)M.h[4]);
-    stats->blocks = nblocks; stats->listed = listed; stats->moved = M.h[0]; stats->unique = M.h[1]; stats->clipped = M.h[2];
-    stats->cost0_sum = M.h[3]; stats->cost_sum = M.h[4]; stats->a = pass.S; stats->b = B.count;
-    M.g = g; M.listed = listed; M.reg = reg;
-    M.stamp = ctx->result_gen;
-    return VC_OK;
-}
-
-// The field of the last vc_hull_motion is current: made on this result, against a register nobody has written since.
-static int motion_current(vc_ctx *ctx, const char *what)
-{
-    if (!ctx->carved || !ctx->current(ctx->motion.stamp))
-        return fail(ctx, VC_ERR_ARG, "%s: no motion field: call vc_hull_motion on the current carve result", what);
-    return VC_OK;
-}
-
-int vc_fetch_motion(vc_ctx *ctx, vc_motion_t *rows, uint64_t *count)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(motion_current(ctx, "vc_fetch_motion"));
-    static_assert(sizeof(vc_motion_t) == sizeof(MotionRow), "vc_motion_t");
-    if (count) *count = ctx->motion.listed;
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (rows && ctx->motion.listed)
-        VC_HIP(ctx, hipMemcpy(rows, ctx->motion.rows.ptr, (size_t)ctx->motion.listed * sizeof(vc_motion_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_hull_warp(vc_ctx *ctx, uint32_t src, uint32_t dst, uint32_t flags, vc_warp_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_warp: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_warp", "warp", "motion", pass));
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_warp: flags must be 0 (got %u)", flags);
-    VC_TRY(kept_refusals(ctx, "vc_hull_warp", src, true));
-    VC_TRY(kept_refusals(ctx, "vc_hull_warp", dst, false));
-    if (src == dst) return fail(ctx, VC_ERR_ARG, "vc_hull_warp: source and target are both register %u", src);
-    VC_TRY(motion_current(ctx, "vc_hull_warp"));
-    vc_ctx::Motion &M = ctx->motion;
-    if (M.reg != src) return fail(ctx, VC_ERR_ARG, "vc_hull_warp: the motion field was made against register %u, not %u", M.reg, src);
-    StepBuf &cur = *pass.cur;
-    const uint64_t n = pass.n, nwords = pass.nwords, npad = (nwords + 1) & ~1ull;
-    VC_TRY(merge_refuse_index(ctx, "vc_hull_warp", n));
-    const vc_ctx::Kept &B = ctx->setops.reg[src];
-    if (M.g.n != n || M.g.nwords != nwords || B.words.cap < nwords)
-        return fail(ctx, VC_ERR_INTERNAL, "vc_hull_warp: the field's grid of %llu voxels is not the result's %llu", (unsigned long long)M.g.n, (unsigned long long)n);
-    VC_TRY(pass_begin(ctx));
-    vc_ctx::Kept k;                              // built beside the register, which stays as it is until the prediction is whole
-    VC_TRY(ensure(ctx, k.words, (size_t)npad));
-    VC_TRY(ensure(ctx, M.ctr, 8));
-    VC_HIP(ctx, ensure_pinned(M.h, 8));
-    VC_TRY(pass_start(ctx, pass, kWordsAlways));
-    VC_HIP(ctx, hipMemsetAsync(M.ctr.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    MotionWarpParams wp;
-    memset(&wp, 0, sizeof wp);
-    wp.a = cur.words.ptr; wp.b = B.words.ptr; wp.g = M.g; wp.vec = M.vec.ptr; wp.out = k.words.ptr; wp.npad = npad; wp.ctr = M.ctr.ptr;
-    hipLaunchKernelGGL(k_motion_warp, dim3((uint32_t)((npad + kSetopBlock - 1) / kSetopBlock)), dim3(kSetopBlock), 0, ctx->stream, wp);
-    VC_HIP(ctx, hipGetLastError());
-    VC_TRY(pass_stop(ctx, pass));
-    VC_HIP(ctx, hipMemcpyAsync(M.h.ptr, M.ctr.ptr, kWarpCounters * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->warp_ms));
-    if (M.h[0] > n || M.h[1] > M.h[0] || M.h[1] > pass.S)
-        return fail(ctx, VC_ERR_HIP, "vc_hull_warp: %llu predicted voxels, %llu of them among %llu survivors", (unsigned long long)M.h[0],
-                    (unsigned long long)M.h[1], (unsigned long long)pass.S);
-    stats->warped = M.h[0]; stats->common = M.h[1]; stats->a = pass.S;
-    k.count = M.h[0]; k.used = true; k.has_rec = false;
-    ctx->setops.reg[dst] = std::move(k);
-    return VC_OK;
-}
-
-int vc_paint_motion(vc_ctx *ctx)
-{
-    if (!ctx) return VC_ERR_ARG;
-    VC_TRY(motion_current(ctx, "vc_paint_motion"));
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    if (!ctx->survivors) return VC_OK;
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_motion_paint, dim3((uint32_t)((ctx->survivors + kMotionBlock - 1) / kMotionBlock)), dim3(kMotionBlock), 0, ctx->stream,
-                       cur.records.ptr, ctx->survivors, ctx->motion.g, (const uint32_t *)ctx->motion.vec.ptr);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VC_OK;
-}
-
-// ---- ray-cast images of the current carve result (vc_render.h; contract in include/voxcarve.h) ----
-int vc_render(vc_ctx *ctx, uint32_t n_views, const vc_view_t *views, uint32_t H, uint32_t W, const uint8_t *shade,
-              const uint8_t *background, uint32_t flags, vc_render_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_render: flags must be 0 (got %u)", flags);
-    if (n_views == 0 || !views) return fail(ctx, VC_ERR_ARG, "vc_render: no views");
-    if (H < 1 || H > 16384 || W < 1 || W > 16384) return fail(ctx, VC_ERR_ARG, "vc_render: image size %ux%u not in 1..16384", H, W);
-    const uint64_t npix = (uint64_t)n_views * H * W;
-    if (npix > (1ull << 28)) return fail(ctx, VC_ERR_ARG, "vc_render: %u views of %ux%u are %llu pixels, more than 2^28", n_views, H, W,
-                                         (unsigned long long)npix);
-    for (uint32_t k = 0; k < n_views; ++k) {
-        const double *q = views[k].K;                               // the 21 doubles of the view
-        for (int j = 0; j < 21; ++j)
-            if (!std::isfinite(q[j])) return fail(ctx, VC_ERR_ARG, "vc_render: view %u has a parameter that is not finite", k);
-        if (!(views[k].K[0] > 0.0) || !(views[k].K[1] > 0.0))
-            return fail(ctx, VC_ERR_ARG, "vc_render: view %u has fx %g, fy %g (both must be > 0)", k, views[k].K[0], views[k].K[1]);
-    }
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_render", "render", "rendering", pass));
-    if (ctx->nx < 2 || ctx->ny < 2 || ctx->nz < 2)
-        return fail(ctx, VC_ERR_ARG, "vc_render: grid %ux%ux%u has an axis shorter than 2", ctx->nx, ctx->ny, ctx->nz);
-    static_assert(sizeof(vc_view_t) == sizeof(RenderView), "vc_view_t is the device's view");
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    ctx->render.valid = false; ctx->render.stamp = kNever; ctx->normals.sh_valid = false; ctx->texture.valid = false;
-    ctx->light.valid = false; ctx->render.map_built = false;
-    VC_TRY(ensure(ctx, ctx->render.idx, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->render.depth, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->render.rgbf, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->render.views, n_views));
-    VC_TRY(ensure(ctx, ctx->render.ctr, 3));
-    const uint32_t nb[3] = {(ctx->nx + kRenderB - 1) / kRenderB, (ctx->ny + kRenderB - 1) / kRenderB, (ctx->nz + kRenderB - 1) / kRenderB};
-    const uint64_t nblocks = (uint64_t)nb[0] * nb[1] * nb[2];
-    VC_TRY(ensure(ctx, ctx->render.map, (size_t)((nblocks + 63) / 64)));
-    VC_TRY(pass_start(ctx, pass, kWordsAlways));
-    VC_HIP(ctx, hipMemcpyAsync(ctx->render.views.ptr, views, (size_t)n_views * sizeof(vc_view_t), hipMemcpyHostToDevice, ctx->stream));
-    VC_HIP(ctx, hipMemsetAsync(ctx->render.ctr.ptr, 0, 3 * sizeof(unsigned long long), ctx->stream));
-    RenderParams p;
-    memset(&p, 0, sizeof p);
-    p.words = cur.words.ptr;
-    p.bmap = ctx->render.map.ptr;
-    p.records = cur.records.ptr;
-    p.S = ctx->survivors;
-    p.views = ctx->render.views.ptr;
-    p.idx = ctx->render.idx.ptr; p.depth = ctx->render.depth.ptr; p.rgbf = ctx->render.rgbf.ptr;
-    p.ctr = ctx->render.ctr.ptr;
-    const uint32_t n3[3] = {ctx->nx, ctx->ny, ctx->nz};
-    for (int a = 0; a < 3; ++a) {                // item 1 (this file is built without contraction too)
-        p.n[a] = n3[a];
-        p.nb[a] = nb[a];
-        p.s[a] = (ctx->bounds[2 * a + 1] - ctx->bounds[2 * a]) / (double)(n3[a] - 1);
-        p.e[a] = ctx->bounds[2 * a] - 0.5 * p.s[a];
-    }
-    p.H = H; p.W = W;
-    p.tiles_x = (W + 7) / 8;
-    p.tiles_per_view = p.tiles_x * ((H + 7) / 8);
-    p.n_tiles = p.tiles_per_view * n_views;      // <= 2^28 views x tiles of one pixel
-    for (int f = 0; f < 7; ++f) p.shade[f] = shade ? shade[f] : 255u;
-    p.bg = background ? (uint32_t)background[0] | ((uint32_t)background[1] << 8) | ((uint32_t)background[2] << 16) : 0u;
-    p.skip = ctx->render.blocks ? 1u : 0u;
-    if (p.skip) {
-        hipLaunchKernelGGL(k_render_map, dim3((uint32_t)((nblocks + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, ctx->stream,
-                           (const uint64_t *)cur.words.ptr, ctx->render.map.ptr, ctx->nx, ctx->ny, ctx->nz, nb[0], nb[1], nblocks);
-        VC_HIP(ctx, hipGetLastError());
-        ctx->render.map_built = true;
-    }
-    hipLaunchKernelGGL(k_render, dim3((p.n_tiles + kRenderBlock / 64 - 1) / (kRenderBlock / 64)), dim3(kRenderBlock), 0, ctx->stream, p);
-    VC_HIP(ctx, hipGetLastError());
-    VC_TRY(pass_stop(ctx, pass));                   // (the counters' read-back is not part of the render's time)
-    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->render.ctr.ptr, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, stats ? &stats->render_ms : nullptr));
-    ctx->render.valid = true; ctx->render.stamp = ctx->result_gen;
-    ctx->render.n_views = n_views; ctx->render.H = H; ctx->render.W = W;
-    if (ctx->h_res[0] > npix) return fail(ctx, VC_ERR_HIP, "vc_render: %llu hits among %llu pixels", (unsigned long long)ctx->h_res[0],
-                                          (unsigned long long)npix);
-    if (stats) {
-        stats->pixels = npix;
-        stats->hits = ctx->h_res[0];
-        stats->cells_visited = ctx->h_res[1];
-        stats->blocks_skipped = ctx->h_res[2];
-    }
-    return VC_OK;
-}
-
-int vc_fetch_render(vc_ctx *ctx, uint32_t view, uint32_t *idx, float *depth, uint8_t *rgb, uint8_t *face)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!ctx->render.valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: no images: call vc_render first");
-    if (view >= ctx->render.n_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_render: view %u not in [0,%u)", view, ctx->render.n_views);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->render.H * ctx->render.W, off = (size_t)view * HW;
-    if (idx) VC_HIP(ctx, hipMemcpy(idx, ctx->render.idx.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (depth) VC_HIP(ctx, hipMemcpy(depth, ctx->render.depth.ptr + off, HW * sizeof(float), hipMemcpyDeviceToHost));
-    if (rgb || face) {
-        std::vector<uint32_t> px(HW);
-        VC_HIP(ctx, hipMemcpy(px.data(), ctx->render.rgbf.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < HW; ++k) {
-            const uint32_t q = px[k];
-            if (rgb) { rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16); }
-            if (face) face[k] = (uint8_t)(q >> 24);
-        }
-    }
-    return VC_OK;
-}
-
-int vc_fetch_visibility(vc_ctx *ctx, uint16_t *vis)
-{
-    if (!ctx || !vis) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->current(ctx->visible.stamp)) return fail(ctx, VC_ERR_ARG, "no visibility: call vc_color_visible on the current carve result");
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->survivors) VC_HIP(ctx, hipMemcpy(vis, ctx->visible.mask.ptr, ctx->survivors * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_fetch_depth(vc_ctx *ctx, uint32_t cam, float *out)
-{
-    if (!ctx || !out) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->current(ctx->visible.stamp)) return fail(ctx, VC_ERR_ARG, "no depth maps: call vc_color_visible on the current carve result");
-    if (cam >= ctx->C) return fail(ctx, VC_ERR_ARG, "camera %u not in [0,%u)", cam, ctx->C);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->H * ctx->W;
-    VC_HIP(ctx, hipMemcpy(out, ctx->visible.zmap.ptr + (size_t)cam * HW, HW * sizeof(float), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-// ---- marching cubes over the dense ON/OFF volume (reference consumer voxel_reconstruction.py:127-163) ----
-int vc_marching_cubes(vc_ctx *ctx, const uint8_t *volume_bits, uint32_t d0, uint32_t d1, uint32_t d2, float level,
-                      uint64_t *n_verts, uint64_t *n_faces)
-{
-    if (!ctx || !n_verts || !n_faces) return VC_ERR_ARG;
-    *n_verts = *n_faces = 0;
-    ctx->mc_valid = false;
-    if (d0 == 0 || d1 == 0 || d2 == 0) return fail(ctx, VC_ERR_ARG, "volume dimensions must be >= 1");
-    if (!(level >= 0.0f && level < 1.0f)) return fail(ctx, VC_ERR_ARG, "level %g not in [0, 1): ON is 1, OFF is 0", (double)level);
-    const uint64_t n = (uint64_t)d0 * d1 * d2;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "volume of %llu elements exceeds the u32 index", (unsigned long long)n);
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t nwords = (uint32_t)((n + 63) / 64), ngroups = (nwords + 63) / 64;
-    const uint32_t nscan = (ngroups + kScanBlock - 1) / kScanBlock;
-    McParams p;
-    memset(&p, 0, sizeof p);
-    if (volume_bits) {
-        VC_TRY(ensure(ctx, ctx->d_mcbits, (size_t)nwords));
-        VC_HIP(ctx, hipMemsetAsync(ctx->d_mcbits.ptr, 0, (size_t)nwords * sizeof(uint64_t), ctx->stream));
-        VC_HIP(ctx, hipMemcpyAsync(ctx->d_mcbits.ptr, volume_bits, (size_t)((n + 7) / 8), hipMemcpyHostToDevice, ctx->stream));
-        p.bits = ctx->d_mcbits.ptr;
-    } else {
-        if (!ctx->carved) return fail(ctx, VC_ERR_ARG, "no carve result: run vc_carve first or pass a volume");
-        if (n != ctx->n_voxels()) return fail(ctx, VC_ERR_ARG, "%u x %u x %u is not the %llu voxels of the carved slab", d0, d1, d2,
-                                              (unsigned long long)ctx->n_voxels());
-        StepBuf &cur = ctx->sb[ctx->cur];
-        VC_TRY(densify_words(ctx, cur));
-        p.bits = cur.words.ptr;
-    }
-    VC_TRY(ensure(ctx, ctx->d_mcx, (size_t)nwords * 3));
-    VC_TRY(ensure(ctx, ctx->d_mcwbase, (size_t)nwords));
-    VC_TRY(ensure(ctx, ctx->d_mcv, ngroups));
-    VC_TRY(ensure(ctx, ctx->d_mct, ngroups));
-    VC_TRY(ensure_exchange_scratch(ctx, 1));
-    p.n = n; p.d0 = d0; p.d1 = d1; p.d2 = d2; p.nwords = nwords; p.ngroups = ngroups;
-    p.x = ctx->d_mcx.ptr; p.wbase = ctx->d_mcwbase.ptr; p.gv = ctx->d_mcv.cnt.ptr; p.gt = ctx->d_mct.cnt.ptr;
-    p.gvoff = ctx->d_mcv.off.ptr; p.gtoff = ctx->d_mct.off.ptr; p.bvoff = ctx->d_mcv.boff.ptr; p.btoff = ctx->d_mct.boff.ptr;
-    p.level = level;
-    const dim3 grid((ngroups + 3) / 4), block(kBlock);
-    hipLaunchKernelGGL(k_mc_count, grid, block, 0, ctx->stream, p);
-    VC_HIP(ctx, hipGetLastError());
-    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mcv, ctx->d_mcv.cnt.ptr, ngroups, ctx->h_xtotal));
-    VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mct, ctx->d_mct.cnt.ptr, ngroups, ctx->h_xtotal + 1));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)nscan;
-    const uint64_t V = ctx->h_xtotal[0], F = ctx->h_xtotal[1];
-    if (V > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "%llu vertices exceed the u32 vertex number", (unsigned long long)V);
-    VC_TRY(ensure(ctx, ctx->d_mcverts, (size_t)(3 * V + 3)));
-    VC_TRY(ensure(ctx, ctx->d_mcfaces, (size_t)(3 * F + 3)));
-    p.verts = ctx->d_mcverts.ptr; p.faces = ctx->d_mcfaces.ptr; p.vcap = V; p.fcap = F;
-    hipLaunchKernelGGL(k_mc_verts, grid, block, 0, ctx->stream, p);
-    hipLaunchKernelGGL(k_mc_faces, grid, block, 0, ctx->stream, p);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->mc_verts = V; ctx->mc_faces = F; ctx->mc_valid = true;
-    *n_verts = V; *n_faces = F;
-    return VC_OK;
-}
-
-int vc_fetch_mesh(vc_ctx *ctx, float *verts, uint32_t *faces)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!ctx->mc_valid) return fail(ctx, VC_ERR_ARG, "no mesh: call vc_marching_cubes");
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (verts && ctx->mc_verts) VC_HIP(ctx, hipMemcpy(verts, ctx->d_mcverts.ptr, ctx->mc_verts * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (faces && ctx->mc_faces) VC_HIP(ctx, hipMemcpy(faces, ctx->d_mcfaces.ptr, ctx->mc_faces * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-// ---- silhouette-refined surface mesh of the current carve result (vc_surface.h; contract in include/voxcarve.h) ----
-int vc_surface_mesh(vc_ctx *ctx, uint32_t steps, uint32_t flags, vc_surface_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    ctx->surface.valid = false; ctx->surface.stamp = kNever;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: flags must be 0 (got %u)", flags);
-    if (steps > kSurfMaxSteps) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: steps %u not in [0, %u]", steps, kSurfMaxSteps);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_surface_mesh", "colour the mesh from", "meshing", pass));
-    StepBuf &cur = *pass.cur;
-    if (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen)
-        return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: frame set %u has been prepared again since the carve: its masks are not the ones "
-                    "the occupancy came from", cur.slot);
-    const uint64_t n = pass.n;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: %llu voxels exceed the u32 index", (unsigned long long)n);
-    const Slot &s = ctx->slots[cur.slot];
-    VC_TRY(pass_begin(ctx));
-    VC_TRY(pass_start(ctx, pass, kWordsAlways));
-    uint64_t V = 0, F = 0;
-    McParams p;
-    memset(&p, 0, sizeof p);
-    if (n) {
-        // 1 topology: vc_marching_cubes(NULL, nz, nx, ny)'s counts and scans (its scratch, not its mesh)
-        const uint32_t nwords = (uint32_t)((n + 63) / 64), ngroups = (nwords + 63) / 64;
-        VC_TRY(ensure(ctx, ctx->d_mcx, (size_t)nwords * 3));
-        VC_TRY(ensure(ctx, ctx->d_mcwbase, (size_t)nwords));
-        VC_TRY(ensure(ctx, ctx->d_mcv, ngroups));
-        VC_TRY(ensure(ctx, ctx->d_mct, ngroups));
-        p.bits = cur.words.ptr;
-        p.n = n; p.d0 = ctx->nz; p.d1 = ctx->nx; p.d2 = ctx->ny; p.nwords = nwords; p.ngroups = ngroups;
-        p.x = ctx->d_mcx.ptr; p.wbase = ctx->d_mcwbase.ptr; p.gv = ctx->d_mcv.cnt.ptr; p.gt = ctx->d_mct.cnt.ptr;
-        p.gvoff = ctx->d_mcv.off.ptr; p.gtoff = ctx->d_mct.off.ptr; p.bvoff = ctx->d_mcv.boff.ptr; p.btoff = ctx->d_mct.boff.ptr;
-        hipLaunchKernelGGL(k_mc_count, dim3((ngroups + 3) / 4), dim3(kBlock), 0, ctx->stream, p);
-        VC_HIP(ctx, hipGetLastError());
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mcv, ctx->d_mcv.cnt.ptr, ngroups, ctx->h_res));
-        VC_TRY(scan_counts(ctx, ctx->stream, ctx->d_mct, ctx->d_mct.cnt.ptr, ngroups, ctx->h_res + 1));
-        // the one read-back in the middle: the counts size the mesh
-        VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        V = ctx->h_res[0]; F = ctx->h_res[1];
-        if (V > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_surface_mesh: %llu vertices exceed the u32 vertex number", (unsigned long long)V);
-    }
-    VC_TRY(ensure(ctx, ctx->surface.edges, (size_t)(V + 1)));
-    VC_TRY(ensure(ctx, ctx->surface.verts, (size_t)(3 * V + 3)));
-    VC_TRY(ensure(ctx, ctx->surface.faces, (size_t)(3 * F + 3)));
-    VC_TRY(ensure(ctx, ctx->surface.rgb, (size_t)(3 * V + 3)));
-    VC_TRY(ensure(ctx, ctx->surface.refined, (size_t)(V + 1)));
-    VC_TRY(ensure(ctx, ctx->surface.ctr, 2));
-    VC_HIP(ctx, hipMemsetAsync(ctx->surface.ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-    if (V) {
-        // 2 edge entries in vertex order, the faces (k_mc_faces reads the word bases k_surf_edges writes)
-        p.faces = ctx->surface.faces.ptr; p.vcap = V; p.fcap = F;
-        const dim3 grid((p.ngroups + 3) / 4), block(kBlock);
-        hipLaunchKernelGGL(k_surf_edges, grid, block, 0, ctx->stream, p, ctx->surface.edges.ptr);
-        hipLaunchKernelGGL(k_mc_faces, grid, block, 0, ctx->stream, p);
-        VC_HIP(ctx, hipGetLastError());
-        // 3 the refinement and the colours
-        SurfParams q;
-        memset(&q, 0, sizeof q);
-        q.edges = ctx->surface.edges.ptr;
-        q.records = cur.records.ptr;
-        q.S = ctx->survivors;
-        q.V = V;
-        q.xs = ctx->d_axes.ptr; q.ys = q.xs + ctx->nx; q.zs = q.ys + ctx->ny;
-        q.bits = s.bits.ptr;
-        q.mwords = ctx->mwords; q.C = ctx->C; q.H = ctx->H; q.W = ctx->W;
-        q.m = cur.min_views; q.steps = steps; q.order = ctx->surface.order ? 1u : 0u;
-        q.nx = ctx->nx; q.ny = ctx->ny;
-        q.verts = ctx->surface.verts.ptr; q.rgb = ctx->surface.rgb.ptr; q.refined = ctx->surface.refined.ptr;
-        q.ctr = ctx->surface.ctr.ptr;
-        memcpy(q.cam, ctx->cams, sizeof(CamDev) * ctx->C);
-        hipLaunchKernelGGL(k_surf_refine, dim3((uint32_t)((V + kSurfBlock - 1) / kSurfBlock)), dim3(kSurfBlock), 0, ctx->stream, q);
-        VC_HIP(ctx, hipGetLastError());
-    }
-    VC_TRY(pass_stop(ctx, pass));                   // (the counters' read-back is not part of the mesh's time)
-    VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->surface.ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->surface_ms));
-    const uint64_t refined = ctx->h_res[0];
-    if (refined > V) return fail(ctx, VC_ERR_HIP, "vc_surface_mesh: %llu refined among %llu vertices", (unsigned long long)refined,
-                                 (unsigned long long)V);
-    ctx->surface.n_verts = V; ctx->surface.n_faces = F; ctx->surface.valid = true; ctx->surface.stamp = ctx->result_gen;
-    stats->n_verts = V;
-    stats->n_faces = F;
-    stats->refined = refined;
-    stats->unrefined = V - refined;
-    stats->point_tests = ctx->h_res[1];
-    return VC_OK;
-}
-
-int vc_fetch_surface_mesh(vc_ctx *ctx, double *verts, uint32_t *faces, uint8_t *rgb, uint8_t *refined)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!ctx->surface.valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_surface_mesh: no mesh: call vc_surface_mesh first");
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t V = (size_t)ctx->surface.n_verts, F = (size_t)ctx->surface.n_faces;
-    if (verts && V) VC_HIP(ctx, hipMemcpy(verts, ctx->surface.verts.ptr, V * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (faces && F) VC_HIP(ctx, hipMemcpy(faces, ctx->surface.faces.ptr, F * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (rgb && V) VC_HIP(ctx, hipMemcpy(rgb, ctx->surface.rgb.ptr, V * 3, hipMemcpyDeviceToHost));
-    if (refined && V) VC_HIP(ctx, hipMemcpy(refined, ctx->surface.refined.ptr, V, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-// ---- surface normals of the current carve result, shaded renders, mesh normals (vc_normals.h; contract in include/voxcarve.h) ----
-int vc_hull_normals(vc_ctx *ctx, uint64_t r2, uint32_t flags, vc_normals_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: flags must be 0 (got %u)", flags);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_hull_normals", "give normals to", "normal estimation", pass));
-    uint64_t q[3];
-    VC_TRY(dist_metric(ctx, "vc_hull_normals", q));
-    // item 2: the ball's extents and its rows (dx, dz) with their y half-extent
-    const uint64_t root = isqrt_u64(r2);
-    uint32_t ext[3];
-    for (int a = 0; a < 3; ++a) {
-        const uint64_t e = root / q[a];
-        if (e > kNrmMaxExt)
-            return fail(ctx, VC_ERR_ARG, "vc_hull_normals: r2 = %llu um^2 reaches %llu cells along %c, more than %u", (unsigned long long)r2,
-                        (unsigned long long)e, "xyz"[a], kNrmMaxExt);
-        ext[a] = (uint32_t)e;
-    }
-    if (!(ext[0] | ext[1] | ext[2])) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: the ball of r2 = %llu um^2 holds no voxel offset", (unsigned long long)r2);
-    std::vector<uint32_t> rows;
-    uint64_t offsets = 0;
-    for (int32_t dz = -(int32_t)ext[2]; dz <= (int32_t)ext[2]; ++dz)
-        for (int32_t dx = -(int32_t)ext[0]; dx <= (int32_t)ext[0]; ++dx) {
-            const uint64_t used = (q[0] * (uint64_t)std::abs(dx)) * (q[0] * (uint64_t)std::abs(dx)) +
-                                  (q[2] * (uint64_t)std::abs(dz)) * (q[2] * (uint64_t)std::abs(dz));
-            if (used > r2) continue;
-            const uint32_t ky = (uint32_t)(isqrt_u64(r2 - used) / q[1]);         // <= ext[1]
-            if (ky == 0 && dx == 0 && dz == 0) continue;                          // the voxel itself alone
-            rows.push_back(((uint32_t)dx & 255u) | (((uint32_t)dz & 255u) << 8) | (ky << 16));
-            offsets += 2ull * ky + ((dx == 0 && dz == 0) ? 0u : 1u);
-        }
-    const uint64_t S = pass.S, n = pass.n, nwords = pass.nwords;
-    if (n > 0xffffffffull) return fail(ctx, VC_ERR_ARG, "vc_hull_normals: %llu voxels exceed the u32 index", (unsigned long long)n);
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    ctx->normals.stamp = kNever;
-    if (S) {
-        VC_TRY(ensure(ctx, ctx->d_rscan, word_groups(nwords)));
-        VC_TRY(ensure(ctx, ctx->d_woff, (size_t)nwords));
-        VC_TRY(ensure(ctx, ctx->normals.rows, rows.size()));
-        VC_TRY(ensure(ctx, ctx->normals.out, (size_t)S));
-        VC_TRY(ensure(ctx, ctx->normals.ctr, 2));
-    }
-    VC_TRY(pass_start(ctx, pass));
-    ctx->h_res[0] = ctx->h_res[1] = 0;
-    if (S) {
-        VC_HIP(ctx, hipMemcpyAsync(ctx->normals.rows.ptr, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->normals.out.ptr, 0, (size_t)S * sizeof(short4), ctx->stream));
-        VC_HIP(ctx, hipMemsetAsync(ctx->normals.ctr.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        VC_TRY(word_offsets(ctx, cur, nwords, ctx->d_woff, ctx->h_res + 2));
-        NrmParams p;
-        memset(&p, 0, sizeof p);
-        p.words = cur.words.ptr; p.woff = ctx->d_woff.ptr; p.rows = ctx->normals.rows.ptr;
-        p.out = ctx->normals.out.ptr; p.ctr = ctx->normals.ctr.ptr;
-        p.nwords = nwords; p.n = n; p.S = S;
-        for (int a = 0; a < 3; ++a) p.q[a] = (long long)q[a];
-        p.nrows = (uint32_t)rows.size(); p.nx = ctx->nx; p.ny = ctx->ny; p.nz = ctx->nz;
-        const uint64_t per_block = (uint64_t)(kNrmBlock / 64) * kNrmWords;
-        hipLaunchKernelGGL(k_normals, dim3((uint32_t)((nwords + per_block - 1) / per_block)), dim3(kNrmBlock), 0, ctx->stream, p);
-        VC_HIP(ctx, hipGetLastError());
-        VC_HIP(ctx, hipMemcpyAsync(ctx->h_res, ctx->normals.ctr.ptr, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    VC_TRY(pass_end(ctx, pass, &stats->normals_ms));
-    if (S && ctx->h_res[2] != S)
-        return fail(ctx, VC_ERR_HIP, "vc_hull_normals: the occupancy holds %llu voxels, the result %llu records", (unsigned long long)ctx->h_res[2],
-                    (unsigned long long)S);
-    if (ctx->h_res[0] > S || ctx->h_res[1] > ctx->h_res[0])
-        return fail(ctx, VC_ERR_HIP, "vc_hull_normals: %llu surface records, %llu of them without a normal, among %llu", (unsigned long long)ctx->h_res[0],
-                    (unsigned long long)ctx->h_res[1], (unsigned long long)S);
-    stats->survivors = S;
-    stats->surface = ctx->h_res[0];
-    stats->zero = ctx->h_res[1];
-    stats->offsets = offsets;
-    for (int a = 0; a < 3; ++a) { stats->q[a] = q[a]; stats->ext[a] = ext[a]; }
-    ctx->normals.stamp = ctx->result_gen;
-    ctx->normals.n = S;
-    return VC_OK;
-}
-
-int vc_fetch_record_normals(vc_ctx *ctx, int16_t *n4)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->current(ctx->normals.stamp)) return fail(ctx, VC_ERR_ARG, "no normals: call vc_hull_normals on the current carve result");
-    if (!n4) return VC_OK;                       // only asked whether the normals are valid
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->normals.n) VC_HIP(ctx, hipMemcpy(n4, ctx->normals.out.ptr, (size_t)ctx->normals.n * sizeof(short4), hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-int vc_shade_render(vc_ctx *ctx, const double *light, uint32_t ambient, uint32_t flags)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_shade_render: flags must be 0 (got %u)", flags);
-    if (!light) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no lights");
-    if (ambient > 255) return fail(ctx, VC_ERR_ARG, "vc_shade_render: ambient %u not in 0..255", ambient);
-    if (!ctx->carved || !ctx->current(ctx->normals.stamp)) return fail(ctx, VC_ERR_ARG, "vc_shade_render: no normals: call vc_hull_normals on the current carve result");
-    if (!ctx->render.valid || !ctx->current(ctx->render.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_shade_render: no images of the current carve result: call vc_render first");
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    for (uint32_t v = 0; v < ctx->render.n_views; ++v) {
-        const double *L = light + 3 * (size_t)v;
-        if (!std::isfinite(L[0]) || !std::isfinite(L[1]) || !std::isfinite(L[2]))
-            return fail(ctx, VC_ERR_ARG, "vc_shade_render: the light of view %u has a component that is not finite", v);
-        const double ll = (L[0] * L[0] + L[1] * L[1]) + L[2] * L[2];
-        if (!std::isnormal(ll)) return fail(ctx, VC_ERR_ARG, "vc_shade_render: the light of view %u has squared length %g", v, ll);
-    }
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->normals.sh_valid = false;
-    const uint64_t view_pix = (uint64_t)ctx->render.H * ctx->render.W, npix = view_pix * ctx->render.n_views;
-    VC_TRY(ensure(ctx, ctx->normals.sh_rgb, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->normals.sh_light, 3 * (size_t)ctx->render.n_views));
-    VC_HIP(ctx, hipMemcpyAsync(ctx->normals.sh_light.ptr, light, 3 * (size_t)ctx->render.n_views * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ShadeParams p;
-    memset(&p, 0, sizeof p);
-    p.idx = ctx->render.idx.ptr; p.rgbf = ctx->render.rgbf.ptr;
-    p.records = cur.records.ptr; p.normals = ctx->normals.out.ptr; p.light = ctx->normals.sh_light.ptr;
-    p.out = ctx->normals.sh_rgb.ptr;
-    p.S = ctx->survivors; p.npix = npix; p.view_pix = view_pix; p.ambient = ambient;
-    hipLaunchKernelGGL(k_shade, dim3((uint32_t)((npix + kNrmBlock - 1) / kNrmBlock)), dim3(kNrmBlock), 0, ctx->stream, p);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));             // (the lights are the caller's memory)
-    ctx->normals.sh_valid = true;
-    return VC_OK;
-}
-
-int vc_fetch_shaded(vc_ctx *ctx, uint32_t view, uint8_t *rgb)
-{
-    if (!ctx || !rgb) return VC_ERR_ARG;
-    if (!ctx->render.valid || !ctx->normals.sh_valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: no shaded images: call vc_shade_render first");
-    if (view >= ctx->render.n_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_shaded: view %u not in [0,%u)", view, ctx->render.n_views);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->render.H * ctx->render.W, off = (size_t)view * HW;
-    std::vector<uint32_t> px(HW);
-    VC_HIP(ctx, hipMemcpy(px.data(), ctx->normals.sh_rgb.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < HW; ++k) {
-        const uint32_t q = px[k];
-        rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16);
-    }
-    return VC_OK;
-}
-
-int vc_surface_normals(vc_ctx *ctx, int16_t *n4)
-{
-    if (!ctx || !n4) return VC_ERR_ARG;
-    if (!ctx->carved || !ctx->current(ctx->normals.stamp)) return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no normals: call vc_hull_normals on the current carve result");
-    if (!ctx->surface.valid || !ctx->current(ctx->surface.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_surface_normals: no mesh of the current carve result: call vc_surface_mesh first");
-    if (ctx->npending) return fail(ctx, VC_ERR_ARG, "carve steps are in flight: collect them with vc_carve_end first");
-    const uint64_t V = ctx->surface.n_verts;
-    if (!V) return VC_OK;
-    StepBuf &cur = ctx->sb[ctx->cur];
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    VC_TRY(ensure(ctx, ctx->normals.verts, (size_t)V));
-    hipLaunchKernelGGL(k_surf_normals, dim3((uint32_t)((V + kNrmBlock - 1) / kNrmBlock)), dim3(kNrmBlock), 0, ctx->stream,
-                       (const uint64_t *)ctx->surface.edges.ptr, V, (const uint64_t *)cur.records.ptr, ctx->survivors,
-                       (const short4 *)ctx->normals.out.ptr, ctx->nx, ctx->ny, ctx->normals.verts.ptr);
-    VC_HIP(ctx, hipGetLastError());
-    VC_HIP(ctx, hipMemcpyAsync(n4, ctx->normals.verts.ptr, (size_t)V * sizeof(short4), hipMemcpyDeviceToHost, ctx->stream));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return VC_OK;
-}
-
-// ---- free-viewpoint texturing of the last render (vc_texture.h; contract in include/voxcarve.h) ----
-// Reads the images of the last render, the carve's masks and threshold, the depth maps of the current vc_color_visible and the
-// images of `slot`; writes its own images only.
-int vc_texture_render(vc_ctx *ctx, uint32_t slot, uint32_t steps, double reach_mm, float depth_tolerance, uint32_t best,
-                      uint32_t sharpen, uint32_t filter, uint32_t flags, vc_texture_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_texture_render: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_texture_render: flags must be 0 (got %u)", flags);
-    if (steps > kTexMaxSteps) return fail(ctx, VC_ERR_ARG, "vc_texture_render: steps %u not in [0, %u]", steps, kTexMaxSteps);
-    if (!std::isfinite(reach_mm) || reach_mm < 0.0) return fail(ctx, VC_ERR_ARG, "vc_texture_render: reach %g mm is negative or not finite", reach_mm);
-    if (!std::isfinite(depth_tolerance) || depth_tolerance < 0.0f)
-        return fail(ctx, VC_ERR_ARG, "vc_texture_render: depth tolerance %g is negative or not finite", (double)depth_tolerance);
-    if (best < 1 || best > VC_MAX_CAMERAS) return fail(ctx, VC_ERR_ARG, "vc_texture_render: best %u not in [1, %d]", best, VC_MAX_CAMERAS);
-    if (sharpen > kTexMaxSharpen) return fail(ctx, VC_ERR_ARG, "vc_texture_render: sharpen %u not in [0, %u]", sharpen, kTexMaxSharpen);
-    if (filter > 1) return fail(ctx, VC_ERR_ARG, "vc_texture_render: filter %u is neither 0 (nearest) nor 1 (bilinear)", filter);
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_texture_render", "texture", "texturing", pass));
-    if (!ctx->render.valid || !ctx->current(ctx->render.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_texture_render: no images of the current carve result: call vc_render first");
-    if (!ctx->current(ctx->visible.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_texture_render: no depth maps of the current carve result: call vc_color_visible first");
-    if (slot >= ctx->slots.size() || !ctx->slots[slot].have_masks) return fail(ctx, VC_ERR_ARG, "vc_texture_render: no frame set in slot %u", slot);
-    Slot &s = ctx->slots[slot];
-    for (uint32_t c = 0; c < ctx->C; ++c)
-        if (c >= s.have_frame.size() || !s.have_frame[c]) return fail(ctx, VC_ERR_ARG, "vc_texture_render: camera %u has no frame in slot %u", c, slot);
-    StepBuf &cur = *pass.cur;
-    // the point test reads the masks the occupancy came from (vc_surface_mesh's rule); bringing new images of the carve's own frame
-    // set into the record layout below would prepare it again
-    if (steps > 0 && (cur.slot >= ctx->slots.size() || ctx->slots[cur.slot].gen != cur.slot_gen || (slot == cur.slot && !s.bits_valid)))
-        return fail(ctx, VC_ERR_ARG, "vc_texture_render: frame set %u has been prepared again since the carve, or has masks or images that "
-                    "wait for it: its masks are not the ones the occupancy came from (steps = 0 needs no masks)", cur.slot);
-    VC_TRY(pass_begin(ctx));
-    VC_HIP(ctx, ensure_pinned(ctx->texture.h, 5));
-    ctx->texture.valid = false;
-    const uint32_t V = ctx->render.n_views, H = ctx->render.H, W = ctx->render.W;
-    const uint64_t npix = (uint64_t)V * H * W;
-    VC_TRY(ensure(ctx, ctx->texture.rgbc, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->texture.depth, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->texture.best, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->texture.refined, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->texture.ctr, 5));
-    VC_TRY(visible_start(ctx, s, pass));            // the slot's images in the record layout; the occupancy words are not read
-    VC_HIP(ctx, hipMemsetAsync(ctx->texture.ctr.ptr, 0, 5 * sizeof(unsigned long long), ctx->stream));
-    TexParams p;
-    memset(&p, 0, sizeof p);
-    p.views = ctx->render.views.ptr;
-    p.idx = ctx->render.idx.ptr; p.depth = ctx->render.depth.ptr; p.rgbf = ctx->render.rgbf.ptr;
-    p.zmap = ctx->visible.zmap.ptr;
-    p.frames = s.frames.ptr;
-    p.bits = ctx->slots[cur.slot].bits.ptr;
-    p.rgbc = ctx->texture.rgbc.ptr; p.odepth = ctx->texture.depth.ptr; p.best = ctx->texture.best.ptr; p.refined = ctx->texture.refined.ptr;
-    p.ctr = ctx->texture.ctr.ptr;
-    p.H = H; p.W = W;
-    p.tiles_x = (W + 7) / 8;
-    p.tiles_per_view = p.tiles_x * ((H + 7) / 8);
-    p.n_tiles = p.tiles_per_view * V;
-    p.C = ctx->C; p.CH = ctx->H; p.CW = ctx->W; p.mwords = ctx->mwords;
-    p.m = cur.min_views; p.steps = steps; p.keep = best; p.sharpen = sharpen; p.filter = filter;
-    p.tol = depth_tolerance;
-    p.reach = reach_mm;
-    memcpy(p.cam, ctx->cams, sizeof(CamDev) * ctx->C);
-    for (uint32_t c = 0; c < ctx->C; ++c) {          // item 5: a camera's centre, as the render makes a view's origin
-        const double *R = ctx->cams[c].r, *t = ctx->cams[c].t;
-        for (int j = 0; j < 3; ++j) p.centre[c][j] = -((R[j] * t[0] + R[3 + j] * t[1]) + R[6 + j] * t[2]);
-    }
-    hipLaunchKernelGGL(k_texture, dim3((p.n_tiles + kTexBlock / 64 - 1) / (kTexBlock / 64)), dim3(kTexBlock), 0, ctx->stream, p);
-    VC_HIP(ctx, hipGetLastError());
-    VC_TRY(pass_stop(ctx, pass));                   // (the counters' read-back is not part of the pass's time)
-    VC_HIP(ctx, hipMemcpyAsync(ctx->texture.h, ctx->texture.ctr.ptr, 5 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->texture_ms));
-    const uint64_t *h = ctx->texture.h;
-    if (h[0] > npix || h[1] > h[0] || h[2] + h[3] != h[0])
-        return fail(ctx, VC_ERR_HIP, "vc_texture_render: %llu hits among %llu pixels, %llu refined, %llu textured, %llu fallback",
-                    (unsigned long long)h[0], (unsigned long long)npix, (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3]);
-    ctx->texture.valid = true;
-    stats->pixels = npix;
-    stats->hits = h[0];
-    stats->refined = h[1];
-    stats->textured = h[2];
-    stats->fallback = h[3];
-    stats->point_tests = h[4];
-    return VC_OK;
-}
-
-int vc_fetch_textured(vc_ctx *ctx, uint32_t view, uint8_t *rgb, float *depth, uint8_t *count, uint8_t *best_cam, uint8_t *refined)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!ctx->render.valid || !ctx->texture.valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_textured: no textured images: call vc_texture_render first");
-    if (view >= ctx->render.n_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_textured: view %u not in [0,%u)", view, ctx->render.n_views);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->render.H * ctx->render.W, off = (size_t)view * HW;
-    if (rgb || count) {
-        std::vector<uint32_t> px(HW);
-        VC_HIP(ctx, hipMemcpy(px.data(), ctx->texture.rgbc.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < HW; ++k) {
-            const uint32_t q = px[k];
-            if (rgb) { rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16); }
-            if (count) count[k] = (uint8_t)(q >> 24);
-        }
-    }
-    if (depth) VC_HIP(ctx, hipMemcpy(depth, ctx->texture.depth.ptr + off, HW * sizeof(float), hipMemcpyDeviceToHost));
-    if (best_cam) VC_HIP(ctx, hipMemcpy(best_cam, ctx->texture.best.ptr + off, HW, hipMemcpyDeviceToHost));
-    if (refined) VC_HIP(ctx, hipMemcpy(refined, ctx->texture.refined.ptr + off, HW, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
-// ---- lit renders: cast shadows, ambient occlusion and a floor for the last render (vc_light.h; contract in include/voxcarve.h) ----
-// Reads the images of the last render, the occupancy words, the block map and the records (smooth = 1: the normals); writes its
-// own images only.
-int vc_light_render(vc_ctx *ctx, const vc_light_t *light, uint32_t flags, vc_light_stats_t *stats)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!stats) return fail(ctx, VC_ERR_ARG, "vc_light_render: stats must not be NULL");
-    memset(stats, 0, sizeof *stats);
-    if (flags != 0) return fail(ctx, VC_ERR_ARG, "vc_light_render: flags must be 0 (got %u)", flags);
-    if (!light) return fail(ctx, VC_ERR_ARG, "vc_light_render: no light");
-    const vc_light_t &l = *light;
-    for (int j = 0; j < 4; ++j)
-        if (!std::isfinite(l.pos[j])) return fail(ctx, VC_ERR_ARG, "vc_light_render: the light has a component that is not finite");
-    if (l.pos[3] != 0.0 && l.pos[3] != 1.0)
-        return fail(ctx, VC_ERR_ARG, "vc_light_render: pos[3] = %g is neither 1 (a point in mm) nor 0 (a direction)", l.pos[3]);
-    if (l.pos[3] == 0.0 && !std::isnormal((l.pos[0] * l.pos[0] + l.pos[1] * l.pos[1]) + l.pos[2] * l.pos[2]))
-        return fail(ctx, VC_ERR_ARG, "vc_light_render: the light's direction has squared length %g",
-                    (l.pos[0] * l.pos[0] + l.pos[1] * l.pos[1]) + l.pos[2] * l.pos[2]);
-    if (l.ambient > 255) return fail(ctx, VC_ERR_ARG, "vc_light_render: ambient %u not in 0..255", l.ambient);
-    if (l.smooth > 1) return fail(ctx, VC_ERR_ARG, "vc_light_render: smooth %u is neither 0 nor 1", l.smooth);
-    if (!std::isfinite(l.ao_reach) || l.ao_reach < 0.0) return fail(ctx, VC_ERR_ARG, "vc_light_render: ao_reach %g is negative or not finite", l.ao_reach);
-    if (l.floor > 1) return fail(ctx, VC_ERR_ARG, "vc_light_render: floor %u is neither 0 nor 1", l.floor);
-    if (l.floor) {
-        double big = 0.0;
-        for (int j = 0; j < 4; ++j) {
-            if (!std::isfinite(l.floor_rect[j])) return fail(ctx, VC_ERR_ARG, "vc_light_render: the floor's rectangle has a bound that is not finite");
-            big = std::fabs(l.floor_rect[j]) > big ? std::fabs(l.floor_rect[j]) : big;
-        }
-        if (!std::isfinite(l.floor_z)) return fail(ctx, VC_ERR_ARG, "vc_light_render: floor_z is not finite");
-        if (l.floor_rect[0] > l.floor_rect[1] || l.floor_rect[2] > l.floor_rect[3])
-            return fail(ctx, VC_ERR_ARG, "vc_light_render: the floor's rectangle [%g, %g] x [%g, %g] is empty", l.floor_rect[0], l.floor_rect[1],
-                        l.floor_rect[2], l.floor_rect[3]);
-        // (the cells of a point of the rectangle are counted in 64-bit integers)
-        if (!std::isfinite(l.floor_cell_mm) || !(l.floor_cell_mm > 0.0) || !(big / l.floor_cell_mm < 4503599627370496.0))
-            return fail(ctx, VC_ERR_ARG, "vc_light_render: floor cells of %g mm (must be > 0 and at most 2^52 of them to the rectangle's bounds)",
-                        l.floor_cell_mm);
-    }
-    Pass pass;
-    VC_TRY(pass_open(ctx, "vc_light_render", "light", "lighting", pass));
-    if (!ctx->render.valid || !ctx->current(ctx->render.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_light_render: no images of the current carve result: call vc_render first");
-    if (l.smooth && !ctx->current(ctx->normals.stamp))
-        return fail(ctx, VC_ERR_ARG, "vc_light_render: smooth = 1 and no normals: call vc_hull_normals on the current carve result");
-    StepBuf &cur = *pass.cur;
-    VC_TRY(pass_begin(ctx));
-    VC_HIP(ctx, ensure_pinned(ctx->light.h, 7));
-    ctx->light.valid = false;
-    const uint32_t V = ctx->render.n_views, H = ctx->render.H, W = ctx->render.W;
-    const uint64_t npix = (uint64_t)V * H * W;                           // <= 2^28 (vc_render)
-    VC_TRY(ensure(ctx, ctx->light.rgb, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->light.jobs, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->light.depth, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->light.kind, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->light.shadow, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->light.ao, (size_t)npix));
-    VC_TRY(ensure(ctx, ctx->light.ctr, 7));
-    const uint32_t nb[3] = {(ctx->nx + kRenderB - 1) / kRenderB, (ctx->ny + kRenderB - 1) / kRenderB, (ctx->nz + kRenderB - 1) / kRenderB};
-    const uint64_t nblocks = (uint64_t)nb[0] * nb[1] * nb[2];
-    VC_TRY(ensure(ctx, ctx->render.map, (size_t)((nblocks + 63) / 64)));
-    VC_TRY(pass_start(ctx, pass, kWordsAlways));
-    VC_HIP(ctx, hipMemsetAsync(ctx->light.ctr.ptr, 0, 7 * sizeof(unsigned long long), ctx->stream));
-    LightParams p;
-    memset(&p, 0, sizeof p);
-    p.words = cur.words.ptr;
-    p.bmap = ctx->render.map.ptr;
-    p.records = cur.records.ptr;
-    p.normals = ctx->normals.out.ptr;
-    p.S = ctx->survivors;
-    p.views = ctx->render.views.ptr;
-    p.idx = ctx->render.idx.ptr; p.depth = ctx->render.depth.ptr; p.rgbf = ctx->render.rgbf.ptr;
-    p.jobs = ctx->light.jobs.ptr;
-    p.rgb = ctx->light.rgb.ptr; p.odepth = ctx->light.depth.ptr;
-    p.kind = ctx->light.kind.ptr; p.shadow = ctx->light.shadow.ptr; p.ao = ctx->light.ao.ptr;
-    p.ctr = ctx->light.ctr.ptr;
-    const uint32_t n3[3] = {ctx->nx, ctx->ny, ctx->nz};
-    for (int a = 0; a < 3; ++a) {                // item 1 of vc_render
-        p.n[a] = n3[a];
-        p.nb[a] = nb[a];
-        p.s[a] = (ctx->bounds[2 * a + 1] - ctx->bounds[2 * a]) / (double)(n3[a] - 1);
-        p.e[a] = ctx->bounds[2 * a] - 0.5 * p.s[a];
-    }
-    p.H = H; p.W = W; p.npix = (uint32_t)npix;
-    p.skip = ctx->render.blocks ? 1u : 0u;
-    for (int j = 0; j < 4; ++j) { p.pos[j] = l.pos[j]; p.rect[j] = l.floor_rect[j]; }
-    p.ambient = l.ambient; p.smooth = l.smooth; p.floor = l.floor;
-    p.ao_reach = l.ao_reach; p.floor_z = l.floor_z; p.cell = l.floor_cell_mm;
-    for (int k = 0; k < 2; ++k)
-        p.floor_rgb[k] = (uint32_t)l.floor_rgb[k][0] | ((uint32_t)l.floor_rgb[k][1] << 8) | ((uint32_t)l.floor_rgb[k][2] << 16);
-    if (p.skip && !ctx->render.map_built) {       // (render_blocks was 0 when the render ran: the map of the same result, now)
-        hipLaunchKernelGGL(k_render_map, dim3((uint32_t)((nblocks + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, ctx->stream,
-                           (const uint64_t *)cur.words.ptr, ctx->render.map.ptr, ctx->nx, ctx->ny, ctx->nz, nb[0], nb[1], nblocks);
-        VC_HIP(ctx, hipGetLastError());
-        ctx->render.map_built = true;
-    }
-    hipLaunchKernelGGL(k_light_classify, dim3((uint32_t)((npix + kLightBlock - 1) / kLightBlock)), dim3(kLightBlock), 0, ctx->stream, p);
-    VC_HIP(ctx, hipGetLastError());
-    const LightSel sel{ctx->light.kind.ptr, ctx->render.rgbf.ptr, ctx->light.jobs.ptr};
-    VC_TRY(compact(ctx, sel, npix, ctx->h_res + 0));
-    VC_HIP(ctx, hipStreamSynchronize(ctx->stream));                  // the list's length sizes the launch
-    const uint64_t njobs = ctx->h_res[0];
-    if (njobs > npix) return fail(ctx, VC_ERR_HIP, "vc_light_render: %llu pixels listed among %llu", (unsigned long long)njobs, (unsigned long long)npix);
-    p.njobs = (uint32_t)njobs;
-    if (njobs) {
-        const uint64_t per = kLightBlock / kLightRays, want = (njobs + per - 1) / per;
-        hipLaunchKernelGGL(k_light, dim3((uint32_t)(want < kLightMaxBlocks ? want : kLightMaxBlocks)), dim3(kLightBlock), 0, ctx->stream, p);
-        VC_HIP(ctx, hipGetLastError());
-    }
-    VC_TRY(pass_stop(ctx, pass));                   // (the counters' read-back is not part of the pass's time)
-    VC_HIP(ctx, hipMemcpyAsync(ctx->light.h, ctx->light.ctr.ptr, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    VC_TRY(pass_end(ctx, pass, &stats->light_ms));
-    const uint64_t *h = ctx->light.h;
-    if (h[0] + h[1] > npix || njobs > h[0] + h[1] || h[2] + h[3] > njobs)
-        return fail(ctx, VC_ERR_HIP, "vc_light_render: %llu hull and %llu floor pixels among %llu, %llu listed, %llu shadowed, %llu facing away",
-                    (unsigned long long)h[0], (unsigned long long)h[1], (unsigned long long)npix, (unsigned long long)njobs,
-                    (unsigned long long)h[2], (unsigned long long)h[3]);
-    ctx->light.valid = true;
-    stats->pixels = npix;
-    stats->hull_pixels = h[0];
-    stats->floor_pixels = h[1];
-    stats->shadowed = h[2];
-    stats->facing_away = h[3];
-    stats->rays_walked = h[4];
-    stats->cells_visited = h[5];
-    stats->blocks_skipped = h[6];
-    return VC_OK;
-}
-
-int vc_fetch_lit(vc_ctx *ctx, uint32_t view, uint8_t *rgb, float *depth, uint8_t *kind, uint8_t *shadow, uint8_t *ao)
-{
-    if (!ctx) return VC_ERR_ARG;
-    if (!ctx->render.valid || !ctx->light.valid) return fail(ctx, VC_ERR_ARG, "vc_fetch_lit: no lit images: call vc_light_render first");
-    if (view >= ctx->render.n_views) return fail(ctx, VC_ERR_ARG, "vc_fetch_lit: view %u not in [0,%u)", view, ctx->render.n_views);
-    VC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t HW = (size_t)ctx->render.H * ctx->render.W, off = (size_t)view * HW;
-    if (rgb) {
-        std::vector<uint32_t> px(HW);
-        VC_HIP(ctx, hipMemcpy(px.data(), ctx->light.rgb.ptr + off, HW * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < HW; ++k) {
-            const uint32_t q = px[k];
-            rgb[3 * k] = (uint8_t)q; rgb[3 * k + 1] = (uint8_t)(q >> 8); rgb[3 * k + 2] = (uint8_t)(q >> 16);
-        }
-    }
-    if (depth) VC_HIP(ctx, hipMemcpy(depth, ctx->light.depth.ptr + off, HW * sizeof(float), hipMemcpyDeviceToHost));
-    if (kind) VC_HIP(ctx, hipMemcpy(kind, ctx->light.kind.ptr + off, HW, hipMemcpyDeviceToHost));
-    if (shadow) VC_HIP(ctx, hipMemcpy(shadow, ctx->light.shadow.ptr + off, HW, hipMemcpyDeviceToHost));
-    if (ao) VC_HIP(ctx, hipMemcpy(ao, ctx->light.ao.ptr + off, HW, hipMemcpyDeviceToHost));
-    return VC_OK;
-}
-
 // From here on the host side of a family lives beside its kernels in a file of its own under host/, included once, in dependency
 // order (still this one translation unit: a file may use what stands above it).
+#include "host/motion.h"     // vc_hull_motion, vc_hull_warp, vc_paint_motion (the kept hulls of the set algebra above)
+#include "host/render.h"     // vc_render, vc_fetch_render (the pass frame above); the colouring pass's vc_fetch_visibility, vc_fetch_depth
+#include "host/mc.h"         // vc_marching_cubes over the dense volume (densify_words and scan_counts above)
+#include "host/surface.h"    // vc_surface_mesh: the silhouette-refined mesh (scan_counts above)
+#include "host/normals.h"    // vc_hull_normals, vc_shade_render, vc_surface_normals (dist_metric and isqrt_u64 of the distance and grow passes above)
+#include "host/texture.h"    // vc_texture_render (the last render of render.h; visible_start of the colouring pass above)
+#include "host/light.h"      // vc_light_render: shadows, ambient occlusion, floor (the last render of render.h)
 #include "host/clusters.h"   // vc_hull_clusters (dist_metric of the distance passes above)
 #include "host/geodesic.h"   // vc_hull_geodesic, extremities, paths (dist_metric and the survivors' box of the distance passes above)
 #include "host/measure.h"    // vc_hull_measure (the labels of clusters.h and geodesic.h); ms_divisor
