@@ -502,7 +502,8 @@ int vc_fetch_grown(vc_ctx *ctx, uint8_t *added);   /* u8 [S_after], record order
  *     words, and the staging buffer become P.
  *  11 vc_fetch_temporal fails unless the current result is the last call's output; vc_fetch_temporal_history fails for age >= m.
  * Memory: (window + 2) nwords 8 bytes (0.94 GB at 1024^3 with window 5), allocated by the first call.  What it does not do: it lags
- * a moving figure by about window / 2 frames, there is no motion compensation, and multi-GPU is refused.
+ * a moving figure by about window / 2 frames, there is no motion compensation (vc_hull_temporal_motion below has it; a ring that
+ * call filled is started over by this one, as by another `window`), and multi-GPU is refused.
  * Synchronous, one read-back in the middle (the five counts). */
 #define VC_TEMPORAL_MAX_WINDOW 15u
 typedef struct {
@@ -660,6 +661,58 @@ int vc_hull_motion(vc_ctx *ctx, uint32_t reg, uint32_t block, uint32_t apron, ui
 int vc_fetch_motion(vc_ctx *ctx, vc_motion_t *rows /* NULL ok */, uint64_t *count /* NULL ok */);
 int vc_hull_warp(vc_ctx *ctx, uint32_t src, uint32_t dst, uint32_t flags /* must be 0 */, vc_warp_stats_t *stats);
 int vc_paint_motion(vc_ctx *ctx);
+
+/* ---- the vote over the last hulls, motion compensated (no reference counterpart) --------------------------------------------------
+ * vc_hull_temporal never moves the older hulls, so on a figure that walks it votes the figure away: the hulls of five frames of a
+ * body that moves two voxels a frame overlap in a sliver.  vc_hull_temporal_motion is a second entry point to the same ring and the
+ * same P: before it counts, it aligns every older snapshot and P to the current hull by the block motion field between the ring's
+ * newest snapshot and the current hull.  Integers and bits only (tests/temporal_motion_np.py restates it bit for bit).  Item
+ * numbers in brackets are vc_hull_temporal's (T) and vc_hull_motion's (M) above.
+ *   1 push, m, thresholds: as T1 - T3.  H_t is the current result's occupancy, m = min(pushes since the last reset, window), on
+ *     and off scale with m.
+ *   2 field: when the ring holds a hull before this push, F_t is the field of M1 - M4 with A = H_t and B = the ring's newest
+ *     snapshot, which is the raw H_{t-1} (the newest snapshot is never moved before the next push), at block / apron / search
+ *     with that call's ranges: b in {4, 8, 16}, a <= 16, 1 <= s <= 8, b + 2a + 2s <= 64, at most 2^26 blocks.  The first push after
+ *     a reset has no field: listed = 0 and every motion stat but `blocks` is 0.
+ *   3 align: for X = P and X = each snapshot that stays in the ring (the min(have, window - 1) newest, have = the hulls in the ring
+ *     before this push): X'(v) = X(v - d_k) for v in listed block k; X'(v) = X(v) for v in an unlisted block (d = 0 there, NOT the
+ *     emptying of vc_hull_warp: an old speck in a block that H_t and H_{t-1} both leave empty keeps its vote).  A source cell
+ *     outside the grid is empty.  A gather: no holes.
+ *   4 count and vote: c(v) counts over H_t and the aligned snapshots; O_t = { c >= on } + { v in P' : c >= off }.
+ *   5 what the ring stores: the ALIGNED snapshots, and P becomes O_t.  The next call aligns them again by its own field, so a
+ *     snapshot of age j has gone through a chain of j integer gathers.  What that costs: where neighbouring blocks have different
+ *     vectors the content tears or doubles at the seam between them, such damage is never undone, and it compounds with age.
+ *     vc_fetch_temporal_history(age) returns the aligned snapshot of that age; age 0 is the raw H_t.
+ *   6 result, records, votes, `added`, invalidation: as T5.  A kept record keeps its 8 bytes, a voxel of O_t \ H_t is coloured as
+ *     item 3 of vc_hull_grow colours one, and when O_t = H_t nothing is invalidated.  vc_fetch_temporal serves both calls.
+ *   7 stats: window, frames, on, off, block, apron, search; survivors_before, survivors_after, added, removed; raw_changed =
+ *     |H_t xor H_{t-1}| unaligned, as the plain call reports it; aligned_changed = |H_t xor H'_{t-1}|, what the field does not
+ *     explain (0 when m = 1); out_changed = |O_t xor P'|; blocks, listed, moved, unique, clipped, cost0_sum, cost_sum as M5;
+ *     temporal_ms = HIP events around the whole call.
+ *   8 state and mixing: ring and P are vc_hull_temporal's, they survive what T7 says and are reset by what T7 says.  The ring
+ *     remembers which of the two calls filled it: a call of the other kind starts it over, exactly as another `window` does.
+ *     keep_on, keep_off, block, apron and search may change from call to call.  The field lives in a state of the call's own:
+ *     a field of vc_hull_motion and the hull registers are neither read nor written.
+ *   9 one push per result (T8), and VC_ERR_ARG by name, with nothing launched and no state touched, for everything T9 lists and
+ *     for the parameters M7 refuses.
+ *  10 a failure leaves result, ring and P as they were (T10): the aligned snapshots are written to a second ring beside the
+ *     first (a gather cannot run in place anyway), O_t to the staging buffer, every buffer is sized before anything is
+ *     committed, and the commit is a swap of the two rings.  The aligned P is used by the vote alone and is not stored.
+ *  11 vc_fetch_temporal_motion: the rows of the call that produced the current result, as vc_fetch_motion returns rows; the count
+ *     is 0 for a first push.  It fails when vc_fetch_temporal fails, and after a vc_hull_temporal.
+ * Memory: (2 window + 2) nwords 8 bytes (1.6 GB at 1024^3 with window 5) and the field's few bytes per block.  Synchronous, two
+ * read-backs: the listed blocks, then the counters.  What it does not do: everything vc_hull_motion does not do (no sub-voxel
+ * vectors, no search beyond 8, no regularisation of the field), no per-snapshot fields that would avoid the accumulated warp,
+ * and multi-GPU is refused. */
+typedef struct {
+    uint32_t window, frames /* m */, on, off, block, apron, search, reserved;
+    uint64_t survivors_before, survivors_after, added, removed, raw_changed, aligned_changed, out_changed;
+    uint64_t blocks, listed, moved, unique, clipped, cost0_sum, cost_sum;
+    float temporal_ms;
+} vc_temporal_motion_stats_t;
+int vc_hull_temporal_motion(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t keep_off, uint32_t block, uint32_t apron, uint32_t search,
+                            uint32_t flags /* must be 0 */, vc_temporal_motion_stats_t *stats);
+int vc_fetch_temporal_motion(vc_ctx *ctx, vc_motion_t *rows /* NULL ok */, uint64_t *count /* NULL ok */);
 
 /* ---- ray-cast images of the current result (no reference counterpart: the reference's viewer draws instanced cubes with OpenGL,
  *      executable.py) -----------------------------------------------------------------------------------------------------------

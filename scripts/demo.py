@@ -35,6 +35,10 @@ printed and the PLY holds the shell; LEVEL 1..6 (default 0) lists the cells of a
 pixels flipped by a generator seeded with 7000 + the frame number, are carved one after the other and every hull is replaced by
 the vote of the last T hulls on the device, assignment.configure(temporal_window=T) -- the voxels that change between consecutive
 raw hulls and between consecutive voted hulls are printed per frame, and the last voted hull is what is written;
+--temporal T --temporal-motion [BLOCK]: the motion-compensated vote, assignment.configure(temporal_window=T,
+temporal_motion=(BLOCK, None, 4)) with BLOCK 4, 8 (the default) or 16, on a source that moves: frame t has its masks rolled by 2 t
+columns, with the --noise flips on top -- per frame the raw, the aligned (what the block field does not explain) and the voted
+change are printed with the listed and moved blocks (with it, --motion may stand beside --temporal: both want the rolled source);
 --save-hull PATH: the hull as it stands after every pass (grid, bounds, records) as an .npz, CarveEngine.save_hull;
 --subtract PATH / --clip PATH: a hull saved that way is subtracted from / intersected with every frame's hull on the device right
 after the carve, assignment.configure(hull_subtract=PATH, hull_clip=PATH) -- the voxels each takes away are printed;
@@ -159,7 +163,17 @@ if "--motion" in sys.argv:
 motion_paint = "--motion-paint" in sys.argv
 if motion_paint:
     sys.argv.remove("--motion-paint")
-if motion_block and "--temporal" in sys.argv:
+temporal_motion = None
+if "--temporal-motion" in sys.argv:
+    k = sys.argv.index("--temporal-motion")
+    temporal_motion = (8, None, 4)
+    if k + 1 < len(sys.argv) and sys.argv[k + 1] in ("4", "8", "16"):
+        temporal_motion = (int(sys.argv[k + 1]), None, 4)
+        del sys.argv[k + 1]
+    del sys.argv[k]
+    if "--temporal" not in sys.argv:
+        sys.exit("--temporal-motion is a setting of --temporal T")
+if motion_block and "--temporal" in sys.argv and temporal_motion is None:
     sys.exit("--motion rolls the masks from frame to frame, --temporal flips their pixels: one of the two")
 temporal, n_frames, noise = 0, 4 if motion_block else 16, 0.02
 for flag, conv in (("--temporal", int), ("--frames", int), ("--noise", float)):
@@ -187,10 +201,11 @@ if temporal:
     sets = []
     for t in range(n_frames):
         rng = np.random.default_rng(7000 + t)
-        sets.append((frames, [np.where(rng.random(m.shape) < noise, 255 - m, m).astype(np.uint8) for m in masks]))
-if motion_block:
+        moved = [np.roll(m, 2 * t, axis=1) for m in masks] if temporal_motion else masks
+        sets.append((frames, [np.where(rng.random(m.shape) < noise, 255 - m, m).astype(np.uint8) for m in moved]))
+if motion_block and not temporal:
     sets = [(frames, [np.roll(m, 2 * t, axis=1) for m in masks]) for t in range(n_frames)]
-assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal, motion_block=motion_block,
+assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal, temporal_motion=temporal_motion, motion_block=motion_block,
                      motion_paint=motion_paint,
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
@@ -209,11 +224,14 @@ if temporal:
         print("frame %2d: %d hulls, on %d off %d: raw hull %d voxels (%d changed), voted hull %d voxels (%d changed; %d restored, %d dropped), "
               "%.3f ms" % (t, ts["frames"], ts["on"], ts["off"], ts["survivors_before"], ts["raw_changed"], ts["survivors_after"],
                            ts["out_changed"], ts["added"], ts["removed"], ts["temporal_ms"]))
+        if temporal_motion:
+            print("          change against the last hull: raw %d, aligned %d, voted %d; %d of %d blocks listed, %d moved, %d at the range"
+                  % (ts["raw_changed"], ts["aligned_changed"], ts["out_changed"], ts["listed"], ts["blocks"], ts["moved"], ts["clipped"]))
         if t >= temporal:
             raw_sum += ts["raw_changed"]
             out_sum += ts["out_changed"]
     print("flicker over frames %d..%d: %d voxels between raw hulls, %d between voted hulls" % (temporal, n_frames - 1, raw_sum, out_sum))
-if motion_block:
+if motion_block and not temporal:                                # (beside --temporal the vote's lines above say what moved)
     for t in range(1, n_frames):
         pos, col = assignment.set_voxel_positions(g, g // 2, g)
         mo = assignment.motion()

@@ -7,7 +7,7 @@ import ctypes
 import os
 
 from . import lighting           # the lit pass's structs (vc_light_t, vc_light_stats_t) and its defaults
-from . import motion             # the motion pass's structs (vc_motion_t, vc_motion_stats_t, vc_warp_stats_t)
+from . import motion             # the motion pass's structs (vc_motion_t, vc_motion_stats_t, vc_warp_stats_t, vc_temporal_motion_stats_t)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvoxcarve.so")
@@ -304,6 +304,9 @@ SIGNATURES = {
     "vc_fetch_motion": (ctypes.c_int, [c_ctx, ctypes.c_void_p, c_u64p]),
     "vc_hull_warp": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(motion.WarpStats)]),
     "vc_paint_motion": (ctypes.c_int, [c_ctx]),
+    "vc_hull_temporal_motion": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(motion.TemporalMotionStats)]),
+    "vc_fetch_temporal_motion": (ctypes.c_int, [c_ctx, ctypes.c_void_p, c_u64p]),
     "vc_hull_normals": (ctypes.c_int, [c_ctx, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(VcNormalsStats)]),
     "vc_fetch_record_normals": (ctypes.c_int, [c_ctx, c_i16p]),
     "vc_shade_render": (ctypes.c_int, [c_ctx, c_f64p, ctypes.c_uint32, ctypes.c_uint32]),

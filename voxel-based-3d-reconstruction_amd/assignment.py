@@ -197,6 +197,16 @@ def _check_temporal(s):
     if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or t < 0:
         raise ValueError("temporal_window %r, expected an integer in 0..15" % (t,))
     CarveEngine.temporal_thresholds(t if t > 0 else 1, s["temporal_keep"] if t > 0 else None, s["temporal_keep_off"] if t > 0 else None)
+    from . import motion
+    motion.vote_params(s["temporal_motion"])
+
+
+def _run_temporal(s):
+    """The vote; with temporal_motion the motion-compensated one.  Without it the call is the three-argument one it always was."""
+    if s["temporal_motion"] is None:
+        _last.update(temporal=_engine.temporal_filter(s["temporal_window"], s["temporal_keep"], s["temporal_keep_off"]))
+    else:
+        _last.update(temporal=_engine.temporal_filter(s["temporal_window"], s["temporal_keep"], s["temporal_keep_off"], motion=s["temporal_motion"]))
 
 
 def _check_min_column(s):
@@ -346,9 +356,8 @@ STAGES = [
     Stage("hull_subtract", {"hull_subtract": None}, [_operand("hull_subtract")], lambda s: s["hull_subtract"] is not None,
           lambda s: _last.update(hull_ops={"subtract": _engine.combine_hull("andnot", HULL_SUBTRACT_REG)})),
     Stage("hull_clip", {"hull_clip": None}, [_operand("hull_clip")], lambda s: s["hull_clip"] is not None, _run_clip),
-    Stage("temporal", {"temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None}, [_check_temporal],
-          lambda s: s["temporal_window"] > 0,
-          lambda s: _last.update(temporal=_engine.temporal_filter(s["temporal_window"], s["temporal_keep"], s["temporal_keep_off"]))),
+    Stage("temporal", {"temporal_window": 0, "temporal_keep": None, "temporal_keep_off": None, "temporal_motion": None}, [_check_temporal],
+          lambda s: s["temporal_window"] > 0, _run_temporal),
     Stage("close", {"hull_close_mm": 0.0}, [lambda s: CarveEngine.radius_r2(s["hull_close_mm"])], lambda s: s["hull_close_mm"] > 0,
           lambda s: _engine.close_hull(s["hull_close_mm"])),
     Stage("open", {"hull_open_mm": 0.0, "hull_border": "open"},
@@ -392,10 +401,13 @@ def configure(frame_source=None, **settings):
     indices or uint64 records: voxcarve.hullio.as_operand), or None (the default: nothing runs).  The operand is uploaded once,
     to registers 3 and 2 of the engine; the stages are CarveEngine.combine_hull("andnot", 3) (the static scene leaves the hull)
     and CarveEngine.combine_hull("and", 2) (the hull is clipped to a region of interest).  hull_ops() returns their stats.
-    3. temporal_window, temporal_keep, temporal_keep_off: when temporal_window = T > 0 (at most 15),
+    3. temporal_window, temporal_keep, temporal_keep_off, temporal_motion: when temporal_window = T > 0 (at most 15),
     CarveEngine.temporal_filter(T, temporal_keep, temporal_keep_off): the hull becomes the vote of the last T frames' hulls (keep
     defaults to the majority, keep_off to keep), which takes the frame-to-frame flicker of mask noise out and lags a moving
-    figure by about T / 2 frames.  temporal() returns the last frame's stats.  0 (the default) runs nothing.
+    figure by about T / 2 frames.  temporal_motion = True or (block, apron, search) makes it the motion-compensated vote
+    (temporal_filter(..., motion=temporal_motion); True is (8, None, 4), apron None is block // 2): the older hulls are aligned
+    to the frame's hull by the block motion field first, so a figure that walks is voted on where it is now; None (the default)
+    is the plain vote.  temporal() returns the last frame's stats.  temporal_window = 0 (the default) runs nothing.
     4. hull_close_mm: when > 0, CarveEngine.close_hull(hull_close_mm) (close, then open, is the usual clean-up order): tunnels and
     dents narrower than a ball of that radius in world millimetres are filled -- what a hole in one camera's mask carves through
     the figure; the added voxels are coloured from the colour camera.  voxels_status() describes the closed hull.
@@ -575,7 +587,7 @@ def measurements():
 
 def temporal():
     """The stats of the last set_voxel_positions call's vote over the last frames' hulls (configure(temporal_window=T)): the dict
-    of CarveEngine.temporal_filter."""
+    of CarveEngine.temporal_filter (with configure(temporal_motion=...) the longer one of the motion-compensated vote)."""
     return _last_result("temporal", "temporal vote", "temporal_window=T")
 
 

@@ -51,6 +51,7 @@
 #include "vc_temporal.h"
 #include "vc_setops.h"
 #include "vc_motion.h"
+#include "vc_temporal_motion.h"
 #include "vc_normals.h"
 #include "vc_texture.h"
 #include "vc_light.h"
@@ -428,11 +429,31 @@ struct vc_ctx {
         uint64_t stamp = kNever;         // added belongs to the vc_hull_grow that produced the current result
         uint64_t n = 0;                  // its survivors_after
     } grow;
+    // vc_hull_motion / vc_hull_warp / vc_paint_motion: voxel counts per block, the groups' masks of listed blocks, the rows, the
+    // vector of each block, the counters and their read-back; the launch geometry of the field and the register it was made against
+    struct Motion {
+        DevBuf<uint32_t> counts, vec;
+        DevBuf<uint64_t> mask;
+        DevBuf<MotionRow> rows;
+        DevBuf<unsigned long long> ctr;
+        Pinned<uint64_t> h;              // page-locked read-back of the counters
+        MotionGrid g = {};
+        uint64_t stamp = kNever;         // the field belongs to the vc_hull_motion that ran on the current result ...
+        uint32_t reg = 0;                // ... against this register, which has not been written since (motion_reg_written)
+        uint64_t listed = 0;
+    };
     // vc_hull_temporal: the ring of the last `window` hulls ([window][npad] words, slot `head` the newest), the previous output P,
     // the staging buffer of O_t (swapped with P by a finished call), the five counters and their read-back, the records' vote and
     // `added` bytes.  Ring, P, window, head and pushes OUTLIVE a result: a carve leaves them alone, geometry_changed starts them over.
+    // vc_hull_temporal_motion shares all of it and adds the second ring its aligned snapshots are written to (swapped with the first
+    // by a finished call), the kind of call that filled the ring, and a field of its own (its stamp and register are not used:
+    // the field is current while `stamp` below is).
     struct Temporal {
         DevBuf<uint64_t> ring, prev, stage;
+        DevBuf<uint64_t> ring2;          // vc_hull_temporal_motion only
+        bool aligned = false;            // the ring was filled by vc_hull_temporal_motion: a call of the other kind starts it over
+        bool has_field = false;          // ... and the call that produced the current result was one (vc_fetch_temporal_motion)
+        Motion field;
         DevBuf<unsigned long long> ctr;
         Pinned<uint64_t> h;              // page-locked read-back of the counters
         DevBuf<uint8_t> votes, added;
@@ -461,19 +482,7 @@ struct vc_ctx {
         uint64_t stamp = kNever;         // added belongs to the vc_hull_combine that produced the current result
         uint64_t n = 0;                  // its survivors_after
     } setops;
-    // vc_hull_motion / vc_hull_warp / vc_paint_motion: voxel counts per block, the groups' masks of listed blocks, the rows, the
-    // vector of each block, the counters and their read-back; the launch geometry of the field and the register it was made against
-    struct Motion {
-        DevBuf<uint32_t> counts, vec;
-        DevBuf<uint64_t> mask;
-        DevBuf<MotionRow> rows;
-        DevBuf<unsigned long long> ctr;
-        Pinned<uint64_t> h;              // page-locked read-back of the counters
-        MotionGrid g = {};
-        uint64_t stamp = kNever;         // the field belongs to the vc_hull_motion that ran on the current result ...
-        uint32_t reg = 0;                // ... against this register, which has not been written since (motion_reg_written)
-        uint64_t listed = 0;
-    } motion;
+    Motion motion;
     // vc_render: the images of the last render ([V][H W] index, depth, colour | face << 24), its views, the block map, counters
     struct Render {
         DevBuf<uint32_t> idx, rgbf;
@@ -3426,7 +3435,7 @@ int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t ke
                                                 (unsigned long long)cur.words.cap, (unsigned long long)npad);
     VC_TRY(pass_begin(ctx));
     // a ring of another window or another grid starts over; its buffers are made beside the old ones, which stay until the call commits
-    const bool restart = T.pushes == 0 || T.window != window || T.nwords != nwords;
+    const bool restart = T.pushes == 0 || T.window != window || T.nwords != nwords || T.aligned;
     const bool alloc = T.ring.cap < (size_t)window * npad || T.prev.cap < npad || T.stage.cap < npad || !T.ring.ptr;
     DevBuf<uint64_t> ring2, prev2, stage2;
     if (alloc) {
@@ -3479,7 +3488,10 @@ int vc_hull_temporal(vc_ctx *ctx, uint32_t window, uint32_t keep_on, uint32_t ke
         T.window = window; T.nwords = nwords; T.npad = npad;
         T.head = window - 1;
         T.pushes = 0;
+        T.aligned = false;
+        T.ring2.reset();                         // (the second ring of vc_hull_temporal_motion: this ring has no use for it)
     }
+    T.has_field = false;
     T.head = (T.head + 1) % window;
     T.pushes += 1;
     VC_HIP(ctx, hipMemcpyAsync(T.ring.ptr + (size_t)T.head * npad, cur.words.ptr, (size_t)nwords * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
@@ -3857,6 +3869,7 @@ int vc_hull_compare(vc_ctx *ctx, uint32_t reg, uint32_t flags, vc_compare_stats_
 // From here on the host side of a family lives beside its kernels in a file of its own under host/, included once, in dependency
 // order (still this one translation unit: a file may use what stands above it).
 #include "host/motion.h"     // vc_hull_motion, vc_hull_warp, vc_paint_motion (the kept hulls of the set algebra above)
+#include "host/temporal_motion.h"   // vc_hull_temporal_motion (the vote's ring and hand-over above, motion_field of motion.h)
 #include "host/render.h"     // vc_render, vc_fetch_render (the pass frame above); the colouring pass's vc_fetch_visibility, vc_fetch_depth
 #include "host/mc.h"         // vc_marching_cubes over the dense volume (densify_words and scan_counts above)
 #include "host/surface.h"    // vc_surface_mesh: the silhouette-refined mesh (scan_counts above)

@@ -669,15 +669,32 @@ class CarveEngine:
                              % (window, keep, keep_off, _lib.VC_TEMPORAL_MAX_WINDOW))
         return int(window), int(keep), int(keep_off)
 
-    def temporal_filter(self, window=5, keep=None, keep_off=None):
+    def temporal_filter(self, window=5, keep=None, keep_off=None, motion=None):
         """Pushes the current carve result onto a ring of the last `window` hulls on the device and replaces it by their vote: a
         voxel enters when at least `keep` of the hulls hold it (default: the majority) and, once in, stays while at least keep_off
         do (default: keep, a plain vote); the thresholds scale with the ring while it fills, so the first call returns the hull
         as it is.  Restored voxels are coloured from the colour camera as close_hull colours (contract: include/voxcarve.h).  The
         ring survives carves; temporal_reset, set_grid / set_cameras and another window start it over.  One call per carve.
         Returns the stats as a dict: window, frames, on, off, survivors_before, survivors_after, added, removed, raw_changed,
-        out_changed, temporal_ms."""
+        out_changed, temporal_ms.
+
+        motion=True or (block, apron, search) is the motion-compensated vote (vc_hull_temporal_motion): before it counts, the
+        older hulls and the previous output are aligned to the current hull by the block motion field between the last hull
+        and this one (hull_motion's parameters; True is 8, None, 4), and the ring keeps the aligned hulls.  The stats gain
+        block, apron, search, aligned_changed and the field's blocks, listed, moved, unique, clipped, cost0_sum, cost_sum;
+        fetch_temporal_motion returns the field.  A ring filled by the other kind of call starts over."""
         window, keep, keep_off = self.temporal_thresholds(window, keep, keep_off)
+        from . import motion as mo
+        params = mo.vote_params(motion)
+        if params is not None:
+            st = mo.TemporalMotionStats()
+            self._check(self._L.vc_hull_temporal_motion(self._ctx, window, keep, keep_off, params[0], params[1], params[2], 0, ctypes.byref(st)),
+                        "vc_hull_temporal_motion")
+            self.count = int(st.survivors_after)
+            self._temporal_motion = params
+            out = _stats(st)
+            del out["reserved"]
+            return out
         st = _lib.VcTemporalStats()
         self._check(self._L.vc_hull_temporal(self._ctx, window, keep, keep_off, 0, ctypes.byref(st)), "vc_hull_temporal")
         self.count = int(st.survivors_after)
@@ -690,9 +707,21 @@ class CarveEngine:
         self._check(self._L.vc_fetch_temporal(self._ctx, _ptr(votes, ctypes.c_uint8), _ptr(added, ctypes.c_uint8)), "vc_fetch_temporal")
         return votes, added
 
+    def fetch_temporal_motion(self):
+        """The field of the last temporal_filter(motion=...) as the dict of fetch_motion (no rows for the first push of a ring);
+        fails when fetch_temporal fails, and after a temporal_filter without motion."""
+        from . import motion
+        n = ctypes.c_uint64(0)
+        self._check(self._L.vc_fetch_temporal_motion(self._ctx, None, ctypes.byref(n)), "vc_fetch_temporal_motion")
+        raw = np.zeros(int(n.value), dtype=motion.ROW_DTYPE)
+        if n.value:
+            self._check(self._L.vc_fetch_temporal_motion(self._ctx, raw.ctypes.data_as(ctypes.c_void_p), None), "vc_fetch_temporal_motion")
+        return motion.rows_dict(raw, self.grid, *getattr(self, "_temporal_motion", (8, 4, 4)))
+
     def temporal_history(self, age):
-        """The raw hull that temporal_filter pushed `age` calls ago (0 = the last one) as occupancy words, uint64 [ceil(N / 64)]
-        laid out as vc_fetch_occupancy; fails for an age the ring does not hold."""
+        """The hull that temporal_filter pushed `age` calls ago (0 = the last one, always raw; with motion= the older ones as the
+        calls since have aligned them) as occupancy words, uint64 [ceil(N / 64)] laid out as vc_fetch_occupancy; fails for an
+        age the ring does not hold."""
         raw = np.empty((self.n_voxels + 63) // 64 if self.grid is not None else 0, dtype=np.uint64)
         self._check(self._L.vc_fetch_temporal_history(self._ctx, int(age), raw.ctypes.data_as(_lib.c_u8p)), "vc_fetch_temporal_history")
         return raw

@@ -31,6 +31,16 @@ class WarpStats(ctypes.Structure):           # vc_warp_stats_t
     _fields_ = [("warped", ctypes.c_uint64), ("common", ctypes.c_uint64), ("a", ctypes.c_uint64), ("warp_ms", ctypes.c_float)]
 
 
+class TemporalMotionStats(ctypes.Structure):   # vc_temporal_motion_stats_t (the vote aligned by this field)
+    _fields_ = [("window", ctypes.c_uint32), ("frames", ctypes.c_uint32), ("on", ctypes.c_uint32), ("off", ctypes.c_uint32),
+                ("block", ctypes.c_uint32), ("apron", ctypes.c_uint32), ("search", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("survivors_before", ctypes.c_uint64), ("survivors_after", ctypes.c_uint64), ("added", ctypes.c_uint64),
+                ("removed", ctypes.c_uint64), ("raw_changed", ctypes.c_uint64), ("aligned_changed", ctypes.c_uint64),
+                ("out_changed", ctypes.c_uint64), ("blocks", ctypes.c_uint64), ("listed", ctypes.c_uint64), ("moved", ctypes.c_uint64),
+                ("unique", ctypes.c_uint64), ("clipped", ctypes.c_uint64), ("cost0_sum", ctypes.c_uint64), ("cost_sum", ctypes.c_uint64),
+                ("temporal_ms", ctypes.c_float)]
+
+
 def check_params(block, apron, search):
     """(block, apron, search) as integers, apron=None meaning block // 2; ValueError outside the ranges of vc_hull_motion."""
     block = int(block)
@@ -45,6 +55,21 @@ def check_params(block, apron, search):
     if block + 2 * apron + 2 * search > ROW_BITS:
         raise ValueError("motion: block + 2 apron + 2 search = %d exceeds the %d bits of a row" % (block + 2 * apron + 2 * search, ROW_BITS))
     return block, apron, search
+
+
+def vote_params(motion):
+    """(block, apron, search) of temporal_filter's `motion` (and configure's temporal_motion): True is (8, None, 4), a
+    (block, apron, search) tuple goes through check_params (apron None = block // 2); None stays None; ValueError otherwise."""
+    if motion is None:
+        return None
+    if motion is True:
+        motion = (8, None, 4)
+    if isinstance(motion, (bool, np.bool_)) or not isinstance(motion, (tuple, list)) or len(motion) != 3:
+        raise ValueError("temporal motion %r, expected None, True or (block, apron, search)" % (motion,))
+    for name, v in zip(("block", "apron", "search"), motion):
+        if isinstance(v, bool) or not (isinstance(v, (int, np.integer)) or (v is None and name == "apron")):
+            raise ValueError("temporal motion %r: %s %r, expected an integer" % (tuple(motion), name, v))
+    return check_params(*motion)
 
 
 def block_dims(grid, edge):
