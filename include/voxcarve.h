@@ -662,6 +662,55 @@ int vc_fetch_motion(vc_ctx *ctx, vc_motion_t *rows /* NULL ok */, uint64_t *coun
 int vc_hull_warp(vc_ctx *ctx, uint32_t src, uint32_t dst, uint32_t flags /* must be 0 */, vc_warp_stats_t *stats);
 int vc_paint_motion(vc_ctx *ctx);
 
+/* ---- coarse-to-fine block motion: vectors beyond the search range (no reference counterpart) ---------------------------------------
+ * vc_hull_motion finds no vector longer than s <= 8 voxels.  vc_hull_motion_pyramid is a second entry point to the same field:
+ * it halves both hulls L times, matches the coarsest level as vc_hull_motion does, and on every finer level lets each block choose
+ * among the displacements around twice its parent block's vector and twice the vectors of the parent's face neighbours.  Integers
+ * and bits only (tests/motion_pyramid_np.py restates it bit for bit).  vc_hull_motion keeps its results.
+ *   1 parameters: levels L in 0..3, refine radius r in 1..s; block, apron and search as for vc_hull_motion, refused in the same
+ *     words (b + 2a + 2s <= 64 covers r).  reach = s 2^L + r (2^L - 1) <= 120 bounds every component of a vector, so int8 d holds
+ *     it.  With L = 0, r is checked and otherwise unused: rows, vectors, counters and the nine stats of vc_motion_stats_t equal
+ *     vc_hull_motion's bit for bit.
+ *   2 levels: level 0 is the grid; level l has ceil(n / 2) cells per axis of level l - 1.  Cell v of A_l is the OR of the at most
+ *     eight cells 2v + {0,1}^3 of A_{l-1} that lie in its grid; B_l likewise from the register's words.  Linear order and word
+ *     layout are the same on every level: (iz nx_l + ix) ny_l + iy, 64 cells per word, the bits from n_l on zero.
+ *     vc_fetch_motion_occupancy returns these words (which = 0: A, 1: B; level 0: the result's and the register's own).
+ *   3 coarsest level: vc_hull_motion's items 1 to 4 applied to (A_L, B_L) with b, a and s, unchanged.
+ *   4 listing and parents on a level l < L: blocks of edge b on level l's grid, listed when they hold a cell of A_l or of B_l, in
+ *     ascending block index.  The parent of block (bx, by, bz) is block (bx >> 1, by >> 1, bz >> 1) of level l + 1.  With OR
+ *     levels and an even b the parent of a listed block is listed; the device counts violations, and one is VC_ERR_HIP.
+ *   5 candidates on a level l < L: the block's prediction is c = 2 d(parent); its centres are c and 2 d of each listed face
+ *     neighbour of the parent (+-x, +-y, +-z in the coarser block grid), at most 7; its candidate set D is the union over the
+ *     centres of centre + [-r, r]^3, a displacement reached from two centres counting once.
+ *   6 choice on a level l < L: the cost of d in D is vc_hull_motion's on this level (the cells v of the window, the block grown by
+ *     a, with A_l(v) != B_l(v - d); cells off the grid are empty).  The smallest (cost, |d - c|^2, dz, dx, dy) wins; ties = the
+ *     distinct d in D at the smallest cost; cost0 = the cost of d = 0, whether or not 0 is in D.
+ *   7 flags of a row of a level l < L: bit 0: some face neighbour d +- e_axis of the winner is not in D (a better vector may lie
+ *     outside what was tried; on a single level this is vc_hull_motion's bit 0).  Bit 1: the winner does not lie in
+ *     c + [-r, r]^3: it was borrowed from a neighbour's prediction.
+ *   8 what the call leaves: the level-0 rows and vectors are the field: vc_fetch_motion, vc_hull_warp, vc_paint_motion and the
+ *     lifetime of item 8 of vc_hull_motion apply unchanged, and vc_paint_motion divides by reach where it divides by s (with
+ *     L = 0 the two are equal).  vc_fetch_motion_level returns the rows of level l <= L while the field is current (level 0:
+ *     vc_fetch_motion's); a level above L, as `which` above 1, is VC_ERR_ARG.  A later vc_hull_motion leaves a field of L = 0.
+ *   9 stats (required): the nine integers of vc_motion_stats_t over level 0; levels, refine, reach; listed_level[l] and
+ *     dims_level[l] = (nx, ny, nz) of level l (0 above L); evaluated = the sum of |D| over the listed blocks of all levels
+ *     below L; borrowed = the level-0 rows with bit 1; motion_ms.
+ *  10 the call changes nothing: not the records, not the result generation, not the register.  Synchronous, one read-back per
+ *     level (its listed blocks).  Refused as vc_hull_motion is (item 7 there), and for L > 3, r = 0, r > s. */
+typedef struct {
+    uint64_t blocks, listed, moved, unique, clipped, cost0_sum, cost_sum, a, b;
+    uint32_t levels, refine, reach, reserved;
+    uint64_t listed_level[4];
+    uint32_t dims_level[4][3];
+    uint64_t evaluated, borrowed;
+    float motion_ms;
+} vc_motion_pyramid_stats_t;
+int vc_hull_motion_pyramid(vc_ctx *ctx, uint32_t reg, uint32_t block, uint32_t apron, uint32_t search, uint32_t levels, uint32_t refine,
+                           uint32_t flags /* must be 0 */, vc_motion_pyramid_stats_t *stats);
+int vc_fetch_motion_level(vc_ctx *ctx, uint32_t level, vc_motion_t *rows /* NULL ok */, uint64_t *count /* NULL ok */);
+int vc_fetch_motion_occupancy(vc_ctx *ctx, uint32_t level, uint32_t which /* 0 = A, 1 = B */, uint64_t *words /* NULL ok */,
+                              uint64_t *count /* NULL ok */);
+
 /* ---- the vote over the last hulls, motion compensated (no reference counterpart) --------------------------------------------------
  * vc_hull_temporal never moves the older hulls, so on a figure that walks it votes the figure away: the hulls of five frames of a
  * body that moves two voxels a frame overlap in a sliver.  vc_hull_temporal_motion is a second entry point to the same ring and the

@@ -46,7 +46,9 @@ after the carve, assignment.configure(hull_subtract=PATH, hull_clip=PATH) -- the
 carved one after the other and from the second on the block motion against the previous frame's hull is estimated on the device,
 assignment.configure(motion_block=BLOCK) with BLOCK 4, 8 (the default) or 16 -- per frame the listed, unique and moved blocks, the
 change before and after compensation and the median vector in mm are printed; --motion-paint: every voxel coloured by its block's
-vector (grey = at rest), in the PLY, the --render images and the --mesh;
+vector (grey = at rest), in the PLY, the --render images and the --mesh; --motion-levels L (1..3): the coarse-to-fine field,
+assignment.configure(motion_levels=L), which finds vectors beyond the search range -- the line of a frame then also says how many
+vectors were borrowed from a neighbouring block's prediction and the field's reach;
 --help: this text)."""
 import os, sys
 if "--help" in sys.argv or "-h" in sys.argv:
@@ -160,6 +162,13 @@ if "--motion" in sys.argv:
         motion_block = int(sys.argv[k + 1])
         del sys.argv[k + 1]
     del sys.argv[k]
+motion_levels = 0
+if "--motion-levels" in sys.argv:
+    k = sys.argv.index("--motion-levels")
+    if not motion_block or k + 1 >= len(sys.argv) or sys.argv[k + 1] not in ("0", "1", "2", "3"):
+        sys.exit("--motion-levels L (0..3) is a setting of --motion")
+    motion_levels = int(sys.argv[k + 1])
+    del sys.argv[k:k + 2]
 motion_paint = "--motion-paint" in sys.argv
 if motion_paint:
     sys.argv.remove("--motion-paint")
@@ -206,7 +215,7 @@ if temporal:
 if motion_block and not temporal:
     sets = [(frames, [np.roll(m, 2 * t, axis=1) for m in masks]) for t in range(n_frames)]
 assignment.configure(frame_source=assignment.StaticFrameSource(sets), temporal_window=temporal, temporal_motion=temporal_motion, motion_block=motion_block,
-                     motion_paint=motion_paint,
+                     motion_paint=motion_paint, motion_levels=motion_levels,
                      data_path=os.path.join(fx.GOLDEN, "data"), color_mode=color_mode, hull=hull, footprint=footprint,
                      hull_open_mm=open_mm, hull_close_mm=close_mm, clusters=clusters, cluster_paint=cluster_paint,
                      extremities=extremities, geodesic_paint=geodesic_paint if extremities else None,
@@ -239,6 +248,9 @@ if motion_block and not temporal:                                # (beside --tem
         print("frame %2d: %d of %d blocks listed, %d unique, %d moved, %d at the range; change %d -> %d voxels; median vector "
               "x %.1f y %.1f z %.1f mm (%.3f ms on the device)" % (t, ms["listed"], ms["blocks"], ms["unique"], ms["moved"], ms["clipped"],
                                                                    ms["cost0_sum"], ms["cost_sum"], med[0], med[1], med[2], ms["motion_ms"]))
+        if motion_levels:
+            print("          %d levels, vectors up to %d voxels: %d displacements tried, %d vectors borrowed from a neighbour's prediction"
+                  % (ms["levels"], ms["reach"], ms["evaluated"], ms["borrowed"]))
 if subtract or clip:
     for name, st in assignment.hull_ops().items():
         print("%s: %d of %d voxels leave the hull, %d stay (%d in the operand; %.3f ms on the device)" %

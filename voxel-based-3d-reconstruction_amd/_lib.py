@@ -304,6 +304,10 @@ SIGNATURES = {
     "vc_fetch_motion": (ctypes.c_int, [c_ctx, ctypes.c_void_p, c_u64p]),
     "vc_hull_warp": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(motion.WarpStats)]),
     "vc_paint_motion": (ctypes.c_int, [c_ctx]),
+    "vc_hull_motion_pyramid": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(motion.PyramidStats)]),
+    "vc_fetch_motion_level": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_void_p, c_u64p]),
+    "vc_fetch_motion_occupancy": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, c_u64p, c_u64p]),
     "vc_hull_temporal_motion": (ctypes.c_int, [c_ctx, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(motion.TemporalMotionStats)]),
     "vc_fetch_temporal_motion": (ctypes.c_int, [c_ctx, ctypes.c_void_p, c_u64p]),

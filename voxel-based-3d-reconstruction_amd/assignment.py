@@ -167,7 +167,9 @@ _carry = {}              # what a frame leaves for the next: the clusters' centr
 HULL_SUBTRACT_REG, HULL_CLIP_REG = 3, 2      # the registers of CarveEngine that hold the two operands
 MOTION_REG = 1                               # ... and the one that holds the previous frame's hull for the motion stage
 BASE_SETTINGS = {"data_path": "data", "num_cameras": 4, "device": 0, "mode": "fused", "views_threshold": 4,
-                 "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS, "footprint": "centre", "normal_radius_mm": None}
+                 "color_camera": COLOR_CAMERA_INDEX, "bounds": DEFAULT_BOUNDS, "footprint": "centre", "normal_radius_mm": None,
+                 # how the motion stage matches, not whether it runs: the stage's check (_check_motion) covers them
+                 "motion_levels": 0, "motion_refine": 1}
 
 
 # -- the checks of configure(): a check takes the merged settings and raises ValueError; these make one for the setting `name` ----
@@ -236,7 +238,8 @@ def _check_motion(s):
         raise ValueError("motion_block %r, expected 0 or one of %s" % (b, motion.BLOCKS))
     if not isinstance(s["motion_paint"], (bool, np.bool_)):
         raise ValueError("motion_paint %r, expected True or False" % (s["motion_paint"],))
-    motion.check_params(b if b else motion.BLOCKS[0], s["motion_apron"], s["motion_search"])
+    search = motion.check_params(b if b else motion.BLOCKS[0], s["motion_apron"], s["motion_search"])[2]
+    motion.check_pyramid(s["motion_levels"], s["motion_refine"], search)
     if s["motion_paint"] and (s["cluster_paint"] or s["geodesic_paint"] is not None):
         raise ValueError("motion_paint excludes cluster_paint and geodesic_paint: one pass colours the records")
 
@@ -330,7 +333,11 @@ def _run_motion(s):
     """The frame's motion field against the previous frame's hull (see configure); then this frame's hull is kept for the next."""
     from . import motion
     if _carry.get("motion_kept"):
-        stats = _engine.hull_motion(MOTION_REG, int(s["motion_block"]), s["motion_apron"], int(s["motion_search"]))
+        if s["motion_levels"]:
+            stats = _engine.hull_motion(MOTION_REG, int(s["motion_block"]), s["motion_apron"], int(s["motion_search"]),
+                                        levels=int(s["motion_levels"]), refine=int(s["motion_refine"]))
+        else:                                    # (the four-argument call it always was)
+            stats = _engine.hull_motion(MOTION_REG, int(s["motion_block"]), s["motion_apron"], int(s["motion_search"]))
         rows = _engine.fetch_motion()
         _last["motion"] = {"stats": stats, "rows": rows, "description": motion.describe(rows, _engine.grid, _engine.bounds)}
         if s["motion_paint"]:
@@ -442,12 +449,15 @@ def configure(frame_source=None, **settings):
     topology, on the device; the hull itself stays.  skeleton_anchors = "extrema" pins the skeleton at the floor contact and the
     extremities of extremities=K, which turns a noisy curve skeleton into a stick figure; it is refused without extremities=K.
     skeleton() returns the last frame's.
-    12. motion_block, motion_apron, motion_search, motion_paint: when motion_block = b in {4, 8, 16} (0, the default, runs
+    12. motion_block, motion_apron, motion_search, motion_paint, motion_levels, motion_refine: when motion_block = b in {4, 8, 16} (0, the default, runs
     nothing), every frame's hull is kept in register 1 of the engine (CarveEngine.keep_hull), and from the second frame of a
     session on CarveEngine.hull_motion(1, b, motion_apron, motion_search) estimates, before that, where each block of b^3 voxels
     went since the previous frame (motion_apron = None is b // 2; b + 2 motion_apron + 2 motion_search <= 64).  motion() returns
     the last frame's field.  motion_paint=True then paints every voxel by its block's vector (CarveEngine.paint_motion); it
     excludes cluster_paint and geodesic_paint.  The hull that is matched and kept is the one the stages above leave.
+    motion_levels = L in 1..3 (0, the default, is the single-level field) makes the call coarse to fine,
+    CarveEngine.hull_motion(..., levels=L, refine=motion_refine): vectors up to motion_search 2^L + motion_refine (2^L - 1) voxels
+    are found, and a block inside a solid body takes its surroundings' vector (motion_refine in 1..motion_search, default 1).
     13. output, output_level: "all" (the default) returns every survivor, as the reference does.  "shell" runs
     CarveEngine.hull_shell(output_level) and returns the arrays of CarveEngine.fetch_shell_viewer(), made on the device: only the
     voxels with an exposed face, which is everything an opaque cube viewer can show (at level 0 the same rows the full arrays

@@ -34,9 +34,9 @@ static int motion_sized(vc_ctx *ctx, vc_ctx::Motion &M, const MotionGrid &g)
     return VC_OK;
 }
 
-// The field from B's words to A's into M (vec, rows, counters on the device), for vc_hull_motion and vc_hull_temporal_motion.
+// The listed blocks of A and B over g into M: counters and vec zeroed, the rows with block, count_a and count_b at their ranks.
 // Synchronous: the listed blocks are read back in the middle, they size the rows and the matching launch.
-static int motion_field(vc_ctx *ctx, const char *what, vc_ctx::Motion &M, const MotionGrid &g, const uint64_t *a, const uint64_t *b, uint64_t &listed)
+static int motion_listed(vc_ctx *ctx, const char *what, vc_ctx::Motion &M, const MotionGrid &g, const uint64_t *a, const uint64_t *b, uint64_t &listed)
 {
     const uint64_t nblocks = g.nblocks;
     const uint32_t ngroups = (uint32_t)((nblocks + 63) / 64);
@@ -59,6 +59,16 @@ static int motion_field(vc_ctx *ctx, const char *what, vc_ctx::Motion &M, const 
                            (const uint32_t *)M.counts.ptr, (const uint64_t *)M.mask.ptr, (const uint32_t *)ctx->d_rscan.off.ptr,
                            (const uint64_t *)ctx->d_rscan.boff.ptr, M.rows.ptr, listed);
         VC_HIP(ctx, hipGetLastError());
+    }
+    return VC_OK;
+}
+
+// The field from B's words to A's into M (vec, rows, counters on the device), for vc_hull_motion, vc_hull_temporal_motion and the
+// coarsest level of vc_hull_motion_pyramid.
+static int motion_field(vc_ctx *ctx, const char *what, vc_ctx::Motion &M, const MotionGrid &g, const uint64_t *a, const uint64_t *b, uint64_t &listed)
+{
+    VC_TRY(motion_listed(ctx, what, M, g, a, b, listed));
+    if (listed) {
         MotionMatchParams mp;
         memset(&mp, 0, sizeof mp);
         mp.a = a; mp.b = b; mp.g = g; mp.rows = M.rows.ptr; mp.listed = listed; mp.vec = M.vec.ptr; mp.ctr = M.ctr.ptr;
@@ -108,6 +118,7 @@ int vc_hull_motion(vc_ctx *ctx, uint32_t reg, uint32_t block, uint32_t apron, ui
     stats->blocks = g.nblocks; stats->listed = listed; stats->moved = M.h[0]; stats->unique = M.h[1]; stats->clipped = M.h[2];
     stats->cost0_sum = M.h[3]; stats->cost_sum = M.h[4]; stats->a = pass.S; stats->b = B.count;
     M.g = g; M.listed = listed; M.reg = reg;
+    M.levels = 0; M.refine = 0; M.reach = search;
     M.stamp = ctx->result_gen;
     return VC_OK;
 }
@@ -184,8 +195,10 @@ int vc_paint_motion(vc_ctx *ctx)
     if (!ctx->survivors) return VC_OK;
     StepBuf &cur = ctx->sb[ctx->cur];
     VC_HIP(ctx, hipSetDevice(ctx->device));
+    MotionGrid g = ctx->motion.g;
+    g.s = ctx->motion.reach;                     // the largest component a vector of the field can have (vc_hull_motion: the search range)
     hipLaunchKernelGGL(k_motion_paint, dim3((uint32_t)((ctx->survivors + kMotionBlock - 1) / kMotionBlock)), dim3(kMotionBlock), 0, ctx->stream,
-                       cur.records.ptr, ctx->survivors, ctx->motion.g, (const uint32_t *)ctx->motion.vec.ptr);
+                       cur.records.ptr, ctx->survivors, g, (const uint32_t *)ctx->motion.vec.ptr);
     VC_HIP(ctx, hipGetLastError());
     VC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VC_OK;

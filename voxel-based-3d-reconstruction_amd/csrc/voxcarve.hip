@@ -51,6 +51,7 @@
 #include "vc_temporal.h"
 #include "vc_setops.h"
 #include "vc_motion.h"
+#include "vc_motion_pyramid.h"
 #include "vc_temporal_motion.h"
 #include "vc_normals.h"
 #include "vc_texture.h"
@@ -441,7 +442,15 @@ struct vc_ctx {
         uint64_t stamp = kNever;         // the field belongs to the vc_hull_motion that ran on the current result ...
         uint32_t reg = 0;                // ... against this register, which has not been written since (motion_reg_written)
         uint64_t listed = 0;
+        uint32_t levels = 0, refine = 0; // the coarser levels and the refine radius of the call that made it (vc_hull_motion: 0, 0) ...
+        uint32_t reach = 0;              // ... and the largest component its vectors can have (vc_hull_motion: the search range)
     };
+    // vc_hull_motion_pyramid: the coarser levels 1..3 of the field in `motion` (level l in level[l - 1]: its blocks, rows, vectors
+    // and counters, with its grid and listed blocks), and their occupancy words of A and of B.  Current while `motion` is.
+    struct Pyramid {
+        Motion level[3];
+        DevBuf<uint64_t> wa[3], wb[3];
+    } pyramid;
     // vc_hull_temporal: the ring of the last `window` hulls ([window][npad] words, slot `head` the newest), the previous output P,
     // the staging buffer of O_t (swapped with P by a finished call), the five counters and their read-back, the records' vote and
     // `added` bytes.  Ring, P, window, head and pushes OUTLIVE a result: a carve leaves them alone, geometry_changed starts them over.
@@ -3869,6 +3878,7 @@ int vc_hull_compare(vc_ctx *ctx, uint32_t reg, uint32_t flags, vc_compare_stats_
 // From here on the host side of a family lives beside its kernels in a file of its own under host/, included once, in dependency
 // order (still this one translation unit: a file may use what stands above it).
 #include "host/motion.h"     // vc_hull_motion, vc_hull_warp, vc_paint_motion (the kept hulls of the set algebra above)
+#include "host/motion_pyramid.h"    // vc_hull_motion_pyramid and its per-level fetches (motion_grid, motion_listed and motion_field of motion.h)
 #include "host/temporal_motion.h"   // vc_hull_temporal_motion (the vote's ring and hand-over above, motion_field of motion.h)
 #include "host/render.h"     // vc_render, vc_fetch_render (the pass frame above); the colouring pass's vc_fetch_visibility, vc_fetch_depth
 #include "host/mc.h"         // vc_marching_cubes over the dense volume (densify_words and scan_counts above)

@@ -835,31 +835,76 @@ class CarveEngine:
         return self.combine_hull("copy", reg)
 
     # -- block motion between a kept hull and the current result (vc_hull_motion, vc_hull_warp, vc_paint_motion) --------------------
-    def hull_motion(self, reg=0, block=8, apron=None, search=4):
+    def hull_motion(self, reg=0, block=8, apron=None, search=4, levels=0, refine=1):
         """Estimates where each block of `block`^3 voxels went between the hull of register `reg` (the previous frame:
         keep_hull) and the current carve result: exhaustive matching of a window of the block grown by `apron` cells per side
         (None: block // 2) over the displacements of [-search, search]^3 (contract: include/voxcarve.h).  block in {4, 8, 16},
         apron in 0..16, search in 1..8, block + 2 apron + 2 search <= 64.  Changes nothing.  Returns the stats as a dict:
-        blocks, listed, moved, unique, clipped, cost0_sum, cost_sum, a, b, motion_ms."""
+        blocks, listed, moved, unique, clipped, cost0_sum, cost_sum, a, b, motion_ms.
+
+        levels = L in 1..3 is the coarse-to-fine field (vc_hull_motion_pyramid): both hulls are halved L times, the coarsest
+        level is matched as above, and every finer level chooses among the displacements within `refine` (1..search) of twice its
+        parent block's vector and of twice the vectors of the parent's face neighbours, so vectors up to
+        reach = search 2^L + refine (2^L - 1) voxels are found.  The dict then also holds levels, refine, reach, listed_level and
+        dims_level (lists over the levels 0..3), evaluated and borrowed.  The field is fetch_motion's, warp_hull's and
+        paint_motion's either way; fetch_motion_level and fetch_motion_occupancy return the coarser levels."""
         from . import motion
         block, apron, search = motion.check_params(block, apron, search)
-        st = motion.MotionStats()
-        self._check(self._L.vc_hull_motion(self._ctx, int(reg), block, apron, search, 0, ctypes.byref(st)), "vc_hull_motion")
+        levels, refine = motion.check_pyramid(levels, refine, search)
+        if levels == 0:
+            st = motion.MotionStats()
+            self._check(self._L.vc_hull_motion(self._ctx, int(reg), block, apron, search, 0, ctypes.byref(st)), "vc_hull_motion")
+            self._motion = (block, apron, search)
+            self._motion_pyramid = (0, refine, search)
+            return _stats(st)
+        st = motion.PyramidStats()
+        self._check(self._L.vc_hull_motion_pyramid(self._ctx, int(reg), block, apron, search, levels, refine, 0, ctypes.byref(st)),
+                    "vc_hull_motion_pyramid")
         self._motion = (block, apron, search)
-        return _stats(st)
+        self._motion_pyramid = (levels, refine, int(st.reach))
+        return motion.pyramid_stats_dict(st)
 
     def fetch_motion(self):
         """The field of the last hull_motion as a dict of arrays over the listed blocks, ascending block index: block u32 [L],
         ijk int64 [L, 3] (the block's position in blocks), d i8 [L, 3] (voxels, x y z), cost, cost0 u32, count_a, count_b,
-        ties u16, flags u8 (bit 0: clipped by the search range); and the scalars grid, edge, apron, search.  Fails once a carve
-        or a pass has changed the hull, or the register has been written."""
+        ties u16, flags u8 (bit 0: clipped by the search range); and the scalars grid, edge, apron, search.  After
+        hull_motion(levels > 0) flags has bit 1 too (borrowed from a neighbour's prediction) and the dict gains the scalars
+        levels, refine and reach; after a single-level call it is the dict it always was.  Fails once a carve or a pass has
+        changed the hull, or the register has been written."""
+        out = self.fetch_motion_level(0)
+        if not out["levels"]:
+            for key in ("levels", "refine", "reach"):
+                del out[key]
+        return out
+
+    def fetch_motion_level(self, level):
+        """The rows of level `level` (0..levels) of the last hull_motion as the dict of fetch_motion; grid is that level's (level
+        0 is the field itself).  Fails when fetch_motion fails, and for a level the field does not have."""
         from . import motion
+        level = int(level)
+        name = "vc_fetch_motion_level" if level else "vc_fetch_motion"
+        call = (lambda rows, n: self._L.vc_fetch_motion_level(self._ctx, level, rows, n)) if level else \
+            (lambda rows, n: self._L.vc_fetch_motion(self._ctx, rows, n))
         n = ctypes.c_uint64(0)
-        self._check(self._L.vc_fetch_motion(self._ctx, None, ctypes.byref(n)), "vc_fetch_motion")
+        self._check(call(None, ctypes.byref(n)), name)
         raw = np.zeros(int(n.value), dtype=motion.ROW_DTYPE)
         if n.value:
-            self._check(self._L.vc_fetch_motion(self._ctx, raw.ctypes.data_as(ctypes.c_void_p), None), "vc_fetch_motion")
-        return motion.rows_dict(raw, self.grid, *getattr(self, "_motion", (8, 4, 4)))
+            self._check(call(raw.ctypes.data_as(ctypes.c_void_p), None), name)
+        levels, refine, reach = getattr(self, "_motion_pyramid", (0, 1, getattr(self, "_motion", (8, 4, 4))[2]))
+        out = motion.rows_dict(raw, motion.level_grid(self.grid, level), *getattr(self, "_motion", (8, 4, 4)))
+        out.update(levels=levels, refine=refine, reach=reach)
+        return out
+
+    def fetch_motion_occupancy(self, level, which):
+        """uint64 [ceil(n_l / 64)]: the occupancy words of level `level` of the last hull_motion, which = 0 the current result's
+        (A), 1 the register's (B); 64 cells per word in the level's linear order (iz nx_l + ix) ny_l + iy."""
+        n = ctypes.c_uint64(0)
+        self._check(self._L.vc_fetch_motion_occupancy(self._ctx, int(level), int(which), None, ctypes.byref(n)), "vc_fetch_motion_occupancy")
+        words = np.zeros(int(n.value), dtype=np.uint64)
+        if n.value:
+            self._check(self._L.vc_fetch_motion_occupancy(self._ctx, int(level), int(which), words.ctypes.data_as(_lib.c_u64p), None),
+                        "vc_fetch_motion_occupancy")
+        return words
 
     def warp_hull(self, src=0, dst=1):
         """Writes to register `dst` the prediction of the current result from the hull of register `src` and the field of the

@@ -8,6 +8,8 @@ import numpy as np
 BLOCKS = (4, 8, 16)
 MAX_APRON, MAX_SEARCH, ROW_BITS = 16, 8, 64
 FLAG_CLIPPED = 1
+MAX_LEVELS = 3                               # coarser levels of vc_hull_motion_pyramid
+FLAG_BORROWED = 2                            # (a pyramid's rows: the vector came from a neighbour's prediction)
 
 
 class MotionRow(ctypes.Structure):           # vc_motion_t
@@ -25,6 +27,14 @@ class MotionStats(ctypes.Structure):         # vc_motion_stats_t
     _fields_ = [("blocks", ctypes.c_uint64), ("listed", ctypes.c_uint64), ("moved", ctypes.c_uint64), ("unique", ctypes.c_uint64),
                 ("clipped", ctypes.c_uint64), ("cost0_sum", ctypes.c_uint64), ("cost_sum", ctypes.c_uint64), ("a", ctypes.c_uint64),
                 ("b", ctypes.c_uint64), ("motion_ms", ctypes.c_float)]
+
+
+class PyramidStats(ctypes.Structure):        # vc_motion_pyramid_stats_t
+    _fields_ = [("blocks", ctypes.c_uint64), ("listed", ctypes.c_uint64), ("moved", ctypes.c_uint64), ("unique", ctypes.c_uint64),
+                ("clipped", ctypes.c_uint64), ("cost0_sum", ctypes.c_uint64), ("cost_sum", ctypes.c_uint64), ("a", ctypes.c_uint64),
+                ("b", ctypes.c_uint64), ("levels", ctypes.c_uint32), ("refine", ctypes.c_uint32), ("reach", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("listed_level", ctypes.c_uint64 * 4), ("dims_level", (ctypes.c_uint32 * 3) * 4),
+                ("evaluated", ctypes.c_uint64), ("borrowed", ctypes.c_uint64), ("motion_ms", ctypes.c_float)]
 
 
 class WarpStats(ctypes.Structure):           # vc_warp_stats_t
@@ -55,6 +65,44 @@ def check_params(block, apron, search):
     if block + 2 * apron + 2 * search > ROW_BITS:
         raise ValueError("motion: block + 2 apron + 2 search = %d exceeds the %d bits of a row" % (block + 2 * apron + 2 * search, ROW_BITS))
     return block, apron, search
+
+
+def check_pyramid(levels, refine, search):
+    """(levels, refine) as integers; ValueError outside the ranges of vc_hull_motion_pyramid: levels in 0..MAX_LEVELS, refine in
+    1..search (checked with levels = 0 too, where it is not used)."""
+    for name, v in (("levels", levels), ("refine", refine)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("motion: %s %r, expected an integer" % (name, v))
+    levels, refine, search = int(levels), int(refine), int(search)
+    if not 0 <= levels <= MAX_LEVELS:
+        raise ValueError("motion: %r coarser levels, expected 0..%d" % (levels, MAX_LEVELS))
+    if not 1 <= refine <= search:
+        raise ValueError("motion: refine radius %r not in 1..search = %d" % (refine, search))
+    return levels, refine
+
+
+def reach(search, levels, refine):
+    """The largest component a vector of the field can have: search 2^L + refine (2^L - 1)."""
+    return int(search) * 2 ** int(levels) + int(refine) * (2 ** int(levels) - 1)
+
+
+def level_grid(grid, level):
+    """(nx, ny, nz) of level `level`: every level has ceil(n / 2) cells per axis of the one below."""
+    g = tuple(int(n) for n in grid)
+    for _ in range(int(level)):
+        g = tuple((n + 1) // 2 for n in g)
+    return g
+
+
+def pyramid_stats_dict(st):
+    """A filled PyramidStats as the dict CarveEngine.hull_motion(levels > 0) returns: the keys of MotionStats, then levels, refine,
+    reach, listed_level [4], dims_level [4][3] (zeros above `levels`), evaluated, borrowed."""
+    out = {name: int(getattr(st, name)) for name in ("blocks", "listed", "moved", "unique", "clipped", "cost0_sum", "cost_sum", "a", "b",
+                                                     "levels", "refine", "reach", "evaluated", "borrowed")}
+    out["listed_level"] = [int(v) for v in st.listed_level]
+    out["dims_level"] = [[int(v) for v in row] for row in st.dims_level]
+    out["motion_ms"] = float(st.motion_ms)
+    return out
 
 
 def vote_params(motion):
