@@ -6,11 +6,13 @@ setops_np, motion_np, texture_np, light_np, oracle.marching_np); nothing is rest
 which frame set it reads, whose labels it takes, what it invalidates, and the state that outlives a result (the vote's ring, the
 four hull registers, the images of the last render and of the passes over them).
 
-Four families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
+Five families of chains.  A (SEEDS, CHAIN_LEN, KINDS) is drawn as it was before the vote, the measurements and the skeleton existed
 and does not know them: tests/golden/chain_digests.json holds its records, so that it cannot move.  B (SEEDS_B, CHAIN_LEN_B,
 KINDS_B) draws from every kind, with carve -> temporal pairs on different slots in most chains.  tests/test_gpu_chain.py walks family
 A on the device; family B is held to its coverage conditions, its literal twins and its faults in tests/test_chain_model.py, and
-its walk on the device is not in the suite yet (REFUSAL_B names what its products' fetches are to refuse with there).
+its walk on the device is not in the suite (REFUSAL_B names what its products' fetches are to refuse with there): alone it passed
+on the device, all 24 chains, and exited clean; the whole suite's process with it aborted at exit once more ("The abort
+at exit").
 
 Family C (SEEDS_C, CHAIN_LEN_C, KINDS_C) is family A's kinds and the hull registers: keep, upload, release, combine, compare
 (tests/setops_np.py), motion, warp, paint_motion (tests/motion_np.py).  The model holds the four registers -- each None or
@@ -37,12 +39,26 @@ fetches of the three products refuse with while there are no images; tests/golde
 the digests of the records and of the three products; tests/test_gpu_chain.py walks the family on the device and compares every
 pixel after every step.
 
+Family E (SEEDS_E, CHAIN_LEN_E, KINDS_E) is family C's kinds, `temporal_motion` (vc_hull_temporal_motion, through
+temporal_motion_np.AlignedVote) and temporal_reset; every `motion` carries `levels` and `refine` from PYRAMID_SETTINGS and runs
+through motion_pyramid_np.match_pyramid where levels > 0.  The aligned vote goes on the SAME ring and P as the plain one
+(Model.ring()): a ring filled by the other kind of call starts over, in both directions; the ring keeps the aligned hulls; the
+call's own field is the product `temporal_field` (REFUSAL_E), refused while the votes are stale and after a plain vote, with no
+rows behind the first push of a ring.  A vote that changes nothing leaves the generation and every product, a current motion
+field included; one that changes the result takes the field with it.  A pyramid's `motion` product covers the rows of every
+level, the level words of A and B and the scalars; `warp` reads level 0; `paint_motion` scales by the reach behind a pyramid and
+by the search range behind a single level; a single-level call behind a pyramid leaves the levels 0..0.  A second vote on one
+result is drawn on purpose and refused with the library's words (OP_REFUSAL_E), also behind a vote that changed nothing;
+temporal_reset lifts it.  The plain vote, the measurements, the skeleton and the shell are not drawn here: the family's walk does
+not lean on family B's.  tests/golden/chain_digests_e.json holds, per chain and step, the digests of records, registers, products
+and ring; tests/test_gpu_chain.py walks the family on the device (test_chain_e).
+
 The hull's shell (vc_hull_shell) is no drawn kind: neither family's draws may move.  with_shell(ops, seed) puts `shell` operations
 at fixed places of a chain instead, without a random number; trace, run and replay take shell=True and walk the interleaved chain,
 whose original steps keep their records and their products (tests/test_chain_model.py asserts it).
 
   scene(grid)            one of GRIDS, the golden cameras, three frame sets (slots 0, 1, 2) with different hulls and colours
-  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B, C: CHAIN_LEN_C, D: CHAIN_LEN_D) operations with all their parameters, drawn
+  draw_chain(seed)       (scene, ops): CHAIN_LEN (family B: CHAIN_LEN_B, C: CHAIN_LEN_C, D: CHAIN_LEN_D, E: CHAIN_LEN_E) operations with all their parameters, drawn
                          with numpy.random.default_rng(seed) alone; some draws (min_voxels, the sources of a measurement, anchors,
                          which registers are filled, the hull of an upload) look at the model's state, so the chain is applied while
                          it is drawn
@@ -70,12 +86,14 @@ import geodesic_np as gn
 import light_np as ln
 import measure_np as mn
 import motion_np as mo
+import motion_pyramid_np as mp
 import normals_np as nn
 import photo_np as pn
 import render_np as rn
 import setops_np as so
 import shell_np as shn
 import surface_np as sn
+import temporal_motion_np as tmn
 import temporal_np as tpn
 import texture_np as tn
 import thin_np as thn
@@ -157,6 +175,20 @@ FAULTS_D = ("textured_survives_render", "lit_dies_with_carve", "stale_depth_maps
 LIGHT_POINTS = ((900.0, -1400.0, -2600.0), (-2000.0, 800.0, -1500.0), (0.0, 0.0, -3000.0))    # from the grid's centre, mm (up is -z)
 LIGHT_SUNS = ((0.35, -0.5, -1.0), (-0.6, 0.2, -0.7), (0.0, 0.0, -1.0))                         # from the surface towards the light
 FLOOR_CELL_MM, FLOOR_RGB = 170.0, ((70, 80, 90), (210, 200, 190))                               # test_gpu_light._floor's
+
+SEEDS_E = tuple(range(1001, 1013))          # family E: family C's kinds, the aligned vote and the motion pyramid
+CHAIN_LEN_E = 12
+VOTE_KINDS = ("temporal_motion", "temporal_reset")
+KINDS_E = KINDS_C + VOTE_KINDS
+PYRAMID_SETTINGS = ((0, 1), (1, 1), (2, 2), (3, 1), (1, 2), (2, 1))      # levels, refine (at most the search range) of a `motion`
+VOTE_PARAMS = ((4, 2, 2), (8, 4, 4), (4, 0, 1), (8, 4, 8), (16, 8, 4))   # block edge, apron, search range of an aligned vote
+# the product that only family E knows -> the refusal of vc_fetch_temporal_motion: while the votes are stale, and after a plain vote
+REFUSAL_E = {"temporal_field": "no field: call vc_hull_temporal_motion"}
+# why a call of family E is refused -> a substring of the library's message
+OP_REFUSAL_E = {"one_push": "one push per result"}
+FAULTS_E = ("field_survives_vote", "aligned_ring_keeps_raw", "plain_ring_kept_by_aligned", "pyramid_paint_by_search",
+            "levels_survive_single_motion")
+assert not set(REFUSAL_E) & set(PRODUCTS)
 
 LOW = np.uint64(0xffffffff)
 NOT_RGB = np.uint64(0xff000000ffffffff)
@@ -268,6 +300,25 @@ class Scene:
             self._matches[key] = rows
         return self._matches[key]
 
+    def match_pyramid(self, a, b_occ, b, ap, s, levels, refine, literal=False):
+        """motion_pyramid_np.match_pyramid of two hulls of this grid, cached as match is."""
+        key = (hashlib.sha1(np.packbits(a)).digest(), hashlib.sha1(np.packbits(b_occ)).digest(), b, ap, s, levels, refine, bool(literal))
+        if key not in self._matches:
+            self._matches[key] = (mp.match_pyramid_literal if literal else mp.match_pyramid)(a, b_occ, self.grid, b, ap, s, levels, refine)
+        return self._matches[key]
+
+
+class AlignedVote(tmn.AlignedVote):
+    """temporal_motion_np's state machine with the scene's cache of block matchings behind it."""
+
+    def __init__(self, sc, literal=False):
+        self.scene, self.literal = sc, literal
+        super().__init__()
+
+    def match(self, hull, last, grid, b, ap, s):
+        assert tuple(grid) == self.scene.grid
+        return self.scene.match(hull, last, b, ap, s, self.literal)
+
 
 _SCENES = {}
 
@@ -296,7 +347,11 @@ class Model:
     pass made before the hull changed, "texture_carve_slot" samples the carve's frame set instead of the call's,
     "recolour_stales_render" makes the render stale at a pass that only recolours, "render_follows_records" gives the pixels that
     keep the render's rgb the colours the records have now, "smooth_accepts_stale_normals" lets a smooth light read normals of a
-    hull that is gone, "steps_ignore_feed" lets texture refine against a frame set that has been fed since the carve."""
+    hull that is gone, "steps_ignore_feed" lets texture refine against a frame set that has been fed since the carve.  Family E's
+    (FAULTS_E): "field_survives_vote" keeps the motion field over a vote that changes the result, "aligned_ring_keeps_raw" lets the
+    aligned vote's ring keep the hulls as they were pushed, "plain_ring_kept_by_aligned" lets the aligned vote go on with a ring
+    and a P that the plain vote filled, "pyramid_paint_by_search" scales the paint behind a pyramid by the search range instead
+    of the reach, "levels_survive_single_motion" leaves a pyramid's coarser levels in the field behind a single-level call."""
 
     def __init__(self, sc, fault=None, literal=False, hw=RENDER_HW):
         self.scene = sc
@@ -312,6 +367,9 @@ class Model:
         self.mesh_shape = (0, 0)             # (V, F) of the last surface mesh
         self.painted = False                 # a colour pass or a paint has run since the carve
         self.vote = tpn.Vote()               # the ring and P of vc_hull_temporal: they outlive carves, passes and results
+        self.avote = AlignedVote(sc, literal)  # the same ring and P while vc_hull_temporal_motion fills them (temporal_motion_np's
+        self.aligned = False                 # words): `aligned` says which kind of call filled the ring; the other kind starts it over
+        self.vote_params = None              # block, apron, search of the last aligned vote: the scalars of its field
         self.labels = {}                     # what a measurement or a skeleton may read while the product of that name is valid:
         #                                      "clusters" (u8 labels, K), "geodesic" (u8 labels, extremities, distances),
         #                                      "component_labels" (the dict of components_np)
@@ -691,6 +749,10 @@ class Model:
     def _temporal(self, op):
         sc = self.scene
         hull, S0 = self.occ(), self.S
+        if self.aligned:                         # a ring filled by vc_hull_temporal_motion starts over
+            self.vote.reset()
+            self.avote.reset()
+            self.aligned = False
         ring_before, window_before = len(self.vote.ring), self.vote.window
         out, counts, st = self.vote.push(hull, op["window"], op["keep"], op["keep_off"])
         cc = self.carve["color_cam"]             # restored voxels: the carve's own frame set and colour camera
@@ -705,13 +767,71 @@ class Model:
         else:                                    # O_t == H_t: nothing is invalidated, the result generation stays
             assert np.array_equal(rec, self.records) and not added.any()
             self.products.update(own)
+            self.products.pop("temporal_field", None)            # (the field of an aligned vote before: a plain vote has none)
         return {"stats": st, "votes": votes, "added": added, "changed": changed, "ring_before": ring_before,
                 "window_before": window_before, "by_hysteresis": int((out & ~(counts >= st["on"])).sum())}
 
     def _temporal_reset(self, op):
         self.vote.reset()
+        self.avote.reset()
         self.products.pop("temporal", None)
+        self.products.pop("temporal_field", None)
         return {}
+
+    def ring(self):
+        """The hulls of the vote's ring, newest last: the raw ones of vc_hull_temporal, or the aligned ones (the newest raw) of
+        vc_hull_temporal_motion."""
+        return (self.avote if self.aligned else self.vote).ring
+
+    def ring_digest(self):
+        h = hashlib.sha1(b"aligned" if self.aligned else b"plain")
+        for hull in self.ring():
+            h.update(mo.words(hull).tobytes())
+        return h.hexdigest()
+
+    @staticmethod
+    def field_bytes(rows, b, a, s):
+        return Model.motion_bytes(rows, b, a, s)
+
+    def _temporal_motion(self, op):
+        """vc_hull_temporal_motion: the ring and P of _temporal, aligned by the block motion between the ring's newest hull and this
+        one before the count.  A second vote on one result is refused, as the plain one's would be."""
+        sc = self.scene
+        if "temporal" in self.products:          # also behind a vote that changed nothing; vc_temporal_reset lifts it
+            return {"refused": "one_push", "refusal": OP_REFUSAL_E["one_push"]}
+        if not self.aligned:                     # a ring filled by vc_hull_temporal starts over, P with it
+            if self.fault == "plain_ring_kept_by_aligned":
+                self.avote.window, self.avote.ring, self.avote.prev = self.vote.window, list(self.vote.ring), self.vote.prev
+            else:
+                self.avote.reset()
+            self.vote.reset()
+            self.aligned = True
+        hull = self.occ()
+        b, ap, s = op["block"], op["apron"], op["search"]
+        ring_before, window_before = len(self.avote.ring), self.avote.window
+        raw_before = list(self.avote.ring) if op["window"] == self.avote.window else []
+        out, counts, st = self.avote.push(hull, op["window"], op["keep"], op["keep_off"], b, ap, s)
+        if self.fault == "aligned_ring_keeps_raw":
+            self.avote.ring = (raw_before + [hull.copy()])[-op["window"]:]
+        cc = self.carve["color_cam"]             # restored voxels: the carve's own frame set and colour camera
+        rec, votes, added = tpn.records_after(self.records, hull, out, counts, self.grid, self.bounds, None if cc is None else sc.oc[cc],
+                                              None if cc is None else sc.frames[self.carve["slot"]][cc], sc.H, sc.W)
+        rows = self.avote.rows
+        self.vote_params = (b, ap, s)            # the scalars of the field that vc_fetch_temporal_motion returns
+        own = {"temporal": votes.tobytes() + added.tobytes(), "temporal_field": self.field_bytes(rows, b, ap, s)}
+        changed = bool(st["added"] or st["removed"])
+        field_before = "motion" in self.products
+        if changed:
+            kept = self.products.get("motion") if self.fault == "field_survives_vote" else None
+            self.records = rec
+            self._changed(own)
+            if kept is not None:
+                self.products["motion"] = kept
+        else:                                    # O_t == H_t: the generation and every product stay, a current motion field included
+            assert np.array_equal(rec, self.records) and not added.any()
+            self.products.update(own)
+        return {"stats": st, "votes": votes, "added": added, "changed": changed, "ring_before": ring_before, "window_before": window_before,
+                "rows": rows, "field_before": field_before, "field_after": "motion" in self.products}
 
     def components_current(self):
         """The components of a filter_components that is current and removed nothing: its labels are in the result's order."""
@@ -856,10 +976,29 @@ class Model:
         B = self.registers[op["reg"]]
         b, ap, s = op["block"], op["apron"], op["search"]
         a = self.occ()
+        L, refine = op.get("levels", 0), op.get("refine", 1)
+        if L:                                    # vc_hull_motion_pyramid: the field of every level, its rows' bytes, the level words
+            res = self.scene.match_pyramid(a, B["occ"], b, ap, s, L, refine, self.literal)      # of A and B and the scalars
+            self.field = {"rows": res["rows"][0], "b": b, "a": ap, "s": s, "reg": op["reg"], "levels": L, "refine": refine,
+                          "reach": res["reach"], "res": res}
+            self.products["motion"] = self.pyramid_bytes(res, b, ap, s)
+            return {"stats": mp.stats(res, a, B["occ"], self.grid, b), "rows": res["rows"][0], "res": res}
         rows = self.scene.match(a, B["occ"], b, ap, s, self.literal)
-        self.field = {"rows": rows, "b": b, "a": ap, "s": s, "reg": op["reg"]}
+        stale = self.field["res"] if self.fault == "levels_survive_single_motion" and self.field is not None and self.field.get("levels") else None
+        self.field = {"rows": rows, "b": b, "a": ap, "s": s, "reg": op["reg"], "levels": 0, "refine": refine, "reach": s, "res": None}
         self.products["motion"] = self.motion_bytes(rows, b, ap, s)
+        if stale is not None:                    # (the wrong model: the coarser levels of the pyramid before are still there)
+            self.products["motion"] += self.pyramid_bytes(stale, b, ap, s, first=1)
         return {"stats": mo.stats(rows, a, B["occ"], self.grid, b), "rows": rows}
+
+    @staticmethod
+    def pyramid_bytes(res, b, a, s, first=0):
+        """The rows of the levels first..L, the level words of A and B, and b, a, s, levels, refine, reach."""
+        parts = []
+        for l in range(first, res["levels"] + 1):
+            parts += [np.ascontiguousarray(res["rows"][l][k]).tobytes() for k in MOTION_ROW_KEYS]
+            parts += [mo.words(res["a"][l]).tobytes(), mo.words(res["b"][l]).tobytes()]
+        return b"".join(parts) + np.array([b, a, s, res["levels"], res["refine"], res["reach"]], dtype=np.uint32).tobytes()
 
     def _warp(self, op):
         f = self.field
@@ -872,7 +1011,10 @@ class Model:
     def _paint_motion(self, op):
         f = self.field
         assert self.motion_valid()
-        self.records = mo.paint(self.records, f["rows"], self.grid, f["b"], f["s"])
+        if f.get("levels") and self.fault != "pyramid_paint_by_search":      # behind a pyramid the colours scale by its reach
+            self.records = mp.paint(self.records, f["res"], self.grid, f["b"])
+        else:
+            self.records = mo.paint(self.records, f["rows"], self.grid, f["b"], f["s"])
         self.painted = True
         return {}
 
@@ -965,6 +1107,16 @@ def _draw(rng, sc, model, kind, hint=None):
         return {"op": kind, "window": window, "keep": keep, "keep_off": 1 if r < 0.35 else keep if r < 0.6 else int(rng.integers(1, keep + 1))}
     if kind == "temporal_reset":
         return {"op": kind}
+    if kind == "temporal_motion":                # family E: mostly the ring's own window; hint "window": that one, or "other"
+        cur = model.avote.window if model.aligned else 0
+        window = hint.get("window", cur if cur and rng.random() < 0.9 else pick((2, 3, 4)))
+        if window == "other":
+            window = pick([w for w in (2, 3, 4) if w != cur])
+        r = rng.random()
+        keep = window if r < 0.35 else int(rng.integers(1, window + 1))
+        b, ap, s = pick(VOTE_PARAMS, (0.3, 0.3, 0.15, 0.15, 0.1))
+        return {"op": kind, "window": window, "keep": keep, "keep_off": 1 if r < 0.35 else keep if r < 0.6 else int(rng.integers(1, keep + 1)),
+                "block": b, "apron": ap, "search": s}
     if kind == "measure":                        # among the sources that are current, the rarer ones more often
         have = [("all", 1.0), ("host", 1.0)] + [(s, 6.0) for s in ("clusters", "geodesic") if s in model.products] + \
             ([("components", 8.0)] if model.components_current() else [])
@@ -1012,6 +1164,10 @@ def _draw(rng, sc, model, kind, hint=None):
             op["distance"] = hint["distance"] if "distance" in hint else bool(rng.integers(2))
         else:
             op["block"], op["apron"], op["search"] = pick(MOTION_PARAMS, (0.25, 0.25, 0.25, 0.12, 0.13))
+            if "pyramid" in hint:                # family E: True a pyramid, False a single level, None either
+                some = [x for x in PYRAMID_SETTINGS if hint["pyramid"] is None or (x[0] > 0) == hint["pyramid"]]
+                L, r = pick(some)
+                op["levels"], op["refine"] = L, min(r, op["search"])
         return op
     if kind == "warp":
         src = model.field["reg"]
@@ -1073,14 +1229,14 @@ def model_of(seed, fault=None, literal=False):
 
 
 def family(seed):
-    return "B" if seed in SEEDS_B else "C" if seed in SEEDS_C else "D" if seed in SEEDS_D else "A"
+    return "B" if seed in SEEDS_B else "C" if seed in SEEDS_C else "D" if seed in SEEDS_D else "E" if seed in SEEDS_E else "A"
 
 
 def draw_chain(seed):
     """(scene, ops) of chain `seed`.  Family A: a carve, then CHAIN_LEN - 1 drawn operations; now and then a burst of hull-changing
     passes.  Family B: see _draw_chain_b.  Family C: see _draw_chain_c.  Family D: see _draw_chain_d."""
     if seed not in _CHAINS:
-        _CHAINS[seed] = {"A": _draw_chain, "B": _draw_chain_b, "C": _draw_chain_c, "D": _draw_chain_d}[family(seed)](seed)
+        _CHAINS[seed] = {"A": _draw_chain, "B": _draw_chain_b, "C": _draw_chain_c, "D": _draw_chain_d, "E": _draw_chain_e}[family(seed)](seed)
     return _CHAINS[seed]
 
 
@@ -1330,6 +1486,93 @@ def _draw_chain_d(seed):
     return sc, ops
 
 
+_WEIGHTS_E = {"carve": 1.2, "close": 0.3, "dilate": 0.3, "erode": 0.3, "open": 0.3, "filter_components": 0.3, "photo_carve": 0.3,
+              "color_visible": 0.4, "clusters": 0.3, "geodesic": 0.3, "hull_distance": 0.4, "hull_normals": 0.2, "render": 0.1,
+              "surface_mesh": 0.1, "keep": 0.6, "upload": 1.0, "release": 0.3, "combine": 0.6, "compare": 0.4, "motion": 1.6,
+              "warp": 0.5, "paint_motion": 0.5, "temporal_motion": 2.0, "temporal_reset": 0.2}
+assert set(_WEIGHTS_E) == set(KINDS_E) and not set(KINDS_E) & set(NEW_KINDS + ("shell",))
+
+
+def _draw_chain_e(seed):
+    """A carve, then CHAIN_LEN_E - 1 operations drawn from family C's kinds, the aligned vote (temporal_motion) and temporal_reset;
+    every `motion` draws its levels and its refine radius from PYRAMID_SETTINGS.  The plain vote, the measurements, the skeleton
+    and the shell are family B's and are not drawn.  As in family C, a combine, a comparison or a motion estimate drawn while
+    every register is empty becomes the keep that it needs, and a warp or a paint drawn without a current field the motion
+    estimate.  A vote drawn on a result that is already a vote's output becomes the carve that it asks for, with the vote behind
+    it; the refusal itself is drawn on purpose in the second sequence below.  The header refuses a vote in two more cases that no
+    chain reaches, as in family B: steps in flight (a pipelined carve collects both of its steps) and a frame set with input
+    waiting (nothing here feeds one).  Behind a carve (nine times in ten), and behind every second other operation once the queue
+    is empty, one of ten sequences is queued: the chain's first two in turn from the seed on (twelve chains of twelve operations
+    are too few to leave each sequence to chance), the later ones at random, the first of the list more often than not; T is the aligned vote, C' a carve of another frame
+    set than the last one, P a motion pyramid and M a single-level estimate against the register just kept:
+      T C' T C' T: carve -> vote pairs on frame sets whose masks are rolled against each other, so that blocks move;
+      T T (refused: one push per result) reset T (accepted: the first push of a ring changes nothing) C' T;
+      T keep C P T, with C the last carve once more: the ring holds this very hull, the vote changes nothing while a pyramid's
+      field is current, and the field stays;
+      T keep C' P T: a vote on a ring that holds another frame set's hull -- the result changes and the field dies;
+      keep C' T P warp paint_motion;  keep C' T P M: a single level behind a pyramid;
+      keep C' T P, a quiet pass, a write to the pyramid's register: the field of every level is stale, the quiet product stays;
+      a hull changer, T C' T: a vote on a pass's hull;  T C' T with another window (the ring starts over) C' T;
+      upload, combine or compare with it, release."""
+    rng = np.random.default_rng(seed)
+    sc = scene(GRIDS[int(rng.integers(len(GRIDS)))])
+    model = Model(sc)
+    kinds = list(_WEIGHTS_E)
+    p = np.array([_WEIGHTS_E[k] for k in kinds])
+    p /= p.sum()
+    pick = lambda seq: seq[int(rng.integers(len(seq)))]
+    ops, queue, queued = [], [], 0
+    while len(ops) < CHAIN_LEN_E:
+        hint = None
+        if not ops:
+            kind = "carve"
+        elif model.S == 0 and rng.random() < 0.5:
+            kind, queue = "carve", []
+        elif queue:
+            kind, hint = queue.pop(0)
+        else:
+            kind = kinds[int(rng.choice(len(kinds), p=p))]
+        if kind in ("combine", "compare", "motion") and not model.filled():
+            queue.insert(0, (kind, hint))
+            kind, hint = "keep", None
+        if kind in ("warp", "paint_motion") and not model.motion_valid():
+            queue.insert(0, (kind, None))
+            kind, hint = ("motion" if model.filled() else "keep"), None
+        if kind == "temporal_motion" and "temporal" in model.products and not (hint or {}).get("refused"):
+            queue.insert(0, (kind, hint))
+            kind, hint = "carve", {"not_slot": model.carve["slot"]}
+        if kind == "motion":
+            hint = dict({"pyramid": None}, **(hint or {}))
+        if kind == "carve" and (hint or {}).get("same"):         # the last carve once more: the same hull, another result
+            op = dict(last_carve, first=None if last_carve["first"] is None else dict(last_carve["first"]))
+        else:
+            op = _draw(rng, sc, model, kind, hint)
+        if kind == "carve":
+            last_carve = op
+        if not queue and rng.random() < (0.9 if kind == "carve" else 0.5):
+            T, other = ("temporal_motion", None), ("carve", {"not_slot": op["slot"] if kind == "carve" else model.carve["slot"]})
+            again = ("carve", {"same": True})
+            reg = {"reg": int(rng.integers(REGISTERS))}
+            K, P = ("keep", reg), ("motion", dict(reg, pyramid=True))
+            writer = pick(("keep", "upload", "release"))
+            which = (seed + 4 * queued) % 10 if queued < 2 else 0 if rng.random() < 0.6 else int(rng.integers(10))
+            queued += 1
+            queue = [[T, other, T, other, T],
+                     [T, ("temporal_motion", {"refused": True}), ("temporal_reset", None), T, other, T],
+                     [T, K, again, P, T],
+                     [T, K, other, P, T],
+                     [K, other, T, P, ("warp", None), ("paint_motion", None)],
+                     [K, other, T, P, ("motion", dict(reg, pyramid=False))],
+                     [K, other, T, P, (pick(QUIET), None), (writer, reg)],
+                     [(pick(HULL_CHANGERS), None), T, other, T],
+                     [T, other, ("temporal_motion", {"window": "other"}), other, T],
+                     [("upload", reg), (pick(("combine", "compare")), reg), ("release", reg)],
+                     ][which]
+        model.apply(op)
+        ops.append(op)
+    return sc, ops
+
+
 SHELL_AFTER = (2, 6, 10)                     # a shell behind these steps of a chain ...
 SHELL_LEVELS = (0, 0, 1, 0, 2)               # ... at these levels in turn, starting at the seed's place in the list
 SHELL_STALERS = HULL_CHANGERS + ("carve", "temporal")
@@ -1393,6 +1636,11 @@ def replay(seed, upto=None, fault=None, literal=False, shell=False):
     return model
 
 
+def replay_out(seed, step, shell=False):
+    """What step `step` of chain `seed` returns, on the model in front of it."""
+    return replay(seed, upto=step, shell=shell).apply(walk_of(seed, shell)[1][step])
+
+
 def describe_op(op):
     """The parameters of an operation as one short line (arrays as their type and shape), for the failure messages."""
     return ", ".join("%s=%s" % (k, ("%s%r" % (v.dtype.name, v.shape)) if isinstance(v, np.ndarray) else repr(v)) for k, v in op.items())
@@ -1433,6 +1681,11 @@ def trace(seed, fault=None, shell=False):
                "fed_before": bool(model.carve is not None and (model.prepared_again or model.carve["slot"] in model.dirty))}
         out = model.apply(op)
         row["refused"] = out.get("refused")
+        row["ring_digest"] = model.ring_digest()
+        row["field_levels"] = model.field.get("levels", 0) if model.motion_valid() else None
+        for k in ("field_before", "field_after"):
+            if k in out:
+                row[k] = out[k]
         row["dropped"] = out.get("dropped", ())
         row["pictures"] = tuple(sorted(model.pictures))
         row["pictures_digest"] = model.pictures_digest()

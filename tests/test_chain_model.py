@@ -14,6 +14,10 @@ Family D (chain_model.SEEDS_D) is family A's kinds and the passes over a render'
 and the feed of the carve's frame set, with the refusals that the model expects drawn on purpose.  tests/test_gpu_chain.py walks
 it on the device; here it has its coverage conditions, its eight faults, the literal twins of texture and light inside the model,
 and golden digests of the records and of the three passes' images (tests/golden/chain_digests_d.json).
+Family E (chain_model.SEEDS_E) is family C's kinds, the aligned vote (temporal_motion) and temporal_reset, with 0 to 3 coarser
+levels in every motion estimate.  tests/test_gpu_chain.py walks it on the device; here it has its coverage conditions, its faults,
+the switch between the two kinds of vote (scripted: the plain vote is not drawn), the literal twins of the aligned vote and of the
+pyramid, and golden digests of records, registers, products and ring (tests/golden/chain_digests_e.json).
 
 The coverage conditions below are conditions on the INPUTS of the GPU test (the seeds, the draw weights, the lengths), asserted here
 so that it cannot pass by doing nothing; where one fails, the seeds, the weights or the length change, never the thresholds.  Then:
@@ -822,3 +826,290 @@ def test_literal_twins_of_the_image_passes(traces_d):
             assert (cm.hashlib.sha1(m.records.tobytes()).hexdigest(), m.pictures_digest(), out.get("refused")) == \
                 (row["digest"], row["pictures_digest"], row["refused"]), (seed, step, cm.describe_op(op))
         assert ran["texture"] + ran["light"] >= 2, (seed, dict(ran))
+
+
+# ---- family E: the aligned vote and the motion pyramid ------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def traces_e():
+    return {seed: cm.trace(seed) for seed in cm.SEEDS_E}
+
+
+def _golden_e():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "chain_digests_e.json")) as f:
+        return json.load(f)
+
+
+def _digests_e(row):
+    """What tests/golden/chain_digests_e.json holds of a step: the records, the registers, the products and the vote's ring."""
+    return {"records": row["digest"], "registers": row["registers_digest"], "products": row["products_digest"], "ring": row["ring_digest"]}
+
+
+def test_family_e_constants():
+    assert cm.SEEDS_E == tuple(range(1001, 1013)) and cm.CHAIN_LEN_E == 12 and cm.family(cm.SEEDS_E[0]) == "E"
+    assert not set(cm.SEEDS_E) & (set(cm.SEEDS) | set(cm.SEEDS_B) | set(cm.SEEDS_C) | set(cm.SEEDS_D))
+    assert set(cm.KINDS_E) - set(cm.KINDS_C) == {"temporal_motion", "temporal_reset"}
+    assert not set(cm.KINDS_E) & {"temporal", "measure", "thin", "shell"}       # (family B's: this family's walk does not lean on them)
+    assert {L for L, _ in cm.PYRAMID_SETTINGS} == {0, 1, 2, 3} and max(r for _, r in cm.PYRAMID_SETTINGS) > 1
+    assert cm.REFUSAL_E == {"temporal_field": "no field: call vc_hull_temporal_motion"} and not set(cm.REFUSAL_E) & set(cm.PRODUCTS)
+    assert set(cm.FAULTS_E) >= {"field_survives_vote", "aligned_ring_keeps_raw", "plain_ring_kept_by_aligned", "pyramid_paint_by_search",
+                                "levels_survive_single_motion"}
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    assert cm.OP_REFUSAL_E["one_push"] in open(os.path.join(root, "include", "voxcarve.h")).read()
+    host = open(os.path.join(root, "voxel-based-3d-reconstruction_amd", "csrc", "host", "temporal_motion.h")).read()
+    assert '"%s' % cm.REFUSAL_E["temporal_field"] in host and "(%s)" % cm.OP_REFUSAL_E["one_push"] in host     # (the library's words)
+
+
+def _coverage_e(traces_e):
+    n = collections.Counter()
+    levels = collections.Counter()
+    for seed, rows in traces_e.items():
+        assert len(rows) == cm.CHAIN_LEN_E and rows[0]["op"] == "carve"
+        for k, r in enumerate(rows):
+            op, p, st = r["op"], r["params"], r["stats"]
+            n[op] += 1
+            prev = rows[k - 1] if k else None
+            if op == "motion":
+                levels[p["levels"]] += 1
+                assert 1 <= p["refine"] <= p["search"]
+                if p["levels"]:
+                    n["borrowed > 0"] += st["borrowed"] > 0 or any((np.asarray(lv["flags"]) & 2).any() for lv in cm.replay_out(seed, k)["res"]["rows"])
+                    assert r["field_levels"] == p["levels"]
+                    # what stands behind the pyramid while its field is current
+                    for later in rows[k + 1:]:
+                        if later["op"] in ("warp", "paint_motion") and later["motion_reg_before"] is not None:
+                            n[later["op"] + " behind a pyramid"] += 1
+                        if later["op"] == "motion":
+                            n["a single level behind a pyramid"] += later["params"]["levels"] == 0
+                        if later["op"] in ("motion", "carve") or later["motion_reg_before"] is None:
+                            break
+                        if later["op"] in cm.REGISTER_WRITERS and later["motion_reg"] is None and "motion" not in later["valid"]:
+                            writes = later["params"]["dst" if later["op"] == "warp" else "reg"] == p["reg"]
+                            n["a pyramid made stale by a write to its register"] += writes
+                            if writes:           # (nothing else left: the write changes no result)
+                                assert set(later["valid"]) == set(later["valid_before"]) - {"motion"}
+                            break
+                elif r["field_levels"] is not None:
+                    assert r["field_levels"] == 0
+            if op == "temporal_reset" and k + 1 < len(rows) and rows[k + 1]["op"] == "temporal_motion" and not rows[k + 1]["refused"]:
+                n["a reset then a vote"] += 1
+            if op != "temporal_motion":
+                continue
+            if r["refused"]:
+                assert r["refused"] == "one_push" and "temporal" in r["valid_before"] and r["valid"] == r["valid_before"] and r["after"] == r["before"]
+                n["refused: one push"] += 1
+                continue
+            n["votes"] += 1
+            n["frames >= 2"] += st["frames"] >= 2
+            n["first pushes"] += st["frames"] == 1
+            n["moved and changed"] += st["moved"] > 0 and r["changed"]
+            n["moved"] += st["moved"] > 0
+            n["changed"] += r["changed"]
+            made = r["made_by"]
+            n["behind a pipelined carve"] += made["op"] == "carve" and made["first"] is not None
+            n["behind a footprint carve"] += made["op"] == "carve" and made["footprint"] != "centre"
+            n["on a pass's hull"] += made["op"] != "carve"
+            n["a window change"] += r["ring_before"] > 0 and r["window_before"] != p["window"]
+            assert "temporal" in r["valid"] and "temporal_field" in r["valid"]
+            if st["frames"] == 1:
+                assert not r["changed"] and st["listed"] == 0
+            if r["field_before"]:
+                if r["changed"]:
+                    assert not r["field_after"]
+                    n["the result changes and the field dies"] += 1
+                else:
+                    assert r["field_after"] and r["valid"]["motion"] == r["valid_before"]["motion"]
+                    n["nothing changes and the field survives"] += 1
+            if not r["changed"]:
+                assert {k_: v for k_, v in r["valid"].items() if k_ not in ("temporal", "temporal_field")} == \
+                    {k_: v for k_, v in r["valid_before"].items() if k_ not in ("temporal", "temporal_field")}
+    return n, levels
+
+
+def test_coverage_of_family_e(traces_e):
+    """What the 12 chains of family E exercise of the aligned vote and the motion pyramid (the issue's list: conditions on the
+    draw, met by the draw's weights and queues)."""
+    n, levels = _coverage_e(traces_e)
+    print(sorted(n.items()), sorted(levels.items()))
+    for kind in cm.VOTE_KINDS + cm.REGISTER_KINDS:
+        assert n[kind] >= 1, kind
+    assert set(levels) == {0, 1, 2, 3}, levels
+    assert n["frames >= 2"] > n["first pushes"]
+    assert 4 * n["moved and changed"] >= n["votes"], (n["moved and changed"], n["votes"])
+    for name in ("behind a pipelined carve", "behind a footprint carve", "on a pass's hull", "a window change", "a reset then a vote",
+                 "refused: one push", "nothing changes and the field survives", "the result changes and the field dies",
+                 "a pyramid made stale by a write to its register", "warp behind a pyramid", "paint_motion behind a pyramid",
+                 "a single level behind a pyramid", "borrowed > 0"):
+        assert n[name] >= 2, (name, n[name])
+
+
+def test_family_e_is_held_to_its_digests(traces_e):
+    """The records, the registers, the products and the vote's ring behind every step of family E, and a second draw of it: the
+    same operations, the same digests."""
+    want = _golden_e()
+    assert sorted(want) == sorted(str(s) for s in cm.SEEDS_E)
+    for seed in cm.SEEDS_E:
+        assert [_digests_e(r) for r in traces_e[seed]] == want[str(seed)], seed
+    for seed in cm.SEEDS_E[:3]:
+        sc, ops = cm.draw_chain(seed)
+        sc2, ops2 = cm._draw_chain_e(seed)                       # (drawn again, past the cache)
+        assert sc2 is sc and [cm.describe_op(o) for o in ops2] == [cm.describe_op(o) for o in ops]
+        assert all(np.array_equal(a.get("palette"), b.get("palette")) for a, b in zip(ops, ops2))
+        again = cm.trace(seed)
+        assert [_digests_e(r) for r in again] == [_digests_e(r) for r in traces_e[seed]]
+        for upto in (1, 5, 9, cm.CHAIN_LEN_E):
+            m = cm.replay(seed, upto=upto)
+            row = traces_e[seed][upto - 1]
+            assert _digests_e(row) == {"records": cm.hashlib.sha1(m.records.tobytes()).hexdigest(), "registers": m.registers_digest(),
+                                       "products": cm.products_digest(m), "ring": m.ring_digest()}, (seed, upto)
+            assert m.products == row["valid"]
+
+
+def test_single_level_motion_in_family_e_is_family_cs():
+    """levels = 0: the `motion` product's bytes are what family C's are."""
+    seed, step = next((s, k) for s in cm.SEEDS_E for k, op in enumerate(cm.draw_chain(s)[1]) if op["op"] == "motion" and op["levels"] == 0)
+    m = cm.replay(seed, upto=step)
+    op = cm.draw_chain(seed)[1][step]
+    a, bo = m.occ(), m.registers[op["reg"]]["occ"]
+    out = m.apply(op)
+    rows = cm.mo.match(a, bo, m.grid, op["block"], op["apron"], op["search"])
+    assert m.products["motion"] == cm.Model.motion_bytes(rows, op["block"], op["apron"], op["search"])
+    assert out["stats"] == cm.mo.stats(rows, a, bo, m.grid, op["block"]) and m.field["levels"] == 0
+
+
+def _told_e(traces_e, fault, at_most=3):
+    """(seed, step, op) of the first step of each chain (at most `at_most` chains) at which the model with `fault` leaves other
+    digests than the right one."""
+    told = []
+    for seed in traces_e:
+        for step, op, out, model in cm.run(seed, fault):
+            got = {"records": cm.hashlib.sha1(model.records.tobytes()).hexdigest(), "registers": model.registers_digest(),
+                   "products": cm.products_digest(model), "ring": model.ring_digest()}
+            if got != _digests_e(traces_e[seed][step]):
+                told.append((seed, step, op["op"]))
+                break
+        if len(told) >= at_most:
+            break
+    return told
+
+
+@pytest.mark.parametrize("fault", [f for f in cm.FAULTS_E if f != "plain_ring_kept_by_aligned"])
+def test_a_wrong_model_of_family_e_is_told_apart(traces_e, fault):
+    """Each of family E's deliberate mistakes changes a byte that the walk on the device compares -- the records, a product or its
+    validity, the ring -- in at least one chain."""
+    told = _told_e(traces_e, fault)
+    print("%s told apart in family E at (seed, step, op):" % fault, told)
+    assert told, "no chain of family E tells the %s model from the right one" % fault
+
+
+def _ring_state(traces_e, frames=2):
+    """(seed, step): the first accepted vote of family E that left `frames` hulls or more in the ring and has a carve behind it."""
+    for seed, rows in traces_e.items():
+        for r in rows[:-2]:
+            if r["op"] == "temporal_motion" and not r["refused"] and r["stats"]["frames"] >= frames:
+                return seed, r["step"]
+    raise AssertionError("no such state")
+
+
+@pytest.mark.parametrize("fault", [None, "plain_ring_kept_by_aligned"])
+def test_the_ring_switch_in_both_directions(traces_e, fault):
+    """A ring filled by the other kind of call starts over, P with it: scripted on a replayed model of family E (whose ring the
+    aligned vote has filled), beside the two restatements, each fed with nothing but the hulls since the switch.  The plain vote is
+    not drawn in family E, so no chain of it can tell the model that lets the aligned vote take a plain ring over: this script
+    does."""
+    seed, step = _ring_state(traces_e)
+    m = cm.replay(seed, upto=step + 1, fault=fault)
+    assert m.aligned and len(m.ring()) >= 2
+    window = m.avote.window
+    slot = m.carve["slot"]
+    carve = lambda k: {"op": "carve", "slot": (slot + k) % 3, "mode": "fused", "min_views": m.scene.C, "color_cam": 1, "footprint": "centre", "first": None}
+    plain, aligned = tpn.Vote(), cm.tmn.AlignedVote()
+    params = dict(block=4, apron=2, search=2)
+    differs = False
+    script = [("temporal", plain, True), ("temporal", plain, False), ("temporal_motion", aligned, True), ("temporal_motion", aligned, False),
+              ("temporal", plain, True)]
+    for k, (kind, ref, fresh) in enumerate(script):
+        m.apply(carve(k + 1))
+        hull = m.occ()
+        if fresh:
+            ref.reset()
+        op = dict({"op": kind, "window": window, "keep": window, "keep_off": 1}, **(params if kind == "temporal_motion" else {}))
+        out = m.apply(op)
+        assert not out.get("refused")
+        if kind == "temporal":
+            want_out, _, want = ref.push(hull, window, window, 1)
+        else:
+            want_out, _, want = ref.push(hull, window, window, 1, 4, 2, 2)
+        same = out["stats"] == want and np.array_equal(m.occ(), want_out) and len(m.ring()) == len(ref.ring) and \
+            all(np.array_equal(a, b) for a, b in zip(m.ring(), ref.ring))
+        if fault is None:
+            assert same, (k, kind, out["stats"], want)
+            assert m.aligned == (kind == "temporal_motion") and out["stats"]["frames"] == (1 if fresh else 2)
+            assert ("temporal_field" in m.products) == (kind == "temporal_motion")
+            if kind == "temporal_motion" and fresh:              # the first push of a ring has a field of no rows
+                assert len(out["rows"]["block"]) == 0 and m.products["temporal_field"] == cm.Model.field_bytes(cm.tmn.no_rows(m.grid, 4, 2), 4, 2, 2)
+        differs |= not same
+    assert differs == (fault is not None)
+
+
+def test_literal_twin_of_the_aligned_vote(traces_e):
+    """temporal_motion_np.Literal, voxel by voxel, beside the model on one chain of the smallest grid: every accepted vote whose
+    search range is at most 2, cut short behind the third; a window change starts the literal ring over as it does the model's."""
+    small = min(cm.scene(g).grid[0] * cm.scene(g).grid[1] * cm.scene(g).grid[2] for g in {cm.draw_chain(s)[0].grid for s in cm.SEEDS_E})
+    best = None
+    for seed in cm.SEEDS_E:
+        sc, ops = cm.draw_chain(seed)
+        if sc.grid[0] * sc.grid[1] * sc.grid[2] != small:
+            continue
+        votes = [r for r in traces_e[seed] if r["op"] == "temporal_motion" and not r["refused"]]
+        head = []
+        for r in votes:
+            if r["params"]["search"] > 2 or len(head) == 3:
+                break
+            head.append(r)
+        if len(head) >= 2 and any(r["stats"]["frames"] >= 2 and r["stats"]["listed"] > 0 for r in head) and (best is None or len(head) > len(best[1])):
+            best = (seed, head)
+    assert best is not None, "no chain of the smallest grid starts with two votes of a search range of at most 2"
+    seed, head = best
+    sc, ops = cm.draw_chain(seed)
+    m = cm.model_of(seed)
+    lit, done = None, 0
+    for step, op in enumerate(ops[:head[-1]["step"] + 1]):
+        hull = None if m.records is None else m.occ()
+        voted = op["op"] == "temporal_motion" and "temporal" not in m.products
+        if op["op"] == "temporal_reset":
+            lit = None
+        out = m.apply(op)
+        if not voted:
+            continue
+        if lit is None or lit.window != op["window"]:
+            lit = cm.tmn.Literal(op["window"])
+        want_out, counts, st = lit.push(hull, op["keep"], op["keep_off"], op["block"], op["apron"], op["search"])
+        assert np.array_equal(m.occ(), want_out), (seed, step)
+        for k, v in st.items():
+            assert out["stats"][k] == v, (seed, step, k)
+        for key in cm.MOTION_ROW_KEYS:
+            assert np.array_equal(np.asarray(out["rows"][key]).reshape(-1), np.asarray(lit.rows[key]).reshape(-1)), (seed, step, key)
+        assert np.array_equal(out["votes"], counts.reshape(-1)[m.idx]), (seed, step)
+        assert all(np.array_equal(a, b) for a, b in zip(m.ring(), lit.ring)) and len(m.ring()) == len(lit.ring)
+        done += 1
+    assert done == len(head)
+
+
+def test_literal_twin_of_the_motion_pyramid(traces_e):
+    """motion_pyramid_np.match_pyramid_literal against match_pyramid on a window of the two hulls at three pyramids of the
+    chains, with the operation's own parameters where the search range is at most 2 and (4, 2, 2) otherwise."""
+    found = sorted((r["before"], seed, r["step"]) for seed, rows in traces_e.items() for r in rows
+                   if r["op"] == "motion" and r["params"]["levels"] and r["stats"]["listed"] > 0)
+    assert len(found) >= 3
+    for _, seed, step in found[:3]:
+        m = cm.replay(seed, upto=step)
+        op = cm.draw_chain(seed)[1][step]
+        b, ap, s = (op["block"], op["apron"], op["search"]) if op["search"] <= 2 else (4, 2, 2)
+        L, refine = op["levels"], min(op["refine"], s)
+        a, bo = _window(m, op["reg"], (2 * b, 2 * b, 2 * b))
+        grid = (a.shape[1], a.shape[2], a.shape[0])
+        want, got = cm.mp.match_pyramid(a, bo, grid, b, ap, s, L, refine), cm.mp.match_pyramid_literal(a, bo, grid, b, ap, s, L, refine)
+        assert want["reach"] == got["reach"] and want["evaluated"] == got["evaluated"] and len(want["rows"][0]["block"]) > 0
+        for l in range(L + 1):
+            for key in cm.MOTION_ROW_KEYS:
+                assert np.array_equal(want["rows"][l][key], got["rows"][l][key]), (seed, step, l, key)

@@ -19,6 +19,14 @@ pixel of every view (chain_model.HW_D, 24 x 32: 3 x 4 tiles of the kernels) of t
 name; a view index of n_views is refused too) and of the last render, which like them outlives the result it was made of.  A call
 that the model refuses must raise with the model's words, and the whole comparison then holds as before: nothing moved.
 
+test_chain_e walks family E (chain_model.SEEDS_E: 12 chains of 12 operations, family C's kinds, the aligned vote and
+temporal_reset, every motion estimate with 0 to 3 coarser levels).  After every operation it compares, besides what test_chain_c
+checks, every level of a current motion field (rows, scalars, the level words of A and B; the level behind the coarsest is
+refused; every level's fetch refuses once the field is stale), the votes, the vote's own field (chain_model.REFUSAL_E) and the
+ring.  "One push per result" is drawn: the call must raise with the model's words, and nothing may have moved.
+
+Family B (the plain vote, the measurements, the skeleton, the shell) is not walked here: DESIGN.md, "The abort at exit".
+
 A failure names (seed, step, operation, parameters); chain_model.replay(seed, upto=step) rebuilds the model in front of it."""
 import contextlib
 import ctypes
@@ -309,7 +317,7 @@ def _registers_equal_model(e, m):
         got, f = e.fetch_motion(), m.field
         for key in cm.MOTION_ROW_KEYS:
             assert np.array_equal(np.asarray(got[key]).astype(np.int64), np.asarray(f["rows"][key]).astype(np.int64)), ("motion field", key)
-        assert sorted(got) == sorted(cm.MOTION_ROW_KEYS + ("grid", "edge", "apron", "search"))
+        assert sorted(got) == sorted(cm.MOTION_ROW_KEYS + ("grid", "edge", "apron", "search") + (("levels", "refine", "reach") if f.get("levels") else ()))
         assert (got["grid"], got["edge"], got["apron"], got["search"]) == (m.grid, f["b"], f["a"], f["s"]), "the field's scalars"
     else:
         for call in (e.fetch_motion, e.paint_motion):
@@ -392,6 +400,23 @@ def test_chain_c(eng, cams, masks, frames, seed):
             _result_equals_model(e, m)
             _registers_equal_model(e, m)
     _end_of_chain(e, sc, m, seed, after=lambda: _registers_equal_model(e, m))
+
+
+# ---- the vote's state, for family E ---------------------------------------------------------------------------------------------------
+def _refuses_b(name):
+    from voxcarve._lib import VoxcarveError
+    return pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + cm.REFUSAL_B[name])
+
+
+def _ring_equals_model(e, m):
+    """Every hull of the vote's ring, newest first, and the refusal of the age behind the oldest."""
+    from voxcarve._lib import VoxcarveError
+    ring = m.ring()                              # (newest last; the aligned vote's ring holds the aligned hulls)
+    held = len(ring)
+    for age in range(held):
+        assert np.array_equal(e.temporal_history(age), motion_np.words(ring[held - 1 - age])), ("the ring's hull of age", age)
+    with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*the ring holds %d hulls" % held):
+        e.temporal_history(held)
 
 
 # ---- family D: the passes over a render's images -------------------------------------------------------------------------------------
@@ -533,3 +558,109 @@ def test_chain_d(eng, cams, masks, frames, seed):
         _told_of_the_probe(e, m)
         _pictures_equal_model(e, m)
     _end_of_chain(e, sc, m, seed, after=after, run=_run_d)
+
+
+# ---- family E: the aligned vote and the motion pyramid ------------------------------------------------------------------------------------
+def _temporal_motion(e, op, out):
+    call = lambda: e.temporal_filter(op["window"], op["keep"], op["keep_off"], motion=(op["block"], op["apron"], op["search"]))
+    if out.get("refused"):
+        with _refuses(out):
+            call()
+        return
+    st = call()
+    assert st.pop("temporal_ms") > 0
+    assert sorted(st) == sorted(out["stats"])                    # (every field of the stats but the time)
+    _same(st, out["stats"], sorted(st))
+
+
+def _motion_e(e, op, out):
+    if not op["levels"]:
+        return _motion(e, op, out)
+    st = _timed(e.hull_motion(op["reg"], op["block"], op["apron"], op["search"], levels=op["levels"], refine=op["refine"]), "motion_ms")
+    assert st == out["stats"], (st, out["stats"])
+
+
+def _run_e(e, sc, step, op, out):
+    kind = op["op"]
+    if kind == "temporal_motion":
+        _temporal_motion(e, op, out)
+    elif kind == "temporal_reset":
+        e.temporal_reset()
+    elif kind == "motion":
+        _motion_e(e, op, out)
+    else:
+        _run(e, sc, step, op, out)
+
+
+def _same_rows(got, want, what):
+    for key in cm.MOTION_ROW_KEYS:
+        assert np.array_equal(np.asarray(got[key]).astype(np.int64).reshape(-1), np.asarray(want[key]).astype(np.int64).reshape(-1)), (what, key)
+
+
+def _votes_and_levels_equal_model(e, m):
+    """Every level of a current motion field (rows, scalars, the level words of A and B; the level behind the coarsest one is
+    refused), or the refusal of every level's fetches; the votes, the aligned vote's field (the model's rows and scalars, or the
+    refusal by name) and the ring."""
+    from voxcarve._lib import VoxcarveError
+    import motion_pyramid_np as mp
+    if "motion" in m.products:
+        f = m.field
+        L = f["levels"]
+        for l in range(L + 1):
+            rows = e.fetch_motion_level(l)
+            _same_rows(rows, f["res"]["rows"][l] if L else f["rows"], "level %d" % l)
+            assert rows["grid"] == mp.level_grid(m.grid, l) and (rows["edge"], rows["apron"], rows["search"]) == (f["b"], f["a"], f["s"]), l
+            assert (rows["levels"], rows["reach"]) == (L, f["reach"]) and (not L or rows["refine"] == f["refine"]), l
+            a, b = (f["res"]["a"][l], f["res"]["b"][l]) if L else (m.occ(), m.registers[f["reg"]]["occ"])
+            assert np.array_equal(e.fetch_motion_occupancy(l, 0), motion_np.words(a)), ("the words of A, level", l)
+            assert np.array_equal(e.fetch_motion_occupancy(l, 1), motion_np.words(b)), ("the words of B, level", l)
+        for call in (lambda: e.fetch_motion_level(L + 1), lambda: e.fetch_motion_occupancy(L + 1, 0)):
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*the field has the levels 0..%d" % L):
+                call()
+    else:
+        for call in (lambda: e.fetch_motion_level(0), lambda: e.fetch_motion_level(1), lambda: e.fetch_motion_occupancy(0, 0),
+                     lambda: e.fetch_motion_occupancy(1, 1)):
+            with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + cm.REFUSAL_C["motion"]):
+                call()
+    if "temporal" in m.products:
+        votes, added = e.fetch_temporal()
+        assert votes.tobytes() + added.tobytes() == m.products["temporal"], "product temporal differs from the model"
+    else:
+        with _refuses_b("temporal"):
+            e.fetch_temporal()
+    if "temporal_field" in m.products:
+        got = e.fetch_temporal_motion()
+        _same_rows(got, m.avote.rows, "the vote's field")
+        assert (got["grid"], got["edge"], got["apron"], got["search"]) == ((m.grid,) + m.vote_params), "the scalars of the vote's field"
+    else:
+        with pytest.raises(VoxcarveError, match="VC_ERR_ARG.*" + cm.REFUSAL_E["temporal_field"]):
+            e.fetch_temporal_motion()
+    _ring_equals_model(e, m)
+
+
+@pytest.mark.parametrize("seed", cm.SEEDS_E)
+def test_chain_e(eng, cams, masks, frames, seed):
+    """Family E: test_chain_c's loop with the aligned vote (vc_hull_temporal_motion) and the motion pyramid
+    (vc_hull_motion_pyramid) among the operations.  After every operation also every level of the motion field, the votes, the
+    vote's field and the ring; a refusal the model draws must raise with the model's words, and the whole comparison then holds
+    as before.  The engine is the one the chains before have used: set_cameras empties the registers and the ring."""
+    e = eng
+    sc, ops = cm.draw_chain(seed)
+    _setup(e, sc, cams, masks, frames)
+    m = cm.model_of(seed)
+    with _at(seed, "start", {"op": "nothing"}):
+        assert not m.ring() and not set(m.products)
+        _registers_equal_model(e, m)
+        _votes_and_levels_equal_model(e, m)
+    for step, op in enumerate(ops):
+        out = m.apply(op)
+        with _at(seed, step, op):
+            _run_e(e, sc, step, op, out)
+            _result_equals_model(e, m)
+            _registers_equal_model(e, m)
+            _votes_and_levels_equal_model(e, m)
+
+    def after():
+        _registers_equal_model(e, m)
+        _votes_and_levels_equal_model(e, m)
+    _end_of_chain(e, sc, m, seed, after=after, run=_run_e)

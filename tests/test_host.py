@@ -159,3 +159,67 @@ def test_drop_in_default_source_fails_early_and_by_name():
     with pytest.raises(VoxcarveError, match=r"configure\(frame_source"):
         assignment.set_voxel_positions(8, 4, 8)
     assert not assignment.initialized
+
+
+_EXIT_CHILD = r'''
+import os, sys
+sys.path.insert(0, sys.argv[1])
+import voxcarve
+from voxcarve import _lib, background_subtraction as bs
+from voxcarve.engine import CarveEngine
+
+
+class FakeLibrary:
+    """Records every call, with whether the interpreter was finalising, at once on stdout: nothing is left to a print at exit."""
+
+    def __getattr__(self, name, write=os.write, finalizing=sys.is_finalizing):
+        def call(*args):
+            write(1, ("%s %d\n" % (name, finalizing())).encode())
+            return 0
+        return call
+
+
+def engine():
+    e = CarveEngine.__new__(CarveEngine)
+    e._L, e._ctx, e._pin_bytes = FakeLibrary(), _lib.c_ctx(1), 0
+    return e
+
+
+def subtractor(cls, eng, handle):
+    s = cls.__new__(cls)
+    s._eng, s._model = eng, handle
+    return s
+
+
+eng = engine()
+mog, mog2 = subtractor(bs.BackgroundSubtractorMOG, eng, 1), subtractor(bs.BackgroundSubtractorMOG2, eng, 2)
+bs._engine = eng                                 # (the module's global engine, as _default_engine leaves it)
+if sys.argv[2] == "close":
+    for x in (mog, mog2, eng):
+        x.close()
+        x.close()
+elif sys.argv[2] == "del":
+    bs._engine = None
+    del mog, mog2
+    del eng
+os.write(1, b"end of main\n")
+'''
+
+
+@pytest.mark.parametrize("how", ["alive", "close", "del"])
+def test_no_destroy_call_from_a_finalising_interpreter(how):
+    """CarveEngine and the two background subtractors around a library object that records calls, in a fresh interpreter.  Left
+    alive in module globals to a normal exit, none of them calls a destroy function: their __del__ runs in a finalising interpreter,
+    where the context's teardown (HIP) is left to the process's exit.  Deleted or closed before the exit, each reaches its destroy
+    call exactly once; close() twice is one call."""
+    import subprocess
+    import sys
+    run = subprocess.run([sys.executable, "-c", _EXIT_CHILD, fx.ROOT, how], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stderr
+    lines = run.stdout.split("\n")[:-1]
+    assert "end of main" in lines, run.stdout
+    calls = [tuple(l.split()) for l in lines if l != "end of main"]
+    late = [c for c in calls if c[1] != "0"] + [tuple(l.split()) for l in lines[lines.index("end of main") + 1:]]
+    assert not late, "calls from a finalising interpreter, or behind the end of the program: %r" % (late,)
+    want = [] if how == "alive" else ["vc_mog_destroy", "vc_mog2_destroy", "vc_destroy"]
+    assert [c[0] for c in calls] == want, calls

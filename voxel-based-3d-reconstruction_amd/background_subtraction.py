@@ -24,6 +24,8 @@ The cv2 stage needs cv2 (as the reference does), and so does decoding the traini
 Parity of the GPU stages with cv2 is unpinned: the contour stage is held to a literal restatement of the published border
 following, fillPoly and drawContours (tests/contour_literal.py), the others to oracle/foreground_np.py, oracle/mog_np.py and
 tests/mog2_np.py."""
+import sys
+
 import numpy as np
 
 from ._lib import VoxcarveError
@@ -64,6 +66,8 @@ class BackgroundSubtractorMOG:
             self._model = None
 
     def __del__(self):
+        if sys.is_finalizing():                  # as CarveEngine.__del__: no HIP call from a finalising interpreter; the process's
+            return                               # exit takes the model with the context
         try:
             self.close()
         except Exception:
@@ -121,6 +125,8 @@ class BackgroundSubtractorMOG2:
             self._model = None
 
     def __del__(self):
+        if sys.is_finalizing():                  # as CarveEngine.__del__: no HIP call from a finalising interpreter; the process's
+            return                               # exit takes the model with the context
         try:
             self.close()
         except Exception:
